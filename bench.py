@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- fast_aggregate_verify/s (128 pubkeys, 32-byte message) on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run builds the inputs, runs W warm-up steps and K timed steps, checks the accept bitmap against the expectation and prints
+the headline line (ms_per_step = one timed step). --dump-outputs DIR writes what the last timed step returned (dump_outputs).
+--full adds every other figure: per-kernel phase times, roofline / valu_issue, the other key forms, other configs and sizes, the
+multi-device and sharded legs, the collective timed alone and the CPU baselines.
 
 A "step" is one pass of the hot path (mbls_fast_aggregate_verify_batch_device: aggregate -> sig -> hash -> Miller ->
 final exponentiation -> bitmap) over one batch of 2^16 synthetic (signature, message, 128-pubkey set) items per GPU
@@ -800,11 +805,13 @@ def stub_rank(args, rank, world):
         if world > 1:
             shard.all_gather_bitmap(bm, world, out=d_all)
     elapsed = timed_steps(step, args.steps, args.warmup, world, lambda: None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, bm, n, d_all if world > 1 else None, world)
     per_rank = gather_per_rank(LAST_OWN_ELAPSED[0] / args.steps * 1e3, world)
-    coll = collective_figure(lambda: shard.all_gather_bitmap(bm, world, out=d_all), world, lambda: None, reps=5)
+    coll = collective_figure(lambda: shard.all_gather_bitmap(bm, world, out=d_all), world, lambda: None, reps=5) if args.full else None
     # configs[4] as the real path times it at 8 ranks (config5_leg): the rank's own shard, then the gather -- here with the stand-in verifier
     shard_leg = None
-    if world == 8:
+    if args.full and world == 8:
         e5 = timed_steps(step, 2, 0, world, lambda: None)
         shard_leg = {"workload": "configs[4] (stub): %d items per rank over 8 ranks + the bitmap gather" % n, "value": n * world * 2 / e5, "unit": "fast_aggregate_verify/s",
                      "ms_per_step": e5 / 2 * 1e3, "steps": 2,
@@ -818,8 +825,8 @@ def stub_rank(args, rank, world):
     if rank == 0:
         emit_result(json.dumps({"metric": "fast_aggregate_verify/sec (128 pubkeys, 32B msg)", "stub": True, "value": n * world * args.steps / elapsed,
                           "unit": "fast_aggregate_verify/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-                          "ms_per_step_per_rank": per_rank, "bitmap_matches_expectation": ok, "higher_is_better": True, "scaling": "weak",
-                          "collective": coll, "configs4_shard_leg": shard_leg}))
+                          "ms_per_step_per_rank": per_rank, "bitmap_matches_expectation": ok, "higher_is_better": True, "scaling": "weak", "full": args.full,
+                          **({"collective": coll, "configs4_shard_leg": shard_leg} if args.full else {})}))
     if world > 1:
         dist.barrier(); dist.destroy_process_group()
     return 0 if ok else 3
@@ -841,6 +848,29 @@ def protect_stdout():
 def emit_result(line):
     sys.stdout.flush()
     os.write(_RESULT_FD if _RESULT_FD is not None else 1, (line + "\n").encode())
+
+
+DUMP_BYTES_MAX = 60 << 20        # under 64 MB with room for the .npy headers
+
+
+def dump_outputs(out_dir, d_res, d_bm, n, d_all=None, world=1):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, as float32 .npy files -- `results` (one 0/1 verdict per item),
+    `bitmap` (the packed accept bitmap, unpacked to one 0/1 per item) and, with more than one rank, `bitmap_gathered` (every rank's bitmap after the
+    all-gather, in rank order). Beyond DUMP_BYTES_MAX in all, every array is cut to a fixed, seeded sample of its items, whose indices go to
+    `<name>_index.npy` (float64)."""
+    arrays = {"results": d_res.cpu().to(torch.float32).numpy(), "bitmap": shard.unpack_bits(d_bm.cpu(), n).to(torch.float32).numpy()}
+    if d_all is not None:
+        words = d_bm.numel()
+        arrays["bitmap_gathered"] = torch.cat([shard.unpack_bits(d_all[r * words:(r + 1) * words].cpu(), n) for r in range(world)]).to(torch.float32).numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES_MAX:
+            keep = max(1, a.size * DUMP_BYTES_MAX // (3 * total))        # 4 + 8 bytes per kept item (value + index): all arrays within the limit
+            idx = np.sort(np.random.default_rng(SEED).choice(a.size, keep, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def git_head():
@@ -910,8 +940,13 @@ def main():
     ap.add_argument("--pk-format", choices=["uncompressed", "compressed", "indexed"], default="uncompressed",
                     help="how the timed path receives the keys: 96-byte decoded form (default: what the reference's fast_aggregate_verify takes), "
                          "48-byte wire form, or indices into a resident key table")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the compressed-key and indexed-key legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also every figure beside the headline: per-kernel phase times, roofline and VALU issue, the other key forms, the other configs and "
+                         "sizes, the multi-device legs, the sharded verify_multiple leg, configs[4] at 8 ranks, the collective timed alone and the CPU "
+                         "baselines (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the other key forms, the other configs and the multi-device legs")
     ap.add_argument("--multi-leg", type=int, default=0, help=argparse.SUPPRESS)      # internal: run ONLY the in-process multi-device leg over this many devices, print it
     ap.add_argument("--stub", action="store_true", help="CPU test of the multi-rank plumbing only: gloo backend and a stand-in verifier; the line it prints is "
                                                          "labelled a stub and is not a measurement")
@@ -954,7 +989,10 @@ def main():
     sptr = C.c_void_p(stream.cuda_stream)
 
     t_in = time.perf_counter()
-    d_sigs, d_msgs, d_pks, expect, d_idx, table = build_inputs(ctx, dev, n, k, N.PK_UNCOMPRESSED, rank, return_indices=True)
+    # the key table (the same keys as indices) only where a leg reads it: the indexed form, and under --full its variant and the multi-device legs
+    inp = build_inputs(ctx, dev, n, k, N.PK_UNCOMPRESSED, rank, return_indices=args.full or args.pk_format == "indexed")
+    d_sigs, d_msgs, d_pks, expect = inp[:4]
+    d_idx, table = inp[4:] if len(inp) > 4 else (None, None)
     t_in = time.perf_counter() - t_in
     ctx.reserve(n)
 
@@ -992,7 +1030,7 @@ def main():
 
     own_ms = {}
 
-    def run_leg(kind, steps, warmup):
+    def run_leg(kind, steps, warmup, phases=True, dump_dir=None):
         d_res = torch.zeros(n, dtype=torch.uint8, device=dev)
         d_bm = torch.zeros(words, dtype=torch.int64, device=dev)
         d_all = torch.zeros(words * world, dtype=torch.int64, device=dev) if world > 1 else None
@@ -1004,10 +1042,14 @@ def main():
         lib.mbls_enable_phase_timing(ctx.handle, 0)
         elapsed = timed_steps(step, steps, warmup, world, torch.cuda.synchronize)
         own_ms[kind] = LAST_OWN_ELAPSED[0] / steps * 1e3
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, d_res, d_bm, n, d_all, world)
         ok = check_bitmap(d_res, d_bm, expect)
         if world > 1:
             ok = ok and check_gathered(d_all, world, words, d_bm, rank)
         ok = reduce_all_ok(ok, world)
+        if not phases:
+            return elapsed, ok, None
         # per-kernel timing with HIP events on the launch stream (separate, untimed pass): 2 discarded warm-ups (the events make every
         # call synchronise, which lets the clocks settle differently from the free-running timed loop), then the median of 5
         lib.mbls_enable_phase_timing(ctx.handle, 1)
@@ -1022,9 +1064,9 @@ def main():
         lib.mbls_enable_phase_timing(ctx.handle, 0)
         return elapsed, ok, {nm: float(v) for nm, v in zip(N.PHASE_NAMES, phase)}
 
-    elapsed, ok, phase_ms = run_leg(args.pk_format, args.steps, args.warmup)
+    elapsed, ok, phase_ms = run_leg(args.pk_format, args.steps, args.warmup, phases=args.full, dump_dir=args.dump_outputs)
     variants = {}
-    if not args.no_variants and world == 1:
+    if args.full and not args.no_variants and world == 1:
         for kind in ("compressed", "indexed", "uncompressed"):
             if kind == args.pk_format:
                 continue
@@ -1037,16 +1079,18 @@ def main():
 
     per_rank_ms = gather_per_rank(own_ms[args.pk_format], world)
     coll = None
-    if world > 1:
+    if args.full and world > 1:
         _bm = torch.zeros(words, dtype=torch.int64, device=dev); _all = torch.zeros(words * world, dtype=torch.int64, device=dev)
         coll = collective_figure(lambda: shard.all_gather_bitmap(_bm, world, out=_all), world, torch.cuda.synchronize)
-    # one step = the kernels of one in-order stream (+ the gather): their event-timed sum against this rank's own step time, on every rank
-    phase_sum_own = sum(phase_ms.values())
-    phase_gap = abs(phase_sum_own - own_ms[args.pk_format]) / own_ms[args.pk_format]
-    worst_gap = reduce_max(phase_gap, world)
+    worst_gap = None
+    if args.full:
+        # one step = the kernels of one in-order stream (+ the gather): their event-timed sum against this rank's own step time, on every rank
+        phase_sum_own = sum(phase_ms.values())
+        phase_gap = abs(phase_sum_own - own_ms[args.pk_format]) / own_ms[args.pk_format]
+        worst_gap = reduce_max(phase_gap, world)
     other = {}
     multi_legs = None
-    if not args.no_variants and world == 1:
+    if args.full and not args.no_variants and world == 1:
         other = other_configs(ctx, lib, dev, sptr)
         other["aggregate_verify_batch 2^14 items x 4 (message, key) pairs"] = aggregate_verify_leg(ctx, lib, dev, sptr)
         other["operations either side of the path (2^16 each)"] = keyops_figures(ctx, lib, dev)
@@ -1071,26 +1115,19 @@ def main():
             else:
                 break                                      # a leg that could not run (time limit, crash): the larger ones are not tried -- the line must not wait for them
     vm_leg = None
-    if n == (1 << 16) and not args.no_variants:
+    if args.full and n == (1 << 16) and not args.no_variants:
         vm_leg = sharded_verify_multiple_leg(ctx, lib, dev, sptr, rank, world, k)
         ok = ok and vm_leg["correct"]
     shard_leg = None
-    if world == 8 and n == (1 << 16):
+    if args.full and world == 8 and n == (1 << 16):
         # BASELINE configs[4] as it is named: 2^20 items over 8 GPUs = 2^17 per rank (the default legs above are configs[2] per GPU)
         shard_leg = config5_leg(ctx, lib, dev, sptr, rank, world, k)
 
     if rank == 0:
-        pkb = {"compressed": 48 * k, "uncompressed": 96 * k, "indexed": 4 * k}[args.pk_format]
-        bytes_per_item = pkb + 96 + 32 + 1          # algorithmic bytes in + 1 out
         ms_per_step = elapsed / args.steps * 1e3
         value = n * world * args.steps / elapsed
-        dom = max((nm for nm in phase_ms), key=lambda nm: phase_ms[nm])
-        achieved = n * bytes_per_item / (phase_ms[dom] * 1e-3) / 1e9          # algorithmic GB/s through the dominant kernel
         cfg_name = ("configs[2]" if world == 1 else "configs[2] on every GPU (weak scaling: %d x 2^16 items)" % world) if n == (1 << 16) else (
             "the configs[4] shard (2^20 items / 8 GPUs)" if n == (1 << 17) else "custom size")
-        phase_sum = sum(phase_ms.values())
-        phase_pass = "consistent" if worst_gap <= 0.02 + (0.02 if world > 1 else 0.0) else "inconsistent"
-        traffic, traffic_note = measured_traffic(dom)
         out = {
             "metric": "fast_aggregate_verify/sec (128 pubkeys, 32B msg)", "value": value, "unit": "fast_aggregate_verify/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "ms_per_step_per_rank": per_rank_ms, "higher_is_better": True,
@@ -1101,37 +1138,47 @@ def main():
                        "negatives": "every 16th item corrupted (msg bit / wrong key / sig not in G2 / infinity sig / apk = infinity)",
                        "parallelism": "items sharded over %d GPU(s), RCCL all-gather of the accept bitmap" % world},
             "bitmap_matches_expectation": ok,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_note, "kernel": "k_" + dom, "kernel_ms": phase_ms[dom],
-                         "algorithmic_bytes_per_item": bytes_per_item,
-                         "note": "VALU-issue-bound path (see valu_issue): the HBM fraction is reported as measured; traffic = HBM bytes per launch of the dominant "
-                                 "kernel from the PMC counters (separate passes, never inside a timed run), attached only when collected on this very build"},
-            "traffic_from_profile": from_profile("hbm_traffic.json", dom),
-            "valu_issue": valu_issue_figure(lib, ctx, phase_ms, n, {"uncompressed": "k_aggregate", "indexed": "k_aggregate_indexed"}.get(args.pk_format) if k == 128 else None),
-            "phase_ms": phase_ms,
-            "phase_notes": "sig = signature decoding: the subgroup test psi(sig) = [x] sig is read off the Miller loop's running point (k_sig_verdict, counted under miller)",
-            "phase_pass": {"verdict": phase_pass, "sum_phase_ms": phase_sum, "ms_per_step": ms_per_step, "worst_rank_gap": worst_gap,
-                           "method": "median of %d event-timed calls after 2 discarded ones; 'consistent' = on EVERY rank the kernels of its in-order stream sum to that rank's own "
-                                     "timed step within 2 %% (4 %% with the bitmap gather inside the step, world > 1); worst_rank_gap = the largest relative gap" % PHASE_REPS},
-            "variants": variants,
-            "other_configs": other,
-            "multi_handle_leg": multi_legs,
-            # true only when every leg over the visible devices RAN and matched; false when one ran and disagreed (exit code 3) or produced no result at all
-            "multi_legs_ok": (all(l.get("ran") and l.get("results_match") for l in multi_legs) if multi_legs is not None else None),
-            "configs4_shard_leg": shard_leg,
-            "collective": coll,
-            "sharded_verify_multiple_leg": vm_leg,
-            "input_build_s": t_in,
-            "head": git_head(), "library_source_hash": library_source_hash(),
+            "full": args.full,
         }
+        if args.full:
+            pkb = {"compressed": 48 * k, "uncompressed": 96 * k, "indexed": 4 * k}[args.pk_format]
+            bytes_per_item = pkb + 96 + 32 + 1          # algorithmic bytes in + 1 out
+            dom = max((nm for nm in phase_ms), key=lambda nm: phase_ms[nm])
+            achieved = n * bytes_per_item / (phase_ms[dom] * 1e-3) / 1e9          # algorithmic GB/s through the dominant kernel
+            phase_sum = sum(phase_ms.values())
+            phase_pass = "consistent" if worst_gap <= 0.02 + (0.02 if world > 1 else 0.0) else "inconsistent"
+            traffic, traffic_note = measured_traffic(dom)
+            out.update({
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                             "traffic": traffic, "traffic_source": traffic_note, "kernel": "k_" + dom, "kernel_ms": phase_ms[dom],
+                             "algorithmic_bytes_per_item": bytes_per_item,
+                             "note": "VALU-issue-bound path (see valu_issue): the HBM fraction is reported as measured; traffic = HBM bytes per launch of the dominant "
+                                     "kernel from the PMC counters (separate passes, never inside a timed run), attached only when collected on this very build"},
+                "traffic_from_profile": from_profile("hbm_traffic.json", dom),
+                "valu_issue": valu_issue_figure(lib, ctx, phase_ms, n, {"uncompressed": "k_aggregate", "indexed": "k_aggregate_indexed"}.get(args.pk_format) if k == 128 else None),
+                "phase_ms": phase_ms,
+                "phase_notes": "sig = signature decoding: the subgroup test psi(sig) = [x] sig is read off the Miller loop's running point (k_sig_verdict, counted under miller)",
+                "phase_pass": {"verdict": phase_pass, "sum_phase_ms": phase_sum, "ms_per_step": ms_per_step, "worst_rank_gap": worst_gap,
+                               "method": "median of %d event-timed calls after 2 discarded ones; 'consistent' = on EVERY rank the kernels of its in-order stream sum to that rank's own "
+                                         "timed step within 2 %% (4 %% with the bitmap gather inside the step, world > 1); worst_rank_gap = the largest relative gap" % PHASE_REPS},
+                "variants": variants,
+                "other_configs": other,
+                "multi_handle_leg": multi_legs,
+                # true only when every leg over the visible devices RAN and matched; false when one ran and disagreed (exit code 3) or produced no result at all
+                "multi_legs_ok": (all(l.get("ran") and l.get("results_match") for l in multi_legs) if multi_legs is not None else None),
+                "configs4_shard_leg": shard_leg,
+                "collective": coll,
+                "sharded_verify_multiple_leg": vm_leg,
+            })
+        out.update({"input_build_s": t_in, "head": git_head(), "library_source_hash": library_source_hash()})
         if share_gpu:
             out["share_gpu_test"] = "all %d ranks on ONE device, gathers through gloo: a functional test of the multi-rank path, not a scaling measurement" % world
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             allc, one, cfg1 = cpu_baseline(d_sigs, d_msgs, d_pks, expect, k, N.PK_UNCOMPRESSED)
             out["cpu_baseline"] = allc
             out["cpu_baseline_1t"] = one
             out["cpu_config1"] = cfg1
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = None
         emit_result(json.dumps(out))
     if world > 1:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Instruction-cache counters of the bench's kernels (dev probe, run on the GPU box through gpurun): two --pmc passes, nothing else in them.
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/icache_pmc; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-variants --steps 2 --warmup 1"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-variants --steps 2 --warmup 1"
 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE --output-format csv -d $OUT/a -o a -- $B > /dev/null 2> $OUT/a.err
 rocprofv3 --pmc SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT/b -o b -- $B > /dev/null 2> $OUT/b.err
 cd $ROOT

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cp milagro_bls_amd/libmbls_hip.so.srchash $OUT/source_hash.txt      # the build every counter below belongs to
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-variants"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-variants"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o $TAG -- $B --steps 5 --warmup 1 > $OUT/stats_bench.json 2> $OUT/stats.err
 for CFG in 2 4 lat mid; do
@@ -24,8 +24,8 @@ cd $ROOT
 # roofline.traffic only when the hash matches the library it loaded. (The same collection is repeated in the container on the merged files, for the commit.)
 echo '{}' > $OUT/bench_line.json
 python3 scripts/collect_profiles.py $TAG $OUT/stats $OUT/fetch $OUT/write $OUT/sq $OUT/bench_line.json > $OUT/collect_on_box.log 2>&1
-python3 bench.py --steps 10 --warmup 2 > $OUT/bench_line.json 2> $OUT/bench.err
-python3 bench.py --items 131072 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_line_131072.json 2>> $OUT/bench.err
+python3 bench.py --full --steps 10 --warmup 2 > $OUT/bench_line.json 2> $OUT/bench.err
+python3 bench.py --full --items 131072 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_line_131072.json 2>> $OUT/bench.err
 python3 scripts/latency.py $OUT/latency.json > $OUT/latency.log 2>&1
 python3 scripts/time_keyops.py > $OUT/keyops.log 2>&1; cp gpurun_out/keyops.json $OUT/keyops.json
 bash scripts/kstats.sh > $OUT/kstats.txt 2>&1

@@ -110,6 +110,41 @@ def test_gpus_flag_without_a_launcher_spawns_the_ranks():
     assert d["ms_per_step"] >= 10.0 * 0.9 and d["ms_per_step"] >= max(d["ms_per_step_per_rank"]) * 0.95
 
 
+def test_a_plain_run_times_the_steps_and_dumps_what_they_returned(tmp_path):
+    """a plain line (no --full) carries the headline and none of the figures that take runs of their own; --dump-outputs writes the last timed step's
+    verdicts, its bitmap and (two ranks) the gathered bitmap as float32 arrays, equal to what the stub verifier returned"""
+    import numpy as np
+    out = tmp_path / "dump"
+    rc, lines, err = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--stub", "--dump-outputs", str(out))
+    assert rc == 0, err
+    assert len(lines) == 1
+    d = lines[0]
+    assert d["full"] is False and d["steps"] == 3 and d["ms_per_step"] > 0 and "collective" not in d and "configs4_shard_leg" not in d
+    want = np.ones(1000, dtype=np.float32); want[7::16] = 0
+    for name, expect in (("results", want), ("bitmap", want), ("bitmap_gathered", np.tile(want, 2))):
+        a = np.load(out / (name + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, expect), name
+    assert sorted(p.name for p in out.iterdir()) == ["bitmap.npy", "bitmap_gathered.npy", "results.npy"]
+
+
+def test_dumped_outputs_beyond_the_size_limit_are_a_fixed_seeded_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    from milagro_bls_amd import shard
+    res = torch.ones(1000, dtype=torch.uint8); res[7::16] = 0
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 3000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), res, shard.pack_bits(res), 1000)
+    total = 0
+    for name in ("results", "bitmap"):
+        a, idx = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "a" / (name + "_index.npy"))
+        assert a.dtype == np.float32 and idx.dtype == np.float64 and 0 < len(a) == len(idx) < 1000
+        assert np.array_equal(a, res.numpy()[idx.astype(np.int64)].astype(np.float32))
+        assert np.array_equal(idx, np.load(tmp_path / "b" / (name + "_index.npy")))          # the same sample every run
+        total += a.nbytes + idx.nbytes
+    assert total <= 3000
+
+
 def test_a_failing_rank_or_a_wrong_world_size_is_an_error_exit_not_a_one_gpu_line():
     rc, lines, err = _bench("--gpus", "2", "--steps", "2", "--warmup", "0", "--stub", env={"MBLS_STUB_FAIL_RANK": "1"})
     assert rc == 3 and (not lines or lines[0]["bitmap_matches_expectation"] is False)
@@ -126,7 +161,7 @@ def test_a_failing_rank_or_a_wrong_world_size_is_an_error_exit_not_a_one_gpu_lin
 def test_eight_ranks_print_what_a_scale_record_needs():
     """`bench.py --gpus 8 --stub`: the line a SCALE record is made from at N = 8 -- n_gpus, one ms_per_step per rank, the gathered bitmap checked on every rank, the
     process group's own rank count and the time of the one collective, and configs[4]'s shard leg (timed at 8 ranks only)."""
-    rc, lines, err = _bench("--gpus", "8", "--steps", "2", "--warmup", "1", "--stub")
+    rc, lines, err = _bench("--gpus", "8", "--steps", "2", "--warmup", "1", "--stub", "--full")
     assert rc == 0, err
     assert len(lines) == 1
     d = lines[0]

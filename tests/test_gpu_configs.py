@@ -90,7 +90,7 @@ def test_bench_two_ranks_sharing_the_gpu_real_verifier():
     import sys
     env = dict(os.environ, MBLS_BENCH_SHARE_GPU="1")
     p = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--items", "4096",
-                        "--no-cpu-baseline", "--no-variants"], env=env, capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--no-variants", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -100,7 +100,7 @@ def test_bench_two_ranks_sharing_the_gpu_real_verifier():
     c = d["collective"]
     assert c["group_world_size"] == 2 and c["group_rank_count_matches_n_gpus"] is True and c["all_gather_ms_per_step"] > 0 and c["backend"] == "gloo"
     # one rank, with the in-process multi-device leg (it makes an RCCL communicator): still one line on stdout
-    p = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--items", "4096", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--items", "4096", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -109,6 +109,29 @@ def test_bench_two_ranks_sharing_the_gpu_real_verifier():
     assert d1["multi_legs_ok"] is True and all(l["ran"] and l["results_match"] for l in d1["multi_handle_leg"])
     k = d1["valu_issue"]["kernels"]["k_miller"]
     assert 0 < k["mac_frac"] < 1.0 and 0.5 < k["mac_share_of_valu"] < 0.8 and k["mac_peak"] > 0          # (4 096 items: not the kernels' operating point; the keys are what is checked)
+
+
+def test_plain_bench_run_prints_the_headline_and_dumps_the_timed_outputs(tmp_path):
+    """`bench.py` without --full: the headline line only (no leg beside the timed one), and --dump-outputs holds the verdicts and the bitmap of the last
+    timed step as float32 -- every 16th item (i % 16 == 7) rejected, every other one accepted, as build_inputs constructs them"""
+    import json
+    import os
+    import subprocess
+    import sys
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--items", "4096",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["bitmap_matches_expectation"] is True
+    assert d["unit"] == "fast_aggregate_verify/s" and d["higher_is_better"] is True and d["value"] > 0 and d["dtype"]
+    assert not {"phase_ms", "variants", "other_configs", "valu_issue", "cpu_baseline", "multi_handle_leg"} & set(d)
+    want = np.ones(4096, dtype=np.float32); want[7::16] = 0
+    for name in ("results", "bitmap"):
+        a = np.load(out / (name + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, want), name
 
 
 def test_bench_multi_device_leg_in_a_child_process():
