@@ -203,6 +203,74 @@ int mbls_fast_aggregate_verify_batch_indexed(mbls_ctx* ctx, const mbls_keytable*
                                              const uint64_t* msg_offsets, const uint32_t* key_idx, const uint32_t* offsets, uint64_t n,
                                              uint32_t k, uint8_t* results, uint32_t* status);
 
+/* ---- verification stream: many small calls packed into full rounds ---------------------------------------
+ * The verification entries run at their full rate only when one call carries a whole round (CUs x 4 x 64 items, 65 536 on MI355X). A
+ * stream takes calls of ANY size, hands back a ticket per call, packs the items of many calls back to back into full-round launches of
+ * the entries above, and puts each call's results back where that call asked for them.
+ * STREAM. Belongs to one context; fixed at creation to one mode (MBLS_STREAM_FAST_AGGREGATE_VERIFY: reference src/aggregates.rs:177-215,
+ *   MBLS_STREAM_VERIFY: src/signature.rs:27-40) and one key source: pk_format MBLS_PK_UNCOMPRESSED (96-byte keys), MBLS_PK_COMPRESSED
+ *   (48-byte keys), or t != NULL: indices into a key table of the same context (fast_aggregate_verify mode only).
+ * CALLS. Each call has the shape of a mbls_fast_aggregate_verify_batch[_indexed]_device / mbls_verify_batch_device call: n >= 1 items,
+ *   messages msg_len bytes each or ragged through h_msg_offsets, keys k per item or ragged through h_pk_offsets (verify mode: k = 1 and no
+ *   key offsets), per-item results, optional status words and (device submits) an optional packed bitmap. Results, status words and bitmap
+ *   are bit-identical to what that direct entry returns for the same inputs, every MBLS_ST_* bit included.
+ * OFFSET TABLES LIVE IN HOST MEMORY for both submit entries, even when the bytes they index are on the device: the library cuts rounds
+ *   with them. At submit they are checked as the host entries check theirs (non-decreasing, messages below 2^32 bytes); a bad table
+ *   refuses the call with MBLS_ERR_ARGUMENT and the call gets no ticket.
+ * PACKING. Items are packed densely, in submission order, into rounds of round_items items (default: the context's round,
+ *   mbls_ctx_get_limits), round_keys keys (default 128 x round_items) and round_msg_bytes message bytes (default 64 x round_items); the
+ *   stream's staging buffers are sized from these. A round closes when it is full or when the next item's keys or message would not fit;
+ *   a call may be split across rounds. An item that does not fit an empty round is refused at submit (MBLS_ERR_ARGUMENT, the message
+ *   names the capacity).
+ * LAUNCH. A round always launches when it is full, on mbls_stream_flush, on mbls_stream_wait for a call in it, and on destroy. Policy
+ *   MBLS_STREAM_WORK_CONSERVING (default): also as soon as fewer than `depth` launched rounds are unfinished (default 2: one running, one
+ *   queued behind it) -- a lone call starts at once, and under load the open round fills while the device is busy. MBLS_STREAM_FULL_ROUNDS:
+ *   only full rounds (and flush / wait / destroy): deterministic launches, what tests and throughput runs want.
+ * COMPLETION. Rounds finish in order, so calls complete in ticket order: wait(t) = "every ticket <= t is done". mbls_stream_wait blocks
+ *   without spinning and returns MBLS_OK or the error of a round that held a piece of the call; mbls_stream_query returns MBLS_PENDING
+ *   while the call is not done. An unknown ticket is MBLS_ERR_ARGUMENT. After a device error the stream refuses submits (MBLS_ERR_DEVICE).
+ * LIFETIMES AND ORDERING. A device submit records an event on the caller's `stream` (and zeroes the call's bitmap words there first): the
+ *   gather of the call's round waits for it, so inputs produced on that stream are safe. The caller's input and output buffers -- host
+ *   submits included: their inputs are not copied at submit -- must stay valid and unchanged until the call completes; host results are
+ *   in the caller's buffers when wait / query report the call done. Destroy streams before their context.
+ * KEY TABLE. Read at the size it has when the call's round launches (entries are never removed: an index valid at submit stays valid).
+ * THREADS. Submit, flush, wait, query and stats are thread-safe; any number of threads may share a stream.
+ * ALLOCATION. Everything is allocated at creation: the staging slots (depth + 1), the context's workspace for every round size
+ *   (mbls_plan_workspace_items) and, for 48-byte keys, the staging of decompressed keys (mbls_ctx_reserve_keys) -- no round grows the
+ *   workspace, and the stream never allocates on the device afterwards. */
+#define MBLS_PENDING 102
+enum { MBLS_STREAM_FAST_AGGREGATE_VERIFY = 0, MBLS_STREAM_VERIFY = 1 };
+enum { MBLS_STREAM_WORK_CONSERVING = 0, MBLS_STREAM_FULL_ROUNDS = 1 };
+typedef struct mbls_stream mbls_stream;
+typedef struct mbls_stream_opts { uint64_t round_items, round_keys, round_msg_bytes; uint32_t depth, policy; } mbls_stream_opts;   /* 0 = default */
+/* rounds: launched; full_rounds: of them closed because the next item did not fit; pieces: (call, round) parts; split_calls: calls of
+   more than one piece; gathered_bytes: input bytes staged into the rounds */
+typedef struct mbls_stream_stats { uint64_t calls, items, pieces, rounds, full_rounds, split_calls, gathered_bytes; } mbls_stream_stats;
+/* opts may be NULL (every default); t != NULL makes an index stream (pk_format is then ignored) */
+int mbls_stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, const mbls_stream_opts* opts, mbls_stream** out);
+void mbls_stream_destroy(mbls_stream* s);                /* flushes, waits for every call, frees */
+const char* mbls_stream_last_error(mbls_stream* s);
+/* device buffers, host offset tables; d_pks for byte-key streams, d_key_idx for index streams (the other NULL) */
+int mbls_stream_submit_device(mbls_stream* s, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* h_msg_offsets,
+                              const uint8_t* d_pks, const uint32_t* d_key_idx, const uint32_t* h_pk_offsets, uint64_t n, uint32_t k,
+                              uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream, uint64_t* ticket);
+/* host buffers (read when the call's round launches, written when it completes) */
+int mbls_stream_submit(mbls_stream* s, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* msg_offsets,
+                       const uint8_t* pks, const uint32_t* key_idx, const uint32_t* pk_offsets, uint64_t n, uint32_t k,
+                       uint8_t* results, uint32_t* status, uint64_t* ticket);
+int mbls_stream_flush(mbls_stream* s);
+int mbls_stream_wait(mbls_stream* s, uint64_t ticket);
+int mbls_stream_query(mbls_stream* s, uint64_t ticket);
+int mbls_stream_get_stats(mbls_stream* s, mbls_stream_stats* out);
+/* Pure (no GPU, no context): how a sequence of calls is cut into rounds -- the same incremental rule the stream's launcher runs -- with a
+ * forced launch after call i where flush_after[i] != 0 (opts fully given: no zero defaults). out may be NULL with max_pieces = 0 to count;
+ * *n_pieces receives the count. MBLS_ERR_ARGUMENT for null pointers, zero options, no calls, a call of n = 0, a bad offset table, an item
+ * larger than an empty round, or more pieces than max_pieces. */
+typedef struct mbls_stream_call_shape { uint64_t n; uint32_t k, msg_len; const uint32_t* pk_offsets; const uint64_t* msg_offsets; uint32_t flush_after; } mbls_stream_call_shape;
+typedef struct mbls_stream_piece { uint64_t call, first, items, round, round_first; } mbls_stream_piece;
+int mbls_stream_cut(const mbls_stream_opts* opts, const mbls_stream_call_shape* calls, uint64_t n_calls,
+                    mbls_stream_piece* out, uint64_t max_pieces, uint64_t* n_pieces);
+
 /* ---- several GPUs behind one handle ------------------------------------------------------------------------
  * Items are independent (reference src/aggregates.rs:177-215 keeps no state between calls), so a batch shards embarrassingly:
  * device g of G verifies items [n g / G, n (g + 1) / G). One context and one host thread per listed device; every thread stages its

@@ -19,7 +19,10 @@
 #include <array>
 #include <cstdint>
 #include <cstring>
+#include <deque>
 #include <exception>
+#include <memory>
+#include <mutex>
 #include <random>
 #include <stdexcept>
 #include <string>
@@ -372,4 +375,55 @@ public:
     }
 };
 
+
+// A verification stream on the library's context (include/mbls.h, "verification stream"): calls of any size are packed into full-round
+// launches. submit() takes the same objects as MultiGpu::fast_aggregate_verify and returns a ticket; Ticket::get() waits for the call.
+// The stream keeps every call's staged inputs until the call completes; destroying it completes every pending call.
+class VerifyStream {
+    struct Call { Bytes s, m, p; std::vector<uint64_t> moff; std::vector<uint32_t> koff; std::vector<uint8_t> res; uint64_t ticket = 0; size_t n = 0; };
+    mbls_stream* h_ = nullptr;
+    std::mutex mu_;
+    std::deque<std::shared_ptr<Call>> live_;
+    void check(int rc) const { if (rc != MBLS_OK) throw DeviceError(std::string("mbls_stream: ") + mbls_stream_last_error(h_)); }
+public:
+    class Ticket {
+        VerifyStream* vs_; std::shared_ptr<Call> c_;
+    public:
+        Ticket(VerifyStream* vs, std::shared_ptr<Call> c) : vs_(vs), c_(std::move(c)) {}
+        uint64_t id() const { return c_->ticket; }
+        bool ready() const { return mbls_stream_query(vs_->h_, c_->ticket) != MBLS_PENDING; }
+        std::vector<bool> get() const { vs_->wait(c_->ticket); return std::vector<bool>(c_->res.begin(), c_->res.begin() + c_->n); }
+    };
+    // policy: MBLS_STREAM_WORK_CONSERVING or MBLS_STREAM_FULL_ROUNDS; round_items 0 = the device's round
+    explicit VerifyStream(uint32_t policy = MBLS_STREAM_WORK_CONSERVING, uint64_t round_items = 0) {
+        mbls_stream_opts o{}; o.round_items = round_items; o.policy = policy;
+        if (mbls_stream_create(detail::ctx(), MBLS_STREAM_FAST_AGGREGATE_VERIFY, MBLS_PK_UNCOMPRESSED, nullptr, &o, &h_) != MBLS_OK)
+            throw DeviceError(std::string("mbls_stream_create: ") + mbls_last_error(detail::ctx()));
+    }
+    VerifyStream(const VerifyStream&) = delete; VerifyStream& operator=(const VerifyStream&) = delete;
+    ~VerifyStream() { mbls_stream_destroy(h_); }
+    mbls_stream* handle() const { return h_; }
+    // n x AggregateSignature::fast_aggregate_verify; messages of any length each
+    Ticket submit(const std::vector<AggregateSignature>& sigs, const std::vector<Bytes>& msgs, const std::vector<std::vector<const PublicKey*>>& keys) {
+        const size_t n = sigs.size();
+        if (n == 0 || msgs.size() != n || keys.size() != n) throw std::invalid_argument("one message and one key set per signature, at least one item");
+        auto c = std::make_shared<Call>();
+        c->moff.push_back(0); c->koff.push_back(0); c->n = n; c->res.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            c->s.insert(c->s.end(), sigs[i].point.begin(), sigs[i].point.end());
+            c->m.insert(c->m.end(), msgs[i].begin(), msgs[i].end()); c->moff.push_back(c->m.size());
+            for (auto* k : keys[i]) c->p.insert(c->p.end(), k->point.begin(), k->point.end());
+            if (c->p.size() / 96 > 0xFFFFFFFFull) throw std::invalid_argument("VerifyStream::submit: key offsets are 32-bit");
+            c->koff.push_back(uint32_t(c->p.size() / 96));
+        }
+        std::lock_guard<std::mutex> g(mu_);
+        while (!live_.empty() && mbls_stream_query(h_, live_.front()->ticket) != MBLS_PENDING) live_.pop_front();
+        check(mbls_stream_submit(h_, c->s.data(), c->m.data(), 0, c->moff.data(), c->p.data(), nullptr, c->koff.data(), n, 0, c->res.data(), nullptr, &c->ticket));
+        live_.push_back(c);
+        return Ticket(this, c);
+    }
+    void flush() { check(mbls_stream_flush(h_)); }
+    void wait(uint64_t ticket) const { check(mbls_stream_wait(h_, ticket)); }
+    mbls_stream_stats stats() const { mbls_stream_stats st{}; check(mbls_stream_get_stats(h_, &st)); return st; }
+};
 }  // namespace milagro_bls

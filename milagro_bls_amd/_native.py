@@ -16,6 +16,7 @@ ERR_INVALID_SECRET_KEY_SIZE = 5
 ERR_INVALID_SECRET_KEY_RANGE = 6
 ERR_DEVICE = 100
 ERR_ARGUMENT = 101
+PENDING = 102                   # mbls_stream_query: the call is not done
 PK_COMPRESSED, PK_UNCOMPRESSED = 0, 1
 VM_PARTIAL_BYTES = 896          # include/mbls.h MBLS_VM_PARTIAL_BYTES
 N_PHASES = 6
@@ -71,6 +72,54 @@ def plan_workspace_items(n, k, split_layout=True, limits=None):
     """workspace items the plan of n items of k keys needs (pure: no GPU); split_layout: uniform 96-byte keys or key-table indices"""
     L = limits if limits is not None else default_limits()
     return int(lib().mbls_plan_workspace_items(C.byref(L), n, k, 1 if split_layout else 0))
+
+
+class StreamOpts(C.Structure):
+    """include/mbls.h mbls_stream_opts (0 = default)"""
+    _fields_ = [("round_items", C.c_uint64), ("round_keys", C.c_uint64), ("round_msg_bytes", C.c_uint64), ("depth", C.c_uint32), ("policy", C.c_uint32)]
+
+
+class StreamStats(C.Structure):
+    """include/mbls.h mbls_stream_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "items", "pieces", "rounds", "full_rounds", "split_calls", "gathered_bytes")]
+
+
+class StreamCallShape(C.Structure):
+    """include/mbls.h mbls_stream_call_shape"""
+    _fields_ = [("n", C.c_uint64), ("k", C.c_uint32), ("msg_len", C.c_uint32), ("pk_offsets", u32p), ("msg_offsets", u64p), ("flush_after", C.c_uint32)]
+
+
+class StreamPiece(C.Structure):
+    """include/mbls.h mbls_stream_piece"""
+    _fields_ = [(n, C.c_uint64) for n in ("call", "first", "items", "round", "round_first")]
+
+
+STREAM_FAST_AGGREGATE_VERIFY, STREAM_VERIFY = 0, 1
+STREAM_WORK_CONSERVING, STREAM_FULL_ROUNDS = 0, 1
+
+
+def stream_cut(calls, round_items, round_keys, round_msg_bytes):
+    """how a verification stream cuts a sequence of calls into rounds (pure: no GPU) -> [piece dicts]. calls: dicts with n and optionally k, msg_len,
+    pk_offsets, msg_offsets (sequences) and flush_after (a launch is forced after the call)"""
+    o = StreamOpts(round_items, round_keys, round_msg_bytes, 1, STREAM_FULL_ROUNDS)
+    shapes = (StreamCallShape * max(1, len(calls)))()
+    keep = []
+    for i, c in enumerate(calls):
+        s = shapes[i]
+        s.n, s.k, s.msg_len, s.flush_after = c["n"], c.get("k", 0), c.get("msg_len", 0), int(bool(c.get("flush_after", 0)))
+        if c.get("pk_offsets") is not None:
+            a = (C.c_uint32 * len(c["pk_offsets"]))(*c["pk_offsets"]); keep.append(a); s.pk_offsets = C.cast(a, u32p)
+        if c.get("msg_offsets") is not None:
+            a = (C.c_uint64 * len(c["msg_offsets"]))(*c["msg_offsets"]); keep.append(a); s.msg_offsets = C.cast(a, u64p)
+    cnt = C.c_uint64(0)
+    rc = lib().mbls_stream_cut(C.byref(o), shapes, len(calls), None, 0, C.byref(cnt))
+    if rc != OK:
+        raise MblsError(rc, "mbls_stream_cut")
+    out = (StreamPiece * max(1, cnt.value))()
+    rc = lib().mbls_stream_cut(C.byref(o), shapes, len(calls), out, cnt.value, C.byref(cnt))
+    if rc != OK:
+        raise MblsError(rc, "mbls_stream_cut")
+    return [{f: getattr(out[i], f) for f, _ in StreamPiece._fields_} for i in range(cnt.value)]
 
 
 # mbls_scalar_source (include/mbls.h): void draw(void* user, uint64_t* out, uint64_t count)
@@ -164,6 +213,16 @@ SIGNATURES = {
     "mbls_multi_keytable_replica": (vp, [vp, C.c_int]),
     "mbls_multi_keytable_append": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), vp]),
     "mbls_multi_fast_aggregate_verify_batch_indexed": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
+    "mbls_stream_create": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.POINTER(vp)]),
+    "mbls_stream_destroy": (None, [vp]),
+    "mbls_stream_last_error": (C.c_char_p, [vp]),
+    "mbls_stream_submit_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_uint64)]),
+    "mbls_stream_submit": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(C.c_uint64)]),
+    "mbls_stream_flush": (C.c_int, [vp]),
+    "mbls_stream_wait": (C.c_int, [vp, C.c_uint64]),
+    "mbls_stream_query": (C.c_int, [vp, C.c_uint64]),
+    "mbls_stream_get_stats": (C.c_int, [vp, vp]),
+    "mbls_stream_cut": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "mbls_enable_phase_timing": (C.c_int, [vp, C.c_int]),
     "mbls_last_phase_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
 }

@@ -1,0 +1,84 @@
+// mbls_stream.h -- the pure parts of the verification stream (include/mbls.h, "verification stream"), in a header of their own so that a
+// host compiler can build them for the CPU tests (tests/host_emul/mbls_stream_harness.cpp): the cutting rule that packs calls into rounds,
+// the layout decision of a round, and the bit arithmetic of the scatter into a caller's bitmap. mbls_stream.hip runs exactly these.
+#ifndef MBLS_STREAM_H
+#define MBLS_STREAM_H
+#include <stdint.h>
+#include "../../include/mbls.h"
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define MBLS_SFN static inline __host__ __device__
+#else
+#define MBLS_SFN static inline
+#endif
+
+// ---- cutting: the fill of the open round and the largest run of a call's items that still fits it
+struct mbls_stream_fill { uint64_t items, keys, msg_bytes; };
+
+MBLS_SFN uint64_t stream_item_keys(const mbls_stream_call_shape& c, uint64_t i) { return c.pk_offsets ? (uint64_t)(c.pk_offsets[i + 1] - c.pk_offsets[i]) : c.k; }
+MBLS_SFN uint64_t stream_item_msg(const mbls_stream_call_shape& c, uint64_t i) { return c.msg_offsets ? c.msg_offsets[i + 1] - c.msg_offsets[i] : c.msg_len; }
+
+// items [first, first + return value) of call c join the open round (f is advanced past them); fewer than c.n - first means the next item does
+// not fit: the round is full. Uniform calls take their run in one step, ragged ones item by item.
+MBLS_SFN uint64_t stream_take(const mbls_stream_opts& o, mbls_stream_fill& f, const mbls_stream_call_shape& c, uint64_t first) {
+    if (first >= c.n || f.items >= o.round_items) return 0;
+    uint64_t t;
+    if (!c.pk_offsets && !c.msg_offsets) {
+        uint64_t room = o.round_items - f.items;
+        if (c.k) { const uint64_t r = (o.round_keys - f.keys) / c.k; room = r < room ? r : room; }
+        if (c.msg_len) { const uint64_t r = (o.round_msg_bytes - f.msg_bytes) / c.msg_len; room = r < room ? r : room; }
+        t = c.n - first < room ? c.n - first : room;
+        f.keys += t * c.k; f.msg_bytes += t * c.msg_len;
+    } else {
+        uint64_t i = first, keys = f.keys, msg = f.msg_bytes;
+        const uint64_t end = first + (o.round_items - f.items) < c.n ? first + (o.round_items - f.items) : c.n;
+        for (; i < end; i++) {
+            const uint64_t ki = stream_item_keys(c, i), mi = stream_item_msg(c, i);
+            if (keys + ki > o.round_keys || msg + mi > o.round_msg_bytes) break;
+            keys += ki; msg += mi;
+        }
+        t = i - first; f.keys = keys; f.msg_bytes = msg;
+    }
+    f.items += t;
+    return t;
+}
+
+// the call as a whole: offsets non-decreasing (messages below 2^32 bytes, as the host entries require), and no item larger than an empty round.
+// Returns 0, or 1 + the index of the first offending item with *what = 1 (offsets), 2 (keys), 3 (message bytes).
+MBLS_SFN uint64_t stream_check_call(const mbls_stream_opts& o, const mbls_stream_call_shape& c, int* what) {
+    for (uint64_t i = 0; i < c.n; i++) {
+        if (c.pk_offsets && c.pk_offsets[i + 1] < c.pk_offsets[i]) { *what = 1; return i + 1; }
+        if (c.msg_offsets && (c.msg_offsets[i + 1] < c.msg_offsets[i] || c.msg_offsets[i + 1] - c.msg_offsets[i] > 0xFFFFFFFFull)) { *what = 1; return i + 1; }
+        if (stream_item_keys(c, i) > o.round_keys) { *what = 2; return i + 1; }
+        if (stream_item_msg(c, i) > o.round_msg_bytes) { *what = 3; return i + 1; }
+        if (!c.pk_offsets && !c.msg_offsets) break;                       // uniform: every item is the first
+    }
+    *what = 0; return 0;
+}
+
+// ---- layout of a round: the uniform layout (no offset tables) where every piece shares it -- it keeps the fast forms the pipeline picks for
+// uniform layouts (the staged decompression of 48-byte keys, the eight-lane key sum on the wave engine) --, ragged tables otherwise. Keys and
+// messages are decided separately.
+struct mbls_stream_layout { int keys_uniform, msgs_uniform; uint32_t k, msg_len; };
+MBLS_SFN void stream_layout_add(mbls_stream_layout& l, bool first_piece, const mbls_stream_call_shape& c) {
+    if (first_piece) { l.keys_uniform = !c.pk_offsets; l.msgs_uniform = !c.msg_offsets; l.k = c.k; l.msg_len = c.msg_len; return; }
+    if (c.pk_offsets || c.k != l.k) l.keys_uniform = 0;
+    if (c.msg_offsets || c.msg_len != l.msg_len) l.msgs_uniform = 0;
+}
+
+// ---- scatter of a piece's accept bits into the caller's bitmap. The piece covers bits [call_first, call_first + items) of the call's bitmap
+// and results [round_first, ...) of the round. It touches words [w0, w0 + nw); a word entirely inside the piece is stored whole, a boundary
+// word (shared with the call's other pieces) is OR-ed in.
+MBLS_SFN void stream_bitmap_words(uint64_t call_first, uint64_t items, uint64_t* w0, uint64_t* nw) {
+    *w0 = call_first / 64; *nw = items ? (call_first + items - 1) / 64 - *w0 + 1 : 0;
+}
+// the bits of call word w that the piece owns (round_res: the round's result bytes); *whole = the word lies entirely inside the piece
+MBLS_SFN uint64_t stream_bitmap_word(const uint8_t* round_res, uint64_t round_first, uint64_t call_first, uint64_t items, uint64_t w, int* whole) {
+    const uint64_t wlo = 64 * w, lo = wlo > call_first ? wlo : call_first;
+    const uint64_t hi = wlo + 64 < call_first + items ? wlo + 64 : call_first + items;
+    uint64_t bits = 0;
+    for (uint64_t b = lo; b < hi; b++) bits |= (uint64_t)(round_res[round_first + (b - call_first)] != 0) << (b - wlo);
+    *whole = lo == wlo && hi == wlo + 64;
+    return bits;
+}
+#endif

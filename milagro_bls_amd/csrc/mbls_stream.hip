@@ -1,0 +1,525 @@
+// mbls_stream.hip -- the verification stream (include/mbls.h, "verification stream"): calls of any size in, full-round launches of the
+// public device entries out. Built on the public ABI only: mbls_ctx_get_limits, mbls_ctx_reserve[_keys], mbls_plan_workspace_items and the
+// three *_device verification entries, so every result comes out of the same verify_pipeline the parity tests pin.
+//
+// Per stream: depth + 1 staging SLOTS (one round each: the open one and up to depth launched), one LAUNCHER thread that cuts the queue of
+// submitted calls into the open slot (stream_take, the rule mbls_stream_cut states as data), gathers the round's inputs into the slot on the
+// stream's gather stream (k_stream_gather; host pieces by hipMemcpyAsync), runs the device entry on the stream's main HIP stream, scatters
+// the results back to the callers (k_stream_scatter; host pieces through a pinned area) and records a blocking-sync event, and one COMPLETER
+// thread that waits on those events in order, copies host results, advances completed_through and frees the slot. Neither thread calls into
+// the context with the stream's lock held; no HIP call is made from a host callback.
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+#include <algorithm>
+#include <condition_variable>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <thread>
+#include <vector>
+#include "mbls_stream.h"
+
+namespace {
+
+constexpr unsigned SWG = 64;                        // one wave per workgroup, like the rest of the library
+constexpr uint64_t GATHER_TILE = 128 * 1024;         // bytes per gather tile (a multiple of 16: tiles of one segment keep its alignment)
+constexpr uint64_t SCATTER_TILE = 4096;              // items per scatter tile, cut at multiples of this in the CALL's item space (so at bitmap words)
+
+struct gtile { const uint8_t* src; uint8_t* dst; uint64_t bytes; };
+struct stile { uint8_t* res; uint32_t* st; uint64_t* bm; uint64_t call_first, items, round_first; };
+
+}  // namespace
+
+// One workgroup per tile: 16-byte loads and stores where source and destination are both 16-byte aligned, dwords where both are 4-byte
+// aligned, bytes otherwise (ragged messages start anywhere).
+__global__ __launch_bounds__(SWG) void k_stream_gather(const gtile* __restrict__ tiles) {
+    const gtile t = tiles[blockIdx.x];
+    const unsigned l = threadIdx.x;
+    const uintptr_t a = (uintptr_t)t.src | (uintptr_t)t.dst;
+    uint64_t done = 0;
+    if ((a & 15) == 0) {
+        const uint64_t n16 = t.bytes / 16;
+        const uint4* s = (const uint4*)t.src; uint4* d = (uint4*)t.dst;
+#pragma unroll 4
+        for (uint64_t i = l; i < n16; i += SWG) d[i] = s[i];
+        done = 16 * n16;
+    } else if ((a & 3) == 0) {
+        const uint64_t n4 = t.bytes / 4;
+        const uint32_t* s = (const uint32_t*)t.src; uint32_t* d = (uint32_t*)t.dst;
+#pragma unroll 4
+        for (uint64_t i = l; i < n4; i += SWG) d[i] = s[i];
+        done = 4 * n4;
+    }
+    for (uint64_t i = done + l; i < t.bytes; i += SWG) t.dst[i] = t.src[i];
+}
+
+// One workgroup per tile of a device piece: result bytes and status words to caller + first, the accept bits into the caller's bitmap (words
+// entirely inside the piece stored whole, boundary words OR-ed in: the call's other pieces own their other bits; the words were zeroed on the
+// caller's stream at submit).
+__global__ __launch_bounds__(SWG) void k_stream_scatter(const stile* __restrict__ tiles, const uint8_t* __restrict__ round_res, const uint32_t* __restrict__ round_st) {
+    const stile t = tiles[blockIdx.x];
+    const unsigned l = threadIdx.x;
+    for (uint64_t i = l; i < t.items; i += SWG) {
+        t.res[t.call_first + i] = round_res[t.round_first + i];
+        if (t.st) t.st[t.call_first + i] = round_st[t.round_first + i];
+    }
+    if (t.bm) {
+        uint64_t w0, nw; stream_bitmap_words(t.call_first, t.items, &w0, &nw);
+        for (uint64_t j = l; j < nw; j += SWG) {
+            int whole; const uint64_t bits = stream_bitmap_word(round_res, t.round_first, t.call_first, t.items, w0 + j, &whole);
+            if (whole) t.bm[w0 + j] = bits;
+            else if (bits) atomicOr((unsigned long long*)&t.bm[w0 + j], (unsigned long long)bits);
+        }
+    }
+}
+
+namespace {
+
+struct call_rec {
+    uint64_t ticket = 0; bool host = false; bool split = false;
+    mbls_stream_call_shape shape{};
+    const uint8_t* sigs = nullptr; const uint8_t* msgs = nullptr; const uint8_t* keys = nullptr;   // keys: bytes or indices
+    uint8_t* res = nullptr; uint64_t* bm = nullptr; uint32_t* st = nullptr;
+    hipEvent_t ev = nullptr;                                                 // device submits: recorded on the caller's stream
+};
+struct piece_rec { std::shared_ptr<call_rec> c; uint64_t first, items, round_first; };
+
+struct slot {
+    uint8_t *d_sigs = nullptr, *d_msgs = nullptr, *d_keys = nullptr, *d_res = nullptr, *d_meta = nullptr; uint32_t* d_st = nullptr;
+    uint8_t *h_meta = nullptr, *h_res = nullptr; uint32_t* h_st = nullptr;      // pinned
+    hipEvent_t gev = nullptr, done = nullptr;
+    std::vector<piece_rec> pieces;
+    mbls_stream_fill fill{};
+    bool full = false;
+    uint64_t first_ticket = 0, done_through = 0;
+    int rc = MBLS_OK;
+};
+
+}  // namespace
+
+struct mbls_stream {
+    mbls_ctx* ctx = nullptr; const mbls_keytable* tab = nullptr;
+    int mode = 0, fmt = MBLS_PK_UNCOMPRESSED, dev = 0; size_t unit = 96;
+    mbls_stream_opts o{};
+    uint64_t meta_bytes = 0;
+    hipStream_t hs = nullptr, gs = nullptr;
+    std::vector<slot> slots;
+
+    std::mutex mu;
+    std::condition_variable cv_launch, cv_complete, cv_done;
+    std::deque<std::shared_ptr<call_rec>> calls;     // submitted, not yet complete; calls[t - base] holds ticket t
+    uint64_t base = 1, last_ticket = 0, cursor = 1, item_off = 0, flush_upto = 0, completed_through = 0, cut_done_through = 0;
+    std::deque<int> free_slots, inflight;
+    int open = -1;
+    bool stop = false, closing = false, dead = false;
+    int err_code = MBLS_OK; uint64_t err_ticket = 0;
+    mbls_stream_stats stats{};
+    std::vector<hipEvent_t> ev_pool;
+    std::thread launcher, completer;
+    std::mutex err_mu; char err[256] = "";
+};
+
+namespace {
+
+int fail(mbls_stream* s, int rc, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+int fail(mbls_stream* s, int rc, const char* fmt, ...) {
+    std::lock_guard<std::mutex> g(s->err_mu);
+    va_list ap; va_start(ap, fmt); vsnprintf(s->err, sizeof(s->err), fmt, ap); va_end(ap);
+    return rc;
+}
+
+uint64_t meta_capacity(const mbls_stream_opts& o, size_t unit) {
+    const uint64_t R = o.round_items;
+    const uint64_t bytes = 96 * R + o.round_msg_bytes + unit * o.round_keys;
+    const uint64_t ng = bytes / GATHER_TILE + 3 * R + 3, ns = 2 * R + R / SCATTER_TILE + 1;      // (a piece takes at most items / tile + 2 scatter tiles)
+    return ng * sizeof(gtile) + ns * sizeof(stile) + 4 * (R + 1) + 8 * (R + 1) + 64;
+}
+
+// The round in the open slot: gather, the device entry, scatter, completion event. Runs on the launcher thread without the stream's lock.
+int launch_round(mbls_stream* s, slot& sl) {
+    const uint64_t n = sl.fill.items;
+    mbls_stream_layout lay{};
+    for (size_t p = 0; p < sl.pieces.size(); p++) stream_layout_add(lay, p == 0, sl.pieces[p].c->shape);
+    if (s->mode == MBLS_STREAM_VERIFY) { lay.keys_uniform = 1; lay.k = 1; }
+    // the meta area, packed: gather tiles | scatter tiles | key offsets | message offsets -- one upload from pinned memory
+    std::vector<gtile> gt; std::vector<stile> stv;
+    std::vector<uint32_t> pkoff; std::vector<uint64_t> moff;
+    if (!lay.keys_uniform) pkoff.resize(n + 1);
+    if (!lay.msgs_uniform) moff.resize(n + 1);
+    uint64_t key_cur = 0, msg_cur = 0, gathered = 0;
+    bool any_host = false;
+    hipError_t e = hipSuccess;
+    auto seg = [&](bool host, const uint8_t* src, uint8_t* dst, uint64_t bytes) {
+        if (!bytes) return;
+        gathered += bytes;
+        if (host) { if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s->gs); return; }
+        for (uint64_t o = 0; o < bytes; o += GATHER_TILE) gt.push_back(gtile{src + o, dst + o, std::min(GATHER_TILE, bytes - o)});
+    };
+    hipEvent_t last_ev = nullptr;
+    for (const piece_rec& p : sl.pieces) {
+        const call_rec& c = *p.c; const mbls_stream_call_shape& sh = c.shape;
+        if (!c.host && c.ev != last_ev) { if (e == hipSuccess) e = hipStreamWaitEvent(s->gs, c.ev, 0); last_ev = c.ev; }
+        any_host |= c.host;
+        seg(c.host, c.sigs + 96 * p.first, sl.d_sigs + 96 * p.round_first, 96 * p.items);
+        const uint64_t m0 = sh.msg_offsets ? sh.msg_offsets[p.first] : (uint64_t)sh.msg_len * p.first;
+        const uint64_t mb = sh.msg_offsets ? sh.msg_offsets[p.first + p.items] - m0 : (uint64_t)sh.msg_len * p.items;
+        seg(c.host, c.msgs + m0, sl.d_msgs + msg_cur, mb);
+        const uint64_t k0 = sh.pk_offsets ? sh.pk_offsets[p.first] : (uint64_t)sh.k * p.first;
+        const uint64_t kc = sh.pk_offsets ? sh.pk_offsets[p.first + p.items] - k0 : (uint64_t)sh.k * p.items;
+        seg(c.host, c.keys + s->unit * k0, sl.d_keys + s->unit * key_cur, s->unit * kc);
+        if (!lay.keys_uniform || !lay.msgs_uniform)
+        for (uint64_t i = 0; i < p.items; i++) {
+            if (!lay.keys_uniform) pkoff[p.round_first + i] = (uint32_t)(key_cur + (sh.pk_offsets ? sh.pk_offsets[p.first + i] - k0 : (uint64_t)sh.k * i));
+            if (!lay.msgs_uniform) moff[p.round_first + i] = msg_cur + (sh.msg_offsets ? sh.msg_offsets[p.first + i] - m0 : (uint64_t)sh.msg_len * i);
+        }
+        key_cur += kc; msg_cur += mb;
+        if (!c.host)
+            for (uint64_t a = p.first; a < p.first + p.items;) {
+                const uint64_t b = std::min(p.first + p.items, (a / SCATTER_TILE + 1) * SCATTER_TILE);
+                stv.push_back(stile{c.res, c.st, c.bm, a, b - a, p.round_first + (a - p.first)});
+                a = b;
+            }
+    }
+    if (!lay.keys_uniform) pkoff[n] = (uint32_t)key_cur;
+    if (!lay.msgs_uniform) moff[n] = msg_cur;
+    auto up = [](uint64_t x, uint64_t a) { return (x + a - 1) / a * a; };
+    const uint64_t at_g = 0, at_s = up(at_g + gt.size() * sizeof(gtile), 16), at_k = up(at_s + stv.size() * sizeof(stile), 8), at_m = up(at_k + pkoff.size() * 4, 8);
+    const uint64_t off = at_m + moff.size() * 8;
+    if (off > s->meta_bytes) return fail(s, MBLS_ERR_DEVICE, "internal: round meta of %llu bytes exceeds the slot's %llu", (unsigned long long)off, (unsigned long long)s->meta_bytes);
+    if (!gt.empty()) memcpy(sl.h_meta + at_g, gt.data(), gt.size() * sizeof(gtile));
+    if (!stv.empty()) memcpy(sl.h_meta + at_s, stv.data(), stv.size() * sizeof(stile));
+    if (!pkoff.empty()) memcpy(sl.h_meta + at_k, pkoff.data(), pkoff.size() * 4);
+    if (!moff.empty()) memcpy(sl.h_meta + at_m, moff.data(), moff.size() * 8);
+    if (e == hipSuccess && off) e = hipMemcpyAsync(sl.d_meta, sl.h_meta, off, hipMemcpyHostToDevice, s->gs);
+    if (e == hipSuccess && !gt.empty()) { hipLaunchKernelGGL(k_stream_gather, dim3((unsigned)gt.size()), dim3(SWG), 0, s->gs, (const gtile*)(sl.d_meta + at_g)); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipEventRecord(sl.gev, s->gs);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s->hs, sl.gev, 0);
+    if (e != hipSuccess) return fail(s, MBLS_ERR_DEVICE, "gather: %s", hipGetErrorString(e));
+    const uint64_t* d_moff = lay.msgs_uniform ? nullptr : (const uint64_t*)(sl.d_meta + at_m);
+    const uint32_t* d_pkoff = lay.keys_uniform ? nullptr : (const uint32_t*)(sl.d_meta + at_k);
+    const uint32_t msg_len = lay.msgs_uniform ? lay.msg_len : 0, k = lay.keys_uniform ? lay.k : 0;
+    int rc;
+    if (s->mode == MBLS_STREAM_VERIFY)
+        rc = mbls_verify_batch_device(s->ctx, sl.d_sigs, sl.d_msgs, msg_len, d_moff, sl.d_keys, s->fmt, n, sl.d_res, nullptr, sl.d_st, s->hs);
+    else if (s->tab)
+        rc = mbls_fast_aggregate_verify_batch_indexed_device(s->ctx, s->tab, sl.d_sigs, sl.d_msgs, msg_len, d_moff, (const uint32_t*)sl.d_keys, d_pkoff, n, k,
+                                                             sl.d_res, nullptr, sl.d_st, s->hs);
+    else
+        rc = mbls_fast_aggregate_verify_batch_device(s->ctx, sl.d_sigs, sl.d_msgs, msg_len, d_moff, sl.d_keys, s->fmt, d_pkoff, n, k, sl.d_res, nullptr, sl.d_st, s->hs);
+    if (rc) return fail(s, rc, "round of %llu items: %s", (unsigned long long)n, mbls_last_error(s->ctx));
+    if (!stv.empty()) { hipLaunchKernelGGL(k_stream_scatter, dim3((unsigned)stv.size()), dim3(SWG), 0, s->hs, (const stile*)(sl.d_meta + at_s), (const uint8_t*)sl.d_res, (const uint32_t*)sl.d_st); e = hipGetLastError(); }
+    if (e == hipSuccess && any_host) e = hipMemcpyAsync(sl.h_res, sl.d_res, n, hipMemcpyDeviceToHost, s->hs);
+    if (e == hipSuccess && any_host) e = hipMemcpyAsync(sl.h_st, sl.d_st, 4 * n, hipMemcpyDeviceToHost, s->hs);
+    if (e == hipSuccess) e = hipEventRecord(sl.done, s->hs);
+    if (e != hipSuccess) return fail(s, MBLS_ERR_DEVICE, "scatter: %s", hipGetErrorString(e));
+    std::lock_guard<std::mutex> g(s->mu);
+    s->stats.gathered_bytes += gathered;
+    return MBLS_OK;
+}
+
+// cut queued calls into the open slot (lock held): the same stream_take mbls_stream_cut runs, a flush boundary after call flush_upto
+void absorb(mbls_stream* s, slot& sl) {
+    while (s->cursor <= s->last_ticket && !sl.full) {
+        const std::shared_ptr<call_rec>& c = s->calls[s->cursor - s->base];
+        if (sl.fill.items && sl.first_ticket <= s->flush_upto && c->ticket > s->flush_upto) break;
+        const uint64_t before = sl.fill.items;
+        const uint64_t t = stream_take(s->o, sl.fill, c->shape, s->item_off);
+        if (t) {
+            if (sl.pieces.empty()) sl.first_ticket = c->ticket;
+            if (s->item_off) c->split = true;
+            sl.pieces.push_back(piece_rec{c, s->item_off, t, before});
+            s->item_off += t;
+        }
+        if (s->item_off == c->shape.n) { sl.done_through = c->ticket; s->cursor++; s->item_off = 0; }
+        else sl.full = true;
+        if (sl.fill.items == s->o.round_items) sl.full = true;
+    }
+}
+
+void launcher_main(mbls_stream* s) {
+    (void)hipSetDevice(s->dev);
+    std::unique_lock<std::mutex> lk(s->mu);
+    for (;;) {
+        if (s->open < 0) {
+            while (s->free_slots.empty() && !s->stop) s->cv_launch.wait(lk);
+            if (s->stop) return;
+            s->open = s->free_slots.front(); s->free_slots.pop_front();
+            slot& o = s->slots[s->open];
+            o.pieces.clear(); o.fill = mbls_stream_fill{}; o.full = false; o.first_ticket = 0; o.done_through = s->cut_done_through; o.rc = MBLS_OK;
+        }
+        slot& o = s->slots[s->open];
+        absorb(s, o);
+        const bool flush = o.fill.items && o.first_ticket <= s->flush_upto;
+        const bool wc = s->o.policy == MBLS_STREAM_WORK_CONSERVING && s->inflight.size() < s->o.depth;
+        if (o.fill.items && (o.full || flush || wc)) {
+            const int si = s->open; s->open = -1;
+            s->cut_done_through = o.done_through;
+            s->stats.rounds++; s->stats.full_rounds += o.full; s->stats.pieces += o.pieces.size();
+            for (const piece_rec& p : o.pieces) if (p.first && p.c->split && p.first + p.items == p.c->shape.n) s->stats.split_calls++;
+            const bool dead = s->dead;
+            lk.unlock();
+            int rc = dead ? MBLS_ERR_DEVICE : launch_round(s, o);
+            lk.lock();
+            o.rc = rc;
+            s->inflight.push_back(si);
+            s->cv_complete.notify_one();
+            continue;
+        }
+        if (s->stop) return;
+        s->cv_launch.wait(lk);
+    }
+}
+
+void completer_main(mbls_stream* s) {
+    (void)hipSetDevice(s->dev);
+    std::unique_lock<std::mutex> lk(s->mu);
+    for (;;) {
+        while (s->inflight.empty() && !s->stop) s->cv_complete.wait(lk);
+        if (s->inflight.empty()) return;
+        const int si = s->inflight.front();
+        slot& sl = s->slots[si];
+        lk.unlock();
+        int rc = sl.rc;
+        if (!rc) { const hipError_t e = hipEventSynchronize(sl.done); if (e != hipSuccess) rc = fail(s, MBLS_ERR_DEVICE, "round: %s", hipGetErrorString(e)); }
+        if (!rc)
+            for (const piece_rec& p : sl.pieces) {
+                if (!p.c->host) continue;
+                memcpy(p.c->res + p.first, sl.h_res + p.round_first, p.items);
+                if (p.c->st) memcpy(p.c->st + p.first, sl.h_st + p.round_first, 4 * p.items);
+            }
+        lk.lock();
+        if (rc) {
+            s->dead = true;
+            if (!s->err_code) { s->err_code = rc; s->err_ticket = sl.first_ticket; }
+        }
+        if (sl.done_through > s->completed_through) s->completed_through = sl.done_through;
+        sl.pieces.clear();
+        while (!s->calls.empty() && s->calls.front()->ticket <= s->completed_through && s->calls.front()->ticket < s->cursor) {
+            if (s->calls.front()->ev) s->ev_pool.push_back(s->calls.front()->ev);
+            s->calls.pop_front(); s->base++;
+        }
+        s->inflight.pop_front(); s->free_slots.push_back(si);
+        s->cv_launch.notify_one(); s->cv_done.notify_all();
+    }
+}
+
+void free_stream(mbls_stream* s) {
+    for (slot& sl : s->slots) {
+        for (uint8_t* p : {sl.d_sigs, sl.d_msgs, sl.d_keys, sl.d_res, sl.d_meta}) if (p) (void)hipFree(p);
+        if (sl.d_st) (void)hipFree(sl.d_st);
+        for (void* p : {(void*)sl.h_meta, (void*)sl.h_res, (void*)sl.h_st}) if (p) (void)hipHostFree(p);
+        if (sl.gev) (void)hipEventDestroy(sl.gev);
+        if (sl.done) (void)hipEventDestroy(sl.done);
+    }
+    for (hipEvent_t ev : s->ev_pool) (void)hipEventDestroy(ev);
+    for (auto& c : s->calls) if (c->ev) (void)hipEventDestroy(c->ev);
+    if (s->hs) (void)hipStreamDestroy(s->hs);
+    if (s->gs) (void)hipStreamDestroy(s->gs);
+    delete s;
+}
+
+int submit(mbls_stream* s, bool host, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, const uint8_t* pks,
+           const uint32_t* idx, const uint32_t* poff, uint64_t n, uint32_t k, uint8_t* res, uint64_t* bm, uint32_t* st, void* stream, uint64_t* ticket) {
+    if (!s) return MBLS_ERR_ARGUMENT;
+    if (!ticket) return fail(s, MBLS_ERR_ARGUMENT, "null ticket pointer");
+    if (n == 0) return fail(s, MBLS_ERR_ARGUMENT, "a call holds at least one item");
+    if (!sigs || !res) return fail(s, MBLS_ERR_ARGUMENT, "null buffer");
+    if (s->mode == MBLS_STREAM_VERIFY && (poff || k != 1)) return fail(s, MBLS_ERR_ARGUMENT, "verify mode: one key per item (k = 1, no key offsets)");
+    if (s->tab ? pks != nullptr : idx != nullptr)
+        return fail(s, MBLS_ERR_ARGUMENT, s->tab ? "an index stream takes key indices, not key bytes" : "a byte-key stream takes key bytes, not key indices");
+    mbls_stream_call_shape sh{n, k, msg_len, poff, moff, 0};
+    int what = 0; const uint64_t bad = stream_check_call(s->o, sh, &what);
+    if (bad) {
+        const uint64_t i = bad - 1;
+        if (what == 1) return fail(s, MBLS_ERR_ARGUMENT, "offset table runs backwards (or holds a message of 2^32 bytes or more) at item %llu", (unsigned long long)i);
+        if (what == 2) return fail(s, MBLS_ERR_ARGUMENT, "item %llu has %llu keys; a round holds %llu (mbls_stream_opts.round_keys)", (unsigned long long)i,
+                                   (unsigned long long)stream_item_keys(sh, i), (unsigned long long)s->o.round_keys);
+        return fail(s, MBLS_ERR_ARGUMENT, "item %llu has a %llu-byte message; a round holds %llu message bytes (mbls_stream_opts.round_msg_bytes)", (unsigned long long)i,
+                    (unsigned long long)stream_item_msg(sh, i), (unsigned long long)s->o.round_msg_bytes);
+    }
+    const uint64_t msg_total = moff ? moff[n] - moff[0] : (uint64_t)msg_len * n;
+    const uint64_t key_total = poff ? (uint64_t)(poff[n] - poff[0]) : (uint64_t)k * n;
+    if (msg_total && !msgs) return fail(s, MBLS_ERR_ARGUMENT, "null message buffer");
+    if (key_total && !(s->tab ? (const void*)idx : (const void*)pks)) return fail(s, MBLS_ERR_ARGUMENT, "null key buffer");
+    auto c = std::make_shared<call_rec>();
+    c->host = host; c->shape = sh; c->sigs = sigs; c->msgs = msgs; c->keys = s->tab ? (const uint8_t*)idx : pks; c->res = res; c->bm = bm; c->st = st;
+    if (!host) {
+        {
+            std::lock_guard<std::mutex> g(s->mu);
+            if (!s->ev_pool.empty()) { c->ev = s->ev_pool.back(); s->ev_pool.pop_back(); }
+        }
+        hipError_t e = hipSetDevice(s->dev);
+        if (e == hipSuccess && !c->ev) e = hipEventCreateWithFlags(&c->ev, hipEventDisableTiming);
+        if (e == hipSuccess && bm) e = hipMemsetAsync(bm, 0, 8 * ((n + 63) / 64), (hipStream_t)stream);
+        if (e == hipSuccess) e = hipEventRecord(c->ev, (hipStream_t)stream);
+        if (e != hipSuccess) {
+            if (c->ev) { std::lock_guard<std::mutex> g(s->mu); s->ev_pool.push_back(c->ev); }
+            return fail(s, MBLS_ERR_DEVICE, "submit: %s", hipGetErrorString(e));
+        }
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->dead || s->closing) {
+        if (c->ev) s->ev_pool.push_back(c->ev);
+        return s->dead ? fail(s, MBLS_ERR_DEVICE, "the stream met a device error") : fail(s, MBLS_ERR_ARGUMENT, "the stream is being destroyed");
+    }
+    c->ticket = ++s->last_ticket;
+    s->calls.push_back(c);
+    s->stats.calls++; s->stats.items += n;
+    *ticket = c->ticket;
+    s->cv_launch.notify_one();
+    return MBLS_OK;
+}
+
+}  // namespace
+
+extern "C" int mbls_stream_cut(const mbls_stream_opts* o, const mbls_stream_call_shape* calls, uint64_t n_calls, mbls_stream_piece* out, uint64_t max_pieces,
+                               uint64_t* n_pieces) {
+    if (!o || !calls || !n_calls || !n_pieces || !o->round_items || !o->round_keys || !o->round_msg_bytes || (!out && max_pieces)) return MBLS_ERR_ARGUMENT;
+    for (uint64_t j = 0; j < n_calls; j++) {
+        int what; if (!calls[j].n || stream_check_call(*o, calls[j], &what)) return MBLS_ERR_ARGUMENT;
+    }
+    mbls_stream_fill f{}; uint64_t round = 0, np = 0;
+    for (uint64_t j = 0; j < n_calls; j++) {
+        uint64_t first = 0;
+        while (first < calls[j].n) {
+            const uint64_t before = f.items, t = stream_take(*o, f, calls[j], first);
+            if (t) { if (np < max_pieces) out[np] = mbls_stream_piece{j, first, t, round, before}; np++; first += t; }
+            if (first < calls[j].n || f.items == o->round_items) { round++; f = mbls_stream_fill{}; }
+        }
+        if (calls[j].flush_after && f.items) { round++; f = mbls_stream_fill{}; }
+    }
+    *n_pieces = np;
+    return np <= max_pieces || !out ? MBLS_OK : MBLS_ERR_ARGUMENT;
+}
+
+extern "C" int mbls_stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, const mbls_stream_opts* opts, mbls_stream** out) {
+    if (!ctx || !out) return MBLS_ERR_ARGUMENT;
+    *out = nullptr;
+    if (mode != MBLS_STREAM_FAST_AGGREGATE_VERIFY && mode != MBLS_STREAM_VERIFY) return MBLS_ERR_ARGUMENT;
+    if (t && mode != MBLS_STREAM_FAST_AGGREGATE_VERIFY) return MBLS_ERR_ARGUMENT;           // only fast_aggregate_verify has an indexed entry
+    if (!t && pk_format != MBLS_PK_COMPRESSED && pk_format != MBLS_PK_UNCOMPRESSED) return MBLS_ERR_ARGUMENT;
+    // a table of another context is refused by the indexed entry itself (an empty call enqueues nothing)
+    if (t && mbls_fast_aggregate_verify_batch_indexed_device(ctx, t, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr))
+        return MBLS_ERR_ARGUMENT;
+    mbls_limits L; int rc = mbls_ctx_get_limits(ctx, &L); if (rc) return rc;
+    mbls_stream_opts o = opts ? *opts : mbls_stream_opts{};
+    if (o.policy != MBLS_STREAM_WORK_CONSERVING && o.policy != MBLS_STREAM_FULL_ROUNDS) return MBLS_ERR_ARGUMENT;
+    if (!o.round_items) o.round_items = L.round_items;
+    if (!o.round_keys) o.round_keys = (mode == MBLS_STREAM_VERIFY ? 1 : 128) * o.round_items;
+    if (!o.round_msg_bytes) o.round_msg_bytes = 64 * o.round_items;
+    if (!o.depth) o.depth = 2;
+    if (o.round_items > (1ull << 31) || o.round_keys > 0xFFFFFFFFull || o.depth > 64) return MBLS_ERR_ARGUMENT;    // key offsets of a round are 32-bit
+    mbls_stream* s = new (std::nothrow) mbls_stream();
+    if (!s) return MBLS_ERR_DEVICE;
+    s->ctx = ctx; s->tab = t; s->mode = mode; s->fmt = t ? MBLS_PK_UNCOMPRESSED : pk_format; s->o = o;
+    s->unit = t ? 4 : (pk_format == MBLS_PK_COMPRESSED ? 48 : 96);
+    // every round size's workspace up front (a partial round on the wave engine may take the eight-lane key sum, n + 8 n items): no round grows it
+    uint64_t ws = 0;
+    const uint32_t kmax = (uint32_t)std::min<uint64_t>(o.round_keys, 0xFFFFFFFFull);
+    for (uint64_t n = 1; n <= o.round_items; n++) {
+        ws = std::max(ws, mbls_plan_workspace_items(&L, n, kmax, 1));
+        if (kmax >= 32) ws = std::max(ws, mbls_plan_workspace_items(&L, n, 32, 1));
+    }
+    rc = mbls_ctx_reserve(ctx, ws);                       // (leaves the context's device current on this thread)
+    if (!rc && !t && pk_format == MBLS_PK_COMPRESSED) rc = mbls_ctx_reserve_keys(ctx, o.round_keys);
+    if (rc) { delete s; return rc; }
+    hipError_t e = hipGetDevice(&s->dev);
+    s->meta_bytes = meta_capacity(o, s->unit);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->hs, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->gs, hipStreamNonBlocking);
+    s->slots.resize(o.depth + 1);
+    for (slot& sl : s->slots) {
+        if (e == hipSuccess) e = hipMalloc(&sl.d_sigs, 96 * o.round_items);
+        if (e == hipSuccess) e = hipMalloc(&sl.d_msgs, std::max<uint64_t>(o.round_msg_bytes, 16));
+        if (e == hipSuccess) e = hipMalloc(&sl.d_keys, std::max<uint64_t>(s->unit * o.round_keys, 16));
+        if (e == hipSuccess) e = hipMalloc(&sl.d_res, o.round_items);
+        if (e == hipSuccess) e = hipMalloc(&sl.d_st, 4 * o.round_items);
+        if (e == hipSuccess) e = hipMalloc(&sl.d_meta, s->meta_bytes);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&sl.h_meta, s->meta_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&sl.h_res, o.round_items, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&sl.h_st, 4 * o.round_items, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.gev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync);
+    }
+    if (e != hipSuccess) { free_stream(s); return MBLS_ERR_DEVICE; }
+    for (int i = 0; i < (int)s->slots.size(); i++) s->free_slots.push_back(i);
+    try {
+        s->launcher = std::thread(launcher_main, s);
+        s->completer = std::thread(completer_main, s);
+    } catch (...) {
+        { std::lock_guard<std::mutex> g(s->mu); s->stop = true; }
+        s->cv_launch.notify_all(); s->cv_complete.notify_all();
+        if (s->launcher.joinable()) s->launcher.join();
+        free_stream(s); return MBLS_ERR_DEVICE;
+    }
+    *out = s;
+    return MBLS_OK;
+}
+
+extern "C" void mbls_stream_destroy(mbls_stream* s) {
+    if (!s) return;
+    {
+        std::unique_lock<std::mutex> lk(s->mu);
+        s->closing = true;
+        s->flush_upto = s->last_ticket;
+        s->cv_launch.notify_one();
+        while (s->completed_through < s->last_ticket) s->cv_done.wait(lk);
+        s->stop = true;
+    }
+    s->cv_launch.notify_all(); s->cv_complete.notify_all();
+    s->launcher.join(); s->completer.join();
+    (void)hipSetDevice(s->dev);
+    (void)hipStreamSynchronize(s->gs); (void)hipStreamSynchronize(s->hs);
+    free_stream(s);
+}
+
+extern "C" const char* mbls_stream_last_error(mbls_stream* s) { return s ? s->err : "null stream"; }
+
+extern "C" int mbls_stream_submit_device(mbls_stream* s, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* h_msg_offsets,
+                                         const uint8_t* d_pks, const uint32_t* d_key_idx, const uint32_t* h_pk_offsets, uint64_t n, uint32_t k,
+                                         uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream, uint64_t* ticket) {
+    return submit(s, false, d_sigs, d_msgs, msg_len, h_msg_offsets, d_pks, d_key_idx, h_pk_offsets, n, k, d_results, d_bitmap, d_status, stream, ticket);
+}
+
+extern "C" int mbls_stream_submit(mbls_stream* s, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* msg_offsets,
+                                  const uint8_t* pks, const uint32_t* key_idx, const uint32_t* pk_offsets, uint64_t n, uint32_t k,
+                                  uint8_t* results, uint32_t* status, uint64_t* ticket) {
+    return submit(s, true, sigs, msgs, msg_len, msg_offsets, pks, key_idx, pk_offsets, n, k, results, nullptr, status, nullptr, ticket);
+}
+
+extern "C" int mbls_stream_flush(mbls_stream* s) {
+    if (!s) return MBLS_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> g(s->mu);
+    s->flush_upto = s->last_ticket;
+    s->cv_launch.notify_one();
+    return MBLS_OK;
+}
+
+extern "C" int mbls_stream_wait(mbls_stream* s, uint64_t ticket) {
+    if (!s) return MBLS_ERR_ARGUMENT;
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (!ticket || ticket > s->last_ticket) return fail(s, MBLS_ERR_ARGUMENT, "unknown ticket %llu", (unsigned long long)ticket);
+    if (s->completed_through < ticket) {
+        if (s->flush_upto < ticket) { s->flush_upto = ticket; s->cv_launch.notify_one(); }     // its round launches now, whatever the policy
+        while (s->completed_through < ticket) s->cv_done.wait(lk);
+    }
+    return s->err_code && ticket >= s->err_ticket ? s->err_code : MBLS_OK;
+}
+
+extern "C" int mbls_stream_query(mbls_stream* s, uint64_t ticket) {
+    if (!s) return MBLS_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> g(s->mu);
+    if (!ticket || ticket > s->last_ticket) return fail(s, MBLS_ERR_ARGUMENT, "unknown ticket %llu", (unsigned long long)ticket);
+    if (s->completed_through < ticket) return MBLS_PENDING;
+    return s->err_code && ticket >= s->err_ticket ? s->err_code : MBLS_OK;
+}
+
+extern "C" int mbls_stream_get_stats(mbls_stream* s, mbls_stream_stats* out) {
+    if (!s || !out) return MBLS_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> g(s->mu);
+    *out = s->stats;
+    return MBLS_OK;
+}

@@ -1,0 +1,139 @@
+"""Verification stream (include/mbls.h, "verification stream"): calls of any size are packed into full-round launches of the device entries.
+
+    with VerifyStream(ctx, pk_format=PK_UNCOMPRESSED) as vs:
+        t = vs.submit_device(d_sigs, d_msgs, d_pks, n, k, d_results, msg_len=32)       # device tensors or pointers
+        h = vs.submit(sigs, msgs, pks, n, k, msg_len=32)                                # host bytes -> HostTicket
+        vs.wait(t); results, status = h.result()
+"""
+import ctypes as C
+from collections import deque
+
+from . import _native as N
+
+
+def _ptr(x):
+    """device pointer of a torch tensor, an int or None"""
+    if x is None:
+        return None
+    if hasattr(x, "data_ptr"):
+        return x.data_ptr()
+    return int(x)
+
+
+def _host(x, dtype):
+    """host input -> (object to keep alive, pointer): numpy arrays are passed in place, anything else is copied"""
+    import numpy as np
+    if isinstance(x, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(bytes(x) if not isinstance(x, bytes) else x, dtype=np.uint8)
+    else:
+        a = np.ascontiguousarray(np.asarray(x, dtype=dtype))
+    return a, (a.ctypes.data if a.size else None)
+
+
+def _offsets(seq, ctype):
+    if seq is None:
+        return None
+    return (ctype * len(seq))(*[int(v) for v in seq])
+
+
+class HostTicket:
+    """a host submit: result() waits for the call and returns (results bytes, status list)"""
+
+    def __init__(self, vs, ticket, res, st, n):
+        self.vs, self.ticket, self._res, self._st, self.n = vs, ticket, res, st, n
+
+    def result(self):
+        self.vs.wait(self.ticket)
+        return bytes(self._res)[:self.n], list(self._st)[:self.n]
+
+
+class VerifyStream:
+    """One stream on one context: mode STREAM_FAST_AGGREGATE_VERIFY / STREAM_VERIFY; keys as pk_format bytes, or indices into `table` (a KeyTable)."""
+
+    def __init__(self, ctx=None, mode=N.STREAM_FAST_AGGREGATE_VERIFY, pk_format=N.PK_UNCOMPRESSED, table=None, round_items=0, round_keys=0, round_msg_bytes=0,
+                 depth=0, policy=N.STREAM_WORK_CONSERVING):
+        self.ctx = ctx or N.default_context()          # held: the stream is destroyed before its context
+        self.table = table
+        self.indexed = table is not None
+        self._h = N.vp()
+        o = N.StreamOpts(round_items, round_keys, round_msg_bytes, depth, policy)
+        rc = N.lib().mbls_stream_create(self.ctx.handle, mode, pk_format, table.handle if table is not None else None, C.byref(o), C.byref(self._h))
+        if rc != N.OK:
+            raise N.MblsError(rc, "mbls_stream_create: " + self.ctx.last_error())
+        self._live = deque()                           # (ticket, buffers) kept alive until the call completes
+
+    def close(self):
+        if self._h:
+            N.lib().mbls_stream_destroy(self._h)
+            self._h = N.vp()
+            self._live.clear()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def last_error(self):
+        return N.lib().mbls_stream_last_error(self._h).decode()
+
+    def check(self, rc):
+        if rc != N.OK:
+            raise N.MblsError(rc, self.last_error())
+
+    def _keep(self, ticket, bufs):
+        while self._live and N.lib().mbls_stream_query(self._h, self._live[0][0]) != N.PENDING:
+            self._live.popleft()
+        self._live.append((ticket, bufs))
+
+    def submit_device(self, sigs, msgs, keys, n, k, results, msg_len=0, msg_offsets=None, pk_offsets=None, bitmap=None, status=None, stream=None):
+        """device buffers (torch tensors or pointers); keys = key bytes, or uint32 table indices for a key-table stream; offsets are host sequences;
+        stream: a torch stream or a raw hipStream_t -> ticket"""
+        mo, po = _offsets(msg_offsets, C.c_uint64), _offsets(pk_offsets, C.c_uint32)
+        hs = getattr(stream, "cuda_stream", stream)
+        t = C.c_uint64(0)
+        kp = _ptr(keys)
+        self.check(N.lib().mbls_stream_submit_device(self._h, _ptr(sigs), _ptr(msgs), msg_len, mo, None if self.indexed else kp, kp if self.indexed else None, po,
+                                                     n, k, _ptr(results), _ptr(bitmap), _ptr(status), hs, C.byref(t)))
+        self._keep(t.value, (mo, po, sigs, msgs, keys, results, bitmap, status))
+        return t.value
+
+    def submit(self, sigs, msgs, keys, n, k, msg_len=0, msg_offsets=None, pk_offsets=None):
+        """host bytes or numpy arrays (keys: key bytes, or uint32 table indices for a key-table stream; numpy arrays are read in place, when the
+        call's round launches) -> HostTicket"""
+        import numpy as np
+        (sa, sp), (ma, mp) = _host(sigs, np.uint8), _host(msgs, np.uint8)
+        ka, kp = _host(keys, np.uint32 if self.indexed else np.uint8)
+        mo, po = _offsets(msg_offsets, C.c_uint64), _offsets(pk_offsets, C.c_uint32)
+        res, st = N.outbuf(n), (C.c_uint32 * max(1, n))()
+        t = C.c_uint64(0)
+        self.check(N.lib().mbls_stream_submit(self._h, sp, mp, msg_len, mo, None if self.indexed else kp, kp if self.indexed else None, po, n, k, res, st, C.byref(t)))
+        self._keep(t.value, (sa, ma, ka, mo, po, res, st))
+        return HostTicket(self, t.value, res, st, n)
+
+    def flush(self):
+        self.check(N.lib().mbls_stream_flush(self._h))
+
+    def wait(self, ticket):
+        self.check(N.lib().mbls_stream_wait(self._h, ticket))
+        while self._live and self._live[0][0] <= ticket:
+            self._live.popleft()
+
+    def query(self, ticket):
+        """OK / PENDING (or the call's error code)"""
+        return N.lib().mbls_stream_query(self._h, ticket)
+
+    def stats(self):
+        s = N.StreamStats()
+        self.check(N.lib().mbls_stream_get_stats(self._h, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in N.StreamStats._fields_}
