@@ -24,27 +24,26 @@ def test_config3_fast_aggregate_verify_128_keys_both_formats(env):
     # configs[2] AS NAMED: 2^16 items x 128 public keys in the 96-byte form the headline is measured on (26 ms of GPU time; building and signing the batch
     # on the device takes longer); the 48-byte wire form at 2^13 items (its decompression is 8 x the work per item)
     torch, bench, N, ctx = env
-    import orc
     dev = torch.device("cuda:0")
     for fmt in (N.PK_UNCOMPRESSED, N.PK_COMPRESSED):
         n, k = (1 << 16) if fmt == N.PK_UNCOMPRESSED else (1 << 13), 128
         d_sigs, d_msgs, d_pks, expect = bench.build_inputs(ctx, dev, n, k, fmt, rank=3)
-        d_res = torch.zeros(n, dtype=torch.uint8, device=dev); d_bm = torch.zeros(n // 64, dtype=torch.int64, device=dev)
-        d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+        # outputs pre-filled with what no item may end with: a word the call leaves unwritten fails below
+        d_res = torch.full((n,), 7, dtype=torch.uint8, device=dev); d_bm = torch.full((n // 64,), -1, dtype=torch.int64, device=dev)
+        d_st = torch.full((n,), -1, dtype=torch.int32, device=dev)
         ctx.check(N.lib().mbls_fast_aggregate_verify_batch_device(ctx.handle, d_sigs.data_ptr(), d_msgs.data_ptr(), 32, None, d_pks.data_ptr(), fmt, None,
                                                                   n, k, d_res.data_ptr(), d_bm.data_ptr(), d_st.data_ptr(), None))
         torch.cuda.synchronize()
         assert torch.equal(d_res.cpu(), expect)
-        st = d_st.cpu().numpy()
-        bad = np.arange(7, n, 16)
-        want_flag = [0x40, 0x40, 0x02, 0x40, 0x08]     # msg bit, wrong key, sig not in G2, infinity sig (pairing fails), apk = infinity
-        for j, i in enumerate(bad[:40]):
-            assert st[i] & want_flag[j % 5], (i, j % 5, st[i])
-        m = 48
-        pkb = 96 if fmt == N.PK_UNCOMPRESSED else 48
-        got = orc.batch_fast_aggregate_verify(d_sigs[:m].cpu().numpy().tobytes(), d_msgs[:m].cpu().numpy().tobytes(),
-                                              d_pks[:m].cpu().numpy().tobytes(), m, k, fmt, nthreads=8)
-        assert got == [bool(x) for x in expect[:m].tolist()]
+        e = expect.numpy()
+        assert (helpers.bitmap_bits(d_bm, n) == e).all()                # every bit of the bitmap, not only the results array
+        # every rejected item carries its class's flag (msg bit, wrong key, infinity sig: pairing fails 0x40; sig not in G2 0x02; apk = infinity 0x08)
+        # and no undefined bit; accepted items carry none (so no 0x5F rejection bit)
+        helpers.check_status_classes(d_st.cpu().numpy(), e)
+        # the oracle on a sample over the whole batch: wave edges, the tail, 8+ items of every rejection class (the 48-byte leg decompresses 128 keys per item)
+        sel = sorted(set(helpers.sample_indices(n, seed=0x2c0 + fmt, count=1024 if fmt == N.PK_UNCOMPRESSED else 512)) | set(range(48)))
+        assert len(sel) >= 512
+        helpers.oracle_check_fav(d_sigs, d_msgs, d_pks, sel, k, fmt, expect, d_res)
 
 
 def test_config4_verify_multiple_2_14_sets_128_keys(env):
@@ -68,8 +67,54 @@ def test_config4_verify_multiple_2_14_sets_128_keys(env):
     d_sigs[n - 1] = torch.frombuffer(bytearray(probe), dtype=torch.uint8).to(dev)
     assert batch.verify_multiple_sets_device(*args, pk_format=N.PK_UNCOMPRESSED) is False
     d_sigs[n - 1] = keep
-    # small case against the oracle with the same blinding scalars
+    # five kinds of corruption at seeded positions over the whole range: each -> false, the restored input -> true again
+    rng = np.random.default_rng(0xc0f3)
+    pos = [int(x) for x in rng.choice(n - 1, size=5, replace=False)]
+    G2_INF = torch.frombuffer(bytearray(helpers.G2_INF), dtype=torch.uint8).to(dev)
+
+    def spoiled(i, kind):
+        if kind == "msg bit":
+            d_msgs[i, int(rng.integers(32))] ^= 1 << int(rng.integers(8))
+        elif kind == "swap":                                             # two neighbouring signatures swapped
+            d_sigs[[i, i + 1]] = d_sigs[[i + 1, i]].clone()
+        elif kind == "key":                                              # one key replaced by another pool key
+            j = int(rng.integers(k))
+            other = next(d_pks[(i + 1) % n, c].clone() for c in range(k) if not torch.equal(d_pks[(i + 1) % n, c], d_pks[i, j]))
+            d_pks[i, j] = other
+        elif kind == "zero scalar":
+            rands[i] = 0
+        elif kind == "infinity sig":
+            d_sigs[i] = G2_INF
+
+    for i, kind in zip(pos, ("msg bit", "swap", "key", "zero scalar", "infinity sig")):
+        keep = [t.clone() for t in (d_sigs, d_msgs, d_pks, rands)]
+        spoiled(i, kind)
+        assert batch.verify_multiple_sets_device(*args, pk_format=N.PK_UNCOMPRESSED) is False, (i, kind)
+        for t, v in zip((d_sigs, d_msgs, d_pks, rands), keep):
+            t.copy_(v)
+        assert batch.verify_multiple_sets_device(*args, pk_format=N.PK_UNCOMPRESSED) is True, (i, kind)
+    # 64 sets at random indices against the oracle with the same blinding scalars: aggregate keys summed on the oracle, valid -> true, one
+    # message bit flipped -> false, on both sides
     import orc
+    m = 64
+    sel = torch.from_numpy(np.sort(rng.choice(n, size=m, replace=False))).to(dev)
+    s_sigs, s_msgs, s_pks, s_rands = d_sigs[sel].contiguous(), d_msgs[sel].contiguous(), d_pks[sel].contiguous(), rands[sel].contiguous()
+    pk_rows = s_pks.cpu().numpy()
+    sets = []
+    for i in range(m):
+        e, apk = orc.aggregate_pks([pk_rows[i, j].tobytes() for j in range(k)])
+        assert e == 0
+        sets.append((orc.g2_from_compressed(s_sigs[i].cpu().numpy().tobytes())[1], apk, s_msgs[i].cpu().numpy().tobytes()))
+    rr = [int(x) for x in s_rands.cpu().tolist()]
+    sub = (s_sigs.data_ptr(), s_pks.data_ptr(), s_msgs.data_ptr(), s_rands.data_ptr(), m, k)
+    assert orc.verify_multiple(sets, rr) is True
+    assert batch.verify_multiple_sets_device(*sub, pk_format=N.PK_UNCOMPRESSED) is True
+    j = int(rng.integers(m))
+    s_msgs[j, 0] ^= 1
+    sets[j] = (sets[j][0], sets[j][1], s_msgs[j].cpu().numpy().tobytes())
+    assert orc.verify_multiple(sets, rr) is False
+    assert batch.verify_multiple_sets_device(*sub, pk_format=N.PK_UNCOMPRESSED) is False
+    # the first sets of the batch, as before (the device call on a prefix of the same buffers)
     m = 6
     sets = []
     apks, _ = batch.aggregate_public_keys_batch(d_pks[:m].cpu().numpy().tobytes(), m, k, pk_format=N.PK_UNCOMPRESSED)

@@ -537,28 +537,27 @@ def test_argument_validation(mb, N):
 def test_config5_shard_2_17_items_128_keys(N):
     """BASELINE configs[4]: 2^20 items over 8 GPUs = 2^17 items x 128 keys per GPU. One shard through the device entry point:
     bitmap and results by construction (sign -> aggregate -> verify round trip, every 16th item corrupted in five ways), status
-    classes, and a 64-item subsample pinned to the oracle."""
+    classes, and a seeded sample (the last wave, the round seam, 1 024 items over the whole range) pinned to the oracle."""
     import torch
     import bench
     ctx = N.default_context()
     dev = torch.device("cuda:0")
     n, k = 1 << 17, 128
     d_sigs, d_msgs, d_pks, expect = bench.build_inputs(ctx, dev, n, k, N.PK_UNCOMPRESSED, rank=6)
-    d_res = torch.zeros(n, dtype=torch.uint8, device=dev); d_bm = torch.zeros(n // 64, dtype=torch.int64, device=dev)
-    d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_res = torch.full((n,), 7, dtype=torch.uint8, device=dev); d_bm = torch.full((n // 64,), -1, dtype=torch.int64, device=dev)
+    d_st = torch.full((n,), -1, dtype=torch.int32, device=dev)
     ctx.check(N.lib().mbls_fast_aggregate_verify_batch_device(ctx.handle, d_sigs.data_ptr(), d_msgs.data_ptr(), 32, None, d_pks.data_ptr(), N.PK_UNCOMPRESSED, None,
                                                               n, k, d_res.data_ptr(), d_bm.data_ptr(), d_st.data_ptr(), None))
     torch.cuda.synchronize()
     assert torch.equal(d_res.cpu(), expect)
-    bits = d_bm.cpu().numpy().view(np.uint64)
-    unpacked = ((bits[:, None] >> np.arange(64, dtype=np.uint64)[None, :]) & np.uint64(1)).reshape(-1).astype(np.uint8)
-    assert (unpacked == expect.numpy()).all()
+    assert (helpers.bitmap_bits(d_bm, n) == expect.numpy()).all()
     st = d_st.cpu().numpy()
     assert (st[expect.numpy() == 1] & 0x5F == 0).all()                 # accepted items carry no rejection bit
-    sel = list(range(n - 64, n))                                        # the last wave of the last round of workgroups
-    sub = lambda t: t[sel].cpu().numpy().tobytes()
-    got = orc.batch_fast_aggregate_verify(sub(d_sigs), sub(d_msgs), sub(d_pks), 64, k, 1, nthreads=8)
-    assert got == [bool(x) for x in expect[sel].tolist()]
+    helpers.check_status_classes(st, expect.numpy())                    # ... nor any other; every rejected one its class's bit
+    # the oracle on a seeded sample: the last wave of the last round of workgroups, the round seam at 65 536, every rejection class
+    sel = helpers.sample_indices(n, seed=0x517)
+    assert set(range(n - 64, n)) | {65535, 65536, 65537} <= set(sel)
+    helpers.oracle_check_fav(d_sigs, d_msgs, d_pks, sel, k, N.PK_UNCOMPRESSED, expect, d_res)
 
 
 # ------------------------------------------------------------------------------------------------ seeded randomised sweep

@@ -32,8 +32,7 @@ def mb():
 @pytest.fixture(scope="module")
 def big():
     """20 480 items x 2 uncompressed keys, every fourth item one of the seven rejection classes; the oracle's verdict for every item"""
-    import os
-    nt = min(32, os.cpu_count() or 8)
+    nt = helpers.oracle_threads()
     b = helpers.make_batch(N_BIG, 2, fmt=1, seed=4242, pool_n=64, nthreads=nt)
     b.want = orc.batch_fast_aggregate_verify(b.sigs, b.msgs, b.pks, b.n, b.k, 1, nthreads=nt)
     assert b.want == b.expect
@@ -530,7 +529,7 @@ def test_a_remainder_on_the_wave_engine_never_grows_the_workspace_under_the_roun
     and table indices; the same with the workspace pre-reserved for what the passes' own workspace_items say (too small: the call grows it ONCE, up front)."""
     import torch
     from milagro_bls_amd import _native as N
-    nt = min(32, os.cpu_count() or 8)
+    nt = helpers.oracle_threads()
     n, k = 168, 32
     b = helpers.make_batch(n, k, fmt=1, seed=77, pool_n=64, nthreads=nt)
     want = orc.batch_fast_aggregate_verify(b.sigs, b.msgs, b.pks, b.n, b.k, 1, nthreads=nt)
