@@ -1189,6 +1189,9 @@ class _LanePair:
         return (self.ma, self.mb)
 
 
+FIXUPS = [0]                     # doubling fix-ups _blind_run has taken (one-lane runs), for tests that must be sure they drove that case
+
+
 def _blind_run(kind, r, ws_init, out_slots, ct=False, two_lane=False, skip_test=False):
     """the instruction streams of g1_blind_routine / g2_blind_routine in their control order (the skeleton's loops mirrored here: table
     of 1 P .. 8 P, top digit, sixteen windows of four doublings + one table addition), returning the words left in out_slots.
@@ -1214,6 +1217,7 @@ def _blind_run(kind, r, ws_init, out_slots, ct=False, two_lane=False, skip_test=
         pr = lambda nm: m.s[("pair", int(nm[2:nm.index(":")]))]
         if pr(t.M_H0) and pr(t.M_R0) and not pr(t.M_INF1) and not pr(t.M_INF2):
             m.run(pieces["fix"])
+            FIXUPS[0] += 1
     verdict = None
     if kind == "g2":
         m.run(pieces["s_start"])
@@ -1352,6 +1356,74 @@ def test_g1_blinding_routine():
         assert jac_affine(X, Y, Z) == M.g1_mul(pt, r), hex(r)
     out, _ = _blind_run("g1", 12345, {0: 0, 1: R384 % P, 2: 0}, range(3))
     assert out[2] == 0
+
+
+def _g1_blind_check(M, pt, scalars):
+    """g1_blind_routine on the affine model point pt (random Jacobian form) for every scalar against the model's [r] pt -> fix-ups taken"""
+    rng = random.Random(35)
+    ri = pow(R384, -1, P)
+    before = FIXUPS[0]
+    for r in scalars:
+        z = rng.randrange(1, P)
+        jac = (pt[0] * z * z % P, pt[1] * z * z * z % P, z)
+        out, _ = _blind_run("g1", r, {i: jac[i] * R384 % P for i in range(3)}, range(3))
+        X, Y, Z = [w * ri % P for w in out]
+        assert jac_affine(X, Y, Z) == M.g1_mul(pt, r), (pt, hex(r))
+    return FIXUPS[0] - before
+
+
+def test_g1_blinding_routine_with_keys_outside_g1():
+    """the same routine on keys a verify entry accepts unchecked (tests/edge_points.py): a point of order 3 -- its table 1 P .. 8 P is built through opposite
+    operands (3 P), an accumulator at infinity (4 P) and EQUAL operands (5 P = P + P, the doubling fix-up), and its windows keep meeting them --, the 3-torsion
+    point (0, 2) (x = 0), a point of order 11 and a G1 point shifted by one of order 3, over the edge scalars (digits -8, 0, 7, the carry digit, multiples of
+    the order) against the model's scalar multiplication. The order-3 runs must have taken the fix-up."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    M = _g2m()
+    import edge_points as E
+    tors = E.g1_torsion_points(random.Random(36), orders=(3, 11))
+    (_, t3, g), (_, t11, _g), (_, t0, _n) = tors[:3]
+    rs = E.edge_scalars()
+    assert M.g1_mul(t3, 3) is None and M.g1_mul(t11, 11) is None and t0 == (0, 2)
+    assert _g1_blind_check(M, t0, rs) > len(rs)                         # the table alone takes two (5 P, 8 P)
+    assert _g1_blind_check(M, t3, rs[0::3]) > 0
+    _g1_blind_check(M, t11, rs[1::3])
+    assert _g1_blind_check(M, M.g1_add(g, t3), rs[2::3]) == 0          # a point of order 3 r: no coincidence with 64-bit scalars
+
+
+def test_g2_tree_bodies_addition_cases():
+    """g2_tree_routine's bodies in its control order (start: the lane's own sum and the partner's, s71 bytes further on; add; the doubling fix-up where both
+    masks say equal operands; the epilogue's canonical store): general position, equal operands, opposite operands, either operand or both at infinity --
+    the sum left in the lane's slots against the model's g2_add. The fix-up runs for equal operands and for nothing else."""
+    M = _g2m()
+    rng = random.Random(37)
+    ri = pow(R384, -1, P)
+    full, pieces, _ = t.g2_tree_routine()
+    assert not any("scratch" in l or "buffer_" in l for l in full)
+    A = M.g2_mul(M.G2, rng.randrange(1, M.R)); Bp = M.g2_mul(M.G2, rng.randrange(1, M.R))
+    PARTNER = 4 * 37                                                     # the partner item's byte offset
+    cases = {"general": (A, Bp), "equal": (A, A), "opposite": (A, M.g2_neg(A)), "acc_inf": (None, Bp), "ad_inf": (A, None), "both_inf": (None, None)}
+    for case, (a, b) in cases.items():
+        def jac(pt):
+            if pt is None:
+                return [(rng.randrange(P), rng.randrange(P)), (rng.randrange(P), rng.randrange(P)), (0, 0)]
+            z = (rng.randrange(1, P), rng.randrange(P)); z2 = M.f2_sqr(z)
+            return [M.f2_mul(pt[0], z2), M.f2_mul(pt[1], M.f2_mul(z2, z)), z]
+        m = miller_machine(0)
+        for off, pt in ((0, jac(a)), (PARTNER, jac(b))):
+            for i, c in enumerate([x for co in pt for x in co]):
+                for j, w in enumerate(limbs(c * R384 % P)):
+                    m.mem[ws_addr(t.BL_OUT + i, j) + off] = w
+        m.s[71] = PARTNER
+        m.run(pieces["pro"]); m.run(pieces["start"]); m.run(pieces["add"])
+        pr = lambda nm: m.s[("pair", int(nm[2:nm.index(":")]))]
+        fix = bool(pr(t.M_H0) and pr(t.M_R0) and not pr(t.M_INF1) and not pr(t.M_INF2))
+        assert fix == (case == "equal"), case
+        if fix:
+            m.run(pieces["fix"])
+        m.run(pieces["epi"][:-1])
+        c = [ws_get(m, t.BL_OUT + i) * ri % P for i in range(6)]
+        assert all(ws_get(m, t.BL_OUT + i) < P for i in range(6))
+        assert jac2_affine(M, (c[0], c[1]), (c[2], c[3]), (c[4], c[5])) == M.g2_add(a, b), case
 
 
 def test_g2_blinding_routine():

@@ -198,24 +198,13 @@ def test_key_validate_outside_the_subgroup_vs_oracle(mb):
     """KeyValidate (reference src/keys.rs:176-185: subgroup_check_g1 = [r]P == O) on curve points outside G1: points of every prime order
     dividing the cofactor, G1 points shifted by them, random curve points -- the kernel decides by phi(P) == [-x^2]P, the oracle by [r]P."""
     import bls12_381 as M
+    import edge_points as E
     rnd = random.Random(77)
-    def curve_point():
-        while True:
-            x = rnd.randrange(M.P); y = M.fp_sqrt((x * x * x + 4) % M.P)
-            if y is not None:
-                return (x, y if rnd.getrandbits(1) else (-y) % M.P)
-    h = (M.X_ABS + 1) ** 2 // 3                                      # G1 cofactor (x - 1)^2 / 3, x = -X_ABS
-    assert h * M.R == M.P + 1 - (-M.X_ABS + 1)                      # #E(Fp) = p + 1 - t, t = x + 1
+    curve_point = lambda: E.curve_point(rnd)
+    h = E.G1_COFACTOR                                                # (x - 1)^2 / 3, x = -X_ABS
     pts = []
-    for ell in (3, 11, 10177, 859267, 52437899):
-        assert h % ell == 0
-        for _ in range(2):
-            t = None
-            while t is None:
-                t = M.g1_mul(curve_point(), h * M.R // (ell if ell == 3 else ell * ell))   # E[ell] is rational for ell | x - 1, ell != 3
-            g = M.g1_mul(M.G1, rnd.randrange(1, M.R))
-            pts += [t, M.g1_add(g, t), M.g1_add(M.g1_mul(t, 2), g)]
-    pts.append((0, 2)); pts.append((0, M.P - 2))                     # the 3-torsion points with x = 0
+    for ell, t, g in E.g1_torsion_points(rnd, per_order=2):          # two points of each prime order dividing h, then (0, 2) and (0, p - 2)
+        pts += [t] if g is None else [t, M.g1_add(g, t), M.g1_add(M.g1_mul(t, 2), g)]
     pts += [curve_point() for _ in range(96)]
     pts += [M.g1_mul(M.G1, rnd.randrange(1, M.R)) for _ in range(24)]
     pts += [M.g1_mul(curve_point(), h) for _ in range(8)]            # cofactor-cleared: in G1
