@@ -438,6 +438,46 @@ int mbls_verify_multiple_partial_device(mbls_ctx* ctx, const uint8_t* d_sigs96, 
 int mbls_verify_multiple_finish_device(mbls_ctx* ctx, const uint8_t* d_partials, uint64_t n_partials, uint8_t* d_result, uint32_t* d_status,
                                        void* stream);
 
+/* MANY verify_multiple BATCHES IN ONE CALL. A consensus client calls verify_multiple_aggregate_signatures once per SMALL batch (one block's sets, one gossip
+ * batch), and every entry above answers one bool per call -- a call is a latency chain of a few milliseconds whatever its size. These entries take B batches
+ * over n_sets sets laid out back to back -- batch b owns the sets [batch_offsets[b], batch_offsets[b+1]) (n_batches + 1 offsets starting at 0) or
+ * sets_per_batch each when the table is NULL (n_sets must then be n_batches x sets_per_batch) -- and answer per batch:
+ *   results[b] = exactly what mbls_verify_multiple_aggregate_signatures returns for batch b's sets with batch b's scalars (an empty batch: 1);
+ *   status[b] (optional) = the status word mbls_verify_multiple_aggregate_signatures_device writes for that batch (the OR of its sets' MBLS_ST_* bits; an empty
+ *     batch: 0), PLUS MBLS_ST_PAIRING_FAILED exactly where the pairing check itself is what rejects the batch: results[b] = 0 and none of the rejecting bits
+ *     (MBLS_ST_BAD_SIG_ENCODING, MBLS_ST_SIG_NOT_IN_G2, MBLS_ST_BAD_PK_ENCODING, MBLS_ST_BAD_MSG_RANGE, MBLS_ST_BAD_SCALAR) is set. (The one-batch entries
+ *     report a failed pairing check through the bool only.)
+ * No value crosses a batch boundary -- not a signature sum, not a product, not a status bit: a bad batch rejects itself and nothing else. The per-set work is
+ * the one-batch entries' (one lane per set); the sum of a batch's blinded signatures and the product of its pairings are per-batch trees, the B (S_b, -G1)
+ * pairs ride the sets' Miller launch, and every batch gets its own final exponentiation. n_batches = 0 (with n_sets = 0): MBLS_OK, nothing written.
+ * d_rands / rands: one NONZERO scalar per set (see above); NULL is MBLS_ERR_ARGUMENT, a zero scalar rejects its batch (MBLS_ST_BAD_SCALAR).
+ * The *_device forms ONLY ENQUEUE and order their use of the workspace against other calls like their neighbours. Keys per set: d_apks96 (one 96-byte aggregate key
+ * per set) or, when that is NULL, wire-format keys d_pks / pk_format / d_pk_offsets / k as in mbls_verify_multiple_sets_device; the indexed form names them in a
+ * resident key table as mbls_verify_multiple_sets_indexed_device does. Messages: msg_len bytes each or through d_msg_offsets (n_sets + 1 entries). A DEVICE-SIDE
+ * batch table is not seen by the host: a range that runs backwards or ends beyond n_sets, and every range that shares a set with another, rejects the batches
+ * involved (MBLS_ST_BAD_PK_ENCODING in their words) and never becomes a read outside the call's buffers; batches with sound ranges of their own are not touched.
+ * Workspace: n_sets + 2 n_batches items (2 n_sets for calls of at most half a round, if that is more); mbls_ctx_reserve beforehand keeps allocation out of the call. */
+int mbls_verify_multiple_batches_device(mbls_ctx* ctx, const uint8_t* d_sigs96, const uint8_t* d_apks96, const uint8_t* d_pks, int pk_format,
+                                        const uint32_t* d_pk_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_msg_offsets,
+                                        const uint64_t* d_rands, uint64_t n_sets, const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches,
+                                        uint8_t* d_results, uint32_t* d_status, void* stream);
+int mbls_verify_multiple_batches_indexed_device(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* d_sigs96, const uint32_t* d_key_idx, const uint32_t* d_offsets,
+                                                uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_msg_offsets, const uint64_t* d_rands,
+                                                uint64_t n_sets, const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint8_t* d_results,
+                                                uint32_t* d_status, void* stream);
+/* host buffers (aggregate keys, as mbls_verify_multiple_aggregate_signatures); the tables are validated on the host: batch_offsets must start at 0, be
+ * non-decreasing and end at n_sets, msg_offsets as everywhere -- MBLS_ERR_ARGUMENT otherwise, nothing enqueued */
+int mbls_verify_multiple_batches(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* msg_offsets,
+                                 const uint64_t* rands, uint64_t n_sets, const uint32_t* batch_offsets, uint32_t sets_per_batch, uint64_t n_batches,
+                                 uint8_t* results, uint32_t* status);
+/* The reference's order (see mbls_verify_multiple_aggregate_signatures_rng), generalised: the signatures of ALL batches are decoded and tested first, the host reads
+ * the verdicts, and `draw` is called AT MOST ONCE for, batch after batch in order, the scalars of the sets in front of that batch's first signature outside G2 (all
+ * of the batch's sets when there is none) -- the sequence of draws n_batches consecutive reference calls sharing one generator would make, handed out in set
+ * order. No second subgroup test afterwards. results[b] as above. */
+int mbls_verify_multiple_batches_rng(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* msg_offsets,
+                                     uint64_t n_sets, const uint32_t* batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint8_t* results,
+                                     mbls_scalar_source draw, void* user);
+
 /* ---- batch helpers used to build inputs and caches on the device ---- */
 /* n x PublicKey::from_bytes[_unchecked] / from_uncompressed_bytes: errs[i] = MBLS_OK / MBLS_ERR_* per key */
 int mbls_pk_decode_batch(mbls_ctx* ctx, const uint8_t* in, int in_format, int validate, uint64_t n, uint8_t* out96, uint8_t* errs);

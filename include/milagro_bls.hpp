@@ -8,6 +8,7 @@
 //     sig.verify(msg, &pk) -> bool                       sig.verify(msg, pk) -> bool
 //     AggregateSignature::fast_aggregate_verify(..)      same
 //     AggregateSignature::verify_multiple_aggregate_signatures(rng, iter)   same, rng = any callable returning uint8_t
+//     (one call of it per batch, batch after batch)      AggregateSignature::verify_multiple_aggregate_signatures_batches(rng, batches) -> vector<bool>, ONE call
 //
 // Every curve / pairing operation runs in the HIP kernels; there is no CPU fallback: constructing the first object without a
 // GPU throws DeviceError. The only host arithmetic is SecretKey::key_generate (HKDF-SHA-256 + one reduction mod r), which the
@@ -270,6 +271,39 @@ struct AggregateSignature {
         const bool ok = mbls_verify_multiple_aggregate_signatures_rng(detail::ctx(), sigs.data(), apks.data(), msgs.data(), 0, moff.data(), sets.size(), draw, &u) == 1;
         if (u.err) std::rethrow_exception(u.err);
         return ok;
+    }
+    // Not in the reference: what verify_multiple_aggregate_signatures(rng, batch) returns for every batch of `batches`, called once per batch in order -- as ONE
+    // call (mbls_verify_multiple_batches_rng), for about the cost of one such call. One bool per batch; a bad batch rejects itself and nothing else. The scalars
+    // are drawn in the order those calls would draw them (for every batch, the sets in front of its first signature outside G2): rng is left where they leave it.
+    template <typename Rng>
+    static std::vector<bool> verify_multiple_aggregate_signatures_batches(
+            Rng&& rng, const std::vector<std::vector<std::tuple<const AggregateSignature*, const AggregatePublicKey*, Bytes>>>& batches) {
+        std::vector<bool> out;
+        if (batches.empty()) return out;
+        Bytes sigs, apks, msgs; std::vector<uint64_t> moff{0}; std::vector<uint32_t> boff{0};
+        for (auto& b : batches) {
+            for (auto& s : b) {
+                sigs.insert(sigs.end(), std::get<0>(s)->point.begin(), std::get<0>(s)->point.end());
+                apks.insert(apks.end(), std::get<1>(s)->point.begin(), std::get<1>(s)->point.end());
+                msgs.insert(msgs.end(), std::get<2>(s).begin(), std::get<2>(s).end());
+                moff.push_back(msgs.size());
+            }
+            boff.push_back(uint32_t(moff.size() - 1));
+        }
+        using R = typename std::remove_reference<Rng>::type;
+        struct src { R* rng; std::exception_ptr err; } u{&rng, nullptr};
+        mbls_scalar_source draw = [](void* user, uint64_t* o, uint64_t count) {
+            src* p = static_cast<src*>(user);
+            try { for (uint64_t i = 0; i < count; i++) o[i] = draw_scalar(*p->rng); }
+            catch (...) { p->err = std::current_exception(); for (uint64_t i = 0; i < count; i++) o[i] = 0; }        // never unwind through the C frames
+        };
+        Bytes res(batches.size(), 0);
+        const int rc = mbls_verify_multiple_batches_rng(detail::ctx(), sigs.data(), apks.data(), msgs.data(), 0, moff.data(), moff.size() - 1, boff.data(), 0,
+                                                        batches.size(), res.data(), draw, &u);
+        if (u.err) std::rethrow_exception(u.err);
+        detail::check(rc);
+        for (uint8_t r : res) out.push_back(r == 1);
+        return out;
     }
     // the same check with the sets cut into one shard per device of a multi-device handle (mbls_multi_create): same bool, same RNG order, ONE call
     // (mbls_multi_verify_multiple_aggregate_signatures_rng: every device tests its shard's signatures first, the scalars are asked for once)

@@ -329,6 +329,49 @@ class AggregateSignature:
             raise failed[0]
         return ok
 
+    @staticmethod
+    def verify_multiple_aggregate_signatures_batches(rng, batches):
+        """Not in the reference: what calling verify_multiple_aggregate_signatures(rng, batch) once per batch, in order, returns -- as ONE call on the GPU
+        (mbls_verify_multiple_batches_rng), which costs about what one such call costs. `batches`: an iterable of iterables of
+        (signature, aggregate_public_key, message). Returns list[bool], one per batch; a bad batch rejects itself and nothing else. The scalars are drawn as
+        above and in the order the per-batch calls would draw them (for every batch, the sets in front of its first signature outside G2), so `rng` is left
+        exactly where those calls would leave it."""
+        batches = [list(b) for b in batches]
+        if not batches:
+            return []
+        sets = [s for b in batches for s in b]
+        boffs = [0]
+        for b in batches:
+            boffs.append(boffs[-1] + len(b))
+        failed = []
+
+        def draw(_user, out, count):                    # src/aggregates.rs:280-287
+            try:
+                for i in range(count):
+                    r = 0
+                    while r == 0:
+                        v = int.from_bytes(bytes(rng.getrandbits(8) for _ in range(8)), "big", signed=True)
+                        r = abs(v) & 0xFFFFFFFFFFFFFFFF
+                    out[i] = r
+            except BaseException as e:                  # an exception must not unwind through the C frames: the batches fail, the error is raised afterwards
+                failed.append(e)
+                for i in range(count):
+                    out[i] = 0
+        offs = [0]
+        for s in sets:
+            offs.append(offs[-1] + len(s[2]))
+        moff = (C.c_uint64 * len(offs))(*offs)
+        boff = (C.c_uint32 * len(boffs))(*boffs)
+        res = N.outbuf(len(batches))
+        cb = N.SCALAR_SOURCE(draw)
+        ctx = _ctx()
+        rc = N.lib().mbls_verify_multiple_batches_rng(ctx.handle, N.cbuf(b"".join(s[0].point for s in sets)), N.cbuf(b"".join(s[1].point for s in sets)),
+                                                      N.cbuf(b"".join(bytes(s[2]) for s in sets)), 0, moff, len(sets), boff, 0, len(batches), res, cb, None)
+        if failed:
+            raise failed[0]
+        ctx.check(rc)
+        return [bool(x) for x in bytes(res)[:len(batches)]]
+
     @classmethod
     def from_bytes(cls, data):
         out = N.outbuf(96)

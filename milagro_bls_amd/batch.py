@@ -273,3 +273,37 @@ def multi_fast_aggregate_verify_batch_indexed(mctx, mtable, sigs, msgs, key_idx,
     mctx.check(N.lib().mbls_multi_fast_aggregate_verify_batch_indexed(mctx.handle, mtable.handle, N.cbuf(sigs), N.cbuf(msgs), msg_len, _moff(msg_offsets),
                                                                       idx, off, n, k, res, st))
     return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
+
+
+def _boff(batch_offsets):
+    return None if batch_offsets is None else (C.c_uint32 * len(batch_offsets))(*batch_offsets)
+
+
+def verify_multiple_batches(sigs, apks, msgs, rands, n_sets, n_batches, batch_offsets=None, sets_per_batch=0, msg_len=32, msg_offsets=None, ctx=None):
+    """n_batches x verify_multiple_aggregate_signatures (reference src/aggregates.rs:261-316) in ONE call (mbls_verify_multiple_batches): the sets of all
+    batches back to back, batch b owning sets [batch_offsets[b], batch_offsets[b+1]) or sets_per_batch each; host buffers (signatures 96 B, decoded aggregate
+    keys 96 B, messages, one nonzero 64-bit scalar per set). Returns (results: list[bool], status: list[int]), one entry per batch."""
+    ctx = ctx or _c()
+    res = N.outbuf(max(1, n_batches))
+    st = (C.c_uint32 * max(1, n_batches))()
+    r = None if rands is None else (C.c_uint64 * max(1, n_sets))(*rands)
+    ctx.check(N.lib().mbls_verify_multiple_batches(ctx.handle, N.cbuf(sigs), N.cbuf(apks), N.cbuf(msgs), msg_len, _moff(msg_offsets), r, n_sets,
+                                                   _boff(batch_offsets), sets_per_batch, n_batches, res, st))
+    return [bool(x) for x in bytes(res)[:n_batches]], list(st)[:n_batches]
+
+
+def verify_multiple_batches_device(d_sigs, d_msgs, d_rands, n_sets, n_batches, d_results, d_status=None, d_apks=None, d_pks=None, k=0, pk_format=N.PK_COMPRESSED,
+                                   d_pk_offsets=None, msg_len=32, d_msg_offsets=None, d_batch_offsets=None, sets_per_batch=0, stream=None, ctx=None):
+    """The same over device buffers (raw device pointers / ints): keys as one aggregate key per set (d_apks) or wire-format keys (d_pks, k or d_pk_offsets).
+    Enqueues only: n_batches result bytes at d_results, n_batches status words at d_status (optional)."""
+    ctx = ctx or _c()
+    ctx.check(N.lib().mbls_verify_multiple_batches_device(ctx.handle, d_sigs, d_apks, d_pks, pk_format, d_pk_offsets, k, d_msgs, msg_len, d_msg_offsets, d_rands,
+                                                          n_sets, d_batch_offsets, sets_per_batch, n_batches, d_results, d_status, stream))
+
+
+def verify_multiple_batches_indexed_device(table, d_sigs, d_key_idx, d_msgs, d_rands, n_sets, n_batches, d_results, d_status=None, k=0, d_offsets=None, msg_len=32,
+                                           d_msg_offsets=None, d_batch_offsets=None, sets_per_batch=0, stream=None, ctx=None):
+    """The same over sets named by indices into a resident KeyTable (the deployment's form). Enqueues only."""
+    ctx = ctx or table.ctx
+    ctx.check(N.lib().mbls_verify_multiple_batches_indexed_device(ctx.handle, table.handle, d_sigs, d_key_idx, d_offsets, k, d_msgs, msg_len, d_msg_offsets, d_rands,
+                                                                  n_sets, d_batch_offsets, sets_per_batch, n_batches, d_results, d_status, stream))

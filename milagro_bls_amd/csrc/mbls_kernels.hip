@@ -19,6 +19,7 @@
 #include <unistd.h>
 #include "mbls_ops.h"
 #include "mbls_coop.h"
+#include "mbls_vmb.h"
 #include "../../include/mbls.h"
 
 // The product library exists only with the generated routines: the host side below selects kernels (the fused subgroup verdict of
@@ -499,6 +500,84 @@ __global__ void MBLS_LB k_f12_seg_gather(mbls_ws ws, const uint32_t* off, const 
 __global__ void MBLS_LB k_status_or(const uint32_t* status, uint64_t n, uint32_t* out) {
     uint64_t i = gid(); uint32_t v = (i < n) ? status[i] : 0;
     if (__ballot(v != 0)) { if (v) atomicOr(out, v); }
+}
+// ---- many verify_multiple batches in one call (mbls_verify_multiple_batches*; reference src/aggregates.rs:261-316, B calls at once). Workspace items: [0, n)
+// the sets of all batches back to back (batch b owns [off[b], off[b+1]) or k each), [n, n + B) the (S_b, -G1) pairs, [n + B, n + 2 B) staging. The segment rules
+// -- who takes which partner, who owns what, what a faulty table turns into -- are mbls_vmb.h's (host-testable).
+// set j -> the batch that owns it (ragged layouts; one lane per batch claims the sets of its range, a faulty range claims nothing: vmb_range, vmb_claim)
+__global__ void MBLS_LB k_vmb_set_map(const uint32_t* off, uint64_t B, uint64_t n, uint32_t* map) {
+    const uint64_t b = gid(); if (b >= B) return;
+    uint64_t lo, hi;
+    if (!vmb_range(off, 0, n, b, &lo, &hi)) return;
+    for (uint64_t j = lo; j < hi; j++) {
+        const uint32_t found = atomicCAS(map + j, MBLS_VMB_NO_OWNER, (uint32_t)b);
+        if (found != MBLS_VMB_NO_OWNER) atomicExch(map + j, vmb_claim(found, (uint32_t)b));
+    }
+}
+// One level of the per-batch sums of the blinded signatures (slot S): the twin of k_f12_seg_tree_d on the generated G2 addition; lanes without a partner at this
+// level return before the routine.
+__global__ void MBLS_LB k_g2_seg_tree_d(mbls_ws ws, const uint32_t* map, const uint32_t* off, uint32_t k, uint64_t B, uint64_t n, uint64_t half) {
+#if MBLS_DEVICE_ASM
+    __shared__ uint32_t spill[154 * 64];
+    const uint64_t j = gid();
+    uint64_t lo, hi;
+    if (!vmb_owner_range(map, off, k, B, n, j, &lo, &hi)) return;
+    if (!vmb_takes_partner(j, lo, hi, half)) return;
+    tree_level_d_call<true>(ws, j, half, (MBLS_LDS uint32_t*)spill, threadIdx.x);
+#endif
+}
+// batch b's sum S_b (slot S at the head of its range; infinity for an empty or faulty range) -> the operands of its (S_b, -G1) pair in the slots the one-pair
+// Miller kernels read, item n + b: H = S_b (Jacobian), APK = -G1 -- so that the B signature pairs ride the sets' Miller launch (k_sigpair_setup's role)
+__global__ void MBLS_LB k_vmb_sigpair_setup(mbls_ws ws, const uint32_t* off, uint32_t k, uint64_t B, uint64_t n) {
+    const uint64_t b = gid(); if (b >= B) return;
+    uint64_t lo, hi; (void)vmb_range(off, k, n, b, &lo, &hi);
+    const bool some = hi > lo;
+    const uint64_t it = some ? lo : 0;                            // (item 0 exists in every workspace: an empty range reads it and keeps nothing)
+    g2j o; g2_set_inf(&o);
+    g2j s; s.x = ws_ld2(ws, MBLS_SLOT_S, it); s.y = ws_ld2(ws, MBLS_SLOT_S + 2, it); s.z = ws_ld2(ws, MBLS_SLOT_S + 4, it);
+    s.x = fp2_select(some, s.x, o.x); s.y = fp2_select(some, s.y, o.y); s.z = fp2_select(some, s.z, o.z);
+    ws_st2(ws, MBLS_SLOT_H, n + b, s.x); ws_st2(ws, MBLS_SLOT_H + 2, n + b, s.y); ws_st2(ws, MBLS_SLOT_H + 4, n + b, s.z);
+    ws_st(ws, MBLS_SLOT_APK, n + b, fp_load_const(MBLS_G1_X)); ws_st(ws, MBLS_SLOT_APK + 1, n + b, fp_load_const(MBLS_G1_NEG_Y)); ws_st(ws, MBLS_SLOT_APK + 2, n + b, fp_one());
+}
+// the per-batch status fold, one lane per SET: set j's word is ORed into its owner's, and (ragged layouts) the owner counts the sets it owns by the map
+__global__ void MBLS_LB k_vmb_status_fold(const uint32_t* map, const uint32_t* off, uint32_t k, uint64_t B, uint64_t n, const uint32_t* st_set, uint32_t* st_batch, uint32_t* owned) {
+    const uint64_t j = gid();
+    uint64_t lo, hi;
+    if (!vmb_owner_range(map, off, k, B, n, j, &lo, &hi)) return;
+    const uint64_t b = off ? map[j] : j / k;
+    if (off) atomicAdd(owned + b, 1u);
+    const uint32_t st = st_set[j];
+    if (st) atomicOr(st_batch + b, st);
+}
+// the gather multiplies nothing, it collects: batch b's product from the head of its range -> staging item n + B + b (1 for an empty range), and the ownership
+// verdict: a faulty range, or a range of which another batch owns a set (vmb_owns_all), rejects the batch (MBLS_ST_BAD_PK_ENCODING, as k_f12_seg_gather)
+__global__ void MBLS_LB k_vmb_gather(mbls_ws ws, const uint32_t* off, uint32_t k, uint64_t B, uint64_t n, uint32_t* st_batch, const uint32_t* owned) {
+    const uint64_t b = gid(); if (b >= B) return;
+    uint64_t lo, hi;
+    uint32_t st = 0;
+    if (!vmb_range(off, k, n, b, &lo, &hi)) st |= MBLS_ST_BAD_PK_ENCODING;
+    if (!vmb_owns_all(off ? owned : nullptr, b, lo, hi)) st |= MBLS_ST_BAD_PK_ENCODING;
+    fp12 f; fp12_set_one(&f);
+    const fp* one = &f.c0.c0.c0;
+    const bool some = hi > lo;
+    for (int t = 0; t < 12; t++) ws_st(ws, MBLS_SLOT_F + t, n + B + b, some ? ws_ld(ws, MBLS_SLOT_F + t, lo) : one[t]);
+    if (st) atomicOr(st_batch + b, st);
+}
+// the tail: one final exponentiation per batch with verify_multiple's reject mask (lane_final<true>: the body of k_final / k_final2, the fold of final_fold_batch)
+__global__ void MBLS_LB k_vmb_final(mbls_ws ws, uint32_t* status, uint8_t* results, uint64_t n) {
+    __shared__ uint32_t accstore[154 * 64];
+    uint64_t i = gid(); if (i >= n) return;
+    uint32_t st = status[i]; uint8_t r; lane_final<true>(ws, i, &st, &r, (MBLS_LDS uint32_t*)accstore, threadIdx.x, true); status[i] = st; results[i] = r;
+}
+__global__ void MBLS_LB k_vmb_final2(mbls_ws ws, uint32_t* status, uint8_t* results, uint64_t n) {
+    __shared__ uint32_t accstore[154 * 64];
+    const uint64_t t = gid(); if (t >= 2 * n) return;
+    const uint64_t i = t >> 1;
+#if MBLS_DEVICE_ASM
+    uint32_t st = status[i]; uint8_t r;
+    lane_final2<true>(ws, i, &st, &r, (MBLS_LDS uint32_t*)accstore, threadIdx.x);
+    if ((t & 1) == 0) { status[i] = st; results[i] = r; }
+#endif
 }
 // verify_multiple over several devices ("one exchange step"): what one shard contributes is the product of its
 // sets' Miller values (slot F of item 0), its sum of blinded signatures (slot S of item 0) and the OR of its status words -- a
@@ -2469,6 +2548,203 @@ extern "C" int mbls_verify_multiple_aggregate_signatures_rng(mbls_ctx* c, const 
     c->ws_pending = false;
     if (g.dout.down(&r, 1) != hipSuccess) return 0;
     return r;
+}
+
+// ---- B independent verify_multiple batches in ONE call (include/mbls.h, mbls_verify_multiple_batches*): what B consecutive calls of the entries above return,
+// one bool and one status word per batch. The per-set work (key sum, [r] apk, decode + subgroup test + [r] sig, message phase, one-pair Miller loop) is one lane
+// per set and knows nothing of batches; what ties a batch together -- the sum of its blinded signatures, the product of its Miller values, its status word, its
+// final exponentiation -- runs segmented: per-batch trees over the sets (k_g2_seg_tree_d, k_f12_seg_tree_d; rules in mbls_vmb.h), the B (S_b, -G1) pairs as
+// workspace items [n, n + B) inside the sets' Miller launch, one final exponentiation per batch with verify_multiple's reject mask (k_vmb_final / k_vmb_final2).
+// No value crosses a batch boundary. Routing by size with verify_multiple_impl's thresholds. Every fallible set-up step (reserve, staging, table_acquire) comes
+// before the first kernel is enqueued on a side stream. Enqueues only.
+// longest: the longest range of the table when the host has seen it (0: a device-side table -- any batch may hold every set, the trees get every level)
+// sigs_resident / hash_enqueued: as in verify_multiple_impl (the _rng entry's second half)
+struct vmb_keys {
+    const uint8_t* d_apks = nullptr; const uint8_t* d_pks = nullptr; int pk_format = MBLS_PK_UNCOMPRESSED; const uint32_t* d_pk_offsets = nullptr; uint32_t k = 0;
+    const mbls_keytable* tab = nullptr; const uint32_t* d_idx = nullptr;
+};
+static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands,
+        uint64_t n, const uint32_t* d_boff, uint32_t spb, uint64_t B, uint64_t longest, uint8_t* d_results, uint32_t* d_status, void* stream,
+        bool sigs_resident = false, bool hash_enqueued = false) {
+    if (!c) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
+    if (!d_results) ARGFAIL(c, "null results");
+    if (n > 0xFFFFFFFEull || B > 0xFFFFFFFEull) ARGFAIL(c, "set and batch indices are 32-bit");
+    if (!d_boff && (uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch");
+    if (n && !d_rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
+    if (n && ((!d_sigs && !sigs_resident) || (!d_msgs && msg_len && !d_moff))) ARGFAIL(c, "null buffer");
+    if (n && !ks.tab && !ks.d_apks && !ks.d_pks) ARGFAIL(c, "null keys");
+    if (n && ks.tab && !ks.d_idx) ARGFAIL(c, "null key indices");
+    if (ks.tab && ks.tab->c != c) ARGFAIL(c, "key table belongs to another context");
+    if (!ks.tab && !ks.d_apks && ks.pk_format != MBLS_PK_COMPRESSED && ks.pk_format != MBLS_PK_UNCOMPRESSED) ARGFAIL(c, "pk_format");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const bool pair_hash = n && n <= c->split_max_items && 2 * n <= c->round_items;       // as verify_multiple_impl decides
+    int rc = mbls_ctx_reserve(c, vmb_workspace_items(n, B, pair_hash)); if (rc) return rc;
+    uint32_t* map = nullptr;
+    sbuf dmap(c, 9);
+    if (d_boff) { HIPCHK(c, dmap.alloc(4 * (n ? n : 1))); map = dmap.as<uint32_t>(); }
+    mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
+    mbls_ws wv = ws; wv.w += n;                                    // the batches' view: item b of wv = workspace item n + b
+    rc = ws_acquire(c, s); if (rc) return rc;
+    if (ks.tab) { rc = table_acquire(c, ks.tab, s); if (rc) return rc; }
+    uint32_t* st_set = c->d_status;                                // (cap >= n + 2 B words)
+    uint32_t* st_batch = d_status ? d_status : c->d_status + n;
+    uint32_t* owned = c->d_status + n + B;
+    if (n && !sigs_resident) HIPCHK(c, hipMemsetAsync(st_set, 0, 4 * n, s));          // (resident: cleared before k_sig, and the message phase may be writing its bits)
+    HIPCHK(c, hipMemsetAsync(c->d_status + n, 0, 8 * B, s));
+    if (d_status) HIPCHK(c, hipMemsetAsync(d_status, 0, 4 * B, s));
+    if (map) HIPCHK(c, hipMemsetAsync(map, 0xFF, 4 * (n ? n : 1), s));                // every entry the map kernel does not write reads as "no owner"
+    HIPCHK(c, hipMemsetAsync(d_results, 0, B, s));                 // false until the tail kernel has spoken (fail closed)
+    // the three chains side by side below half a round, as in verify_multiple_impl
+    const bool fork = n && 2 * n <= c->round_items;
+    hipStream_t s_sig = fork ? c->hs_b : s, s_msg = fork ? c->hs_c : s;
+    if (fork) { HIPCHK(c, hipEventRecord(c->hs_ev, s)); HIPCHK(c, hipStreamWaitEvent(s_sig, c->hs_ev, 0)); HIPCHK(c, hipStreamWaitEvent(s_msg, c->hs_ev, 0)); }
+    const bool hash_first = fork && !hash_enqueued;
+    if (hash_first) launch_hash(c, ws, d_msgs, msg_len, d_moff, st_set, n, s_msg, pair_hash);
+    if (n) {
+        if (ks.tab)
+            hipLaunchKernelGGL(k_aggregate_indexed_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)ks.tab->d_recs, ks.tab->size, ks.d_idx, ks.d_pk_offsets, ks.k, MBLS_MODE_VERIFY, st_set, n);
+        else if (!ks.d_apks)
+            launch_aggregate(ws, ks.d_pks, ks.d_pk_offsets, ks.k, ks.pk_format, MBLS_MODE_VERIFY, st_set, n, s);
+        hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (ks.tab || !ks.d_apks) ? (const uint8_t*)nullptr : ks.d_apks, d_rands, st_set, n);
+        if (map) hipLaunchKernelGGL(k_vmb_set_map, dim3(nblk(B)), dim3(WG), 0, s_sig, d_boff, B, n, map);
+        if (2 * n <= c->coop_max_items)      // small calls: the signature chain is what the call waits for -- two lanes per signature
+            hipLaunchKernelGGL(k_blind_sig2_d, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, st_set, n);
+        else
+            hipLaunchKernelGGL(k_blind_sig_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, st_set, n);
+        if (!longest) longest = d_boff ? n : spb;
+        for (uint64_t half = 1; half < longest; half *= 2)         // S_b: the per-batch sums of the blinded signatures, left at the head of each range
+            hipLaunchKernelGGL(k_g2_seg_tree_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, (const uint32_t*)map, d_boff, spb, B, n, half);
+        if (!(hash_enqueued && fork) && !hash_first) launch_hash(c, ws, d_msgs, msg_len, d_moff, st_set, n, s_msg, pair_hash);
+    }
+    if (fork) {
+        HIPCHK(c, hipEventRecord(c->hs_ev2, s_sig)); HIPCHK(c, hipEventRecord(c->hs_ev3, s_msg));
+        HIPCHK(c, hipStreamWaitEvent(s, c->hs_ev2, 0)); HIPCHK(c, hipStreamWaitEvent(s, c->hs_ev3, 0));
+    }
+    // the B signature pairs join the sets: one Miller loop per workspace item [0, n + B) (set up only now: the lane-pair message phase works on items [0, 2 n))
+    hipLaunchKernelGGL(k_vmb_sigpair_setup, dim3(nblk(B)), dim3(WG), 0, s, ws, d_boff, spb, B, n);
+    if (2 * (n + B) <= c->coop_max_items)
+        coop_run(c, COOP_MILLER1, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, n + B, (uint32_t*)nullptr, (uint8_t*)nullptr, COOP_RES_ITEM, s);
+    else
+        launch_miller_single(c, ws, n + B, s);
+    if (n) {
+        hipLaunchKernelGGL(k_vmb_status_fold, dim3(nblk(n)), dim3(WG), 0, s, (const uint32_t*)map, d_boff, spb, B, n, (const uint32_t*)st_set, st_batch, owned);
+        for (uint64_t half = 1; half < longest; half *= 2)         // the per-batch products of the sets' Miller values
+            hipLaunchKernelGGL(k_f12_seg_tree_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)map, d_boff, spb, B, n, half);
+    }
+    hipLaunchKernelGGL(k_vmb_gather, dim3(nblk(B)), dim3(WG), 0, s, ws, d_boff, spb, B, n, st_batch, (const uint32_t*)owned);
+    hipLaunchKernelGGL(k_f12_tree_d, dim3(nblk(B)), dim3(WG), 0, s, wv, 2 * B, B);      // batch b <- (its signature pair) x (its sets' product)
+    if (B <= c->split_max_items && 2 * B <= c->round_items) hipLaunchKernelGGL(k_vmb_final2, dim3(nblk(2 * B)), dim3(WG), 0, s, wv, st_batch, d_results, B);
+    else hipLaunchKernelGGL(k_vmb_final, dim3(nblk(B)), dim3(WG), 0, s, wv, st_batch, d_results, B);
+    HIPCHK(c, hipGetLastError());
+    return ws_release(c, s);
+}
+extern "C" int mbls_verify_multiple_batches_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_pks, int pk_format,
+        const uint32_t* d_pk_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n,
+        const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint8_t* d_results, uint32_t* d_status, void* stream) {
+    vmb_keys ks; ks.d_apks = d_apks;
+    if (!d_apks) { ks.d_pks = d_pks; ks.pk_format = pk_format; ks.d_pk_offsets = d_pk_offsets; ks.k = k; }
+    return vmb_impl(c, d_sigs, ks, d_msgs, msg_len, d_moff, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, 0, d_results, d_status, stream);
+}
+extern "C" int mbls_verify_multiple_batches_indexed_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx, const uint32_t* d_offsets,
+        uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n, const uint32_t* d_batch_offsets,
+        uint32_t sets_per_batch, uint64_t n_batches, uint8_t* d_results, uint32_t* d_status, void* stream) {
+    if (!c || !t) return MBLS_ERR_ARGUMENT;
+    vmb_keys ks; ks.tab = t; ks.d_idx = d_key_idx; ks.d_pk_offsets = d_offsets; ks.k = k;
+    return vmb_impl(c, d_sigs, ks, d_msgs, msg_len, d_moff, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, 0, d_results, d_status, stream);
+}
+// the host checks shared by the two host entries: the batch table (first 0, non-decreasing, last n) or the uniform count, the message table, the buffers
+static int vmb_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n,
+                          const uint32_t* boff, uint32_t spb, uint64_t B, const uint8_t* results, uint64_t* longest) {
+    if (!results) ARGFAIL(c, "null results");
+    if (n > 0xFFFFFFFEull || B > 0xFFFFFFFEull) ARGFAIL(c, "set and batch indices are 32-bit");
+    if (boff) { if (!vmb_offsets_ok(boff, B, n, longest)) ARGFAIL(c, "batch_offsets must start at 0, be non-decreasing and end at n_sets"); }
+    else { if ((uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch"); *longest = spb; }
+    if (moff && !msg_offsets_ok(moff, n)) ARGFAIL(c, "msg_offsets must be non-decreasing, messages below 2^32 bytes");
+    const size_t msg_total = moff ? (size_t)(moff[n] - moff[0]) : (size_t)msg_len * n;
+    if (n && (!sigs96 || !apks96 || (!msgs && msg_total))) ARGFAIL(c, "null buffer");
+    return MBLS_OK;
+}
+extern "C" int mbls_verify_multiple_batches(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        const uint64_t* rands, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, uint32_t* status) {
+    if (!c) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
+    uint64_t longest = 0;
+    int rc = vmb_host_check(c, sigs96, apks96, msgs, msg_len, moff, n, boff, spb, B, results, &longest); if (rc) return rc;
+    if (n && !rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t msg_first = moff ? moff[0] : 0;
+    const size_t msg_total = moff ? (size_t)(moff[n] - moff[0]) : (size_t)msg_len * n;
+    sbuf ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dbo(c, 5), dmo(c, 6), dres(c, 7), dst(c, 8);
+    HIPCHK(c, ds.up(sigs96, 96 * n)); HIPCHK(c, da.up(apks96, 96 * n)); HIPCHK(c, dm.up(msgs ? msgs + msg_first : nullptr, msg_total)); HIPCHK(c, dr.up(rands, 8 * n));
+    if (boff) HIPCHK(c, dbo.up(boff, 4 * (B + 1)));
+    if (moff) HIPCHK(c, dmo.up(moff, 8 * (n + 1)));
+    HIPCHK(c, dres.alloc(B)); HIPCHK(c, dst.alloc(4 * B));
+    vmb_keys ks; ks.d_apks = da.as<uint8_t>();
+    rc = vmb_impl(c, ds.as<uint8_t>(), ks, dm.as<uint8_t>() - msg_first, msg_len, moff ? dmo.as<uint64_t>() : nullptr, dr.as<uint64_t>(), n,
+                  boff ? dbo.as<uint32_t>() : nullptr, spb, B, longest ? longest : 1, dres.as<uint8_t>(), dst.as<uint32_t>(), c->hs_a);
+    if (rc) { vm_rng_drain(c); return rc; }
+    HIPCHK(c, hipStreamSynchronize(c->hs_a));
+    c->ws_pending = false;
+    HIPCHK(c, dres.down(results, B));
+    if (status) HIPCHK(c, dst.down(status, 4 * B));
+    return MBLS_OK;
+}
+// The reference's order, generalised to B batches: B consecutive reference calls sharing one generator test batch b's signatures one by one and draw a scalar
+// for every set in front of its first signature outside G2 (all of its sets when there is none), batch after batch (src/aggregates.rs:272-287). Here the
+// signatures of ALL batches are decoded and tested first (vm_rng_phase1), the host reads the verdicts, `draw` is asked ONCE for exactly that sequence of
+// scalars, and the rest runs without a second subgroup test (the points are in the slots). A batch with a bad signature is false through its status bits; its
+// sets behind the bad one never had a scalar drawn and get the scalar 1, which changes nothing (the batch is rejected whatever its pairing product is).
+extern "C" int mbls_verify_multiple_batches_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, mbls_scalar_source draw, void* user) {
+    if (!c) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
+    uint64_t longest = 0;
+    int rc = vmb_host_check(c, sigs96, apks96, msgs, msg_len, moff, n, boff, spb, B, results, &longest); if (rc) return rc;
+    if (n == 0) { memset(results, 1, B); return MBLS_OK; }                  // empty iterators: true, the generator untouched
+    if (!draw) ARGFAIL(c, "null scalar source");
+    std::vector<uint64_t> rands, drawn; std::vector<uint32_t> st;
+    try { rands.resize(n); drawn.resize(n); st.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
+    HIPCHK(c, hipSetDevice(c->device));
+    // everything that may allocate comes before the first kernel: the workspace of the WHOLE call (phase 1 alone would reserve less, and growing it later would
+    // lose the decoded signatures), the staging of the table, the results and the map
+    const bool pair_hash = n <= c->split_max_items && 2 * n <= c->round_items;
+    rc = mbls_ctx_reserve(c, vmb_workspace_items(n, B, pair_hash)); if (rc) return rc;
+    sbuf dbo(c, 5), dres(c, 7), dmap(c, 9);
+    if (boff) { HIPCHK(c, dbo.up(boff, 4 * (B + 1))); HIPCHK(c, dmap.alloc(4 * n)); }
+    HIPCHK(c, dres.alloc(B));
+    vm_rng_stage g(c);
+    rc = vm_rng_phase1(c, g, sigs96, apks96, msgs, msg_len, moff, n, 8, st.data()); if (rc) return rc;
+    uint64_t total = 0;
+    std::vector<uint64_t> reach;
+    try { reach.resize(B); } catch (...) { vm_rng_drain(c); ARGFAIL(c, "out of host memory"); }
+    for (uint64_t b = 0; b < B; b++) {
+        const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
+        uint64_t r = hi;
+        for (uint64_t i = lo; i < hi; i++) if (st[i] & (MBLS_ST_BAD_SIG_ENCODING | MBLS_ST_SIG_NOT_IN_G2)) { r = i; break; }
+        reach[b] = r - lo; total += r - lo;
+    }
+    if (total) draw(user, drawn.data(), total);
+    uint64_t pos = 0;
+    for (uint64_t b = 0; b < B; b++) {
+        const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
+        for (uint64_t i = lo; i < hi; i++) rands[i] = i - lo < reach[b] ? drawn[pos++] : 1;
+    }
+    hipError_t e = g.dr.up(rands.data(), 8 * n);
+    std::fill(rands.begin(), rands.end(), 0); std::fill(drawn.begin(), drawn.end(), 0);
+    if (e != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
+    vmb_keys ks; ks.d_apks = g.da.as<uint8_t>();
+    rc = vmb_impl(c, nullptr, ks, g.d_msgs, msg_len, g.d_moff, g.dr.as<uint64_t>(), n, boff ? dbo.as<uint32_t>() : nullptr, spb, B, longest ? longest : 1,
+                  dres.as<uint8_t>(), nullptr, c->hs_a, true, true);
+    if (rc) { vm_rng_drain(c); return rc; }
+    if (hipStreamSynchronize(c->hs_a) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
+    c->ws_pending = false;
+    HIPCHK(c, dres.down(results, B));
+    return MBLS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ several GPUs behind one handle

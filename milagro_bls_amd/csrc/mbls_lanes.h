@@ -407,11 +407,26 @@ MBLS_FN uint32_t lane_sig_verdict(const mbls_ws& ws, uint64_t i, uint64_t t_item
     const bool same = !fp2_is_zero(Z) & fp2_eq(fp2_mul(px, Z), X) & fp2_eq(fp2_mul(py, Z), fp2_neg(Y));      // psi(sig) = [x] sig = -[|x|] sig
     return (!same & !fp2_is_zero(qy)) ? MBLS_ST_SIG_NOT_IN_G2 : 0u;
 }
+// The verdict of ONE BATCH of verify_multiple (lane_final<true> / lane_final2<true>: mbls_verify_multiple_batches*, one lane or lane pair per batch). `status`
+// comes in as the OR of the batch's sets' words. A batch rejects on the batch mask -- the bits of mbls_coop.h's COOP_REJECT_BATCH: an undecodable member, a
+// signature outside G2, a bad message range, a ZERO SCALAR; NOT an infinite key or an empty key list, which the reference's loop multiplies in like any other
+// (src/aggregates.rs:289-301) -- or when the product of its pairings is not one. MBLS_ST_PAIRING_FAILED is added only where the pairing check is what rejects: no
+// rejecting bit set and the product not one (with a rejecting bit the product was never going to be checked by the reference, and says nothing).
+MBLS_FN void final_fold_batch(bool is_one, uint32_t* status, uint8_t* result) {
+    const uint32_t reject = MBLS_ST_BAD_SIG_ENCODING | MBLS_ST_SIG_NOT_IN_G2 | MBLS_ST_BAD_PK_ENCODING | MBLS_ST_BAD_MSG_RANGE | MBLS_ST_BAD_SCALAR;
+    uint32_t st = *status;
+    const bool bad = (st & reject) != 0;
+    if (!bad && !is_one) st |= MBLS_ST_PAIRING_FAILED;
+    *status = st;
+    *result = (bad || !is_one) ? 0 : 1;
+}
 #if MBLS_DEVICE_ASM && !defined(MBLS_NO_FP2_ASM)
 // two lanes per item (k_final2): both lanes come back with the same value; `result` / `status` as lane_final
+template <bool BATCH = false>
 MBLS_FN void lane_final2(const mbls_ws& ws, uint64_t i, uint32_t* status, uint8_t* result, MBLS_LDS uint32_t* ls, uint32_t lane) {
     fp12 f;
     final_exp_ws_d2(&f, ws.w, ws.stride, i, ls, lane);
+    if (BATCH) { final_fold_batch(fp12_is_one(&f), status, result); return; }
     uint32_t st = *status;
     if (!fp12_is_one(&f)) st |= MBLS_ST_PAIRING_FAILED;
     *status = st;
@@ -420,6 +435,7 @@ MBLS_FN void lane_final2(const mbls_ws& ws, uint64_t i, uint32_t* status, uint8_
     *result = (st & reject) ? 0 : 1;
 }
 #endif
+template <bool BATCH = false>
 MBLS_FN void lane_final(const mbls_ws& ws, uint64_t i, uint32_t* status, uint8_t* result, MBLS_LDS uint32_t* ls = nullptr, uint32_t lane = 0, bool use_lds = false) {
     fp12 f; fp2* c = &f.c0.c0;
 #if MBLS_DEVICE_ASM && !defined(MBLS_NO_FP2_ASM)
@@ -430,6 +446,7 @@ MBLS_FN void lane_final(const mbls_ws& ws, uint64_t i, uint32_t* status, uint8_t
         for (int s = 0; s < 6; s++) c[s] = ws_ld2(ws, MBLS_SLOT_F + 2 * s, i);
         final_exp(&f, &f);
     }
+    if (BATCH) { final_fold_batch(fp12_is_one(&f), status, result); return; }
     uint32_t st = *status;
     if (!fp12_is_one(&f)) st |= MBLS_ST_PAIRING_FAILED;
     *status = st;

@@ -71,6 +71,23 @@ extern "C" {
     fn mbls_verify_multiple_aggregate_signatures_rng(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
                                                      n: usize, draw: MblsScalarSource, user: *mut c_void) -> c_int;
     fn mbls_sig_check_batch(ctx: *mut MblsCtx, in96: *const u8, n: u64, errs: *mut u8, in_g2: *mut u8) -> c_int;
+    fn mbls_verify_multiple_batches(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
+                                    rands: *const u64, n_sets: u64, batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64, results: *mut u8,
+                                    status: *mut u32) -> c_int;
+    fn mbls_verify_multiple_batches_rng(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
+                                        n_sets: u64, batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64, results: *mut u8, draw: MblsScalarSource,
+                                        user: *mut c_void) -> c_int;
+    // device buffers: for callers that keep their inputs resident (not used by the types below)
+    #[allow(dead_code)]
+    fn mbls_verify_multiple_batches_device(ctx: *mut MblsCtx, d_sigs96: *const u8, d_apks96: *const u8, d_pks: *const u8, pk_format: c_int, d_pk_offsets: *const u32,
+                                           k: u32, d_msgs: *const u8, msg_len: u32, d_msg_offsets: *const u64, d_rands: *const u64, n_sets: u64,
+                                           d_batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64, d_results: *mut u8, d_status: *mut u32,
+                                           stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn mbls_verify_multiple_batches_indexed_device(ctx: *mut MblsCtx, t: *const MblsKeyTable, d_sigs96: *const u8, d_key_idx: *const u32, d_offsets: *const u32,
+                                                   k: u32, d_msgs: *const u8, msg_len: u32, d_msg_offsets: *const u64, d_rands: *const u64, n_sets: u64,
+                                                   d_batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64, d_results: *mut u8, d_status: *mut u32,
+                                                   stream: *mut c_void) -> c_int;
     fn mbls_fast_aggregate_verify_batch(ctx: *mut MblsCtx, sigs: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64, pks: *const u8, pk_format: c_int,
                                         pk_offsets: *const u32, n: u64, k: u32, results: *mut u8, status: *mut u32) -> c_int;
     fn mbls_aggregate_verify_batch(ctx: *mut MblsCtx, sigs96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64, pks96: *const u8,
@@ -545,6 +562,44 @@ impl AggregateSignature {
             std::panic::resume_unwind(payload);
         }
         ok
+    }
+    /// Not in the reference: what `verify_multiple_aggregate_signatures(rng, batch)` returns for every batch, called once per batch in order --
+    /// as ONE call on the GPU (`mbls_verify_multiple_batches_rng`), for about the cost of one such call. One bool per batch; a bad batch rejects
+    /// itself and nothing else. The scalars are drawn in the order those calls would draw them (for every batch, the sets in front of its first
+    /// signature outside G2), so `rng` is left exactly where they would leave it.
+    pub fn verify_multiple_aggregate_signatures_batches<'a, R, I, B>(rng: &mut R, batches: I) -> Result<Vec<bool>, AmclError>
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = B>,
+        B: Iterator<Item = (&'a AggregateSignature, &'a AggregatePublicKey, &'a [u8])>,
+    {
+        let (mut sigs, mut apks, mut msgs) = (Vec::new(), Vec::new(), Vec::new());
+        let mut moff: Vec<u64> = vec![0];
+        let mut boff: Vec<u32> = vec![0];
+        for b in batches {
+            for (s, a, m) in b {
+                sigs.extend_from_slice(&s.point);
+                apks.extend_from_slice(&a.point);
+                msgs.extend_from_slice(m);
+                moff.push(msgs.len() as u64);
+            }
+            boff.push((moff.len() - 1) as u32);
+        }
+        let n_batches = boff.len() - 1;
+        if n_batches == 0 {
+            return Ok(Vec::new());
+        }
+        let mut res = vec![0u8; n_batches];
+        let mut st = DrawState { rng, panic: None };
+        let rc = unsafe {
+            mbls_verify_multiple_batches_rng(ctx(), sigs.as_ptr(), apks.as_ptr(), msgs.as_ptr(), 0, moff.as_ptr(), (moff.len() - 1) as u64, boff.as_ptr(), 0,
+                                             n_batches as u64, res.as_mut_ptr(), draw_scalars::<R>, &mut st as *mut DrawState<R> as *mut c_void)
+        };
+        if let Some(payload) = st.panic.take() {
+            std::panic::resume_unwind(payload);
+        }
+        check(rc)?;
+        Ok(res.into_iter().map(|r| r == 1).collect())
     }
     /// `src/aggregates.rs:319-322`
     pub fn from_bytes(bytes: &[u8]) -> Result<AggregateSignature, AmclError> {
