@@ -89,7 +89,10 @@ MBLS_FN void lane_aggregate(const mbls_ws& ws, uint64_t i, const uint8_t* pks, u
 extern "C" __device__ __attribute__((noinline, used, aligned(64))) void mbls_fp_mulpair_d_asm_fn() { asm volatile(MBLS_FP_MULPAIR_D_ASM); }
 extern "C" __device__ __attribute__((noinline, used, aligned(64))) void mbls_fp_mul1_d_asm_fn() { asm volatile(MBLS_FP_MUL1_D_ASM); }
 extern "C" __device__ __attribute__((noinline, used, aligned(64))) void mbls_fp_sqrpair_d_asm_fn() { asm volatile(MBLS_FP_SQRPAIR_D_ASM); }
-extern "C" __device__ __attribute__((noinline, used, aligned(64))) void mbls_g1_aggregate_raw_d_asm_fn() { asm volatile(MBLS_G1_AGGREGATE_RAW_D_ASM); }
+extern "C" __device__ __attribute__((noinline, used, aligned(64))) void mbls_fp_redc7_d_asm_fn() { asm volatile(MBLS_FP_REDC7_D_ASM); }
+// 96-byte keys are summed on the isomorphic curve y^2 = x^3 + 4 l^6, l = 2^-196, where their plain digits already are Montgomery
+// representations (gen_tower_d.py, mode "rawiso"); the routine's epilogue maps the sum back, so slots 0..2 hold the sum on E as before.
+extern "C" __device__ __attribute__((noinline, used, aligned(64))) void mbls_g1_aggregate_rawiso_d_asm_fn() { asm volatile(MBLS_G1_AGGREGATE_RAWISO_D_ASM); }
 extern "C" __device__ __attribute__((noinline, used, aligned(64))) void mbls_g1_aggregate_indexed_d_asm_fn() { asm volatile(MBLS_G1_AGGREGATE_INDEXED_D_ASM); }
 template <bool INDEXED>
 MBLS_FN uint32_t lane_aggregate_d(const mbls_ws& ws, uint64_t i, const void* keys, uint32_t cnt, int mode, uint32_t lane,
@@ -107,7 +110,7 @@ MBLS_FN uint32_t lane_aggregate_d(const mbls_ws& ws, uint64_t i, const void* key
                      : "{v252}"(addr), "{s68}"(gb_lo), "{s69}"(gb_hi), "{s70}"(st4), "{s94}"(r_lo), "{s95}"(r_hi), "{s96}"(ts)
                      : MBLS_G1_AGG_D_ASM_CLOBBERS);
     } else {
-        asm volatile(MBLS_ASM_CALL("mbls_g1_aggregate_raw_d_asm_fn")
+        asm volatile(MBLS_ASM_CALL("mbls_g1_aggregate_rawiso_d_asm_fn")
                      : "={v251}"(fl), "+{v248}"(plo), "+{v249}"(phi), "+{v250}"(c)
                      : "{v252}"(addr), "{s68}"(gb_lo), "{s69}"(gb_hi), "{s70}"(st4)
                      : MBLS_G1_AGG_D_ASM_CLOBBERS, "s94", "s95", "s96");

@@ -18,6 +18,8 @@ Register contract (blocks of 14 VGPRs, block i = v[14 i .. 14 i + 13]):
     mbls_fp_mulpair_d_asm_fn a0 blk0, a1 blk1, b0 blk2, b1 blk3 (preserved)  ->  a0 b0 blk5, a1 b1 blk6   (two independent Fp products)
     mbls_fp_mul1_d_asm_fn    a0 blk0, b0 blk2 (preserved)                    ->  a0 b0 blk5
     mbls_fp_sqrpair_d_asm_fn a0 blk0, a1 blk1 (preserved)                    ->  a0^2 blk5, a1^2 blk6   (blk2, blk3 = doubled digits)
+    mbls_fp4_sqr0_d_asm_fn   a0 blk0, a1 blk1, b0 blk2, b1 blk3 (preserved)  ->  a^2 + (1 + i) b^2 in blk5, blk6   (blk4, blk8..12 = sums, differences, doubled digits)
+    mbls_fp_redc7_d_asm_fn   a0 blk0 (preserved)                             ->  a0 2^-196 blk5   (seven Montgomery steps, no product)
 Resident constants (loaded once by the calling routine's shell, load_constants()): digits of p in s40-s47, s56-s61, -p^-1 mod 2^28
 in s64, the digit mask in s65. Carries: vcc and s[62:63]. Results: digits 0..12 in [0, 2^28), digit 13 signed (the value lies in
 (-X, p + X) with X = sum |a||b| / 2^392, a tiny multiple of p for every operand the callers produce).
@@ -180,9 +182,80 @@ def fp_mul1_d_body():
     return signed_scan([(BLK(0), BLK(2))], BLK(5), ACC_A, CARRY_A)
 
 
+def fp4_sqr0_d_body(blocks=None):
+    """blocks: (A0, A1, B0, B1, SA, DA, A0D, SB, DB, B0D, C0, C1), default 0, 1, 2, 3, 4, 8, 9, 10, 11, 12, 5, 6.
+    The first half of the Fp4 squaring (a + b s)^2 = (a^2 + xi b^2) + 2 a b s, xi = 1 + i, of the compressed cyclotomic squaring, as ONE pair
+    of scans: c = a^2 + xi b^2, i.e. with P1 = (a0 + a1)(a0 - a1), 2 P2 = (2 a0) a1, P3 = (b0 + b1)(b0 - b1), 2 P4 = (2 b0) b1
+        c0 = P1 + P3 - 2 P4,    c1 = 2 P2 + P3 + 2 P4
+    four products and two Montgomery reductions where two Fp2 squarings take four and four. As in fp2_mul_d_body both scans walk the columns
+    in lockstep and the shared products are formed once per column in fresh accumulators (X_k of P3, Y_k of 2 P4): c0's scan receives
+    X_k - Y_k, c1's X_k + Y_k. The doublings sit in operand digits. Input limits (gen_tower_d.py call_limits_ok): each scan sums three
+    digit-vector products in a signed 64-bit column."""
+    A0, A1, B0, B1, SA, DA, A0D, SB, DB, B0D, C0, C1 = blocks or (BLK(0), BLK(1), BLK(2), BLK(3), BLK(4), BLK(8), BLK(9), BLK(10), BLK(11), BLK(12), BLK(5), BLK(6))
+    ACC0, ACC1, X, Y = "v[98:99]", "v[100:101]", "v[108:109]", "v[110:111]"
+    L = []
+    for j in range(14):
+        L += ["v_add_u32_e64 %s, %s, %s" % (SA(j), A0(j), A1(j)), "v_sub_u32_e64 %s, %s, %s" % (DA(j), A0(j), A1(j)), "v_lshlrev_b32_e64 %s, 1, %s" % (A0D(j), A0(j)),
+              "v_add_u32_e64 %s, %s, %s" % (SB(j), B0(j), B1(j)), "v_sub_u32_e64 %s, %s, %s" % (DB(j), B0(j), B1(j)), "v_lshlrev_b32_e64 %s, 1, %s" % (B0D(j), B0(j))]
+    first0 = first1 = True
+    for k in range(28):
+        idx = list(range(max(0, k - 13), min(k, 13) + 1))
+        fx = True
+        for i in idx:                                   # four independent chains, interleaved
+            L.append("v_mad_i64_i32 %s, vcc, %s, %s, %s" % (X, SB(i), DB(k - i), "0" if fx else X))
+            L.append("v_mad_i64_i32 %s, s[62:63], %s, %s, %s" % (Y, B0D(i), B1(k - i), "0" if fx else Y)); fx = False
+            L.append("v_mad_i64_i32 %s, vcc, %s, %s, %s" % (ACC0, SA(i), DA(k - i), "0" if first0 else ACC0)); first0 = False
+            L.append("v_mad_i64_i32 %s, s[62:63], %s, %s, %s" % (ACC1, A0D(i), A1(k - i), "0" if first1 else ACC1)); first1 = False
+        for i in (range(k) if k < 14 else range(k - 13, 14)):                       # the Montgomery quotient digits times p, both scans
+            L.append("v_mad_i64_i32 %s, vcc, %s, %s, %s" % (ACC0, SP28(k - i), C0(i), ACC0))
+            L.append("v_mad_i64_i32 %s, s[62:63], %s, %s, %s" % (ACC1, SP28(k - i), C1(i), ACC1))
+        if idx:
+            L += ["v_lshl_add_u64 %s, %s, 0, %s" % (ACC1, X, ACC1), "v_lshl_add_u64 %s, %s, 0, %s" % (ACC1, Y, ACC1)]                   # + X + Y
+            L += ["v_sub_co_u32_e64 v108, vcc, v108, v110", "v_subb_co_u32_e64 v109, vcc, v109, v111, vcc"]                            # X - Y
+            L.append("v_lshl_add_u64 %s, %s, 0, %s" % (ACC0, X, ACC0))
+        for (out, A, lo, cy) in ((C0, ACC0, "v98", "vcc"), (C1, ACC1, "v100", "s[62:63]")):
+            if k < 14:
+                L += ["v_mul_lo_u32 %s, %s, %s" % (out(k), lo, SNP28), "v_and_b32_e64 %s, %s, %s" % (out(k), out(k), SMASK28),
+                      "v_mad_i64_i32 %s, %s, %s, %s, %s" % (A, cy, SP28(0), out(k), A), "v_ashrrev_i64 %s, 28, %s" % (A, A)]
+            elif k < 27:
+                L += ["v_and_b32_e64 %s, %s, %s" % (out(k - 14), lo, SMASK28), "v_ashrrev_i64 %s, 28, %s" % (A, A)]
+            else:
+                L.append("v_mov_b32_e64 %s, %s" % (out(13), lo))
+    return L
+
+
+REDC7_STEPS = 7
+
+
+def fp_redc7_d_body():
+    """a0 * 2^-196 mod p: the first seven steps of a Montgomery reduction run on the 14 digits themselves (the public-key sum turns a plain
+    y into the representation of y * 2^-588 with it, see prog_g1_step in tools/gen_tower_d.py). Column k < 7 fixes the quotient digit q_k that
+    clears it, columns 7..20 are the result: (a0 + Q p) / 2^196 with 0 <= Q < 2^196, so the value lies in [a0 / 2^196, a0 / 2^196 + p).
+    98 + 7 quotient products; the digits of a0 enter their columns through a multiplication by the inline constant 1. q_k waits in the
+    result register of column 14 + k, which is written only after its last use (column 13 + k)."""
+    Y, out = BLK(0), BLK(5)
+    A, lo, cy = "v[%d:%d]" % (ACC_A, ACC_A + 1), "v%d" % ACC_A, CARRY_A
+    q = lambda i: out(7 + i)
+    S, first = [], True
+    for k in range(14 + REDC7_STEPS):
+        macs = [(Y(k), "1")] if k < 14 else []
+        macs += [(SP28(k - i), q(i)) for i in range(max(0, k - 13), min(k, REDC7_STEPS))]
+        for (x, y) in macs:
+            S.append("v_mad_i64_i32 %s, %s, %s, %s, %s" % (A, cy, x, y, "0" if first else A)); first = False
+        if k < REDC7_STEPS:
+            S += ["v_mul_lo_u32 %s, %s, %s" % (q(k), lo, SNP28), "v_and_b32_e64 %s, %s, %s" % (q(k), q(k), SMASK28),
+                  "v_mad_i64_i32 %s, %s, %s, %s, %s" % (A, cy, SP28(0), q(k), A), "v_ashrrev_i64 %s, 28, %s" % (A, A)]
+        elif k < 13 + REDC7_STEPS:
+            S += ["v_and_b32_e64 %s, %s, %s" % (out(k - REDC7_STEPS), lo, SMASK28), "v_ashrrev_i64 %s, 28, %s" % (A, A)]
+        else:
+            S.append("v_mov_b32_e64 %s, %s" % (out(13), lo))          # top digit: signed, whatever is left
+    return S
+
+
 ROUTINE_BODIES = {"mbls_fp2_mul_d_asm_fn": fp2_mul_d_body, "mbls_fp2_sqr_d_asm_fn": fp2_sqr_d_body, "mbls_fp2_mulfp_d_asm_fn": fp2_mulfp_d_body,
                   "mbls_fp_mulpair_d_asm_fn": fp_mulpair_d_body, "mbls_fp_mul1_d_asm_fn": fp_mul1_d_body,
-                  "mbls_fp_sqrpair_d_asm_fn": fp_sqrpair_d_body}
+                  "mbls_fp_sqrpair_d_asm_fn": fp_sqrpair_d_body, "mbls_fp_redc7_d_asm_fn": fp_redc7_d_body,
+                  "mbls_fp4_sqr0_d_asm_fn": fp4_sqr0_d_body}
 
 
 # ---- input limits: the worst column of a scan must stay inside a signed 64-bit accumulator

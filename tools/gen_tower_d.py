@@ -30,7 +30,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gen_fp_asm import P, P28, M28, SP28, SMASK28, emit  # noqa: E402
-from gen_fpd_asm import load_constants, column_ok, fp2_mul_d_body, fp2_sqr_d_body, fp2_mulfp_d_body  # noqa: E402
+from gen_fpd_asm import load_constants, column_ok, fp2_mul_d_body, fp2_sqr_d_body, fp2_mulfp_d_body, fp4_sqr0_d_body  # noqa: E402
 
 
 class Prog:
@@ -137,6 +137,7 @@ class Prog:
     def mulpair(self, a0, b0, a1, b1):
         return self.call("sqrpair", [a0, a1]) if (a0 == b0 and a1 == b1 and a0 != a1) else self.call("mulpair", [a0, a1, b0, b1])
     def mul1(self, a, b): return self.call("mul1", [a, b])[0]
+    def redc7(self, a): return self.call("redc7", [a])[0]                     # a * 2^-196: seven Montgomery steps, no product
 
     def iszero(self, a, mask):
         """mask (an SGPR pair) <- lanes in which a = 0 mod p"""
@@ -259,6 +260,50 @@ def pair_products(p, window=160):
     return p
 
 
+# ---------------------------------------------------------------------------------------------- fused Fp4 squarings
+# The compressed cyclotomic squaring records each Fp4 squaring (a + b s)^2 = (a^2 + xi b^2, 2 a b) as three Fp2 squarings:
+#     t0 = a^2, t1 = b^2, c0 = xi t1 + t0, c1 = (a + b)^2 - t0 - t1        six Fp products, six Montgomery reductions
+# fuse_fp4_squarings() rewrites that pattern in a recorded program into
+#     c0 = fp4sqr0(a, b)   one pair of scans, four products and two reductions (mbls_fp4_sqr0_d_asm_fn, tools/gen_fpd_asm.py)
+#     c1 = (2 a) b         the Fp2 product: three products, two reductions
+# 2 156 multiply-accumulates instead of 2 352. "fp4sqr0" exists only in the rewritten list the allocator walks (like the "x2" kinds of
+# pair_products): the recorder, and the models that implement its interface, never see it.
+def fuse_fp4_squarings(p):
+    ops = list(p.ops)
+    if not ops:                                      # (a model program computes as it records: nothing to rewrite)
+        return p
+    uses = {}
+    for op in ops:
+        for v in op[2]:
+            uses[v] = uses.get(v, 0) + 1
+    out, i, fused = [], 0, 0
+    while i < len(ops):
+        w = ops[i:i + 8]
+        m = None
+        if len(w) == 8 and [o[0] for o in w] == ["sqr", "sqr", "pair", "pair", "pair", "sqr", "pair", "pair"]:
+            (a0, a1), (b0, b1), t0, t1 = w[0][2], w[1][2], w[0][1], w[1][1]
+            xi, c0, sm, ss, u, c1 = w[2][1], w[3][1], w[4][1], w[5][1], w[6][1], w[7][1]
+            ok = (w[2][2] == [t1[0], t1[1], t1[0], t1[1]] and w[2][3] == ("sub", "add")              # xi t1
+                  and w[3][2] == [xi[0], t0[0], xi[1], t0[1]] and w[3][3] == ("add", "add")          # + t0
+                  and w[4][2] == [a0, b0, a1, b1] and w[4][3] == ("add", "add")                      # a + b
+                  and w[5][2] == [sm[0], sm[1]]
+                  and w[6][2] == [ss[0], t0[0], ss[1], t0[1]] and w[6][3] == ("sub", "sub")
+                  and w[7][2] == [u[0], t1[0], u[1], t1[1]] and w[7][3] == ("sub", "sub")
+                  and all(uses.get(v, 0) == n for vs, n in ((t0, 2), (t1, 3), (xi, 1), (sm, 1), (ss, 1), (u, 1)) for v in vs))
+            if ok:
+                m = (a0, a1, b0, b1, c0, c1)
+        if m is None:
+            out.append(ops[i]); i += 1
+            continue
+        a0, a1, b0, b1, c0, c1 = m
+        d0, d1 = p.new(), p.new()
+        out += [("fp4sqr0", list(c0), [a0, a1, b0, b1], None), ("scale", [d0], [a0], 2), ("scale", [d1], [a1], 2), ("mul", list(c1), [d0, d1, b0, b1], None)]
+        i += 8; fused += 1
+    p.ops = out
+    p.fused_fp4 = fused
+    return p
+
+
 def is_product(kind):
     return kind in ROUTINES or (kind.endswith("x2") and kind[:-2] in ROUTINES)
 
@@ -289,6 +334,8 @@ ROUTINES = {
     "mulpair": dict(name="mbls_fp_mulpair_d_asm_fn", ins=[0, 1, 2, 3], outs=[5, 6], clob=[5, 6, 7]),     # (a0 b0, a1 b1)
     "mul1": dict(name="mbls_fp_mul1_d_asm_fn", ins=[0, 2], outs=[5], clob=[5, 7]),
     "sqrpair": dict(name="mbls_fp_sqrpair_d_asm_fn", ins=[0, 1], outs=[5, 6], clob=[2, 3, 5, 6, 7]),     # (a0^2, a1^2)
+    "fp4sqr0": dict(name="mbls_fp4_sqr0_d_asm_fn", ins=[0, 1, 2, 3], outs=[5, 6], clob=[4, 5, 6, 7, 8, 9, 10, 11, 12]),    # a^2 + xi b^2
+    "redc7": dict(name="mbls_fp_redc7_d_asm_fn", ins=[0], outs=[5], clob=[5, 7]),                         # a0 * 2^-196
 }
 
 
@@ -1145,12 +1192,20 @@ class AllocD:
             return 2 * m[0] < (1 << 31) and 2 * m[1] < (1 << 31) and column_ok([(m[0], m[0])]) and column_ok([(m[1], m[1])])
         if kind == "mul1":
             return column_ok([(m[0], m[1])])
+        if kind == "fp4sqr0":                               # each scan sums three products: (a0 + a1)(a0 - a1) / (2 a0) a1, (b0 + b1)(b0 - b1), (2 b0) b1
+            sa, da, sb, db = B[0] + B[1], B[0] - B[1], B[2] + B[3], B[2] - B[3]
+            shared = [(sb.mag(), db.mag()), (2 * m[2], m[3])]
+            return (sa.fits() and da.fits() and sb.fits() and db.fits() and 2 * m[0] < (1 << 31) and 2 * m[2] < (1 << 31)
+                    and column_ok([(sa.mag(), da.mag())] + shared) and column_ok([(2 * m[0], m[1])] + shared))
+        if kind == "redc7":                                 # a column holds one digit, seven quotient products below 2^56 and a carry
+            return B[0].fits()
         return column_ok([(m[0], m[2])]) and column_ok([(m[1], m[2])])
 
     # kinds that can be inlined: (scratch blocks, body) -- block order of the bodies: operands, scratch, results (see gen_fpd_asm.py)
     INLINE = {"mul": (2, lambda o, t, r: fp2_mul_d_body((o[0], o[1], o[2], o[3], t[0], r[0], r[1], t[1]))),
               "sqr": (3, lambda o, t, r: fp2_sqr_d_body((o[0], o[1], t[0], t[1], t[2], r[0], r[1]))),
-              "mulfp": (0, lambda o, t, r: fp2_mulfp_d_body((o[0], o[1], o[2], r[0], r[1])))}
+              "mulfp": (0, lambda o, t, r: fp2_mulfp_d_body((o[0], o[1], o[2], r[0], r[1]))),
+              "fp4sqr0": (6, lambda o, t, r: fp4_sqr0_d_body((o[0], o[1], o[2], o[3], t[0], t[1], t[2], t[3], t[4], t[5], r[0], r[1])))}
 
     def call_bounds(self, kind, B):
         if kind == "mul":
@@ -1163,6 +1218,11 @@ class AllocD:
             return [product_bound([(B[0], B[0])]), product_bound([(B[1], B[1])])]
         if kind == "mul1":
             return [product_bound([(B[0], B[1])])]
+        if kind == "fp4sqr0":
+            shared = [(B[2] + B[3], B[2] - B[3]), (B[2] + B[2], B[3])]
+            return [product_bound([(B[0] + B[1], B[0] - B[1])] + shared), product_bound([(B[0] + B[0], B[1])] + shared)]
+        if kind == "redc7":                                 # (a + Q p) / 2^196 with 0 <= Q < 2^196
+            return [Bound.normalised((B[0].vlo >> 196) - 1, P + (B[0].vhi >> 196) + 1)]
         return [product_bound([(B[0], B[2])]), product_bound([(B[1], B[2])])]
 
     def do_call_inline(self, k, kind, outs, ins):
@@ -2067,6 +2127,8 @@ def build_fexp(which, pair_mode=False):
     p = FEXP_BODIES[which]()
     if pair_mode:
         pair_products(p)
+    elif which == "csqr":
+        fuse_fp4_squarings(p)
     inb = {v: (STATE_IN if l[0] in ("a", "v") else PACKED if l[0] in ("gd", "gk") else G_IN) for v, l in p.init_loc.items()}
     al = AllocD(p, inb, n_lds=11, lds_base=0, a_pool=list(range(NA)), inline=(which in FEXP_INLINE),
                 free_v=(CSTATE_FREE_V if which in CSTATE_BODIES else None))
@@ -2200,6 +2262,11 @@ def final_exp_d_routine(two_lane=False):
 # the running sum in AGPR blocks 0..2. The Fp products come in independent pairs (mbls_fp_mulpair_d_asm_fn).
 #   raw:     96-byte uncompressed keys (big-endian x || y, flag bits in byte 0) at a per-lane address: byte order, flag and range
 #            checks in the shell, conversion to the Montgomery domain and the on-curve check y^2 = x^3 + 4 in the body (16 products)
+#   rawiso:  the same keys and checks as raw, summed on the isomorphic curve E_l: y^2 = x^3 + 4 l^6 with l = 2^-196. The plain digits of x
+#            ARE the 2^392-domain representation of x' = l^2 x, and y' = l^3 y is represented by y 2^-196 (seven Montgomery steps on the
+#            digits, mbls_fp_redc7_d_asm_fn): no product brings the key into the domain. The mixed addition and the a = 0 doubling do not
+#            contain b and run unchanged; (X, Y, Z) on E_l is (X, Y, l Z) on E, which the epilogue's constant for Z restores (14 products).
+#            This is what k_aggregate_raw_d runs; raw stays in the generator (its tests pin it) but is no longer emitted.
 #   indexed: 32-bit indices at a per-lane address into a resident table of 128-byte records (x, y in the 2^384 Montgomery domain,
 #            a flag word; see MBLS_KEYREC_DWORDS in mbls_lanes.h): 11 products
 # Shell registers (blocks 15..17 are withheld from the allocator): v224..v247 the 24 words of the key in flight, v[248:249] running
@@ -2213,11 +2280,15 @@ EXEC_ALL, EXEC_ACT = "s[82:83]", "s[90:91]"
 R392SQ = R392 * R392 % P             # x (plain) times this, Montgomery-multiplied, is x in the 2^392 domain
 FOUR_D = 4 * R392 % P
 G1_RAW_IN = Bound.normalised(0, P - 1)
+LAMBDA_D = pow(1 << 196, -1, P)      # l = 2^-196 (as a plain factor)
+FOUR_ISO_D = 4 * pow(LAMBDA_D, 6, P) * R392 % P          # the constant 4 l^6 of E_l in the 2^392 domain
+K384_ISO = K384 * LAMBDA_D % P       # 2^392 domain -> 2^384 domain and Z on E_l -> Z on E in one product
+G1_RAW_MODES = ("raw", "rawiso")
 
 
 def prog_g1_step(mode):
     """acc <- acc + key. Live in: acc = (X, Y, Z) in AGPR blocks 0..2; the key's coordinates in VGPR blocks 8, 9 -- plain integers
-    below p (raw) or Montgomery words cut as 2^392-domain digits (indexed); mask M_INF2 = the key counts as infinity. Out: the new sum
+    below p (raw, rawiso) or Montgomery words cut as 2^392-domain digits (indexed); mask M_INF2 = the key counts as infinity. Out: the new sum
     in AGPR blocks 0..2, the old one in 5..7 (for the doubling case), masks M_H0, M_R0, M_INF1, M_INF2F (raw: includes off-curve)."""
     p = Prog()
     X, Y, Z = [p.live_in(("a", i)) for i in range(3)]
@@ -2228,6 +2299,15 @@ def prog_g1_step(mode):
         xx, yy = p.mulpair(x2, x2, y2, y2)
         x3, Z1Z1 = p.mulpair(xx, x2, Z, Z)
         p.iszero(p.sub(p.sub(yy, x3), p.const(FOUR_D)), M_CURVE)           # y^2 = x^3 + 4
+        p.mask_orn2(M_INF2F, M_INF2, M_CURVE)
+        T, U2 = p.mulpair(y2, Z, x2, Z1Z1)
+        H = p.sub(U2, X)
+        S2, ZH = p.mulpair(T, Z1Z1, Z, H)
+    elif mode == "rawiso":
+        x2, y2 = kx, p.redc7(ky)                                            # (x', y') on E_l
+        xx, yy = p.mulpair(x2, x2, y2, y2)
+        x3, Z1Z1 = p.mulpair(xx, x2, Z, Z)
+        p.iszero(p.sub(p.sub(yy, x3), p.const(FOUR_ISO_D)), M_CURVE)       # y'^2 = x'^3 + 4 l^6
         p.mask_orn2(M_INF2F, M_INF2, M_CURVE)
         T, U2 = p.mulpair(y2, Z, x2, Z1Z1)
         H = p.sub(U2, X)
@@ -2249,7 +2329,7 @@ def prog_g1_step(mode):
     M0, M1 = p.mulpair(RR, p.sub(V, X3), Y, J)
     Y3 = p.sub(M0, p.scale(M1, 2))
     Z3 = p.scale(ZH, 2)                                                    # (Z + H)^2 - Z^2 - H^2
-    inf2 = M_INF2F if mode == "raw" else M_INF2
+    inf2 = M_INF2F if mode in G1_RAW_MODES else M_INF2
     out = [p.sel(M_INF1, X3, x2), p.sel(M_INF1, Y3, y2), p.sel(M_INF1, Z3, p.const(ONE_D))]
     out = [p.sel(inf2, out[0], X), p.sel(inf2, out[1], Y), p.sel(inf2, out[2], Z)]
     for i, v in enumerate((X, Y, Z)):
@@ -2279,7 +2359,7 @@ def prog_g1_dbl(src=5):
 
 def build_g1(which):
     p = prog_g1_dbl() if which == "dbl" else prog_g1_step(which)
-    key_in = G1_RAW_IN if which == "raw" else G_IN
+    key_in = G1_RAW_IN if which in G1_RAW_MODES else G_IN
     inb = {v: (STATE_IN if l[0] == "a" else key_in) for v, l in p.init_loc.items()}
     al = AllocD(p, inb, n_lds=0, a_pool=list(range(8, NA)), free_v=G1_FREE_V)
     body = al.run()
@@ -2327,7 +2407,8 @@ def g1_status(inf_mask, bad_mask):
 def g1_aggregate_d_routine(mode):
     """In:  v[248:249] address of the lane's first key (raw: 96-byte records) or first index (indexed: uint32), v250 its key count;
          indexed: s[94:95] the table's records, s96 its size; v252, s[68:69], s70 the workspace addressing of the other routines.
-    Out: the sum in workspace slots 0..2 (Jacobian X, Y, Z; canonical, 2^384 domain); v251 status bits."""
+    Out: the sum in workspace slots 0..2 (Jacobian X, Y, Z on E; canonical, 2^384 domain); v251 status bits."""
+    raw_keys = mode in G1_RAW_MODES
     step, st_step = build_g1(mode)
     dbl, st_dbl = build_g1("dbl")
     pro = ["s_mov_b64 s[80:81], s[30:31]", "s_waitcnt vmcnt(0)"] + shell_constants()
@@ -2343,7 +2424,7 @@ def g1_aggregate_d_routine(mode):
         # the comparison itself must see every lane: a v_cmp writes zeros for lanes that are switched off
         return pre + ["s_mov_b64 exec, %s" % EXEC_ALL, "v_cmp_gt_u32_e64 vcc, v250, %s" % src, "s_mov_b64 exec, vcc"]
 
-    if mode == "raw":
+    if raw_keys:
         fetch = ["global_load_dwordx4 v[%d:%d], v[248:249], off offset:%d" % (224 + 4 * q, 227 + 4 * q, 16 * q) for q in range(6)]
         advance = ["v_add_co_u32_e32 v248, vcc, 0x60, v248", "v_addc_co_u32_e32 v249, vcc, 0, v249, vcc"]
         pro += ["v_mov_b32_e32 %s, 0x%08x" % (PLIMB(j), P_LIMBS[j]) for j in range(12)]
@@ -2367,12 +2448,12 @@ def g1_aggregate_d_routine(mode):
         decode += seq_conv(lambda j: "v%d" % (vb(8) + j), [KW(j) for j in range(12)], True)
         decode += seq_conv(lambda j: "v%d" % (vb(9) + j), [KW(12 + j) for j in range(12)], True)
         nxt = lanes_with_key(1) + addr + fetch + ["v_mov_b32_e32 v218, %s" % OOB] + lanes_with_key(2) + load_id
-    inf_final = M_INF2F if mode == "raw" else M_INF2
+    inf_final = M_INF2F if raw_keys else M_INF2
     loop = ["1:"] + lanes_with_key(0) + ["s_mov_b64 %s, exec" % EXEC_ACT, "s_cbranch_execnz 3f"] + far_fwd(9) + ["3:", "s_waitcnt vmcnt(0)"]
     loop += decode + nxt + ["s_mov_b64 exec, %s" % EXEC_ACT]
     loop += expand_calls_d(step)
     post = []
-    if mode == "raw":                                   # an off-curve key is undecodable too
+    if raw_keys:                                        # an off-curve key is undecodable too
         post += ["s_andn2_b64 s[92:93], %s, %s" % (M_INF2F, M_INF2), "s_or_b64 %s, %s, s[92:93]" % (M_BAD, M_BAD)]
     post += g1_status(inf_final, M_BAD)
     loop += post
@@ -2386,6 +2467,8 @@ def g1_aggregate_d_routine(mode):
     epi += ["v_mov_b32_e32 %s, 0x%08x" % (B2(j), dgt) for j, dgt in enumerate(digits_of(K384))]
     for half in range(2):
         srcs = (0, 1) if half == 0 else (2, 2)
+        if half == 1 and mode == "rawiso":                  # Z on E_l times l is Z on E
+            epi += ["v_mov_b32_e32 %s, 0x%08x" % (B2(j), dgt) for j, dgt in enumerate(digits_of(K384_ISO))]
         epi += ["v_accvgpr_read_b32 %s, a%d" % (B0(j), vb(srcs[0]) + j) for j in range(14)]
         epi += ["v_accvgpr_read_b32 %s, a%d" % (B1(j), vb(srcs[1]) + j) for j in range(14)]
         epi += ["CALL mbls_fp2_mulfp_d_asm_fn"]
@@ -3158,7 +3241,7 @@ def main():
     txt += emit("MBLS_FINAL_EXP2_D_ASM", full2) + "\n"
     print("final_exp_d two lanes per item: csqr", len(pieces2["csqr"]), "pstart", len(pieces2["pstart"]), "psave", len(pieces2["psave"]), "lines")
     txt += "#define MBLS_FINAL_EXP_D_ASM_CLOBBERS MBLS_MILLER_D_ASM_CLOBBERS, \"v253\", \"s50\", \"s51\", \"s52\", \"s53\", \"s79\", \"s71\", \"s72\", \"s80\", \"s81\", " + ", ".join('\"s%d\"' % i for i in range(84, 100)) + "\n"
-    for mode in ("raw", "indexed"):
+    for mode in ("rawiso", "indexed"):
         full, pieces, st = g1_aggregate_d_routine(mode)
         txt += emit("MBLS_G1_AGGREGATE_%s_D_ASM" % mode.upper(), full) + "\n"
         print("g1 aggregate", mode, "step", len(pieces["step"]), "lines", st["step"], "dbl", len(pieces["dbl"]))
