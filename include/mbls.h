@@ -430,7 +430,8 @@ int mbls_verify_multiple_sets_indexed_device(mbls_ctx* ctx, const mbls_keytable*
  * through the host), and mbls_verify_multiple_finish_device joins G records -- any G >= 0, in any order as long as every participant uses
  * the same -- into the bool the one-device call returns for the concatenated sets. Keys: d_apks96 (one aggregate key per set) or, when
  * that is NULL, d_pks / pk_format / d_pk_offsets / k as in mbls_verify_multiple_sets_device. An empty shard (n = 0) is a valid
- * participant. Both entries only enqueue. */
+ * participant. Both entries only enqueue. A record that was not written by mbls_verify_multiple_partial_device -- wrong tag word, or a coefficient
+ * of its Miller product that is not below p -- makes the joined check fail (MBLS_ST_PAIRING_FAILED | MBLS_ST_BAD_SIG_ENCODING in the status word). */
 #define MBLS_VM_PARTIAL_BYTES 896
 int mbls_verify_multiple_partial_device(mbls_ctx* ctx, const uint8_t* d_sigs96, const uint8_t* d_apks96, const uint8_t* d_pks, int pk_format,
                                         const uint32_t* d_pk_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len,
@@ -519,6 +520,11 @@ int mbls_aggregate_public_keys_batch(mbls_ctx* ctx, const uint8_t* pks, int pk_f
  * 1 a^2, 2 Fp2 product and 3 Fp2 square over element pairs (2i, 2i+1) = (real, imaginary), 4 a^-1 (0 -> 0),
  * 5 a^((p-3)/4), 6 the paired-product routine on elements 2i and 2i+1 */
 int mbls_fp_mul_batch(mbls_ctx* ctx, const uint8_t* a48, const uint8_t* b48, uint64_t n, uint8_t* out48, int op);
+/* raw-register probe for the parity tests of the generated digit-form routines (tools/gen_tower_d.py probe_ops(): op = index in that list -- the eight
+ * leaf bodies of tools/gen_fpd_asm.py, then the carry / reduce / pack / canonical passes and the word conversion). Lane i of n (at most 2^24) runs the body on the
+ * int32 register contents in[w * n + i], w < n_in, and leaves the registers the probe lists in out[w * n + i], w < n_out; no value is interpreted or checked. MBLS_ERR_DEVICE if the library was built without the generated routines. */
+int mbls_dform_probe_shape(int op, uint32_t* n_in, uint32_t* n_out);
+int mbls_dform_probe(mbls_ctx* ctx, int op, const int32_t* in, uint64_t n, int32_t* out);
 /* integer-ALU calibration: runs `iters` dependent Fp multiplications per lane on n lanes, returns elapsed ms */
 int mbls_fp_mul_bench(mbls_ctx* ctx, uint64_t n_lanes, uint32_t iters, float* ms_out);
 

@@ -151,6 +151,27 @@ def fp_mul_batch(a48, b48, n, square=False, ctx=None, op=None):
     return bytes(out)[:48 * n]
 
 
+def dform_probe_shape(op):
+    """(input words, output words) per lane of probe `op` (include/mbls.h mbls_dform_probe)"""
+    nin, nout = C.c_uint32(), C.c_uint32()
+    if N.lib().mbls_dform_probe_shape(op, C.byref(nin), C.byref(nout)) != 0:
+        raise ValueError("no such probe: %r" % (op,))
+    return nin.value, nout.value
+
+
+def dform_probe(op, words, n, ctx=None):
+    """raw-register probe of a generated digit-form body: words = n_in * n unsigned 32-bit register contents, word-major (word w of lane i at w * n + i);
+    returns the n_out * n register contents the probe stores, in the same layout"""
+    ctx = ctx or _c()
+    nin, nout = dform_probe_shape(op)
+    if len(words) != nin * n:
+        raise ValueError("probe %d takes %d words per lane" % (op, nin))
+    src = (C.c_uint32 * max(1, nin * n))(*words)
+    out = (C.c_uint32 * max(1, nout * n))()
+    ctx.check(N.lib().mbls_dform_probe(ctx.handle, op, src, n, out))
+    return list(out)[:nout * n]
+
+
 def fp_mul_bench(n_lanes, iters, ctx=None):
     """Integer-ALU calibration: `iters` dependent Fp multiplications on each of n_lanes lanes -> elapsed ms."""
     ctx = ctx or _c()

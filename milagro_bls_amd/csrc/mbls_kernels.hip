@@ -607,13 +607,21 @@ __global__ void MBLS_LB k_vm_export(mbls_ws ws, const uint32_t* st_or, int empty
     for (uint32_t j = 218 + t; j < MBLS_VM_PARTIAL_WORDS; j += WG) out[j] = 0;
 }
 static_assert(MBLS_SLOT_S == MBLS_SLOT_F + 12, "k_vm_export / k_vm_import copy slots F and S as one range");
-// record g -> slots F, S of item g; the status words ORed into st_or[0]; a record that is not one (wrong magic) makes the check fail
+// record g -> slots F, S of item g; the status words ORed into st_or[0]; a record that is not one (wrong magic, or a coefficient of the Miller value that is
+// not below p) makes the check fail. The range check is what lets the product tree's routine be generated for canonical words (tools/gen_tower_d.py G_CANON_IN):
+// k_vm_export only ever writes such values, so a record that fails it was not made by this library; its Miller value is replaced by zeros, which are in range.
 __global__ void MBLS_LB k_vm_import(mbls_ws ws, const uint32_t* in, uint64_t G, uint32_t* st_or) {
     const uint64_t g = gid(); if (g >= G) return;
     const uint32_t* r = in + g * MBLS_VM_PARTIAL_WORDS;
-    for (uint32_t j = 0; j < 216; j++) ws.w[((uint64_t)(MBLS_SLOT_F + j / 12) * 12 + j % 12) * ws.stride + g] = r[j];
+    bool wide = false;
+    for (uint32_t a = 0; a < 12; a++) {
+        int cmp = 0;                                                     // the sign of value - p, decided at the highest limb that differs
+        for (int j = 11; j >= 0 && cmp == 0; j--) { const uint32_t w = r[12 * a + j], pl = fp_plimb(j); cmp = w > pl ? 1 : (w < pl ? -1 : 0); }
+        wide |= cmp >= 0;
+    }
+    for (uint32_t j = 0; j < 216; j++) ws.w[((uint64_t)(MBLS_SLOT_F + j / 12) * 12 + j % 12) * ws.stride + g] = (wide && j < 144) ? 0u : r[j];
     uint32_t st = r[216];
-    if (r[217] != MBLS_VM_MAGIC) st |= MBLS_ST_PAIRING_FAILED | MBLS_ST_BAD_SIG_ENCODING;
+    if (r[217] != MBLS_VM_MAGIC || wide) st |= MBLS_ST_PAIRING_FAILED | MBLS_ST_BAD_SIG_ENCODING;
     if (st) atomicOr(st_or, st);
 }
 // the signature k_sig decoded into slots 3..6 of item `item` (affine; y = 0: infinity) -> slot S of the same item in Jacobian form: the
@@ -650,6 +658,26 @@ __global__ void MBLS_LB k_g2_add(const uint8_t* a, const uint8_t* b, uint64_t n,
 __global__ void MBLS_LB k_g1_add(const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out, uint8_t* err) { uint64_t i = gid(); if (i < n) op_g1_add(i, a, b, out, err); }
 __global__ void MBLS_LB k_sk_to_pk(const uint8_t* sks, int fmt, uint64_t n, uint8_t* out) { uint64_t i = gid(); if (i < n) op_sk_to_pk(i, sks, fmt, out); }
 __global__ void MBLS_LB k_fp_mul(const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out, int op) { uint64_t i = gid(); if (i < n) op_fp_mul(i, n, a, b, out, op); }
+// Raw-register probe of the digit-form leaves and passes (tools/gen_tower_d.py probe_ops): lane i runs ONE generated body on the register contents in[w n + i] and
+// stores the registers the probe lists to out[w n + i]; tests/test_gpu_dform.py compares them with the CPU interpreter of the same instructions. The generated text
+// loads and stores its own registers (SADDR form, like the routines' workspace traffic): nothing here sits between the test's integers and the body.
+#if MBLS_DEVICE_ASM
+#define MBLS_DFORM_PROBE_CASE(k, body) case k: asm volatile(body : "+{s66}"(ilo), "+{s67}"(ihi), "+{s68}"(olo), "+{s69}"(ohi) : "{v252}"(off), "{s70}"(st4) : MBLS_DFORM_PROBE_CLOBBERS); break;
+#endif
+__global__ void MBLS_LB k_dform_probe(const int32_t* in, int32_t* out, uint64_t n, int op, uint32_t* ran) {
+    const uint64_t i = gid(); if (i >= n) return;
+#if MBLS_DEVICE_ASM
+    if (i == 0) *ran = 1u;                                                               // a build without the generated routines leaves it 0: the host reports that
+    const uint32_t off = (uint32_t)(4 * i);                                              // n <= 2^24: every byte offset fits 32 bits
+    uint32_t ilo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)in), ihi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)(uintptr_t)in >> 32));
+    uint32_t olo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)out), ohi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)(uintptr_t)out >> 32));
+    const uint32_t st4 = __builtin_amdgcn_readfirstlane((uint32_t)(4 * n));
+    switch (op) {
+        MBLS_DFORM_PROBE_EACH(MBLS_DFORM_PROBE_CASE)
+        default: break;
+    }
+#endif
+}
 // PublicKey::from_secret_key as a key sum: [sk] G1 = sum_j [d_j 16^j] G1 over the 64 hexadecimal digits of sk, every term a record of a
 // fixed 64 x 16 table (record 16 j + d; d = 0 is the point at infinity) -- the indexed key-sum routine does the rest, no doubling at all
 __global__ void MBLS_LB k_sk_digits(const uint8_t* sks32, uint64_t n, uint32_t* idx) {
@@ -1980,6 +2008,30 @@ extern "C" int mbls_fp_mul_batch(mbls_ctx* c, const uint8_t* a, const uint8_t* b
     sbuf da(c, 0), db(c, 1), dout(c, 2); HIPCHK(c, da.up(a, 48 * n)); HIPCHK(c, db.up(b, 48 * n)); HIPCHK(c, dout.alloc(48 * n));
     hipLaunchKernelGGL(k_fp_mul, dim3(nblk(n)), dim3(WG), 0, c->hs_a, da.as<uint8_t>(), db.as<uint8_t>(), n, dout.as<uint8_t>(), square);
     HIPCHK(c, hipStreamSynchronize(c->hs_a)); HIPCHK(c, dout.down(out, 48 * n)); return MBLS_OK;
+}
+#ifndef MBLS_DFORM_PROBE_NOPS
+#include "mbls_towerd_asm.inc"          // the host pass does not see the generated routines: here only for the probes' shape tables (macros, no code)
+#endif
+static const uint32_t DFORM_PROBE_NIN[MBLS_DFORM_PROBE_NOPS] = MBLS_DFORM_PROBE_NIN, DFORM_PROBE_NOUT[MBLS_DFORM_PROBE_NOPS] = MBLS_DFORM_PROBE_NOUT;
+extern "C" int mbls_dform_probe_shape(int op, uint32_t* n_in, uint32_t* n_out) {
+    if (op < 0 || op >= MBLS_DFORM_PROBE_NOPS || !n_in || !n_out) return MBLS_ERR_ARGUMENT;
+    *n_in = DFORM_PROBE_NIN[op]; *n_out = DFORM_PROBE_NOUT[op]; return MBLS_OK;
+}
+extern "C" int mbls_dform_probe(mbls_ctx* c, int op, const int32_t* in, uint64_t n, int32_t* out) {
+    if (!c || !in || !out) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (op < 0 || op >= MBLS_DFORM_PROBE_NOPS) ARGFAIL(c, "no such probe");
+    if (n > (1u << 24)) ARGFAIL(c, "at most 2^24 lanes per probe launch");
+    if (!n) return MBLS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bin = (size_t)4 * DFORM_PROBE_NIN[op] * n, bout = (size_t)4 * DFORM_PROBE_NOUT[op] * n;
+    sbuf di(c, 0), dout(c, 1), dran(c, 2); HIPCHK(c, di.up(in, bin)); HIPCHK(c, dout.alloc(bout));
+    uint32_t ran = 0; HIPCHK(c, dran.up(&ran, 4));
+    hipLaunchKernelGGL(k_dform_probe, dim3(nblk(n)), dim3(WG), 0, c->hs_a, di.as<int32_t>(), dout.as<int32_t>(), n, op, dran.as<uint32_t>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->hs_a)); HIPCHK(c, dran.down(&ran, 4));
+    if (!ran) { snprintf(c->err, sizeof(c->err), "this build has no generated digit-form routines: nothing ran"); return MBLS_ERR_DEVICE; }
+    HIPCHK(c, dout.down(out, bout)); return MBLS_OK;
 }
 extern "C" int mbls_fp_mul_bench(mbls_ctx* c, uint64_t n_lanes, uint32_t iters, float* ms_out) {
     if (!c || !ms_out || !n_lanes) return MBLS_ERR_ARGUMENT;

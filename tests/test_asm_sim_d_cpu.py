@@ -1461,3 +1461,30 @@ def test_g2_blinding_routine_constant_time_table_access():
         assert verdict is True
         c = [w * ri % P for w in out]
         assert jac2_affine(M, (c[0], c[1]), (c[2], c[3]), (c[4], c[5])) == M.g2_mul(pt, r), hex(r)
+
+
+def test_f12_tree_routine():
+    """one product of the n-pairing paths' tree, the whole routine: the lane's Miller value times the partner's, both canonical words of the 2^384 domain (the bound
+    G_CANON_IN the body is generated under), at the edges of that domain and at random; out: canonical words of the product in the groups F_OUT"""
+    rng = random.Random(31)
+    full, pieces, _ = t.f12_tree_routine()
+    POFF = 64                                                         # the partner's byte offset (s71)
+    for trial in range(3):
+        m = miller_machine(0); m.s[71] = POFF
+        init = {}
+        for i in range(12):
+            for kind, off in (("g", 0), ("gka", POFF)):
+                x = rng.randrange(P)
+                if trial == 0:
+                    x = (P - 1) * pow(R384, -1, P) % P                # the words themselves are p - 1: the top of the domain
+                elif trial == 1:
+                    x = [0, 1, P - 1][(i + (off > 0)) % 3]
+                init[(kind, t.FEXP_IN_SLOT + i)] = x
+                for j, w in enumerate(limbs(x * R384 % P)):
+                    m.mem[ws_addr(t.FEXP_IN_SLOT + i, j) + off] = w
+        m.run(pieces["pro"] + pieces["body"] + pieces["epi"])
+        mp = run_model(t.prog_f12_treemul, init, {})
+        assert len(mp.out_home) == 12
+        for loc, x in mp.out_home.items():
+            b = t.F_OUT[loc[1]]
+            assert from_limbs(m.v[b:b + 12]) == x * R384 % P, (trial, loc)

@@ -268,3 +268,22 @@ def test_verify_multiple_over_key_table_indices(N):
     assert int(res[0].item()) == 0 and (int(st[0].item()) & 0x04)
     d_idx[5, 1] = keep
     assert batch.verify_multiple_sets_indexed_device(*args) is True
+
+
+def test_join_rejects_a_record_whose_miller_value_is_not_below_p(N):
+    """the product tree's routine is generated for canonical words: a record whose first Miller coefficient is v + p (the same residue, but no value the library
+    ever writes) is not a record -- the join fails, where the untouched records and the record with v itself pass"""
+    import torch
+    rnd = random.Random(83)
+    sks, pks, msgs, sigs, rands = _sets(rnd, 4)
+
+    def plus_p(k):
+        def spoil(recs):
+            w = recs[N.VM_PARTIAL_BYTES:N.VM_PARTIAL_BYTES + 48]                  # record 1, coefficient 0: 12 little-endian 32-bit limbs
+            v = int.from_bytes(bytes(w.cpu().tolist()), "little")
+            assert v < helpers.P
+            w.copy_(torch.tensor(list((v + k * helpers.P).to_bytes(48, "little")), dtype=torch.uint8, device=recs.device))
+        return spoil
+    assert _sharded(N, sigs, pks, msgs, rands, [0, 2, 4]) is True
+    assert _sharded(N, sigs, pks, msgs, rands, [0, 2, 4], spoil=plus_p(0)) is True
+    assert _sharded(N, sigs, pks, msgs, rands, [0, 2, 4], spoil=plus_p(1)) is False

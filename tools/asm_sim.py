@@ -6,8 +6,25 @@ big-integer model on the CPU before they ever run on a GPU. One lane is simulate
 are single bits and an LDS address is just a key. Unknown instructions raise.
 """
 import re
+from fractions import Fraction
 
 M32 = 0xFFFFFFFF
+
+
+class _Poison:
+    """what the carry destination of v_mad_i64_i32 holds afterwards: the hardware overwrites vcc / the SGPR pair with a per-lane signed-overflow
+    bit nobody here means to use, so code that reads it as a mask or as a carry-in relies on a value the instruction destroyed. (v_mad_u64_u32
+    writes the true carry of its 64-bit addition there, and the limb-form product chains of tools/gen_fp_asm.py add it up: that one is modelled.)"""
+    def __repr__(self):
+        return "<carry register overwritten by v_mad_i64_i32>"
+
+
+POISON = _Poison()
+
+
+def _shift(count, limit, line):
+    assert 0 <= count < limit, "shift count %d outside 0..%d (the hardware would use it modulo %d): %s" % (count, limit - 1, limit, line)
+    return count
 
 
 class Machine:
@@ -60,13 +77,17 @@ class Machine:
         if k == "imm":
             return i
         if k == "s":
+            assert self.s.get(("pair", i & ~1)) is not POISON, "s%d read after a v_mad_i64_i32 overwrote its pair" % i
             return self.s[i]
         if k == "a":
             return self.a[i]
         if k == "vcc":
+            assert self.vcc is not POISON, "vcc read after a v_mad_i64_i32 overwrote it"
             return self.vcc
         if k == "s2":
-            return self.s.get(("pair", i), 0)
+            r = self.s.get(("pair", i), 0)
+            assert r is not POISON, "s[%d:%d] read after a v_mad_i64_i32 overwrote it" % (i, i + 1)
+            return r
         if k == "exec":
             return self.exec_on if self.model_exec else 1
         return self.v[i] | (self.v[i + 1] << 32)     # v2
@@ -157,15 +178,15 @@ class Machine:
                 self.wr(args[0], t); self.wr_carry(args[1], 1 if t < 0 else 0)
             elif op == "v_mad_u64_u32":
                 t = self.rd(args[2]) * self.rd(args[3]) + self.rd(args[4])
-                self.wr(args[0], t & 0xFFFFFFFFFFFFFFFF); self.wr_carry(args[1], t >> 64)
+                self.wr(args[0], t & 0xFFFFFFFFFFFFFFFF); self.wr_carry(args[1], t >> 64)       # unsigned: a true carry, which fp_mul_body's chains consume
             elif op == "v_mad_i64_i32":
                 t = s32(self.rd(args[2])) * s32(self.rd(args[3])) + s64(self.rd(args[4]))
                 assert -(1 << 63) <= t < (1 << 63), "signed 64-bit accumulator overflow: " + line
-                self.wr(args[0], t & 0xFFFFFFFFFFFFFFFF)
+                self.wr(args[0], t & 0xFFFFFFFFFFFFFFFF); self.wr_carry(args[1], POISON)
             elif op == "v_ashrrev_i64":
-                self.wr(args[0], (s64(self.rd(args[2])) >> self.rd(args[1])) & 0xFFFFFFFFFFFFFFFF)
+                self.wr(args[0], (s64(self.rd(args[2])) >> _shift(self.rd(args[1]), 64, line)) & 0xFFFFFFFFFFFFFFFF)
             elif op == "v_ashrrev_i32_e64":
-                self.wr(args[0], s32(self.rd(args[2])) >> self.rd(args[1]))
+                self.wr(args[0], s32(self.rd(args[2])) >> _shift(self.rd(args[1]), 32, line))
             elif op == "v_cvt_f32_i32_e64":
                 self.wr(args[0], f32_bits(float(s32(self.rd(args[1])))))
             elif op == "v_mul_f32_e64":
@@ -192,15 +213,15 @@ class Machine:
             elif op in ("v_and_b32_e32", "v_and_b32_e64"):
                 self.wr(args[0], self.rd(args[1]) & self.rd(args[2]))
             elif op == "v_lshrrev_b32_e64":
-                self.wr(args[0], self.rd(args[2]) >> self.rd(args[1]))
+                self.wr(args[0], self.rd(args[2]) >> _shift(self.rd(args[1]), 32, line))
             elif op == "v_lshlrev_b32_e64":
-                self.wr(args[0], self.rd(args[2]) << self.rd(args[1]))
+                self.wr(args[0], self.rd(args[2]) << _shift(self.rd(args[1]), 32, line))
             elif op == "v_lshrrev_b64":
-                self.wr(args[0], self.rd(args[2]) >> self.rd(args[1]))
-            elif op == "v_lshl_add_u64":
-                self.wr(args[0], ((self.rd(args[1]) << self.rd(args[2])) + self.rd(args[3])) & 0xFFFFFFFFFFFFFFFF)
+                self.wr(args[0], self.rd(args[2]) >> _shift(self.rd(args[1]), 64, line))
+            elif op == "v_lshl_add_u64":                # the shift field of this instruction only goes up to 4
+                self.wr(args[0], ((self.rd(args[1]) << _shift(self.rd(args[2]), 5, line)) + self.rd(args[3])) & 0xFFFFFFFFFFFFFFFF)
             elif op == "v_lshl_add_u32":
-                self.wr(args[0], (self.rd(args[1]) << self.rd(args[2])) + self.rd(args[3]))
+                self.wr(args[0], (self.rd(args[1]) << _shift(self.rd(args[2]), 32, line)) + self.rd(args[3]))
             elif op == "v_mbcnt_lo_u32_b32":      # with the mask -1: the number of lanes below this one among lanes 0..31
                 assert args[1] == "-1"
                 self.wr(args[0], min(self.lane, 32) + self.rd(args[2]))
@@ -216,7 +237,7 @@ class Machine:
                 assert "quad_perm:[1,0,3,2]" in rest and "row_mask:0xf" in rest and "bank_mask:0xf" in rest, line
                 yield (args[0], args[1].split()[0])
             elif op == "v_lshl_or_b32":
-                self.wr(args[0], (self.rd(args[1]) << self.rd(args[2])) | self.rd(args[3]))
+                self.wr(args[0], (self.rd(args[1]) << _shift(self.rd(args[2]), 32, line)) | self.rd(args[3]))
             elif op == "v_sub_u32_e32":
                 self.wr(args[0], self.rd(args[1]) - self.rd(args[2]))
             elif op == "v_subrev_u32_e32":
@@ -226,10 +247,10 @@ class Machine:
             elif op == "v_cmp_gt_i32_e64":
                 self.wr_carry(args[0], 1 if s32(self.rd(args[1])) > s32(self.rd(args[2])) else 0)
             elif op == "v_lshlrev_b32_e32":
-                self.wr(args[0], self.rd(args[2]) << self.rd(args[1]))
+                self.wr(args[0], self.rd(args[2]) << _shift(self.rd(args[1]), 32, line))
             elif op == "v_alignbit_b32":
                 t = (self.rd(args[1]) << 32) | self.rd(args[2])
-                self.wr(args[0], t >> self.rd(args[3]))
+                self.wr(args[0], t >> _shift(self.rd(args[3]), 32, line))
             elif op in ("v_or_b32_e32", "v_or_b32_e64"):
                 self.wr(args[0], self.rd(args[1]) | self.rd(args[2]))
             elif op == "v_or3_b32":
@@ -272,7 +293,7 @@ class Machine:
                 o0, o1 = int(m.group(4) or 0), int(m.group(5) or 0)
                 self.lds[addr + o0 * 256] = self.rd(m.group(2)); self.lds[addr + o1 * 256] = self.rd(m.group(3))
             elif op == "v_add_f32_e64":
-                self.wr(args[0], f32_bits(bits_f32(self.rd(args[1])) + bits_f32(self.rd(args[2]))))
+                self.wr(args[0], f32_add_bits(self.rd(args[1]), self.rd(args[2])))
             elif op == "s_mul_i32":
                 self.wr(args[0], self.rd(args[1]) * self.rd(args[2]))
             elif op == "s_mul_hi_u32":
@@ -291,7 +312,7 @@ class Machine:
                 for q in range(4 if op.endswith("x4") else 1):
                     self.v[lo + q] = self.mem[addr + 4 * q]
             elif op == "v_lshlrev_b64":
-                self.wr(args[0], (self.rd(args[2]) << self.rd(args[1])) & 0xFFFFFFFFFFFFFFFF)
+                self.wr(args[0], (self.rd(args[2]) << _shift(self.rd(args[1]), 64, line)) & 0xFFFFFFFFFFFFFFFF)
             elif op == "v_cmp_gt_u32_e64":
                 self.wr_carry(args[0], 1 if self.rd(args[1]) > self.rd(args[2]) else 0)
             elif op == "v_cmp_le_u32_e64":
@@ -349,6 +370,31 @@ def run_pair(ma, mb, lines):
 def f32_bits(x):
     import struct
     return struct.unpack("<I", struct.pack("<f", x))[0]
+
+
+def f32_round(x):
+    """the f32 nearest to the exact rational x (ties to even), as a Python float: ONE rounding, where adding in doubles and rounding the 53-bit sum again can
+    land on the other neighbour. Finite, non-overflowing values only."""
+    if x == 0:
+        return 0.0
+    m = abs(x)
+    e = m.numerator.bit_length() - m.denominator.bit_length()
+    if m < Fraction(2) ** e:
+        e -= 1                                       # 2^e <= m < 2^(e+1)
+    ulp = Fraction(2) ** (max(e, -126) - 23)
+    r = round(m / ulp) * ulp                         # round() of a Fraction: to the nearest integer, ties to even
+    assert r < Fraction(2) ** 128, "f32 overflow"
+    return float(-r if x < 0 else r)
+
+
+def f32_add_bits(a, b):
+    """v_add_f32 on bit patterns (signs of zero follow IEEE round-to-nearest: -0 only from -0 + -0)"""
+    fa, fb = bits_f32(a), bits_f32(b)
+    assert fa == fa and fb == fb and abs(fa) != float("inf") and abs(fb) != float("inf"), "v_add_f32: NaN / infinity not modelled"
+    r = f32_round(Fraction(fa) + Fraction(fb))
+    if r == 0.0 and (a & M32) == 0x80000000 and (b & M32) == 0x80000000:
+        return 0x80000000
+    return f32_bits(r)
 
 
 def bits_f32(b):

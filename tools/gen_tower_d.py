@@ -379,19 +379,115 @@ class Bound:
         return "B(d[%.2f,%.2f] v[%.2fp,%.2fp])" % (self.dlo / (1 << 28), self.dhi / (1 << 28), self.vlo / P, self.vhi / P)
 
 
+def norm_ok(B):
+    """what seq_norm needs: every digit PLUS the carry that reaches it stays a signed 32-bit number (fits() alone does not say so: 2^31 - 1 plus a carry
+    of 7 wraps)"""
+    chi = clo = 0
+    for _ in range(3):
+        chi, clo = (max(B.dhi, 0) + chi) >> 28, (min(B.dlo, 0) + clo) >> 28
+    return (max(B.dhi, B.thi) + chi < (1 << 31)) and (min(B.dlo, B.tlo) + clo >= -(1 << 31))
+
+
 def product_bound(pairs):
     """result of a Montgomery scan over the listed (a, b) operand bounds: digits normalised, value in (-X, p + X)"""
     X = sum(a.vabs() * b.vabs() for a, b in pairs) // R392 + 2
-    return Bound.normalised(-X, P + X)
+    res = Bound.normalised(-X, P + X)
+    assert res.fits(), ("the top digit of a product does not fit a register", res)
+    return res
 
 
 STATE_IN = None
 REDUCED = Bound.normalised(-(P // 2) - (P >> 10), (P // 2) + (P >> 10))      # after `reduce`: the representative nearest to zero
 
 
-STATE_IN = Bound.normalised(REDUCED.vlo, P)         # a loop-carried value: canonical on entry of a routine, reduced afterwards
+# ... for inputs up to about 740 p: beyond that the quotient estimate is off by more than p / 1024 (reduced_bound() below hands out the bound that
+# holds). REDUCED_ANY contains the result of seq_reduce for EVERY input whose top digit fits a register (eps < 1/32 up to 2^31 / PTOP = 20163 p): it is what
+# "reduced" means wherever a later step only needs |v| < p -- the zero test, the canonical pass, a value carried into the next round of a loop.
+REDUCED_ANY = Bound.normalised(-(P // 2) - (P >> 5), (P // 2) + (P >> 5))
+STATE_IN = Bound.normalised(REDUCED_ANY.vlo, P)     # a loop-carried value: canonical on entry of a routine, reduced afterwards
 PACKED = Bound.normalised(P // 2 - (P >> 10), P + P // 2 + (P >> 10))      # a value parked in LDS by seq_pack_pass
+
+
+# ---- what the quotient estimate of seq_reduce / seq_pack_pass guarantees, as a function of what goes in
+# x = t 2^364 + L (t the top digit, L the lower digits), p = PTOP 2^364 + pl, lam = L / 2^364, pi = pl / 2^364 (0.1197...):
+#     x / p - t / PTOP = lam / (PTOP + pi) - t pi / (PTOP (PTOP + pi))                      the neglected lower digits of x and of p
+#     est = fl(fl(t) * RECIP) = (t / PTOP) (1 + d1)(1 + dc)(1 + d2)                           |d1|, |d2| <= 2^-24 (d1 = 0 for |t| <= 2^24), dc: the constant's
+#     pack pass only: fl(est - 1) adds at most 2^-24 |est - 1|
+#     q = rndne(est): |q - est| <= 1/2, exact in f32 and in the conversion back (|est| < 2^31 / PTOP < 2^15)
+# so |x - q p| <= (1/2 + eps) p with eps = the sum of the terms above at their bounds. The second term grows with |x|: about 1.3e-6 per p, which is
+# why the slack p / 1024 of REDUCED / PACKED is PROVED only for |x| up to about 740 p (normalised digits) and the bound handed out beyond that carries eps.
+def estimate_error(vabs, dlo=0, dhi=M28, pack=False, tmag=None):
+    """eps (an exact Fraction) for a value |x| <= vabs whose digits 0..12 lie in [dlo, dhi] (and whose top digit is at most tmag in magnitude, where
+    the caller tracks that separately)"""
+    from fractions import Fraction as Fr
+    import struct
+    s = sum(1 << (28 * j) for j in range(13))
+    lam = Fr(max(abs(dlo), abs(dhi)) * s, 1 << 364)
+    top = Fr(vabs, 1 << 364) + lam                                     # |t|
+    if tmag is not None:
+        top = min(top, Fr(tmag))
+    assert top < (1 << 31), "the top digit does not fit a register"
+    pi = Fr(P & ((1 << 364) - 1), 1 << 364)
+    recip = Fr(struct.unpack(">f", bytes.fromhex(RECIP_PTOP[2:]))[0])    # the constant the routines load, exactly
+    u = Fr(1, 1 << 24)
+    dc = abs(recip * PTOP - 1)
+    eps = lam / PTOP + top * pi / (PTOP * (PTOP + pi))
+    fl = (1 + (u if top > (1 << 24) else 0)) * (1 + dc) * (1 + u) - 1
+    eps += top / PTOP * fl
+    if pack:
+        eps += u * (top / PTOP * (1 + fl) + 1)
+    return eps
+
+
+def _slack(B, pack):
+    eps = estimate_error(B.vabs(), B.dlo, B.dhi, pack, max(abs(B.tlo), abs(B.thi)))
+    return max(P >> 10, -((-eps.numerator * P) // eps.denominator))     # never below the fixed slack: small inputs keep REDUCED / PACKED as they were
+
+
+def reduced_bound(B):
+    """the bound of seq_reduce's result for an input inside B: REDUCED itself wherever its slack is proved, wider where it is not"""
+    sl = _slack(B, False)
+    assert sl <= P >> 5, ("outside REDUCED_ANY", B)
+    return REDUCED if sl == P >> 10 else Bound.normalised(-(P // 2) - sl, (P // 2) + sl)
+
+
+def packed_bound(B):
+    sl = _slack(B, True)
+    return PACKED if sl == P >> 10 else Bound.normalised(P // 2 - sl, P + P // 2 + sl)
+
+
+# every place that emits seq_reduce / seq_pack_pass notes (site, pass, input bound, the result bound it goes on with) here while the routines are generated:
+# tests/test_dform_cases_cpu.py walks the list (the recorded inputs are where it searches for the worst case, and every result bound must carry eps)
+QSITES = []
+
+
+def qsite(site, kind, B, res=None, need=None):
+    """kind: 'reduce' / 'pack'. res: the bound the caller records for the result (default: the derived one). need: what the code after the pass relies on
+    (for the hand-written shells, which keep no bounds: asserted here)"""
+    assert B.vabs() < (P << 16), (site, "quotient estimate out of range", B)
+    res = res or (packed_bound(B) if kind == "pack" else reduced_bound(B))
+    if need is not None:
+        assert need.vlo <= res.vlo and res.vhi <= need.vhi, (site, res, need)
+    QSITES.append((site, kind, B, res))
+    return res
+
+
+CANON_IN = Bound.normalised(-P + 1, P - 1)          # what seq_canonical accepts
+SHELL_STATE = Bound.normalised(-16 * P, 16 * P)     # contains STATE_IN, F_IN and G2_IN: whatever a body leaves in the AGPRs for its shell's epilogue
+
+
+def k384_site(site, state=None, k=None):
+    """the shells' way out of the 2^392 domain -- CALL mulfp by the constant 2^384 mod p (or k), seq_reduce, seq_canonical, seq_to32 --: the reduction's
+    input is the product (-X, p + X), X = 16 p k / 2^392 + 2 < p / 150; the canonical pass after it needs (-p, p)"""
+    k = K384 if k is None else k
+    return qsite(site, "reduce", product_bound([(state or SHELL_STATE, Bound(0, M28, k >> 364, k >> 364, k, k))]), need=CANON_IN)
+WORDS_IN = Bound.normalised(1, (1 << 384) - 1)      # what seq_to32 packs without loss (digits normalised, top digit below 2^20)
 G_IN = Bound(0, M28, 0, M28, 0, (1 << 392) - 1)     # 12 words (2^384 domain) cut as digits of words * 2^8: the 2^392 domain, unreduced
+# the same cut of CANONICAL words (below p): below 256 p. For inputs that only this library writes, always canonical: the records of the resident key table
+# (k_keytable_append stores decoded coordinates) and the Miller values of the product tree (f_out_epilogue ends in seq_canonical). Under G_IN's 2520 p a value
+# selected or summed from such inputs is too wide for the reduction that follows to return it inside STATE_IN, and a product of two sums of them (X = 20162 p)
+# too wide for its own top digit.
+G_CANON_IN = Bound(0, M28, 0, ((P - 1) << 8) >> 364, 0, (P - 1) << 8)
 GBASE, GSTRIDE, GADDR, GT0, GT1 = "s[68:69]", "s70", "s[74:75]", "s76", "s77"   # HBM workspace: base (adjusted by the caller so that
 # LADDR is the lane offset), bytes between consecutive words of a value, running address, temporaries
 
@@ -508,7 +604,8 @@ def seq_qpass(reg, setup):
 
 def seq_reduce(reg):
     """value -> the representative nearest to zero, digits normalised: q = rndne(top digit / top digit of p) in floating point (the
-    unnormalised lower digits and the lower digits of p move the estimate by < 2e-4)"""
+    unnormalised lower digits, the lower digits of p and the f32 roundings move the estimate by estimate_error(): about 1.3e-6 per p of the
+    input, below 1 / 1024 up to about 740 p -- reduced_bound() is the bound that holds for a given input)"""
     return seq_qpass(reg, ["v_cvt_f32_i32_e64 %s, %s" % (NQ, reg(13)), "v_mul_f32_e64 %s, %s, %s" % (NQ, RECIP_PTOP_S, NQ), "v_rndne_f32_e64 %s, %s" % (NQ, NQ),
                            "v_cvt_i32_f32_e64 %s, %s" % (NQ, NQ), "v_sub_u32_e64 %s, 0, %s" % (NQ, NQ)])
 
@@ -820,6 +917,7 @@ class AllocD:
         b = self.to_vgpr(v, k)
         if ok is None or not ok(self.bound[v]):
             self.wait_lds()
+            assert norm_ok(self.bound[v]), ("carry pass: a digit plus its carry overflows", self.bound[v])
             for l in seq_norm(lambda j: "v%d" % (vb(b) + j)):
                 self.e(l)
             self.stats["norm"] += 39
@@ -833,11 +931,11 @@ class AllocD:
         if self.bound[v].dlo >= 0 and self.bound[v].dhi <= M28:
             b = self.to_vgpr(v, k)
             self.wait_lds()
-            assert self.bound[v].vabs() < (P << 16)
+            res = qsite("narrow", "reduce", self.bound[v])
             for l in seq_reduce(lambda j: "v%d" % (vb(b) + j)):
                 self.e(l)
             self.stats["reduce"] += 60
-            self.bound[v] = REDUCED
+            self.bound[v] = res
         else:
             self.ensure(v, k)
 
@@ -953,7 +1051,7 @@ class AllocD:
     def do_reduce(self, k, d, a):
         b = self.to_vgpr(a, k)
         self.wait_lds()
-        assert self.bound[a].vabs() < (P << 16), ("reduce: quotient estimate out of range", self.bound[a])
+        res = qsite("do_reduce", "reduce", self.bound[a])
         if self.next_use(a, k + 1) != INF:                  # the operand lives on: work on a copy
             nb = self.alloc_v(k, avoid=(b,))
             self.copy(("v", b), ("v", nb)); b = nb
@@ -963,7 +1061,7 @@ class AllocD:
             self.e(l)
         self.stats["reduce"] += 60
         self.place(d, ("v", b))
-        self.bound[d] = REDUCED
+        self.bound[d] = res
 
     def do_scale(self, k, d, a, c):
         """d = c a for a small positive constant: a shift or one multiplication by an inline constant per digit; where c a would
@@ -984,6 +1082,7 @@ class AllocD:
                 assert B.mag() > (1 << 28) + 64, ("scale: digit overflow", B, c)
                 if src != bd:
                     self.copy(("v", src), ("v", bd)); src = bd
+                assert norm_ok(B), ("carry pass: a digit plus its carry overflows", B)
                 for l in seq_norm(lambda j: "v%d" % (vb(bd) + j)):
                     self.e(l)
                 self.stats["norm"] += 39
@@ -1010,6 +1109,7 @@ class AllocD:
             self.copy(("v", b), ("v", nb)); b = nb
         else:
             self.release(a)
+        assert norm_ok(self.bound[a]), ("carry pass: a digit plus its carry overflows", self.bound[a])
         for l in seq_norm(lambda j: "v%d" % (vb(b) + j)):
             self.e(l)
         self.stats["norm"] += 39
@@ -1039,17 +1139,17 @@ class AllocD:
         b = self.to_vgpr(a, k)
         self.wait_lds()
         B = self.bound[a]
-        red = B.vlo >= REDUCED.vlo and B.vhi <= REDUCED.vhi and B.dlo >= 0 and B.dhi <= M28
+        red = B.vlo >= REDUCED_ANY.vlo and B.vhi <= REDUCED_ANY.vhi and B.dlo >= 0 and B.dhi <= M28
         if self.next_use(a, k + 1) != INF and not red:          # the operand lives on unreduced: test a copy
             nb = self.alloc_v(k, avoid=(b,))
             self.copy(("v", b), ("v", nb)); b = nb
         if not red:
-            assert B.vabs() < (P << 16)
+            res = qsite("do_iszero", "reduce", B, need=CANON_IN)      # the test below needs |v| < p
             for l in seq_reduce(lambda j: "v%d" % (vb(b) + j)):
                 self.e(l)
             self.stats["reduce"] += 60
             if self.loc.get(a) == ("v", b):
-                self.bound[a] = REDUCED
+                self.bound[a] = res
         self.e("v_or_b32_e64 %s, v%d, v%d" % (TMP, vb(b), vb(b) + 1))
         for j in range(2, 14, 2):
             self.e("v_or3_b32 %s, %s, v%d, v%d" % (TMP, TMP, vb(b) + j, vb(b) + j + 1))
@@ -1070,7 +1170,9 @@ class AllocD:
             assert self.next_use(x, k + 1) == INF
             reg = lambda j, b=b: "v%d" % (vb(b) + j)
             B = self.bound[x]
-            red = B.vlo >= REDUCED.vlo and B.vhi <= REDUCED.vhi and B.dlo >= 0 and B.dhi <= M28
+            red = B.vlo >= REDUCED_ANY.vlo and B.vhi <= REDUCED_ANY.vhi and B.dlo >= 0 and B.dhi <= M28
+            if not red:
+                qsite("do_sgn0", "reduce", B, need=CANON_IN)
             for l in ([] if red else seq_reduce(reg)) + seq_canonical(reg):
                 self.e(l)
             regs.append(b)
@@ -1094,7 +1196,7 @@ class AllocD:
         b = self.to_vgpr(a, k)
         self.wait_lds()
         B = self.bound[a]
-        assert B.vlo >= REDUCED.vlo and B.vhi <= REDUCED.vhi and B.dlo >= 0 and B.dhi <= M28, ("inv: operand not reduced", B)
+        assert B.vlo >= REDUCED_ANY.vlo and B.vhi <= REDUCED_ANY.vhi and B.dlo >= 0 and B.dhi <= M28, ("inv: operand not reduced", B)
         assert self.next_use(a, k + 1) == INF
         reg = lambda j: "v%d" % (vb(b) + j)
         for l in seq_canonical(reg) + seq_to32(reg):
@@ -1168,14 +1270,14 @@ class AllocD:
             self.copy(("v", b), ("v", nb)); b = nb
         else:
             self.release(a)
-        assert self.bound[a].vabs() < (P << 16)
+        res = qsite("do_storep", "pack", self.bound[a], need=WORDS_IN)
         reg = lambda j: "v%d" % (vb(b) + j)
         for l in seq_pack_pass(reg) + seq_to32(reg) + seq_gstore(reg, slot, koff=(kind == "gk")):
             self.e(l)
         self.stats["reduce"] += 62 + 21 + 38
         if self.next_use(a, k + 1) != INF:                  # from now on the slot is a home of the value: register copies of it can be
             self.home[a] = (kind, slot)                     # dropped and fetched again (same value, the packed representative)
-            self.home_bound[a] = PACKED
+            self.home_bound[a] = res
 
     def call_limits_ok(self, kind, B):
         m = [x.mag() for x in B]
@@ -1499,7 +1601,7 @@ def build_cyc_sqr_d():
     al = AllocD(p, inb, n_lds=11, lds_base=0, a_pool=list(range(12, NA)))
     body = al.run()
     for dst, B in al.stored.items():
-        assert B.vlo >= REDUCED.vlo and B.vhi <= REDUCED.vhi and B.dlo >= 0 and B.dhi <= M28, (dst, B)
+        assert B.vlo >= REDUCED_ANY.vlo and B.vhi <= REDUCED_ANY.vhi and B.dlo >= 0 and B.dhi <= M28, (dst, B)
     return body, al.stats
 
 
@@ -1780,6 +1882,7 @@ def f_out_epilogue(ret="s[36:37]"):
         epi += ["v_accvgpr_read_b32 %s, a%d" % (B1(j), vb(2 * i + 1) + j) for j in range(14)]
         epi += ["CALL mbls_fp2_mulfp_d_asm_fn"]
         for h, B in ((0, B5), (1, B6)):
+            k384_site("f_out_epilogue")             # input bound: a product by the constant, |v| < 1.01 p
             epi += seq_reduce(B) + seq_canonical(B) + seq_to32(B)
             epi += ["v_mov_b32_e64 v%d, %s" % (F_OUT[2 * i + h] + j, B(j)) for j in range(12)]
     epi += ["s_mov_b64 s[30:31], %s" % ret]
@@ -1815,6 +1918,10 @@ def miller_loop_d_routine(pairs=(0, 1), pair_mode=False):
                     pro += ["v_mov_b32_e32 %s, 0x%08x" % (W(j), dgt) for j, dgt in enumerate(digits_of(ONE_D if i == 0 else 0))]
                 else:
                     pro += seq_gload(W, sl[i], True)
+                # input bound: the constant 1, or CANONICAL words cut as digits of words * 2^8 (below 256 p) -- the point set-up of the compiled code
+                # (mbls_fp.h keeps every Fp value below p) writes these slots. The bodies are generated under PACKED for them; arbitrary words (G_IN,
+                # 2520 p) would come out as far as 0.4967 p .. 1.5033 p
+                qsite("miller_prologue", "pack", G_CANON_IN, need=PACKED)
                 pro += seq_pack_pass(W) + seq_to32(W) + seq_gstore(W, T_SLOT(k, e, i))
     # control flow (every far jump goes backwards): the first iteration (f = 1: the lines ARE f), then
     #   5: addition step(s); phase += 1;  4: RUNS[phase] doubling iterations;  phase == 5 ? done : back to 5
@@ -2157,6 +2264,20 @@ VBLK = lambda b: (lambda j: "v%d" % (vb(b) + j))
 CS2_CU, CS2_CV, CS2_LANE = "v84", "v85", "v86"          # block 6: scratch of the squarings, free between them
 
 
+def csqr2_reduce_in():
+    """what the reductions at the end of csqr2_body take, for a state inside REDUCED_ANY (pstart2_body and csqr2_body itself leave it there): 3 w +- 2 z with
+    w one of first = xi v^2 + u^2, second = (u + v)^2 - u^2 - v^2, xi second (after a carry pass) and z the partner's state"""
+    S = REDUCED_ANY
+    sq = lambda a: AllocD.call_bounds(None, "sqr", [a[0], a[1]])
+    t0, t1, q = sq((S, S)), sq((S, S)), sq((S + S, S + S))
+    second = (q[0] - t0[0] - t1[0], q[1] - t0[1] - t1[1])
+    first = (t1[0] - t1[1] + t0[0], t1[0] + t1[1] + t0[1])
+    xis = (second[0] - second[1], second[0] + second[1])
+    V = 3 * max(b.vabs() for b in second + first + xis) + 2 * S.vabs()
+    # digits: 3 w_j + c z_j with c = -2 or 2 (CS2_CU / CS2_CV, chosen by the lane's role), w_j and z_j in [0, 2^28) after the carry pass / the last reduction
+    return Bound(-2 * M28, 5 * M28, -(V >> 364) - 8, (V >> 364) + 8, -V, V)
+
+
 def csqr2_body():
     """one compressed squaring on a pair of lanes (see above); roles swap at the end"""
     U0, U1, V0, V1 = VBLK(0), VBLK(1), VBLK(2), VBLK(3)
@@ -2184,6 +2305,7 @@ def csqr2_body():
     L += ["v_cndmask_b32_e64 %s, -2, 2, %s" % (CS2_CU, ROLE), "v_cndmask_b32_e64 %s, 2, -2, %s" % (CS2_CV, ROLE)]
     for (w, part, dst, c) in ((B[8], B[16], U0, CS2_CU), (B[9], B[17], U1, CS2_CU), (B[14], B[10], V0, CS2_CV), (B[15], B[11], V1, CS2_CV)):
         L += seq_norm(w)                                                         # digits into [0, 2^28): 3 w + 2 p stays far inside 32 bits
+        qsite("csqr2_body", "reduce", csqr2_reduce_in(), need=REDUCED_ANY)        # input bound: |3 w +- 2 z| < 13.1 p, digits in [-2, 5] 2^28, see csqr2_reduce_in
         for j in range(14):
             L += ["v_mul_lo_u32 %s, %s, %s" % (part(j), part(j), c), "v_lshl_add_u32 %s, %s, 1, %s" % (dst(j), w(j), part(j)),
                   "v_add_u32_e64 %s, %s, %s" % (dst(j), dst(j), w(j))]
@@ -2201,6 +2323,7 @@ def pstart2_body():
         dst = VBLK(k)
         L += seq_gload(dst, Y_SLOT + C_IDX[k], aform=False) + seq_gload(T, Y_SLOT + C_IDX[4 + k], aform=False)
         L += ["v_cndmask_b32_e64 %s, %s, %s, %s" % (dst(j), dst(j), T(j), ROLE) for j in range(14)]
+        qsite("pstart2_body", "reduce", Bound.normalised(0, (1 << 384) - 1), need=REDUCED_ANY)      # input bound: 12 words as they are, below 2^384 = 9.9 p
         L += seq_reduce(dst)
     return L
 
@@ -2214,6 +2337,7 @@ def psave2_body():
     for k in range(4):
         src = VBLK(k)
         L += ["v_mov_b64_e64 v[%d:%d], v[%d:%d]" % (vb(4) + j, vb(4) + j + 1, vb(k) + j, vb(k) + j + 1) for j in range(0, 14, 2)]
+        qsite("psave2_body", "pack", REDUCED_ANY, need=WORDS_IN)                  # input bound: the state, reduced
         L += seq_pack_pass(T) + seq_to32(T) + seq_gstore(T, K_SLOT + k, koff=True, lane=CS2_LANE)
     return L
 
@@ -2359,7 +2483,7 @@ def prog_g1_dbl(src=5):
 
 def build_g1(which):
     p = prog_g1_dbl() if which == "dbl" else prog_g1_step(which)
-    key_in = G1_RAW_IN if which in G1_RAW_MODES else G_IN
+    key_in = G1_RAW_IN if which in G1_RAW_MODES else G_CANON_IN
     inb = {v: (STATE_IN if l[0] == "a" else key_in) for v, l in p.init_loc.items()}
     al = AllocD(p, inb, n_lds=0, a_pool=list(range(8, NA)), free_v=G1_FREE_V)
     body = al.run()
@@ -2473,6 +2597,7 @@ def g1_aggregate_d_routine(mode):
         epi += ["v_accvgpr_read_b32 %s, a%d" % (B1(j), vb(srcs[1]) + j) for j in range(14)]
         epi += ["CALL mbls_fp2_mulfp_d_asm_fn"]
         for h, B in ((0, B5), (1, B6))[:2 if half == 0 else 1]:
+            k384_site("g1_aggregate_epilogue", STATE_IN, K384_ISO if half == 1 and mode == "rawiso" else K384)      # input bound: |v| < 1.01 p
             epi += seq_reduce(B) + seq_canonical(B) + seq_to32(B)
             if half == 1:
                 epi += ["v_or_b32_e64 v211, %s, %s" % (B(0), B(1))] + ["v_or3_b32 v211, v211, %s, %s" % (B(j), B(j + 1)) for j in range(2, 12, 2)]
@@ -2516,6 +2641,7 @@ def g2_dbl_d_routine():
     W = lambda j: "v%d" % j
     pro = ["s_mov_b32 s39, s38"]
     for i in range(6):                              # words * 2^8 can be 256 p: reduce, so that the bounds the body was generated under hold
+        qsite("g2_dbl_prologue", "reduce", G_IN, need=G2_IN)    # input bound: any 12 words, below 2^392 = 2520 p (the callers pass canonical ones: 256 p)
         pro += seq_conv(W, ["v%d" % (G2D_ARG[i] + q) for q in range(12)], True) + seq_reduce(W)        # from the first round on
         pro += ["v_accvgpr_write_b32 a%d, v%d" % (vb(i) + j, j) for j in range(14)]
     B0, B1, B2, B5, B6 = (lambda j: "v%d" % j), (lambda j: "v%d" % (14 + j)), (lambda j: "v%d" % (28 + j)), (lambda j: "v%d" % (70 + j)), (lambda j: "v%d" % (84 + j))
@@ -2525,6 +2651,7 @@ def g2_dbl_d_routine():
         epi += ["v_accvgpr_read_b32 %s, a%d" % (B1(j), vb(2 * i + 1) + j) for j in range(14)]
         epi += ["CALL mbls_fp2_mulfp_d_asm_fn"]
         for h, B in ((0, B5), (1, B6)):
+            k384_site("g2_dbl_epilogue", G2_IN)             # input bound: |v| < 1.01 p
             epi += seq_reduce(B) + seq_canonical(B) + seq_to32(B)
             epi += ["v_mov_b32_e64 v%d, %s" % (G2D_ARG[2 * i + h] + j, B(j)) for j in range(12)]
     full = wrap_loop_d(expand_calls_d(body), "s39", pro, expand_calls_d(epi))
@@ -2894,6 +3021,7 @@ def g2_group_routine(kind, two_lane=False):
             epi += ["v_accvgpr_read_b32 %s, a%d" % (B1(j), vb(2 * i + 1) + j) for j in range(14)]
             epi += ["CALL mbls_fp2_mulfp_d_asm_fn"]
             for h, Bk in ((0, B5), (1, B6)):
+                k384_site("g2_group_epilogue")        # input bound: |v| < 1.01 p
                 epi += seq_reduce(Bk) + seq_canonical(Bk) + seq_to32(Bk) + seq_gstore(Bk, S["H"] + 2 * i + h)
     else:
         main = X("s_start") + call_ladder() + X("s_compare")
@@ -2920,7 +3048,7 @@ def f12_tree_routine():
     """In:  slots 13..24 of this lane's item and of the item s71 bytes further on (Miller values, 2^384 domain); v252 / s[68:69] / s70 as in the
     other routines (11 LDS spill slots). Out: their product in v108..v251 (twelve groups of 12 words, canonical, 2^384 domain)."""
     p = prog_f12_treemul()
-    inb = {v: G_IN for v in p.init_loc}
+    inb = {v: G_CANON_IN for v in p.init_loc}
     al = AllocD(p, inb, n_lds=11, lds_base=0, a_pool=list(range(NA)))
     body = al.run()
     for dst, B in al.stored.items():
@@ -2964,6 +3092,7 @@ def g2_tree_routine():
         epi += ["v_accvgpr_read_b32 %s, a%d" % (B1(j), vb(2 * i + 1) + j) for j in range(14)]
         epi += ["CALL mbls_fp2_mulfp_d_asm_fn"]
         for h, Bk in ((0, B5), (1, B6)):
+            k384_site("g2_blind_epilogue")        # input bound: |v| < 1.01 p
             epi += seq_reduce(Bk) + seq_canonical(Bk) + seq_to32(Bk) + seq_gstore(Bk, BL_OUT + 2 * i + h)
     epi += ["s_waitcnt vmcnt(0)", "s_mov_b64 s[30:31], s[80:81]"]
     return pro + main + expand_calls_d(epi), dict(bodies, pro=pro, epi=epi), {}
@@ -3122,6 +3251,7 @@ def g1_blind_routine():
         epi += ["v_accvgpr_read_b32 %s, a%d" % (B1(j), vb(srcs[1]) + j) for j in range(14)]
         epi += ["CALL mbls_fp2_mulfp_d_asm_fn"]
         for h, Bk in ((0, B5), (1, B6))[:2 if half == 0 else 1]:
+            k384_site("g1_blind_epilogue")        # input bound: |v| < 1.01 p
             epi += seq_reduce(Bk) + seq_canonical(Bk) + seq_to32(Bk) + seq_gstore(Bk, 2 * half + h)
     epi += ["s_waitcnt vmcnt(0)", "s_mov_b64 s[30:31], s[80:81]"]
     ret = ["s_setpc_b64 s[30:31]"]
@@ -3196,6 +3326,7 @@ def g2_blind_routine(ct=False, two_lane=False):
         epi += ["v_accvgpr_read_b32 %s, a%d" % (B1(j), vb(2 * i + 1) + j) for j in range(14)]
         epi += ["CALL mbls_fp2_mulfp_d_asm_fn"]
         for h, Bk in ((0, B5), (1, B6)):
+            k384_site("g2_blind_epilogue")        # input bound: |v| < 1.01 p
             epi += seq_reduce(Bk) + seq_canonical(Bk) + seq_to32(Bk) + seq_gstore(Bk, BL_OUT + 2 * i + h)
     epi += ["s_waitcnt vmcnt(0)", "s_mov_b64 s[30:31], s[80:81]"]
     ret = ["s_setpc_b64 s[30:31]"]
@@ -3203,10 +3334,61 @@ def g2_blind_routine(ct=False, two_lane=False):
     return pro + main + expand_calls_d(epi) + ret + lad + dbl4 + subs, pieces, st
 
 
-def main():
-    here = os.path.dirname(os.path.abspath(__file__))
-    # MBLS_GEN_OUT_DIR: write there instead of over the tracked file (the freshness tests generate into a temporary directory and compare)
-    path = os.path.join(os.environ.get("MBLS_GEN_OUT_DIR") or os.path.join(os.path.dirname(here), "milagro_bls_amd", "csrc"), "mbls_towerd_asm.inc")
+# ---------------------------------------------------------------------------------------------- raw-register probes (test-only kernel k_dform_probe)
+# One generated body per lane, fed with RAW register contents: the leaves of tools/gen_fpd_asm.py and the passes above run on the GPU on the inputs their own
+# limits admit -- redundant digits up to 2^31, columns at the column_ok limit, quotient estimates at their rounding edges -- and every register they leave is compared
+# with tools/asm_sim.py (tests/test_gpu_dform.py). A probe loads its input registers from in[w * n + lane] (w = 0, 1, ...: the listed registers in order), loads
+# the resident constants like every shell, runs the body exactly as the routines contain it and stores the listed output registers to out[w * n + lane].
+# In: s[66:67] = in, s[68:69] = out (both advanced by the probe), s70 = 4 n, v252 = 4 lane.
+PROBE_IN, PROBE_OUT, PROBE_STRIDE = ("s66", "s67", "s[66:67]"), ("s68", "s69", "s[68:69]"), "s70"
+PROBE_BLK = 8                                     # the block the pass probes work in (v112..v125)
+
+
+def probe_ops():
+    """[(name, input registers, output registers, body)]; the index in this list is the op number of mbls_dform_probe"""
+    from gen_fpd_asm import ROUTINE_BODIES
+    blk = lambda b: ["v%d" % (vb(b) + j) for j in range(14)]
+    ops = []
+    outs = {r["name"]: r["outs"] for r in ROUTINES.values()}
+    for sym, fn in ROUTINE_BODIES.items():          # operands: blocks 0..3; stored: the operand blocks again (the contract says "preserved") and the result blocks
+        ops.append((sym[5:-7], blk(0) + blk(1) + blk(2) + blk(3), blk(0) + blk(1) + blk(2) + blk(3) + [r for b in outs[sym] for r in blk(b)], fn()))
+    reg = lambda j: "v%d" % (vb(PROBE_BLK) + j)
+    W = blk(PROBE_BLK)
+    ops.append(("norm", W, W, seq_norm(reg)))
+    ops.append(("reduce", W, W + [NQ], seq_reduce(reg)))
+    ops.append(("pack32", W, W + [NQ], seq_pack_pass(reg) + seq_to32(reg)))
+    ops.append(("canon32", W, W + [NQ], seq_canonical(reg) + seq_to32(reg)))
+    ops.append(("conv_reduce", W[2:], W + [NQ], seq_conv(reg, W[2:], True) + seq_reduce(reg)))      # 12 words, as seq_gload leaves them
+    return ops
+
+
+def probe_lines(ins, outs, body):
+    step = lambda r: ["s_add_u32 %s, %s, %s" % (r[0], r[0], PROBE_STRIDE), "s_addc_u32 %s, %s, 0" % (r[1], r[1])]
+    L = []
+    for r in ins:
+        L += ["global_load_dword %s, %s, %s" % (r, LADDR, PROBE_IN[2])] + step(PROBE_IN)
+    L += ["s_waitcnt vmcnt(0)"] + shell_constants() + list(body)
+    for r in outs:
+        L += ["global_store_dword %s, %s, %s" % (LADDR, r, PROBE_OUT[2])] + step(PROBE_OUT)
+    return L + ["s_waitcnt vmcnt(0)"]
+
+
+def emit_probes():
+    ops = probe_ops()
+    txt = "// raw-register probes of the digit-form leaves and passes (test-only: mbls_dform_probe)\n"
+    for name, ins, outs, body in ops:
+        txt += emit("MBLS_DFORM_PROBE_%s_ASM" % name.upper(), probe_lines(ins, outs, body)) + "\n"
+    txt += "#define MBLS_DFORM_PROBE_NOPS %d\n" % len(ops)
+    txt += "#define MBLS_DFORM_PROBE_NIN {%s}\n" % ", ".join(str(len(o[1])) for o in ops)
+    txt += "#define MBLS_DFORM_PROBE_NOUT {%s}\n" % ", ".join(str(len(o[2])) for o in ops)
+    txt += "#define MBLS_DFORM_PROBE_EACH(X) %s\n" % " ".join("X(%d, MBLS_DFORM_PROBE_%s_ASM)" % (i, o[0].upper()) for i, o in enumerate(ops))
+    sg = ",".join('"s%d"' % i for i in list(range(40, 48)) + list(range(56, 66)) + [73])
+    txt += "#define MBLS_DFORM_PROBE_CLOBBERS %s, %s, \"vcc\", \"scc\", \"memory\"\n" % (",".join('"v%d"' % i for i in range(256) if i != 252), sg)
+    return txt
+
+
+def generate_text():
+    """every routine, as the text of the generated file (tests call this to fill QSITES without writing anything)"""
     txt = "// GENERATED by tools/gen_tower_d.py -- do not edit.\n"
     body, stats = build_cyc_sqr_d()
     print("cyc_sqr_d", len(body), "lines", stats)
@@ -3297,6 +3479,15 @@ def main():
     sg = '"s30","s31","s36","s37","s39","s40","s41","s42","s43","s44","s45","s46","s47","s56","s57","s58","s59","s60","s61","s62","s63","s64","s65","s66","s67","s73","vcc","scc","memory"'
     txt += "#define MBLS_G2D_ASM_CLOBBERS %s,%s, \\\n    %s\n" % (
         ",".join('"v%d"' % i for i in range(256) if i not in g2r and i not in UNTOUCHED_V), ",".join('"a%d"' % i for i in range(252)), sg)
+    txt += emit_probes()
+    return txt
+
+
+def main():
+    here = os.path.dirname(os.path.abspath(__file__))
+    # MBLS_GEN_OUT_DIR: write there instead of over the tracked file (the freshness tests generate into a temporary directory and compare)
+    path = os.path.join(os.environ.get("MBLS_GEN_OUT_DIR") or os.path.join(os.path.dirname(here), "milagro_bls_amd", "csrc"), "mbls_towerd_asm.inc")
+    txt = generate_text()
     with open(path, "w") as f:
         f.write(txt)
     print("wrote", path)
