@@ -203,6 +203,61 @@ int mbls_fast_aggregate_verify_batch_indexed(mbls_ctx* ctx, const mbls_keytable*
                                              const uint64_t* msg_offsets, const uint32_t* key_idx, const uint32_t* offsets, uint64_t n,
                                              uint32_t k, uint8_t* results, uint32_t* status);
 
+/* ---- shared message lists: hash each distinct message once ------------------------------------------------
+ * The members of a committee sign the same message: a slot's gossip is tens of thousands of signatures over a few hundred distinct signing roots, and a batch
+ * that spells the message out per item hashes every one of them to G2 (the second largest kernel of the full round). These entries are the message side's
+ * counterpart of the key table: the call carries a LIST of n_msgs messages -- msg_len bytes each, or message j = msgs[msg_offsets[j] .. msg_offsets[j+1]) with a
+ * table of n_msgs + 1 entries -- and one uint32 per item: item i's message is message msg_idx[i]. The list is hashed once, in the form ITS size asks for (a few
+ * hundred messages take the wave engine whatever n is), and the message phase of every item is a 288-byte copy. results[i], status[i] and the bitmap are exactly
+ * what the entry without `_shared_msgs` returns for the same signatures and keys with item i's message spelled out. n_msgs may be smaller than, equal to or larger
+ * than n (unused messages are hashed and ignored); n = 0 returns MBLS_OK with nothing written.
+ * DEVICE ENTRIES (enqueue only; ordered against other users of the workspace like their neighbours): msg_idx[i] >= n_msgs (n_msgs = 0 included) rejects item i
+ * with MBLS_ST_BAD_MSG_RANGE and result 0; a listed message whose range runs backwards or is 2^32 bytes or more rejects every item that names it and nothing else.
+ * Neither becomes a read outside the call's buffers; such items check against H of the empty message, like the bad-range items of the per-item entries.
+ * HOST ENTRIES refuse a bad offset table, or an index >= n_msgs, with MBLS_ERR_ARGUMENT before anything is enqueued (results and status are left unwritten).
+ * ALLOCATION: the hashed points live in a table of the context (288 bytes per message), and the list is hashed in the call's workspace: a call whose list is
+ * larger than any before grows them first (which drains the device, see mbls_ctx_reserve). mbls_ctx_reserve_msgs(ctx, max_msgs) and
+ * mbls_ctx_reserve(ctx, mbls_plan_shared_msgs_workspace_items(...)) beforehand keep every allocation out of the call.
+ * Not covered: the verification stream and the mbls_multi handle take per-item messages only. */
+int mbls_ctx_reserve_msgs(mbls_ctx* ctx, uint64_t max_msgs);
+/* Routing as data (pure: no GPU, no context), beside mbls_plan_batch: `batch` is mbls_plan_batch(limits, n) with the message phase of every pass marked
+ * MBLS_MESSAGE_GATHER; the list of n_msgs messages is hashed in list_pieces pieces of list_piece_items messages (the last may be shorter; a piece is at most one
+ * round), in the form list_message (MBLS_MESSAGE_*, chosen by the size of a piece, not by n), message j of a piece in workspace item j of list_workspace_items
+ * (two per message on lane pairs). A plan of one pass hashes the list on the pass's message stream, beside its key sum and signature phases; a plan of several
+ * passes hashes it once, before the first. table_entries = n_msgs + 1 (the empty message's entry). n_msgs = 0: no pieces, list_message = 0. The SAME function
+ * the shared-message entries act on. MBLS_ERR_ARGUMENT for n = 0 or null pointers. */
+enum { MBLS_MESSAGE_GATHER = 5 };      /* k_h_gather: the item copies its message's point from the context's table */
+typedef struct mbls_shared_msgs_plan {
+    mbls_batch_plan batch;
+    uint32_t list_message, list_pieces;
+    uint64_t list_piece_items, list_workspace_items, table_entries;
+} mbls_shared_msgs_plan;
+int mbls_plan_batch_shared_msgs(const mbls_limits* limits, uint64_t n, uint64_t n_msgs, mbls_shared_msgs_plan* out);
+/* the workspace items such a call reserves before it queues anything: the larger of mbls_plan_workspace_items(limits, n, k, split_layout) and list_workspace_items */
+uint64_t mbls_plan_shared_msgs_workspace_items(const mbls_limits* limits, uint64_t n, uint64_t n_msgs, uint32_t k, int split_layout);
+/* mbls_fast_aggregate_verify_batch[_device] over a message list */
+int mbls_fast_aggregate_verify_batch_shared_msgs_device(mbls_ctx* ctx, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len,
+                                                        const uint64_t* d_msg_offsets, uint64_t n_msgs, const uint32_t* d_msg_idx, const uint8_t* d_pks,
+                                                        int pk_format, const uint32_t* d_pk_offsets, uint64_t n, uint32_t k, uint8_t* d_results,
+                                                        uint64_t* d_bitmap, uint32_t* d_status, void* stream);
+int mbls_fast_aggregate_verify_batch_shared_msgs(mbls_ctx* ctx, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* msg_offsets,
+                                                 uint64_t n_msgs, const uint32_t* msg_idx, const uint8_t* pks, int pk_format, const uint32_t* pk_offsets,
+                                                 uint64_t n, uint32_t k, uint8_t* results, uint32_t* status);
+/* mbls_verify_batch[_device] over a message list */
+int mbls_verify_batch_shared_msgs_device(mbls_ctx* ctx, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_msg_offsets,
+                                         uint64_t n_msgs, const uint32_t* d_msg_idx, const uint8_t* d_pks, int pk_format, uint64_t n,
+                                         uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream);
+int mbls_verify_batch_shared_msgs(mbls_ctx* ctx, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* msg_offsets, uint64_t n_msgs,
+                                  const uint32_t* msg_idx, const uint8_t* pks, int pk_format, uint64_t n, uint8_t* results, uint32_t* status);
+/* mbls_fast_aggregate_verify_batch_indexed[_device] over a message list: keys by table index, messages by list index */
+int mbls_fast_aggregate_verify_batch_indexed_shared_msgs_device(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* d_sigs, const uint8_t* d_msgs,
+                                                                uint32_t msg_len, const uint64_t* d_msg_offsets, uint64_t n_msgs, const uint32_t* d_msg_idx,
+                                                                const uint32_t* d_key_idx, const uint32_t* d_offsets, uint64_t n, uint32_t k,
+                                                                uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream);
+int mbls_fast_aggregate_verify_batch_indexed_shared_msgs(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
+                                                         const uint64_t* msg_offsets, uint64_t n_msgs, const uint32_t* msg_idx, const uint32_t* key_idx,
+                                                         const uint32_t* offsets, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status);
+
 /* ---- verification stream: many small calls packed into full rounds ---------------------------------------
  * The verification entries run at their full rate only when one call carries a whole round (CUs x 4 x 64 items, 65 536 on MI355X). A
  * stream takes calls of ANY size, hands back a ticket per call, packs the items of many calls back to back into full-round launches of

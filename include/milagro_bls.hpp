@@ -359,6 +359,31 @@ inline std::vector<bool> aggregate_verify_batch(const std::vector<AggregateSigna
     return out;
 }
 
+// n x AggregateSignature::fast_aggregate_verify (src/aggregates.rs:177-215) over a LIST of messages (mbls_fast_aggregate_verify_batch_shared_msgs; not part of the
+// reference's API, whose hash_to_curve sits inside every verify): item i = (sigs[i], msgs[msg_idx[i]], keys[i]). The members of a committee sign the same message:
+// every listed message is hashed to G2 once, whatever the number of items that name it. The same bools as one fast_aggregate_verify per item.
+inline std::vector<bool> fast_aggregate_verify_batch_shared_msgs(const std::vector<AggregateSignature>& sigs, const std::vector<Bytes>& msgs,
+                                                                 const std::vector<uint32_t>& msg_idx, const std::vector<std::vector<const PublicKey*>>& keys) {
+    const size_t n = sigs.size();
+    if (msg_idx.size() != n || keys.size() != n) throw std::invalid_argument("one message index and one key list per signature");
+    if (msgs.size() > 0xFFFFFFFFull) throw std::invalid_argument("fast_aggregate_verify_batch_shared_msgs: message indices are 32-bit");
+    for (uint32_t j : msg_idx) if (j >= msgs.size()) throw std::invalid_argument("fast_aggregate_verify_batch_shared_msgs: an index names no message of the list");
+    Bytes s, m, p; std::vector<uint64_t> moff{0}; std::vector<uint32_t> koff{0};
+    for (auto& x : msgs) { m.insert(m.end(), x.begin(), x.end()); moff.push_back(m.size()); }
+    for (size_t i = 0; i < n; i++) {
+        s.insert(s.end(), sigs[i].point.begin(), sigs[i].point.end());
+        for (auto* k : keys[i]) p.insert(p.end(), k->point.begin(), k->point.end());
+        if (p.size() / 96 > 0xFFFFFFFFull) throw std::invalid_argument("fast_aggregate_verify_batch_shared_msgs: key indices are 32-bit");
+        koff.push_back(uint32_t(p.size() / 96));
+    }
+    std::vector<uint8_t> res(n ? n : 1);
+    detail::check(mbls_fast_aggregate_verify_batch_shared_msgs(detail::ctx(), s.data(), m.data(), 0, moff.data(), msgs.size(), msg_idx.data(), p.data(), MBLS_PK_UNCOMPRESSED,
+                                                               koff.data(), n, 0, res.data(), nullptr));
+    std::vector<bool> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = res[i] == 1;
+    return out;
+}
+
 class MultiGpu {
     mbls_multi* h_ = nullptr;
 public:

@@ -74,6 +74,33 @@ def plan_workspace_items(n, k, split_layout=True, limits=None):
     return int(lib().mbls_plan_workspace_items(C.byref(L), n, k, 1 if split_layout else 0))
 
 
+class SharedMsgsPlan(C.Structure):
+    """include/mbls.h mbls_shared_msgs_plan"""
+    _fields_ = [("batch", BatchPlan), ("list_message", C.c_uint32), ("list_pieces", C.c_uint32), ("list_piece_items", C.c_uint64), ("list_workspace_items", C.c_uint64),
+                ("table_entries", C.c_uint64)]
+
+
+MESSAGE_GATHER = 5
+
+
+def plan_batch_shared_msgs(n, n_msgs, limits=None):
+    """what the *_shared_msgs entries would do with n items over a list of n_msgs messages under `limits` (pure: no GPU) -> (mode, [pass dicts], list dict)"""
+    L = limits if limits is not None else default_limits()
+    sp = SharedMsgsPlan()
+    rc = lib().mbls_plan_batch_shared_msgs(C.byref(L), n, n_msgs, C.byref(sp))
+    if rc != OK:
+        raise MblsError(rc, "mbls_plan_batch_shared_msgs")
+    b = sp.batch
+    return (b.mode, [{f: getattr(b.passes[i], f) for f, _ in PassPlan._fields_} for i in range(b.n_passes)],
+            {f: getattr(sp, f) for f in ("list_message", "list_pieces", "list_piece_items", "list_workspace_items", "table_entries")})
+
+
+def plan_shared_msgs_workspace_items(n, n_msgs, k, split_layout=True, limits=None):
+    """workspace items a *_shared_msgs call of n items of k keys over n_msgs messages reserves (pure: no GPU)"""
+    L = limits if limits is not None else default_limits()
+    return int(lib().mbls_plan_shared_msgs_workspace_items(C.byref(L), n, n_msgs, k, 1 if split_layout else 0))
+
+
 class StreamOpts(C.Structure):
     """include/mbls.h mbls_stream_opts (0 = default)"""
     _fields_ = [("round_items", C.c_uint64), ("round_keys", C.c_uint64), ("round_msg_bytes", C.c_uint64), ("depth", C.c_uint32), ("policy", C.c_uint32)]
@@ -156,6 +183,15 @@ SIGNATURES = {
     "mbls_keytable_get": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, vp]),
     "mbls_fast_aggregate_verify_batch_indexed_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp]),
     "mbls_fast_aggregate_verify_batch_indexed": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
+    "mbls_ctx_reserve_msgs": (C.c_int, [vp, C.c_uint64]),
+    "mbls_plan_batch_shared_msgs": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp]),
+    "mbls_plan_shared_msgs_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int]),
+    "mbls_fast_aggregate_verify_batch_shared_msgs_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_shared_msgs": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp, vp]),
+    "mbls_verify_batch_shared_msgs_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_int, C.c_uint64, vp, vp, vp, vp]),
+    "mbls_verify_batch_shared_msgs": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_int, C.c_uint64, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_indexed_shared_msgs_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_indexed_shared_msgs": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
     "mbls_aggregate_signatures_batch": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
     "mbls_aggregate_signatures_batch_device": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp, vp]),
     "mbls_pk_from_bytes": (C.c_int, [vp, vp, C.c_size_t, vp]),
@@ -297,6 +333,10 @@ class Context:
 
     def reserve(self, n):
         self.check(lib().mbls_ctx_reserve(self._h, n))
+
+    def reserve_msgs(self, n_msgs):
+        """the table of hashed points for message lists of up to n_msgs messages (the *_shared_msgs entries)"""
+        self.check(lib().mbls_ctx_reserve_msgs(self._h, n_msgs))
 
     def set_coop_max_items(self, n):
         """batches up to n items take the one-wave-per-item pairing check (0: never)"""

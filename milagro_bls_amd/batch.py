@@ -43,6 +43,53 @@ def fast_aggregate_verify_batch_indexed(table, sigs, msgs, key_idx, n, k=None, m
     return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
 
 
+def _midx(msg_idx, n):
+    if len(msg_idx) != n:
+        raise ValueError("msg_idx must have n = %d entries, got %d" % (n, len(msg_idx)))
+    return (C.c_uint32 * max(1, n))(*msg_idx)
+
+
+def fast_aggregate_verify_batch_shared_msgs(sigs, msgs, n_msgs, msg_idx, pks, n, k=None, pk_format=N.PK_COMPRESSED, msg_len=32, pk_offsets=None, ctx=None,
+                                            msg_offsets=None):
+    """fast_aggregate_verify_batch over a LIST of n_msgs messages (msg_len bytes each, or msg_offsets of n_msgs + 1 entries): item i's message is message
+    msg_idx[i]; every listed message is hashed once. Same (results, status) as fast_aggregate_verify_batch with the messages spelled out per item."""
+    ctx = ctx or _c()
+    res = N.outbuf(n)
+    st = (C.c_uint32 * max(1, n))()
+    off = None
+    if pk_offsets is not None:
+        off = (C.c_uint32 * len(pk_offsets))(*pk_offsets)
+        k = 0
+    ctx.check(N.lib().mbls_fast_aggregate_verify_batch_shared_msgs(ctx.handle, N.cbuf(sigs), N.cbuf(msgs), msg_len, _moff(msg_offsets), n_msgs, _midx(msg_idx, n),
+                                                                   N.cbuf(pks), pk_format, off, n, k, res, st))
+    return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
+
+
+def fast_aggregate_verify_batch_indexed_shared_msgs(table, sigs, msgs, n_msgs, msg_idx, key_idx, n, k=None, msg_len=32, offsets=None, ctx=None, msg_offsets=None):
+    """The same over a resident key table: keys by table index (as fast_aggregate_verify_batch_indexed), messages by list index."""
+    ctx = ctx or table.ctx
+    res = N.outbuf(n)
+    st = (C.c_uint32 * max(1, n))()
+    idx = (C.c_uint32 * max(1, len(key_idx)))(*key_idx)
+    off = None
+    if offsets is not None:
+        off = (C.c_uint32 * len(offsets))(*offsets)
+        k = 0
+    ctx.check(N.lib().mbls_fast_aggregate_verify_batch_indexed_shared_msgs(ctx.handle, table.handle, N.cbuf(sigs), N.cbuf(msgs), msg_len, _moff(msg_offsets), n_msgs,
+                                                                           _midx(msg_idx, n), idx, off, n, k, res, st))
+    return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
+
+
+def verify_batch_shared_msgs(sigs, msgs, n_msgs, msg_idx, pks, n, pk_format=N.PK_COMPRESSED, msg_len=32, ctx=None, msg_offsets=None):
+    """verify_batch (n x Signature::verify) over a list of n_msgs messages: item i's message is message msg_idx[i]."""
+    ctx = ctx or _c()
+    res = N.outbuf(n)
+    st = (C.c_uint32 * max(1, n))()
+    ctx.check(N.lib().mbls_verify_batch_shared_msgs(ctx.handle, N.cbuf(sigs), N.cbuf(msgs), msg_len, _moff(msg_offsets), n_msgs, _midx(msg_idx, n), N.cbuf(pks),
+                                                    pk_format, n, res, st))
+    return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
+
+
 def aggregate_signatures_batch(sigs96, n, k=None, offsets=None, ctx=None):
     """n x AggregateSignature::aggregate (reference src/aggregates.rs:100-106) -> (compressed sums, errs)"""
     ctx = ctx or _c()

@@ -195,6 +195,22 @@ __global__ void __launch_bounds__(WG) k_h_compact_b(mbls_ws ws, uint64_t n) {
     uint64_t i = gid(); if (i >= n) return;
     for (int w = 0; w < 72; w++) ws.w[((uint64_t)(MBLS_SLOT_H * 12 + w)) * ws.stride + i] = ws.w[((uint64_t)(19 * 12 + w)) * ws.stride + i];
 }
+// Shared message lists (mbls_*_shared_msgs): the points of the m messages a piece of the list hash left in slot H of workspace items [0, m) go to the context's
+// table (entries first_entry + i; lane_h_export), and every item of a pass copies the entry its index names into its own slot H (lane_h_gather). Copies and
+// nothing else: 72 dword loads and stores per lane, consecutive lanes = consecutive items / entries on the strided side, a few registers -- blocks of four waves,
+// eight waves per SIMD, no LDS. (The gather's reads follow the indices: with a few hundred messages the table is a few tens of KB and stays in cache.)
+// (k_h_export_tab: k_h_export is the hash probe's kernel further down, which writes compressed points)
+#define MBLS_HB 256
+__global__ void __launch_bounds__(MBLS_HB) k_h_export_tab(mbls_ws ws, uint32_t* tab, uint64_t tstride, uint32_t* flags, const uint32_t* st_list, uint64_t first_entry, uint64_t m) {
+    const uint64_t i = (uint64_t)blockIdx.x * MBLS_HB + threadIdx.x; if (i >= m) return;
+    lane_h_export(ws, i, tab, tstride, first_entry + i, flags, st_list);
+}
+__global__ void __launch_bounds__(MBLS_HB) k_h_gather(mbls_ws ws, const uint32_t* tab, uint64_t tstride, const uint32_t* flags, const uint32_t* msg_idx, uint64_t n_msgs,
+                                                      uint32_t* status, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * MBLS_HB + threadIdx.x; if (i >= n) return;
+    const uint32_t st = lane_h_gather(ws, i, tab, tstride, flags, msg_idx[i], n_msgs);
+    if (st) atomicOr(status + i, st);             // beside the key sum and the signature phase, like k_hash
+}
 // hash_to_field alone (SHA-256 / expand_message_xmd, one lane per item): u0, u1 into slots 31, 32 / 37, 38 -- the input of the cooperative
 // engine's hashg2 program (small batches: one WAVE per item walks the maps, the addition and the cofactor clearing)
 __global__ void MBLS_LB k_hash_fields(mbls_ws ws, const uint8_t* msgs, uint32_t mlen, const uint64_t* moff, uint32_t* status, uint64_t n) {
@@ -893,6 +909,9 @@ struct mbls_ctx {
     uint64_t key_cap = 0;              // decompressed-key staging (compressed wire format): capacity in keys
     uint32_t* d_keys_xy = nullptr;     // [key_cap][24] affine Montgomery coordinates
     uint8_t* d_key_flags = nullptr;
+    // shared message lists (mbls_*_shared_msgs): the hashed points of a call's list, [72][htab_cap] dwords (entry 0: H of the empty message, hashed on the first
+    // call after every (re)allocation; message j: entry j + 1), one bad-range word per entry, and the status words of the list's own hash
+    uint64_t htab_cap = 0; uint32_t* d_htab = nullptr; uint32_t* d_hflag = nullptr; uint32_t* d_hst = nullptr; bool h_empty_ready = false;
     struct { void* p; size_t cap; } stage[MBLS_N_STAGE] = {};
     hipStream_t hs_a = nullptr, hs_b = nullptr, hs_c = nullptr, hs_d = nullptr;      // streams of the host-buffer entry points (hs_d: the signature phase while hs_b uploads keys)
     hipEvent_t hs_ev = nullptr, hs_ev2 = nullptr, hs_ev3 = nullptr;
@@ -1002,6 +1021,9 @@ static void ctx_free(mbls_ctx* c) {
     if (c->d_sksel) (void)hipFree(c->d_sksel);
     if (c->d_keys_xy) (void)hipFree(c->d_keys_xy);
     if (c->d_key_flags) (void)hipFree(c->d_key_flags);
+    if (c->d_htab) (void)hipFree(c->d_htab);
+    if (c->d_hflag) (void)hipFree(c->d_hflag);
+    if (c->d_hst) (void)hipFree(c->d_hst);
     if (c->d_coop) (void)hipFree(c->d_coop);
     for (int i = 0; i < MBLS_N_STAGE; i++) if (c->stage[i].p) (void)hipFree(c->stage[i].p);
     for (int i = 0; i <= MBLS_N_PHASES; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1175,6 +1197,23 @@ extern "C" int mbls_ctx_reserve_keys(mbls_ctx* c, uint64_t max_keys) {
     HIPCHK(c, hipSetDevice(c->device));
     return reserve_keys(c, max_keys);
 }
+// the table of hashed points of a shared message list: max_msgs messages + the entry of the empty message (grow-only; growth drains the device like mbls_ctx_reserve)
+static int reserve_msgs(mbls_ctx* c, uint64_t max_msgs) {
+    const uint64_t want = ((max_msgs + 1 + WG - 1) / WG) * WG;
+    if (want <= c->htab_cap) return MBLS_OK;
+    if (c->d_htab) { (void)hipFree(c->d_htab); (void)hipFree(c->d_hflag); (void)hipFree(c->d_hst); c->d_htab = nullptr; c->d_hflag = nullptr; c->d_hst = nullptr; c->htab_cap = 0; }
+    c->h_empty_ready = false;
+    HIPCHK(c, hipMalloc(&c->d_htab, (size_t)MBLS_H_DWORDS * want * 4));
+    HIPCHK(c, hipMalloc(&c->d_hflag, want * 4));
+    HIPCHK(c, hipMalloc(&c->d_hst, want * 4));
+    c->htab_cap = want; return MBLS_OK;
+}
+extern "C" int mbls_ctx_reserve_msgs(mbls_ctx* c, uint64_t max_msgs) {
+    if (!c) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return reserve_msgs(c, max_msgs);
+}
 extern "C" int mbls_enable_phase_timing(mbls_ctx* c, int on) { if (!c) return MBLS_ERR_ARGUMENT; mbls_lock lk(c->mu); c->timing = on != 0; return MBLS_OK; }
 extern "C" int mbls_last_phase_ms(mbls_ctx* c, float ms[MBLS_N_PHASES]) {
     if (!c) return MBLS_ERR_ARGUMENT;
@@ -1323,6 +1362,37 @@ extern "C" uint64_t mbls_plan_workspace_items(const mbls_limits* limits, uint64_
     }
     return need;
 }
+// Shared message lists (mbls_*_shared_msgs): the plan of the n items is plan_batch's with every pass's message phase a gather from the context's table of hashed
+// points, and the list of n_msgs messages is hashed by launch_hash in the form ITS size asks for -- the forms and limits of plan_pass's message phase, applied to the
+// messages of one piece: the wave engine up to coop_hash_max_items (four per wave above the packing limit), lane pairs (2 workspace items per message) up to
+// hash2_max_items and half a round, one lane per message otherwise. A piece is at most one round of messages (more would cost a second round of k_hash anyway, and
+// the workspace a call reserves for its list stays at one round); message j of a piece works in workspace item j of the call's workspace.
+static void plan_shared(const mbls_limits& L, uint64_t n, uint64_t n_msgs, bool one_pass, bool timing, mbls_shared_msgs_plan* sp) {
+    memset(sp, 0, sizeof(*sp));
+    plan_batch(L, n, one_pass, timing, &sp->batch);
+    for (uint32_t i = 0; i < sp->batch.n_passes; i++) sp->batch.pass[i].message = MBLS_MESSAGE_GATHER;
+    sp->table_entries = n_msgs + 1;
+    if (!n_msgs) return;
+    const uint64_t R = L.round_items;
+    const uint64_t m = (R && n_msgs > R) ? R : n_msgs;               // messages of a (full) piece
+    const bool waves = m <= L.coop_hash_max_items && m <= L.coop_max_items;
+    const bool pairs = !waves && m <= L.split_max_items && m <= L.hash2_max_items && 2 * m <= R;
+    sp->list_message = waves ? (m > L.coop_hash_pack_min_items ? MBLS_MESSAGE_WAVE_X4 : MBLS_MESSAGE_WAVE) : pairs ? MBLS_MESSAGE_LANES2 : MBLS_MESSAGE_LANE;
+    sp->list_piece_items = m;
+    sp->list_pieces = (n_msgs + m - 1) / m;
+    sp->list_workspace_items = pairs ? 2 * m : m;
+}
+extern "C" int mbls_plan_batch_shared_msgs(const mbls_limits* limits, uint64_t n, uint64_t n_msgs, mbls_shared_msgs_plan* out) {
+    if (!limits || !out || !n) return MBLS_ERR_ARGUMENT;
+    plan_shared(*limits, n, n_msgs, false, false, out); return MBLS_OK;
+}
+// what a shared-message call reserves before it queues anything: the larger of the items' plan (mbls_plan_workspace_items) and the list hash's items
+extern "C" uint64_t mbls_plan_shared_msgs_workspace_items(const mbls_limits* limits, uint64_t n, uint64_t n_msgs, uint32_t k, int split_layout) {
+    if (!limits || !n) return 0;
+    mbls_shared_msgs_plan sp; plan_shared(*limits, n, n_msgs, false, false, &sp);
+    const uint64_t a = mbls_plan_workspace_items(limits, n, k, split_layout);
+    return a > sp.list_workspace_items ? a : sp.list_workspace_items;
+}
 #ifdef MBLS_COOP_PROFILE
 extern "C" int mbls_coop_profile_read(unsigned long long out[64], int reset) {     // dev builds only (not declared in mbls.h)
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mbls_coop_prof), 64 * 8) != hipSuccess) return MBLS_ERR_DEVICE;
@@ -1357,15 +1427,45 @@ static uint64_t pass_ws_items(const mbls_pass_plan& pp, const keysrc& ks, uint32
     const uint64_t split = pass_key_split(pp, ks, k) ? n + n * MBLS_KEY_SPLIT : 0;
     return split > pp.workspace_items ? split : pp.workspace_items;
 }
+// where an item's message comes from when the call carries a shared list: index i of d_idx names a message of the list, whose points are (or, `list` given, are
+// put by this pass's message phase) in the context's table
+struct msgsrc {
+    const uint32_t* d_idx = nullptr; uint64_t n_msgs = 0;
+    const mbls_shared_msgs_plan* list = nullptr;      // non-null: the pass hashes the list itself (a one-pass plan: on its message stream, beside the other front phases)
+};
+// the hash of the list on stream s: piece after piece through launch_hash in workspace items [0, piece), each followed by its export to the table; first of all,
+// once per allocation of the table, the entry of the empty message
+static int shared_hash_list(mbls_ctx* c, const mbls_shared_msgs_plan& sp, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, hipStream_t s) {
+    mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
+    if (!c->h_empty_ready) {
+        HIPCHK(c, hipMemsetAsync(c->d_hst, 0, 4, s));
+        launch_hash(c, ws, (const uint8_t*)c->d_htab, 0u, (const uint64_t*)nullptr, c->d_hst, (uint64_t)1, s);
+        hipLaunchKernelGGL(k_h_export_tab, dim3(1), dim3(MBLS_HB), 0, s, ws, c->d_htab, c->htab_cap, c->d_hflag, (const uint32_t*)c->d_hst, (uint64_t)0, (uint64_t)1);
+        c->h_empty_ready = true;
+    }
+    const int form = sp.list_message == MBLS_MESSAGE_LANE ? HASH_FORM_LANE : sp.list_message == MBLS_MESSAGE_LANES2 ? HASH_FORM_PAIR : HASH_FORM_WAVE;
+    for (uint64_t first = 0; first < n_msgs; first += sp.list_piece_items) {
+        const uint64_t m = n_msgs - first < sp.list_piece_items ? n_msgs - first : sp.list_piece_items;
+        uint32_t* st_list = c->d_hst + 1 + first;
+        HIPCHK(c, hipMemsetAsync(st_list, 0, 4 * m, s));
+        // uniform messages advance the base pointer, an offset table is absolute (its slice goes with the unmoved base)
+        launch_hash(c, ws, (d_moff || !d_msgs) ? d_msgs : d_msgs + (uint64_t)msg_len * first, msg_len, d_moff ? d_moff + first : nullptr, st_list, m, s,
+                    form == HASH_FORM_PAIR, form);
+        hipLaunchKernelGGL(k_h_export_tab, dim3((unsigned)((m + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s, ws, c->d_htab, c->htab_cap, c->d_hflag, (const uint32_t*)st_list,
+                           1 + first, m);
+    }
+    HIPCHK(c, hipGetLastError());
+    return MBLS_OK;
+}
 static track track0(mbls_ctx* c) { track t; t.sb = c->hs_b; t.sc = c->hs_c; t.sd = c->hs_d; t.ev2 = c->hs_ev2; t.ev3 = c->hs_ev3; return t; }
 static int verify_pipeline_one(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const keysrc& ks,
                                uint64_t n, uint32_t k, int mode, uint8_t* d_results, uint64_t* d_bitmap,
-                               uint32_t* d_status, hipStream_t s, int part = 0, const track* tkp = nullptr, bool no_growth = false) {
+                               uint32_t* d_status, hipStream_t s, int part = 0, const track* tkp = nullptr, bool no_growth = false, const msgsrc* ms = nullptr) {
     const int fmt = ks.fmt; const uint32_t* d_off = ks.d_off;
     if (!c || (fmt != MBLS_PK_COMPRESSED && fmt != MBLS_PK_UNCOMPRESSED)) return MBLS_ERR_ARGUMENT;
     if (n == 0) return MBLS_OK;
     const bool have_keys = ks.indexed ? (ks.d_idx != nullptr) : (ks.d_pks != nullptr);
-    if (!d_sigs || (!d_msgs && msg_len && !d_moff) || !d_results || (!have_keys && (k || d_off) && part != 1)) ARGFAIL(c, "null buffer");
+    if (!d_sigs || (!ms && !d_msgs && msg_len && !d_moff) || (ms && !ms->d_idx) || !d_results || (!have_keys && (k || d_off) && part != 1)) ARGFAIL(c, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
     const track tk = tkp ? *tkp : track0(c);
     bool tm = c->timing;
@@ -1418,9 +1518,17 @@ static int verify_pipeline_one(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t
         if (on_waves && !fused_sig) hipLaunchKernelGGL(k_sig2, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, d_sigs, st, n);
         else hipLaunchKernelGGL(k_sig, dim3(g), dim3(WG), 0, s_sig, ws, d_sigs, st, n, fused_sig ? 0 : 1);
     };
+    // the message phase: the items' own messages through launch_hash, or -- a shared list -- [the hash of the list and its export, then] the gather from the table
+    auto launch_msg = [&]() -> int {
+        if (!ms) { launch_hash(c, ws, d_msgs, msg_len, d_moff, st, n, s_msg, hash_pairs, hform); return MBLS_OK; }
+        if (ms->list) { const int rl = shared_hash_list(c, *ms->list, d_msgs, msg_len, d_moff, ms->n_msgs, s_msg); if (rl) return rl; }
+        hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, (const uint32_t*)c->d_htab, c->htab_cap,
+                           (const uint32_t*)c->d_hflag, ms->d_idx, ms->n_msgs, st, n);
+        return MBLS_OK;
+    };
     if (part == 1) {
         launch_sig();
-        launch_hash(c, ws, d_msgs, msg_len, d_moff, st, n, s_msg, hash_pairs, hform);
+        rc = launch_msg(); if (rc) return rc;
         HIPCHK(c, hipGetLastError());
         return MBLS_OK;
     }
@@ -1446,7 +1554,7 @@ static int verify_pipeline_one(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t
     if (tm) HIPCHK(c, hipEventRecord(c->ev[1], s));
     if (!keys_later) launch_sig();
     if (tm) HIPCHK(c, hipEventRecord(c->ev[2], s));
-    if (!keys_later) launch_hash(c, ws, d_msgs, msg_len, d_moff, st, n, s_msg, hash_pairs, hform);
+    if (!keys_later) { rc = launch_msg(); if (rc) return rc; }
     if (tm) HIPCHK(c, hipEventRecord(c->ev[3], s));
     if (fork) {      // join
         if (s_sig != s) { HIPCHK(c, hipEventRecord(tk.ev2, s_sig)); HIPCHK(c, hipStreamWaitEvent(s, tk.ev2, 0)); }
@@ -1485,8 +1593,15 @@ static int verify_pipeline_one(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t
 // with the unmoved base); lo is a multiple of 64, so the bitmap advances by whole words.
 static int verify_pipeline_from(mbls_ctx* c, uint64_t lo, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const keysrc& ks,
                                 uint64_t n, uint32_t k, int mode, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, hipStream_t s, const track* tk = nullptr,
-                                bool no_growth = false) {
+                                bool no_growth = false, const msgsrc* ms = nullptr) {
     keysrc t = ks;
+    if (ms) {            // a shared list: the indices advance with the items, the list (hashed before the first pass) does not
+        msgsrc m2 = *ms; m2.d_idx = ms->d_idx + lo; m2.list = nullptr;
+        if (ks.d_off) t.d_off = ks.d_off + lo;
+        else { const size_t u = ks.fmt == MBLS_PK_COMPRESSED ? 48 : 96; if (ks.d_pks) t.d_pks = ks.d_pks + u * (uint64_t)k * lo; if (ks.d_idx) t.d_idx = ks.d_idx + (uint64_t)k * lo; }
+        return verify_pipeline_one(c, d_sigs + 96 * lo, d_msgs, msg_len, d_moff, t, n - lo, k, mode, d_results + lo, d_bitmap ? d_bitmap + lo / 64 : nullptr,
+                                   d_status ? d_status + lo : nullptr, s, 0, tk, no_growth, &m2);
+    }
     const size_t unit = ks.fmt == MBLS_PK_COMPRESSED ? 48 : 96;
     if (ks.d_off) t.d_off = ks.d_off + lo;
     else { if (ks.d_pks) t.d_pks = ks.d_pks + unit * (uint64_t)k * lo; if (ks.d_idx) t.d_idx = ks.d_idx + (uint64_t)k * lo; }
@@ -1497,12 +1612,12 @@ static int verify_pipeline_from(mbls_ctx* c, uint64_t lo, const uint8_t* d_sigs,
 // caller's stream, track 1 on the context's second set of streams, forked from and joined to the caller's stream --, stages one after the other.
 static int verify_pipeline(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const keysrc& ks,
                            uint64_t n, uint32_t k, int mode, uint8_t* d_results, uint64_t* d_bitmap,
-                           uint32_t* d_status, hipStream_t s, int part = 0) {
+                           uint32_t* d_status, hipStream_t s, int part = 0, const msgsrc* ms = nullptr) {
     if (!c || part != 0 || n == 0)
-        return verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, part);
+        return verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, part, nullptr, false, ms);
     mbls_batch_plan bp; plan_batch(ctx_limits(c), n, c->timing, c->timing, &bp);
     if (bp.mode == MBLS_BATCH_ONE_PASS)
-        return verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, 0);
+        return verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, 0, nullptr, false, ms);
     // one growth of the workspace (and of the staging of decompressed keys) for the whole plan: nothing may be reallocated under a pass in flight
     // (a pass on the wave engine may take the eight-lane key sum: n + 8 n items -- pass_ws_items, the figure the pass itself acts on; the staging of decompressed keys
     // is indexed by ITEM, so it follows the items' extent, not the partial sums')
@@ -1514,12 +1629,12 @@ static int verify_pipeline(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_
     int rc = mbls_ctx_reserve(c, need); if (rc) return rc;
     if (!ks.indexed && ks.fmt == MBLS_PK_COMPRESSED && !ks.d_off && k > 1) { rc = reserve_keys(c, need_items * (uint64_t)k); if (rc) return rc; }
     if (bp.mode == MBLS_BATCH_ROUNDS_THEN_REST) {
-        rc = verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, bp.pass[0].items, k, mode, d_results, d_bitmap, d_status, s, 0, nullptr, true); if (rc) return rc;
-        return verify_pipeline_from(c, bp.pass[1].first_item, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, nullptr, true);
+        rc = verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, bp.pass[0].items, k, mode, d_results, d_bitmap, d_status, s, 0, nullptr, true, ms); if (rc) return rc;
+        return verify_pipeline_from(c, bp.pass[1].first_item, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, nullptr, true, ms);
     }
     // two tracks: [rounds in front,] then two passes side by side
     uint32_t i = 0;
-    if (bp.n_passes == 3) { rc = verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, bp.pass[0].items, k, mode, d_results, d_bitmap, d_status, s, 0, nullptr, true); if (rc) return rc; i = 1; }
+    if (bp.n_passes == 3) { rc = verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, bp.pass[0].items, k, mode, d_results, d_bitmap, d_status, s, 0, nullptr, true, ms); if (rc) return rc; i = 1; }
     const mbls_pass_plan& pa = bp.pass[i]; const mbls_pass_plan& pb = bp.pass[i + 1];
     const bool side = bp.mode == MBLS_BATCH_ROUND_BESIDE_REST;
     const uint64_t fm = side ? ~0ull : (pa.front == MBLS_FRONT_IN_A_ROW ? 0 : c->fork_max_items);
@@ -1529,11 +1644,11 @@ static int verify_pipeline(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_
     track tb; tb.no_waves = side; tb.fork_max = fm; tb.ws_off = pb.workspace_first; tb.sb = c->t1_b; tb.sc = c->t1_c; tb.sd = c->t1_b; tb.ev2 = c->t1_ev2; tb.ev3 = c->t1_ev3; tb.ws_sync = false;
     const uint64_t lo = pa.first_item, mid = pb.first_item;
     if (side) {          // the round first: its kernels fill the chip, the remainder's waves take what they leave between them
-        rc = verify_pipeline_from(c, lo, d_sigs, d_msgs, msg_len, d_moff, ks, mid, k, mode, d_results, d_bitmap, d_status, s, &ta, true);
-        if (!rc) rc = verify_pipeline_from(c, mid, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, c->t1_s, &tb, true);
+        rc = verify_pipeline_from(c, lo, d_sigs, d_msgs, msg_len, d_moff, ks, mid, k, mode, d_results, d_bitmap, d_status, s, &ta, true, ms);
+        if (!rc) rc = verify_pipeline_from(c, mid, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, c->t1_s, &tb, true, ms);
     } else {
-        rc = verify_pipeline_from(c, mid, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, c->t1_s, &tb, true);
-        if (!rc) rc = verify_pipeline_from(c, lo, d_sigs, d_msgs, msg_len, d_moff, ks, mid, k, mode, d_results, d_bitmap, d_status, s, &ta, true);
+        rc = verify_pipeline_from(c, mid, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, c->t1_s, &tb, true, ms);
+        if (!rc) rc = verify_pipeline_from(c, lo, d_sigs, d_msgs, msg_len, d_moff, ks, mid, k, mode, d_results, d_bitmap, d_status, s, &ta, true, ms);
     }
     // join: the caller's stream ends when both tracks have (also on an error path: nothing of the call stays in flight unordered)
     hipError_t e1 = hipEventRecord(c->t1_ev, c->t1_s), e2 = hipStreamWaitEvent(s, c->t1_ev, 0);
@@ -1757,6 +1872,121 @@ extern "C" int mbls_fast_aggregate_verify_batch_indexed(mbls_ctx* c, const mbls_
         const uint64_t* moff, const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
     if (!c || !t) return MBLS_ERR_ARGUMENT;
     return verify_host(c, sigs, msgs, msg_len, moff, nullptr, MBLS_PK_UNCOMPRESSED, t, idx, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
+}
+
+// ---- shared message lists: the call carries n_msgs messages and one index per item (include/mbls.h). The list is hashed once -- by the same launch_hash, in the
+// form its size asks for (plan_shared) --, its points go to the context's table (k_h_export_tab), and the message phase of every pass is the gather (k_h_gather).
+// One-pass plans hash the list inside the pass, on its message stream beside the key sum and the signatures; plans of several passes hash it on the caller's stream
+// before the first pass. Everything is reserved before anything is queued: the workspace for the larger of the items' plan and the list, the table, the key staging.
+static int verify_shared_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_midx,
+                                const keysrc& ks, uint64_t n, uint32_t k, int mode, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, hipStream_t s) {
+    if (ks.fmt != MBLS_PK_COMPRESSED && ks.fmt != MBLS_PK_UNCOMPRESSED) return MBLS_ERR_ARGUMENT;
+    if (n == 0) return MBLS_OK;
+    if (n_msgs > 0xFFFFFFFFull) ARGFAIL(c, "message indices are 32-bit");
+    if (!d_sigs || !d_midx || !d_results || (n_msgs && !d_msgs && msg_len && !d_moff)) ARGFAIL(c, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    mbls_shared_msgs_plan sp; plan_shared(ctx_limits(c), n, n_msgs, c->timing, c->timing, &sp);
+    uint64_t need = sp.list_workspace_items, need_items = 0;
+    for (uint32_t i = 0; i < sp.batch.n_passes; i++) {
+        const uint64_t e = sp.batch.pass[i].workspace_first + pass_ws_items(sp.batch.pass[i], ks, k, sp.batch.pass[i].items); if (e > need) need = e;
+        const uint64_t ei = sp.batch.pass[i].workspace_first + sp.batch.pass[i].items; if (ei > need_items) need_items = ei;
+    }
+    int rc = mbls_ctx_reserve(c, need); if (rc) return rc;
+    rc = reserve_msgs(c, n_msgs); if (rc) return rc;
+    if (!ks.indexed && ks.fmt == MBLS_PK_COMPRESSED && !ks.d_off && k > 1) { rc = reserve_keys(c, need_items * (uint64_t)k); if (rc) return rc; }
+    msgsrc ms; ms.d_idx = d_midx; ms.n_msgs = n_msgs;
+    if (sp.batch.mode == MBLS_BATCH_ONE_PASS) {
+        ms.list = &sp;
+        return verify_pipeline(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, 0, &ms);
+    }
+    rc = ws_acquire(c, s); if (rc) return rc;
+    rc = shared_hash_list(c, sp, d_msgs, msg_len, d_moff, n_msgs, s); if (rc) return rc;
+    return verify_pipeline(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, 0, &ms);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_shared_msgs_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff,
+        uint64_t n_msgs, const uint32_t* d_msg_idx, const uint8_t* d_pks, int fmt, const uint32_t* d_off, uint64_t n, uint32_t k, uint8_t* d_results, uint64_t* d_bitmap,
+        uint32_t* d_status, void* stream) {
+    if (!c) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    keysrc ks; ks.d_pks = d_pks; ks.fmt = fmt; ks.d_off = d_off;
+    return verify_shared_device(c, d_sigs, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status, (hipStream_t)stream);
+}
+extern "C" int mbls_verify_batch_shared_msgs_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs,
+        const uint32_t* d_msg_idx, const uint8_t* d_pks, int fmt, uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
+    if (!c) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    keysrc ks; ks.d_pks = d_pks; ks.fmt = fmt;
+    return verify_shared_device(c, d_sigs, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, ks, n, 1, MBLS_MODE_VERIFY, d_results, d_bitmap, d_status, (hipStream_t)stream);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_indexed_shared_msgs_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len,
+        const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_msg_idx, const uint32_t* d_idx, const uint32_t* d_off, uint64_t n, uint32_t k, uint8_t* d_results,
+        uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
+    if (!c || !t) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (t->c != c) ARGFAIL(c, "key table belongs to another context");
+    keysrc ks; ks.indexed = true; ks.d_recs = t->d_recs; ks.tsize = t->size; ks.d_idx = d_idx; ks.d_off = d_off; ks.tab = t;
+    return verify_shared_device(c, d_sigs, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status, (hipStream_t)stream);
+}
+// Host buffers in, results out: the tables are checked here (a bad offset table or an index that names no message refuses the call, nothing enqueued), everything is
+// staged through the context's buffers, and the device pipeline above runs on the context's stream.
+static int verify_host_shared(mbls_ctx* c, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n_msgs, const uint32_t* msg_idx,
+                              const uint8_t* pks, int fmt, const mbls_keytable* tab, const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, int mode,
+                              uint8_t* results, uint32_t* status) {
+    if (!c) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (n == 0) return MBLS_OK;
+    if (n_msgs > 0xFFFFFFFFull) ARGFAIL(c, "message indices are 32-bit");
+    if (!sigs || !msg_idx || !results) ARGFAIL(c, "null buffer");
+    if (moff && !msg_offsets_ok(moff, n_msgs)) ARGFAIL(c, "msg_offsets must be non-decreasing, messages below 2^32 bytes");
+    for (uint64_t i = 0; i < n; i++) if (msg_idx[i] >= n_msgs) ARGFAIL(c, "msg_idx names no message of the list");
+    const uint64_t msg_first = moff ? moff[0] : 0;
+    const size_t msg_total = moff ? (size_t)(moff[n_msgs] - moff[0]) : (size_t)msg_len * n_msgs;
+    if (!msgs && msg_total) ARGFAIL(c, "null buffer");
+    if (fmt != MBLS_PK_COMPRESSED && fmt != MBLS_PK_UNCOMPRESSED) ARGFAIL(c, "pk_format");
+    if (tab && tab->c != c) ARGFAIL(c, "key table belongs to another context");
+    if (off && !offsets_ok(off, n)) ARGFAIL(c, "offsets must be non-decreasing");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t key_first = off ? off[0] : 0;
+    const uint64_t total_keys = off ? (uint64_t)(off[n] - off[0]) : (uint64_t)k * n;
+    const bool indexed = tab != nullptr;
+    if (total_keys && !(indexed ? (const void*)idx : (const void*)pks)) ARGFAIL(c, "null key buffer");
+    const size_t unit = indexed ? 4 : (fmt == MBLS_PK_COMPRESSED ? 48 : 96);
+    sbuf ds(c, 0), dm(c, 1), dp(c, 2), doff(c, 3), dr(c, 4), dst(c, 5), dmo(c, 6), dmi(c, 7);
+    HIPCHK(c, ds.up(sigs, 96 * n)); HIPCHK(c, dm.up(msgs ? msgs + msg_first : nullptr, msg_total)); HIPCHK(c, dmi.up(msg_idx, 4 * n));
+    if (off) HIPCHK(c, doff.up(off, 4 * (n + 1)));
+    const uint64_t* d_moff = nullptr; const uint8_t* d_msgs = dm.as<uint8_t>();
+    if (moff) { HIPCHK(c, dmo.up(moff, 8 * (n_msgs + 1))); d_moff = dmo.as<uint64_t>(); d_msgs -= msg_first; }     // the table as given; the uploaded bytes start at msgs[moff[0]]
+    HIPCHK(c, dr.alloc(n)); HIPCHK(c, dst.alloc(4 * n));
+    HIPCHK(c, dp.up(total_keys ? (indexed ? (const void*)(idx + key_first) : (const void*)(pks + unit * key_first)) : nullptr, unit * total_keys));
+    keysrc ks; ks.fmt = fmt; ks.d_off = off ? doff.as<uint32_t>() : nullptr; ks.indexed = indexed;
+    if (indexed) { ks.d_recs = tab->d_recs; ks.tsize = tab->size; ks.tab = tab; ks.d_idx = dp.as<uint32_t>() - key_first; } else ks.d_pks = dp.as<uint8_t>() - unit * key_first;
+    const bool tm = c->timing; c->timing = false;        // the phase timers describe the device entries
+    const int rc = verify_shared_device(c, ds.as<uint8_t>(), d_msgs, msg_len, d_moff, n_msgs, dmi.as<uint32_t>(), ks, n, k, mode, dr.as<uint8_t>(), nullptr, dst.as<uint32_t>(), c->hs_a);
+    c->timing = tm;
+    if (rc) {         // nothing of this call is left in flight when it returns an error
+        (void)hipStreamSynchronize(c->hs_a); (void)hipStreamSynchronize(c->hs_b); (void)hipStreamSynchronize(c->hs_c); (void)hipStreamSynchronize(c->hs_d);
+        (void)hipStreamSynchronize(c->t1_s);
+        c->ws_pending = false;
+        return rc;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->hs_a));
+    c->ws_pending = false;
+    HIPCHK(c, dr.down(results, n));
+    if (status) HIPCHK(c, dst.down(status, 4 * n));
+    return MBLS_OK;
+}
+extern "C" int mbls_fast_aggregate_verify_batch_shared_msgs(mbls_ctx* c, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n_msgs,
+        const uint32_t* msg_idx, const uint8_t* pks, int fmt, const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
+    return verify_host_shared(c, sigs, msgs, msg_len, moff, n_msgs, msg_idx, pks, fmt, nullptr, nullptr, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
+}
+extern "C" int mbls_verify_batch_shared_msgs(mbls_ctx* c, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n_msgs,
+        const uint32_t* msg_idx, const uint8_t* pks, int fmt, uint64_t n, uint8_t* results, uint32_t* status) {
+    return verify_host_shared(c, sigs, msgs, msg_len, moff, n_msgs, msg_idx, pks, fmt, nullptr, nullptr, nullptr, n, 1, MBLS_MODE_VERIFY, results, status);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_indexed_shared_msgs(mbls_ctx* c, const mbls_keytable* t, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
+        const uint64_t* moff, uint64_t n_msgs, const uint32_t* msg_idx, const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
+    if (!c || !t) return MBLS_ERR_ARGUMENT;
+    return verify_host_shared(c, sigs, msgs, msg_len, moff, n_msgs, msg_idx, nullptr, MBLS_PK_UNCOMPRESSED, t, idx, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
 }
 
 // ---- batch helpers

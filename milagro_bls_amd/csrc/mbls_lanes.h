@@ -361,6 +361,29 @@ MBLS_FN void lane_hash(const mbls_ws& ws, uint64_t i, const uint8_t* msg, uint32
     g2j h; hash_to_g2(&h, msg, mlen, MBLS_DST_POP, MBLS_DST_POP_LEN);
     ws_st2(ws, MBLS_SLOT_H, i, h.x); ws_st2(ws, MBLS_SLOT_H + 2, i, h.y); ws_st2(ws, MBLS_SLOT_H + 4, i, h.z);
 }
+// SHARED MESSAGE LISTS (mbls_*_shared_msgs, include/mbls.h): the distinct messages of a call are hashed ONCE, their points H (slots 7..12: 72 dwords) are copied
+// out of the workspace into a table of the context -- entry-major like the workspace: dword w of entry e at tab[w * tstride + e], so that a wave that exports 64
+// consecutive messages stores 64 consecutive dwords per instruction -- and every item copies the entry its index names into its own slot H. Entry 0 is H of the
+// empty message: what an item gets whose index names no message of the list (today's bad-range items hash the empty message too); message j is entry j + 1.
+#define MBLS_H_DWORDS 72
+// message `i` of a piece of the list (workspace item i, status word st_list[i] of the piece's hash) -> table entry e; its bad-range bit -> flags[e]
+MBLS_FN void lane_h_export(const mbls_ws& ws, uint64_t i, uint32_t* tab, uint64_t tstride, uint64_t e, uint32_t* flags, const uint32_t* st_list) {
+    const uint32_t* src = ws.w + (uint64_t)MBLS_SLOT_H * 12 * ws.stride + i;
+    uint32_t* dst = tab + e;
+#pragma unroll 8
+    for (int w = 0; w < MBLS_H_DWORDS; w++) dst[(uint64_t)w * tstride] = src[(uint64_t)w * ws.stride];
+    flags[e] = st_list[i] & MBLS_ST_BAD_MSG_RANGE;
+}
+// item i takes the point of message j (j >= n_msgs: no such message -- entry 0 and the bad-range bit); returns the status bits the message brings
+MBLS_FN uint32_t lane_h_gather(const mbls_ws& ws, uint64_t i, const uint32_t* tab, uint64_t tstride, const uint32_t* flags, uint32_t j, uint64_t n_msgs) {
+    const bool none = (uint64_t)j >= n_msgs;
+    const uint64_t e = none ? 0 : (uint64_t)j + 1;
+    const uint32_t* src = tab + e;
+    uint32_t* dst = ws.w + (uint64_t)MBLS_SLOT_H * 12 * ws.stride + i;
+#pragma unroll 8
+    for (int w = 0; w < MBLS_H_DWORDS; w++) dst[(uint64_t)w * ws.stride] = src[(uint64_t)w * tstride];
+    return none ? MBLS_ST_BAD_MSG_RANGE : flags[e];
+}
 // use_lds: the kernel provides an LDS home for the running points (an explicit flag: a __shared__ array may sit at LDS
 // address 0, so the pointer itself cannot say whether it is there)
 MBLS_FN void lane_miller(const mbls_ws& ws, uint64_t i, MBLS_LDS uint32_t* tstore = nullptr, uint32_t lane = 0, bool use_lds = false) {

@@ -101,6 +101,16 @@ extern "C" {
     fn mbls_keytable_get(t: *mut MblsKeyTable, first_index: u64, n: u64, pks96: *mut u8, errs: *mut u8) -> c_int;
     fn mbls_fast_aggregate_verify_batch_indexed(ctx: *mut MblsCtx, t: *const MblsKeyTable, sigs: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
                                                 key_idx: *const u32, offsets: *const u32, n: u64, k: u32, results: *mut u8, status: *mut u32) -> c_int;
+    // shared message lists (include/mbls.h): n_msgs messages, one index per item; every listed message is hashed once
+    fn mbls_ctx_reserve_msgs(ctx: *mut MblsCtx, max_msgs: u64) -> c_int;
+    fn mbls_fast_aggregate_verify_batch_shared_msgs(ctx: *mut MblsCtx, sigs: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64, n_msgs: u64,
+                                                    msg_idx: *const u32, pks: *const u8, pk_format: c_int, pk_offsets: *const u32, n: u64, k: u32,
+                                                    results: *mut u8, status: *mut u32) -> c_int;
+    fn mbls_verify_batch_shared_msgs(ctx: *mut MblsCtx, sigs: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64, n_msgs: u64, msg_idx: *const u32,
+                                     pks: *const u8, pk_format: c_int, n: u64, results: *mut u8, status: *mut u32) -> c_int;
+    fn mbls_fast_aggregate_verify_batch_indexed_shared_msgs(ctx: *mut MblsCtx, t: *const MblsKeyTable, sigs: *const u8, msgs: *const u8, msg_len: u32,
+                                                            msg_offsets: *const u64, n_msgs: u64, msg_idx: *const u32, key_idx: *const u32, offsets: *const u32,
+                                                            n: u64, k: u32, results: *mut u8, status: *mut u32) -> c_int;
 }
 #[repr(C)]
 pub struct MblsMulti {
@@ -909,6 +919,62 @@ impl KeyTable {
         }
         res.into_iter().map(|b| b == 1).collect()
     }
+    /// The same over a LIST of messages: item i's message is `messages[message_indices[i]]` (the members of a committee sign the same root: every listed
+    /// message is hashed to G2 once). An index that names no message of the list is a caller error (the library refuses the call).
+    pub fn fast_aggregate_verify_shared_msgs(&self, signatures: &[AggregateSignature], messages: &[[u8; 32]], message_indices: &[u32], key_indices: &[u32], k: u32) -> Vec<bool> {
+        let n = signatures.len();
+        assert!(message_indices.len() == n && key_indices.len() == n * k as usize);
+        assert!(message_indices.iter().all(|&j| (j as usize) < messages.len()));
+        let sigs: Vec<u8> = signatures.iter().flat_map(|s| s.point.iter().copied()).collect();
+        let msgs: Vec<u8> = messages.iter().flat_map(|m| m.iter().copied()).collect();
+        let mut res = vec![0u8; n];
+        let rc = unsafe {
+            mbls_fast_aggregate_verify_batch_indexed_shared_msgs(ctx(), self.h, sigs.as_ptr(), msgs.as_ptr(), 32, std::ptr::null(), messages.len() as u64, message_indices.as_ptr(),
+                                                                 key_indices.as_ptr(), std::ptr::null(), n as u64, k, res.as_mut_ptr(), std::ptr::null_mut())
+        };
+        if rc != 0 {
+            err(rc);
+        }
+        res.into_iter().map(|b| b == 1).collect()
+    }
+}
+/// Pre-allocates the context's table of hashed points for message lists of up to `max_msgs` messages (keeps allocation out of the first call).
+pub fn reserve_message_list(max_msgs: u64) {
+    let rc = unsafe { mbls_ctx_reserve_msgs(ctx(), max_msgs) };
+    if rc != 0 {
+        err(rc);
+    }
+}
+/// n x `AggregateSignature::fast_aggregate_verify` over a list of messages, keys as decoded `PublicKey`s: item i = (signatures[i], messages[message_indices[i]], keys[i]).
+pub fn fast_aggregate_verify_batch_shared_msgs(signatures: &[AggregateSignature], messages: &[&[u8]], message_indices: &[u32], keys: &[&[&PublicKey]]) -> Vec<bool> {
+    let n = signatures.len();
+    assert!(message_indices.len() == n && keys.len() == n);
+    assert!(message_indices.iter().all(|&j| (j as usize) < messages.len()));
+    let sigs: Vec<u8> = signatures.iter().flat_map(|s| s.point.iter().copied()).collect();
+    let mut msgs: Vec<u8> = Vec::new();
+    let mut moff: Vec<u64> = vec![0];
+    for m in messages {
+        msgs.extend_from_slice(m);
+        moff.push(msgs.len() as u64);
+    }
+    let mut pks: Vec<u8> = Vec::new();
+    let mut koff: Vec<u32> = vec![0];
+    for ks in keys {
+        for k in ks.iter() {
+            pks.extend_from_slice(&k.point);
+        }
+        koff.push((pks.len() / 96) as u32);
+    }
+    let mut res = vec![0u8; n.max(1)];
+    let rc = unsafe {
+        mbls_fast_aggregate_verify_batch_shared_msgs(ctx(), sigs.as_ptr(), msgs.as_ptr(), 0, moff.as_ptr(), messages.len() as u64, message_indices.as_ptr(), pks.as_ptr(),
+                                                     PK_UNCOMPRESSED, koff.as_ptr(), n as u64, 0, res.as_mut_ptr(), std::ptr::null_mut())
+    };
+    if rc != 0 {
+        err(rc);
+    }
+    res.truncate(n);
+    res.into_iter().map(|b| b == 1).collect()
 }
 impl Drop for KeyTable {
     fn drop(&mut self) {
