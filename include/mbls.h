@@ -562,6 +562,10 @@ int mbls_hash_to_g2_batch(mbls_ctx* ctx, const uint8_t* msgs, uint32_t msg_len, 
  * 1 = the generated one-lane-per-item routine of the batch path, 2 = the one-wave-per-item program of small batches, 3 = two lanes per
  * message (the form batches between the wave engine's limit and half a round take) */
 int mbls_hash_to_g2_batch_mode(mbls_ctx* ctx, const uint8_t* msgs, uint32_t msg_len, uint64_t n, uint8_t* out96, int mode);
+/* test probe: everything of hash_to_curve_g2 AFTER hash_to_field. u192: n x (u0.c0, u0.c1, u1.c0, u1.c1), canonical
+ * 48-byte big-endian values below p (MBLS_ERR_ARGUMENT otherwise). mode: 0 the compiled lane body, 1/2/3 as
+ * mbls_hash_to_g2_batch_mode (generated lane routine / wave program / lane pair). out96: compressed H, infinity as 0xC0||0.. */
+int mbls_map_to_g2_probe(mbls_ctx* ctx, const uint8_t* u192, uint64_t n, uint8_t* out96, int mode);
 /* n x AggregateSignature::aggregate (src/aggregates.rs:100-106): set i sums its k signatures (or the signatures
  * [offsets[i], offsets[i+1]) of sigs96), starting from infinity (an empty set gives 0xC0 || 0..). errs[i] = MBLS_OK or the
  * Signature::from_bytes error of the first member that does not decode. No subgroup check, like the reference. */

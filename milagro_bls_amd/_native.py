@@ -233,6 +233,7 @@ SIGNATURES = {
     "mbls_hash_to_g2_batch_mode": (C.c_int, [vp, vp, C.c_uint32, C.c_uint64, vp, C.c_int]),
     "mbls_aggregate_public_keys_batch": (C.c_int, [vp, vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp, vp]),
     "mbls_fp_mul_batch": (C.c_int, [vp, vp, vp, C.c_uint64, vp, C.c_int]),
+    "mbls_map_to_g2_probe": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int]),
     "mbls_dform_probe_shape": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mbls_dform_probe": (C.c_int, [vp, C.c_int, vp, C.c_uint64, vp]),
     "mbls_fp_mul_bench": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),

@@ -178,6 +178,20 @@ def hash_to_g2_batch(msgs, n, msg_len=32, ctx=None, mode=0):
     return bytes(out)[:96 * n]
 
 
+def map_to_g2_batch(u, n, mode=1, ctx=None):
+    """test probe (include/mbls.h, mbls_map_to_g2_probe): hash_to_curve_g2 after hash_to_field on n pairs of field elements; u = a list of
+    ((c0, c1), (c0, c1)) integer pairs (u0, u1) or 192 n packed bytes (u0.c0, u0.c1, u1.c0, u1.c1, 48 bytes big-endian each). mode 0: the
+    compiled lane body, 1 / 2 / 3 as hash_to_g2_batch. n compressed points"""
+    ctx = ctx or _c()
+    if not isinstance(u, (bytes, bytearray)):
+        u = b"".join(int(c).to_bytes(48, "big") for u0, u1 in u for c in (u0[0], u0[1], u1[0], u1[1]))
+    if len(u) != 192 * n:
+        raise ValueError("map_to_g2_batch takes 192 bytes per item")
+    out = N.outbuf(96 * n)
+    ctx.check(N.lib().mbls_map_to_g2_probe(ctx.handle, N.cbuf(u), n, out, mode))
+    return bytes(out)[:96 * n]
+
+
 def aggregate_public_keys_batch(pks, n, k=None, pk_format=N.PK_COMPRESSED, pk_offsets=None, ctx=None):
     ctx = ctx or _c()
     out = N.outbuf(96 * n)

@@ -226,6 +226,38 @@ __global__ void MBLS_LB k_hash_fields(mbls_ws ws, const uint8_t* msgs, uint32_t 
     hash_fields_to_ws(ws.w, ws.stride, i, m, len);
 #endif
 }
+// Test probe (mbls_map_to_g2_probe): the message phase AFTER hash_to_field on field elements the caller names -- the branches no hashed message reaches (u = 0,
+// sgn0 with a zero real part, q0 = +-q1). k_map_import stands in for hash_fields_to_ws: item i's four values (canonical 48-byte big-endian) in Montgomery form
+// into slots 31, 32 / 37, 38; pair != 0: two lanes per message, lane t = 2 i + e stores into ITS item t, the odd lane with u0 and u1 exchanged (k_hash2's swap).
+// k_map_lane / k_map_pair are k_hash / k_hash2 from that point on: the same launch shape, the same LDS array, the same generated routines.
+__global__ void __launch_bounds__(WG) k_map_import(mbls_ws ws, const uint8_t* u192, uint64_t n, int pair) {
+    const uint64_t t = gid(); if (t >= (pair ? 2 * n : n)) return;
+    const uint64_t i = pair ? t >> 1 : t; const uint32_t swap = pair ? (uint32_t)(t & 1) : 0u;
+    for (uint32_t k = 0; k < 4; k++)
+        ws_st(ws, (int)(31 + (k & 1) + 6 * ((k >> 1) ^ swap)), t, fp_to_mont(fp_raw_from_be(u192 + 192 * i + 48 * k)));
+}
+__global__ void MBLS_LB k_map_lane(mbls_ws ws, uint64_t n) {
+#if MBLS_DEVICE_ASM
+    __shared__ uint32_t spill[154 * 64];
+    uint64_t i = gid(); if (i >= n) return;
+    g2_group_d_call<true>(ws, i, (MBLS_LDS uint32_t*)spill, threadIdx.x);
+#endif
+}
+__global__ void MBLS_LB k_map_pair(mbls_ws ws, uint64_t n) {
+#if MBLS_DEVICE_ASM
+    __shared__ uint32_t spill[154 * 64];
+    const uint64_t t = gid(); if (t >= 2 * n) return;
+    g2_hash2_d_call(ws, t, (MBLS_LDS uint32_t*)spill, threadIdx.x);
+#endif
+}
+// the compiled body of the same steps (mbls_hash.h / mbls_curve.h)
+__global__ void MBLS_LB k_map_body(mbls_ws ws, uint64_t n) {
+    uint64_t i = gid(); if (i >= n) return;
+    const fp2 u0 = ws_ld2(ws, 31, i), u1 = ws_ld2(ws, 37, i);
+    g2j q0, q1, h; map_to_curve_g2(&q0, &u0); map_to_curve_g2(&q1, &u1);
+    g2_add(&q0, &q0, &q1); g2_clear_cofactor(&h, &q0);
+    ws_st2(ws, MBLS_SLOT_H, i, h.x); ws_st2(ws, MBLS_SLOT_H + 2, i, h.y); ws_st2(ws, MBLS_SLOT_H + 4, i, h.z);
+}
 __global__ void MBLS_LB k_miller(mbls_ws ws, uint64_t n) {
     // one wave per SIMD = 4 waves per CU: each wave can park 36 KB of loop state in LDS (144 of the 160 KB)
     __shared__ uint32_t tstore[154 * 64];         // 11 spill slots of 14 dwords per lane for the generated loop (the running points are in HBM)
@@ -2173,6 +2205,38 @@ extern "C" int mbls_hash_to_g2_batch_mode(mbls_ctx* c, const uint8_t* msgs, uint
         hipLaunchKernelGGL(k_h_export, dim3(nblk(n)), dim3(WG), 0, c->hs_a, ws, n, dout.as<uint8_t>());
     }
     HIPCHK(c, hipStreamSynchronize(c->hs_a)); c->ws_pending = false; HIPCHK(c, dout.down(out96, 96 * n)); return MBLS_OK;
+}
+// test probe: the message phase after hash_to_field on the caller's field elements (include/mbls.h). The import kernel stands in for hash_fields_to_ws; from
+// there every mode runs what launch_hash runs for that form -- the same generated routines and wave programs, the packing limit obeyed -- and k_h_export.
+extern "C" int mbls_map_to_g2_probe(mbls_ctx* c, const uint8_t* u192, uint64_t n, uint8_t* out96, int mode) {
+    if (!c || !out96 || (!u192 && n) || mode < 0 || mode > 3) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (!n) return MBLS_OK;
+    static const uint8_t P_BE[48] = {0x1a, 0x01, 0x11, 0xea, 0x39, 0x7f, 0xe6, 0x9a, 0x4b, 0x1b, 0xa7, 0xb6, 0x43, 0x4b, 0xac, 0xd7, 0x64, 0x77, 0x4b, 0x84, 0xf3, 0x85, 0x12, 0xbf,
+                                      0x67, 0x30, 0xd2, 0xa0, 0xf6, 0xb0, 0xf6, 0x24, 0x1e, 0xab, 0xff, 0xfe, 0xb1, 0x53, 0xff, 0xff, 0xb9, 0xfe, 0xff, 0xff, 0xff, 0xff, 0xaa, 0xab};
+    for (uint64_t j = 0; j < 4 * n; j++) if (memcmp(u192 + 48 * j, P_BE, 48) >= 0) ARGFAIL(c, "a field element is not below p");
+    HIPCHK(c, hipSetDevice(c->device));
+    sbuf du(c, 0), dout(c, 1); HIPCHK(c, du.up(u192, 192 * n)); HIPCHK(c, dout.alloc(96 * n));
+    const uint64_t lanes = mode == 3 ? 2 * n : n;
+    int rc = mbls_ctx_reserve(c, lanes); if (rc) return rc;
+    mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
+    hipStream_t s = c->hs_a;
+    rc = ws_acquire(c, s); if (rc) return rc;
+    hipLaunchKernelGGL(k_map_import, dim3(nblk(lanes)), dim3(WG), 0, s, ws, du.as<uint8_t>(), n, mode == 3 ? 1 : 0);
+    if (mode == 0)
+        hipLaunchKernelGGL(k_map_body, dim3(nblk(n)), dim3(WG), 0, s, ws, n);
+    else if (mode == 1)
+        hipLaunchKernelGGL(k_map_lane, dim3(nblk(n)), dim3(WG), 0, s, ws, n);
+    else if (mode == 2)
+        coop_run(c, n > c->coop_hash_pack_min_items ? COOP_HASHG2X4 : COOP_HASHG2, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, n, (uint32_t*)nullptr, (uint8_t*)nullptr, COOP_RES_ITEM, s);
+    else {
+        hipLaunchKernelGGL(k_map_pair, dim3(nblk(2 * n)), dim3(WG), 0, s, ws, n);
+        hipLaunchKernelGGL(k_h_compact_a, dim3(nblk(n)), dim3(WG), 0, s, ws, n);
+        hipLaunchKernelGGL(k_h_compact_b, dim3(nblk(n)), dim3(WG), 0, s, ws, n);
+    }
+    hipLaunchKernelGGL(k_h_export, dim3(nblk(n)), dim3(WG), 0, s, ws, n, dout.as<uint8_t>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s)); c->ws_pending = false; HIPCHK(c, dout.down(out96, 96 * n)); return MBLS_OK;
 }
 extern "C" int mbls_aggregate_public_keys_batch(mbls_ctx* c, const uint8_t* pks, int fmt, const uint32_t* off, uint64_t n, uint32_t k,
                                                 uint8_t* apks96, uint32_t* status) {

@@ -60,6 +60,19 @@ void emul_hash_fields(const uint8_t* msgs, uint32_t mlen, uint64_t n, uint32_t* 
     }
     free(ws.w);
 }
+// hash_to_curve_g2 after hash_to_field on caller-supplied field elements (the compiled body mbls_map_to_g2_probe runs in mode 0):
+// u192 = n x (u0.c0, u0.c1, u1.c0, u1.c1), canonical 48-byte big-endian values; compressed output
+void emul_map_to_g2(const uint8_t* u192, uint64_t n, uint8_t* out96) {
+    for (uint64_t i = 0; i < n; i++) {
+        fp2 u[2];
+        for (int e = 0; e < 2; e++) {
+            u[e].c0 = fp_to_mont(fp_raw_from_be(u192 + 192 * i + 96 * e)); u[e].c1 = fp_to_mont(fp_raw_from_be(u192 + 192 * i + 96 * e + 48));
+        }
+        g2j q0, q1, h; map_to_curve_g2(&q0, &u[0]); map_to_curve_g2(&q1, &u[1]);
+        g2_add(&q0, &q0, &q1); g2_clear_cofactor(&h, &q0);
+        g2_encode_jacobian(out96 + 96 * i, &h);
+    }
+}
 void emul_fp_mul(const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out, int op) { for (uint64_t i = 0; i < n; i++) op_fp_mul(i, n, a, b, out, op); }
 void emul_aggregate(const uint8_t* pks, int fmt, const uint32_t* offsets, uint64_t n, uint32_t k, uint8_t* out96, uint32_t* status) {
     mbls_ws ws; ws.stride = n ? n : 1; ws.w = (uint32_t*)calloc((size_t)MBLS_SLOT_COUNT * 12 * ws.stride, 4);

@@ -836,8 +836,9 @@ def test_g1_sum_routine_shell(mode):
 
 
 # ---------------------------------------------------------------------------------------------- G2 group routines
-def g2_piece_runner(kind, two_lane=False):
-    """(machine, state, step): step(name) runs a body of g2_group_routine(kind) on the machine and the same program on field values"""
+def g2_piece_runner(kind, two_lane=False, log=None):
+    """(machine, state, step): step(name) runs a body of g2_group_routine(kind) on the machine and the same program on field values
+    (log: a list that receives the names of the bodies in the order they run)"""
     full, pieces, st = t.g2_group_routine(kind, two_lane) if two_lane else t.g2_group_routine(kind)
     assert not any("scratch" in l or "buffer_" in l for l in full)
     m = miller_machine(0)
@@ -848,6 +849,8 @@ def g2_piece_runner(kind, two_lane=False):
              "madd": lambda: t.prog_g2_madd(ad)}
 
     def step(name):
+        if log is not None:
+            log.append(name)
         m.run(pieces[name])
         model_name = "h_start" if name == "h_start2" else name         # the same step on field values: where q1 comes from is the machine's business
         mp = run_model(progs.get(model_name, lambda: t.prog_g2_glue(model_name)), state, masks)
@@ -944,16 +947,14 @@ def test_g2_addition_cases():
         assert jac2_affine(M, *acc) == M.g2_add(a, b), case
 
 
-def test_g2_hash_routine():
-    """The message phase's generated routine through its bodies in its control order, from the two field elements u0, u1 to H: two
-    map_to_curve evaluations (run-time records 0 and 1), q0 + q1, the cofactor clearing with two full ladders -- against the Python
-    model (sswu_g2, iso3_g2, g2_add, clear_cofactor_g2)"""
+def hash_routine_one_lane(u):
+    """the one-lane routine on the field elements u = [u0, u1], every body checked against the model as it runs and H against the model's point;
+    returns (the model's point -- None: infinity --, the names of the bodies in the order they ran)"""
     M = _g2m()
     import gen_fp_asm as gf
-    rng = random.Random(10)
     S = t.G2_SLOTS
-    u = [(rng.randrange(P), rng.randrange(P)) for _ in range(2)]
-    m, state, masks, step, add, ladder = g2_piece_runner("hash")
+    log = []
+    m, state, masks, step, add, ladder = g2_piece_runner("hash", log=log)
     m.routines.update(gf.pow_subroutines()); m.routines["mbls_fp_pow_pm3d4_asm_fn"] = gf.pow_body(gf.EXP_PM3D4)
     full, pieces, _ = t.g2_group_routine("hash")
     for rec in range(2):
@@ -974,19 +975,25 @@ def test_g2_hash_routine():
     ri = pow(R384, -1, P)
     got = [(ws_get(m, S["H"] + 2 * e) * ri % P, ws_get(m, S["H"] + 2 * e + 1) * ri % P) for e in range(3)]
     assert jac2_affine(M, *got) == want
+    return want, log
 
 
+def test_g2_hash_routine():
+    """The message phase's generated routine through its bodies in its control order, from the two field elements u0, u1 to H: two
+    map_to_curve evaluations (run-time records 0 and 1), q0 + q1, the cofactor clearing with two full ladders -- against the Python
+    model (sswu_g2, iso3_g2, g2_add, clear_cofactor_g2)"""
+    rng = random.Random(10)
+    hash_routine_one_lane([(rng.randrange(P), rng.randrange(P)) for _ in range(2)])
 
-def test_g2_hash_routine_two_lanes_per_message():
-    """k_hash2's routine on a lane pair: the even lane maps u0, the odd lane (a workspace item of its own, 4 bytes further on, u1 in the slots
-    of u0) maps u1 with the SAME body; then both fetch q0 / q1 from the even / odd lane's item (per-lane offsets) and walk the addition and
-    the cofactor clearing together, products in pairs -- the model's H in BOTH items"""
+
+def hash_routine_two_lanes(u):
+    """the two-lane routine on the field elements u = [u0, u1] (the even lane maps u0, the odd lane u1), every body checked against the model as it
+    runs and H in both items against the model's point; returns (the model's point, the names of the bodies in the order they ran)"""
     from asm_sim import run_pair
     M = _g2m()
     import gen_fp_asm as gf
-    rng = random.Random(12)
     S = t.G2_SLOTS
-    u = [(rng.randrange(P), rng.randrange(P)) for _ in range(2)]
+    log = []
     full, pieces, st = t.g2_group_routine("hash", two_lane=True)
     assert st["dbl"].get("pairs") == 3 and st["add"].get("pairs") == 7 and "pairs" not in st["sswu"] and "pairs" not in st["fix"]
     # the control skeleton is the one-lane routine's minus one map_to_curve body (a shape check: the bodies themselves are run piece by piece below)
@@ -1018,6 +1025,7 @@ def test_g2_hash_routine_two_lanes_per_message():
     progs = {"add": lambda: t.prog_g2_add(ad, False), "sub": lambda: t.prog_g2_add(ad, True), "dbl": t.prog_g2_dbl_d, "fix": lambda: t.prog_g2_dbl_d(6, 0)}
 
     def step(name, model=None):
+        log.append(name)
         run_pair(ma, mb, pieces[name])
         model = model or name
         if model == "none":
@@ -1056,6 +1064,15 @@ def test_g2_hash_routine_two_lanes_per_message():
     for lane in (0, 1):
         got = [tuple(from_limbs([ma.mem[ws_addr(S["H"] + 2 * e + h, j) + 4 * lane] for j in range(12)]) * ri % P for h in range(2)) for e in range(3)]
         assert jac2_affine(M, *got) == want, lane
+    return want, log
+
+
+def test_g2_hash_routine_two_lanes_per_message():
+    """k_hash2's routine on a lane pair: the even lane maps u0, the odd lane (a workspace item of its own, 4 bytes further on, u1 in the slots
+    of u0) maps u1 with the SAME body; then both fetch q0 / q1 from the even / odd lane's item (per-lane offsets) and walk the addition and
+    the cofactor clearing together, products in pairs -- the model's H in BOTH items"""
+    rng = random.Random(12)
+    hash_routine_two_lanes([(rng.randrange(P), rng.randrange(P)) for _ in range(2)])
 
 
 def test_compressed_squaring_decompression_formulas():
