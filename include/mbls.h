@@ -534,6 +534,59 @@ int mbls_verify_multiple_batches_rng(mbls_ctx* ctx, const uint8_t* sigs96, const
                                      uint64_t n_sets, const uint32_t* batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint8_t* results,
                                      mbls_scalar_source draw, void* user);
 
+/* verify_multiple OVER A SHARED MESSAGE LIST: ONE MILLER LOOP PER MESSAGE. The sets come in the caller's order, each with one uint32 naming its message in a
+ * list of the shape of the `_shared_msgs` entries above (msgs, msg_len or msg_offsets[n_msgs + 1], n_msgs, msg_idx[n]). Pairings are bilinear in the key argument
+ * over all of E(Fp), so  prod_i e([r_i] apk_i, H(m_i)) = prod_j e(sum_{i: msg(i) = j} [r_i] apk_i, H(m_j)):  n sets over M distinct messages need M hashes and M
+ * Miller loops instead of n of each. The list is hashed once (the path of the entries above); the blinded keys are grouped by message ON THE DEVICE (count, scan,
+ * scatter; mbls_vms.h), summed per message (k_g1_seg_tree_d) and each sum walks one Miller loop with its message's point. [r] apk, [r] sig, the signatures' sum
+ * and the single final exponentiation are mbls_verify_multiple_aggregate_signatures_device's.
+ * CONTRACT. *d_result is byte for byte what mbls_verify_multiple_aggregate_signatures_device writes for the same signatures, keys and scalars with each set's
+ * message spelled out. *d_status (optional) equals that entry's word in the bits that reject a batch -- MBLS_ST_BAD_SIG_ENCODING, MBLS_ST_SIG_NOT_IN_G2,
+ * MBLS_ST_BAD_PK_ENCODING, MBLS_ST_BAD_MSG_RANGE, MBLS_ST_BAD_SCALAR --; the other bits (MBLS_ST_APK_INFINITY, MBLS_ST_PK_INFINITY, MBLS_ST_NO_KEYS) are the OR
+ * over the sets as the key phase reports them and equal it too; MBLS_ST_PAIRING_FAILED is never set (a failed pairing check shows in the bool only, as there).
+ * n = 0: result 1, status 0. rands == NULL: MBLS_ERR_ARGUMENT. A zero scalar rejects (MBLS_ST_BAD_SCALAR). Listed messages no set names are harmless (hashed,
+ * and their Miller item has an infinite key and contributes 1). Two list entries with equal bytes are two groups.
+ * DEVICE ENTRIES (enqueue only): msg_idx[i] >= n_msgs (n_msgs = 0 included) rejects the check with MBLS_ST_BAD_MSG_RANGE -- such a set joins no group --; a listed
+ * message whose range runs backwards or is 2^32 bytes or more rejects the check exactly when a set names it. Neither becomes a read outside the call's buffers,
+ * and every slot a Miller loop reads has been written by this call. HOST ENTRIES refuse both with MBLS_ERR_ARGUMENT before anything is queued (outputs untouched).
+ * ROUTING (mbls_ctx_set_vm_grouping; mbls_ctx_reset_tuning restores 0): 0 auto -- grouped when 2 n_msgs <= n --, 1 always grouped, 2 never: the list is still
+ * hashed once and every set copies its message's point (k_h_gather) and walks its own Miller loop -- the route for lists with almost as many messages as sets.
+ * ALLOCATION: workspace (mbls_plan_verify_multiple_shared_msgs_workspace_items) and message table are reserved once, before the first kernel;
+ * mbls_ctx_reserve and mbls_ctx_reserve_msgs beforehand keep allocation out of the call.
+ * OUT OF SCOPE: the mbls_multi handle, the verification stream, the shard form (d_partial) and sets given by wire-format keys (d_pks) take per-set messages only. */
+int mbls_ctx_set_vm_grouping(mbls_ctx* ctx, int mode);
+/* Routing as data (pure: no GPU, no context; the SAME function the entries act on). route; the list hash as mbls_plan_batch_shared_msgs states it (list_*,
+ * table_entries); miller_items = the one-pair Miller loops (grouped: max(n_msgs, 1); per set: n), walked one WAVE each (miller = MBLS_PAIRING_WAVE) up to
+ * coop_max_items / 2, else as miller_rounds whole rounds of one lane each followed by miller_rest_items in the form `miller` (MBLS_PAIRING_LANES2 up to half a
+ * round, MBLS_PAIRING_LANE); tree_levels = the levels of the per-message key sums a DEVICE entry enqueues (all n sets may share a message: vmb_levels(n); the
+ * host entries count the longest group and enqueue fewer); chains_beside / sig_lane_pairs: the per-set chains as mbls_verify_multiple_aggregate_signatures_device
+ * shapes them (side by side up to half a round; two lanes per signature up to coop_max_items / 2); workspace_items = what the call reserves.
+ * MBLS_ERR_ARGUMENT for n = 0, a mode outside 0..2 or null pointers (the workspace function then returns 0). */
+enum { MBLS_VM_ROUTE_PER_SET = 0, MBLS_VM_ROUTE_GROUPED = 1 };
+typedef struct mbls_vm_shared_msgs_plan {
+    uint32_t route, list_message, list_pieces, miller, tree_levels, chains_beside, sig_lane_pairs, reserved;
+    uint64_t list_piece_items, list_workspace_items, table_entries, miller_items, miller_rounds, miller_rest_items, workspace_items;
+} mbls_vm_shared_msgs_plan;
+int mbls_plan_verify_multiple_shared_msgs(const mbls_limits* limits, uint64_t n, uint64_t n_msgs, int mode, mbls_vm_shared_msgs_plan* out);
+uint64_t mbls_plan_verify_multiple_shared_msgs_workspace_items(const mbls_limits* limits, uint64_t n, uint64_t n_msgs, int mode);
+int mbls_verify_multiple_shared_msgs_device(mbls_ctx* ctx, const uint8_t* d_sigs96, const uint8_t* d_apks96, const uint8_t* d_msgs, uint32_t msg_len,
+                                            const uint64_t* d_msg_offsets, uint64_t n_msgs, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n,
+                                            uint8_t* d_result, uint32_t* d_status, void* stream);
+/* keys by index into a resident key table, as mbls_verify_multiple_sets_indexed_device names them (the deployment's form) */
+int mbls_verify_multiple_sets_indexed_shared_msgs_device(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* d_sigs96, const uint32_t* d_key_idx,
+                                                         const uint32_t* d_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len,
+                                                         const uint64_t* d_msg_offsets, uint64_t n_msgs, const uint32_t* d_msg_idx, const uint64_t* d_rands,
+                                                         uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream);
+/* host buffers; returns a status code, the bool through *result (and the status word through *status, optional), like mbls_verify_multiple_batches */
+int mbls_verify_multiple_shared_msgs(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len,
+                                     const uint64_t* msg_offsets, uint64_t n_msgs, const uint32_t* msg_idx, const uint64_t* rands, uint64_t n,
+                                     uint8_t* result, uint32_t* status);
+/* the reference's order exactly as mbls_verify_multiple_aggregate_signatures_rng keeps it: signatures decoded and tested first, `draw` called at most once for
+ * the sets in front of the first bad signature (*result = 0 then), no second subgroup test */
+int mbls_verify_multiple_shared_msgs_rng(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len,
+                                         const uint64_t* msg_offsets, uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result,
+                                         mbls_scalar_source draw, void* user);
+
 /* ---- batch helpers used to build inputs and caches on the device ---- */
 /* n x PublicKey::from_bytes[_unchecked] / from_uncompressed_bytes: errs[i] = MBLS_OK / MBLS_ERR_* per key */
 int mbls_pk_decode_batch(mbls_ctx* ctx, const uint8_t* in, int in_format, int validate, uint64_t n, uint8_t* out96, uint8_t* errs);

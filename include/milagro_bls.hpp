@@ -9,6 +9,7 @@
 //     AggregateSignature::fast_aggregate_verify(..)      same
 //     AggregateSignature::verify_multiple_aggregate_signatures(rng, iter)   same, rng = any callable returning uint8_t
 //     (one call of it per batch, batch after batch)      AggregateSignature::verify_multiple_aggregate_signatures_batches(rng, batches) -> vector<bool>, ONE call
+//     (the same over sets that share messages)            AggregateSignature::verify_multiple_aggregate_signatures_shared_msgs(rng, iter): one hash and, where it pays, one Miller loop per message
 //
 // Every curve / pairing operation runs in the HIP kernels; there is no CPU fallback: constructing the first object without a
 // GPU throws DeviceError. The only host arithmetic is SecretKey::key_generate (HKDF-SHA-256 + one reduction mod r), which the
@@ -22,6 +23,7 @@
 #include <cstring>
 #include <deque>
 #include <exception>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <random>
@@ -271,6 +273,37 @@ struct AggregateSignature {
         const bool ok = mbls_verify_multiple_aggregate_signatures_rng(detail::ctx(), sigs.data(), apks.data(), msgs.data(), 0, moff.data(), sets.size(), draw, &u) == 1;
         if (u.err) std::rethrow_exception(u.err);
         return ok;
+    }
+    // Not in the reference: verify_multiple_aggregate_signatures(rng, sets) -- same sets, same bool, rng left in the same state -- for batches whose sets share
+    // messages (mbls_verify_multiple_shared_msgs_rng): the messages are deduplicated here by their bytes, each distinct message is hashed once and, where it
+    // pays, the check walks one Miller loop per message instead of one per set.
+    template <typename Rng>
+    static bool verify_multiple_aggregate_signatures_shared_msgs(Rng&& rng, const std::vector<std::tuple<const AggregateSignature*, const AggregatePublicKey*, Bytes>>& sets) {
+        if (sets.empty()) return true;
+        Bytes sigs, apks, msgs; std::vector<uint64_t> moff{0}; std::vector<uint32_t> idx; std::map<Bytes, uint32_t> index;
+        for (auto& s : sets) {
+            sigs.insert(sigs.end(), std::get<0>(s)->point.begin(), std::get<0>(s)->point.end());
+            apks.insert(apks.end(), std::get<1>(s)->point.begin(), std::get<1>(s)->point.end());
+            auto it = index.find(std::get<2>(s));
+            if (it == index.end()) {
+                it = index.emplace(std::get<2>(s), uint32_t(index.size())).first;
+                msgs.insert(msgs.end(), std::get<2>(s).begin(), std::get<2>(s).end());
+                moff.push_back(msgs.size());
+            }
+            idx.push_back(it->second);
+        }
+        using R = typename std::remove_reference<Rng>::type;
+        struct src { R* rng; std::exception_ptr err; } u{&rng, nullptr};
+        mbls_scalar_source draw = [](void* user, uint64_t* out, uint64_t count) {
+            src* p = static_cast<src*>(user);
+            try { for (uint64_t i = 0; i < count; i++) out[i] = draw_scalar(*p->rng); }
+            catch (...) { p->err = std::current_exception(); for (uint64_t i = 0; i < count; i++) out[i] = 0; }        // never unwind through the C frames
+        };
+        uint8_t ok = 0;
+        const int rc = mbls_verify_multiple_shared_msgs_rng(detail::ctx(), sigs.data(), apks.data(), msgs.data(), 0, moff.data(), index.size(), idx.data(), sets.size(), &ok, draw, &u);
+        if (u.err) std::rethrow_exception(u.err);
+        detail::check(rc);
+        return ok == 1;
     }
     // Not in the reference: what verify_multiple_aggregate_signatures(rng, batch) returns for every batch of `batches`, called once per batch in order -- as ONE
     // call (mbls_verify_multiple_batches_rng), for about the cost of one such call. One bool per batch; a bad batch rejects itself and nothing else. The scalars

@@ -101,6 +101,33 @@ def plan_shared_msgs_workspace_items(n, n_msgs, k, split_layout=True, limits=Non
     return int(lib().mbls_plan_shared_msgs_workspace_items(C.byref(L), n, n_msgs, k, 1 if split_layout else 0))
 
 
+class VmSharedMsgsPlan(C.Structure):
+    """include/mbls.h mbls_vm_shared_msgs_plan"""
+    _fields_ = [(n, C.c_uint32) for n in ("route", "list_message", "list_pieces", "miller", "tree_levels", "chains_beside", "sig_lane_pairs", "reserved")] + \
+               [(n, C.c_uint64) for n in ("list_piece_items", "list_workspace_items", "table_entries", "miller_items", "miller_rounds", "miller_rest_items",
+                                          "workspace_items")]
+
+
+VM_ROUTE_PER_SET, VM_ROUTE_GROUPED = 0, 1
+VM_GROUPING_AUTO, VM_GROUPING_ALWAYS, VM_GROUPING_NEVER = 0, 1, 2
+
+
+def plan_verify_multiple_shared_msgs(n, n_msgs, mode=0, limits=None):
+    """what the verify_multiple*_shared_msgs entries would do with n sets over a list of n_msgs messages under `limits` and grouping mode (pure: no GPU) -> dict"""
+    L = limits if limits is not None else default_limits()
+    vp_ = VmSharedMsgsPlan()
+    rc = lib().mbls_plan_verify_multiple_shared_msgs(C.byref(L), n, n_msgs, mode, C.byref(vp_))
+    if rc != OK:
+        raise MblsError(rc, "mbls_plan_verify_multiple_shared_msgs")
+    return {f: getattr(vp_, f) for f, _ in VmSharedMsgsPlan._fields_ if f != "reserved"}
+
+
+def plan_verify_multiple_shared_msgs_workspace_items(n, n_msgs, mode=0, limits=None):
+    """workspace items such a call reserves (pure: no GPU; 0 for arguments the plan refuses)"""
+    L = limits if limits is not None else default_limits()
+    return int(lib().mbls_plan_verify_multiple_shared_msgs_workspace_items(C.byref(L), n, n_msgs, mode))
+
+
 class StreamOpts(C.Structure):
     """include/mbls.h mbls_stream_opts (0 = default)"""
     _fields_ = [("round_items", C.c_uint64), ("round_keys", C.c_uint64), ("round_msg_bytes", C.c_uint64), ("depth", C.c_uint32), ("policy", C.c_uint32)]
@@ -216,6 +243,13 @@ SIGNATURES = {
     "mbls_verify_multiple_sets_indexed_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
     "mbls_verify_multiple_partial_device": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, vp]),
     "mbls_verify_multiple_finish_device": (C.c_int, [vp, vp, C.c_uint64, vp, vp, vp]),
+    "mbls_ctx_set_vm_grouping": (C.c_int, [vp, C.c_int]),
+    "mbls_plan_verify_multiple_shared_msgs": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, vp]),
+    "mbls_plan_verify_multiple_shared_msgs_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64, C.c_int]),
+    "mbls_verify_multiple_shared_msgs_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp]),
+    "mbls_verify_multiple_sets_indexed_shared_msgs_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp]),
+    "mbls_verify_multiple_shared_msgs": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp]),
+    "mbls_verify_multiple_shared_msgs_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, SCALAR_SOURCE, vp]),
     "mbls_verify_multiple_batches_device": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp, vp]),
     "mbls_verify_multiple_batches_indexed_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp, vp]),
     "mbls_verify_multiple_batches": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp]),

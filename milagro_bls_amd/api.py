@@ -330,6 +330,50 @@ class AggregateSignature:
         return ok
 
     @staticmethod
+    def verify_multiple_aggregate_signatures_shared_msgs(rng, signature_sets):
+        """Not in the reference: verify_multiple_aggregate_signatures(rng, signature_sets) -- the same (signature, aggregate_public_key, message) sets, the same
+        bool, `rng` left in the same state -- for batches whose sets share messages (a slot's gossip: tens of thousands of sets over a few hundred signing
+        roots). The messages are deduplicated here by their bytes, and ONE call (mbls_verify_multiple_shared_msgs_rng) hashes each distinct message once and,
+        where it pays, walks one Miller loop per message instead of one per set. The scalars are drawn as there, in the reference's order."""
+        sets = list(signature_sets)
+        if not sets:
+            return True
+        failed = []
+
+        def draw(_user, out, count):                    # src/aggregates.rs:280-287, as verify_multiple_aggregate_signatures draws
+            try:
+                for i in range(count):
+                    r = 0
+                    while r == 0:
+                        v = int.from_bytes(bytes(rng.getrandbits(8) for _ in range(8)), "big", signed=True)
+                        r = abs(v) & 0xFFFFFFFFFFFFFFFF
+                    out[i] = r
+            except BaseException as e:                  # an exception must not unwind through the C frames: the batch fails, the error is raised afterwards
+                failed.append(e)
+                for i in range(count):
+                    out[i] = 0
+        index, listed, idx = {}, [], []
+        for s in sets:
+            m = bytes(s[2])
+            if m not in index:
+                index[m] = len(listed)
+                listed.append(m)
+            idx.append(index[m])
+        offs = [0]
+        for m in listed:
+            offs.append(offs[-1] + len(m))
+        moff = (C.c_uint64 * len(offs))(*offs)
+        midx = (C.c_uint32 * len(idx))(*idx)
+        cb = N.SCALAR_SOURCE(draw)
+        res = N.outbuf(1)
+        ctx = _ctx()
+        ctx.check(N.lib().mbls_verify_multiple_shared_msgs_rng(ctx.handle, N.cbuf(b"".join(s[0].point for s in sets)), N.cbuf(b"".join(s[1].point for s in sets)),
+                                                               N.cbuf(b"".join(listed)), 0, moff, len(listed), midx, len(sets), res, cb, None))
+        if failed:
+            raise failed[0]
+        return bool(bytes(res)[0])
+
+    @staticmethod
     def verify_multiple_aggregate_signatures_batches(rng, batches):
         """Not in the reference: what calling verify_multiple_aggregate_signatures(rng, batch) once per batch, in order, returns -- as ONE call on the GPU
         (mbls_verify_multiple_batches_rng), which costs about what one such call costs. `batches`: an iterable of iterables of

@@ -389,3 +389,56 @@ def verify_multiple_batches_indexed_device(table, d_sigs, d_key_idx, d_msgs, d_r
     ctx = ctx or table.ctx
     ctx.check(N.lib().mbls_verify_multiple_batches_indexed_device(ctx.handle, table.handle, d_sigs, d_key_idx, d_offsets, k, d_msgs, msg_len, d_msg_offsets, d_rands,
                                                                   n_sets, d_batch_offsets, sets_per_batch, n_batches, d_results, d_status, stream))
+
+
+# ---- verify_multiple over a shared message list: one Miller loop per message (include/mbls.h, mbls_verify_multiple*_shared_msgs)
+def set_vm_grouping(mode, ctx=None):
+    """routing of the entries below: 0 auto (grouped when 2 n_msgs <= n), 1 always one Miller loop per message, 2 never (every set gathers its message's point)"""
+    ctx = ctx or _c()
+    ctx.check(N.lib().mbls_ctx_set_vm_grouping(ctx.handle, mode))
+
+
+plan_verify_multiple_shared_msgs = N.plan_verify_multiple_shared_msgs
+
+
+def verify_multiple_shared_msgs(sigs, apks, msgs, n_msgs, msg_idx, rands, n, msg_len=32, msg_offsets=None, ctx=None):
+    """verify_multiple_aggregate_signatures (reference src/aggregates.rs:261-316) over n sets whose messages are named by index in a LIST of n_msgs messages
+    (msg_len bytes each, or msg_offsets of n_msgs + 1 entries); host buffers (signatures 96 B, decoded aggregate keys 96 B, one nonzero 64-bit scalar per set).
+    Returns (bool, status word): what verify_multiple returns with set i's message spelled out."""
+    ctx = ctx or _c()
+    res = N.outbuf(1)
+    st = C.c_uint32(0)
+    r = None if rands is None else (C.c_uint64 * max(1, n))(*rands)
+    ctx.check(N.lib().mbls_verify_multiple_shared_msgs(ctx.handle, N.cbuf(sigs), N.cbuf(apks), N.cbuf(msgs), msg_len, _moff(msg_offsets), n_msgs, _midx(msg_idx, n), r, n,
+                                                       res, C.byref(st)))
+    return bool(bytes(res)[0]), st.value
+
+
+def verify_multiple_shared_msgs_rng(sigs, apks, msgs, n_msgs, msg_idx, n, draw, msg_len=32, msg_offsets=None, ctx=None):
+    """The same with the reference's draw order (mbls_verify_multiple_shared_msgs_rng): draw(count) -> `count` nonzero scalars, called at most once, for the sets
+    in front of the first signature outside G2. Returns the bool."""
+    ctx = ctx or _c()
+    res = N.outbuf(1)
+
+    def source(_user, out, count):
+        for i, v in enumerate(draw(int(count))):
+            out[i] = v
+    cb = N.SCALAR_SOURCE(source)
+    ctx.check(N.lib().mbls_verify_multiple_shared_msgs_rng(ctx.handle, N.cbuf(sigs), N.cbuf(apks), N.cbuf(msgs), msg_len, _moff(msg_offsets), n_msgs, _midx(msg_idx, n), n,
+                                                           res, cb, None))
+    return bool(bytes(res)[0])
+
+
+def verify_multiple_shared_msgs_device(d_sigs, d_apks, d_msgs, n_msgs, d_msg_idx, d_rands, n, d_result, d_status=None, msg_len=32, d_msg_offsets=None, stream=None, ctx=None):
+    """The same over device buffers (raw device pointers / ints). Enqueues only: the bool at the device byte d_result, the status word at d_status (optional)."""
+    ctx = ctx or _c()
+    ctx.check(N.lib().mbls_verify_multiple_shared_msgs_device(ctx.handle, d_sigs, d_apks, d_msgs, msg_len, d_msg_offsets, n_msgs, d_msg_idx, d_rands, n, d_result, d_status,
+                                                              stream))
+
+
+def verify_multiple_sets_indexed_shared_msgs_device(table, d_sigs, d_key_idx, d_msgs, n_msgs, d_msg_idx, d_rands, n, d_result, d_status=None, k=0, d_offsets=None, msg_len=32,
+                                                    d_msg_offsets=None, stream=None, ctx=None):
+    """The same over sets named by indices into a resident KeyTable (the deployment's form). Enqueues only."""
+    ctx = ctx or table.ctx
+    ctx.check(N.lib().mbls_verify_multiple_sets_indexed_shared_msgs_device(ctx.handle, table.handle, d_sigs, d_key_idx, d_offsets, k, d_msgs, msg_len, d_msg_offsets, n_msgs,
+                                                                           d_msg_idx, d_rands, n, d_result, d_status, stream))

@@ -20,6 +20,7 @@
 #include "mbls_ops.h"
 #include "mbls_coop.h"
 #include "mbls_vmb.h"
+#include "mbls_vms.h"
 #include "../../include/mbls.h"
 
 // The product library exists only with the generated routines: the host side below selects kernels (the fused subgroup verdict of
@@ -611,6 +612,78 @@ __global__ void MBLS_LB k_vmb_gather(mbls_ws ws, const uint32_t* off, uint32_t k
     for (int t = 0; t < 12; t++) ws_st(ws, MBLS_SLOT_F + t, n + B + b, some ? ws_ld(ws, MBLS_SLOT_F + t, lo) : one[t]);
     if (st) atomicOr(st_batch + b, st);
 }
+// ---- verify_multiple over a shared message list, one Miller loop per MESSAGE (mbls_verify_multiple*_shared_msgs): prod_i e([r_i] apk_i, H(m_i)) =
+// prod_j e(sum_{i: msg(i) = j} [r_i] apk_i, H(m_j)). The blinded keys (slot APK of the sets [0, n), the Jacobian form k_blind_g1_d leaves) are moved to
+// POSITIONS -- workspace items pbase + p, the sets of one message next to each other --, summed there by per-message trees and the sums handed to the Miller
+// items [0, miller_items). The arithmetic of groups, positions and ranges is mbls_vms.h's (host-testable). All of it is enqueued: the host never sees the indices.
+// sets per message (one lane per set); a set whose index names no message joins no group and carries the bit that rejects the check
+__global__ void MBLS_LB k_vms_count(const uint32_t* msg_idx, uint64_t n_msgs, uint64_t n, uint32_t* cnt, uint32_t* status) {
+    const uint64_t i = gid(); if (i >= n) return;
+    const uint32_t g = vms_group(msg_idx[i], n_msgs);
+    if (g == MBLS_VMS_NO_GROUP) atomicOr(status + i, MBLS_ST_BAD_MSG_RANGE);
+    else atomicAdd(cnt + g, 1u);
+}
+// off[0 .. n_msgs] = the exclusive scan of the counts: ONE workgroup, lane t sums its chunk (vms_scan_chunk), the chunk sums are scanned in LDS, lane t writes its chunk
+__global__ void __launch_bounds__(MBLS_VMS_SCAN_LANES) k_vms_scan(const uint32_t* cnt, uint64_t n_msgs, uint32_t* off) {
+    __shared__ uint32_t part[MBLS_VMS_SCAN_LANES];
+    const uint32_t t = threadIdx.x;
+    uint64_t lo, hi; vms_scan_chunk(n_msgs, MBLS_VMS_SCAN_LANES, t, &lo, &hi);
+    uint32_t sum = 0;
+    for (uint64_t j = lo; j < hi; j++) sum += cnt[j];
+    part[t] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < MBLS_VMS_SCAN_LANES; d *= 2) {
+        const uint32_t v = t >= d ? part[t - d] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - sum;
+    for (uint64_t j = lo; j < hi; j++) { off[j] = run; run += cnt[j]; }
+    if (t == MBLS_VMS_SCAN_LANES - 1) off[n_msgs] = part[t];
+}
+// set i takes a position inside its message's range (vms_position; the ticket from the group's atomic counter), its blinded key moves there, and the map says
+// which message the position belongs to. The order inside a group depends on the order the atomics arrive in and differs from run to run; the RESULT and the
+// STATUS do not: a group's sum is a sum in the abelian group E(Fp), which g1_tree_routine computes exactly whatever the operands are (equal, opposite,
+// infinite: settled by selection), so every order gives the same POINT -- in another Jacobian representation at most, and the Miller loop reads the point
+// through its affine coordinates --, and the status bits are ORs over the sets.
+__global__ void MBLS_LB k_vms_scatter(mbls_ws ws, const uint32_t* msg_idx, uint64_t n_msgs, uint64_t n, const uint32_t* off, uint32_t* cur, uint32_t* map, uint64_t pbase) {
+    const uint64_t i = gid(); if (i >= n) return;
+    const uint32_t g = vms_group(msg_idx[i], n_msgs);
+    if (g == MBLS_VMS_NO_GROUP) return;
+    const uint64_t p = vms_position(off, g, atomicAdd(cur + g, 1u));
+    if (p >= n) return;                                                // (tickets stay below the count: the counts were taken from the same indices)
+    map[p] = g;
+    const uint32_t* src = ws.w + (uint64_t)MBLS_SLOT_APK * 12 * ws.stride + i;
+    uint32_t* dst = ws.w + (uint64_t)MBLS_SLOT_APK * 12 * ws.stride + pbase + p;
+#pragma unroll 12
+    for (int w = 0; w < 36; w++) dst[(uint64_t)w * ws.stride] = src[(uint64_t)w * ws.stride];
+}
+// One level of the per-message sums of the blinded keys (slot APK of the positions; wp = the workspace seen from the first position): the twin of k_g2_seg_tree_d
+// on the generated G1 addition; lanes without a partner at this level return before the routine.
+__global__ void MBLS_LB k_g1_seg_tree_d(mbls_ws wp, const uint32_t* map, const uint32_t* off, uint64_t n_msgs, uint64_t n, uint64_t half) {
+#if MBLS_DEVICE_ASM
+    const uint64_t p = gid();
+    uint64_t lo, hi;
+    if (!vms_owner_range(map, off, n_msgs, n, p, &lo, &hi)) return;
+    if (!vmb_takes_partner(p, lo, hi, half)) return;
+    g1_tree_d_call(wp, p, half, threadIdx.x);
+#endif
+}
+// Miller item j < miller_items: H <- the table entry of message j (lane_h_gather; an empty list: the empty message's), APK <- the sum at the head of message
+// j's range, infinity for a message no set names (its pair is skipped: it contributes 1). A listed message with a bad range rejects the check exactly when a
+// set names it: its bit goes to the call's status word. Every slot the Miller loops read is written here.
+__global__ void __launch_bounds__(MBLS_HB) k_vms_heads(mbls_ws ws, const uint32_t* tab, uint64_t tstride, const uint32_t* flags, const uint32_t* off, const uint32_t* cnt,
+                                                       uint64_t n_msgs, uint64_t miller_items, uint64_t pbase, uint32_t* st_or) {
+    const uint64_t j = (uint64_t)blockIdx.x * MBLS_HB + threadIdx.x; if (j >= miller_items) return;
+    const uint32_t st = lane_h_gather(ws, j, tab, tstride, flags, (uint32_t)j, n_msgs);
+    const bool some = j < n_msgs && cnt[j] != 0;
+    const uint64_t it = pbase + (some ? (uint64_t)off[j] : 0);             // (the first position exists in every such workspace: a message without sets reads it and keeps nothing)
+    g1j o; g1_set_inf(&o);
+    g1j a; a.x = ws_ld(ws, MBLS_SLOT_APK, it); a.y = ws_ld(ws, MBLS_SLOT_APK + 1, it); a.z = ws_ld(ws, MBLS_SLOT_APK + 2, it);
+    ws_st(ws, MBLS_SLOT_APK, j, fp_select(some, a.x, o.x)); ws_st(ws, MBLS_SLOT_APK + 1, j, fp_select(some, a.y, o.y)); ws_st(ws, MBLS_SLOT_APK + 2, j, fp_select(some, a.z, o.z));
+    if (some && st) atomicOr(st_or, st);
+}
 // the tail: one final exponentiation per batch with verify_multiple's reject mask (lane_final<true>: the body of k_final / k_final2, the fold of final_fold_batch)
 __global__ void MBLS_LB k_vmb_final(mbls_ws ws, uint32_t* status, uint8_t* results, uint64_t n) {
     __shared__ uint32_t accstore[154 * 64];
@@ -944,6 +1017,10 @@ struct mbls_ctx {
     // shared message lists (mbls_*_shared_msgs): the hashed points of a call's list, [72][htab_cap] dwords (entry 0: H of the empty message, hashed on the first
     // call after every (re)allocation; message j: entry j + 1), one bad-range word per entry, and the status words of the list's own hash
     uint64_t htab_cap = 0; uint32_t* d_htab = nullptr; uint32_t* d_hflag = nullptr; uint32_t* d_hst = nullptr; bool h_empty_ready = false;
+    // verify_multiple over a shared list, grouped by message (mbls_vms.h): per table entry the sets that name it, the cursor that hands out their positions and
+    // the exclusive scan (d_hgrp: [3][htab_cap], allocated with the table), and per workspace item the map position -> message (d_vmap: [cap], with the workspace)
+    uint32_t* d_hgrp = nullptr; uint32_t* d_vmap = nullptr;
+    int vm_grouping = 0;               // mbls_ctx_set_vm_grouping: 0 auto (vms_grouped), 1 always one Miller loop per message, 2 never
     struct { void* p; size_t cap; } stage[MBLS_N_STAGE] = {};
     hipStream_t hs_a = nullptr, hs_b = nullptr, hs_c = nullptr, hs_d = nullptr;      // streams of the host-buffer entry points (hs_d: the signature phase while hs_b uploads keys)
     hipEvent_t hs_ev = nullptr, hs_ev2 = nullptr, hs_ev3 = nullptr;
@@ -1056,6 +1133,8 @@ static void ctx_free(mbls_ctx* c) {
     if (c->d_htab) (void)hipFree(c->d_htab);
     if (c->d_hflag) (void)hipFree(c->d_hflag);
     if (c->d_hst) (void)hipFree(c->d_hst);
+    if (c->d_hgrp) (void)hipFree(c->d_hgrp);
+    if (c->d_vmap) (void)hipFree(c->d_vmap);
     if (c->d_coop) (void)hipFree(c->d_coop);
     for (int i = 0; i < MBLS_N_STAGE; i++) if (c->stage[i].p) (void)hipFree(c->stage[i].p);
     for (int i = 0; i <= MBLS_N_PHASES; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1147,6 +1226,7 @@ extern "C" int mbls_ctx_set_coop_packing(mbls_ctx* c, uint64_t pairing_min_items
 }
 // every routing parameter back to its default (what mbls_ctx_create sets, environment included)
 static void ctx_default_tuning(mbls_ctx* c) {
+    c->vm_grouping = 0;
     c->coop_max_items = MBLS_DEFAULT_COOP_MAX_ITEMS; c->coop_hash_max_items = MBLS_DEFAULT_COOP_HASH_MAX_ITEMS;
     c->coop_pack_min_items = 1024; c->coop_pack_max_items = 2048; c->coop_hash_pack_min_items = 768;
     hipDeviceProp_t prop;
@@ -1168,6 +1248,12 @@ extern "C" int mbls_ctx_reset_tuning(mbls_ctx* c) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
     ctx_default_tuning(c); return MBLS_OK;
+}
+// verify_multiple over a shared message list: 0 auto (group when 2 n_msgs <= n), 1 always one Miller loop per message, 2 never (mbls_vms.h vms_grouped)
+extern "C" int mbls_ctx_set_vm_grouping(mbls_ctx* c, int mode) {
+    if (!c || mode < 0 || mode > 2) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    c->vm_grouping = mode; return MBLS_OK;
 }
 // items per round of the one-lane kernels (default: CUs x 4 SIMDs x 64 lanes); batches above it have their remainder routed as a batch of its own
 extern "C" int mbls_ctx_set_round_items(mbls_ctx* c, uint64_t items) {
@@ -1210,7 +1296,9 @@ extern "C" int mbls_ctx_reserve(mbls_ctx* c, uint64_t max_items) {
     uint64_t want = ((max_items + 1 + WG - 1) / WG) * WG;     // +1: the extra (sig, -G1) lane of the n-pairing paths
     if (want <= c->cap) return MBLS_OK;
     if (c->d_w) { (void)hipFree(c->d_w); (void)hipFree(c->d_status); (void)hipFree(c->d_results); c->d_w = nullptr; c->d_status = nullptr; c->d_results = nullptr; c->cap = 0; }
+    if (c->d_vmap) { (void)hipFree(c->d_vmap); c->d_vmap = nullptr; }
     HIPCHK(c, hipMalloc(&c->d_w, (size_t)MBLS_SLOT_TOTAL * 12 * want * 4));
+    HIPCHK(c, hipMalloc(&c->d_vmap, want * 4));
     HIPCHK(c, hipMalloc(&c->d_status, want * 4));
     HIPCHK(c, hipMalloc(&c->d_results, want));
     c->cap = want; return MBLS_OK;
@@ -1234,7 +1322,9 @@ static int reserve_msgs(mbls_ctx* c, uint64_t max_msgs) {
     const uint64_t want = ((max_msgs + 1 + WG - 1) / WG) * WG;
     if (want <= c->htab_cap) return MBLS_OK;
     if (c->d_htab) { (void)hipFree(c->d_htab); (void)hipFree(c->d_hflag); (void)hipFree(c->d_hst); c->d_htab = nullptr; c->d_hflag = nullptr; c->d_hst = nullptr; c->htab_cap = 0; }
+    if (c->d_hgrp) { (void)hipFree(c->d_hgrp); c->d_hgrp = nullptr; }
     c->h_empty_ready = false;
+    HIPCHK(c, hipMalloc(&c->d_hgrp, 3 * want * 4));
     HIPCHK(c, hipMalloc(&c->d_htab, (size_t)MBLS_H_DWORDS * want * 4));
     HIPCHK(c, hipMalloc(&c->d_hflag, want * 4));
     HIPCHK(c, hipMalloc(&c->d_hst, want * 4));
@@ -1424,6 +1514,38 @@ extern "C" uint64_t mbls_plan_shared_msgs_workspace_items(const mbls_limits* lim
     mbls_shared_msgs_plan sp; plan_shared(*limits, n, n_msgs, false, false, &sp);
     const uint64_t a = mbls_plan_workspace_items(limits, n, k, split_layout);
     return a > sp.list_workspace_items ? a : sp.list_workspace_items;
+}
+// verify_multiple over a shared message list (mbls_verify_multiple*_shared_msgs): the route, the form of the list hash (plan_shared's), the Miller items, the
+// tree levels and the workspace, as a pure function of the limits -- what verify_multiple_impl acts on. The thresholds are verify_multiple_impl's: n for the
+// per-set chains, the Miller items for the Miller phase.
+static void plan_vm_shared(const mbls_limits& L, uint64_t n, uint64_t n_msgs, int mode, uint64_t longest, mbls_vm_shared_msgs_plan* vp) {
+    memset(vp, 0, sizeof(*vp));
+    mbls_shared_msgs_plan sp; plan_shared(L, n, n_msgs, false, false, &sp);
+    vp->list_message = sp.list_message; vp->list_pieces = sp.list_pieces; vp->list_piece_items = sp.list_piece_items;
+    vp->list_workspace_items = sp.list_workspace_items; vp->table_entries = sp.table_entries;
+    const bool grouped = vms_grouped(n, n_msgs, mode);
+    vp->route = grouped ? MBLS_VM_ROUTE_GROUPED : MBLS_VM_ROUTE_PER_SET;
+    vp->miller_items = grouped ? vms_miller_items(n_msgs) : n;
+    vp->tree_levels = grouped ? vms_levels(n, longest) : 0;
+    vp->workspace_items = vms_workspace_items(n, n_msgs, grouped, sp.list_workspace_items);
+    vp->chains_beside = 2 * n <= L.round_items ? 1 : 0;
+    vp->sig_lane_pairs = 2 * n <= L.coop_max_items ? 1 : 0;
+    const uint64_t m = vp->miller_items, R = L.round_items;
+    if (2 * m <= L.coop_max_items) { vp->miller = MBLS_PAIRING_WAVE; vp->miller_rest_items = m; }       // npairing_finish / launch_miller_single
+    else {
+        const uint64_t full = (R && m > R) ? (m / R) * R : 0, rest = m - full;
+        vp->miller_rounds = R ? full / R : 0; vp->miller_rest_items = rest;
+        vp->miller = (rest && 2 * rest <= R) ? MBLS_PAIRING_LANES2 : MBLS_PAIRING_LANE;
+    }
+}
+extern "C" int mbls_plan_verify_multiple_shared_msgs(const mbls_limits* limits, uint64_t n, uint64_t n_msgs, int mode, mbls_vm_shared_msgs_plan* out) {
+    if (!limits || !out || !n || mode < 0 || mode > 2) return MBLS_ERR_ARGUMENT;
+    plan_vm_shared(*limits, n, n_msgs, mode, 0, out); return MBLS_OK;
+}
+extern "C" uint64_t mbls_plan_verify_multiple_shared_msgs_workspace_items(const mbls_limits* limits, uint64_t n, uint64_t n_msgs, int mode) {
+    if (!limits || !n || mode < 0 || mode > 2) return 0;
+    mbls_vm_shared_msgs_plan vp; plan_vm_shared(*limits, n, n_msgs, mode, 0, &vp);
+    return vp.workspace_items;
 }
 #ifdef MBLS_COOP_PROFILE
 extern "C" int mbls_coop_profile_read(unsigned long long out[64], int reset) {     // dev builds only (not declared in mbls.h)
@@ -2497,7 +2619,9 @@ static void launch_miller_single(mbls_ctx* c, mbls_ws ws, uint64_t m, hipStream_
     else hipLaunchKernelGGL(k_miller_single, dim3(nblk(rest)), dim3(WG), 0, s, wr, rest, 0, (uint64_t)0);
 }
 static int npairing_finish(mbls_ctx* c, uint64_t n, hipStream_t s, uint8_t* d_result, hipEvent_t s_miller_ev = nullptr, bool late_status = false,
-                           uint32_t* d_partial = nullptr, bool side_s_chain = false) {
+                           uint32_t* d_partial = nullptr, bool side_s_chain = false, uint64_t n_sets = 0) {
+    // n_sets (grouped shared-message route): the n Miller items are the MESSAGES; the signatures' sum tree and the status fold still cover all n_sets sets
+    const uint64_t ns = n_sets ? n_sets : n;
     const bool s_miller_done = s_miller_ev != nullptr || side_s_chain;
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     if (2 * n <= c->coop_max_items)     // few pairs: one WAVE per Miller loop (program miller1, ~0.9 ms) instead of one lane (6.6 ms)
@@ -2506,7 +2630,7 @@ static int npairing_finish(mbls_ctx* c, uint64_t n, hipStream_t s, uint8_t* d_re
         launch_miller_single(c, ws, n, s);
     if (side_s_chain) {
         HIPCHK(c, hipEventRecord(c->hs_ev2, s)); HIPCHK(c, hipStreamWaitEvent(c->hs_b, c->hs_ev2, 0));
-        g2_tree(c, ws, n, c->hs_b);
+        g2_tree(c, ws, ns, c->hs_b);
         if (!d_partial) coop_run(c, COOP_SMILLER, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, (uint64_t)1, (uint32_t*)nullptr, (uint8_t*)nullptr, COOP_RES_ITEM, c->hs_b);
         HIPCHK(c, hipEventRecord(c->hs_ev, c->hs_b));
         s_miller_ev = c->hs_ev;
@@ -2514,7 +2638,7 @@ static int npairing_finish(mbls_ctx* c, uint64_t n, hipStream_t s, uint8_t* d_re
     f12_tree(c, ws, n, s);
     // s_miller_done: the Miller value of (S, -G1) is left in slots 97..108 of item 0 by program smiller, running beside the chains
     if (s_miller_done) HIPCHK(c, hipStreamWaitEvent(s, s_miller_ev, 0));
-    if (late_status) hipLaunchKernelGGL(k_status_or, dim3(nblk(n)), dim3(WG), 0, s, c->d_status, n, c->d_scalar);
+    if (late_status) hipLaunchKernelGGL(k_status_or, dim3(nblk(ns)), dim3(WG), 0, s, c->d_status, ns, c->d_scalar);
     if (d_partial) hipLaunchKernelGGL(k_vm_export, dim3(1), dim3(WG), 0, s, ws, (const uint32_t*)c->d_scalar, 0, d_partial);
     else coop_run(c, s_miller_done ? COOP_VMFINAL : COOP_VMTAIL, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, (uint64_t)1, c->d_scalar, d_result, COOP_RES_BATCH, s);
     HIPCHK(c, hipGetLastError());
@@ -2660,10 +2784,32 @@ extern "C" int mbls_aggregate_verify_batch(mbls_ctx* c, const uint8_t* sigs, con
     if (status) HIPCHK(c, dst.down(status, 4 * n));
     return MBLS_OK;
 }
+// the message list of mbls_verify_multiple*_shared_msgs: d_msgs / msg_len / d_moff then describe the n_msgs LISTED messages, set i's is message d_midx[i]
+struct vm_shared {
+    uint64_t n_msgs = 0; const uint32_t* d_midx = nullptr;
+    uint64_t longest = 0;              // the longest group where the host has counted it (host entries); 0: a device-side index table
+    mbls_shared_msgs_plan sp;          // the list hash (plan_shared)
+    mbls_vm_shared_msgs_plan vp;       // the route (plan_vm_shared)
+};
+// the message phase of the shared-message entries on stream s_msg: the list is hashed once into the context's table (the existing path of section 5d); the
+// per-set route then gives every set its point (k_h_gather), the grouped route reads the table from its Miller items (k_vms_heads)
+static int vm_shared_message_phase(mbls_ctx* c, mbls_ws ws, const vm_shared& sh, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n, hipStream_t s_msg) {
+    const int rc = shared_hash_list(c, sh.sp, d_msgs, msg_len, d_moff, sh.n_msgs, s_msg); if (rc) return rc;
+    if (sh.vp.route == MBLS_VM_ROUTE_PER_SET)
+        hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, (const uint32_t*)c->d_htab, c->htab_cap,
+                           (const uint32_t*)c->d_hflag, sh.d_midx, sh.n_msgs, c->d_status, n);
+    return MBLS_OK;
+}
+static int vm_shared_plan_and_reserve(mbls_ctx* c, vm_shared& sh, uint64_t n) {
+    plan_shared(ctx_limits(c), n, sh.n_msgs, false, false, &sh.sp);
+    plan_vm_shared(ctx_limits(c), n, sh.n_msgs, c->vm_grouping, sh.longest, &sh.vp);
+    int rc = mbls_ctx_reserve(c, sh.vp.workspace_items); if (rc) return rc;
+    return reserve_msgs(c, sh.n_msgs);
+}
 static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_pks, int pk_format,
         const uint32_t* d_pk_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n,
         uint8_t* d_result, uint32_t* d_status_or, void* stream, uint32_t* d_partial = nullptr, const mbls_keytable* tab = nullptr, const uint32_t* d_idx = nullptr,
-        bool sigs_resident = false, bool hash_enqueued = false) {
+        bool sigs_resident = false, bool hash_enqueued = false, vm_shared* sh = nullptr) {
     // sigs_resident: k_sig (decode + subgroup test) has run over these signatures on this workspace and the host has seen every one pass: d_sigs is not read.
     // hash_enqueued (batches whose chains run side by side only): the message phase is already on the context's message stream.
     if (!c || (!d_result && !d_partial)) return MBLS_ERR_ARGUMENT;
@@ -2682,10 +2828,13 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
         return MBLS_OK;
     }
     if (!d_rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
-    if ((!d_sigs && !sigs_resident) || (!d_msgs && msg_len && !d_moff)) ARGFAIL(c, "null buffer");
+    if ((!d_sigs && !sigs_resident) || (!d_msgs && msg_len && !d_moff && !(sh && !sh->n_msgs))) ARGFAIL(c, "null buffer");
     // batches of at most half a round: two lanes per message in the message phase (items [0, 2 n), slots no other chain touches)
-    const bool pair_hash = n <= c->split_max_items && 2 * n <= c->round_items;
-    int rc = mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
+    const bool pair_hash = !sh && n <= c->split_max_items && 2 * n <= c->round_items;
+    // a shared list: the workspace (sets, Miller items, positions, the list's own hash) and the table are reserved here, once, before the first kernel
+    int rc = sh ? vm_shared_plan_and_reserve(c, *sh, n) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
+    const bool grouped = sh && sh->vp.route == MBLS_VM_ROUTE_GROUPED;
+    const uint64_t n_miller = grouped ? sh->vp.miller_items : n;
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     rc = ws_acquire(c, s); if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_scalar, 0, 64, s));
@@ -2702,13 +2851,32 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
     // side by side, the message phase is the chain the sets' Miller loops wait for: it is ENQUEUED first (behind the ~20 launches of the signature chain's sum tree
     // it started 0.26 ms late: 2^14 sets 9.47 -> 9.2 ms)
     const bool hash_first = fork && !hash_enqueued;
-    if (hash_first) launch_hash(c, ws, d_msgs, msg_len, d_moff, c->d_status, n, s_msg, pair_hash);
+    auto message_phase = [&]() -> int {
+        if (sh) return vm_shared_message_phase(c, ws, *sh, d_msgs, msg_len, d_moff, n, s_msg);
+        launch_hash(c, ws, d_msgs, msg_len, d_moff, c->d_status, n, s_msg, pair_hash); return MBLS_OK;
+    };
+    if (hash_first) { rc = message_phase(); if (rc) return rc; }
     if (tab) {      // sets given by indices into a resident key table: the indexed key sum (the keys were decoded and validated once)
         rc = table_acquire(c, tab, s); if (rc) return rc;
         hipLaunchKernelGGL(k_aggregate_indexed_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)tab->d_recs, tab->size, d_idx, d_pk_offsets, k, MBLS_MODE_VERIFY, c->d_status, n);
     } else if (!d_apks)    // sets given by their wire-format keys: AggregatePublicKey::aggregate on the device first (src/aggregates.rs:29-39)
         launch_aggregate(ws, d_pks, d_pk_offsets, k, pk_format, MBLS_MODE_VERIFY, c->d_status, n, s);
     hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, tab ? (const uint8_t*)nullptr : d_apks, d_rands, c->d_status, n);
+    // one Miller loop per message: count, scan, scatter and the per-message sums of the blinded keys follow the keys on their stream (beside the list's hash and
+    // the signature chain where the chains run side by side); the heads wait for the table further down
+    const uint64_t pbase = grouped ? vms_position_base(n, sh->n_msgs) : 0;
+    uint32_t* const g_cnt = c->d_hgrp; uint32_t* const g_cur = c->d_hgrp + c->htab_cap; uint32_t* const g_off = c->d_hgrp + 2 * c->htab_cap;
+    if (grouped) {
+        const uint64_t M = sh->n_msgs;
+        HIPCHK(c, hipMemsetAsync(g_cnt, 0, 4 * (M + 1), s)); HIPCHK(c, hipMemsetAsync(g_cur, 0, 4 * (M + 1), s)); HIPCHK(c, hipMemsetAsync(c->d_vmap, 0xFF, 4 * n, s));
+        hipLaunchKernelGGL(k_vms_count, dim3(nblk(n)), dim3(WG), 0, s, sh->d_midx, M, n, g_cnt, c->d_status);
+        hipLaunchKernelGGL(k_vms_scan, dim3(1), dim3(MBLS_VMS_SCAN_LANES), 0, s, (const uint32_t*)g_cnt, M, g_off);
+        hipLaunchKernelGGL(k_vms_scatter, dim3(nblk(n)), dim3(WG), 0, s, ws, sh->d_midx, M, n, (const uint32_t*)g_off, g_cur, c->d_vmap, pbase);
+        mbls_ws wp = ws; wp.w += pbase;
+        uint64_t half = 1;
+        for (uint32_t l = 0; l < sh->vp.tree_levels; l++, half *= 2)
+            hipLaunchKernelGGL(k_g1_seg_tree_d, dim3(nblk(n)), dim3(WG), 0, s, wp, (const uint32_t*)c->d_vmap, (const uint32_t*)g_off, M, n, half);
+    }
     // small batches (their Miller loops run one WAVE per pair, see npairing_finish): the signature chain is what the call waits for -- two lanes per signature
     if (2 * n <= c->coop_max_items)
         hipLaunchKernelGGL(k_blind_sig2_d, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, c->d_status, n);
@@ -2722,15 +2890,18 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
             coop_run(c, COOP_SMILLER, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, (uint64_t)1, (uint32_t*)nullptr, (uint8_t*)nullptr, COOP_RES_ITEM, s_sig);
         HIPCHK(c, hipEventRecord(c->hs_ev, s_sig));                  // ... and its Miller value (awaited just before the tail)
     }
-    if (!(hash_enqueued && fork) && !hash_first) launch_hash(c, ws, d_msgs, msg_len, d_moff, c->d_status, n, s_msg, pair_hash);
+    if (!(hash_enqueued && fork) && !hash_first) { rc = message_phase(); if (rc) return rc; }
     if (fork) {      // the sets' Miller loops need the keys (this stream) and the messages; the signature chain is awaited before the tail (hs_ev)
         HIPCHK(c, hipEventRecord(c->hs_ev3, s_msg));
         HIPCHK(c, hipStreamWaitEvent(s, c->hs_ev3, 0));
     } else
         hipLaunchKernelGGL(k_status_or, dim3(nblk(n)), dim3(WG), 0, s, c->d_status, n, c->d_scalar);
+    if (grouped)     // the table is complete: every Miller item gets its message's point and its group's key (a bad listed range some set names: the status word)
+        hipLaunchKernelGGL(k_vms_heads, dim3((unsigned)((n_miller + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s, ws, (const uint32_t*)c->d_htab, c->htab_cap,
+                           (const uint32_t*)c->d_hflag, (const uint32_t*)g_off, (const uint32_t*)g_cnt, sh->n_msgs, n_miller, pbase, c->d_scalar);
     // a set whose signature is outside G2 (reference src/aggregates.rs:274-276), an undecodable member or a zero scalar makes the tail
     // answer false: the status bits are folded in on the device, the call only enqueues
-    rc = npairing_finish(c, n, s, d_result, fork ? c->hs_ev : nullptr, fork, d_partial, side_s_chain); if (rc) return rc;
+    rc = npairing_finish(c, n_miller, s, d_result, fork ? c->hs_ev : nullptr, fork, d_partial, side_s_chain, n); if (rc) return rc;
     if (d_status_or) HIPCHK(c, hipMemcpyAsync(d_status_or, c->d_scalar, 4, hipMemcpyDeviceToDevice, s));
     return ws_release(c, s);
 }
@@ -2831,25 +3002,28 @@ extern "C" int mbls_verify_multiple_aggregate_signatures(mbls_ctx* c, const uint
 // tests its signatures (they stay in the workspace), starts the message phase and reads the verdicts back; phase 2 takes the scalars and runs the rest -- up to the
 // bool (d_partial == nullptr) or up to the shard's record. The caller holds the context's lock across both.
 struct vm_rng_stage {
-    sbuf ds, da, dm, dr, dmo, dout;
+    sbuf ds, da, dm, dr, dmo, dout, dmi;
     const uint8_t* d_msgs = nullptr; const uint64_t* d_moff = nullptr;
-    vm_rng_stage(mbls_ctx* c) : ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dmo(c, 6), dout(c, 4) {}
+    vm_rng_stage(mbls_ctx* c) : ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dmo(c, 6), dout(c, 4), dmi(c, 7) {}
 };
 static void vm_rng_drain(mbls_ctx* c) { (void)hipStreamSynchronize(c->hs_a); (void)hipStreamSynchronize(c->hs_b); (void)hipStreamSynchronize(c->hs_c); c->ws_pending = false; }
 // sigs96 / apks96: the shard's own sets; msgs: the buffer the (absolute) offsets of moff[0 .. n] point into, or n x msg_len bytes. -> MBLS_OK and st[0 .. n) (status words)
+// sh (the shared-message form): msgs / moff describe the sh->n_msgs LISTED messages, msg_idx the sets' indices (uploaded here; sh->d_midx is set)
 static int vm_rng_phase1(mbls_ctx* c, vm_rng_stage& g, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, size_t n,
-                         size_t out_bytes, uint32_t* st) {
+                         size_t out_bytes, uint32_t* st, vm_shared* sh = nullptr, const uint32_t* msg_idx = nullptr) {
     if (hipSetDevice(c->device) != hipSuccess) return MBLS_ERR_DEVICE;
     if (g.dout.alloc(out_bytes) != hipSuccess) return MBLS_ERR_DEVICE;
     if (n == 0) return MBLS_OK;
+    const size_t nm = sh ? (size_t)sh->n_msgs : n;                          // messages the buffers describe
     const uint64_t msg_first = moff ? moff[0] : 0;
-    const size_t msg_total = moff ? (size_t)(moff[n] - moff[0]) : (size_t)msg_len * n;
+    const size_t msg_total = moff ? (size_t)(moff[nm] - moff[0]) : (size_t)msg_len * nm;
     if (g.ds.up(sigs96, 96 * n) != hipSuccess || g.da.up(apks96, 96 * n) != hipSuccess || g.dm.up(msgs ? msgs + msg_first : nullptr, msg_total) != hipSuccess ||
-        g.dr.alloc(8 * n) != hipSuccess || (moff && g.dmo.up(moff, 8 * (n + 1)) != hipSuccess)) return MBLS_ERR_DEVICE;
+        g.dr.alloc(8 * n) != hipSuccess || (moff && g.dmo.up(moff, 8 * (nm + 1)) != hipSuccess)) return MBLS_ERR_DEVICE;
     g.d_msgs = g.dm.as<uint8_t>() - msg_first; g.d_moff = moff ? g.dmo.as<uint64_t>() : nullptr;
+    if (sh) { if (g.dmi.up(msg_idx, 4 * n) != hipSuccess) return MBLS_ERR_DEVICE; sh->d_midx = g.dmi.as<uint32_t>(); }
     hipStream_t s = c->hs_a;
-    const bool pair_hash = n <= c->split_max_items && 2 * n <= c->round_items, fork = 2 * n <= c->round_items;       // as verify_multiple_impl decides
-    int rc = mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
+    const bool pair_hash = !sh && n <= c->split_max_items && 2 * n <= c->round_items, fork = 2 * n <= c->round_items;       // as verify_multiple_impl decides
+    int rc = sh ? vm_shared_plan_and_reserve(c, *sh, n) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     rc = ws_acquire(c, s); if (rc) return rc;
     hipStream_t s_sig = fork ? c->hs_b : s;
@@ -2857,16 +3031,17 @@ static int vm_rng_phase1(mbls_ctx* c, vm_rng_stage& g, const uint8_t* sigs96, co
     if (fork) { (void)hipEventRecord(c->hs_ev, s); (void)hipStreamWaitEvent(c->hs_b, c->hs_ev, 0); (void)hipStreamWaitEvent(c->hs_c, c->hs_ev, 0); }
     if (2 * n <= c->coop_max_items) hipLaunchKernelGGL(k_sig2, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, (const uint8_t*)g.ds.as<uint8_t>(), c->d_status, (uint64_t)n);
     else hipLaunchKernelGGL(k_sig, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, (const uint8_t*)g.ds.as<uint8_t>(), c->d_status, (uint64_t)n, 1);
-    if (fork) launch_hash(c, ws, g.d_msgs, msg_len, g.d_moff, c->d_status, n, c->hs_c, pair_hash);       // the message phase does not wait for the host
+    if (fork && sh) { rc = vm_shared_message_phase(c, ws, *sh, g.d_msgs, msg_len, g.d_moff, n, c->hs_c); if (rc) { vm_rng_drain(c); return rc; } }
+    else if (fork) launch_hash(c, ws, g.d_msgs, msg_len, g.d_moff, c->d_status, n, c->hs_c, pair_hash);       // the message phase does not wait for the host
     if (hipStreamSynchronize(s_sig) != hipSuccess || hipMemcpy(st, c->d_status, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
     return MBLS_OK;
 }
 // rands[0 .. n): the shard's scalars. d_partial == false: the bool is left in g.dout (1 byte); true: the shard's record (MBLS_VM_PARTIAL_BYTES). Enqueues on hs_a.
-static int vm_rng_phase2(mbls_ctx* c, vm_rng_stage& g, uint32_t msg_len, const uint64_t* rands, size_t n, bool partial) {
+static int vm_rng_phase2(mbls_ctx* c, vm_rng_stage& g, uint32_t msg_len, const uint64_t* rands, size_t n, bool partial, vm_shared* sh = nullptr) {
     if (hipSetDevice(c->device) != hipSuccess) return MBLS_ERR_DEVICE;
     if (n && g.dr.up(rands, 8 * n) != hipSuccess) return MBLS_ERR_DEVICE;
     return verify_multiple_impl(c, nullptr, g.da.as<uint8_t>(), nullptr, 0, nullptr, 0, g.d_msgs, msg_len, g.d_moff, g.dr.as<uint64_t>(), n, partial ? nullptr : g.dout.as<uint8_t>(),
-                                nullptr, c->hs_a, partial ? g.dout.as<uint32_t>() : nullptr, nullptr, nullptr, true, true);
+                                nullptr, c->hs_a, partial ? g.dout.as<uint32_t>() : nullptr, nullptr, nullptr, true, true, sh);
 }
 extern "C" int mbls_verify_multiple_aggregate_signatures_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs,
         uint32_t msg_len, const uint64_t* moff, size_t n, mbls_scalar_source draw, void* user) {
@@ -2894,6 +3069,104 @@ extern "C" int mbls_verify_multiple_aggregate_signatures_rng(mbls_ctx* c, const 
     c->ws_pending = false;
     if (g.dout.down(&r, 1) != hipSuccess) return 0;
     return r;
+}
+
+// ---- verify_multiple over a shared message list (include/mbls.h, mbls_verify_multiple*_shared_msgs): the entries above with the sets' messages named by index in
+// a list that is hashed once. Grouped route: one Miller loop per message (the kernels of the k_vms_* family, mbls_vms.h); per-set route: every set gathers its point.
+static int vm_shared_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint8_t* d_apks, const uint32_t* d_key_idx, const uint32_t* d_offsets, uint32_t k,
+                            const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n,
+                            uint8_t* d_result, uint32_t* d_status_or, void* stream, uint64_t longest) {
+    if (!c || !d_result) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (n && !(t ? (const void*)d_key_idx : (const void*)d_apks)) ARGFAIL(c, "null key buffer");
+    if (t && t->c != c) ARGFAIL(c, "key table belongs to another context");
+    if (n && !d_midx) ARGFAIL(c, "null buffer");
+    if (n_msgs > 0xFFFFFFFFull || n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
+    vm_shared sh; sh.n_msgs = n_msgs; sh.d_midx = d_midx; sh.longest = longest;
+    return verify_multiple_impl(c, d_sigs, t ? nullptr : d_apks, nullptr, MBLS_PK_UNCOMPRESSED, t ? d_offsets : nullptr, t ? k : 0, d_msgs, msg_len, d_moff, d_rands, n, d_result,
+                                d_status_or, stream, nullptr, t, t ? d_key_idx : nullptr, false, false, &sh);
+}
+extern "C" int mbls_verify_multiple_shared_msgs_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff,
+        uint64_t n_msgs, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream) {
+    return vm_shared_device(c, nullptr, d_sigs, d_apks, nullptr, nullptr, 0, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, d_rands, n, d_result, d_status, stream, 0);
+}
+extern "C" int mbls_verify_multiple_sets_indexed_shared_msgs_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx, const uint32_t* d_offsets,
+        uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n,
+        uint8_t* d_result, uint32_t* d_status, void* stream) {
+    if (!t) return MBLS_ERR_ARGUMENT;
+    return vm_shared_device(c, t, d_sigs, nullptr, d_key_idx, d_offsets, k, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, d_rands, n, d_result, d_status, stream, 0);
+}
+// the host entries' checks (nothing is queued when they fail; the outputs stay untouched): the list's offset table, every index inside the list. -> the longest group
+static int vm_shared_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n_msgs,
+                                const uint32_t* msg_idx, uint64_t n, uint64_t* longest) {
+    if (n_msgs > 0xFFFFFFFFull || n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
+    if (!sigs96 || !apks96 || !msg_idx) ARGFAIL(c, "null buffer");
+    if (moff && !msg_offsets_ok(moff, n_msgs)) ARGFAIL(c, "msg_offsets must be non-decreasing, messages below 2^32 bytes");
+    const size_t msg_total = moff ? (size_t)(moff[n_msgs] - moff[0]) : (size_t)msg_len * n_msgs;
+    if (!msgs && msg_total) ARGFAIL(c, "null buffer");
+    std::vector<uint32_t> cnt;
+    try { cnt.assign(n_msgs, 0); } catch (...) { ARGFAIL(c, "out of host memory"); }
+    uint64_t m = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (msg_idx[i] >= n_msgs) ARGFAIL(c, "msg_idx names no message of the list");
+        if (++cnt[msg_idx[i]] > m) m = cnt[msg_idx[i]];
+    }
+    *longest = m;
+    return MBLS_OK;
+}
+extern "C" int mbls_verify_multiple_shared_msgs(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        uint64_t n_msgs, const uint32_t* msg_idx, const uint64_t* rands, uint64_t n, uint8_t* result, uint32_t* status) {
+    if (!c || !result) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (n == 0) { *result = 1; if (status) *status = 0; return MBLS_OK; }
+    if (!rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
+    uint64_t longest = 0;
+    int rc = vm_shared_host_check(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, n, &longest); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t msg_first = moff ? moff[0] : 0;
+    const size_t msg_total = moff ? (size_t)(moff[n_msgs] - moff[0]) : (size_t)msg_len * n_msgs;
+    sbuf ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dmo(c, 6), dres(c, 4), dmi(c, 7);
+    HIPCHK(c, ds.up(sigs96, 96 * n)); HIPCHK(c, da.up(apks96, 96 * n)); HIPCHK(c, dm.up(msgs ? msgs + msg_first : nullptr, msg_total)); HIPCHK(c, dr.up(rands, 8 * n));
+    HIPCHK(c, dmi.up(msg_idx, 4 * n)); HIPCHK(c, dres.alloc(8));
+    if (moff) HIPCHK(c, dmo.up(moff, 8 * (n_msgs + 1)));
+    rc = vm_shared_device(c, nullptr, ds.as<uint8_t>(), da.as<uint8_t>(), nullptr, nullptr, 0, dm.as<uint8_t>() - msg_first, msg_len, moff ? dmo.as<uint64_t>() : nullptr, n_msgs,
+                          dmi.as<uint32_t>(), dr.as<uint64_t>(), n, dres.as<uint8_t>(), dres.as<uint32_t>() + 1, c->hs_a, longest);
+    if (rc) { vm_rng_drain(c); return rc; }
+    HIPCHK(c, hipStreamSynchronize(c->hs_a));
+    c->ws_pending = false;
+    uint32_t out[2] = {0, 0};
+    HIPCHK(c, dres.down(out, 8));
+    *result = (uint8_t)(out[0] & 0xFF); if (status) *status = out[1];
+    return MBLS_OK;
+}
+// the reference's order, as mbls_verify_multiple_aggregate_signatures_rng keeps it (vm_rng_phase1 / vm_rng_phase2 with the list): signatures decoded and tested
+// first, `draw` called once for the sets in front of the first bad signature, no second subgroup test
+extern "C" int mbls_verify_multiple_shared_msgs_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user) {
+    if (!c || !result) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (n == 0) { *result = 1; return MBLS_OK; }                            // empty iterator: true, the generator untouched
+    if (!draw) ARGFAIL(c, "no scalar source");
+    vm_shared sh; sh.n_msgs = n_msgs;
+    int rc = vm_shared_host_check(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, n, &sh.longest); if (rc) return rc;
+    std::vector<uint64_t> rands; std::vector<uint32_t> st;
+    try { rands.resize(n); st.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
+    vm_rng_stage g(c);
+    rc = vm_rng_phase1(c, g, sigs96, apks96, msgs, msg_len, moff, n, 8, st.data(), &sh, msg_idx); if (rc) return rc;
+    size_t reached = n;                                                     // the sets the reference's loop draws a scalar for
+    for (size_t i = 0; i < n; i++)
+        if (st[i] & (MBLS_ST_BAD_SIG_ENCODING | MBLS_ST_SIG_NOT_IN_G2)) { reached = i; break; }
+    if (reached) draw(user, rands.data(), (uint64_t)reached);
+    if (reached < n) { vm_rng_drain(c); *result = 0; return MBLS_OK; }     // src/aggregates.rs:273-275
+    rc = vm_rng_phase2(c, g, msg_len, rands.data(), n, false, &sh);
+    std::fill(rands.begin(), rands.end(), 0);
+    if (rc) { vm_rng_drain(c); return rc; }
+    if (hipStreamSynchronize(c->hs_a) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
+    c->ws_pending = false;
+    uint8_t r = 0;
+    HIPCHK(c, g.dout.down(&r, 1));
+    *result = r;
+    return MBLS_OK;
 }
 
 // ---- B independent verify_multiple batches in ONE call (include/mbls.h, mbls_verify_multiple_batches*): what B consecutive calls of the entries above return,

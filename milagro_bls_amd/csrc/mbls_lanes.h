@@ -258,6 +258,17 @@ MBLS_FN void g1_blind_d_call(const mbls_ws& ws, uint64_t i, uint32_t lane, uint6
     asm volatile(MBLS_ASM_CALL("mbls_g1_blind_d_asm_fn") : "+{v248}"(rlo), "+{v249}"(rhi) : "{v252}"(addr), "{s68}"(gb_lo), "{s69}"(gb_hi), "{s70}"(st4)
                  : MBLS_G1_BLIND_D_ASM_CLOBBERS);
 }
+// One level of the per-message key sums of the shared-message verify_multiple (tools/gen_tower_d.py g1_tree_routine): the Jacobian G1 point in slots 0..2 of
+// item i plus the one of the item `half` further on, back into slots 0..2 of item i (canonical). No LDS: addressing as g1_blind_d_call.
+extern "C" __device__ __attribute__((noinline, used, aligned(64))) void mbls_g1_tree_d_asm_fn() { asm volatile(MBLS_G1_TREE_D_ASM); }
+MBLS_FN void g1_tree_d_call(const mbls_ws& ws, uint64_t i, uint64_t half, uint32_t lane) {
+    const uint32_t addr = 4u * lane;
+    const uint64_t gb = (uint64_t)(uintptr_t)ws.w + 4ull * (i - lane);
+    const uint32_t gb_lo = __builtin_amdgcn_readfirstlane((uint32_t)gb), gb_hi = __builtin_amdgcn_readfirstlane((uint32_t)(gb >> 32));
+    const uint32_t st4 = __builtin_amdgcn_readfirstlane((uint32_t)(ws.stride * 4));
+    const uint32_t poff = __builtin_amdgcn_readfirstlane((uint32_t)(half * 4));          // the partner's byte offset (half < 2^30 items)
+    asm volatile(MBLS_ASM_CALL("mbls_g1_tree_d_asm_fn") : : "{v252}"(addr), "{s68}"(gb_lo), "{s69}"(gb_hi), "{s70}"(st4), "{s71}"(poff) : MBLS_G2_TREE_D_ASM_CLOBBERS);
+}
 // verify_multiple's signature phase (reference src/aggregates.rs:274-276, :303) as one generated routine (tools/gen_tower_d.py g2_blind_routine): the
 // subgroup test of the signature in slots 3..6, then [r] sig by signed 4-bit windows into slots 25..30. Returns bit 0 = psi(P) = [x]P.
 extern "C" __device__ __attribute__((noinline, used, aligned(64))) void mbls_g2_blind_d_asm_fn() { asm volatile(MBLS_G2_BLIND_D_ASM); }

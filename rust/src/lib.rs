@@ -71,6 +71,8 @@ extern "C" {
     fn mbls_verify_multiple_aggregate_signatures_rng(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
                                                      n: usize, draw: MblsScalarSource, user: *mut c_void) -> c_int;
     fn mbls_sig_check_batch(ctx: *mut MblsCtx, in96: *const u8, n: u64, errs: *mut u8, in_g2: *mut u8) -> c_int;
+    fn mbls_verify_multiple_shared_msgs_rng(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
+                                            n_msgs: u64, msg_idx: *const u32, n: u64, result: *mut u8, draw: MblsScalarSource, user: *mut c_void) -> c_int;
     fn mbls_verify_multiple_batches(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
                                     rands: *const u64, n_sets: u64, batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64, results: *mut u8,
                                     status: *mut u32) -> c_int;
@@ -572,6 +574,46 @@ impl AggregateSignature {
             std::panic::resume_unwind(payload);
         }
         ok
+    }
+    /// Not in the reference: `verify_multiple_aggregate_signatures(rng, signature_sets)` -- same sets, same bool, `rng` left in the same state --
+    /// for batches whose sets share messages (`mbls_verify_multiple_shared_msgs_rng`): the messages are deduplicated here by their bytes, each
+    /// distinct message is hashed once and, where it pays, the check walks one Miller loop per message instead of one per set.
+    /// (Like the rest of this crate: source only, never compiled.)
+    pub fn verify_multiple_aggregate_signatures_shared_msgs<'a, R, I>(rng: &mut R, signature_sets: I) -> bool
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, &'a AggregatePublicKey, &'a [u8])>,
+    {
+        let sets: Vec<(&AggregateSignature, &AggregatePublicKey, &[u8])> = signature_sets.collect();
+        let n = sets.len();
+        if n == 0 {
+            return true;
+        }
+        let (mut sigs, mut apks, mut msgs) = (Vec::new(), Vec::new(), Vec::new());
+        let mut moff: Vec<u64> = vec![0];
+        let mut idx: Vec<u32> = Vec::with_capacity(n);
+        let mut index: std::collections::HashMap<&[u8], u32> = std::collections::HashMap::new();
+        for (s, a, m) in &sets {
+            sigs.extend_from_slice(&s.point);
+            apks.extend_from_slice(&a.point);
+            let next = index.len() as u32;
+            let j = *index.entry(*m).or_insert_with(|| {
+                msgs.extend_from_slice(m);
+                moff.push(msgs.len() as u64);
+                next
+            });
+            idx.push(j);
+        }
+        let mut st = DrawState { rng, panic: None };
+        let mut ok: u8 = 0;
+        let rc = unsafe {
+            mbls_verify_multiple_shared_msgs_rng(ctx(), sigs.as_ptr(), apks.as_ptr(), msgs.as_ptr(), 0, moff.as_ptr(), index.len() as u64, idx.as_ptr(), n as u64,
+                                                 &mut ok, draw_scalars::<R>, &mut st as *mut DrawState<R> as *mut c_void)
+        };
+        if let Some(payload) = st.panic.take() {
+            std::panic::resume_unwind(payload);
+        }
+        rc == 0 && ok == 1
     }
     /// Not in the reference: what `verify_multiple_aggregate_signatures(rng, batch)` returns for every batch, called once per batch in order --
     /// as ONE call on the GPU (`mbls_verify_multiple_batches_rng`), for about the cost of one such call. One bool per batch; a bad batch rejects

@@ -3194,6 +3194,13 @@ def prog_g1b_glue(which):
     elif which == "inf":
         for i, c in enumerate((0, ONE_D, 0)):
             p.store(prog_reduce(p, p.const(c)), ("a", i))
+    elif which == "tstart":                          # acc = the lane's own point (slots 0..2), record 0 of the table slots <- the partner's, s71 bytes further on
+        own = [prog_reduce(p, p.live_in(("g", i))) for i in range(3)]
+        oth = [prog_reduce(p, p.live_in(("gka", i))) for i in range(3)]
+        for i, v in enumerate(oth):
+            p.ops.append(("storep", [], [v], G1B_TAB + i))
+        for i, v in enumerate(own):
+            p.store(v, ("a", i))
     else:
         raise ValueError(which)
     return p
@@ -3257,6 +3264,35 @@ def g1_blind_routine():
     ret = ["s_setpc_b64 s[30:31]"]
     pieces = dict(B, pro=pro, epi=epi, rprime=BLIND_RPRIME, top=BLIND_TOP, digit=BLIND_DIGIT)
     return pro + main + expand_calls_d(epi) + ret + dbl4 + subs, pieces, st
+
+
+def g1_tree_routine():
+    """slots 0..2 of this lane's item (a Jacobian G1 point, 2^384 domain) <- that point + the same slots of the item s71 bytes further on: one level of the
+    per-message sums of the blinded keys (k_g1_seg_tree_d), the twin of g2_tree_routine. The addition is g1_blind_routine's -- prog_g1_jadd with either operand,
+    or both, at infinity and opposite operands settled by selection, equal operands by the doubling fix-up under the lanes' mask -- on ANY two points of E(Fp):
+    keys outside G1 included. Slots 109..111 (the first table record of g1_blind_routine) are scratch. No LDS, no lane-private memory; v252 / s[68:69] / s70
+    as in g1_blind_routine."""
+    B, st = {}, {}
+    for nm in ["tstart", "add", "fix"]:
+        B[nm], st[nm] = build_g1b(nm)
+    X = lambda nm: expand_calls_d(B[nm])
+    pro = ["s_mov_b64 s[80:81], s[30:31]", "s_waitcnt vmcnt(0)"] + shell_constants() + ["s_mov_b64 %s, exec" % EXEC_ALL]
+    main = X("tstart") + ["s_waitcnt vmcnt(0)"] + X("add")
+    main += ["s_and_b64 s[92:93], %s, %s" % (M_H0, M_R0), "s_andn2_b64 s[92:93], s[92:93], %s" % M_INF1, "s_andn2_b64 s[92:93], s[92:93], %s" % M_INF2,
+             "s_and_b64 s[92:93], s[92:93], exec", "s_cbranch_scc1 3f"] + far_fwd(6) + ["3:", "s_mov_b64 exec, s[92:93]"] + X("fix") + ["6:", "s_mov_b64 exec, %s" % EXEC_ALL]
+    epi = ["s_waitcnt vmcnt(0)"]
+    B0, B1, B2, B5, B6 = (lambda j: "v%d" % j), (lambda j: "v%d" % (14 + j)), (lambda j: "v%d" % (28 + j)), (lambda j: "v%d" % (70 + j)), (lambda j: "v%d" % (84 + j))
+    epi += ["v_mov_b32_e32 %s, 0x%08x" % (B2(j), dgt) for j, dgt in enumerate(digits_of(K384))]
+    for half in range(2):
+        srcs = (0, 1) if half == 0 else (2, 2)
+        epi += ["v_accvgpr_read_b32 %s, a%d" % (B0(j), vb(srcs[0]) + j) for j in range(14)]
+        epi += ["v_accvgpr_read_b32 %s, a%d" % (B1(j), vb(srcs[1]) + j) for j in range(14)]
+        epi += ["CALL mbls_fp2_mulfp_d_asm_fn"]
+        for h, Bk in ((0, B5), (1, B6))[:2 if half == 0 else 1]:
+            k384_site("g1_tree_epilogue")         # input bound: |v| < 1.01 p
+            epi += seq_reduce(Bk) + seq_canonical(Bk) + seq_to32(Bk) + seq_gstore(Bk, 2 * half + h)
+    epi += ["s_waitcnt vmcnt(0)", "s_mov_b64 s[30:31], s[80:81]"]
+    return pro + main + expand_calls_d(epi), dict(B, pro=pro, epi=epi), st
 
 
 def g2_blind_routine(ct=False, two_lane=False):
@@ -3465,6 +3501,9 @@ def generate_text():
     print("g1 blind routine", len(full), "lines; addt", len(pieces["addt"]), st["addt"], "dbl", len(pieces["dbl"]))
     txt += "#define MBLS_G1_BLIND_D_ASM_CLOBBERS %s,%s, \\\n    %s\n" % (
         ",".join('"v%d"' % i for i in range(256) if i not in (248, 249, 252) and i not in UNTOUCHED_V), ",".join('"a%d"' % i for i in range(252)), sgb)
+    full, pieces, st = g1_tree_routine()
+    txt += emit("MBLS_G1_TREE_D_ASM", full) + "\n"
+    print("g1 tree routine", len(full), "lines; add", len(pieces["add"]), st["add"])
     sgt = sgm.replace('"vcc"', ",".join('"s%d"' % i for i in list(range(50, 54)) + [72] + list(range(79, 100))) + ',"vcc"')
     txt += "#define MBLS_G2_TREE_D_ASM_CLOBBERS %s,%s, \\\n    %s\n" % (
         ",".join('"v%d"' % i for i in range(256) if i != 252 and i not in UNTOUCHED_V), ",".join('"a%d"' % i for i in range(252)), sgt)
