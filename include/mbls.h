@@ -534,6 +534,54 @@ int mbls_verify_multiple_batches_rng(mbls_ctx* ctx, const uint8_t* sigs96, const
                                      uint64_t n_sets, const uint32_t* batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint8_t* results,
                                      mbls_scalar_source draw, void* user);
 
+/* WHICH SETS OF A REJECTED BATCH. A client that gets results[b] = 0 must know which sets to drop; a second call over the rejected batches' sets would hash the
+ * same messages, decode, subgroup-test and blind the same signatures and blind the same keys again, behind a second host round trip. The _locate entries answer
+ * per set in the SAME call: arguments, table validation, MBLS_ERR_ARGUMENT cases, n_batches = 0 and empty batches are those of the corresponding
+ * mbls_verify_multiple_batches* entry, plus d_set_results (n_sets bytes, REQUIRED: NULL is MBLS_ERR_ARGUMENT, nothing written) and d_set_status (n_sets words,
+ * optional). The *_device forms ONLY ENQUEUE -- no host synchronisation anywhere; in particular the number of sets to examine is never read back.
+ * CONTRACT.
+ *  1. d_results[b] / d_status[b] are byte for byte what mbls_verify_multiple_batches_device writes for the same inputs.
+ *  2. Every set of an ACCEPTED batch (d_results[b] = 1) gets d_set_results[i] = 1. A passing batch is NOT EXAMINED set by set: the batch check is the security
+ *     statement verify_multiple makes (reference src/aggregates.rs:261-316), and sets whose errors cancel in it exist only with the blinding's probability 2^-63 --
+ *     examining them would add cost to every call for no statement the function makes.
+ *  3. Every set of a REJECTED batch gets exactly what mbls_verify_multiple_batches_device returns for the one-set batch {i} with the scalar rands[i]: the reject
+ *     mask is verify_multiple's on the set's OWN word -- an undecodable signature, a signature outside G2, a bad key, a bad message range or a zero scalar give 0
+ *     without a pairing --, otherwise the set passes exactly when FE(ML([r_i] apk_i, H(m_i)) . ML(-G1, [r_i] sig_i)) = 1 (an infinite key with an infinite
+ *     signature: 1, as that entry gives).
+ *  4. d_set_status[i] = the set's own MBLS_ST_* bits as phase one found them (the one-set batch's status word), with MBLS_ST_PAIRING_FAILED added exactly where the
+ *     set was examined and its own pairing check is what rejects it.
+ *  5. DEVICE-SIDE batch table: a set that no sound batch owns -- its range runs backwards or ends beyond n_sets, shares a set with another range, or no range
+ *     covers the set -- gets 0 and MBLS_ST_BAD_PK_ENCODING (the bit the entries above use for table faults). Nothing is read outside the call's buffers, and the sets
+ *     of sound batches are not touched by their neighbours' faults.
+ *  6. The _rng form draws exactly as mbls_verify_multiple_batches_rng does. A set at or behind its batch's first signature outside G2 has no scalar (the reference
+ *     never draws one): 0, and the status the signature phase found. Only sets with a scalar can be examined.
+ * MECHANISM. Phase one is mbls_verify_multiple_batches_device's, with set i's blinded signature (as the pair ([r_i] sig_i, -G1)) and its Miller value f_i copied to
+ * a shadow item before the per-batch trees overwrite them. Behind the per-batch tail one lane per set answers every set that needs no pairing and flags the rest;
+ * the flagged sets walk one one-pair Miller loop, one product and one final exponentiation each, on the kernels' usual lane forms (lane pairs up to half a round,
+ * rounds above one). Waves without a flagged set return at once.
+ * WORKSPACE: 2 n_sets + 2 n_batches items (3 n_sets for calls of at most half a round whose message phase runs on lane pairs, if that is more): what
+ * mbls_plan_locate_workspace_items returns -- a pure function; mbls_ctx_reserve(ctx, that) beforehand keeps allocation out of the call. The entries reserve once,
+ * before the first kernel.
+ * NOT PROVIDED: a wave-engine form of phase two for very small calls, locate forms of the shared-message entries, of the mbls_multi handle and of the stream. */
+uint64_t mbls_plan_locate_workspace_items(const mbls_limits* limits, uint64_t n_sets, uint64_t n_batches);
+int mbls_verify_multiple_batches_locate_device(mbls_ctx* ctx, const uint8_t* d_sigs96, const uint8_t* d_apks96, const uint8_t* d_pks, int pk_format,
+                                               const uint32_t* d_pk_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_msg_offsets,
+                                               const uint64_t* d_rands, uint64_t n_sets, const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches,
+                                               uint8_t* d_results, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream);
+int mbls_verify_multiple_batches_locate_indexed_device(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* d_sigs96, const uint32_t* d_key_idx,
+                                                       const uint32_t* d_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_msg_offsets,
+                                                       const uint64_t* d_rands, uint64_t n_sets, const uint32_t* d_batch_offsets, uint32_t sets_per_batch,
+                                                       uint64_t n_batches, uint8_t* d_results, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status,
+                                                       void* stream);
+/* host buffers, aggregate keys; validation as mbls_verify_multiple_batches */
+int mbls_verify_multiple_batches_locate(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len,
+                                        const uint64_t* msg_offsets, const uint64_t* rands, uint64_t n_sets, const uint32_t* batch_offsets, uint32_t sets_per_batch,
+                                        uint64_t n_batches, uint8_t* results, uint32_t* status, uint8_t* set_results, uint32_t* set_status);
+/* the reference's draw order (contract item 6) */
+int mbls_verify_multiple_batches_locate_rng(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len,
+                                            const uint64_t* msg_offsets, uint64_t n_sets, const uint32_t* batch_offsets, uint32_t sets_per_batch, uint64_t n_batches,
+                                            uint8_t* results, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user);
+
 /* verify_multiple OVER A SHARED MESSAGE LIST: ONE MILLER LOOP PER MESSAGE. The sets come in the caller's order, each with one uint32 naming its message in a
  * list of the shape of the `_shared_msgs` entries above (msgs, msg_len or msg_offsets[n_msgs + 1], n_msgs, msg_idx[n]). Pairings are bilinear in the key argument
  * over all of E(Fp), so  prod_i e([r_i] apk_i, H(m_i)) = prod_j e(sum_{i: msg(i) = j} [r_i] apk_i, H(m_j)):  n sets over M distinct messages need M hashes and M

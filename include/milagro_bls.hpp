@@ -338,6 +338,46 @@ struct AggregateSignature {
         for (uint8_t r : res) out.push_back(r == 1);
         return out;
     }
+    // The same, and in the same call (mbls_verify_multiple_batches_locate_rng) WHICH sets of the rejected batches are the bad ones: .first as above, .second one bool
+    // per set of every batch. Every set of an accepted batch reads true -- a passing batch is not examined set by set: the batch check is the statement
+    // verify_multiple makes. A set of a rejected batch reads what the one-set batch with its scalar returns; a set at or behind the batch's first signature outside
+    // G2 has no scalar (the reference never draws one) and reads false. rng is left where verify_multiple_aggregate_signatures_batches leaves it.
+    template <typename Rng>
+    static std::pair<std::vector<bool>, std::vector<std::vector<bool>>> verify_multiple_aggregate_signatures_batches_locate(
+            Rng&& rng, const std::vector<std::vector<std::tuple<const AggregateSignature*, const AggregatePublicKey*, Bytes>>>& batches) {
+        std::pair<std::vector<bool>, std::vector<std::vector<bool>>> out;
+        if (batches.empty()) return out;
+        Bytes sigs, apks, msgs; std::vector<uint64_t> moff{0}; std::vector<uint32_t> boff{0};
+        for (auto& b : batches) {
+            for (auto& s : b) {
+                sigs.insert(sigs.end(), std::get<0>(s)->point.begin(), std::get<0>(s)->point.end());
+                apks.insert(apks.end(), std::get<1>(s)->point.begin(), std::get<1>(s)->point.end());
+                msgs.insert(msgs.end(), std::get<2>(s).begin(), std::get<2>(s).end());
+                moff.push_back(msgs.size());
+            }
+            boff.push_back(uint32_t(moff.size() - 1));
+        }
+        using R = typename std::remove_reference<Rng>::type;
+        struct src { R* rng; std::exception_ptr err; } u{&rng, nullptr};
+        mbls_scalar_source draw = [](void* user, uint64_t* o, uint64_t count) {
+            src* p = static_cast<src*>(user);
+            try { for (uint64_t i = 0; i < count; i++) o[i] = draw_scalar(*p->rng); }
+            catch (...) { p->err = std::current_exception(); for (uint64_t i = 0; i < count; i++) o[i] = 0; }        // never unwind through the C frames
+        };
+        const size_t n = moff.size() - 1;
+        Bytes res(batches.size(), 0), sres(n ? n : 1, 0);
+        const int rc = mbls_verify_multiple_batches_locate_rng(detail::ctx(), sigs.data(), apks.data(), msgs.data(), 0, moff.data(), n, boff.data(), 0,
+                                                               batches.size(), res.data(), sres.data(), nullptr, draw, &u);
+        if (u.err) std::rethrow_exception(u.err);
+        detail::check(rc);
+        for (size_t b = 0; b < batches.size(); b++) {
+            out.first.push_back(res[b] == 1);
+            std::vector<bool> per;
+            for (uint32_t i = boff[b]; i < boff[b + 1]; i++) per.push_back(sres[i] == 1);
+            out.second.push_back(per);
+        }
+        return out;
+    }
     // the same check with the sets cut into one shard per device of a multi-device handle (mbls_multi_create): same bool, same RNG order, ONE call
     // (mbls_multi_verify_multiple_aggregate_signatures_rng: every device tests its shard's signatures first, the scalars are asked for once)
     template <typename Rng>

@@ -74,6 +74,12 @@ def plan_workspace_items(n, k, split_layout=True, limits=None):
     return int(lib().mbls_plan_workspace_items(C.byref(L), n, k, 1 if split_layout else 0))
 
 
+def plan_locate_workspace_items(n_sets, n_batches, limits=None):
+    """workspace items a mbls_verify_multiple_batches_locate* call of n_sets sets in n_batches batches reserves (pure: no GPU)"""
+    L = limits if limits is not None else default_limits()
+    return int(lib().mbls_plan_locate_workspace_items(C.byref(L), n_sets, n_batches))
+
+
 class SharedMsgsPlan(C.Structure):
     """include/mbls.h mbls_shared_msgs_plan"""
     _fields_ = [("batch", BatchPlan), ("list_message", C.c_uint32), ("list_pieces", C.c_uint32), ("list_piece_items", C.c_uint64), ("list_workspace_items", C.c_uint64),
@@ -254,6 +260,13 @@ SIGNATURES = {
     "mbls_verify_multiple_batches_indexed_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp, vp]),
     "mbls_verify_multiple_batches": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp]),
     "mbls_verify_multiple_batches_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, SCALAR_SOURCE, vp]),
+    "mbls_plan_locate_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64]),
+    "mbls_verify_multiple_batches_locate_device": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp,
+                                                             vp, vp, vp]),
+    "mbls_verify_multiple_batches_locate_indexed_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp,
+                                                                     vp, vp, vp]),
+    "mbls_verify_multiple_batches_locate": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp]),
+    "mbls_verify_multiple_batches_locate_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp, vp, SCALAR_SOURCE, vp]),
     "mbls_multi_verify_multiple_aggregate_signatures": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_size_t]),
     "mbls_multi_verify_multiple_aggregate_signatures_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, SCALAR_SOURCE, vp]),
     "mbls_pk_decode_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp]),

@@ -380,9 +380,22 @@ class AggregateSignature:
         (signature, aggregate_public_key, message). Returns list[bool], one per batch; a bad batch rejects itself and nothing else. The scalars are drawn as
         above and in the order the per-batch calls would draw them (for every batch, the sets in front of its first signature outside G2), so `rng` is left
         exactly where those calls would leave it."""
+        return AggregateSignature._vm_batches(rng, batches, False)
+
+    @staticmethod
+    def verify_multiple_aggregate_signatures_batches_locate(rng, batches):
+        """verify_multiple_aggregate_signatures_batches, and in the same call (mbls_verify_multiple_batches_locate_rng) which sets of the rejected batches are the
+        bad ones. Returns (list[bool], list[list[bool]]): one bool per batch as above, and per batch one bool per set. Every set of an accepted batch reads
+        True -- a passing batch is not examined set by set: the batch check is the statement verify_multiple makes. A set of a rejected batch reads what the
+        one-set batch with its scalar returns; a set at or behind the batch's first signature outside G2 has no scalar (the reference never draws one) and
+        reads False. `rng` is left exactly where verify_multiple_aggregate_signatures_batches leaves it."""
+        return AggregateSignature._vm_batches(rng, batches, True)
+
+    @staticmethod
+    def _vm_batches(rng, batches, locate):
         batches = [list(b) for b in batches]
         if not batches:
-            return []
+            return ([], []) if locate else []
         sets = [s for b in batches for s in b]
         boffs = [0]
         for b in batches:
@@ -409,12 +422,22 @@ class AggregateSignature:
         res = N.outbuf(len(batches))
         cb = N.SCALAR_SOURCE(draw)
         ctx = _ctx()
-        rc = N.lib().mbls_verify_multiple_batches_rng(ctx.handle, N.cbuf(b"".join(s[0].point for s in sets)), N.cbuf(b"".join(s[1].point for s in sets)),
-                                                      N.cbuf(b"".join(bytes(s[2]) for s in sets)), 0, moff, len(sets), boff, 0, len(batches), res, cb, None)
+        S, A, M = N.cbuf(b"".join(s[0].point for s in sets)), N.cbuf(b"".join(s[1].point for s in sets)), N.cbuf(b"".join(bytes(s[2]) for s in sets))
+        if locate:
+            sres = N.outbuf(max(1, len(sets)))
+            if not sets:
+                C.memset(sres, 1, 1)
+            rc = N.lib().mbls_verify_multiple_batches_locate_rng(ctx.handle, S, A, M, 0, moff, len(sets), boff, 0, len(batches), res, sres, None, cb, None)
+        else:
+            rc = N.lib().mbls_verify_multiple_batches_rng(ctx.handle, S, A, M, 0, moff, len(sets), boff, 0, len(batches), res, cb, None)
         if failed:
             raise failed[0]
         ctx.check(rc)
-        return [bool(x) for x in bytes(res)[:len(batches)]]
+        out = [bool(x) for x in bytes(res)[:len(batches)]]
+        if not locate:
+            return out
+        per_set = [bool(x) for x in bytes(sres)[:len(sets)]]
+        return out, [per_set[boffs[b]:boffs[b + 1]] for b in range(len(batches))]
 
     @classmethod
     def from_bytes(cls, data):

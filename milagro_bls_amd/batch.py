@@ -391,6 +391,43 @@ def verify_multiple_batches_indexed_device(table, d_sigs, d_key_idx, d_msgs, d_r
                                                                   n_sets, d_batch_offsets, sets_per_batch, n_batches, d_results, d_status, stream))
 
 
+# ---- which sets of a rejected batch (include/mbls.h, mbls_verify_multiple_batches_locate*)
+def verify_multiple_batches_locate(sigs, apks, msgs, rands, n_sets, n_batches, batch_offsets=None, sets_per_batch=0, msg_len=32, msg_offsets=None, ctx=None):
+    """verify_multiple_batches, and in the same call one answer per SET (mbls_verify_multiple_batches_locate): every set of an accepted batch reads True (a passing
+    batch is not examined), every set of a rejected batch reads what the one-set batch with its scalar returns. Returns (results, status, set_results,
+    set_status): the first two per batch as verify_multiple_batches returns them, the last two per set."""
+    ctx = ctx or _c()
+    res = N.outbuf(max(1, n_batches))
+    st = (C.c_uint32 * max(1, n_batches))()
+    sres = N.outbuf(max(1, n_sets))
+    sst = (C.c_uint32 * max(1, n_sets))()
+    r = None if rands is None else (C.c_uint64 * max(1, n_sets))(*rands)
+    ctx.check(N.lib().mbls_verify_multiple_batches_locate(ctx.handle, N.cbuf(sigs), N.cbuf(apks), N.cbuf(msgs), msg_len, _moff(msg_offsets), r, n_sets,
+                                                          _boff(batch_offsets), sets_per_batch, n_batches, res, st, sres, sst))
+    return [bool(x) for x in bytes(res)[:n_batches]], list(st)[:n_batches], [bool(x) for x in bytes(sres)[:n_sets]], list(sst)[:n_sets]
+
+
+def verify_multiple_batches_locate_device(d_sigs, d_msgs, d_rands, n_sets, n_batches, d_results, d_set_results, d_status=None, d_set_status=None, d_apks=None,
+                                          d_pks=None, k=0, pk_format=N.PK_COMPRESSED, d_pk_offsets=None, msg_len=32, d_msg_offsets=None, d_batch_offsets=None,
+                                          sets_per_batch=0, stream=None, ctx=None):
+    """The same over device buffers, as verify_multiple_batches_device: n_sets result bytes at d_set_results (required), n_sets status words at d_set_status
+    (optional). Enqueues only."""
+    ctx = ctx or _c()
+    ctx.check(N.lib().mbls_verify_multiple_batches_locate_device(ctx.handle, d_sigs, d_apks, d_pks, pk_format, d_pk_offsets, k, d_msgs, msg_len, d_msg_offsets, d_rands,
+                                                                 n_sets, d_batch_offsets, sets_per_batch, n_batches, d_results, d_status, d_set_results, d_set_status,
+                                                                 stream))
+
+
+def verify_multiple_batches_locate_indexed_device(table, d_sigs, d_key_idx, d_msgs, d_rands, n_sets, n_batches, d_results, d_set_results, d_status=None,
+                                                  d_set_status=None, k=0, d_offsets=None, msg_len=32, d_msg_offsets=None, d_batch_offsets=None, sets_per_batch=0,
+                                                  stream=None, ctx=None):
+    """The same over sets named by indices into a resident KeyTable. Enqueues only."""
+    ctx = ctx or table.ctx
+    ctx.check(N.lib().mbls_verify_multiple_batches_locate_indexed_device(ctx.handle, table.handle, d_sigs, d_key_idx, d_offsets, k, d_msgs, msg_len, d_msg_offsets,
+                                                                         d_rands, n_sets, d_batch_offsets, sets_per_batch, n_batches, d_results, d_status,
+                                                                         d_set_results, d_set_status, stream))
+
+
 # ---- verify_multiple over a shared message list: one Miller loop per message (include/mbls.h, mbls_verify_multiple*_shared_msgs)
 def set_vm_grouping(mode, ctx=None):
     """routing of the entries below: 0 auto (grouped when 2 n_msgs <= n), 1 always one Miller loop per message, 2 never (every set gathers its message's point)"""

@@ -20,6 +20,7 @@
 #include "mbls_ops.h"
 #include "mbls_coop.h"
 #include "mbls_vmb.h"
+#include "mbls_vml.h"
 #include "mbls_vms.h"
 #include "../../include/mbls.h"
 
@@ -698,6 +699,97 @@ __global__ void MBLS_LB k_vmb_final2(mbls_ws ws, uint32_t* status, uint8_t* resu
     uint32_t st = status[i]; uint8_t r;
     lane_final2<true>(ws, i, &st, &r, (MBLS_LDS uint32_t*)accstore, threadIdx.x);
     if ((t & 1) == 0) { status[i] = st; results[i] = r; }
+#endif
+}
+// ---- which sets of a rejected batch (mbls_verify_multiple_batches_locate*). The per-batch trees work in place and leave sums at range heads, so set i's blinded
+// signature and Miller value are gone when its batch's verdict is known: a SHADOW item per set, workspace item sh + i behind everything phase one works on
+// (mbls_vml.h vml_shadow_first), keeps them. Phase two then gives every set of a rejected batch the one-set batch's check, FE(f_i . ML(-G1, [r_i] sig_i)) = 1,
+// on the lane bodies phase one runs. One wave per SIMD throughout: a wave without a candidate returns at once and costs nothing.
+// before the signatures' trees: set i's [r_i] sig_i (slot S) -> the (sig, -G1) pair of its shadow item in the one-pair Miller kernels' operand layout
+__global__ void MBLS_LB k_vml_keep_sig(mbls_ws ws, uint64_t n, uint64_t sh) {
+    const uint64_t i = gid(); if (i >= n) return;
+    ws_st2(ws, MBLS_SLOT_H, sh + i, ws_ld2(ws, MBLS_SLOT_S, i)); ws_st2(ws, MBLS_SLOT_H + 2, sh + i, ws_ld2(ws, MBLS_SLOT_S + 2, i));
+    ws_st2(ws, MBLS_SLOT_H + 4, sh + i, ws_ld2(ws, MBLS_SLOT_S + 4, i));
+    ws_st(ws, MBLS_SLOT_APK, sh + i, fp_load_const(MBLS_G1_X)); ws_st(ws, MBLS_SLOT_APK + 1, sh + i, fp_load_const(MBLS_G1_NEG_Y)); ws_st(ws, MBLS_SLOT_APK + 2, sh + i, fp_one());
+}
+// item `to` + i <- the Miller value of item `from` + i (12 Fp, word for word)
+static __device__ __forceinline__ void vml_copy_f(const mbls_ws& ws, uint64_t from, uint64_t to) {
+    const uint32_t* src = ws.w + (uint64_t)MBLS_SLOT_F * 12 * ws.stride + from;
+    uint32_t* dst = ws.w + (uint64_t)MBLS_SLOT_F * 12 * ws.stride + to;
+#pragma unroll 12
+    for (int w = 0; w < 144; w++) dst[(uint64_t)w * ws.stride] = src[(uint64_t)w * ws.stride];
+}
+// before the products' trees: set i's Miller value f_i -> slot F of its shadow item
+__global__ void MBLS_LB k_vml_keep_f(mbls_ws ws, uint64_t n, uint64_t sh) {
+    const uint64_t i = gid(); if (i >= n) return;
+    vml_copy_f(ws, i, sh + i);
+}
+// after the per-batch tail, one lane per set: the answer of every set that needs no pairing, and the candidate flags (the rule: mbls_vml.h vml_mark). A
+// candidate's f_i moves back to slot F of the set's own item -- phase one is done with the items [0, n), and the shadow's slot F is where the Miller loop of
+// its (sig, -G1) pair leaves g_i.
+__global__ void MBLS_LB k_vml_mark(mbls_ws ws, const uint32_t* map, const uint32_t* off, uint32_t k, uint64_t B, uint64_t n, const uint32_t* st_set, const uint32_t* owned,
+                                   const uint8_t* batch_results, uint32_t* cand, uint8_t* set_results, uint32_t* set_status, uint64_t sh) {
+    const uint64_t i = gid(); if (i >= n) return;
+    uint64_t lo = 0, hi = 0, b = 0;
+    bool own = vmb_owner_range(map, off, k, B, n, i, &lo, &hi);
+    if (own) { b = off ? map[i] : i / k; own = vmb_owns_all(off ? owned : nullptr, b, lo, hi); }
+    uint32_t st;
+    const uint32_t v = vml_mark(own, own && batch_results[b] != 0, st_set[i], &st);
+    cand[i] = v == MBLS_VML_CANDIDATE ? 1u : 0u;
+    set_results[i] = v == MBLS_VML_TRUE ? 1 : 0;                  // (a candidate stays 0 until its own check has spoken: fail closed)
+    if (set_status) set_status[i] = st;
+    if (v == MBLS_VML_CANDIDATE) vml_copy_f(ws, sh + i, i);
+}
+// g_i = Miller([r_i] sig_i, -G1) over the shadow items (wsh = the workspace seen from the first shadow item of the launch), candidates only: k_miller_single's
+// and k_miller_single2's body
+template <int LPP> MBLS_FN void vml_miller_body(const mbls_ws& wsh, uint64_t n, const uint32_t* cand, uint32_t* spill) {
+    const uint64_t i = LPP == 2 ? gid() >> 1 : gid();
+    const bool on = i < n && cand[i] != 0;
+    if (!__ballot(on)) return;
+    if (!on) return;
+    miller_single_body<LPP>(wsh, n, 0, 0, spill);
+}
+__global__ void MBLS_LB k_vml_miller(mbls_ws wsh, uint64_t n, const uint32_t* cand) {
+    __shared__ uint32_t spill[154 * 64];
+    vml_miller_body<1>(wsh, n, cand, spill);
+}
+__global__ void MBLS_LB k_vml_miller2(mbls_ws wsh, uint64_t n, const uint32_t* cand) {
+    __shared__ uint32_t spill[154 * 64];
+    vml_miller_body<2>(wsh, n, cand, spill);
+}
+// item i <- f_i . g_i (slot F of item i times slot F of its shadow item sh + i: the generated tree routine with the shadow as the partner), candidates only
+__global__ void MBLS_LB k_vml_product(mbls_ws ws, uint64_t n, uint64_t sh, const uint32_t* cand) {
+#if MBLS_DEVICE_ASM
+    __shared__ uint32_t spill[154 * 64];
+    const uint64_t i = gid();
+    const bool on = i < n && cand[i] != 0;
+    if (!__ballot(on)) return;
+    if (!on) return;
+    tree_level_d_call<false>(ws, i, sh, (MBLS_LDS uint32_t*)spill, threadIdx.x);
+#endif
+}
+// the candidates' verdicts: one final exponentiation per candidate with verify_multiple's reject mask on the set's OWN word (k_vmb_final's body; the word
+// carries no rejecting bit, or the set would be no candidate, so MBLS_ST_PAIRING_FAILED is added exactly where the check fails)
+__global__ void MBLS_LB k_vml_final(mbls_ws ws, const uint32_t* st_set, const uint32_t* cand, uint8_t* set_results, uint32_t* set_status, uint64_t n) {
+    __shared__ uint32_t accstore[154 * 64];
+    const uint64_t i = gid();
+    const bool on = i < n && cand[i] != 0;
+    if (!__ballot(on)) return;
+    if (!on) return;
+    uint32_t st = st_set[i]; uint8_t r; lane_final<true>(ws, i, &st, &r, (MBLS_LDS uint32_t*)accstore, threadIdx.x, true);
+    set_results[i] = r; if (set_status) set_status[i] = st;
+}
+__global__ void MBLS_LB k_vml_final2(mbls_ws ws, const uint32_t* st_set, const uint32_t* cand, uint8_t* set_results, uint32_t* set_status, uint64_t n) {
+    __shared__ uint32_t accstore[154 * 64];
+    const uint64_t t = gid();
+    const uint64_t i = t >> 1;
+    const bool on = i < n && cand[i] != 0;
+    if (!__ballot(on)) return;
+    if (!on) return;
+#if MBLS_DEVICE_ASM
+    uint32_t st = st_set[i]; uint8_t r;
+    lane_final2<true>(ws, i, &st, &r, (MBLS_LDS uint32_t*)accstore, threadIdx.x);
+    if ((t & 1) == 0) { set_results[i] = r; if (set_status) set_status[i] = st; }
 #endif
 }
 // verify_multiple over several devices ("one exchange step"): what one shard contributes is the product of its
@@ -3178,17 +3270,23 @@ extern "C" int mbls_verify_multiple_shared_msgs_rng(mbls_ctx* c, const uint8_t* 
 // before the first kernel is enqueued on a side stream. Enqueues only.
 // longest: the longest range of the table when the host has seen it (0: a device-side table -- any batch may hold every set, the trees get every level)
 // sigs_resident / hash_enqueued: as in verify_multiple_impl (the _rng entry's second half)
+// locate mode (mbls_verify_multiple_batches_locate*): phase one as without it, with the sets' blinded signatures and Miller values kept in shadow items before the
+// trees run over them (k_vml_keep_sig, k_vml_keep_f), and phase two behind the per-batch tail: mark (k_vml_mark), then for the candidates -- the sets of rejected
+// batches whose own word carries no rejecting bit -- the Miller loop of (sig, -G1), the product with f_i and a final exponentiation each. Enqueued whatever the
+// verdicts are: the host never learns how many candidates there are, and waves without one return at once.
+struct vmb_locate { uint8_t* d_set_results = nullptr; uint32_t* d_set_status = nullptr; };
 struct vmb_keys {
     const uint8_t* d_apks = nullptr; const uint8_t* d_pks = nullptr; int pk_format = MBLS_PK_UNCOMPRESSED; const uint32_t* d_pk_offsets = nullptr; uint32_t k = 0;
     const mbls_keytable* tab = nullptr; const uint32_t* d_idx = nullptr;
 };
 static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands,
         uint64_t n, const uint32_t* d_boff, uint32_t spb, uint64_t B, uint64_t longest, uint8_t* d_results, uint32_t* d_status, void* stream,
-        bool sigs_resident = false, bool hash_enqueued = false) {
+        bool sigs_resident = false, bool hash_enqueued = false, const vmb_locate* loc = nullptr) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
     if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
     if (!d_results) ARGFAIL(c, "null results");
+    if (loc && !loc->d_set_results) ARGFAIL(c, "null set results");
     if (n > 0xFFFFFFFEull || B > 0xFFFFFFFEull) ARGFAIL(c, "set and batch indices are 32-bit");
     if (!d_boff && (uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch");
     if (n && !d_rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
@@ -3200,7 +3298,8 @@ static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, cons
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const bool pair_hash = n && n <= c->split_max_items && 2 * n <= c->round_items;       // as verify_multiple_impl decides
-    int rc = mbls_ctx_reserve(c, vmb_workspace_items(n, B, pair_hash)); if (rc) return rc;
+    const uint64_t sh = vml_shadow_first(n, B, pair_hash);         // locate mode: the first shadow item
+    int rc = mbls_ctx_reserve(c, loc ? vml_workspace_items(n, B, pair_hash) : vmb_workspace_items(n, B, pair_hash)); if (rc) return rc;
     uint32_t* map = nullptr;
     sbuf dmap(c, 9);
     if (d_boff) { HIPCHK(c, dmap.alloc(4 * (n ? n : 1))); map = dmap.as<uint32_t>(); }
@@ -3216,6 +3315,12 @@ static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, cons
     if (d_status) HIPCHK(c, hipMemsetAsync(d_status, 0, 4 * B, s));
     if (map) HIPCHK(c, hipMemsetAsync(map, 0xFF, 4 * (n ? n : 1), s));                // every entry the map kernel does not write reads as "no owner"
     HIPCHK(c, hipMemsetAsync(d_results, 0, B, s));                 // false until the tail kernel has spoken (fail closed)
+    uint32_t* cand = c->d_status + vml_flags_first(n, B);          // (locate mode: cap >= 2 n + 2 B words)
+    if (loc && n) {
+        HIPCHK(c, hipMemsetAsync(loc->d_set_results, 0, n, s));
+        if (loc->d_set_status) HIPCHK(c, hipMemsetAsync(loc->d_set_status, 0, 4 * n, s));
+        HIPCHK(c, hipMemsetAsync(cand, 0, 4 * n, s));
+    }
     // the three chains side by side below half a round, as in verify_multiple_impl
     const bool fork = n && 2 * n <= c->round_items;
     hipStream_t s_sig = fork ? c->hs_b : s, s_msg = fork ? c->hs_c : s;
@@ -3234,6 +3339,7 @@ static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, cons
         else
             hipLaunchKernelGGL(k_blind_sig_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, st_set, n);
         if (!longest) longest = d_boff ? n : spb;
+        if (loc) hipLaunchKernelGGL(k_vml_keep_sig, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, n, sh);
         for (uint64_t half = 1; half < longest; half *= 2)         // S_b: the per-batch sums of the blinded signatures, left at the head of each range
             hipLaunchKernelGGL(k_g2_seg_tree_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, (const uint32_t*)map, d_boff, spb, B, n, half);
         if (!(hash_enqueued && fork) && !hash_first) launch_hash(c, ws, d_msgs, msg_len, d_moff, st_set, n, s_msg, pair_hash);
@@ -3250,6 +3356,7 @@ static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, cons
         launch_miller_single(c, ws, n + B, s);
     if (n) {
         hipLaunchKernelGGL(k_vmb_status_fold, dim3(nblk(n)), dim3(WG), 0, s, (const uint32_t*)map, d_boff, spb, B, n, (const uint32_t*)st_set, st_batch, owned);
+        if (loc) hipLaunchKernelGGL(k_vml_keep_f, dim3(nblk(n)), dim3(WG), 0, s, ws, n, sh);
         for (uint64_t half = 1; half < longest; half *= 2)         // the per-batch products of the sets' Miller values
             hipLaunchKernelGGL(k_f12_seg_tree_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)map, d_boff, spb, B, n, half);
     }
@@ -3257,6 +3364,25 @@ static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, cons
     hipLaunchKernelGGL(k_f12_tree_d, dim3(nblk(B)), dim3(WG), 0, s, wv, 2 * B, B);      // batch b <- (its signature pair) x (its sets' product)
     if (B <= c->split_max_items && 2 * B <= c->round_items) hipLaunchKernelGGL(k_vmb_final2, dim3(nblk(2 * B)), dim3(WG), 0, s, wv, st_batch, d_results, B);
     else hipLaunchKernelGGL(k_vmb_final, dim3(nblk(B)), dim3(WG), 0, s, wv, st_batch, d_results, B);
+    if (loc && n) {
+        hipLaunchKernelGGL(k_vml_mark, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)map, d_boff, spb, B, n, (const uint32_t*)st_set, (const uint32_t*)owned,
+                           (const uint8_t*)d_results, cand, loc->d_set_results, loc->d_set_status, sh);
+        // the candidates' Miller loops over the shadow items, cut at rounds as launch_miller_single cuts: whole rounds, then the rest in the form its size allows
+        const uint64_t R = c->round_items;
+        const uint64_t full = n > R ? (n / R) * R : 0, rest = n - full;
+        mbls_ws wsh = ws; wsh.w += sh;
+        if (full) hipLaunchKernelGGL(k_vml_miller, dim3(nblk(full)), dim3(WG), 0, s, wsh, full, (const uint32_t*)cand);
+        if (rest) {
+            mbls_ws wr = wsh; wr.w += full;
+            if (2 * rest <= R) hipLaunchKernelGGL(k_vml_miller2, dim3(nblk(2 * rest)), dim3(WG), 0, s, wr, rest, (const uint32_t*)(cand + full));
+            else hipLaunchKernelGGL(k_vml_miller, dim3(nblk(rest)), dim3(WG), 0, s, wr, rest, (const uint32_t*)(cand + full));
+        }
+        hipLaunchKernelGGL(k_vml_product, dim3(nblk(n)), dim3(WG), 0, s, ws, n, sh, (const uint32_t*)cand);
+        if (n <= c->split_max_items && 2 * n <= c->round_items)
+            hipLaunchKernelGGL(k_vml_final2, dim3(nblk(2 * n)), dim3(WG), 0, s, ws, (const uint32_t*)st_set, (const uint32_t*)cand, loc->d_set_results, loc->d_set_status, n);
+        else
+            hipLaunchKernelGGL(k_vml_final, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)st_set, (const uint32_t*)cand, loc->d_set_results, loc->d_set_status, n);
+    }
     HIPCHK(c, hipGetLastError());
     return ws_release(c, s);
 }
@@ -3274,6 +3400,30 @@ extern "C" int mbls_verify_multiple_batches_indexed_device(mbls_ctx* c, const mb
     vmb_keys ks; ks.tab = t; ks.d_idx = d_key_idx; ks.d_pk_offsets = d_offsets; ks.k = k;
     return vmb_impl(c, d_sigs, ks, d_msgs, msg_len, d_moff, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, 0, d_results, d_status, stream);
 }
+extern "C" int mbls_verify_multiple_batches_locate_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_pks, int pk_format,
+        const uint32_t* d_pk_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n,
+        const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint8_t* d_results, uint32_t* d_status, uint8_t* d_set_results,
+        uint32_t* d_set_status, void* stream) {
+    vmb_keys ks; ks.d_apks = d_apks;
+    if (!d_apks) { ks.d_pks = d_pks; ks.pk_format = pk_format; ks.d_pk_offsets = d_pk_offsets; ks.k = k; }
+    vmb_locate loc; loc.d_set_results = d_set_results; loc.d_set_status = d_set_status;
+    return vmb_impl(c, d_sigs, ks, d_msgs, msg_len, d_moff, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, 0, d_results, d_status, stream, false, false, &loc);
+}
+extern "C" int mbls_verify_multiple_batches_locate_indexed_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx,
+        const uint32_t* d_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n,
+        const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint8_t* d_results, uint32_t* d_status, uint8_t* d_set_results,
+        uint32_t* d_set_status, void* stream) {
+    if (!c || !t) return MBLS_ERR_ARGUMENT;
+    vmb_keys ks; ks.tab = t; ks.d_idx = d_key_idx; ks.d_pk_offsets = d_offsets; ks.k = k;
+    vmb_locate loc; loc.d_set_results = d_set_results; loc.d_set_status = d_set_status;
+    return vmb_impl(c, d_sigs, ks, d_msgs, msg_len, d_moff, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, 0, d_results, d_status, stream, false, false, &loc);
+}
+// what a locate call reserves before its first kernel (include/mbls.h): mbls_vml.h's figure under the limits' choice of the message phase
+extern "C" uint64_t mbls_plan_locate_workspace_items(const mbls_limits* limits, uint64_t n_sets, uint64_t n_batches) {
+    if (!limits || !n_batches) return 0;
+    const bool pair_hash = n_sets && n_sets <= limits->split_max_items && 2 * n_sets <= limits->round_items;
+    return vml_workspace_items(n_sets, n_batches, pair_hash);
+}
 // the host checks shared by the two host entries: the batch table (first 0, non-decreasing, last n) or the uniform count, the message table, the buffers
 static int vmb_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n,
                           const uint32_t* boff, uint32_t spb, uint64_t B, const uint8_t* results, uint64_t* longest) {
@@ -3286,13 +3436,16 @@ static int vmb_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apk
     if (n && (!sigs96 || !apks96 || (!msgs && msg_total))) ARGFAIL(c, "null buffer");
     return MBLS_OK;
 }
-extern "C" int mbls_verify_multiple_batches(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
-        const uint64_t* rands, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, uint32_t* status) {
+// locate: the sets' answers as well (set_results required, set_status optional), staged behind one another in one buffer: n words, then n bytes
+static int vmb_host_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        const uint64_t* rands, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, uint32_t* status, bool locate, uint8_t* set_results,
+        uint32_t* set_status) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
     if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
     uint64_t longest = 0;
     int rc = vmb_host_check(c, sigs96, apks96, msgs, msg_len, moff, n, boff, spb, B, results, &longest); if (rc) return rc;
+    if (locate && !set_results) ARGFAIL(c, "null set results");
     if (n && !rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t msg_first = moff ? moff[0] : 0;
@@ -3302,28 +3455,49 @@ extern "C" int mbls_verify_multiple_batches(mbls_ctx* c, const uint8_t* sigs96, 
     if (boff) HIPCHK(c, dbo.up(boff, 4 * (B + 1)));
     if (moff) HIPCHK(c, dmo.up(moff, 8 * (n + 1)));
     HIPCHK(c, dres.alloc(B)); HIPCHK(c, dst.alloc(4 * B));
+    sbuf dset(c, 4);
+    vmb_locate loc;
+    if (locate) { HIPCHK(c, dset.alloc(5 * n)); loc.d_set_status = dset.as<uint32_t>(); loc.d_set_results = dset.as<uint8_t>() + 4 * n; }
     vmb_keys ks; ks.d_apks = da.as<uint8_t>();
     rc = vmb_impl(c, ds.as<uint8_t>(), ks, dm.as<uint8_t>() - msg_first, msg_len, moff ? dmo.as<uint64_t>() : nullptr, dr.as<uint64_t>(), n,
-                  boff ? dbo.as<uint32_t>() : nullptr, spb, B, longest ? longest : 1, dres.as<uint8_t>(), dst.as<uint32_t>(), c->hs_a);
+                  boff ? dbo.as<uint32_t>() : nullptr, spb, B, longest ? longest : 1, dres.as<uint8_t>(), dst.as<uint32_t>(), c->hs_a, false, false,
+                  locate ? &loc : nullptr);
     if (rc) { vm_rng_drain(c); return rc; }
     HIPCHK(c, hipStreamSynchronize(c->hs_a));
     c->ws_pending = false;
     HIPCHK(c, dres.down(results, B));
     if (status) HIPCHK(c, dst.down(status, 4 * B));
+    if (locate) {
+        HIPCHK(c, hipMemcpy(set_results, loc.d_set_results, n, hipMemcpyDeviceToHost));
+        if (set_status) HIPCHK(c, hipMemcpy(set_status, loc.d_set_status, 4 * n, hipMemcpyDeviceToHost));
+    }
     return MBLS_OK;
+}
+extern "C" int mbls_verify_multiple_batches(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        const uint64_t* rands, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, uint32_t* status) {
+    return vmb_host_impl(c, sigs96, apks96, msgs, msg_len, moff, rands, n, boff, spb, B, results, status, false, nullptr, nullptr);
+}
+extern "C" int mbls_verify_multiple_batches_locate(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        const uint64_t* rands, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, uint32_t* status, uint8_t* set_results,
+        uint32_t* set_status) {
+    return vmb_host_impl(c, sigs96, apks96, msgs, msg_len, moff, rands, n, boff, spb, B, results, status, true, set_results, set_status);
 }
 // The reference's order, generalised to B batches: B consecutive reference calls sharing one generator test batch b's signatures one by one and draw a scalar
 // for every set in front of its first signature outside G2 (all of its sets when there is none), batch after batch (src/aggregates.rs:272-287). Here the
 // signatures of ALL batches are decoded and tested first (vm_rng_phase1), the host reads the verdicts, `draw` is asked ONCE for exactly that sequence of
 // scalars, and the rest runs without a second subgroup test (the points are in the slots). A batch with a bad signature is false through its status bits; its
 // sets behind the bad one never had a scalar drawn and get the scalar 1, which changes nothing (the batch is rejected whatever its pairing product is).
-extern "C" int mbls_verify_multiple_batches_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
-        uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, mbls_scalar_source draw, void* user) {
+// locate: the sets' answers as well. A set at or behind its batch's first signature outside G2 has no scalar (the reference never draws one): it cannot be
+// examined -- its answer is 0 and its word what the signature phase found, set on the host from the verdicts phase 1 read back.
+static int vmb_rng_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, mbls_scalar_source draw, void* user, bool locate, uint8_t* set_results,
+        uint32_t* set_status) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
     if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
     uint64_t longest = 0;
     int rc = vmb_host_check(c, sigs96, apks96, msgs, msg_len, moff, n, boff, spb, B, results, &longest); if (rc) return rc;
+    if (locate && !set_results) ARGFAIL(c, "null set results");
     if (n == 0) { memset(results, 1, B); return MBLS_OK; }                  // empty iterators: true, the generator untouched
     if (!draw) ARGFAIL(c, "null scalar source");
     std::vector<uint64_t> rands, drawn; std::vector<uint32_t> st;
@@ -3332,10 +3506,12 @@ extern "C" int mbls_verify_multiple_batches_rng(mbls_ctx* c, const uint8_t* sigs
     // everything that may allocate comes before the first kernel: the workspace of the WHOLE call (phase 1 alone would reserve less, and growing it later would
     // lose the decoded signatures), the staging of the table, the results and the map
     const bool pair_hash = n <= c->split_max_items && 2 * n <= c->round_items;
-    rc = mbls_ctx_reserve(c, vmb_workspace_items(n, B, pair_hash)); if (rc) return rc;
-    sbuf dbo(c, 5), dres(c, 7), dmap(c, 9);
+    rc = mbls_ctx_reserve(c, locate ? vml_workspace_items(n, B, pair_hash) : vmb_workspace_items(n, B, pair_hash)); if (rc) return rc;
+    sbuf dbo(c, 5), dres(c, 7), dmap(c, 9), dset(c, 8);
     if (boff) { HIPCHK(c, dbo.up(boff, 4 * (B + 1))); HIPCHK(c, dmap.alloc(4 * n)); }
     HIPCHK(c, dres.alloc(B));
+    vmb_locate loc;
+    if (locate) { HIPCHK(c, dset.alloc(5 * n)); loc.d_set_status = dset.as<uint32_t>(); loc.d_set_results = dset.as<uint8_t>() + 4 * n; }
     vm_rng_stage g(c);
     rc = vm_rng_phase1(c, g, sigs96, apks96, msgs, msg_len, moff, n, 8, st.data()); if (rc) return rc;
     uint64_t total = 0;
@@ -3358,12 +3534,32 @@ extern "C" int mbls_verify_multiple_batches_rng(mbls_ctx* c, const uint8_t* sigs
     if (e != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
     vmb_keys ks; ks.d_apks = g.da.as<uint8_t>();
     rc = vmb_impl(c, nullptr, ks, g.d_msgs, msg_len, g.d_moff, g.dr.as<uint64_t>(), n, boff ? dbo.as<uint32_t>() : nullptr, spb, B, longest ? longest : 1,
-                  dres.as<uint8_t>(), nullptr, c->hs_a, true, true);
+                  dres.as<uint8_t>(), nullptr, c->hs_a, true, true, locate ? &loc : nullptr);
     if (rc) { vm_rng_drain(c); return rc; }
     if (hipStreamSynchronize(c->hs_a) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
     c->ws_pending = false;
     HIPCHK(c, dres.down(results, B));
+    if (locate) {
+        std::vector<uint32_t> sst;
+        try { sst.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
+        HIPCHK(c, hipMemcpy(set_results, loc.d_set_results, n, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(sst.data(), loc.d_set_status, 4 * n, hipMemcpyDeviceToHost));
+        for (uint64_t b = 0; b < B; b++) {
+            const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
+            for (uint64_t i = lo + reach[b]; i < hi; i++) { set_results[i] = 0; sst[i] = st[i]; }
+        }
+        if (set_status) memcpy(set_status, sst.data(), 4 * n);
+    }
     return MBLS_OK;
+}
+extern "C" int mbls_verify_multiple_batches_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, mbls_scalar_source draw, void* user) {
+    return vmb_rng_impl(c, sigs96, apks96, msgs, msg_len, moff, n, boff, spb, B, results, draw, user, false, nullptr, nullptr);
+}
+extern "C" int mbls_verify_multiple_batches_locate_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len,
+        const uint64_t* moff, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, uint8_t* set_results, uint32_t* set_status,
+        mbls_scalar_source draw, void* user) {
+    return vmb_rng_impl(c, sigs96, apks96, msgs, msg_len, moff, n, boff, spb, B, results, draw, user, true, set_results, set_status);
 }
 
 // ------------------------------------------------------------------------------------------------ several GPUs behind one handle

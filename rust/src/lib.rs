@@ -79,6 +79,24 @@ extern "C" {
     fn mbls_verify_multiple_batches_rng(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
                                         n_sets: u64, batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64, results: *mut u8, draw: MblsScalarSource,
                                         user: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_batches_locate_rng(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
+                                               n_sets: u64, batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64, results: *mut u8,
+                                               set_results: *mut u8, set_status: *mut u32, draw: MblsScalarSource, user: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn mbls_verify_multiple_batches_locate(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
+                                           rands: *const u64, n_sets: u64, batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64, results: *mut u8,
+                                           status: *mut u32, set_results: *mut u8, set_status: *mut u32) -> c_int;
+    #[allow(dead_code)]
+    fn mbls_verify_multiple_batches_locate_device(ctx: *mut MblsCtx, d_sigs96: *const u8, d_apks96: *const u8, d_pks: *const u8, pk_format: c_int,
+                                                  d_pk_offsets: *const u32, k: u32, d_msgs: *const u8, msg_len: u32, d_msg_offsets: *const u64, d_rands: *const u64,
+                                                  n_sets: u64, d_batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64, d_results: *mut u8,
+                                                  d_status: *mut u32, d_set_results: *mut u8, d_set_status: *mut u32, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn mbls_verify_multiple_batches_locate_indexed_device(ctx: *mut MblsCtx, t: *const MblsKeyTable, d_sigs96: *const u8, d_key_idx: *const u32,
+                                                          d_offsets: *const u32, k: u32, d_msgs: *const u8, msg_len: u32, d_msg_offsets: *const u64,
+                                                          d_rands: *const u64, n_sets: u64, d_batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64,
+                                                          d_results: *mut u8, d_status: *mut u32, d_set_results: *mut u8, d_set_status: *mut u32,
+                                                          stream: *mut c_void) -> c_int;
     // device buffers: for callers that keep their inputs resident (not used by the types below)
     #[allow(dead_code)]
     fn mbls_verify_multiple_batches_device(ctx: *mut MblsCtx, d_sigs96: *const u8, d_apks96: *const u8, d_pks: *const u8, pk_format: c_int, d_pk_offsets: *const u32,
@@ -652,6 +670,49 @@ impl AggregateSignature {
         }
         check(rc)?;
         Ok(res.into_iter().map(|r| r == 1).collect())
+    }
+    /// The same, and in the same call (`mbls_verify_multiple_batches_locate_rng`) WHICH sets of the rejected batches are the bad ones: one bool per batch as
+    /// above, and per batch one bool per set. Every set of an accepted batch reads `true` -- a passing batch is not examined set by set: the batch check is
+    /// the statement verify_multiple makes. A set of a rejected batch reads what the one-set batch with its scalar returns; a set at or behind the batch's
+    /// first signature outside G2 has no scalar (the reference never draws one) and reads `false`. `rng` is left where
+    /// `verify_multiple_aggregate_signatures_batches` leaves it.
+    pub fn verify_multiple_aggregate_signatures_batches_locate<'a, R, I, B>(rng: &mut R, batches: I) -> Result<(Vec<bool>, Vec<Vec<bool>>), AmclError>
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = B>,
+        B: Iterator<Item = (&'a AggregateSignature, &'a AggregatePublicKey, &'a [u8])>,
+    {
+        let (mut sigs, mut apks, mut msgs) = (Vec::new(), Vec::new(), Vec::new());
+        let mut moff: Vec<u64> = vec![0];
+        let mut boff: Vec<u32> = vec![0];
+        for b in batches {
+            for (s, a, m) in b {
+                sigs.extend_from_slice(&s.point);
+                apks.extend_from_slice(&a.point);
+                msgs.extend_from_slice(m);
+                moff.push(msgs.len() as u64);
+            }
+            boff.push((moff.len() - 1) as u32);
+        }
+        let n_batches = boff.len() - 1;
+        if n_batches == 0 {
+            return Ok((Vec::new(), Vec::new()));
+        }
+        let n_sets = moff.len() - 1;
+        let mut res = vec![0u8; n_batches];
+        let mut sres = vec![0u8; n_sets.max(1)];
+        let mut st = DrawState { rng, panic: None };
+        let rc = unsafe {
+            mbls_verify_multiple_batches_locate_rng(ctx(), sigs.as_ptr(), apks.as_ptr(), msgs.as_ptr(), 0, moff.as_ptr(), n_sets as u64, boff.as_ptr(), 0,
+                                                    n_batches as u64, res.as_mut_ptr(), sres.as_mut_ptr(), std::ptr::null_mut(), draw_scalars::<R>,
+                                                    &mut st as *mut DrawState<R> as *mut c_void)
+        };
+        if let Some(payload) = st.panic.take() {
+            std::panic::resume_unwind(payload);
+        }
+        check(rc)?;
+        let per_set = (0..n_batches).map(|b| sres[boff[b] as usize..boff[b + 1] as usize].iter().map(|&r| r == 1).collect()).collect();
+        Ok((res.into_iter().map(|r| r == 1).collect(), per_set))
     }
     /// `src/aggregates.rs:319-322`
     pub fn from_bytes(bytes: &[u8]) -> Result<AggregateSignature, AmclError> {
