@@ -667,6 +667,28 @@ int mbls_hash_to_g2_batch_mode(mbls_ctx* ctx, const uint8_t* msgs, uint32_t msg_
  * 48-byte big-endian values below p (MBLS_ERR_ARGUMENT otherwise). mode: 0 the compiled lane body, 1/2/3 as
  * mbls_hash_to_g2_batch_mode (generated lane routine / wave program / lane pair). out96: compressed H, infinity as 0xC0||0.. */
 int mbls_map_to_g2_probe(mbls_ctx* ctx, const uint8_t* u192, uint64_t n, uint8_t* out96, int mode);
+/* test probe: the Miller loop as a VALUE. in624: n x 13 canonical 48-byte big-endian values below p (MBLS_ERR_ARGUMENT otherwise) --
+ * apk = G1 Jacobian X, Y, Z (Z = 0: infinity); sig = G2 affine x.c0, x.c1, y.c0, y.c1 (y = 0: infinity, as in the workspace); H = G2 Jacobian X.c0, X.c1,
+ * Y.c0, Y.c1, Z.c0, Z.c1 (Z = 0: infinity). An import kernel puts them into workspace slots APK, SIG and H (mode 5: H into slot S), the form `mode` names
+ * runs exactly what the pipeline launches for it, an export kernel writes out576: n x 12 coefficients in the order of slot F (c0.c0, c0.c1, c0.c2, c1.c0,
+ * c1.c1, c1.c2 = the coefficients of w^0, w^2, w^4, w^1, w^3, w^5; real part first). With f(Q, P) = f_{|x|,Q}(P) CONJUGATED (x < 0), up to factors from
+ * proper subfields of Fp12 (the projective formulas drop them; the final exponentiation kills them), a pair with an infinite member contributing 1:
+ *   0  the compiled body (lane_miller without LDS)          f(sig, -G1) f(H, apk)
+ *   1  k_miller, the generated two-pair routine             f(sig, -G1) f(H, apk)
+ *   2  k_miller_single, the one-pair routine on one lane    f(H, apk)             (sig is not read)
+ *   3  k_miller_single2, the same on a lane pair            f(H, apk)
+ *   4  wave program miller1                                 f(H, apk)
+ *   5  wave program smiller (S = H)                         conj(f(S, -G1))       (apk and sig are not read)
+ * Modes 0..4 leave f itself in slot F -- "the conjugated values as k_miller_single leaves them" the n-pairing tails multiply --; mode 5 exports slots
+ * 97..108, where smiller leaves the loop's value BEFORE the conjugation (vmfinal multiplies by its conjugate). Synchronises; host buffers. */
+int mbls_miller_probe(mbls_ctx* ctx, const uint8_t* in624, uint64_t n, uint8_t* out576, int mode);
+/* test probe: the final exponentiation as a VALUE. f576: n elements of Fp12, 12 canonical coefficients below p each in the order above, imported into
+ * slot F. mode 0: the compiled final_exp (lane_final's fallback body), 1: k_final's generated routine (final_exp_ws_d), 2: k_final2's routine on a
+ * lane pair (final_exp_ws_d2) -- kernels shaped like k_final / k_final2 (same launch bounds, same LDS array) that store f instead of folding it.
+ * out576[i] = f_i^(3 (p^12 - 1) / r) (the CUBE of the usual value: see mbls_pairing.h), is_one[i] bit 0 = fp12_is_one of it as the kernel evaluates it;
+ * mode 2: bit 1 of is_one[i] = the odd lane of item i came back with the even lane's value (compared on the device). mode 3: wave program vmfinal with
+ * slot F = f_i and 1 in slots 97..108: a verdict only -- is_one[i], out576 is not written (and may be NULL). Synchronises; host buffers. */
+int mbls_final_exp_probe(mbls_ctx* ctx, const uint8_t* f576, uint64_t n, uint8_t* out576, uint8_t* is_one, int mode);
 /* n x AggregateSignature::aggregate (src/aggregates.rs:100-106): set i sums its k signatures (or the signatures
  * [offsets[i], offsets[i+1]) of sigs96), starting from infinity (an empty set gives 0xC0 || 0..). errs[i] = MBLS_OK or the
  * Signature::from_bytes error of the first member that does not decode. No subgroup check, like the reference. */

@@ -281,6 +281,8 @@ SIGNATURES = {
     "mbls_aggregate_public_keys_batch": (C.c_int, [vp, vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp, vp]),
     "mbls_fp_mul_batch": (C.c_int, [vp, vp, vp, C.c_uint64, vp, C.c_int]),
     "mbls_map_to_g2_probe": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int]),
+    "mbls_miller_probe": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int]),
+    "mbls_final_exp_probe": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_int]),
     "mbls_dform_probe_shape": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mbls_dform_probe": (C.c_int, [vp, C.c_int, vp, C.c_uint64, vp]),
     "mbls_fp_mul_bench": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),

@@ -192,6 +192,34 @@ def map_to_g2_batch(u, n, mode=1, ctx=None):
     return bytes(out)[:96 * n]
 
 
+MILLER_MODES = {"body": 0, "two_pair": 1, "one_pair": 2, "one_pair_lane_pair": 3, "miller1": 4, "smiller": 5}
+FINAL_EXP_MODES = {"body": 0, "lane": 1, "lane_pair": 2, "vmfinal": 3}
+
+
+def miller_probe(operands, n, mode, ctx=None):
+    """test probe (include/mbls.h, mbls_miller_probe): the Miller loop of n items in the form `mode` names (MILLER_MODES); operands = 624 n packed bytes
+    (apk X, Y, Z; sig x.c0, x.c1, y.c0, y.c1; H X.c0 .. Z.c1, 48 bytes big-endian each). 576 n bytes: the 12 coefficients of each value in the order of slot F"""
+    ctx = ctx or _c()
+    if len(operands) != 624 * n:
+        raise ValueError("miller_probe takes 624 bytes per item")
+    out = N.outbuf(576 * n)
+    ctx.check(N.lib().mbls_miller_probe(ctx.handle, N.cbuf(operands), n, out, MILLER_MODES.get(mode, mode)))
+    return bytes(out)[:576 * n]
+
+
+def final_exp_probe(f, n, mode, ctx=None):
+    """test probe (include/mbls.h, mbls_final_exp_probe): the final exponentiation of n elements of Fp12 (576 n packed bytes) in the form `mode` names
+    (FINAL_EXP_MODES). (values: 576 n bytes, or None for the verdict-only form; is_one: n bools; lanes_equal: n bools for the lane-pair form, else None)"""
+    ctx = ctx or _c()
+    if len(f) != 576 * n:
+        raise ValueError("final_exp_probe takes 576 bytes per item")
+    mode = FINAL_EXP_MODES.get(mode, mode)
+    out, bits = N.outbuf(576 * n), N.outbuf(n)
+    ctx.check(N.lib().mbls_final_exp_probe(ctx.handle, N.cbuf(f), n, out, bits, mode))
+    bits = bytes(bits)[:n]
+    return (None if mode == 3 else bytes(out)[:576 * n], [bool(b & 1) for b in bits], [bool(b & 2) for b in bits] if mode == 2 else None)
+
+
 def aggregate_public_keys_batch(pks, n, k=None, pk_format=N.PK_COMPRESSED, pk_offsets=None, ctx=None):
     ctx = ctx or _c()
     out = N.outbuf(96 * n)

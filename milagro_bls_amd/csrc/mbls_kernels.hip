@@ -2420,15 +2420,20 @@ extern "C" int mbls_hash_to_g2_batch_mode(mbls_ctx* c, const uint8_t* msgs, uint
     }
     HIPCHK(c, hipStreamSynchronize(c->hs_a)); c->ws_pending = false; HIPCHK(c, dout.down(out96, 96 * n)); return MBLS_OK;
 }
+// the probes below take canonical 48-byte big-endian field elements: every one must be below p
+static const uint8_t MBLS_P_BE[48] = {0x1a, 0x01, 0x11, 0xea, 0x39, 0x7f, 0xe6, 0x9a, 0x4b, 0x1b, 0xa7, 0xb6, 0x43, 0x4b, 0xac, 0xd7, 0x64, 0x77, 0x4b, 0x84, 0xf3, 0x85, 0x12, 0xbf,
+                                      0x67, 0x30, 0xd2, 0xa0, 0xf6, 0xb0, 0xf6, 0x24, 0x1e, 0xab, 0xff, 0xfe, 0xb1, 0x53, 0xff, 0xff, 0xb9, 0xfe, 0xff, 0xff, 0xff, 0xff, 0xaa, 0xab};
+static bool all_below_p(const uint8_t* v48, uint64_t count) {
+    for (uint64_t j = 0; j < count; j++) if (memcmp(v48 + 48 * j, MBLS_P_BE, 48) >= 0) return false;
+    return true;
+}
 // test probe: the message phase after hash_to_field on the caller's field elements (include/mbls.h). The import kernel stands in for hash_fields_to_ws; from
 // there every mode runs what launch_hash runs for that form -- the same generated routines and wave programs, the packing limit obeyed -- and k_h_export.
 extern "C" int mbls_map_to_g2_probe(mbls_ctx* c, const uint8_t* u192, uint64_t n, uint8_t* out96, int mode) {
     if (!c || !out96 || (!u192 && n) || mode < 0 || mode > 3) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
     if (!n) return MBLS_OK;
-    static const uint8_t P_BE[48] = {0x1a, 0x01, 0x11, 0xea, 0x39, 0x7f, 0xe6, 0x9a, 0x4b, 0x1b, 0xa7, 0xb6, 0x43, 0x4b, 0xac, 0xd7, 0x64, 0x77, 0x4b, 0x84, 0xf3, 0x85, 0x12, 0xbf,
-                                      0x67, 0x30, 0xd2, 0xa0, 0xf6, 0xb0, 0xf6, 0x24, 0x1e, 0xab, 0xff, 0xfe, 0xb1, 0x53, 0xff, 0xff, 0xb9, 0xfe, 0xff, 0xff, 0xff, 0xff, 0xaa, 0xab};
-    for (uint64_t j = 0; j < 4 * n; j++) if (memcmp(u192 + 48 * j, P_BE, 48) >= 0) ARGFAIL(c, "a field element is not below p");
+    if (!all_below_p(u192, 4 * n)) ARGFAIL(c, "a field element is not below p");
     HIPCHK(c, hipSetDevice(c->device));
     sbuf du(c, 0), dout(c, 1); HIPCHK(c, du.up(u192, 192 * n)); HIPCHK(c, dout.alloc(96 * n));
     const uint64_t lanes = mode == 3 ? 2 * n : n;
@@ -2451,6 +2456,127 @@ extern "C" int mbls_map_to_g2_probe(mbls_ctx* c, const uint8_t* u192, uint64_t n
     hipLaunchKernelGGL(k_h_export, dim3(nblk(n)), dim3(WG), 0, s, ws, n, dout.as<uint8_t>());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s)); c->ws_pending = false; HIPCHK(c, dout.down(out96, 96 * n)); return MBLS_OK;
+}
+// Test probes of the pairing (mbls_miller_probe, mbls_final_exp_probe; include/mbls.h): the caller's operands go into the workspace slots the phase kernels fill,
+// the form the mode names runs EXACTLY what the pipeline launches for it -- the same kernels, generated routines and wave programs, nothing of them changed --, and
+// the Miller value / the exponentiation's value comes back as canonical bytes. Import and export are copies with a Montgomery conversion, one lane per item.
+#define MBLS_SLOT_SF 97            // 12 Fp: the Miller value of (S, -G1) between the wave programs smiller and vmfinal (tools/gen_coop.py WS_G)
+// item i's 13 values (apk X, Y, Z; sig x.c0 .. y.c1; H X.c0 .. Z.c1) -> slots APK 0..2, SIG 3..6 and h_slot .. h_slot + 5 (H, or S for program smiller)
+__global__ void __launch_bounds__(WG) k_pair_import(mbls_ws ws, const uint8_t* in624, uint64_t n, int h_slot) {
+    const uint64_t i = gid(); if (i >= n) return;
+    for (int k = 0; k < 13; k++) ws_st(ws, k < MBLS_SLOT_H ? k : h_slot + (k - MBLS_SLOT_H), i, fp_to_mont(fp_raw_from_be(in624 + 624 * i + 48 * k)));
+}
+// item i's 12 coefficients -> slot F; one_slot >= 0: the element 1 into slots one_slot .. one_slot + 11 beside it
+__global__ void __launch_bounds__(WG) k_f12_import(mbls_ws ws, const uint8_t* f576, uint64_t n, int one_slot) {
+    const uint64_t i = gid(); if (i >= n) return;
+    for (int k = 0; k < 12; k++) ws_st(ws, MBLS_SLOT_F + k, i, fp_to_mont(fp_raw_from_be(f576 + 576 * i + 48 * k)));
+    if (one_slot >= 0) for (int k = 0; k < 12; k++) ws_st(ws, one_slot + k, i, k ? fp_zero() : fp_one());
+}
+__global__ void __launch_bounds__(WG) k_f12_export(mbls_ws ws, uint64_t n, int slot, uint8_t* out576) {
+    const uint64_t i = gid(); if (i >= n) return;
+    for (int k = 0; k < 12; k++) fp_raw_to_be(out576 + 576 * i + 48 * k, fp_from_mont(ws_ld(ws, slot + k, i)));
+}
+// the compiled two-pair loop (lane_miller without an LDS home for the running points: miller_loop of mbls_pairing.h)
+__global__ void MBLS_LB k_miller_body(mbls_ws ws, uint64_t n) {
+    uint64_t i = gid(); if (i >= n) return;
+    lane_miller(ws, i);
+}
+// The final exponentiation with its VALUE kept: k_final / k_final2 with the fold into the status word replaced by a store of f (slot F of the item) and of
+// fp12_is_one(&f) as the kernel evaluates it. The same launch bounds, the same LDS array, the same generated routines.
+__global__ void MBLS_LB k_fexp_probe(mbls_ws ws, uint8_t* is_one, uint64_t n) {
+#if MBLS_DEVICE_ASM
+    __shared__ uint32_t accstore[154 * 64];
+    uint64_t i = gid(); if (i >= n) return;
+    fp12 f; final_exp_ws_d(&f, ws.w, ws.stride, i, (MBLS_LDS uint32_t*)accstore, threadIdx.x);
+    is_one[i] = fp12_is_one(&f) ? 1 : 0;
+    const fp2* c = &f.c0.c0;
+#pragma unroll
+    for (int s = 0; s < 6; s++) ws_st2(ws, MBLS_SLOT_F + 2 * s, i, c[s]);
+#endif
+}
+// lanes 2 j, 2 j + 1 = item 32 blockIdx + j: the even lane stores value and bit, the odd lane compares its own words with the even lane's (its neighbour in the
+// wave) and stores lanes_equal[i]
+__global__ void MBLS_LB k_fexp2_probe(mbls_ws ws, uint8_t* is_one, uint8_t* lanes_equal, uint64_t n) {
+#if MBLS_DEVICE_ASM
+    __shared__ uint32_t accstore[154 * 64];
+    const uint64_t t = gid(); if (t >= 2 * n) return;
+    const uint64_t i = t >> 1;
+    fp12 f; final_exp_ws_d2(&f, ws.w, ws.stride, i, (MBLS_LDS uint32_t*)accstore, threadIdx.x);
+    const fp* c = &f.c0.c0.c0;
+    uint32_t diff = 0;
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+        const fp v = c[k];
+#pragma unroll
+        for (int j = 0; j < 12; j++) diff |= v[j] ^ (uint32_t)__shfl_xor((int)v[j], 1);
+    }
+    if (t & 1) { lanes_equal[i] = diff == 0 ? 1 : 0; return; }
+    is_one[i] = fp12_is_one(&f) ? 1 : 0;
+#pragma unroll
+    for (int k = 0; k < 12; k++) ws_st(ws, MBLS_SLOT_F + k, i, c[k]);
+#endif
+}
+// the compiled body (lane_final's fallback: final_exp of mbls_pairing.h)
+__global__ void MBLS_LB k_fexp_body(mbls_ws ws, uint8_t* is_one, uint64_t n) {
+    uint64_t i = gid(); if (i >= n) return;
+    fp12 f; fp2* c = &f.c0.c0;
+    for (int s = 0; s < 6; s++) c[s] = ws_ld2(ws, MBLS_SLOT_F + 2 * s, i);
+    final_exp(&f, &f);
+    is_one[i] = fp12_is_one(&f) ? 1 : 0;
+    for (int s = 0; s < 6; s++) ws_st2(ws, MBLS_SLOT_F + 2 * s, i, c[s]);
+}
+extern "C" int mbls_miller_probe(mbls_ctx* c, const uint8_t* in624, uint64_t n, uint8_t* out576, int mode) {
+    if (!c || !out576 || (!in624 && n) || mode < 0 || mode > 5) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (!n) return MBLS_OK;
+    if (!all_below_p(in624, 13 * n)) ARGFAIL(c, "a field element is not below p");
+    HIPCHK(c, hipSetDevice(c->device));
+    sbuf din(c, 0), dout(c, 1); HIPCHK(c, din.up(in624, 624 * n)); HIPCHK(c, dout.alloc(576 * n));
+    int rc = mbls_ctx_reserve(c, n); if (rc) return rc;
+    mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
+    hipStream_t s = c->hs_a;
+    rc = ws_acquire(c, s); if (rc) return rc;
+    hipLaunchKernelGGL(k_pair_import, dim3(nblk(n)), dim3(WG), 0, s, ws, din.as<uint8_t>(), n, mode == 5 ? MBLS_SLOT_S : MBLS_SLOT_H);
+    if (mode == 0) hipLaunchKernelGGL(k_miller_body, dim3(nblk(n)), dim3(WG), 0, s, ws, n);
+    else if (mode == 1) hipLaunchKernelGGL(k_miller, dim3(nblk(n)), dim3(WG), 0, s, ws, n);
+    else if (mode == 2) hipLaunchKernelGGL(k_miller_single, dim3(nblk(n)), dim3(WG), 0, s, ws, n, 0, (uint64_t)0);
+    else if (mode == 3) hipLaunchKernelGGL(k_miller_single2, dim3(nblk(2 * n)), dim3(WG), 0, s, ws, n, 0, (uint64_t)0);
+    else coop_run(c, mode == 4 ? COOP_MILLER1 : COOP_SMILLER, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, n, (uint32_t*)nullptr, (uint8_t*)nullptr, COOP_RES_ITEM, s);
+    hipLaunchKernelGGL(k_f12_export, dim3(nblk(n)), dim3(WG), 0, s, ws, n, mode == 5 ? MBLS_SLOT_SF : MBLS_SLOT_F, dout.as<uint8_t>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s)); c->ws_pending = false; HIPCHK(c, dout.down(out576, 576 * n)); return MBLS_OK;
+}
+extern "C" int mbls_final_exp_probe(mbls_ctx* c, const uint8_t* f576, uint64_t n, uint8_t* out576, uint8_t* is_one, int mode) {
+    if (!c || !is_one || (!f576 && n) || mode < 0 || mode > 3 || (mode != 3 && !out576)) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (!n) return MBLS_OK;
+    if (!all_below_p(f576, 12 * n)) ARGFAIL(c, "a field element is not below p");
+    HIPCHK(c, hipSetDevice(c->device));
+    sbuf din(c, 0), dout(c, 1), dbit(c, 2), deq(c, 3);
+    HIPCHK(c, din.up(f576, 576 * n)); HIPCHK(c, dout.alloc(576 * n)); HIPCHK(c, dbit.alloc(n)); HIPCHK(c, deq.alloc(n));
+    int rc = mbls_ctx_reserve(c, n); if (rc) return rc;
+    mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
+    hipStream_t s = c->hs_a;
+    rc = ws_acquire(c, s); if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(dbit.p, 0, n, s)); HIPCHK(c, hipMemsetAsync(deq.p, 0, n, s));
+    hipLaunchKernelGGL(k_f12_import, dim3(nblk(n)), dim3(WG), 0, s, ws, din.as<uint8_t>(), n, mode == 3 ? MBLS_SLOT_SF : -1);
+    if (mode == 0) hipLaunchKernelGGL(k_fexp_body, dim3(nblk(n)), dim3(WG), 0, s, ws, dbit.as<uint8_t>(), n);
+    else if (mode == 1) hipLaunchKernelGGL(k_fexp_probe, dim3(nblk(n)), dim3(WG), 0, s, ws, dbit.as<uint8_t>(), n);
+    else if (mode == 2) hipLaunchKernelGGL(k_fexp2_probe, dim3(nblk(2 * n)), dim3(WG), 0, s, ws, dbit.as<uint8_t>(), deq.as<uint8_t>(), n);
+    else {            // program vmfinal on a wave per item: (slot F) * conj(1), the exponentiation, == 1 -- folded into a cleared status word, so results[item] is the bit
+        HIPCHK(c, hipMemsetAsync(c->d_status, 0, 4 * n, s));
+        coop_run(c, COOP_VMFINAL, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, n, c->d_status, dbit.as<uint8_t>(), COOP_RES_ITEM, s);
+    }
+    if (mode != 3) hipLaunchKernelGGL(k_f12_export, dim3(nblk(n)), dim3(WG), 0, s, ws, n, (int)MBLS_SLOT_F, dout.as<uint8_t>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s)); c->ws_pending = false;
+    HIPCHK(c, dbit.down(is_one, n));
+    if (mode != 3) HIPCHK(c, dout.down(out576, 576 * n));
+    if (mode == 2) {                // bit 1: the odd lane of the item came back with the even lane's value
+        std::vector<uint8_t> eq(n); HIPCHK(c, deq.down(eq.data(), n));
+        for (uint64_t i = 0; i < n; i++) is_one[i] |= (uint8_t)(eq[i] << 1);
+    }
+    return MBLS_OK;
 }
 extern "C" int mbls_aggregate_public_keys_batch(mbls_ctx* c, const uint8_t* pks, int fmt, const uint32_t* off, uint64_t n, uint32_t k,
                                                 uint8_t* apks96, uint32_t* status) {

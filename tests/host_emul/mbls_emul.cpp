@@ -73,6 +73,38 @@ void emul_map_to_g2(const uint8_t* u192, uint64_t n, uint8_t* out96) {
         g2_encode_jacobian(out96 + 96 * i, &h);
     }
 }
+// the compiled two-pair Miller loop (lane_miller without LDS: what mbls_miller_probe runs in mode 0) on caller-supplied operands: in624 = n x (apk X, Y, Z;
+// sig x.c0, x.c1, y.c0, y.c1 with y = 0 for infinity; H X.c0 .. Z.c1), canonical 48-byte big-endian values; out576 = the 12 coefficients of f in the order of
+// slot F. one_pair != 0: f(H, apk) alone through miller_loop(.., 1), the compiled statement of what the one-pair routines compute.
+void emul_miller(const uint8_t* in624, uint64_t n, uint8_t* out576, int one_pair) {
+    mbls_ws ws; ws.stride = 1; ws.w = (uint32_t*)calloc((size_t)MBLS_SLOT_COUNT * 12, 4);
+    for (uint64_t i = 0; i < n; i++) {
+        for (int k = 0; k < 13; k++) ws_st(ws, k, 0, fp_to_mont(fp_raw_from_be(in624 + 624 * i + 48 * k)));      // slots APK 0..2, SIG 3..6, H 7..12
+        if (one_pair) {
+            g2j h; h.x = ws_ld2(ws, MBLS_SLOT_H, 0); h.y = ws_ld2(ws, MBLS_SLOT_H + 2, 0); h.z = ws_ld2(ws, MBLS_SLOT_H + 4, 0);
+            g1j a; a.x = ws_ld(ws, MBLS_SLOT_APK, 0); a.y = ws_ld(ws, MBLS_SLOT_APK + 1, 0); a.z = ws_ld(ws, MBLS_SLOT_APK + 2, 0);
+            mbls_pair pr; pr.skip = g2_is_inf(&h) | g1_is_inf(&a);
+            g2h_from_jacobian(&pr.q, &h); g1arg_from_jacobian(&pr.p, &a); pr.t = pr.q;
+            fp12 f; miller_loop(&f, &pr, 1);
+            const fp2* c = &f.c0.c0;
+            for (int s = 0; s < 6; s++) ws_st2(ws, MBLS_SLOT_F + 2 * s, 0, c[s]);
+        } else
+            lane_miller(ws, 0);
+        for (int k = 0; k < 12; k++) fp_raw_to_be(out576 + 576 * i + 48 * k, fp_from_mont(ws_ld(ws, MBLS_SLOT_F + k, 0)));
+    }
+    free(ws.w);
+}
+// the compiled final exponentiation (lane_final's fallback body: mbls_final_exp_probe mode 0) on n elements of Fp12, 12 canonical coefficients each in the order of
+// slot F: the value and fp12_is_one of it
+void emul_final_exp(const uint8_t* f576, uint64_t n, uint8_t* out576, uint8_t* is_one) {
+    for (uint64_t i = 0; i < n; i++) {
+        fp12 f; fp* c = &f.c0.c0.c0;
+        for (int k = 0; k < 12; k++) c[k] = fp_to_mont(fp_raw_from_be(f576 + 576 * i + 48 * k));
+        final_exp(&f, &f);
+        for (int k = 0; k < 12; k++) fp_raw_to_be(out576 + 576 * i + 48 * k, fp_from_mont(c[k]));
+        is_one[i] = fp12_is_one(&f) ? 1 : 0;
+    }
+}
 void emul_fp_mul(const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out, int op) { for (uint64_t i = 0; i < n; i++) op_fp_mul(i, n, a, b, out, op); }
 void emul_aggregate(const uint8_t* pks, int fmt, const uint32_t* offsets, uint64_t n, uint32_t k, uint8_t* out96, uint32_t* status) {
     mbls_ws ws; ws.stride = n ? n : 1; ws.w = (uint32_t*)calloc((size_t)MBLS_SLOT_COUNT * 12 * ws.stride, 4);

@@ -120,11 +120,12 @@ def test_kernel_resources(lib_path):
     the key-decompression kernel -- nothing but a square root with the 8-entry window table -- fits 256 registers (two waves per SIMD)."""
     meta = kernel_metadata(lib_path)
     by = lambda prefix: next(v for k, v in meta.items() if k.startswith(prefix))
-    for k in ("_Z8k_miller", "_Z7k_final", "_Z15k_miller_single"):
+    # (k_fexp_probe / k_fexp2_probe: the value-keeping twins of k_final / k_final2 behind mbls_final_exp_probe)
+    for k in ("_Z8k_miller", "_Z7k_final", "_Z15k_miller_single", "_Z12k_fexp_probe", "_Z13k_fexp2_probe"):
         assert int(by(k)["private_segment_fixed_size"]) == 0 and int(by(k)["vgpr_spill_count"]) == 0, k
     for k in ("_Z8k_miller", "_Z7k_final", "_Z6k_hash", "_Z5k_sig"):
         assert int(by(k)["vgpr_count"]) > 256, k
-    for k in ("_Z8k_miller", "_Z7k_final", "_Z15k_miller_single"):
+    for k in ("_Z8k_miller", "_Z7k_final", "_Z15k_miller_single", "_Z12k_fexp_probe", "_Z13k_fexp2_probe"):
         assert int(by(k)["group_segment_fixed_size"]) * 4 <= 160 * 1024, k
     assert int(by("_Z15k_pk_decompress")["vgpr_count"]) <= 256 and int(by("_Z15k_pk_decompress")["agpr_count"]) >= 112
 
