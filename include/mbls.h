@@ -562,7 +562,8 @@ int mbls_verify_multiple_batches_rng(mbls_ctx* ctx, const uint8_t* sigs96, const
  * WORKSPACE: 2 n_sets + 2 n_batches items (3 n_sets for calls of at most half a round whose message phase runs on lane pairs, if that is more): what
  * mbls_plan_locate_workspace_items returns -- a pure function; mbls_ctx_reserve(ctx, that) beforehand keeps allocation out of the call. The entries reserve once,
  * before the first kernel.
- * NOT PROVIDED: a wave-engine form of phase two for very small calls, locate forms of the shared-message entries, of the mbls_multi handle and of the stream. */
+ * NOT PROVIDED: a wave-engine form of phase two for very small calls, locate forms of the mbls_multi handle and of the stream (the shared-message entries have
+ * theirs: mbls_verify_multiple*_shared_msgs_locate* below). */
 uint64_t mbls_plan_locate_workspace_items(const mbls_limits* limits, uint64_t n_sets, uint64_t n_batches);
 int mbls_verify_multiple_batches_locate_device(mbls_ctx* ctx, const uint8_t* d_sigs96, const uint8_t* d_apks96, const uint8_t* d_pks, int pk_format,
                                                const uint32_t* d_pk_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_msg_offsets,
@@ -634,6 +635,57 @@ int mbls_verify_multiple_shared_msgs(mbls_ctx* ctx, const uint8_t* sigs96, const
 int mbls_verify_multiple_shared_msgs_rng(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len,
                                          const uint64_t* msg_offsets, uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result,
                                          mbls_scalar_source draw, void* user);
+
+/* WHICH SETS OF A REJECTED SHARED-MESSAGE CALL. The two features above composed: a caller of mbls_verify_multiple*_shared_msgs who gets 0 would otherwise spell
+ * every set's message out again and run mbls_verify_multiple_batches_locate* over all n sets -- n hashes and n Miller loops, behind a second host round trip, on
+ * the path an attacker triggers with one bad signature. The _locate entries answer per set in the SAME call: arguments, validation, n = 0, rands == NULL, what the
+ * host entries refuse and the routing (mbls_ctx_set_vm_grouping) are those of the corresponding entry above, plus d_set_results (n bytes, REQUIRED: NULL is
+ * MBLS_ERR_ARGUMENT, nothing written) and d_set_status (n words, optional). The *_device forms ONLY ENQUEUE -- no host synchronisation anywhere; in particular the
+ * number of sets to examine is never read back.
+ * CONTRACT.
+ *  1. *d_result / *d_status are byte for byte what mbls_verify_multiple_shared_msgs_device writes for the same inputs and the same grouping mode. Calls without
+ *     _locate do not change in any launch or byte.
+ *  2. An ACCEPTED call gives every set 1. A passing batch is NOT EXAMINED set by set (item 2 of the contract above: the batch check is the security statement).
+ *  3. A REJECTED call gives set i what the one-set call {i} with the scalar rands[i] and its message spelled out returns: a rejecting bit of verify_multiple's
+ *     mask in the set's OWN word gives 0 without a pairing; otherwise the set passes exactly when FE(ML([r_i] apk_i, H(m_{idx(i)})) . ML(-G1, [r_i] sig_i)) = 1
+ *     (an infinite key with an infinite signature: 1, as there).
+ *  4. d_set_status[i] = the set's own MBLS_ST_* bits as phase one found them, with MBLS_ST_PAIRING_FAILED added exactly where the set's own check rejects it.
+ *  5. MESSAGE FAULTS on device-side lists give the set 0 with MBLS_ST_BAD_MSG_RANGE in its own word and no pairing: msg_idx[i] >= n_msgs (n_msgs = 0 included),
+ *     and a set that names a listed message whose range runs backwards or is 2^32 bytes or more (the grouped route reports such a message in the call's word
+ *     only; the mark step looks the message's flag up through msg_idx[i]). Nothing is read outside the call's buffers; a set naming a sound message is untouched
+ *     by its neighbours' faults.
+ *  6. The _rng form draws exactly as mbls_verify_multiple_shared_msgs_rng does. A set at or behind the first signature outside G2 has no scalar (the reference
+ *     never draws one): 0, and the status the signature phase found. Only sets with a scalar -- those in front of it -- can be examined.
+ *  7. Per-set answers are deterministic: positions inside a group vary from run to run with the atomics, and nothing per set depends on them.
+ * MECHANISM. Per-set route (mode 2; auto when 2 n_msgs > n): a Miller value per set exists, and the scheme is the one above with the call as the one batch --
+ * ([r_i] sig_i, -G1) and f_i kept in ONE shadow item per set, mark, one-pair loop, product, final exponentiation. Grouped route: f_i is never computed, the heads
+ * and per-message trees overwrite the sets' blinded keys and the signatures' tree their slot S, so each set gets TWO shadow items: A(i) keeps [r_i] apk_i (copied
+ * behind the blinding, before the grouping), B(i) the pair ([r_i] sig_i, -G1). Behind the tail one lane per set applies the rule (mbls_vsl.h: call verdict, own
+ * word, message flag through msg_idx) and copies a candidate's H(m) from the message table into A(i); one Miller launch walks the 2 n shadow items (cut at rounds,
+ * lane pairs up to half a round; waves without a candidate return after one ballot), a tree level with half = n forms A(i) . B(i), and a final exponentiation
+ * per candidate decides on the set's own word.
+ * WORKSPACE: what the entry above reserves (mbls_plan_verify_multiple_shared_msgs_workspace_items) plus n items on the per-set route, 2 n on the grouped one,
+ * behind everything phase one uses: mbls_plan_verify_multiple_shared_msgs_locate_workspace_items -- a pure function (0 for n = 0, a mode outside 0..2 or null
+ * limits). Reserved once, before the first kernel; the _rng form reserves before its first half.
+ * NOT PROVIDED: a wave-engine form of phase two, compaction of the candidates, a per-message first level that narrows the candidates to the bad groups; the
+ * mbls_multi handle, the stream, the shard form and wire-key sets (as for the entries above). */
+uint64_t mbls_plan_verify_multiple_shared_msgs_locate_workspace_items(const mbls_limits* limits, uint64_t n, uint64_t n_msgs, int mode);
+int mbls_verify_multiple_shared_msgs_locate_device(mbls_ctx* ctx, const uint8_t* d_sigs96, const uint8_t* d_apks96, const uint8_t* d_msgs, uint32_t msg_len,
+                                                   const uint64_t* d_msg_offsets, uint64_t n_msgs, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n,
+                                                   uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream);
+int mbls_verify_multiple_sets_indexed_shared_msgs_locate_device(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* d_sigs96, const uint32_t* d_key_idx,
+                                                                const uint32_t* d_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len,
+                                                                const uint64_t* d_msg_offsets, uint64_t n_msgs, const uint32_t* d_msg_idx, const uint64_t* d_rands,
+                                                                uint64_t n, uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status,
+                                                                void* stream);
+/* host buffers; validation as mbls_verify_multiple_shared_msgs */
+int mbls_verify_multiple_shared_msgs_locate(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len,
+                                            const uint64_t* msg_offsets, uint64_t n_msgs, const uint32_t* msg_idx, const uint64_t* rands, uint64_t n,
+                                            uint8_t* result, uint32_t* status, uint8_t* set_results, uint32_t* set_status);
+/* the reference's draw order (contract item 6) */
+int mbls_verify_multiple_shared_msgs_locate_rng(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len,
+                                                const uint64_t* msg_offsets, uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result,
+                                                uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user);
 
 /* ---- batch helpers used to build inputs and caches on the device ---- */
 /* n x PublicKey::from_bytes[_unchecked] / from_uncompressed_bytes: errs[i] = MBLS_OK / MBLS_ERR_* per key */

@@ -10,6 +10,7 @@
 //     AggregateSignature::verify_multiple_aggregate_signatures(rng, iter)   same, rng = any callable returning uint8_t
 //     (one call of it per batch, batch after batch)      AggregateSignature::verify_multiple_aggregate_signatures_batches(rng, batches) -> vector<bool>, ONE call
 //     (the same over sets that share messages)            AggregateSignature::verify_multiple_aggregate_signatures_shared_msgs(rng, iter): one hash and, where it pays, one Miller loop per message
+//     (... and which sets of a rejected call)             AggregateSignature::verify_multiple_aggregate_signatures_shared_msgs_locate(rng, iter): the bool and one bool per set
 //
 // Every curve / pairing operation runs in the HIP kernels; there is no CPU fallback: constructing the first object without a
 // GPU throws DeviceError. The only host arithmetic is SecretKey::key_generate (HKDF-SHA-256 + one reduction mod r), which the
@@ -279,6 +280,22 @@ struct AggregateSignature {
     // pays, the check walks one Miller loop per message instead of one per set.
     template <typename Rng>
     static bool verify_multiple_aggregate_signatures_shared_msgs(Rng&& rng, const std::vector<std::tuple<const AggregateSignature*, const AggregatePublicKey*, Bytes>>& sets) {
+        return vm_shared(rng, sets, nullptr);
+    }
+    // The same, and in the same call (mbls_verify_multiple_shared_msgs_locate_rng) WHICH sets of a rejected call are the bad ones: .first as above, .second one bool
+    // per set. Every set of an accepted call reads true (a passing batch is not examined set by set); a set of a rejected call reads what the one-set call with
+    // its scalar returns; a set at or behind the first signature outside G2 has no scalar (the reference never draws one) and reads false. rng is left where
+    // verify_multiple_aggregate_signatures_shared_msgs leaves it.
+    template <typename Rng>
+    static std::pair<bool, std::vector<bool>> verify_multiple_aggregate_signatures_shared_msgs_locate(
+            Rng&& rng, const std::vector<std::tuple<const AggregateSignature*, const AggregatePublicKey*, Bytes>>& sets) {
+        std::vector<bool> per_set;
+        const bool ok = vm_shared(rng, sets, &per_set);
+        return {ok, per_set};
+    }
+private:
+    template <typename Rng>
+    static bool vm_shared(Rng& rng, const std::vector<std::tuple<const AggregateSignature*, const AggregatePublicKey*, Bytes>>& sets, std::vector<bool>* per_set) {
         if (sets.empty()) return true;
         Bytes sigs, apks, msgs; std::vector<uint64_t> moff{0}; std::vector<uint32_t> idx; std::map<Bytes, uint32_t> index;
         for (auto& s : sets) {
@@ -300,11 +317,17 @@ struct AggregateSignature {
             catch (...) { p->err = std::current_exception(); for (uint64_t i = 0; i < count; i++) out[i] = 0; }        // never unwind through the C frames
         };
         uint8_t ok = 0;
-        const int rc = mbls_verify_multiple_shared_msgs_rng(detail::ctx(), sigs.data(), apks.data(), msgs.data(), 0, moff.data(), index.size(), idx.data(), sets.size(), &ok, draw, &u);
+        std::vector<uint8_t> sres(per_set ? sets.size() : 0);
+        const int rc = per_set
+            ? mbls_verify_multiple_shared_msgs_locate_rng(detail::ctx(), sigs.data(), apks.data(), msgs.data(), 0, moff.data(), index.size(), idx.data(), sets.size(), &ok,
+                                                          sres.data(), nullptr, draw, &u)
+            : mbls_verify_multiple_shared_msgs_rng(detail::ctx(), sigs.data(), apks.data(), msgs.data(), 0, moff.data(), index.size(), idx.data(), sets.size(), &ok, draw, &u);
         if (u.err) std::rethrow_exception(u.err);
         detail::check(rc);
+        if (per_set) per_set->assign(sres.begin(), sres.end());
         return ok == 1;
     }
+public:
     // Not in the reference: what verify_multiple_aggregate_signatures(rng, batch) returns for every batch of `batches`, called once per batch in order -- as ONE
     // call (mbls_verify_multiple_batches_rng), for about the cost of one such call. One bool per batch; a bad batch rejects itself and nothing else. The scalars
     // are drawn in the order those calls would draw them (for every batch, the sets in front of its first signature outside G2): rng is left where they leave it.

@@ -128,6 +128,12 @@ def plan_verify_multiple_shared_msgs(n, n_msgs, mode=0, limits=None):
     return {f: getattr(vp_, f) for f, _ in VmSharedMsgsPlan._fields_ if f != "reserved"}
 
 
+def plan_verify_multiple_shared_msgs_locate_workspace_items(n, n_msgs, mode=0, limits=None):
+    """workspace items a mbls_verify_multiple*_shared_msgs_locate* call of n sets over n_msgs messages reserves under grouping `mode` (pure: no GPU)"""
+    L = limits if limits is not None else default_limits()
+    return int(lib().mbls_plan_verify_multiple_shared_msgs_locate_workspace_items(C.byref(L), n, n_msgs, mode))
+
+
 def plan_verify_multiple_shared_msgs_workspace_items(n, n_msgs, mode=0, limits=None):
     """workspace items such a call reserves (pure: no GPU; 0 for arguments the plan refuses)"""
     L = limits if limits is not None else default_limits()
@@ -260,6 +266,12 @@ SIGNATURES = {
     "mbls_verify_multiple_batches_indexed_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp, vp]),
     "mbls_verify_multiple_batches": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp]),
     "mbls_verify_multiple_batches_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, SCALAR_SOURCE, vp]),
+    "mbls_plan_verify_multiple_shared_msgs_locate_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64, C.c_int]),
+    "mbls_verify_multiple_shared_msgs_locate_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp, vp]),
+    "mbls_verify_multiple_sets_indexed_shared_msgs_locate_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp,
+                                                                              vp, vp, vp]),
+    "mbls_verify_multiple_shared_msgs_locate": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+    "mbls_verify_multiple_shared_msgs_locate_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, SCALAR_SOURCE, vp]),
     "mbls_plan_locate_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64]),
     "mbls_verify_multiple_batches_locate_device": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp,
                                                              vp, vp, vp]),

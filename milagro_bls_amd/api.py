@@ -335,9 +335,21 @@ class AggregateSignature:
         bool, `rng` left in the same state -- for batches whose sets share messages (a slot's gossip: tens of thousands of sets over a few hundred signing
         roots). The messages are deduplicated here by their bytes, and ONE call (mbls_verify_multiple_shared_msgs_rng) hashes each distinct message once and,
         where it pays, walks one Miller loop per message instead of one per set. The scalars are drawn as there, in the reference's order."""
+        return AggregateSignature._vm_shared(rng, signature_sets, False)
+
+    @staticmethod
+    def verify_multiple_aggregate_signatures_shared_msgs_locate(rng, signature_sets):
+        """verify_multiple_aggregate_signatures_shared_msgs, and in the same call (mbls_verify_multiple_shared_msgs_locate_rng) which sets of a rejected call are
+        the bad ones. Returns (bool, list[bool]). Every set of an accepted call reads True -- a passing batch is not examined set by set. A set of a rejected
+        call reads what the one-set call with its scalar returns; a set at or behind the first signature outside G2 has no scalar (the reference never draws
+        one) and reads False. The messages are deduplicated as there, and `rng` is left exactly where that method leaves it."""
+        return AggregateSignature._vm_shared(rng, signature_sets, True)
+
+    @staticmethod
+    def _vm_shared(rng, signature_sets, locate):
         sets = list(signature_sets)
         if not sets:
-            return True
+            return (True, []) if locate else True
         failed = []
 
         def draw(_user, out, count):                    # src/aggregates.rs:280-287, as verify_multiple_aggregate_signatures draws
@@ -367,11 +379,18 @@ class AggregateSignature:
         cb = N.SCALAR_SOURCE(draw)
         res = N.outbuf(1)
         ctx = _ctx()
-        ctx.check(N.lib().mbls_verify_multiple_shared_msgs_rng(ctx.handle, N.cbuf(b"".join(s[0].point for s in sets)), N.cbuf(b"".join(s[1].point for s in sets)),
-                                                               N.cbuf(b"".join(listed)), 0, moff, len(listed), midx, len(sets), res, cb, None))
+        S, A, M = N.cbuf(b"".join(s[0].point for s in sets)), N.cbuf(b"".join(s[1].point for s in sets)), N.cbuf(b"".join(listed))
+        if locate:
+            sres = N.outbuf(len(sets))
+            rc = N.lib().mbls_verify_multiple_shared_msgs_locate_rng(ctx.handle, S, A, M, 0, moff, len(listed), midx, len(sets), res, sres, None, cb, None)
+        else:
+            rc = N.lib().mbls_verify_multiple_shared_msgs_rng(ctx.handle, S, A, M, 0, moff, len(listed), midx, len(sets), res, cb, None)
+        ctx.check(rc)
         if failed:
             raise failed[0]
-        return bool(bytes(res)[0])
+        if not locate:
+            return bool(bytes(res)[0])
+        return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:len(sets)]]
 
     @staticmethod
     def verify_multiple_aggregate_signatures_batches(rng, batches):

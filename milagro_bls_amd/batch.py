@@ -507,3 +507,56 @@ def verify_multiple_sets_indexed_shared_msgs_device(table, d_sigs, d_key_idx, d_
     ctx = ctx or table.ctx
     ctx.check(N.lib().mbls_verify_multiple_sets_indexed_shared_msgs_device(ctx.handle, table.handle, d_sigs, d_key_idx, d_offsets, k, d_msgs, msg_len, d_msg_offsets, n_msgs,
                                                                            d_msg_idx, d_rands, n, d_result, d_status, stream))
+
+
+# ---- which sets of a rejected call over a shared message list (include/mbls.h, mbls_verify_multiple*_shared_msgs_locate*)
+plan_verify_multiple_shared_msgs_locate_workspace_items = N.plan_verify_multiple_shared_msgs_locate_workspace_items
+
+
+def verify_multiple_shared_msgs_locate(sigs, apks, msgs, n_msgs, msg_idx, rands, n, msg_len=32, msg_offsets=None, ctx=None):
+    """verify_multiple_shared_msgs, and in the same call one answer per SET (mbls_verify_multiple_shared_msgs_locate): every set of an accepted call reads True (a
+    passing batch is not examined), every set of a rejected call reads what the one-set call with its scalar and its message spelled out returns. Returns
+    (bool, status word, set_results, set_status)."""
+    ctx = ctx or _c()
+    res = N.outbuf(1)
+    st = C.c_uint32(0)
+    sres = N.outbuf(max(1, n))
+    sst = (C.c_uint32 * max(1, n))()
+    r = None if rands is None else (C.c_uint64 * max(1, n))(*rands)
+    ctx.check(N.lib().mbls_verify_multiple_shared_msgs_locate(ctx.handle, N.cbuf(sigs), N.cbuf(apks), N.cbuf(msgs), msg_len, _moff(msg_offsets), n_msgs, _midx(msg_idx, n),
+                                                              r, n, res, C.byref(st), sres, sst))
+    return bool(bytes(res)[0]), st.value, [bool(x) for x in bytes(sres)[:n]], list(sst)[:n]
+
+
+def verify_multiple_shared_msgs_locate_rng(sigs, apks, msgs, n_msgs, msg_idx, n, draw, msg_len=32, msg_offsets=None, ctx=None):
+    """The same with the reference's draw order (mbls_verify_multiple_shared_msgs_locate_rng; draw as verify_multiple_shared_msgs_rng takes it). A set at or behind
+    the first signature outside G2 has no scalar and reads False. Returns (bool, set_results, set_status)."""
+    ctx = ctx or _c()
+    res = N.outbuf(1)
+    sres = N.outbuf(max(1, n))
+    sst = (C.c_uint32 * max(1, n))()
+
+    def source(_user, out, count):
+        for i, v in enumerate(draw(int(count))):
+            out[i] = v
+    cb = N.SCALAR_SOURCE(source)
+    ctx.check(N.lib().mbls_verify_multiple_shared_msgs_locate_rng(ctx.handle, N.cbuf(sigs), N.cbuf(apks), N.cbuf(msgs), msg_len, _moff(msg_offsets), n_msgs,
+                                                                  _midx(msg_idx, n), n, res, sres, sst, cb, None))
+    return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:n]], list(sst)[:n]
+
+
+def verify_multiple_shared_msgs_locate_device(d_sigs, d_apks, d_msgs, n_msgs, d_msg_idx, d_rands, n, d_result, d_set_results, d_status=None, d_set_status=None, msg_len=32,
+                                              d_msg_offsets=None, stream=None, ctx=None):
+    """The same over device buffers, as verify_multiple_shared_msgs_device: n result bytes at d_set_results (required), n status words at d_set_status (optional).
+    Enqueues only."""
+    ctx = ctx or _c()
+    ctx.check(N.lib().mbls_verify_multiple_shared_msgs_locate_device(ctx.handle, d_sigs, d_apks, d_msgs, msg_len, d_msg_offsets, n_msgs, d_msg_idx, d_rands, n, d_result,
+                                                                     d_status, d_set_results, d_set_status, stream))
+
+
+def verify_multiple_sets_indexed_shared_msgs_locate_device(table, d_sigs, d_key_idx, d_msgs, n_msgs, d_msg_idx, d_rands, n, d_result, d_set_results, d_status=None,
+                                                           d_set_status=None, k=0, d_offsets=None, msg_len=32, d_msg_offsets=None, stream=None, ctx=None):
+    """The same over sets named by indices into a resident KeyTable. Enqueues only."""
+    ctx = ctx or table.ctx
+    ctx.check(N.lib().mbls_verify_multiple_sets_indexed_shared_msgs_locate_device(ctx.handle, table.handle, d_sigs, d_key_idx, d_offsets, k, d_msgs, msg_len, d_msg_offsets,
+                                                                                  n_msgs, d_msg_idx, d_rands, n, d_result, d_status, d_set_results, d_set_status, stream))

@@ -22,6 +22,7 @@
 #include "mbls_vmb.h"
 #include "mbls_vml.h"
 #include "mbls_vms.h"
+#include "mbls_vsl.h"
 #include "../../include/mbls.h"
 
 // The product library exists only with the generated routines: the host side below selects kernels (the fused subgroup verdict of
@@ -791,6 +792,50 @@ __global__ void MBLS_LB k_vml_final2(mbls_ws ws, const uint32_t* st_set, const u
     lane_final2<true>(ws, i, &st, &r, (MBLS_LDS uint32_t*)accstore, threadIdx.x);
     if ((t & 1) == 0) { set_results[i] = r; if (set_status) set_status[i] = st; }
 #endif
+}
+// ---- which sets of a rejected call over a shared message list (mbls_verify_multiple*_shared_msgs_locate*). The per-set route has a Miller value per set and is
+// the scheme above with the call as the one batch. The GROUPED route never computes f_i = ML([r_i] apk_i, H(m_i)) -- one value per message exists --, its heads
+// and trees overwrite the sets' blinded keys and the signatures' tree their slot S: each set gets TWO shadow items behind everything phase one uses (mbls_vsl.h),
+// A(i) = sh + i for the pair (H(m_i), [r_i] apk_i) and B(i) = sh + n + i for ([r_i] sig_i, -G1; k_vml_keep_sig), and phase two walks both pairs' Miller loops.
+// behind k_blind_g1_d, before the scatter's positions are summed and the heads written: set i's [r_i] apk_i (slot APK, Jacobian) -> slot APK of A(i)
+__global__ void MBLS_LB k_vsl_keep_key(mbls_ws ws, uint64_t n, uint64_t sh) {
+    const uint64_t i = gid(); if (i >= n) return;
+    const uint32_t* src = ws.w + (uint64_t)MBLS_SLOT_APK * 12 * ws.stride + i;
+    uint32_t* dst = ws.w + (uint64_t)MBLS_SLOT_APK * 12 * ws.stride + sh + i;
+#pragma unroll 12
+    for (int w = 0; w < 36; w++) dst[(uint64_t)w * ws.stride] = src[(uint64_t)w * ws.stride];
+}
+// after the call's tail, one lane per set (wsa = the workspace seen from A(0)): the answer of every set that needs no pairing and the candidate flags (the
+// rule: mbls_vsl.h vsl_mark -- the call's verdict, the set's own word, the bad-range flag of the message the set names, looked up through msg_idx[i]). A
+// candidate names a sound message of the list: its point goes from the table to slot H of A(i) (lane_h_gather), which completes the pair.
+__global__ void MBLS_LB k_vsl_mark(mbls_ws wsa, const uint32_t* tab, uint64_t tstride, const uint32_t* flags, const uint32_t* msg_idx, uint64_t n_msgs, uint64_t n,
+                                   const uint32_t* st_set, const uint8_t* call_result, uint32_t* cand, uint8_t* set_results, uint32_t* set_status) {
+    const uint64_t i = gid(); if (i >= n) return;
+    const uint32_t j = msg_idx[i];
+    uint32_t st;
+    const uint32_t v = vsl_mark(call_result[0] != 0, st_set[i], j, n_msgs, flags, &st);
+    cand[i] = v == MBLS_VML_CANDIDATE ? 1u : 0u;
+    set_results[i] = v == MBLS_VML_TRUE ? 1 : 0;                  // (a candidate stays 0 until its own check has spoken: fail closed)
+    if (set_status) set_status[i] = st;
+    if (v == MBLS_VML_CANDIDATE) (void)lane_h_gather(wsa, i, tab, tstride, flags, j, n_msgs);
+}
+// the Miller loops of the candidates' shadow pairs, ONE launch over the shadow items -- 2 n on the grouped route, both pairs of every set; n on the per-set
+// route -- (wv = the workspace seen from the launch's first item, which is item `first` of the shadows; cnt items): k_miller_single's and k_miller_single2's
+// body, the flag read at the item's set (vsl_shadow_set)
+template <int LPP> MBLS_FN void vsl_miller_body(const mbls_ws& wv, uint64_t cnt, uint64_t first, uint64_t n, const uint32_t* cand, uint32_t* spill) {
+    const uint64_t t = LPP == 2 ? gid() >> 1 : gid();
+    const bool on = t < cnt && cand[vsl_shadow_set(first + t, n)] != 0;
+    if (!__ballot(on)) return;
+    if (!on) return;
+    miller_single_body<LPP>(wv, cnt, 0, 0, spill);
+}
+__global__ void MBLS_LB k_vsl_miller(mbls_ws wv, uint64_t cnt, uint64_t first, uint64_t n, const uint32_t* cand) {
+    __shared__ uint32_t spill[154 * 64];
+    vsl_miller_body<1>(wv, cnt, first, n, cand, spill);
+}
+__global__ void MBLS_LB k_vsl_miller2(mbls_ws wv, uint64_t cnt, uint64_t first, uint64_t n, const uint32_t* cand) {
+    __shared__ uint32_t spill[154 * 64];
+    vsl_miller_body<2>(wv, cnt, first, n, cand, spill);
 }
 // verify_multiple over several devices ("one exchange step"): what one shard contributes is the product of its
 // sets' Miller values (slot F of item 0), its sum of blinded signatures (slot S of item 0) and the OR of its status words -- a
@@ -2837,8 +2882,9 @@ static void launch_miller_single(mbls_ctx* c, mbls_ws ws, uint64_t m, hipStream_
     else hipLaunchKernelGGL(k_miller_single, dim3(nblk(rest)), dim3(WG), 0, s, wr, rest, 0, (uint64_t)0);
 }
 static int npairing_finish(mbls_ctx* c, uint64_t n, hipStream_t s, uint8_t* d_result, hipEvent_t s_miller_ev = nullptr, bool late_status = false,
-                           uint32_t* d_partial = nullptr, bool side_s_chain = false, uint64_t n_sets = 0) {
+                           uint32_t* d_partial = nullptr, bool side_s_chain = false, uint64_t n_sets = 0, uint64_t keep_f_at = 0) {
     // n_sets (grouped shared-message route): the n Miller items are the MESSAGES; the signatures' sum tree and the status fold still cover all n_sets sets
+    // keep_f_at (locate calls on the per-set route): the first shadow item -- the sets' Miller values are copied there before the product tree runs over them
     const uint64_t ns = n_sets ? n_sets : n;
     const bool s_miller_done = s_miller_ev != nullptr || side_s_chain;
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
@@ -2846,6 +2892,7 @@ static int npairing_finish(mbls_ctx* c, uint64_t n, hipStream_t s, uint8_t* d_re
         coop_run(c, COOP_MILLER1, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, n, (uint32_t*)nullptr, (uint8_t*)nullptr, COOP_RES_ITEM, s);
     else
         launch_miller_single(c, ws, n, s);
+    if (keep_f_at) hipLaunchKernelGGL(k_vml_keep_f, dim3(nblk(n)), dim3(WG), 0, s, ws, n, keep_f_at);
     if (side_s_chain) {
         HIPCHK(c, hipEventRecord(c->hs_ev2, s)); HIPCHK(c, hipStreamWaitEvent(c->hs_b, c->hs_ev2, 0));
         g2_tree(c, ws, ns, c->hs_b);
@@ -2861,6 +2908,29 @@ static int npairing_finish(mbls_ctx* c, uint64_t n, hipStream_t s, uint8_t* d_re
     else coop_run(c, s_miller_done ? COOP_VMFINAL : COOP_VMTAIL, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, (uint64_t)1, c->d_scalar, d_result, COOP_RES_BATCH, s);
     HIPCHK(c, hipGetLastError());
     return MBLS_OK;
+}
+// Phase two of mbls_verify_multiple*_shared_msgs_locate* behind the mark kernel: the candidates' verdicts (cand[i]: set i is examined; st_set[i]: its own word).
+// The Miller loops walk the m shadow items from item sh on in ONE launch, cut at rounds and put on lane pairs exactly as launch_miller_single decides for m
+// items; then item i of the view wp takes the product with its partner i + half (a tree level), and a final exponentiation per candidate reads it.
+//   per-set route: m = n shadows ([r_i] sig_i, -G1); wp = the workspace, half = sh: f_i (moved back to item i by k_vml_mark) times g_i
+//   grouped route: m = 2 n shadows, A(i) = sh + i: (H(m_i), [r_i] apk_i), B(i) = sh + n + i: ([r_i] sig_i, -G1); wp = the view from A(0), half = n
+static void vsl_examine(mbls_ctx* c, mbls_ws ws, uint64_t n, uint64_t sh, bool grouped, const uint32_t* st_set, const uint32_t* cand, uint8_t* d_set_results,
+                        uint32_t* d_set_status, hipStream_t s) {
+    const uint64_t R = c->round_items, m = grouped ? 2 * n : n;
+    const uint64_t full = m > R ? (m / R) * R : 0, rest = m - full;
+    mbls_ws wsh = ws; wsh.w += sh;
+    if (full) hipLaunchKernelGGL(k_vsl_miller, dim3(nblk(full)), dim3(WG), 0, s, wsh, full, (uint64_t)0, n, cand);
+    if (rest) {
+        mbls_ws wr = wsh; wr.w += full;
+        if (2 * rest <= R) hipLaunchKernelGGL(k_vsl_miller2, dim3(nblk(2 * rest)), dim3(WG), 0, s, wr, rest, full, n, cand);
+        else hipLaunchKernelGGL(k_vsl_miller, dim3(nblk(rest)), dim3(WG), 0, s, wr, rest, full, n, cand);
+    }
+    const mbls_ws wp = grouped ? wsh : ws;
+    hipLaunchKernelGGL(k_vml_product, dim3(nblk(n)), dim3(WG), 0, s, wp, n, grouped ? n : sh, cand);
+    if (n <= c->split_max_items && 2 * n <= c->round_items)
+        hipLaunchKernelGGL(k_vml_final2, dim3(nblk(2 * n)), dim3(WG), 0, s, wp, st_set, cand, d_set_results, d_set_status, n);
+    else
+        hipLaunchKernelGGL(k_vml_final, dim3(nblk(n)), dim3(WG), 0, s, wp, st_set, cand, d_set_results, d_set_status, n);
 }
 extern "C" int mbls_aggregate_verify(mbls_ctx* c, const uint8_t sig[96], const uint8_t* msgs, const size_t* msg_lens, size_t n_msgs,
                                      const uint8_t* pks96, size_t n_pks) {
@@ -3008,6 +3078,9 @@ struct vm_shared {
     uint64_t longest = 0;              // the longest group where the host has counted it (host entries); 0: a device-side index table
     mbls_shared_msgs_plan sp;          // the list hash (plan_shared)
     mbls_vm_shared_msgs_plan vp;       // the route (plan_vm_shared)
+    // the _locate entries: the sets' answers as well (d_set_results required, d_set_status optional), shadow items behind phase one's workspace (mbls_vsl.h)
+    bool locate = false; uint8_t* d_set_results = nullptr; uint32_t* d_set_status = nullptr;
+    uint64_t shadow_first = 0;         // (set by vm_shared_plan_and_reserve)
 };
 // the message phase of the shared-message entries on stream s_msg: the list is hashed once into the context's table (the existing path of section 5d); the
 // per-set route then gives every set its point (k_h_gather), the grouped route reads the table from its Miller items (k_vms_heads)
@@ -3021,7 +3094,9 @@ static int vm_shared_message_phase(mbls_ctx* c, mbls_ws ws, const vm_shared& sh,
 static int vm_shared_plan_and_reserve(mbls_ctx* c, vm_shared& sh, uint64_t n) {
     plan_shared(ctx_limits(c), n, sh.n_msgs, false, false, &sh.sp);
     plan_vm_shared(ctx_limits(c), n, sh.n_msgs, c->vm_grouping, sh.longest, &sh.vp);
-    int rc = mbls_ctx_reserve(c, sh.vp.workspace_items); if (rc) return rc;
+    const bool grouped = sh.vp.route == MBLS_VM_ROUTE_GROUPED;
+    sh.shadow_first = vsl_shadow_first(n, sh.n_msgs, grouped, sh.sp.list_workspace_items);
+    int rc = mbls_ctx_reserve(c, sh.locate ? vsl_workspace_items(n, sh.n_msgs, grouped, sh.sp.list_workspace_items) : sh.vp.workspace_items); if (rc) return rc;
     return reserve_msgs(c, sh.n_msgs);
 }
 static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_pks, int pk_format,
@@ -3053,8 +3128,16 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
     int rc = sh ? vm_shared_plan_and_reserve(c, *sh, n) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
     const bool grouped = sh && sh->vp.route == MBLS_VM_ROUTE_GROUPED;
     const uint64_t n_miller = grouped ? sh->vp.miller_items : n;
+    const bool loc = sh && sh->locate;
+    const uint64_t shf = loc ? sh->shadow_first : 0;                // locate mode: the first shadow item; the candidate flags (cap >= 2 n words)
+    uint32_t* const cand = c->d_status + vsl_flags_first(n);
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     rc = ws_acquire(c, s); if (rc) return rc;
+    if (loc) {
+        HIPCHK(c, hipMemsetAsync(sh->d_set_results, 0, n, s));      // fail closed
+        if (sh->d_set_status) HIPCHK(c, hipMemsetAsync(sh->d_set_status, 0, 4 * n, s));
+        HIPCHK(c, hipMemsetAsync(cand, 0, 4 * n, s));
+    }
     HIPCHK(c, hipMemsetAsync(c->d_scalar, 0, 64, s));
     if (!sigs_resident) HIPCHK(c, hipMemsetAsync(c->d_status, 0, 4 * n, s));      // (resident: cleared before k_sig, and the message phase may be writing its bits)
     if (d_partial) HIPCHK(c, hipMemsetAsync(d_partial, 0, MBLS_VM_PARTIAL_BYTES, s));       // not a record until k_vm_export has spoken
@@ -3089,6 +3172,7 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
         HIPCHK(c, hipMemsetAsync(g_cnt, 0, 4 * (M + 1), s)); HIPCHK(c, hipMemsetAsync(g_cur, 0, 4 * (M + 1), s)); HIPCHK(c, hipMemsetAsync(c->d_vmap, 0xFF, 4 * n, s));
         hipLaunchKernelGGL(k_vms_count, dim3(nblk(n)), dim3(WG), 0, s, sh->d_midx, M, n, g_cnt, c->d_status);
         hipLaunchKernelGGL(k_vms_scan, dim3(1), dim3(MBLS_VMS_SCAN_LANES), 0, s, (const uint32_t*)g_cnt, M, g_off);
+        if (loc) hipLaunchKernelGGL(k_vsl_keep_key, dim3(nblk(n)), dim3(WG), 0, s, ws, n, shf);      // [r_i] apk_i -> A(i), before heads and trees run over the sets' items
         hipLaunchKernelGGL(k_vms_scatter, dim3(nblk(n)), dim3(WG), 0, s, ws, sh->d_midx, M, n, (const uint32_t*)g_off, g_cur, c->d_vmap, pbase);
         mbls_ws wp = ws; wp.w += pbase;
         uint64_t half = 1;
@@ -3100,6 +3184,8 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
         hipLaunchKernelGGL(k_blind_sig2_d, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, c->d_status, n);
     else
         hipLaunchKernelGGL(k_blind_sig_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, c->d_status, n);
+    // locate mode: ([r_i] sig_i, -G1) -> the set's shadow item (grouped: B(i)), before the sum tree runs over slot S
+    if (loc) hipLaunchKernelGGL(k_vml_keep_sig, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, n, grouped ? shf + n : shf);
     const bool side_s_chain = !fork && s != c->hs_b;                  // the sum tree waits for the product tree's company (npairing_finish)
     if (!side_s_chain) g2_tree(c, ws, n, s_sig);
     if (fork) {     // S is complete: its Miller loop runs on one wave beside the other chains and the sets' Miller loops (most SIMDs are idle)
@@ -3119,8 +3205,20 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
                            (const uint32_t*)c->d_hflag, (const uint32_t*)g_off, (const uint32_t*)g_cnt, sh->n_msgs, n_miller, pbase, c->d_scalar);
     // a set whose signature is outside G2 (reference src/aggregates.rs:274-276), an undecodable member or a zero scalar makes the tail
     // answer false: the status bits are folded in on the device, the call only enqueues
-    rc = npairing_finish(c, n_miller, s, d_result, fork ? c->hs_ev : nullptr, fork, d_partial, side_s_chain, n); if (rc) return rc;
+    rc = npairing_finish(c, n_miller, s, d_result, fork ? c->hs_ev : nullptr, fork, d_partial, side_s_chain, n, loc && !grouped ? shf : 0); if (rc) return rc;
     if (d_status_or) HIPCHK(c, hipMemcpyAsync(d_status_or, c->d_scalar, 4, hipMemcpyDeviceToDevice, s));
+    if (loc && grouped) {      // phase two, enqueued whatever the verdict is: mark through msg_idx (candidates get their H), both pairs' Miller loops, product, final
+        mbls_ws wsa = ws; wsa.w += shf;
+        hipLaunchKernelGGL(k_vsl_mark, dim3(nblk(n)), dim3(WG), 0, s, wsa, (const uint32_t*)c->d_htab, c->htab_cap, (const uint32_t*)c->d_hflag, sh->d_midx, sh->n_msgs, n,
+                           (const uint32_t*)c->d_status, (const uint8_t*)d_result, cand, sh->d_set_results, sh->d_set_status);
+        vsl_examine(c, ws, n, shf, true, c->d_status, cand, sh->d_set_results, sh->d_set_status, s);
+        HIPCHK(c, hipGetLastError());
+    } else if (loc) {          // the per-set route: the scheme of mbls_verify_multiple_batches_locate* with the call as the one batch that owns every set
+        hipLaunchKernelGGL(k_vml_mark, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)n, (uint64_t)1, n,
+                           (const uint32_t*)c->d_status, (const uint32_t*)nullptr, (const uint8_t*)d_result, cand, sh->d_set_results, sh->d_set_status, shf);
+        vsl_examine(c, ws, n, shf, false, c->d_status, cand, sh->d_set_results, sh->d_set_status, s);
+        HIPCHK(c, hipGetLastError());
+    }
     return ws_release(c, s);
 }
 // verify_multiple over sets named by indices into a resident key table (the deployment's form: validator keys are decoded once, a set is a list of
@@ -3293,14 +3391,17 @@ extern "C" int mbls_verify_multiple_aggregate_signatures_rng(mbls_ctx* c, const 
 // a list that is hashed once. Grouped route: one Miller loop per message (the kernels of the k_vms_* family, mbls_vms.h); per-set route: every set gathers its point.
 static int vm_shared_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint8_t* d_apks, const uint32_t* d_key_idx, const uint32_t* d_offsets, uint32_t k,
                             const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n,
-                            uint8_t* d_result, uint32_t* d_status_or, void* stream, uint64_t longest) {
+                            uint8_t* d_result, uint32_t* d_status_or, void* stream, uint64_t longest, bool locate = false, uint8_t* d_set_results = nullptr,
+                            uint32_t* d_set_status = nullptr) {
     if (!c || !d_result) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
+    if (locate && !d_set_results) ARGFAIL(c, "null set results");
     if (n && !(t ? (const void*)d_key_idx : (const void*)d_apks)) ARGFAIL(c, "null key buffer");
     if (t && t->c != c) ARGFAIL(c, "key table belongs to another context");
     if (n && !d_midx) ARGFAIL(c, "null buffer");
     if (n_msgs > 0xFFFFFFFFull || n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
     vm_shared sh; sh.n_msgs = n_msgs; sh.d_midx = d_midx; sh.longest = longest;
+    sh.locate = locate; sh.d_set_results = d_set_results; sh.d_set_status = d_set_status;
     return verify_multiple_impl(c, d_sigs, t ? nullptr : d_apks, nullptr, MBLS_PK_UNCOMPRESSED, t ? d_offsets : nullptr, t ? k : 0, d_msgs, msg_len, d_moff, d_rands, n, d_result,
                                 d_status_or, stream, nullptr, t, t ? d_key_idx : nullptr, false, false, &sh);
 }
@@ -3332,10 +3433,13 @@ static int vm_shared_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_
     *longest = m;
     return MBLS_OK;
 }
-extern "C" int mbls_verify_multiple_shared_msgs(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
-        uint64_t n_msgs, const uint32_t* msg_idx, const uint64_t* rands, uint64_t n, uint8_t* result, uint32_t* status) {
+// locate: the sets' answers as well (set_results required, set_status optional), staged behind one another in one buffer: n words, then n bytes
+static int vm_shared_host_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        uint64_t n_msgs, const uint32_t* msg_idx, const uint64_t* rands, uint64_t n, uint8_t* result, uint32_t* status, bool locate, uint8_t* set_results,
+        uint32_t* set_status) {
     if (!c || !result) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
+    if (locate && !set_results) ARGFAIL(c, "null set results");
     if (n == 0) { *result = 1; if (status) *status = 0; return MBLS_OK; }
     if (!rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
     uint64_t longest = 0;
@@ -3343,26 +3447,41 @@ extern "C" int mbls_verify_multiple_shared_msgs(mbls_ctx* c, const uint8_t* sigs
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t msg_first = moff ? moff[0] : 0;
     const size_t msg_total = moff ? (size_t)(moff[n_msgs] - moff[0]) : (size_t)msg_len * n_msgs;
-    sbuf ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dmo(c, 6), dres(c, 4), dmi(c, 7);
+    sbuf ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dmo(c, 6), dres(c, 4), dmi(c, 7), dset(c, 8);
     HIPCHK(c, ds.up(sigs96, 96 * n)); HIPCHK(c, da.up(apks96, 96 * n)); HIPCHK(c, dm.up(msgs ? msgs + msg_first : nullptr, msg_total)); HIPCHK(c, dr.up(rands, 8 * n));
     HIPCHK(c, dmi.up(msg_idx, 4 * n)); HIPCHK(c, dres.alloc(8));
     if (moff) HIPCHK(c, dmo.up(moff, 8 * (n_msgs + 1)));
+    uint32_t* d_sst = nullptr; uint8_t* d_sres = nullptr;
+    if (locate) { HIPCHK(c, dset.alloc(5 * n)); d_sst = dset.as<uint32_t>(); d_sres = dset.as<uint8_t>() + 4 * n; }
     rc = vm_shared_device(c, nullptr, ds.as<uint8_t>(), da.as<uint8_t>(), nullptr, nullptr, 0, dm.as<uint8_t>() - msg_first, msg_len, moff ? dmo.as<uint64_t>() : nullptr, n_msgs,
-                          dmi.as<uint32_t>(), dr.as<uint64_t>(), n, dres.as<uint8_t>(), dres.as<uint32_t>() + 1, c->hs_a, longest);
+                          dmi.as<uint32_t>(), dr.as<uint64_t>(), n, dres.as<uint8_t>(), dres.as<uint32_t>() + 1, c->hs_a, longest, locate, d_sres, d_sst);
     if (rc) { vm_rng_drain(c); return rc; }
     HIPCHK(c, hipStreamSynchronize(c->hs_a));
     c->ws_pending = false;
     uint32_t out[2] = {0, 0};
     HIPCHK(c, dres.down(out, 8));
+    if (locate) {
+        HIPCHK(c, hipMemcpy(set_results, d_sres, n, hipMemcpyDeviceToHost));
+        if (set_status) HIPCHK(c, hipMemcpy(set_status, d_sst, 4 * n, hipMemcpyDeviceToHost));
+    }
     *result = (uint8_t)(out[0] & 0xFF); if (status) *status = out[1];
     return MBLS_OK;
 }
+extern "C" int mbls_verify_multiple_shared_msgs(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        uint64_t n_msgs, const uint32_t* msg_idx, const uint64_t* rands, uint64_t n, uint8_t* result, uint32_t* status) {
+    return vm_shared_host_impl(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, rands, n, result, status, false, nullptr, nullptr);
+}
 // the reference's order, as mbls_verify_multiple_aggregate_signatures_rng keeps it (vm_rng_phase1 / vm_rng_phase2 with the list): signatures decoded and tested
 // first, `draw` called once for the sets in front of the first bad signature, no second subgroup test
-extern "C" int mbls_verify_multiple_shared_msgs_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
-        uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user) {
+// locate: the sets' answers as well. A set at or behind the first signature outside G2 has no scalar (the reference never draws one) and cannot be examined: its
+// answer is 0 and its word what the signature phase found, set on the host from the verdicts phase 1 read back. The sets in front of it have their scalars and
+// are judged one by one: the call goes on (it is rejected through its status bits whatever the product is) with the scalar 1 for the sets without one, which
+// changes nothing -- as mbls_verify_multiple_batches_locate_rng does.
+static int vm_shared_rng_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user, bool locate, uint8_t* set_results, uint32_t* set_status) {
     if (!c || !result) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
+    if (locate && !set_results) ARGFAIL(c, "null set results");
     if (n == 0) { *result = 1; return MBLS_OK; }                            // empty iterator: true, the generator untouched
     if (!draw) ARGFAIL(c, "no scalar source");
     vm_shared sh; sh.n_msgs = n_msgs;
@@ -3370,12 +3489,19 @@ extern "C" int mbls_verify_multiple_shared_msgs_rng(mbls_ctx* c, const uint8_t* 
     std::vector<uint64_t> rands; std::vector<uint32_t> st;
     try { rands.resize(n); st.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
     vm_rng_stage g(c);
+    sbuf dset(c, 8);
+    if (locate) {       // (the workspace of the WHOLE call, shadows included, is reserved by phase 1: growing it later would lose the decoded signatures)
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, dset.alloc(5 * n));
+        sh.locate = true; sh.d_set_status = dset.as<uint32_t>(); sh.d_set_results = dset.as<uint8_t>() + 4 * n;
+    }
     rc = vm_rng_phase1(c, g, sigs96, apks96, msgs, msg_len, moff, n, 8, st.data(), &sh, msg_idx); if (rc) return rc;
     size_t reached = n;                                                     // the sets the reference's loop draws a scalar for
     for (size_t i = 0; i < n; i++)
         if (st[i] & (MBLS_ST_BAD_SIG_ENCODING | MBLS_ST_SIG_NOT_IN_G2)) { reached = i; break; }
     if (reached) draw(user, rands.data(), (uint64_t)reached);
-    if (reached < n) { vm_rng_drain(c); *result = 0; return MBLS_OK; }     // src/aggregates.rs:273-275
+    if (reached < n && !locate) { vm_rng_drain(c); *result = 0; return MBLS_OK; }     // src/aggregates.rs:273-275
+    for (size_t i = reached; i < n; i++) rands[i] = 1;
     rc = vm_rng_phase2(c, g, msg_len, rands.data(), n, false, &sh);
     std::fill(rands.begin(), rands.end(), 0);
     if (rc) { vm_rng_drain(c); return rc; }
@@ -3383,8 +3509,48 @@ extern "C" int mbls_verify_multiple_shared_msgs_rng(mbls_ctx* c, const uint8_t* 
     c->ws_pending = false;
     uint8_t r = 0;
     HIPCHK(c, g.dout.down(&r, 1));
+    if (locate) {
+        HIPCHK(c, hipMemcpy(set_results, sh.d_set_results, n, hipMemcpyDeviceToHost));
+        if (set_status) HIPCHK(c, hipMemcpy(set_status, sh.d_set_status, 4 * n, hipMemcpyDeviceToHost));
+        for (size_t i = reached; i < n; i++) { set_results[i] = 0; if (set_status) set_status[i] = st[i]; }
+    }
     *result = r;
     return MBLS_OK;
+}
+extern "C" int mbls_verify_multiple_shared_msgs_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user) {
+    return vm_shared_rng_impl(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, n, result, draw, user, false, nullptr, nullptr);
+}
+// ---- which sets of a rejected call over a shared message list (include/mbls.h, mbls_verify_multiple*_shared_msgs_locate*): the entries above with one bool and
+// one status word per SET beside the call's own. Phase one is unchanged; the shadows, the mark rule and phase two are described at k_vsl_keep_key.
+extern "C" int mbls_verify_multiple_shared_msgs_locate_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_msgs, uint32_t msg_len,
+        const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status,
+        uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
+    if (!d_set_results) return MBLS_ERR_ARGUMENT;
+    return vm_shared_device(c, nullptr, d_sigs, d_apks, nullptr, nullptr, 0, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, true,
+                            d_set_results, d_set_status);
+}
+extern "C" int mbls_verify_multiple_sets_indexed_shared_msgs_locate_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx,
+        const uint32_t* d_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_msg_idx,
+        const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
+    if (!t || !d_set_results) return MBLS_ERR_ARGUMENT;
+    return vm_shared_device(c, t, d_sigs, nullptr, d_key_idx, d_offsets, k, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, true,
+                            d_set_results, d_set_status);
+}
+extern "C" int mbls_verify_multiple_shared_msgs_locate(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
+        uint64_t n_msgs, const uint32_t* msg_idx, const uint64_t* rands, uint64_t n, uint8_t* result, uint32_t* status, uint8_t* set_results, uint32_t* set_status) {
+    return vm_shared_host_impl(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, rands, n, result, status, true, set_results, set_status);
+}
+extern "C" int mbls_verify_multiple_shared_msgs_locate_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len,
+        const uint64_t* moff, uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw,
+        void* user) {
+    return vm_shared_rng_impl(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, n, result, draw, user, true, set_results, set_status);
+}
+// what a locate call over a shared list reserves before its first kernel: mbls_vsl.h's figure under the route and the list hash the limits choose
+extern "C" uint64_t mbls_plan_verify_multiple_shared_msgs_locate_workspace_items(const mbls_limits* limits, uint64_t n, uint64_t n_msgs, int mode) {
+    if (!limits || !n || mode < 0 || mode > 2) return 0;
+    mbls_vm_shared_msgs_plan vp; plan_vm_shared(*limits, n, n_msgs, mode, 0, &vp);
+    return vsl_workspace_items(n, n_msgs, vp.route == MBLS_VM_ROUTE_GROUPED, vp.list_workspace_items);
 }
 
 // ---- B independent verify_multiple batches in ONE call (include/mbls.h, mbls_verify_multiple_batches*): what B consecutive calls of the entries above return,

@@ -73,6 +73,24 @@ extern "C" {
     fn mbls_sig_check_batch(ctx: *mut MblsCtx, in96: *const u8, n: u64, errs: *mut u8, in_g2: *mut u8) -> c_int;
     fn mbls_verify_multiple_shared_msgs_rng(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
                                             n_msgs: u64, msg_idx: *const u32, n: u64, result: *mut u8, draw: MblsScalarSource, user: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_shared_msgs_locate_rng(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
+                                                   n_msgs: u64, msg_idx: *const u32, n: u64, result: *mut u8, set_results: *mut u8, set_status: *mut u32,
+                                                   draw: MblsScalarSource, user: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn mbls_verify_multiple_shared_msgs_locate(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
+                                               n_msgs: u64, msg_idx: *const u32, rands: *const u64, n: u64, result: *mut u8, status: *mut u32,
+                                               set_results: *mut u8, set_status: *mut u32) -> c_int;
+    #[allow(dead_code)]
+    fn mbls_verify_multiple_shared_msgs_locate_device(ctx: *mut MblsCtx, d_sigs96: *const u8, d_apks96: *const u8, d_msgs: *const u8, msg_len: u32,
+                                                      d_msg_offsets: *const u64, n_msgs: u64, d_msg_idx: *const u32, d_rands: *const u64, n: u64,
+                                                      d_result: *mut u8, d_status: *mut u32, d_set_results: *mut u8, d_set_status: *mut u32,
+                                                      stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn mbls_verify_multiple_sets_indexed_shared_msgs_locate_device(ctx: *mut MblsCtx, t: *const MblsKeyTable, d_sigs96: *const u8, d_key_idx: *const u32,
+                                                                   d_offsets: *const u32, k: u32, d_msgs: *const u8, msg_len: u32, d_msg_offsets: *const u64,
+                                                                   n_msgs: u64, d_msg_idx: *const u32, d_rands: *const u64, n: u64, d_result: *mut u8,
+                                                                   d_status: *mut u32, d_set_results: *mut u8, d_set_status: *mut u32,
+                                                                   stream: *mut c_void) -> c_int;
     fn mbls_verify_multiple_batches(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64,
                                     rands: *const u64, n_sets: u64, batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64, results: *mut u8,
                                     status: *mut u32) -> c_int;
@@ -602,10 +620,28 @@ impl AggregateSignature {
         R: Rng + ?Sized,
         I: Iterator<Item = (&'a AggregateSignature, &'a AggregatePublicKey, &'a [u8])>,
     {
+        Self::vm_shared(rng, signature_sets, false).0
+    }
+    /// The same, and in the same call (`mbls_verify_multiple_shared_msgs_locate_rng`) WHICH sets of a rejected call are the bad ones: the bool as above and
+    /// one bool per set. Every set of an accepted call reads `true` (a passing batch is not examined set by set); a set of a rejected call reads what the
+    /// one-set call with its scalar returns; a set at or behind the first signature outside G2 has no scalar (the reference never draws one) and reads
+    /// `false`. `rng` is left where `verify_multiple_aggregate_signatures_shared_msgs` leaves it. (Like the rest of this crate: source only, never compiled.)
+    pub fn verify_multiple_aggregate_signatures_shared_msgs_locate<'a, R, I>(rng: &mut R, signature_sets: I) -> (bool, Vec<bool>)
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, &'a AggregatePublicKey, &'a [u8])>,
+    {
+        Self::vm_shared(rng, signature_sets, true)
+    }
+    fn vm_shared<'a, R, I>(rng: &mut R, signature_sets: I, locate: bool) -> (bool, Vec<bool>)
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, &'a AggregatePublicKey, &'a [u8])>,
+    {
         let sets: Vec<(&AggregateSignature, &AggregatePublicKey, &[u8])> = signature_sets.collect();
         let n = sets.len();
         if n == 0 {
-            return true;
+            return (true, Vec::new());
         }
         let (mut sigs, mut apks, mut msgs) = (Vec::new(), Vec::new(), Vec::new());
         let mut moff: Vec<u64> = vec![0];
@@ -624,14 +660,21 @@ impl AggregateSignature {
         }
         let mut st = DrawState { rng, panic: None };
         let mut ok: u8 = 0;
+        let mut sres: Vec<u8> = vec![0; if locate { n } else { 0 }];
         let rc = unsafe {
-            mbls_verify_multiple_shared_msgs_rng(ctx(), sigs.as_ptr(), apks.as_ptr(), msgs.as_ptr(), 0, moff.as_ptr(), index.len() as u64, idx.as_ptr(), n as u64,
-                                                 &mut ok, draw_scalars::<R>, &mut st as *mut DrawState<R> as *mut c_void)
+            if locate {
+                mbls_verify_multiple_shared_msgs_locate_rng(ctx(), sigs.as_ptr(), apks.as_ptr(), msgs.as_ptr(), 0, moff.as_ptr(), index.len() as u64, idx.as_ptr(),
+                                                            n as u64, &mut ok, sres.as_mut_ptr(), std::ptr::null_mut(), draw_scalars::<R>,
+                                                            &mut st as *mut DrawState<R> as *mut c_void)
+            } else {
+                mbls_verify_multiple_shared_msgs_rng(ctx(), sigs.as_ptr(), apks.as_ptr(), msgs.as_ptr(), 0, moff.as_ptr(), index.len() as u64, idx.as_ptr(), n as u64,
+                                                     &mut ok, draw_scalars::<R>, &mut st as *mut DrawState<R> as *mut c_void)
+            }
         };
         if let Some(payload) = st.panic.take() {
             std::panic::resume_unwind(payload);
         }
-        rc == 0 && ok == 1
+        (rc == 0 && ok == 1, sres.iter().map(|&b| rc == 0 && b == 1).collect())
     }
     /// Not in the reference: what `verify_multiple_aggregate_signatures(rng, batch)` returns for every batch, called once per batch in order --
     /// as ONE call on the GPU (`mbls_verify_multiple_batches_rng`), for about the cost of one such call. One bool per batch; a bad batch rejects
