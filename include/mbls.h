@@ -218,7 +218,7 @@ int mbls_fast_aggregate_verify_batch_indexed(mbls_ctx* ctx, const mbls_keytable*
  * ALLOCATION: the hashed points live in a table of the context (288 bytes per message), and the list is hashed in the call's workspace: a call whose list is
  * larger than any before grows them first (which drains the device, see mbls_ctx_reserve). mbls_ctx_reserve_msgs(ctx, max_msgs) and
  * mbls_ctx_reserve(ctx, mbls_plan_shared_msgs_workspace_items(...)) beforehand keep every allocation out of the call.
- * Not covered: the verification stream and the mbls_multi handle take per-item messages only. */
+ * A list that outlives the call, for many calls and for the verification stream: the resident message table below (mbls_msgtable_*). */
 int mbls_ctx_reserve_msgs(mbls_ctx* ctx, uint64_t max_msgs);
 /* Routing as data (pure: no GPU, no context), beside mbls_plan_batch: `batch` is mbls_plan_batch(limits, n) with the message phase of every pass marked
  * MBLS_MESSAGE_GATHER; the list of n_msgs messages is hashed in list_pieces pieces of list_piece_items messages (the last may be shorter; a piece is at most one
@@ -257,6 +257,59 @@ int mbls_fast_aggregate_verify_batch_indexed_shared_msgs_device(mbls_ctx* ctx, c
 int mbls_fast_aggregate_verify_batch_indexed_shared_msgs(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
                                                          const uint64_t* msg_offsets, uint64_t n_msgs, const uint32_t* msg_idx, const uint32_t* key_idx,
                                                          const uint32_t* offsets, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status);
+
+/* ---- resident message table: hash a message once, verify against it in any call or stream ------------------
+ * The message side's key table. A slot's gossip arrives in hundreds of small calls over the same few hundred signing roots: the shared lists above hash a
+ * call's list once per CALL, this table hashes a message once. Entry first_index + j holds H(message j) -- the 72 dwords of the hashed point and the message's
+ * bad-range bit, exactly what a shared list's export writes -- and verifications name entries by index, in any later call, on any stream, and in a verification
+ * stream (mbls_stream_create_msgtable). Public indices start at 0 and never change; entries are never rewritten. The table keeps a private entry for the empty
+ * message: what an index that names nothing is checked against.
+ * APPEND hashes in the form the COUNT of appended messages asks for (the list rule of mbls_plan_batch_shared_msgs: pieces of at most one round; wave engine,
+ *   lane pairs or one lane per message), works in the context's workspace (ordered against its other users like any call; mbls_ctx_reserve beforehand keeps the
+ *   allocation out of it) and exports at first_index. Messages as everywhere: msg_len bytes each, or message j = msgs[msg_offsets[j] .. msg_offsets[j+1]) with
+ *   n + 1 offsets. The host form refuses a bad offset table with MBLS_ERR_ARGUMENT; in the device form a message whose range runs backwards or is 2^32 bytes or
+ *   more becomes a FLAGGED entry, which rejects exactly the items that name it, with MBLS_ST_BAD_MSG_RANGE. n = 0 is MBLS_OK with *first_index = size.
+ * ORDERING is the key table's: an append enqueued on one stream is seen by verifications, mbls_msgtable_get and later appends on any other stream (they wait
+ *   for it on the device).
+ * GROWTH. A table created with a sufficient capacity_hint (0: 1 024) never allocates again. Growth beyond it keeps every index and entry; it drains the device,
+ *   as mbls_ctx_reserve does (the layout is entry-major with stride = capacity + 1, so growth moves every entry: csrc/mbls_mtb.h).
+ * mbls_msgtable_get returns the compressed points of n entries in the format of mbls_hash_to_g2_batch; errs[i] = MBLS_ERR_ARGUMENT for a flagged entry.
+ * mbls_msgtable_clear blocks until everything enqueued that reads the table has finished, then sets the size to 0 and keeps the capacity (index 0 names the
+ *   next message appended). It is refused with MBLS_ERR_ARGUMENT (reason in mbls_last_error) while a stream bound to the table has calls that have not
+ *   completed. The intended use is two tables alternated per slot or epoch.
+ * LIFETIME. Destroy a table after the streams bound to it and before its context (a table whose context went first is an empty shell that only
+ *   mbls_msgtable_destroy accepts). A table of another context is refused everywhere.
+ * VERIFICATION ENTRIES. Each is its `_shared_msgs` neighbour with the list arguments (msgs, msg_len, msg_offsets, n_msgs) replaced by the table; msg_idx stays,
+ *   one uint32 per item. No list is hashed. ROUTING: mbls_plan_batch(limits, n) with the message phase of every pass MBLS_MESSAGE_GATHER -- that is
+ *   mbls_plan_batch_shared_msgs(limits, n, 0).batch --, in every plan shape; the workspace is mbls_plan_workspace_items. results[i], status[i] and the bitmap are
+ *   bit for bit what the per-item entry returns with item i's message spelled out. The table is read at the size it has when the call is enqueued: in the device
+ *   forms msg_idx[i] >= size (an empty table included) rejects item i with MBLS_ST_BAD_MSG_RANGE and result 0, checked against the empty message's point -- never
+ *   a read outside the table; the host forms refuse such an index with MBLS_ERR_ARGUMENT before anything is enqueued and leave the outputs unwritten.
+ * OUT OF SCOPE: verify_multiple over a resident table (the grouped route sizes its group arrays by the list), the mbls_multi handle, and device-side
+ *   deduplication (callers intern their messages on the host). */
+typedef struct mbls_msgtable mbls_msgtable;
+int mbls_msgtable_create(mbls_ctx* ctx, uint64_t capacity_hint, mbls_msgtable** out);
+void mbls_msgtable_destroy(mbls_msgtable* t);
+uint64_t mbls_msgtable_size(const mbls_msgtable* t);
+int mbls_msgtable_append(mbls_msgtable* t, const uint8_t* msgs, uint32_t msg_len, const uint64_t* msg_offsets, uint64_t n, uint64_t* first_index);
+int mbls_msgtable_append_device(mbls_msgtable* t, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_msg_offsets, uint64_t n, uint64_t* first_index,
+                                void* stream);
+int mbls_msgtable_get(mbls_msgtable* t, uint64_t first_index, uint64_t n, uint8_t* out96, uint8_t* errs);
+int mbls_msgtable_clear(mbls_msgtable* t);
+int mbls_fast_aggregate_verify_batch_msgtable_device(mbls_ctx* ctx, const uint8_t* d_sigs, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint8_t* d_pks,
+                                                     int pk_format, const uint32_t* d_pk_offsets, uint64_t n, uint32_t k, uint8_t* d_results, uint64_t* d_bitmap,
+                                                     uint32_t* d_status, void* stream);
+int mbls_fast_aggregate_verify_batch_msgtable(mbls_ctx* ctx, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx, const uint8_t* pks, int pk_format,
+                                              const uint32_t* pk_offsets, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status);
+int mbls_verify_batch_msgtable_device(mbls_ctx* ctx, const uint8_t* d_sigs, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint8_t* d_pks, int pk_format,
+                                      uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream);
+int mbls_verify_batch_msgtable(mbls_ctx* ctx, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx, const uint8_t* pks, int pk_format, uint64_t n,
+                               uint8_t* results, uint32_t* status);
+int mbls_fast_aggregate_verify_batch_indexed_msgtable_device(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* d_sigs, const mbls_msgtable* mt,
+                                                             const uint32_t* d_msg_idx, const uint32_t* d_key_idx, const uint32_t* d_offsets, uint64_t n, uint32_t k,
+                                                             uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream);
+int mbls_fast_aggregate_verify_batch_indexed_msgtable(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx,
+                                                      const uint32_t* key_idx, const uint32_t* offsets, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status);
 
 /* ---- verification stream: many small calls packed into full rounds ---------------------------------------
  * The verification entries run at their full rate only when one call carries a whole round (CUs x 4 x 64 items, 65 536 on MI355X). A
@@ -313,6 +366,20 @@ int mbls_stream_submit_device(mbls_stream* s, const uint8_t* d_sigs, const uint8
 int mbls_stream_submit(mbls_stream* s, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* msg_offsets,
                        const uint8_t* pks, const uint32_t* key_idx, const uint32_t* pk_offsets, uint64_t n, uint32_t k,
                        uint8_t* results, uint32_t* status, uint64_t* ticket);
+/* A stream over a resident message table (see "resident message table"): same modes, key sources, policies, depth, threading, completion order and lifetime
+ * rules; a call names its messages by table index. A round stages 4 bytes per item where it staged the message -- the index array is the "message bytes" of a
+ * call shape with msg_len = 4 and no offsets, so rounds are cut exactly as mbls_stream_cut cuts calls of msg_len = 4, and round_msg_bytes defaults to
+ * 4 x round_items -- and launches the `_msgtable_device` entry of its mode. The table is read at the size it has when the call's round launches (the key table's
+ * rule; mbls_msgtable_clear is refused while calls are pending, so an index valid at submit stays valid); in both submit forms an index at or above that size
+ * rejects its item with MBLS_ST_BAD_MSG_RANGE, as an out-of-range key index rejects its item. Per-call results, status words and bitmap are byte for byte what a
+ * direct `_msgtable_device` call on the same inputs returns. mbls_stream_submit[_device] on such a stream, and the two entries below on a stream of
+ * mbls_stream_create, are MBLS_ERR_ARGUMENT. */
+int mbls_stream_create_msgtable(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, mbls_msgtable* mt, const mbls_stream_opts* opts, mbls_stream** out);
+int mbls_stream_submit_msgidx_device(mbls_stream* s, const uint8_t* d_sigs, const uint32_t* d_msg_idx, const uint8_t* d_pks, const uint32_t* d_key_idx,
+                                     const uint32_t* h_pk_offsets, uint64_t n, uint32_t k, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream,
+                                     uint64_t* ticket);
+int mbls_stream_submit_msgidx(mbls_stream* s, const uint8_t* sigs, const uint32_t* msg_idx, const uint8_t* pks, const uint32_t* key_idx, const uint32_t* pk_offsets,
+                              uint64_t n, uint32_t k, uint8_t* results, uint32_t* status, uint64_t* ticket);
 int mbls_stream_flush(mbls_stream* s);
 int mbls_stream_wait(mbls_stream* s, uint64_t ticket);
 int mbls_stream_query(mbls_stream* s, uint64_t ticket);

@@ -480,6 +480,103 @@ inline std::vector<bool> fast_aggregate_verify_batch_shared_msgs(const std::vect
     return out;
 }
 
+// A resident message table on the library's context (include/mbls.h, "resident message table"; not part of the reference's API): every appended message is hashed
+// to G2 once and stays in device memory; verifications -- direct ones below, or calls of a VerifyStream made over the table -- name their messages by index, in
+// any later call. Indices start at 0 and never change until clear(). Destroy the table after the streams made over it.
+class MessageTable {
+    mbls_msgtable* h_ = nullptr;
+public:
+    explicit MessageTable(uint64_t capacity_hint = 0) { detail::check(mbls_msgtable_create(detail::ctx(), capacity_hint, &h_)); }
+    MessageTable(const MessageTable&) = delete; MessageTable& operator=(const MessageTable&) = delete;
+    ~MessageTable() { mbls_msgtable_destroy(h_); }
+    mbls_msgtable* handle() const { return h_; }
+    uint64_t size() const { return mbls_msgtable_size(h_); }
+    // messages of any length each -> the index of the first; message j is entry first + j
+    uint64_t append(const std::vector<Bytes>& msgs) {
+        Bytes m; std::vector<uint64_t> moff{0};
+        for (auto& x : msgs) { m.insert(m.end(), x.begin(), x.end()); moff.push_back(m.size()); }
+        uint64_t first = 0;
+        detail::check(mbls_msgtable_append(h_, m.data(), 0, moff.data(), msgs.size(), &first));
+        return first;
+    }
+    uint64_t append(const Bytes& msg) { return append(std::vector<Bytes>{msg}); }
+    // the compressed point of entry i: what hash_to_curve gives for its message
+    std::array<uint8_t, 96> get(uint64_t i) const {
+        std::array<uint8_t, 96> o{}; uint8_t e = 0;
+        detail::check(mbls_msgtable_get(h_, i, 1, o.data(), &e)); detail::check(e);
+        return o;
+    }
+    // size back to 0, capacity kept; refused (DeviceError) while a stream made over the table has calls that have not completed
+    void clear() { detail::check(mbls_msgtable_clear(h_)); }
+};
+namespace detail {
+inline void flatten_items(const char* what, const std::vector<AggregateSignature>& sigs, const MessageTable& table, const std::vector<uint32_t>& msg_idx,
+                          const std::vector<std::vector<const PublicKey*>>& keys, Bytes& s, Bytes& p, std::vector<uint32_t>& koff) {
+    const size_t n = sigs.size();
+    if (msg_idx.size() != n || keys.size() != n) throw std::invalid_argument(std::string(what) + ": one message index and one key list per signature");
+    const uint64_t size = table.size();
+    for (uint32_t j : msg_idx) if (j >= size) throw std::invalid_argument(std::string(what) + ": an index names no entry of the message table");
+    koff.assign(1, 0);
+    for (size_t i = 0; i < n; i++) {
+        s.insert(s.end(), sigs[i].point.begin(), sigs[i].point.end());
+        for (auto* k : keys[i]) p.insert(p.end(), k->point.begin(), k->point.end());
+        if (p.size() / 96 > 0xFFFFFFFFull) throw std::invalid_argument(std::string(what) + ": key indices are 32-bit");
+        koff.push_back(uint32_t(p.size() / 96));
+    }
+}
+}  // namespace detail
+// n x AggregateSignature::fast_aggregate_verify over a resident message table (mbls_fast_aggregate_verify_batch_msgtable): item i = (sigs[i], entry msg_idx[i],
+// keys[i]); nothing is hashed. The same bools as one fast_aggregate_verify per item with the entry's message.
+inline std::vector<bool> fast_aggregate_verify_batch_msgtable(const std::vector<AggregateSignature>& sigs, const MessageTable& table, const std::vector<uint32_t>& msg_idx,
+                                                              const std::vector<std::vector<const PublicKey*>>& keys) {
+    Bytes s, p; std::vector<uint32_t> koff;
+    detail::flatten_items("fast_aggregate_verify_batch_msgtable", sigs, table, msg_idx, keys, s, p, koff);
+    const size_t n = sigs.size();
+    std::vector<uint8_t> res(n ? n : 1);
+    detail::check(mbls_fast_aggregate_verify_batch_msgtable(detail::ctx(), s.data(), table.handle(), msg_idx.data(), p.data(), MBLS_PK_UNCOMPRESSED, koff.data(), n, 0,
+                                                            res.data(), nullptr));
+    std::vector<bool> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = res[i] == 1;
+    return out;
+}
+// n x Signature::verify over a resident message table (mbls_verify_batch_msgtable): item i = (sigs[i], entry msg_idx[i], keys[i])
+inline std::vector<bool> verify_batch_msgtable(const std::vector<Signature>& sigs, const MessageTable& table, const std::vector<uint32_t>& msg_idx,
+                                               const std::vector<const PublicKey*>& keys) {
+    const size_t n = sigs.size();
+    if (msg_idx.size() != n || keys.size() != n) throw std::invalid_argument("verify_batch_msgtable: one message index and one key per signature");
+    const uint64_t size = table.size();
+    for (uint32_t j : msg_idx) if (j >= size) throw std::invalid_argument("verify_batch_msgtable: an index names no entry of the message table");
+    Bytes s, p;
+    for (size_t i = 0; i < n; i++) { s.insert(s.end(), sigs[i].point.begin(), sigs[i].point.end()); p.insert(p.end(), keys[i]->point.begin(), keys[i]->point.end()); }
+    std::vector<uint8_t> res(n ? n : 1);
+    detail::check(mbls_verify_batch_msgtable(detail::ctx(), s.data(), table.handle(), msg_idx.data(), p.data(), MBLS_PK_UNCOMPRESSED, n, res.data(), nullptr));
+    std::vector<bool> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = res[i] == 1;
+    return out;
+}
+// the same as fast_aggregate_verify_batch_msgtable with the keys named by index into a resident key table of the library's context
+// (mbls_fast_aggregate_verify_batch_indexed_msgtable): item i uses key-table entries key_idx[i]
+inline std::vector<bool> fast_aggregate_verify_batch_indexed_msgtable(const mbls_keytable* key_table, const std::vector<AggregateSignature>& sigs, const MessageTable& table,
+                                                                      const std::vector<uint32_t>& msg_idx, const std::vector<std::vector<uint32_t>>& key_idx) {
+    const size_t n = sigs.size();
+    if (msg_idx.size() != n || key_idx.size() != n) throw std::invalid_argument("fast_aggregate_verify_batch_indexed_msgtable: one message index and one key index list per signature");
+    const uint64_t size = table.size();
+    for (uint32_t j : msg_idx) if (j >= size) throw std::invalid_argument("fast_aggregate_verify_batch_indexed_msgtable: an index names no entry of the message table");
+    Bytes s; std::vector<uint32_t> flat, koff{0};
+    for (size_t i = 0; i < n; i++) {
+        s.insert(s.end(), sigs[i].point.begin(), sigs[i].point.end());
+        flat.insert(flat.end(), key_idx[i].begin(), key_idx[i].end());
+        if (flat.size() > 0xFFFFFFFFull) throw std::invalid_argument("fast_aggregate_verify_batch_indexed_msgtable: key offsets are 32-bit");
+        koff.push_back(uint32_t(flat.size()));
+    }
+    std::vector<uint8_t> res(n ? n : 1);
+    detail::check(mbls_fast_aggregate_verify_batch_indexed_msgtable(detail::ctx(), key_table, s.data(), table.handle(), msg_idx.data(), flat.data(), koff.data(), n, 0,
+                                                                    res.data(), nullptr));
+    std::vector<bool> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = res[i] == 1;
+    return out;
+}
+
 class MultiGpu {
     mbls_multi* h_ = nullptr;
 public:
@@ -535,7 +632,7 @@ public:
 // launches. submit() takes the same objects as MultiGpu::fast_aggregate_verify and returns a ticket; Ticket::get() waits for the call.
 // The stream keeps every call's staged inputs until the call completes; destroying it completes every pending call.
 class VerifyStream {
-    struct Call { Bytes s, m, p; std::vector<uint64_t> moff; std::vector<uint32_t> koff; std::vector<uint8_t> res; uint64_t ticket = 0; size_t n = 0; };
+    struct Call { Bytes s, m, p; std::vector<uint64_t> moff; std::vector<uint32_t> koff, midx; std::vector<uint8_t> res; uint64_t ticket = 0; size_t n = 0; };
     mbls_stream* h_ = nullptr;
     std::mutex mu_;
     std::deque<std::shared_ptr<Call>> live_;
@@ -554,6 +651,12 @@ public:
         mbls_stream_opts o{}; o.round_items = round_items; o.policy = policy;
         if (mbls_stream_create(detail::ctx(), MBLS_STREAM_FAST_AGGREGATE_VERIFY, MBLS_PK_UNCOMPRESSED, nullptr, &o, &h_) != MBLS_OK)
             throw DeviceError(std::string("mbls_stream_create: ") + mbls_last_error(detail::ctx()));
+    }
+    // a stream over a resident message table: its calls name their messages by table index (the submit overload below); destroy it before the table
+    explicit VerifyStream(MessageTable& table, uint32_t policy = MBLS_STREAM_WORK_CONSERVING, uint64_t round_items = 0) {
+        mbls_stream_opts o{}; o.round_items = round_items; o.policy = policy;
+        if (mbls_stream_create_msgtable(detail::ctx(), MBLS_STREAM_FAST_AGGREGATE_VERIFY, MBLS_PK_UNCOMPRESSED, nullptr, table.handle(), &o, &h_) != MBLS_OK)
+            throw DeviceError(std::string("mbls_stream_create_msgtable: ") + mbls_last_error(detail::ctx()));
     }
     VerifyStream(const VerifyStream&) = delete; VerifyStream& operator=(const VerifyStream&) = delete;
     ~VerifyStream() { mbls_stream_destroy(h_); }
@@ -574,6 +677,25 @@ public:
         std::lock_guard<std::mutex> g(mu_);
         while (!live_.empty() && mbls_stream_query(h_, live_.front()->ticket) != MBLS_PENDING) live_.pop_front();
         check(mbls_stream_submit(h_, c->s.data(), c->m.data(), 0, c->moff.data(), c->p.data(), nullptr, c->koff.data(), n, 0, c->res.data(), nullptr, &c->ticket));
+        live_.push_back(c);
+        return Ticket(this, c);
+    }
+    // the same over the stream's message table: item i's message is entry msg_idx[i] (an index the table does not hold when the call's round launches rejects
+    // its item). Only on a stream made over a MessageTable; the overload above only on one that was not.
+    Ticket submit(const std::vector<AggregateSignature>& sigs, const std::vector<uint32_t>& msg_idx, const std::vector<std::vector<const PublicKey*>>& keys) {
+        const size_t n = sigs.size();
+        if (n == 0 || msg_idx.size() != n || keys.size() != n) throw std::invalid_argument("one message index and one key set per signature, at least one item");
+        auto c = std::make_shared<Call>();
+        c->koff.push_back(0); c->n = n; c->res.resize(n); c->midx = msg_idx;
+        for (size_t i = 0; i < n; i++) {
+            c->s.insert(c->s.end(), sigs[i].point.begin(), sigs[i].point.end());
+            for (auto* k : keys[i]) c->p.insert(c->p.end(), k->point.begin(), k->point.end());
+            if (c->p.size() / 96 > 0xFFFFFFFFull) throw std::invalid_argument("VerifyStream::submit: key offsets are 32-bit");
+            c->koff.push_back(uint32_t(c->p.size() / 96));
+        }
+        std::lock_guard<std::mutex> g(mu_);
+        while (!live_.empty() && mbls_stream_query(h_, live_.front()->ticket) != MBLS_PENDING) live_.pop_front();
+        check(mbls_stream_submit_msgidx(h_, c->s.data(), c->midx.data(), c->p.data(), nullptr, c->koff.data(), n, 0, c->res.data(), nullptr, &c->ticket));
         live_.push_back(c);
         return Ticket(this, c);
     }

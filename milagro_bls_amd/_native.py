@@ -231,6 +231,19 @@ SIGNATURES = {
     "mbls_verify_batch_shared_msgs": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_int, C.c_uint64, vp, vp]),
     "mbls_fast_aggregate_verify_batch_indexed_shared_msgs_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp]),
     "mbls_fast_aggregate_verify_batch_indexed_shared_msgs": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
+    "mbls_msgtable_create": (C.c_int, [vp, C.c_uint64, C.POINTER(vp)]),
+    "mbls_msgtable_destroy": (None, [vp]),
+    "mbls_msgtable_size": (C.c_uint64, [vp]),
+    "mbls_msgtable_append": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "mbls_msgtable_append_device": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]),
+    "mbls_msgtable_get": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, vp]),
+    "mbls_msgtable_clear": (C.c_int, [vp]),
+    "mbls_fast_aggregate_verify_batch_msgtable_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_msgtable": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp, vp]),
+    "mbls_verify_batch_msgtable_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_uint64, vp, vp, vp, vp]),
+    "mbls_verify_batch_msgtable": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_uint64, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_indexed_msgtable_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_indexed_msgtable": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
     "mbls_aggregate_signatures_batch": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
     "mbls_aggregate_signatures_batch_device": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp, vp]),
     "mbls_pk_from_bytes": (C.c_int, [vp, vp, C.c_size_t, vp]),
@@ -322,6 +335,9 @@ SIGNATURES = {
     "mbls_stream_last_error": (C.c_char_p, [vp]),
     "mbls_stream_submit_device": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_uint64)]),
     "mbls_stream_submit": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(C.c_uint64)]),
+    "mbls_stream_create_msgtable": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(vp)]),
+    "mbls_stream_submit_msgidx_device": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_uint64)]),
+    "mbls_stream_submit_msgidx": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(C.c_uint64)]),
     "mbls_stream_flush": (C.c_int, [vp]),
     "mbls_stream_wait": (C.c_int, [vp, C.c_uint64]),
     "mbls_stream_query": (C.c_int, [vp, C.c_uint64]),
@@ -481,6 +497,56 @@ class KeyTable:
         out, errs = outbuf(96 * n), outbuf(n)
         self.ctx.check(lib().mbls_keytable_get(self._h, first, n, out, errs))
         return bytes(out)[:96 * n], list(bytes(errs)[:n])
+
+
+class MsgTable:
+    """Resident table of hashed messages in HBM (include/mbls.h, mbls_msgtable_*): hash once, verify by index in any call or stream."""
+
+    def __init__(self, ctx=None, capacity_hint=0):
+        self.ctx = ctx or default_context()
+        self._h = vp()
+        self.ctx.check(lib().mbls_msgtable_create(self.ctx.handle, capacity_hint, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().mbls_msgtable_destroy(self._h)
+            self._h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __len__(self):
+        return int(lib().mbls_msgtable_size(self._h))
+
+    def append(self, msgs, n, msg_len=32, msg_offsets=None):
+        """n messages of msg_len bytes each, or msgs[msg_offsets[j]:msg_offsets[j+1]] (n + 1 offsets) -> first_index"""
+        first = C.c_uint64(0)
+        off = None if msg_offsets is None else (C.c_uint64 * len(msg_offsets))(*msg_offsets)
+        self.ctx.check(lib().mbls_msgtable_append(self._h, cbuf(msgs), msg_len, off, n, C.byref(first)))
+        return int(first.value)
+
+    def append_device(self, d_msgs, n, msg_len=32, d_msg_offsets=None, stream=None):
+        """device pointers; enqueues only (a bad range becomes a flagged entry) -> first_index"""
+        first = C.c_uint64(0)
+        self.ctx.check(lib().mbls_msgtable_append_device(self._h, d_msgs, msg_len, d_msg_offsets, n, C.byref(first), stream))
+        return int(first.value)
+
+    def get(self, first, n=1):
+        """-> (96-byte compressed points of n entries, errs): errs[i] = ERR_ARGUMENT for a flagged entry"""
+        out, errs = outbuf(96 * n), outbuf(n)
+        self.ctx.check(lib().mbls_msgtable_get(self._h, first, n, out, errs))
+        return bytes(out)[:96 * n], list(bytes(errs)[:n])
+
+    def clear(self):
+        """size back to 0, capacity kept; refused while a stream bound to the table has calls that have not completed"""
+        self.ctx.check(lib().mbls_msgtable_clear(self._h))
 
 
 class MultiContext:

@@ -90,6 +90,44 @@ def verify_batch_shared_msgs(sigs, msgs, n_msgs, msg_idx, pks, n, pk_format=N.PK
     return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
 
 
+def fast_aggregate_verify_batch_msgtable(msg_table, sigs, msg_idx, pks, n, k=None, pk_format=N.PK_COMPRESSED, pk_offsets=None, ctx=None):
+    """fast_aggregate_verify_batch over a resident message table (N.MsgTable): item i's message is entry msg_idx[i]; nothing is hashed. Same (results, status)
+    as fast_aggregate_verify_batch with the messages spelled out per item; an index that names no entry raises (MBLS_ERR_ARGUMENT)."""
+    ctx = ctx or msg_table.ctx
+    res = N.outbuf(n)
+    st = (C.c_uint32 * max(1, n))()
+    off = None
+    if pk_offsets is not None:
+        off = (C.c_uint32 * len(pk_offsets))(*pk_offsets)
+        k = 0
+    ctx.check(N.lib().mbls_fast_aggregate_verify_batch_msgtable(ctx.handle, N.cbuf(sigs), msg_table.handle, _midx(msg_idx, n), N.cbuf(pks), pk_format, off, n, k, res, st))
+    return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
+
+
+def fast_aggregate_verify_batch_indexed_msgtable(table, msg_table, sigs, msg_idx, key_idx, n, k=None, offsets=None, ctx=None):
+    """The same over a resident key table: keys by key-table index, messages by message-table index."""
+    ctx = ctx or table.ctx
+    res = N.outbuf(n)
+    st = (C.c_uint32 * max(1, n))()
+    idx = (C.c_uint32 * max(1, len(key_idx)))(*key_idx)
+    off = None
+    if offsets is not None:
+        off = (C.c_uint32 * len(offsets))(*offsets)
+        k = 0
+    ctx.check(N.lib().mbls_fast_aggregate_verify_batch_indexed_msgtable(ctx.handle, table.handle, N.cbuf(sigs), msg_table.handle, _midx(msg_idx, n), idx, off, n, k,
+                                                                        res, st))
+    return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
+
+
+def verify_batch_msgtable(msg_table, sigs, msg_idx, pks, n, pk_format=N.PK_COMPRESSED, ctx=None):
+    """verify_batch (n x Signature::verify) over a resident message table: item i's message is entry msg_idx[i]."""
+    ctx = ctx or msg_table.ctx
+    res = N.outbuf(n)
+    st = (C.c_uint32 * max(1, n))()
+    ctx.check(N.lib().mbls_verify_batch_msgtable(ctx.handle, N.cbuf(sigs), msg_table.handle, _midx(msg_idx, n), N.cbuf(pks), pk_format, n, res, st))
+    return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
+
+
 def aggregate_signatures_batch(sigs96, n, k=None, offsets=None, ctx=None):
     """n x AggregateSignature::aggregate (reference src/aggregates.rs:100-106) -> (compressed sums, errs)"""
     ctx = ctx or _c()

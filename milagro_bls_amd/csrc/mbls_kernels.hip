@@ -15,6 +15,7 @@
 #include <new>
 #include <mutex>
 #include <vector>
+#include <atomic>
 #include <dlfcn.h>
 #include <unistd.h>
 #include "mbls_ops.h"
@@ -23,6 +24,7 @@
 #include "mbls_vml.h"
 #include "mbls_vms.h"
 #include "mbls_vsl.h"
+#include "mbls_mtb.h"
 #include "../../include/mbls.h"
 
 // The product library exists only with the generated routines: the host side below selects kernels (the fused subgroup verdict of
@@ -213,6 +215,20 @@ __global__ void __launch_bounds__(MBLS_HB) k_h_gather(mbls_ws ws, const uint32_t
     const uint64_t i = (uint64_t)blockIdx.x * MBLS_HB + threadIdx.x; if (i >= n) return;
     const uint32_t st = lane_h_gather(ws, i, tab, tstride, flags, msg_idx[i], n_msgs);
     if (st) atomicOr(status + i, st);             // beside the key sum and the signature phase, like k_hash
+}
+// Resident message table (mbls_msgtable_*, mbls_mtb.h). Growth: the stride follows the capacity, so every entry [0, entries) -- the private one included -- moves
+// to its place in the new buffers, one lane per entry (consecutive lanes = consecutive entries on both sides). mbls_msgtable_get: entries first .. first + n - 1
+// into slot H of workspace items [0, n) (k_h_export compresses them from there), errs[i] = MBLS_ERR_ARGUMENT for a flagged entry.
+__global__ void __launch_bounds__(MBLS_HB) k_mtb_relayout(const uint32_t* old_tab, uint64_t old_stride, const uint32_t* old_flags, uint32_t* new_tab, uint64_t new_stride,
+                                                          uint32_t* new_flags, uint64_t entries) {
+    const uint64_t e = (uint64_t)blockIdx.x * MBLS_HB + threadIdx.x; if (e >= entries) return;
+    mtb_relayout_entry(old_tab, old_stride, old_flags, new_tab, new_stride, new_flags, e);
+}
+__global__ void __launch_bounds__(MBLS_HB) k_mtb_get(mbls_ws ws, const uint32_t* tab, uint64_t tstride, const uint32_t* flags, uint64_t first, uint64_t size, uint8_t* errs,
+                                                     uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * MBLS_HB + threadIdx.x; if (i >= n) return;
+    const uint32_t st = lane_h_gather(ws, i, tab, tstride, flags, (uint32_t)(first + i), size);
+    errs[i] = st ? (uint8_t)MBLS_ERR_ARGUMENT : (uint8_t)MBLS_OK;
 }
 // hash_to_field alone (SHA-256 / expand_message_xmd, one lane per item): u0, u1 into slots 31, 32 / 37, 38 -- the input of the cooperative
 // engine's hashg2 program (small batches: one WAVE per item walks the maps, the addition and the cofactor clearing)
@@ -1170,6 +1186,7 @@ struct mbls_ctx {
     hipEvent_t ev[MBLS_N_PHASES + 1] = {};
     float phase_ms[MBLS_N_PHASES] = {};
     std::vector<struct mbls_keytable*> tables;     // the key tables created on this context (orphaned when it is destroyed)
+    std::vector<struct mbls_msgtable*> msgtables;  // the message tables, likewise
     coop_prog coop[10] = {};           // the cooperative engine's microprograms in HBM (mbls_coop.h): pairing2, vmtail, f12mul, g2add, smiller, vmfinal, hashg2, miller1,
                                        // pairing2x2 (two items per wave), hashg2x4 (four)
     uint32_t* d_coop = nullptr;
@@ -1195,6 +1212,15 @@ struct mbls_keytable {
     uint32_t* d_recs = nullptr;        // [cap][MBLS_KEYREC_DWORDS]
     uint64_t size = 0, cap = 0;
     hipEvent_t ev = nullptr; hipStream_t ev_stream = nullptr; bool pending = false;   // the last asynchronous append
+};
+// resident message table (mbls_mtb.h): [72][stride] dwords and one flag word per entry, stride = cap + 1 (entry 0: H of the empty message, hashed at creation;
+// public index j: entry j + 1); d_st: the status words of the appends' own hashes, by entry
+struct mbls_msgtable {
+    mbls_ctx* c = nullptr;             // nullptr: the context was destroyed first
+    uint32_t* d_tab = nullptr; uint32_t* d_flag = nullptr; uint32_t* d_st = nullptr;
+    uint64_t size = 0, cap = 0;
+    hipEvent_t ev = nullptr; hipStream_t ev_stream = nullptr; bool pending = false;   // the last asynchronous append
+    std::atomic<long long> stream_calls{0};        // calls of streams bound to the table that have not completed (mbls_msgtable_clear refuses while there are any)
 };
 typedef std::lock_guard<std::recursive_mutex> mbls_lock;
 
@@ -1422,6 +1448,14 @@ extern "C" void mbls_ctx_destroy(mbls_ctx* c) {
             t->d_recs = nullptr; t->ev = nullptr; t->size = t->cap = 0; t->c = nullptr;
         }
         c->tables.clear();
+        for (mbls_msgtable* t : c->msgtables) {
+            if (t->d_tab) (void)hipFree(t->d_tab);
+            if (t->d_flag) (void)hipFree(t->d_flag);
+            if (t->d_st) (void)hipFree(t->d_st);
+            if (t->ev) (void)hipEventDestroy(t->ev);
+            t->d_tab = t->d_flag = t->d_st = nullptr; t->ev = nullptr; t->size = t->cap = 0; t->c = nullptr;
+        }
+        c->msgtables.clear();
     }
     ctx_free(c);
 }
@@ -1723,12 +1757,19 @@ static uint64_t pass_ws_items(const mbls_pass_plan& pp, const keysrc& ks, uint32
 struct msgsrc {
     const uint32_t* d_idx = nullptr; uint64_t n_msgs = 0;
     const mbls_shared_msgs_plan* list = nullptr;      // non-null: the pass hashes the list itself (a one-pass plan: on its message stream, beside the other front phases)
+    // the table the gather reads: the context's own (a call's list) or a resident one (mbls_msgtable: n_msgs is then its size when the call was enqueued)
+    const uint32_t* tab = nullptr; uint64_t tstride = 0; const uint32_t* flags = nullptr;
 };
+// where the points of a hashed list go: the context's per-call table, or a resident table behind the entries it already holds
+struct htab_dst { uint32_t* tab; uint64_t tstride; uint32_t* flags; uint32_t* st; uint64_t first_entry; };
 // the hash of the list on stream s: piece after piece through launch_hash in workspace items [0, piece), each followed by its export to the table; first of all,
 // once per allocation of the table, the entry of the empty message
-static int shared_hash_list(mbls_ctx* c, const mbls_shared_msgs_plan& sp, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, hipStream_t s) {
+static int shared_hash_list(mbls_ctx* c, const mbls_shared_msgs_plan& sp, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, hipStream_t s,
+                            const htab_dst* dst = nullptr) {
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
-    if (!c->h_empty_ready) {
+    const htab_dst own = {c->d_htab, c->htab_cap, c->d_hflag, c->d_hst, 1};
+    const htab_dst& d = dst ? *dst : own;
+    if (!dst && !c->h_empty_ready) {
         HIPCHK(c, hipMemsetAsync(c->d_hst, 0, 4, s));
         launch_hash(c, ws, (const uint8_t*)c->d_htab, 0u, (const uint64_t*)nullptr, c->d_hst, (uint64_t)1, s);
         hipLaunchKernelGGL(k_h_export_tab, dim3(1), dim3(MBLS_HB), 0, s, ws, c->d_htab, c->htab_cap, c->d_hflag, (const uint32_t*)c->d_hst, (uint64_t)0, (uint64_t)1);
@@ -1737,13 +1778,13 @@ static int shared_hash_list(mbls_ctx* c, const mbls_shared_msgs_plan& sp, const 
     const int form = sp.list_message == MBLS_MESSAGE_LANE ? HASH_FORM_LANE : sp.list_message == MBLS_MESSAGE_LANES2 ? HASH_FORM_PAIR : HASH_FORM_WAVE;
     for (uint64_t first = 0; first < n_msgs; first += sp.list_piece_items) {
         const uint64_t m = n_msgs - first < sp.list_piece_items ? n_msgs - first : sp.list_piece_items;
-        uint32_t* st_list = c->d_hst + 1 + first;
+        uint32_t* st_list = d.st + d.first_entry + first;
         HIPCHK(c, hipMemsetAsync(st_list, 0, 4 * m, s));
         // uniform messages advance the base pointer, an offset table is absolute (its slice goes with the unmoved base)
         launch_hash(c, ws, (d_moff || !d_msgs) ? d_msgs : d_msgs + (uint64_t)msg_len * first, msg_len, d_moff ? d_moff + first : nullptr, st_list, m, s,
                     form == HASH_FORM_PAIR, form);
-        hipLaunchKernelGGL(k_h_export_tab, dim3((unsigned)((m + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s, ws, c->d_htab, c->htab_cap, c->d_hflag, (const uint32_t*)st_list,
-                           1 + first, m);
+        hipLaunchKernelGGL(k_h_export_tab, dim3((unsigned)((m + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s, ws, d.tab, d.tstride, d.flags, (const uint32_t*)st_list,
+                           d.first_entry + first, m);
     }
     HIPCHK(c, hipGetLastError());
     return MBLS_OK;
@@ -1813,8 +1854,7 @@ static int verify_pipeline_one(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t
     auto launch_msg = [&]() -> int {
         if (!ms) { launch_hash(c, ws, d_msgs, msg_len, d_moff, st, n, s_msg, hash_pairs, hform); return MBLS_OK; }
         if (ms->list) { const int rl = shared_hash_list(c, *ms->list, d_msgs, msg_len, d_moff, ms->n_msgs, s_msg); if (rl) return rl; }
-        hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, (const uint32_t*)c->d_htab, c->htab_cap,
-                           (const uint32_t*)c->d_hflag, ms->d_idx, ms->n_msgs, st, n);
+        hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, ms->tab, ms->tstride, ms->flags, ms->d_idx, ms->n_msgs, st, n);
         return MBLS_OK;
     };
     if (part == 1) {
@@ -2185,7 +2225,7 @@ static int verify_shared_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
     int rc = mbls_ctx_reserve(c, need); if (rc) return rc;
     rc = reserve_msgs(c, n_msgs); if (rc) return rc;
     if (!ks.indexed && ks.fmt == MBLS_PK_COMPRESSED && !ks.d_off && k > 1) { rc = reserve_keys(c, need_items * (uint64_t)k); if (rc) return rc; }
-    msgsrc ms; ms.d_idx = d_midx; ms.n_msgs = n_msgs;
+    msgsrc ms; ms.d_idx = d_midx; ms.n_msgs = n_msgs; ms.tab = c->d_htab; ms.tstride = c->htab_cap; ms.flags = c->d_hflag;
     if (sp.batch.mode == MBLS_BATCH_ONE_PASS) {
         ms.list = &sp;
         return verify_pipeline(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, 0, &ms);
@@ -2278,6 +2318,257 @@ extern "C" int mbls_fast_aggregate_verify_batch_indexed_shared_msgs(mbls_ctx* c,
         const uint64_t* moff, uint64_t n_msgs, const uint32_t* msg_idx, const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
     if (!c || !t) return MBLS_ERR_ARGUMENT;
     return verify_host_shared(c, sigs, msgs, msg_len, moff, n_msgs, msg_idx, nullptr, MBLS_PK_UNCOMPRESSED, t, idx, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
+}
+
+// ---- resident message table (include/mbls.h, mbls_msgtable_*): the message side's key table. An append hashes its messages with launch_hash in the form THEIR count
+// asks for (plan_shared's list rule), in the context's workspace, and exports the points behind the entries the table holds (k_h_export_tab at first_index + 1); the
+// verification entries take mbls_plan_batch's plan with every pass's message phase the gather from the table (k_h_gather), and hash nothing. Ordering is the key
+// table's: an append records an event, readers and later appends on other streams wait for it on the device. Index arithmetic and growth: mbls_mtb.h.
+static void msgtable_free_buffers(mbls_msgtable* t) {
+    if (t->d_tab) (void)hipFree(t->d_tab);
+    if (t->d_flag) (void)hipFree(t->d_flag);
+    if (t->d_st) (void)hipFree(t->d_st);
+    t->d_tab = t->d_flag = t->d_st = nullptr;
+}
+static hipError_t msgtable_alloc(uint64_t cap, uint32_t** tab, uint32_t** flag, uint32_t** st) {
+    const uint64_t stride = mtb_stride(cap);
+    *tab = *flag = *st = nullptr;
+    hipError_t e = hipMalloc(tab, (size_t)MBLS_H_DWORDS * stride * 4);
+    if (e == hipSuccess) e = hipMalloc(flag, stride * 4);
+    if (e == hipSuccess) e = hipMalloc(st, stride * 4);
+    if (e != hipSuccess) { if (*tab) (void)hipFree(*tab); if (*flag) (void)hipFree(*flag); if (*st) (void)hipFree(*st); *tab = *flag = *st = nullptr; }
+    return e;
+}
+static int msgtable_acquire(mbls_ctx* c, const mbls_msgtable* t, hipStream_t s) {
+    if (t->pending && t->ev_stream != s) HIPCHK(c, hipStreamWaitEvent(s, t->ev, 0));
+    return MBLS_OK;
+}
+extern "C" int mbls_msgtable_create(mbls_ctx* c, uint64_t capacity_hint, mbls_msgtable** out) {
+    if (!c || !out) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (capacity_hint > 0xFFFFFFFFull) ARGFAIL(c, "message table indices are 32-bit");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = mbls_ctx_reserve(c, 1); if (rc) return rc;
+    mbls_msgtable* t = new (std::nothrow) mbls_msgtable();
+    if (!t) return MBLS_ERR_DEVICE;
+    t->c = c; t->cap = capacity_hint ? capacity_hint : MBLS_MTB_DEFAULT_CAPACITY;
+    hipError_t e = msgtable_alloc(t->cap, &t->d_tab, &t->d_flag, &t->d_st);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
+    // the private entry: H of the empty message, hashed here once (growth carries it along, clear keeps it)
+    if (e == hipSuccess) {
+        hipStream_t s = c->hs_a;
+        mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
+        if (c->ws_pending && c->ws_stream != s) e = hipStreamWaitEvent(s, c->ws_ev, 0);
+        if (e == hipSuccess) e = hipMemsetAsync(t->d_st, 0, 4, s);
+        if (e == hipSuccess) {
+            launch_hash(c, ws, (const uint8_t*)t->d_tab, 0u, (const uint64_t*)nullptr, t->d_st, (uint64_t)1, s);
+            hipLaunchKernelGGL(k_h_export_tab, dim3(1), dim3(MBLS_HB), 0, s, ws, t->d_tab, mtb_stride(t->cap), t->d_flag, (const uint32_t*)t->d_st, (uint64_t)0, (uint64_t)1);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess) c->ws_pending = false;
+    }
+    if (e != hipSuccess) { msgtable_free_buffers(t); if (t->ev) (void)hipEventDestroy(t->ev); delete t; HIPCHK(c, e); }
+    try { c->msgtables.push_back(t); } catch (...) { msgtable_free_buffers(t); (void)hipEventDestroy(t->ev); delete t; return MBLS_ERR_DEVICE; }
+    *out = t; return MBLS_OK;
+}
+extern "C" void mbls_msgtable_destroy(mbls_msgtable* t) {
+    if (!t) return;
+    if (t->c) {
+        mbls_ctx* c = t->c;
+        mbls_lock lk(c->mu); (void)hipSetDevice(c->device); (void)hipDeviceSynchronize();
+        msgtable_free_buffers(t);
+        if (t->ev) (void)hipEventDestroy(t->ev);
+        for (size_t i = 0; i < c->msgtables.size(); i++) if (c->msgtables[i] == t) { c->msgtables.erase(c->msgtables.begin() + i); break; }
+    }
+    delete t;
+}
+extern "C" uint64_t mbls_msgtable_size(const mbls_msgtable* t) { if (!t || !t->c) return 0; mbls_lock lk(t->c->mu); return t->size; }
+// the count of calls that streams bound to the table have taken and not completed (mbls_stream.hip; hidden: not exported from the library)
+extern "C" __attribute__((visibility("hidden"))) void mblsi_msgtable_stream_calls(mbls_msgtable* t, long long delta) { if (t) t->stream_calls.fetch_add(delta); }
+// growth keeps every index and entry: new buffers of the new stride, every entry moved by k_mtb_relayout; the device is drained on both sides, like keytable_grow
+static int msgtable_grow(mbls_msgtable* t, uint64_t need, hipStream_t s) {
+    mbls_ctx* c = t->c;
+    const uint64_t ncap = mtb_grown(t->cap, need);
+    if (ncap == t->cap) return MBLS_OK;
+    uint32_t *nt, *nf, *ns;
+    HIPCHK(c, msgtable_alloc(ncap, &nt, &nf, &ns));
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) {
+        const uint64_t entries = t->size + 1;
+        hipLaunchKernelGGL(k_mtb_relayout, dim3((unsigned)((entries + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s, (const uint32_t*)t->d_tab, mtb_stride(t->cap),
+                           (const uint32_t*)t->d_flag, nt, mtb_stride(ncap), nf, entries);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { (void)hipFree(nt); (void)hipFree(nf); (void)hipFree(ns); HIPCHK(c, e); }
+    t->pending = false;
+    msgtable_free_buffers(t);
+    t->d_tab = nt; t->d_flag = nf; t->d_st = ns; t->cap = ncap;
+    return MBLS_OK;
+}
+extern "C" int mbls_msgtable_append_device(mbls_msgtable* t, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n, uint64_t* first_index, void* stream) {
+    if (!t || !t->c) return MBLS_ERR_ARGUMENT;
+    mbls_ctx* c = t->c;
+    mbls_lock lk(c->mu);
+    if (n && !d_msgs && msg_len && !d_moff) ARGFAIL(c, "null buffer");
+    if (t->size + n > 0xFFFFFFFFull) ARGFAIL(c, "message table indices are 32-bit");
+    if (!n) { if (first_index) *first_index = t->size; return MBLS_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    // the form of the hash is the list rule of plan_shared for a list of n messages: pieces of at most one round; wave engine, lane pairs or k_hash
+    mbls_shared_msgs_plan sp; plan_shared(ctx_limits(c), 1, n, true, false, &sp);
+    int rc = mbls_ctx_reserve(c, sp.list_workspace_items); if (rc) return rc;
+    rc = msgtable_grow(t, t->size + n, s); if (rc) return rc;
+    rc = ws_acquire(c, s); if (rc) return rc;
+    rc = msgtable_acquire(c, t, s); if (rc) return rc;      // the event below replaces the earlier append's: this stream inherits its completion first
+    const htab_dst dst = {t->d_tab, mtb_stride(t->cap), t->d_flag, t->d_st, mtb_append_entry(t->size, 0)};
+    rc = shared_hash_list(c, sp, d_msgs, msg_len, d_moff, n, s, &dst); if (rc) return rc;
+    rc = ws_release(c, s); if (rc) return rc;
+    HIPCHK(c, hipEventRecord(t->ev, s)); t->ev_stream = s; t->pending = true;
+    if (first_index) *first_index = t->size;
+    t->size += n; return MBLS_OK;
+}
+extern "C" int mbls_msgtable_append(mbls_msgtable* t, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n, uint64_t* first_index) {
+    if (!t || !t->c) return MBLS_ERR_ARGUMENT;
+    mbls_ctx* c = t->c;
+    mbls_lock lk(c->mu);
+    if (!n) { if (first_index) *first_index = t->size; return MBLS_OK; }
+    if (moff && !msg_offsets_ok(moff, n)) ARGFAIL(c, "msg_offsets must be non-decreasing, messages below 2^32 bytes");
+    const uint64_t msg_first = moff ? moff[0] : 0;
+    const size_t msg_total = moff ? (size_t)(moff[n] - moff[0]) : (size_t)msg_len * n;
+    if (!msgs && msg_total) ARGFAIL(c, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    sbuf dm(c, 1), dmo(c, 6);
+    HIPCHK(c, dm.up(msgs ? msgs + msg_first : nullptr, msg_total));
+    const uint64_t* d_moff = nullptr; const uint8_t* d_msgs = dm.as<uint8_t>();
+    if (moff) { HIPCHK(c, dmo.up(moff, 8 * (n + 1))); d_moff = dmo.as<uint64_t>(); d_msgs -= msg_first; }
+    const int rc = mbls_msgtable_append_device(t, d_msgs, msg_len, d_moff, n, first_index, c->hs_a);
+    const hipError_t e = hipStreamSynchronize(c->hs_a);       // the staged bytes are read until the hash has run
+    if (rc) return rc;
+    HIPCHK(c, e);
+    c->ws_pending = false;
+    if (t->ev_stream == c->hs_a) t->pending = false;
+    return MBLS_OK;
+}
+extern "C" int mbls_msgtable_get(mbls_msgtable* t, uint64_t first, uint64_t n, uint8_t* out96, uint8_t* errs) {
+    if (!t || !t->c) return MBLS_ERR_ARGUMENT;
+    mbls_ctx* c = t->c;
+    mbls_lock lk(c->mu);
+    if (first > t->size || n > t->size - first || (n && (!out96 || !errs))) ARGFAIL(c, "msgtable_get range");
+    if (!n) return MBLS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    sbuf dout(c, 0), de(c, 1); HIPCHK(c, dout.alloc(96 * n)); HIPCHK(c, de.alloc(n));
+    int rc = mbls_ctx_reserve(c, n); if (rc) return rc;
+    mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
+    hipStream_t s = c->hs_a;
+    rc = ws_acquire(c, s); if (rc) return rc;
+    rc = msgtable_acquire(c, t, s); if (rc) return rc;
+    hipLaunchKernelGGL(k_mtb_get, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s, ws, (const uint32_t*)t->d_tab, mtb_stride(t->cap), (const uint32_t*)t->d_flag,
+                       first, t->size, de.as<uint8_t>(), n);
+    hipLaunchKernelGGL(k_h_export, dim3(nblk(n)), dim3(WG), 0, s, ws, n, dout.as<uint8_t>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s)); c->ws_pending = false;
+    HIPCHK(c, dout.down(out96, 96 * n)); HIPCHK(c, de.down(errs, n));
+    return MBLS_OK;
+}
+extern "C" int mbls_msgtable_clear(mbls_msgtable* t) {
+    if (!t || !t->c) return MBLS_ERR_ARGUMENT;
+    mbls_ctx* c = t->c;
+    mbls_lock lk(c->mu);
+    if (t->stream_calls.load() > 0) ARGFAIL(c, "msgtable_clear: a stream bound to the table has calls that have not completed");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());           // everything enqueued that reads (or still writes) the table
+    t->size = 0; t->pending = false; c->ws_pending = false;
+    return MBLS_OK;
+}
+// the verification entries over a table: mbls_plan_batch's plan, every pass's message phase the gather; the table is read at the size it has now
+static int verify_msgtable_device(mbls_ctx* c, const mbls_msgtable* mt, const uint8_t* d_sigs, const uint32_t* d_midx, const keysrc& ks, uint64_t n, uint32_t k, int mode,
+                                  uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, hipStream_t s) {
+    if (ks.fmt != MBLS_PK_COMPRESSED && ks.fmt != MBLS_PK_UNCOMPRESSED) return MBLS_ERR_ARGUMENT;
+    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
+    if (n == 0) return MBLS_OK;
+    if (!d_sigs || !d_midx || !d_results) ARGFAIL(c, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    // (verify_pipeline reserves the plan's workspace and key staging before it queues the first pass, as for the per-item entries: there is no list to size here)
+    int rc = msgtable_acquire(c, mt, s); if (rc) return rc;      // every stream of the call forks from s behind this
+    msgsrc ms; ms.d_idx = d_midx; ms.n_msgs = mt->size; ms.tab = mt->d_tab; ms.tstride = mtb_stride(mt->cap); ms.flags = mt->d_flag;
+    return verify_pipeline(c, d_sigs, nullptr, 0, nullptr, ks, n, k, mode, d_results, d_bitmap, d_status, s, 0, &ms);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_msgtable_device(mbls_ctx* c, const uint8_t* d_sigs, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint8_t* d_pks,
+        int fmt, const uint32_t* d_off, uint64_t n, uint32_t k, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
+    if (!c || !mt) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    keysrc ks; ks.d_pks = d_pks; ks.fmt = fmt; ks.d_off = d_off;
+    return verify_msgtable_device(c, mt, d_sigs, d_msg_idx, ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status, (hipStream_t)stream);
+}
+extern "C" int mbls_verify_batch_msgtable_device(mbls_ctx* c, const uint8_t* d_sigs, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint8_t* d_pks, int fmt,
+        uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
+    if (!c || !mt) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    keysrc ks; ks.d_pks = d_pks; ks.fmt = fmt;
+    return verify_msgtable_device(c, mt, d_sigs, d_msg_idx, ks, n, 1, MBLS_MODE_VERIFY, d_results, d_bitmap, d_status, (hipStream_t)stream);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_indexed_msgtable_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const mbls_msgtable* mt,
+        const uint32_t* d_msg_idx, const uint32_t* d_idx, const uint32_t* d_off, uint64_t n, uint32_t k, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
+    if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (t->c != c) ARGFAIL(c, "key table belongs to another context");
+    keysrc ks; ks.indexed = true; ks.d_recs = t->d_recs; ks.tsize = t->size; ks.d_idx = d_idx; ks.d_off = d_off; ks.tab = t;
+    return verify_msgtable_device(c, mt, d_sigs, d_msg_idx, ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status, (hipStream_t)stream);
+}
+// Host buffers in, results out: an index that names no entry refuses the call before anything is enqueued
+static int verify_host_msgtable(mbls_ctx* c, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx, const uint8_t* pks, int fmt, const mbls_keytable* tab,
+                                const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, int mode, uint8_t* results, uint32_t* status) {
+    if (!c || !mt) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
+    if (n == 0) return MBLS_OK;
+    if (!sigs || !msg_idx || !results) ARGFAIL(c, "null buffer");
+    for (uint64_t i = 0; i < n; i++) if (mtb_names_nothing(msg_idx[i], mt->size)) ARGFAIL(c, "msg_idx names no entry of the message table");
+    if (fmt != MBLS_PK_COMPRESSED && fmt != MBLS_PK_UNCOMPRESSED) ARGFAIL(c, "pk_format");
+    if (tab && tab->c != c) ARGFAIL(c, "key table belongs to another context");
+    if (off && !offsets_ok(off, n)) ARGFAIL(c, "offsets must be non-decreasing");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t key_first = off ? off[0] : 0;
+    const uint64_t total_keys = off ? (uint64_t)(off[n] - off[0]) : (uint64_t)k * n;
+    const bool indexed = tab != nullptr;
+    if (total_keys && !(indexed ? (const void*)idx : (const void*)pks)) ARGFAIL(c, "null key buffer");
+    const size_t unit = indexed ? 4 : (fmt == MBLS_PK_COMPRESSED ? 48 : 96);
+    sbuf ds(c, 0), dp(c, 2), doff(c, 3), dr(c, 4), dst(c, 5), dmi(c, 7);
+    HIPCHK(c, ds.up(sigs, 96 * n)); HIPCHK(c, dmi.up(msg_idx, 4 * n));
+    if (off) HIPCHK(c, doff.up(off, 4 * (n + 1)));
+    HIPCHK(c, dr.alloc(n)); HIPCHK(c, dst.alloc(4 * n));
+    HIPCHK(c, dp.up(total_keys ? (indexed ? (const void*)(idx + key_first) : (const void*)(pks + unit * key_first)) : nullptr, unit * total_keys));
+    keysrc ks; ks.fmt = fmt; ks.d_off = off ? doff.as<uint32_t>() : nullptr; ks.indexed = indexed;
+    if (indexed) { ks.d_recs = tab->d_recs; ks.tsize = tab->size; ks.tab = tab; ks.d_idx = dp.as<uint32_t>() - key_first; } else ks.d_pks = dp.as<uint8_t>() - unit * key_first;
+    const bool tm = c->timing; c->timing = false;        // the phase timers describe the device entries
+    const int rc = verify_msgtable_device(c, mt, ds.as<uint8_t>(), dmi.as<uint32_t>(), ks, n, k, mode, dr.as<uint8_t>(), nullptr, dst.as<uint32_t>(), c->hs_a);
+    c->timing = tm;
+    if (rc) {         // nothing of this call is left in flight when it returns an error
+        (void)hipStreamSynchronize(c->hs_a); (void)hipStreamSynchronize(c->hs_b); (void)hipStreamSynchronize(c->hs_c); (void)hipStreamSynchronize(c->hs_d);
+        (void)hipStreamSynchronize(c->t1_s);
+        c->ws_pending = false;
+        return rc;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->hs_a));
+    c->ws_pending = false;
+    HIPCHK(c, dr.down(results, n));
+    if (status) HIPCHK(c, dst.down(status, 4 * n));
+    return MBLS_OK;
+}
+extern "C" int mbls_fast_aggregate_verify_batch_msgtable(mbls_ctx* c, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx, const uint8_t* pks, int fmt,
+        const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
+    return verify_host_msgtable(c, sigs, mt, msg_idx, pks, fmt, nullptr, nullptr, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
+}
+extern "C" int mbls_verify_batch_msgtable(mbls_ctx* c, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx, const uint8_t* pks, int fmt, uint64_t n,
+        uint8_t* results, uint32_t* status) {
+    return verify_host_msgtable(c, sigs, mt, msg_idx, pks, fmt, nullptr, nullptr, nullptr, n, 1, MBLS_MODE_VERIFY, results, status);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_indexed_msgtable(mbls_ctx* c, const mbls_keytable* t, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx,
+        const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
+    if (!c || !t) return MBLS_ERR_ARGUMENT;
+    return verify_host_msgtable(c, sigs, mt, msg_idx, nullptr, MBLS_PK_UNCOMPRESSED, t, idx, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
 }
 
 // ---- batch helpers

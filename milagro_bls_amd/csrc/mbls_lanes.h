@@ -15,6 +15,7 @@
 #pragma once
 #include "mbls_hash.h"
 #include "mbls_pairing.h"
+#include "mbls_mtb.h"
 
 #define MBLS_PK_COMPRESSED 0
 #define MBLS_PK_UNCOMPRESSED 1
@@ -387,8 +388,8 @@ MBLS_FN void lane_h_export(const mbls_ws& ws, uint64_t i, uint32_t* tab, uint64_
 }
 // item i takes the point of message j (j >= n_msgs: no such message -- entry 0 and the bad-range bit); returns the status bits the message brings
 MBLS_FN uint32_t lane_h_gather(const mbls_ws& ws, uint64_t i, const uint32_t* tab, uint64_t tstride, const uint32_t* flags, uint32_t j, uint64_t n_msgs) {
-    const bool none = (uint64_t)j >= n_msgs;
-    const uint64_t e = none ? 0 : (uint64_t)j + 1;
+    const bool none = mtb_names_nothing(j, n_msgs) != 0;
+    const uint64_t e = mtb_entry(j, n_msgs);             // mbls_mtb.h: the one statement of the rule, for a call's list and for a resident table alike
     const uint32_t* src = tab + e;
     uint32_t* dst = ws.w + (uint64_t)MBLS_SLOT_H * 12 * ws.stride + i;
 #pragma unroll 8

@@ -1,6 +1,7 @@
 // mbls_stream.hip -- the verification stream (include/mbls.h, "verification stream"): calls of any size in, full-round launches of the
 // public device entries out. Built on the public ABI only: mbls_ctx_get_limits, mbls_ctx_reserve[_keys], mbls_plan_workspace_items and the
-// three *_device verification entries, so every result comes out of the same verify_pipeline the parity tests pin.
+// three *_device verification entries (a message-table stream: their `_msgtable_device` forms), so every result comes out of the same verify_pipeline the parity
+// tests pin. One hook below the ABI, not exported from the library: a message table counts the calls its streams hold (mblsi_msgtable_stream_calls), which mbls_msgtable_clear consults.
 //
 // Per stream: depth + 1 staging SLOTS (one round each: the open one and up to depth launched), one LAUNCHER thread that cuts the queue of
 // submitted calls into the open slot (stream_take, the rule mbls_stream_cut states as data), gathers the round's inputs into the slot on the
@@ -21,6 +22,9 @@
 #include <thread>
 #include <vector>
 #include "mbls_stream.h"
+
+// the table's count of calls that streams bound to it have taken and not completed (mbls_kernels.hip; mbls_msgtable_clear refuses while there are any)
+extern "C" __attribute__((visibility("hidden"))) void mblsi_msgtable_stream_calls(mbls_msgtable* t, long long delta);
 
 namespace {
 
@@ -102,6 +106,7 @@ struct slot {
 
 struct mbls_stream {
     mbls_ctx* ctx = nullptr; const mbls_keytable* tab = nullptr;
+    mbls_msgtable* mt = nullptr;                     // non-null: a message-table stream -- a call's "message bytes" are its uint32 table indices (msg_len = 4)
     int mode = 0, fmt = MBLS_PK_UNCOMPRESSED, dev = 0; size_t unit = 96;
     mbls_stream_opts o{};
     uint64_t meta_bytes = 0;
@@ -202,7 +207,16 @@ int launch_round(mbls_stream* s, slot& sl) {
     const uint32_t* d_pkoff = lay.keys_uniform ? nullptr : (const uint32_t*)(sl.d_meta + at_k);
     const uint32_t msg_len = lay.msgs_uniform ? lay.msg_len : 0, k = lay.keys_uniform ? lay.k : 0;
     int rc;
-    if (s->mode == MBLS_STREAM_VERIFY)
+    if (s->mt) {         // the staged "message bytes" are the items' table indices, dense in round order (every call has msg_len = 4 and no offsets)
+        const uint32_t* d_midx = (const uint32_t*)sl.d_msgs;
+        if (s->mode == MBLS_STREAM_VERIFY)
+            rc = mbls_verify_batch_msgtable_device(s->ctx, sl.d_sigs, s->mt, d_midx, sl.d_keys, s->fmt, n, sl.d_res, nullptr, sl.d_st, s->hs);
+        else if (s->tab)
+            rc = mbls_fast_aggregate_verify_batch_indexed_msgtable_device(s->ctx, s->tab, sl.d_sigs, s->mt, d_midx, (const uint32_t*)sl.d_keys, d_pkoff, n, k,
+                                                                          sl.d_res, nullptr, sl.d_st, s->hs);
+        else
+            rc = mbls_fast_aggregate_verify_batch_msgtable_device(s->ctx, sl.d_sigs, s->mt, d_midx, sl.d_keys, s->fmt, d_pkoff, n, k, sl.d_res, nullptr, sl.d_st, s->hs);
+    } else if (s->mode == MBLS_STREAM_VERIFY)
         rc = mbls_verify_batch_device(s->ctx, sl.d_sigs, sl.d_msgs, msg_len, d_moff, sl.d_keys, s->fmt, n, sl.d_res, nullptr, sl.d_st, s->hs);
     else if (s->tab)
         rc = mbls_fast_aggregate_verify_batch_indexed_device(s->ctx, s->tab, sl.d_sigs, sl.d_msgs, msg_len, d_moff, (const uint32_t*)sl.d_keys, d_pkoff, n, k,
@@ -299,6 +313,7 @@ void completer_main(mbls_stream* s) {
         sl.pieces.clear();
         while (!s->calls.empty() && s->calls.front()->ticket <= s->completed_through && s->calls.front()->ticket < s->cursor) {
             if (s->calls.front()->ev) s->ev_pool.push_back(s->calls.front()->ev);
+            if (s->mt) mblsi_msgtable_stream_calls(s->mt, -1);
             s->calls.pop_front(); s->base++;
         }
         s->inflight.pop_front(); s->free_slots.push_back(si);
@@ -321,10 +336,13 @@ void free_stream(mbls_stream* s) {
     delete s;
 }
 
-int submit(mbls_stream* s, bool host, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, const uint8_t* pks,
+int submit(mbls_stream* s, bool msgidx, bool host, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, const uint8_t* pks,
            const uint32_t* idx, const uint32_t* poff, uint64_t n, uint32_t k, uint8_t* res, uint64_t* bm, uint32_t* st, void* stream, uint64_t* ticket) {
     if (!s) return MBLS_ERR_ARGUMENT;
     if (!ticket) return fail(s, MBLS_ERR_ARGUMENT, "null ticket pointer");
+    if (msgidx != (s->mt != nullptr))
+        return fail(s, MBLS_ERR_ARGUMENT, s->mt ? "a message-table stream takes message indices (mbls_stream_submit_msgidx[_device])"
+                                                : "this stream takes messages, not message-table indices (mbls_stream_submit[_device])");
     if (n == 0) return fail(s, MBLS_ERR_ARGUMENT, "a call holds at least one item");
     if (!sigs || !res) return fail(s, MBLS_ERR_ARGUMENT, "null buffer");
     if (s->mode == MBLS_STREAM_VERIFY && (poff || k != 1)) return fail(s, MBLS_ERR_ARGUMENT, "verify mode: one key per item (k = 1, no key offsets)");
@@ -367,6 +385,7 @@ int submit(mbls_stream* s, bool host, const uint8_t* sigs, const uint8_t* msgs, 
     }
     c->ticket = ++s->last_ticket;
     s->calls.push_back(c);
+    if (s->mt) mblsi_msgtable_stream_calls(s->mt, 1);
     s->stats.calls++; s->stats.items += n;
     *ticket = c->ticket;
     s->cv_launch.notify_one();
@@ -395,7 +414,7 @@ extern "C" int mbls_stream_cut(const mbls_stream_opts* o, const mbls_stream_call
     return np <= max_pieces || !out ? MBLS_OK : MBLS_ERR_ARGUMENT;
 }
 
-extern "C" int mbls_stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, const mbls_stream_opts* opts, mbls_stream** out) {
+static int stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, mbls_msgtable* mt, const mbls_stream_opts* opts, mbls_stream** out) {
     if (!ctx || !out) return MBLS_ERR_ARGUMENT;
     *out = nullptr;
     if (mode != MBLS_STREAM_FAST_AGGREGATE_VERIFY && mode != MBLS_STREAM_VERIFY) return MBLS_ERR_ARGUMENT;
@@ -404,17 +423,19 @@ extern "C" int mbls_stream_create(mbls_ctx* ctx, int mode, int pk_format, const 
     // a table of another context is refused by the indexed entry itself (an empty call enqueues nothing)
     if (t && mbls_fast_aggregate_verify_batch_indexed_device(ctx, t, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr))
         return MBLS_ERR_ARGUMENT;
+    // likewise a message table of another context, by the table entry itself
+    if (mt && mbls_verify_batch_msgtable_device(ctx, nullptr, mt, nullptr, nullptr, MBLS_PK_UNCOMPRESSED, 0, nullptr, nullptr, nullptr, nullptr)) return MBLS_ERR_ARGUMENT;
     mbls_limits L; int rc = mbls_ctx_get_limits(ctx, &L); if (rc) return rc;
     mbls_stream_opts o = opts ? *opts : mbls_stream_opts{};
     if (o.policy != MBLS_STREAM_WORK_CONSERVING && o.policy != MBLS_STREAM_FULL_ROUNDS) return MBLS_ERR_ARGUMENT;
     if (!o.round_items) o.round_items = L.round_items;
     if (!o.round_keys) o.round_keys = (mode == MBLS_STREAM_VERIFY ? 1 : 128) * o.round_items;
-    if (!o.round_msg_bytes) o.round_msg_bytes = 64 * o.round_items;
+    if (!o.round_msg_bytes) o.round_msg_bytes = (mt ? 4 : 64) * o.round_items;
     if (!o.depth) o.depth = 2;
     if (o.round_items > (1ull << 31) || o.round_keys > 0xFFFFFFFFull || o.depth > 64) return MBLS_ERR_ARGUMENT;    // key offsets of a round are 32-bit
     mbls_stream* s = new (std::nothrow) mbls_stream();
     if (!s) return MBLS_ERR_DEVICE;
-    s->ctx = ctx; s->tab = t; s->mode = mode; s->fmt = t ? MBLS_PK_UNCOMPRESSED : pk_format; s->o = o;
+    s->ctx = ctx; s->tab = t; s->mt = mt; s->mode = mode; s->fmt = t ? MBLS_PK_UNCOMPRESSED : pk_format; s->o = o;
     s->unit = t ? 4 : (pk_format == MBLS_PK_COMPRESSED ? 48 : 96);
     // every round size's workspace up front (a partial round on the wave engine may take the eight-lane key sum, n + 8 n items): no round grows it
     uint64_t ws = 0;
@@ -459,6 +480,14 @@ extern "C" int mbls_stream_create(mbls_ctx* ctx, int mode, int pk_format, const 
     return MBLS_OK;
 }
 
+extern "C" int mbls_stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, const mbls_stream_opts* opts, mbls_stream** out) {
+    return stream_create(ctx, mode, pk_format, t, nullptr, opts, out);
+}
+extern "C" int mbls_stream_create_msgtable(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, mbls_msgtable* mt, const mbls_stream_opts* opts, mbls_stream** out) {
+    if (!mt) return MBLS_ERR_ARGUMENT;
+    return stream_create(ctx, mode, pk_format, t, mt, opts, out);
+}
+
 extern "C" void mbls_stream_destroy(mbls_stream* s) {
     if (!s) return;
     {
@@ -481,13 +510,24 @@ extern "C" const char* mbls_stream_last_error(mbls_stream* s) { return s ? s->er
 extern "C" int mbls_stream_submit_device(mbls_stream* s, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* h_msg_offsets,
                                          const uint8_t* d_pks, const uint32_t* d_key_idx, const uint32_t* h_pk_offsets, uint64_t n, uint32_t k,
                                          uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream, uint64_t* ticket) {
-    return submit(s, false, d_sigs, d_msgs, msg_len, h_msg_offsets, d_pks, d_key_idx, h_pk_offsets, n, k, d_results, d_bitmap, d_status, stream, ticket);
+    return submit(s, false, false, d_sigs, d_msgs, msg_len, h_msg_offsets, d_pks, d_key_idx, h_pk_offsets, n, k, d_results, d_bitmap, d_status, stream, ticket);
 }
 
 extern "C" int mbls_stream_submit(mbls_stream* s, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* msg_offsets,
                                   const uint8_t* pks, const uint32_t* key_idx, const uint32_t* pk_offsets, uint64_t n, uint32_t k,
                                   uint8_t* results, uint32_t* status, uint64_t* ticket) {
-    return submit(s, true, sigs, msgs, msg_len, msg_offsets, pks, key_idx, pk_offsets, n, k, results, nullptr, status, nullptr, ticket);
+    return submit(s, false, true, sigs, msgs, msg_len, msg_offsets, pks, key_idx, pk_offsets, n, k, results, nullptr, status, nullptr, ticket);
+}
+
+// message-table streams: the index array travels as the call's message bytes, 4 per item
+extern "C" int mbls_stream_submit_msgidx_device(mbls_stream* s, const uint8_t* d_sigs, const uint32_t* d_msg_idx, const uint8_t* d_pks, const uint32_t* d_key_idx,
+                                                const uint32_t* h_pk_offsets, uint64_t n, uint32_t k, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status,
+                                                void* stream, uint64_t* ticket) {
+    return submit(s, true, false, d_sigs, (const uint8_t*)d_msg_idx, 4, nullptr, d_pks, d_key_idx, h_pk_offsets, n, k, d_results, d_bitmap, d_status, stream, ticket);
+}
+extern "C" int mbls_stream_submit_msgidx(mbls_stream* s, const uint8_t* sigs, const uint32_t* msg_idx, const uint8_t* pks, const uint32_t* key_idx,
+                                         const uint32_t* pk_offsets, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status, uint64_t* ticket) {
+    return submit(s, true, true, sigs, (const uint8_t*)msg_idx, 4, nullptr, pks, key_idx, pk_offsets, n, k, results, nullptr, status, nullptr, ticket);
 }
 
 extern "C" int mbls_stream_flush(mbls_stream* s) {

@@ -4,6 +4,11 @@
         t = vs.submit_device(d_sigs, d_msgs, d_pks, n, k, d_results, msg_len=32)       # device tensors or pointers
         h = vs.submit(sigs, msgs, pks, n, k, msg_len=32)                                # host bytes -> HostTicket
         vs.wait(t); results, status = h.result()
+
+Over a resident message table (N.MsgTable) a call names its messages by table index:
+
+    with VerifyStream(ctx, pk_format=PK_UNCOMPRESSED, msg_table=mt) as vs:
+        t = vs.submit_device(d_sigs, d_msg_idx, d_pks, n, k, d_results)                 # uint32 indices where the messages were
 """
 import ctypes as C
 from collections import deque
@@ -48,18 +53,24 @@ class HostTicket:
 
 
 class VerifyStream:
-    """One stream on one context: mode STREAM_FAST_AGGREGATE_VERIFY / STREAM_VERIFY; keys as pk_format bytes, or indices into `table` (a KeyTable)."""
+    """One stream on one context: mode STREAM_FAST_AGGREGATE_VERIFY / STREAM_VERIFY; keys as pk_format bytes, or indices into `table` (a KeyTable); messages as bytes, or --
+    msg_table given (a MsgTable) -- as uint32 indices into it: submit / submit_device then take the index array where they took the messages."""
 
     def __init__(self, ctx=None, mode=N.STREAM_FAST_AGGREGATE_VERIFY, pk_format=N.PK_UNCOMPRESSED, table=None, round_items=0, round_keys=0, round_msg_bytes=0,
-                 depth=0, policy=N.STREAM_WORK_CONSERVING):
+                 depth=0, policy=N.STREAM_WORK_CONSERVING, msg_table=None):
         self.ctx = ctx or N.default_context()          # held: the stream is destroyed before its context
         self.table = table
         self.indexed = table is not None
         self._h = N.vp()
         o = N.StreamOpts(round_items, round_keys, round_msg_bytes, depth, policy)
-        rc = N.lib().mbls_stream_create(self.ctx.handle, mode, pk_format, table.handle if table is not None else None, C.byref(o), C.byref(self._h))
+        self.msg_table = msg_table                     # held: the stream is destroyed before its message table
+        th = table.handle if table is not None else None
+        if msg_table is not None:
+            rc = N.lib().mbls_stream_create_msgtable(self.ctx.handle, mode, pk_format, th, msg_table.handle, C.byref(o), C.byref(self._h))
+        else:
+            rc = N.lib().mbls_stream_create(self.ctx.handle, mode, pk_format, th, C.byref(o), C.byref(self._h))
         if rc != N.OK:
-            raise N.MblsError(rc, "mbls_stream_create: " + self.ctx.last_error())
+            raise N.MblsError(rc, ("mbls_stream_create_msgtable: " if msg_table is not None else "mbls_stream_create: ") + self.ctx.last_error())
         self._live = deque()                           # (ticket, buffers) kept alive until the call completes
 
     def close(self):
@@ -103,6 +114,13 @@ class VerifyStream:
         hs = getattr(stream, "cuda_stream", stream)
         t = C.c_uint64(0)
         kp = _ptr(keys)
+        if self.msg_table is not None:
+            if msg_len or msg_offsets is not None:
+                raise ValueError("a message-table stream takes uint32 message indices: no msg_len, no msg_offsets")
+            self.check(N.lib().mbls_stream_submit_msgidx_device(self._h, _ptr(sigs), _ptr(msgs), None if self.indexed else kp, kp if self.indexed else None, po,
+                                                                n, k, _ptr(results), _ptr(bitmap), _ptr(status), hs, C.byref(t)))
+            self._keep(t.value, (po, sigs, msgs, keys, results, bitmap, status))
+            return t.value
         self.check(N.lib().mbls_stream_submit_device(self._h, _ptr(sigs), _ptr(msgs), msg_len, mo, None if self.indexed else kp, kp if self.indexed else None, po,
                                                      n, k, _ptr(results), _ptr(bitmap), _ptr(status), hs, C.byref(t)))
         self._keep(t.value, (mo, po, sigs, msgs, keys, results, bitmap, status))
@@ -112,11 +130,17 @@ class VerifyStream:
         """host bytes or numpy arrays (keys: key bytes, or uint32 table indices for a key-table stream; numpy arrays are read in place, when the
         call's round launches) -> HostTicket"""
         import numpy as np
-        (sa, sp), (ma, mp) = _host(sigs, np.uint8), _host(msgs, np.uint8)
+        (sa, sp), (ma, mp) = _host(sigs, np.uint8), _host(msgs, np.uint32 if self.msg_table is not None else np.uint8)
         ka, kp = _host(keys, np.uint32 if self.indexed else np.uint8)
         mo, po = _offsets(msg_offsets, C.c_uint64), _offsets(pk_offsets, C.c_uint32)
         res, st = N.outbuf(n), (C.c_uint32 * max(1, n))()
         t = C.c_uint64(0)
+        if self.msg_table is not None:
+            if msg_len or msg_offsets is not None:
+                raise ValueError("a message-table stream takes uint32 message indices: no msg_len, no msg_offsets")
+            self.check(N.lib().mbls_stream_submit_msgidx(self._h, sp, mp, None if self.indexed else kp, kp if self.indexed else None, po, n, k, res, st, C.byref(t)))
+            self._keep(t.value, (sa, ma, ka, po, res, st))
+            return HostTicket(self, t.value, res, st, n)
         self.check(N.lib().mbls_stream_submit(self._h, sp, mp, msg_len, mo, None if self.indexed else kp, kp if self.indexed else None, po, n, k, res, st, C.byref(t)))
         self._keep(t.value, (sa, ma, ka, mo, po, res, st))
         return HostTicket(self, t.value, res, st, n)

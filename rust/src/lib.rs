@@ -47,6 +47,28 @@ pub struct MblsCtx {
 pub struct MblsKeyTable {
     _p: [u8; 0],
 }
+// (the C names, as include/mbls.h spells them: tests/test_build_cpu.py compares these declarations with the header type by type)
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct mbls_msgtable {
+    _p: [u8; 0],
+}
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct mbls_stream {
+    _p: [u8; 0],
+}
+/// `mbls_stream_opts` (0 = default)
+#[allow(non_camel_case_types)]
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mbls_stream_opts {
+    pub round_items: u64,
+    pub round_keys: u64,
+    pub round_msg_bytes: u64,
+    pub depth: u32,
+    pub policy: u32,
+}
 extern "C" {
     fn mbls_ctx_create(out: *mut *mut MblsCtx, device_id: c_int) -> c_int;
     fn mbls_last_error(ctx: *mut MblsCtx) -> *const c_char;
@@ -141,6 +163,26 @@ extern "C" {
                                                 key_idx: *const u32, offsets: *const u32, n: u64, k: u32, results: *mut u8, status: *mut u32) -> c_int;
     // shared message lists (include/mbls.h): n_msgs messages, one index per item; every listed message is hashed once
     fn mbls_ctx_reserve_msgs(ctx: *mut MblsCtx, max_msgs: u64) -> c_int;
+    // resident message table: hash a message once, verify against it in any call or stream
+    fn mbls_msgtable_create(ctx: *mut MblsCtx, capacity_hint: u64, out: *mut *mut mbls_msgtable) -> c_int;
+    fn mbls_msgtable_destroy(t: *mut mbls_msgtable);
+    fn mbls_msgtable_size(t: *const mbls_msgtable) -> u64;
+    fn mbls_msgtable_append(t: *mut mbls_msgtable, msgs: *const u8, msg_len: u32, msg_offsets: *const u64, n: u64, first_index: *mut u64) -> c_int;
+    fn mbls_msgtable_get(t: *mut mbls_msgtable, first_index: u64, n: u64, out96: *mut u8, errs: *mut u8) -> c_int;
+    fn mbls_msgtable_clear(t: *mut mbls_msgtable) -> c_int;
+    fn mbls_fast_aggregate_verify_batch_msgtable(ctx: *mut MblsCtx, sigs: *const u8, mt: *const mbls_msgtable, msg_idx: *const u32, pks: *const u8, pk_format: c_int,
+                                                 pk_offsets: *const u32, n: u64, k: u32, results: *mut u8, status: *mut u32) -> c_int;
+    fn mbls_verify_batch_msgtable(ctx: *mut MblsCtx, sigs: *const u8, mt: *const mbls_msgtable, msg_idx: *const u32, pks: *const u8, pk_format: c_int, n: u64,
+                                  results: *mut u8, status: *mut u32) -> c_int;
+    fn mbls_fast_aggregate_verify_batch_indexed_msgtable(ctx: *mut MblsCtx, t: *const MblsKeyTable, sigs: *const u8, mt: *const mbls_msgtable, msg_idx: *const u32,
+                                                         key_idx: *const u32, offsets: *const u32, n: u64, k: u32, results: *mut u8, status: *mut u32) -> c_int;
+    fn mbls_stream_create_msgtable(ctx: *mut MblsCtx, mode: c_int, pk_format: c_int, t: *const MblsKeyTable, mt: *mut mbls_msgtable, opts: *const mbls_stream_opts,
+                                   out: *mut *mut mbls_stream) -> c_int;
+    fn mbls_stream_submit_msgidx(s: *mut mbls_stream, sigs: *const u8, msg_idx: *const u32, pks: *const u8, key_idx: *const u32, pk_offsets: *const u32, n: u64, k: u32,
+                                 results: *mut u8, status: *mut u32, ticket: *mut u64) -> c_int;
+    fn mbls_stream_flush(s: *mut mbls_stream) -> c_int;
+    fn mbls_stream_wait(s: *mut mbls_stream, ticket: u64) -> c_int;
+    fn mbls_stream_destroy(s: *mut mbls_stream);
     fn mbls_fast_aggregate_verify_batch_shared_msgs(ctx: *mut MblsCtx, sigs: *const u8, msgs: *const u8, msg_len: u32, msg_offsets: *const u64, n_msgs: u64,
                                                     msg_idx: *const u32, pks: *const u8, pk_format: c_int, pk_offsets: *const u32, n: u64, k: u32,
                                                     results: *mut u8, status: *mut u32) -> c_int;
@@ -1125,6 +1167,179 @@ pub fn fast_aggregate_verify_batch_shared_msgs(signatures: &[AggregateSignature]
 impl Drop for KeyTable {
     fn drop(&mut self) {
         unsafe { mbls_keytable_destroy(self.h) }
+    }
+}
+
+/// Hashed messages resident in GPU memory (`mbls_msgtable_*`; not part of the reference's API): every appended message is hashed to G2 once, and
+/// verifications -- the functions below, `KeyTable::fast_aggregate_verify_msgtable`, or the calls of a `MessageTableStream` -- name their messages by
+/// index, in any later call. Indices start at 0 and never change until `clear`. Drop the table after the streams made over it.
+pub struct MessageTable {
+    h: *mut mbls_msgtable,
+}
+unsafe impl Send for MessageTable {}
+unsafe impl Sync for MessageTable {}
+impl MessageTable {
+    pub fn new(capacity_hint: u64) -> Self {
+        let mut h: *mut mbls_msgtable = std::ptr::null_mut();
+        let rc = unsafe { mbls_msgtable_create(ctx(), capacity_hint, &mut h) };
+        if rc != 0 {
+            err(rc);
+        }
+        MessageTable { h }
+    }
+    pub fn len(&self) -> u64 {
+        unsafe { mbls_msgtable_size(self.h) }
+    }
+    pub fn is_empty(&self) -> bool {
+        self.len() == 0
+    }
+    /// Appends messages of any length each; returns the index of the first (message j is entry first + j).
+    pub fn append(&mut self, messages: &[&[u8]]) -> u64 {
+        let mut msgs: Vec<u8> = Vec::new();
+        let mut moff: Vec<u64> = vec![0];
+        for m in messages {
+            msgs.extend_from_slice(m);
+            moff.push(msgs.len() as u64);
+        }
+        let mut first = 0u64;
+        let rc = unsafe { mbls_msgtable_append(self.h, msgs.as_ptr(), 0, moff.as_ptr(), messages.len() as u64, &mut first) };
+        if rc != 0 {
+            err(rc);
+        }
+        first
+    }
+    /// The compressed point of entry `index`: what hash_to_curve gives for its message.
+    pub fn get(&self, index: u64) -> [u8; 96] {
+        let mut p = [0u8; 96];
+        let mut e = 0u8;
+        let rc = unsafe { mbls_msgtable_get(self.h, index, 1, p.as_mut_ptr(), &mut e) };
+        if rc != 0 || e != 0 {
+            err(if rc != 0 { rc } else { e as c_int });
+        }
+        p
+    }
+    /// Size back to 0, capacity kept. `false`: refused, a stream made over the table has calls that have not completed.
+    pub fn clear(&mut self) -> bool {
+        unsafe { mbls_msgtable_clear(self.h) == 0 }
+    }
+    /// n x `AggregateSignature::fast_aggregate_verify`, keys as decoded `PublicKey`s: item i = (signatures[i], entry message_indices[i], keys[i]). Nothing is hashed.
+    pub fn fast_aggregate_verify(&self, signatures: &[AggregateSignature], message_indices: &[u32], keys: &[&[&PublicKey]]) -> Vec<bool> {
+        let n = signatures.len();
+        assert!(message_indices.len() == n && keys.len() == n);
+        assert!(message_indices.iter().all(|&j| (j as u64) < self.len()));
+        let sigs: Vec<u8> = signatures.iter().flat_map(|s| s.point.iter().copied()).collect();
+        let mut pks: Vec<u8> = Vec::new();
+        let mut koff: Vec<u32> = vec![0];
+        for ks in keys {
+            for k in ks.iter() {
+                pks.extend_from_slice(&k.point);
+            }
+            koff.push((pks.len() / 96) as u32);
+        }
+        let mut res = vec![0u8; n.max(1)];
+        let rc = unsafe {
+            mbls_fast_aggregate_verify_batch_msgtable(ctx(), sigs.as_ptr(), self.h, message_indices.as_ptr(), pks.as_ptr(), PK_UNCOMPRESSED, koff.as_ptr(), n as u64, 0,
+                                                      res.as_mut_ptr(), std::ptr::null_mut())
+        };
+        if rc != 0 {
+            err(rc);
+        }
+        res.truncate(n);
+        res.into_iter().map(|b| b == 1).collect()
+    }
+    /// n x `Signature::verify`: item i = (signatures[i], entry message_indices[i], keys[i]).
+    pub fn verify(&self, signatures: &[Signature], message_indices: &[u32], keys: &[&PublicKey]) -> Vec<bool> {
+        let n = signatures.len();
+        assert!(message_indices.len() == n && keys.len() == n);
+        assert!(message_indices.iter().all(|&j| (j as u64) < self.len()));
+        let sigs: Vec<u8> = signatures.iter().flat_map(|s| s.point.iter().copied()).collect();
+        let pks: Vec<u8> = keys.iter().flat_map(|k| k.point.iter().copied()).collect();
+        let mut res = vec![0u8; n.max(1)];
+        let rc = unsafe {
+            mbls_verify_batch_msgtable(ctx(), sigs.as_ptr(), self.h, message_indices.as_ptr(), pks.as_ptr(), PK_UNCOMPRESSED, n as u64, res.as_mut_ptr(), std::ptr::null_mut())
+        };
+        if rc != 0 {
+            err(rc);
+        }
+        res.truncate(n);
+        res.into_iter().map(|b| b == 1).collect()
+    }
+}
+impl Drop for MessageTable {
+    fn drop(&mut self) {
+        unsafe { mbls_msgtable_destroy(self.h) }
+    }
+}
+impl KeyTable {
+    /// n x fast_aggregate_verify with `k` key-table indices per item and one message-table index per item.
+    pub fn fast_aggregate_verify_msgtable(&self, signatures: &[AggregateSignature], table: &MessageTable, message_indices: &[u32], key_indices: &[u32], k: u32) -> Vec<bool> {
+        let n = signatures.len();
+        assert!(message_indices.len() == n && key_indices.len() == n * k as usize);
+        assert!(message_indices.iter().all(|&j| (j as u64) < table.len()));
+        let sigs: Vec<u8> = signatures.iter().flat_map(|s| s.point.iter().copied()).collect();
+        let mut res = vec![0u8; n.max(1)];
+        let rc = unsafe {
+            mbls_fast_aggregate_verify_batch_indexed_msgtable(ctx(), self.h, sigs.as_ptr(), table.h, message_indices.as_ptr(), key_indices.as_ptr(), std::ptr::null(), n as u64, k,
+                                                              res.as_mut_ptr(), std::ptr::null_mut())
+        };
+        if rc != 0 {
+            err(rc);
+        }
+        res.truncate(n);
+        res.into_iter().map(|b| b == 1).collect()
+    }
+}
+/// A verification stream over a `MessageTable` (`mbls_stream_create_msgtable`): calls of any size are packed into full-round launches, and a call names its
+/// messages by table index. `verify` submits one call and waits for it; calls from several threads share the rounds. Drop the stream before its table.
+pub struct MessageTableStream {
+    h: *mut mbls_stream,
+}
+unsafe impl Send for MessageTableStream {}
+unsafe impl Sync for MessageTableStream {}
+impl MessageTableStream {
+    pub fn new(table: &mut MessageTable, opts: mbls_stream_opts) -> Self {
+        let mut h: *mut mbls_stream = std::ptr::null_mut();
+        let rc = unsafe { mbls_stream_create_msgtable(ctx(), 0, PK_UNCOMPRESSED, std::ptr::null(), table.h, &opts, &mut h) };
+        if rc != 0 {
+            err(rc);
+        }
+        MessageTableStream { h }
+    }
+    /// n x fast_aggregate_verify: item i = (signatures[i], entry message_indices[i], keys[i]); an index the table does not hold when the call's round
+    /// launches rejects its item.
+    pub fn verify(&self, signatures: &[AggregateSignature], message_indices: &[u32], keys: &[&[&PublicKey]]) -> Vec<bool> {
+        let n = signatures.len();
+        assert!(n > 0 && message_indices.len() == n && keys.len() == n);
+        let sigs: Vec<u8> = signatures.iter().flat_map(|s| s.point.iter().copied()).collect();
+        let mut pks: Vec<u8> = Vec::new();
+        let mut koff: Vec<u32> = vec![0];
+        for ks in keys {
+            for k in ks.iter() {
+                pks.extend_from_slice(&k.point);
+            }
+            koff.push((pks.len() / 96) as u32);
+        }
+        let mut res = vec![0u8; n];
+        let mut ticket = 0u64;
+        let mut rc = unsafe {
+            mbls_stream_submit_msgidx(self.h, sigs.as_ptr(), message_indices.as_ptr(), pks.as_ptr(), std::ptr::null(), koff.as_ptr(), n as u64, 0, res.as_mut_ptr(),
+                                      std::ptr::null_mut(), &mut ticket)
+        };
+        if rc == 0 {
+            rc = unsafe { mbls_stream_wait(self.h, ticket) };       // the buffers above stay valid until the call completes
+        }
+        if rc != 0 {
+            err(rc);
+        }
+        res.into_iter().map(|b| b == 1).collect()
+    }
+    pub fn flush(&self) {
+        unsafe { mbls_stream_flush(self.h) };
+    }
+}
+impl Drop for MessageTableStream {
+    fn drop(&mut self) {
+        unsafe { mbls_stream_destroy(self.h) }
     }
 }
 
