@@ -25,6 +25,7 @@
 #include "mbls_vms.h"
 #include "mbls_vsl.h"
 #include "mbls_mtb.h"
+#include "mbls_batch.h"
 #include "../../include/mbls.h"
 
 // The product library exists only with the generated routines: the host side below selects kernels (the fused subgroup verdict of
@@ -1544,17 +1545,24 @@ static int ws_release(mbls_ctx* c, hipStream_t s) {
     HIPCHK(c, hipEventRecord(c->ws_ev, s)); c->ws_stream = s; c->ws_pending = true; return MBLS_OK;
 }
 
-// where an item's public keys come from
-struct keysrc {
-    const uint8_t* d_pks = nullptr; int fmt = MBLS_PK_UNCOMPRESSED; const uint32_t* d_off = nullptr;      // wire bytes
-    const uint32_t* d_recs = nullptr; uint64_t tsize = 0; const uint32_t* d_idx = nullptr; bool indexed = false;   // key table
-    const mbls_keytable* tab = nullptr;
-};
 // readers of a key table on stream s wait (on the device) for the last asynchronous append made on another stream
 static int table_acquire(mbls_ctx* c, const mbls_keytable* t, hipStream_t s) {
     if (t && t->pending && t->ev_stream != s) HIPCHK(c, hipStreamWaitEvent(s, t->ev, 0));
     return MBLS_OK;
 }
+static int msgtable_acquire(mbls_ctx* c, const mbls_msgtable* t, hipStream_t s) {
+    if (t->pending && t->ev_stream != s) HIPCHK(c, hipStreamWaitEvent(s, t->ev, 0));
+    return MBLS_OK;
+}
+// the key source of an _indexed entry: the table at the size it has now (the caller holds the context's lock)
+static int keys_of_table(mbls_ctx* c, const mbls_keytable* t, const uint32_t* d_idx, const uint32_t* d_off, keysrc* ks) {
+    if (t->c != c) ARGFAIL(c, "key table belongs to another context");
+    *ks = keys_table(t->d_recs, t->size, d_idx, d_off, t); return MBLS_OK;
+}
+// The message source of a _msgtable entry. The entry hands over the indices alone (msgs_in_table): what the table holds lives in its handle until verify_device /
+// verify_host, under the context's lock and once they know the table is this context's, read it at the size it has then (msgs_of_table).
+static msgsrc msgs_in_table(const uint32_t* d_idx) { return msgs_table(nullptr, 0, nullptr, 0, d_idx); }
+static msgsrc msgs_of_table(const mbls_msgtable* t, const uint32_t* d_idx) { return msgs_table(t->d_tab, mtb_stride(t->cap), t->d_flag, t->size, d_idx); }
 
 // ---- routing as data (include/mbls.h, mbls_plan_batch): the decisions of the verification pipeline as pure functions of the limits and the batch size. The
 // pipeline below acts on exactly these structures, so what mbls_plan_batch reports is what runs.
@@ -1752,14 +1760,6 @@ static uint64_t pass_ws_items(const mbls_pass_plan& pp, const keysrc& ks, uint32
     const uint64_t split = pass_key_split(pp, ks, k) ? n + n * MBLS_KEY_SPLIT : 0;
     return split > pp.workspace_items ? split : pp.workspace_items;
 }
-// where an item's message comes from when the call carries a shared list: index i of d_idx names a message of the list, whose points are (or, `list` given, are
-// put by this pass's message phase) in the context's table
-struct msgsrc {
-    const uint32_t* d_idx = nullptr; uint64_t n_msgs = 0;
-    const mbls_shared_msgs_plan* list = nullptr;      // non-null: the pass hashes the list itself (a one-pass plan: on its message stream, beside the other front phases)
-    // the table the gather reads: the context's own (a call's list) or a resident one (mbls_msgtable: n_msgs is then its size when the call was enqueued)
-    const uint32_t* tab = nullptr; uint64_t tstride = 0; const uint32_t* flags = nullptr;
-};
 // where the points of a hashed list go: the context's per-call table, or a resident table behind the entries it already holds
 struct htab_dst { uint32_t* tab; uint64_t tstride; uint32_t* flags; uint32_t* st; uint64_t first_entry; };
 // the hash of the list on stream s: piece after piece through launch_hash in workspace items [0, piece), each followed by its export to the table; first of all,
@@ -1790,14 +1790,16 @@ static int shared_hash_list(mbls_ctx* c, const mbls_shared_msgs_plan& sp, const 
     return MBLS_OK;
 }
 static track track0(mbls_ctx* c) { track t; t.sb = c->hs_b; t.sc = c->hs_c; t.sd = c->hs_d; t.ev2 = c->hs_ev2; t.ev3 = c->hs_ev3; return t; }
-static int verify_pipeline_one(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const keysrc& ks,
-                               uint64_t n, uint32_t k, int mode, uint8_t* d_results, uint64_t* d_bitmap,
-                               uint32_t* d_status, hipStream_t s, int part = 0, const track* tkp = nullptr, bool no_growth = false, const msgsrc* ms = nullptr) {
+static int verify_pipeline_one(mbls_ctx* c, const batch& b, hipStream_t s, int part = 0, const track* tkp = nullptr, bool no_growth = false) {
+    const keysrc& ks = b.ks; const msgsrc& ms = b.ms;
+    const uint8_t* const d_sigs = b.d_sigs; uint8_t* const d_results = b.d_results; uint64_t* const d_bitmap = b.d_bitmap; uint32_t* const d_status = b.d_status;
+    const uint64_t n = b.n; const uint32_t k = b.k; const int mode = b.mode;
     const int fmt = ks.fmt; const uint32_t* d_off = ks.d_off;
     if (!c || (fmt != MBLS_PK_COMPRESSED && fmt != MBLS_PK_UNCOMPRESSED)) return MBLS_ERR_ARGUMENT;
     if (n == 0) return MBLS_OK;
     const bool have_keys = ks.indexed ? (ks.d_idx != nullptr) : (ks.d_pks != nullptr);
-    if (!d_sigs || (!ms && !d_msgs && msg_len && !d_moff) || (ms && !ms->d_idx) || !d_results || (!have_keys && (k || d_off) && part != 1)) ARGFAIL(c, "null buffer");
+    if (!d_sigs || (!ms.indexed() && !ms.d_msgs && ms.msg_len && !ms.d_moff) || (ms.indexed() && !ms.d_idx) || !d_results || (!have_keys && (k || d_off) && part != 1))
+        ARGFAIL(c, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
     const track tk = tkp ? *tkp : track0(c);
     bool tm = c->timing;
@@ -1852,9 +1854,9 @@ static int verify_pipeline_one(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t
     };
     // the message phase: the items' own messages through launch_hash, or -- a shared list -- [the hash of the list and its export, then] the gather from the table
     auto launch_msg = [&]() -> int {
-        if (!ms) { launch_hash(c, ws, d_msgs, msg_len, d_moff, st, n, s_msg, hash_pairs, hform); return MBLS_OK; }
-        if (ms->list) { const int rl = shared_hash_list(c, *ms->list, d_msgs, msg_len, d_moff, ms->n_msgs, s_msg); if (rl) return rl; }
-        hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, ms->tab, ms->tstride, ms->flags, ms->d_idx, ms->n_msgs, st, n);
+        if (!ms.indexed()) { launch_hash(c, ws, ms.d_msgs, ms.msg_len, ms.d_moff, st, n, s_msg, hash_pairs, hform); return MBLS_OK; }
+        if (ms.list) { const int rl = shared_hash_list(c, *ms.list, ms.d_msgs, ms.msg_len, ms.d_moff, ms.n_msgs, s_msg); if (rl) return rl; }
+        hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, ms.tab, ms.tstride, ms.flags, ms.d_idx, ms.n_msgs, st, n);
         return MBLS_OK;
     };
     if (part == 1) {
@@ -1920,52 +1922,32 @@ static int verify_pipeline_one(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t
     HIPCHK(c, hipGetLastError());
     return tk.ws_sync ? ws_release(c, s) : MBLS_OK;
 }
-// Items [lo, n) of a batch as a batch of their own: uniform layouts advance the base pointers, offset tables are absolute (their slice goes
-// with the unmoved base); lo is a multiple of 64, so the bitmap advances by whole words.
-static int verify_pipeline_from(mbls_ctx* c, uint64_t lo, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const keysrc& ks,
-                                uint64_t n, uint32_t k, int mode, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, hipStream_t s, const track* tk = nullptr,
-                                bool no_growth = false, const msgsrc* ms = nullptr) {
-    keysrc t = ks;
-    if (ms) {            // a shared list: the indices advance with the items, the list (hashed before the first pass) does not
-        msgsrc m2 = *ms; m2.d_idx = ms->d_idx + lo; m2.list = nullptr;
-        if (ks.d_off) t.d_off = ks.d_off + lo;
-        else { const size_t u = ks.fmt == MBLS_PK_COMPRESSED ? 48 : 96; if (ks.d_pks) t.d_pks = ks.d_pks + u * (uint64_t)k * lo; if (ks.d_idx) t.d_idx = ks.d_idx + (uint64_t)k * lo; }
-        return verify_pipeline_one(c, d_sigs + 96 * lo, d_msgs, msg_len, d_moff, t, n - lo, k, mode, d_results + lo, d_bitmap ? d_bitmap + lo / 64 : nullptr,
-                                   d_status ? d_status + lo : nullptr, s, 0, tk, no_growth, &m2);
-    }
-    const size_t unit = ks.fmt == MBLS_PK_COMPRESSED ? 48 : 96;
-    if (ks.d_off) t.d_off = ks.d_off + lo;
-    else { if (ks.d_pks) t.d_pks = ks.d_pks + unit * (uint64_t)k * lo; if (ks.d_idx) t.d_idx = ks.d_idx + (uint64_t)k * lo; }
-    return verify_pipeline_one(c, d_sigs + 96 * lo, (d_moff || !d_msgs) ? d_msgs : d_msgs + (uint64_t)msg_len * lo, msg_len, d_moff ? d_moff + lo : nullptr, t,
-                               n - lo, k, mode, d_results + lo, d_bitmap ? d_bitmap + lo / 64 : nullptr, d_status ? d_status + lo : nullptr, s, 0, tk, no_growth);
-}
-// The batch as the caller sees it: plan_batch decides (see there), this function carries the plan out. Passes of one stage run side by side -- track 0 on the
-// caller's stream, track 1 on the context's second set of streams, forked from and joined to the caller's stream --, stages one after the other.
-static int verify_pipeline(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const keysrc& ks,
-                           uint64_t n, uint32_t k, int mode, uint8_t* d_results, uint64_t* d_bitmap,
-                           uint32_t* d_status, hipStream_t s, int part = 0, const msgsrc* ms = nullptr) {
-    if (!c || part != 0 || n == 0)
-        return verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, part, nullptr, false, ms);
-    mbls_batch_plan bp; plan_batch(ctx_limits(c), n, c->timing, c->timing, &bp);
-    if (bp.mode == MBLS_BATCH_ONE_PASS)
-        return verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, 0, nullptr, false, ms);
-    // one growth of the workspace (and of the staging of decompressed keys) for the whole plan: nothing may be reallocated under a pass in flight
-    // (a pass on the wave engine may take the eight-lane key sum: n + 8 n items -- pass_ws_items, the figure the pass itself acts on; the staging of decompressed keys
-    // is indexed by ITEM, so it follows the items' extent, not the partial sums')
-    uint64_t need = 0, need_items = 0;
+// One growth of the workspace (and of the staging of decompressed keys) for a whole plan, before its first pass is queued: nothing may be reallocated under a pass
+// in flight (a pass on the wave engine may take the eight-lane key sum: n + 8 n items -- pass_ws_items, the figure the pass itself acts on; the staging of
+// decompressed keys is indexed by ITEM, so it follows the items' extent, not the partial sums'). min_items: what the call needs besides (the hash of a list).
+static int reserve_plan(mbls_ctx* c, const mbls_batch_plan& bp, const keysrc& ks, uint32_t k, uint64_t min_items = 0) {
+    uint64_t need = min_items, need_items = 0;
     for (uint32_t i = 0; i < bp.n_passes; i++) {
         const uint64_t e = bp.pass[i].workspace_first + pass_ws_items(bp.pass[i], ks, k, bp.pass[i].items); if (e > need) need = e;
         const uint64_t ei = bp.pass[i].workspace_first + bp.pass[i].items; if (ei > need_items) need_items = ei;
     }
     int rc = mbls_ctx_reserve(c, need); if (rc) return rc;
-    if (!ks.indexed && ks.fmt == MBLS_PK_COMPRESSED && !ks.d_off && k > 1) { rc = reserve_keys(c, need_items * (uint64_t)k); if (rc) return rc; }
-    if (bp.mode == MBLS_BATCH_ROUNDS_THEN_REST) {
-        rc = verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, bp.pass[0].items, k, mode, d_results, d_bitmap, d_status, s, 0, nullptr, true, ms); if (rc) return rc;
-        return verify_pipeline_from(c, bp.pass[1].first_item, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, nullptr, true, ms);
-    }
+    if (!ks.indexed && ks.fmt == MBLS_PK_COMPRESSED && !ks.d_off && k > 1) return reserve_keys(c, need_items * (uint64_t)k);
+    return MBLS_OK;
+}
+// The batch as the caller sees it: plan_batch decides (see there), this function carries the plan out. Passes of one stage run side by side -- track 0 on the
+// caller's stream, track 1 on the context's second set of streams, forked from and joined to the caller's stream --, stages one after the other.
+static int verify_pipeline(mbls_ctx* c, const batch& b, hipStream_t s, int part = 0) {
+    if (!c || part != 0 || b.n == 0) return verify_pipeline_one(c, b, s, part);
+    mbls_batch_plan bp; plan_batch(ctx_limits(c), b.n, c->timing, c->timing, &bp);
+    if (bp.mode == MBLS_BATCH_ONE_PASS) return verify_pipeline_one(c, b, s);
+    int rc = reserve_plan(c, bp, b.ks, b.k); if (rc) return rc;
+    // a pass of the plan: the slice of its items, in the space reserved above
+    auto run = [&](const mbls_pass_plan& p, hipStream_t ps, const track* tk) { return verify_pipeline_one(c, slice(b, p.first_item, p.first_item + p.items), ps, 0, tk, true); };
+    if (bp.mode == MBLS_BATCH_ROUNDS_THEN_REST) { rc = run(bp.pass[0], s, nullptr); return rc ? rc : run(bp.pass[1], s, nullptr); }
     // two tracks: [rounds in front,] then two passes side by side
     uint32_t i = 0;
-    if (bp.n_passes == 3) { rc = verify_pipeline_one(c, d_sigs, d_msgs, msg_len, d_moff, ks, bp.pass[0].items, k, mode, d_results, d_bitmap, d_status, s, 0, nullptr, true, ms); if (rc) return rc; i = 1; }
+    if (bp.n_passes == 3) { rc = run(bp.pass[0], s, nullptr); if (rc) return rc; i = 1; }
     const mbls_pass_plan& pa = bp.pass[i]; const mbls_pass_plan& pb = bp.pass[i + 1];
     const bool side = bp.mode == MBLS_BATCH_ROUND_BESIDE_REST;
     const uint64_t fm = side ? ~0ull : (pa.front == MBLS_FRONT_IN_A_ROW ? 0 : c->fork_max_items);
@@ -1973,13 +1955,12 @@ static int verify_pipeline(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_
     HIPCHK(c, hipEventRecord(c->t1_ev, s)); HIPCHK(c, hipStreamWaitEvent(c->t1_s, c->t1_ev, 0));
     track ta = track0(c); ta.ws_sync = false; ta.fork_max = fm;
     track tb; tb.no_waves = side; tb.fork_max = fm; tb.ws_off = pb.workspace_first; tb.sb = c->t1_b; tb.sc = c->t1_c; tb.sd = c->t1_b; tb.ev2 = c->t1_ev2; tb.ev3 = c->t1_ev3; tb.ws_sync = false;
-    const uint64_t lo = pa.first_item, mid = pb.first_item;
     if (side) {          // the round first: its kernels fill the chip, the remainder's waves take what they leave between them
-        rc = verify_pipeline_from(c, lo, d_sigs, d_msgs, msg_len, d_moff, ks, mid, k, mode, d_results, d_bitmap, d_status, s, &ta, true, ms);
-        if (!rc) rc = verify_pipeline_from(c, mid, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, c->t1_s, &tb, true, ms);
+        rc = run(pa, s, &ta);
+        if (!rc) rc = run(pb, c->t1_s, &tb);
     } else {
-        rc = verify_pipeline_from(c, mid, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, c->t1_s, &tb, true, ms);
-        if (!rc) rc = verify_pipeline_from(c, lo, d_sigs, d_msgs, msg_len, d_moff, ks, mid, k, mode, d_results, d_bitmap, d_status, s, &ta, true, ms);
+        rc = run(pb, c->t1_s, &tb);
+        if (!rc) rc = run(pa, s, &ta);
     }
     // join: the caller's stream ends when both tracks have (also on an error path: nothing of the call stays in flight unordered)
     hipError_t e1 = hipEventRecord(c->t1_ev, c->t1_s), e2 = hipStreamWaitEvent(s, c->t1_ev, 0);
@@ -1991,20 +1972,53 @@ extern "C" int mbls_ctx_set_tracks(mbls_ctx* c, uint64_t min_rest_items, uint64_
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu); c->tracks_min_rest = min_rest_items; c->tracks_side_max = side_max_items; return MBLS_OK;
 }
+// The one way from the nine *_device entries (and from the host stager) into the pipeline. Per-item messages go straight to verify_pipeline. A shared list (the
+// call carries n_msgs messages and one index per item: include/mbls.h) is hashed once -- by the same launch_hash, in the form its size asks for (plan_shared) --, its
+// points go to the context's table (k_h_export_tab), and the message phase of every pass is the gather (k_h_gather): one-pass plans hash the list inside the pass,
+// on its message stream beside the key sum and the signatures; plans of several passes hash it on the caller's stream before the first pass. Everything is reserved
+// before anything is queued: the workspace for the larger of the items' plan and the list, the key staging, the table. A resident table (mt) is read at the size
+// it has now (the caller holds the context's lock); every stream of the call forks from s behind the table's last append, and nothing is hashed.
+static int verify_device(mbls_ctx* c, batch b, const mbls_msgtable* mt, hipStream_t s) {
+    msgsrc& ms = b.ms;
+    if (b.ks.fmt != MBLS_PK_COMPRESSED && b.ks.fmt != MBLS_PK_UNCOMPRESSED) return MBLS_ERR_ARGUMENT;
+    if (mt) {
+        if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
+        ms = msgs_of_table(mt, ms.d_idx);
+    }
+    if (!ms.indexed()) return verify_pipeline(c, b, s);
+    if (b.n == 0) return MBLS_OK;
+    if (ms.n_msgs > 0xFFFFFFFFull) ARGFAIL(c, "message indices are 32-bit");
+    if (!b.d_sigs || !ms.d_idx || !b.d_results || (ms.n_msgs && !ms.d_msgs && ms.msg_len && !ms.d_moff)) ARGFAIL(c, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (mt) {            // (verify_pipeline reserves the plan's workspace and key staging before it queues the first pass: there is no list to size here)
+        const int ra = msgtable_acquire(c, mt, s); if (ra) return ra;
+        return verify_pipeline(c, b, s);
+    }
+    mbls_shared_msgs_plan sp; plan_shared(ctx_limits(c), b.n, ms.n_msgs, c->timing, c->timing, &sp);
+    int rc = reserve_plan(c, sp.batch, b.ks, b.k, sp.list_workspace_items); if (rc) return rc;
+    rc = reserve_msgs(c, ms.n_msgs); if (rc) return rc;
+    ms.tab = c->d_htab; ms.tstride = c->htab_cap; ms.flags = c->d_hflag;
+    if (sp.batch.mode == MBLS_BATCH_ONE_PASS) ms.list = &sp;
+    else {
+        rc = ws_acquire(c, s); if (rc) return rc;
+        rc = shared_hash_list(c, sp, ms.d_msgs, ms.msg_len, ms.d_moff, ms.n_msgs, s); if (rc) return rc;
+    }
+    return verify_pipeline(c, b, s);
+}
 extern "C" int mbls_fast_aggregate_verify_batch_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len,
         const uint64_t* d_moff, const uint8_t* d_pks, int fmt, const uint32_t* d_off, uint64_t n, uint32_t k, uint8_t* d_results, uint64_t* d_bitmap,
         uint32_t* d_status, void* stream) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    keysrc ks; ks.d_pks = d_pks; ks.fmt = fmt; ks.d_off = d_off;
-    return verify_pipeline(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status, (hipStream_t)stream);
+    return verify_device(c, batch{d_sigs, msgs_per_item(d_msgs, msg_len, d_moff), keys_wire(d_pks, fmt, d_off), n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status},
+                         nullptr, (hipStream_t)stream);
 }
 extern "C" int mbls_verify_batch_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff,
         const uint8_t* d_pks, int fmt, uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    keysrc ks; ks.d_pks = d_pks; ks.fmt = fmt;
-    return verify_pipeline(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, 1, MBLS_MODE_VERIFY, d_results, d_bitmap, d_status, (hipStream_t)stream);
+    return verify_device(c, batch{d_sigs, msgs_per_item(d_msgs, msg_len, d_moff), keys_wire(d_pks, fmt, nullptr), n, 1, MBLS_MODE_VERIFY, d_results, d_bitmap, d_status},
+                         nullptr, (hipStream_t)stream);
 }
 
 // offsets of a ragged key / signature table handed over in host memory: non-decreasing, and the total fits the index type
@@ -2018,60 +2032,79 @@ static bool msg_offsets_ok(const uint64_t* off, uint64_t n) {
     return true;
 }
 
-// Host buffers in, results out. The keys (or key indices) are 99 % of the bytes: they are uploaded on a second stream while the
-// signature and message phases run.
-static int verify_host(mbls_ctx* c, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, const uint8_t* pks, int fmt,
-                       const mbls_keytable* tab, const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, int mode,
-                       uint8_t* results, uint32_t* status) {
+// Host buffers in, results out, for every per-item entry. `hm` describes the messages with HOST pointers: the items' own bytes, a list of n_msgs messages plus one
+// index per item, or indices into the resident table mt. The tables are checked here (a bad offset table or an index that names nothing refuses the call, nothing
+// enqueued), everything is staged through the context's buffers, and the pipeline runs on the context's stream. With per-item messages the keys (or key indices)
+// are 99 % of the bytes: they are uploaded on a second stream while the signature and message phases run.
+static int verify_host(mbls_ctx* c, const uint8_t* sigs, msgsrc hm, const mbls_msgtable* mt, const uint8_t* pks, int fmt, const mbls_keytable* tab,
+                       const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, int mode, uint8_t* results, uint32_t* status) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
+    if (mt) {            // the table's size and buffers are read under the lock: an append or a clear on another thread comes before or after the whole call
+        if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
+        hm = msgs_of_table(mt, hm.d_idx);
+    }
     if (n == 0) return MBLS_OK;
-    if (moff && !msg_offsets_ok(moff, n)) ARGFAIL(c, "msg_offsets must be non-decreasing, messages below 2^32 bytes");
+    const uint8_t* msgs = hm.d_msgs; const uint64_t* moff = hm.d_moff;
+    const uint64_t n_own = hm.kind == MBLS_MSGS_LIST ? hm.n_msgs : n;      // the messages whose bytes the call carries (a table's entries: none, msg_len = 0)
+    if (hm.kind == MBLS_MSGS_LIST && hm.n_msgs > 0xFFFFFFFFull) ARGFAIL(c, "message indices are 32-bit");
+    if (hm.indexed() && (!sigs || !hm.d_idx || !results)) ARGFAIL(c, "null buffer");
+    if (moff && !msg_offsets_ok(moff, n_own)) ARGFAIL(c, "msg_offsets must be non-decreasing, messages below 2^32 bytes");
+    if (hm.indexed())
+        for (uint64_t i = 0; i < n; i++)
+            if (mtb_names_nothing(hm.d_idx[i], hm.n_msgs)) ARGFAIL(c, mt ? "msg_idx names no entry of the message table" : "msg_idx names no message of the list");
     const uint64_t msg_first = moff ? moff[0] : 0;                       // the bytes this call uploads: msgs[msg_first .. msg_first + msg_total)
-    const size_t msg_total = moff ? (size_t)(moff[n] - moff[0]) : (size_t)msg_len * n;
+    const size_t msg_total = moff ? (size_t)(moff[n_own] - moff[0]) : (size_t)hm.msg_len * n_own;
     if (!sigs || (!msgs && msg_total) || !results) ARGFAIL(c, "null buffer");
     if (fmt != MBLS_PK_COMPRESSED && fmt != MBLS_PK_UNCOMPRESSED) ARGFAIL(c, "pk_format");
-    if (tab && tab->c != c) ARGFAIL(c, "key table belongs to another context");
+    keysrc ks = keys_wire(nullptr, fmt, nullptr);
+    if (tab) { const int rk = keys_of_table(c, tab, nullptr, nullptr, &ks); if (rk) return rk; }
     if (off && !offsets_ok(off, n)) ARGFAIL(c, "offsets must be non-decreasing");
     HIPCHK(c, hipSetDevice(c->device));
     // like the messages, a key offset table may start anywhere (a shard of a larger batch): only keys [off[0], off[n]) are uploaded
     const uint64_t key_first = off ? off[0] : 0;
-    uint64_t total_keys = off ? (uint64_t)(off[n] - off[0]) : (uint64_t)k * n;
+    const uint64_t total_keys = off ? (uint64_t)(off[n] - off[0]) : (uint64_t)k * n;
     const bool indexed = tab != nullptr;
     if (total_keys && !(indexed ? (const void*)idx : (const void*)pks)) ARGFAIL(c, "null key buffer");
-    size_t unit = indexed ? 4 : (fmt == MBLS_PK_COMPRESSED ? 48 : 96);
-    sbuf ds(c, 0), dm(c, 1), dp(c, 2), doff(c, 3), dr(c, 4), dst(c, 5), dmo(c, 6);
-    HIPCHK(c, ds.up(sigs, 96 * n)); HIPCHK(c, dm.up(msgs ? msgs + msg_first : nullptr, msg_total));
-    if (off) HIPCHK(c, doff.up(off, 4 * (n + 1)));
-    const uint64_t* d_moff = nullptr; const uint8_t* d_msgs = dm.as<uint8_t>();
+    const size_t unit = indexed ? 4 : (fmt == MBLS_PK_COMPRESSED ? 48 : 96);
+    const void* h_keys = total_keys ? (indexed ? (const void*)(idx + key_first) : (const void*)(pks + unit * key_first)) : nullptr;
+    sbuf ds(c, 0), dm(c, 1), dp(c, 2), doff(c, 3), dr(c, 4), dst(c, 5), dmo(c, 6), dmi(c, 7);
+    batch b{nullptr, hm, ks, n, k, mode, nullptr, nullptr, nullptr};       // the same batch with DEVICE pointers
+    HIPCHK(c, ds.up(sigs, 96 * n)); b.d_sigs = ds.as<uint8_t>();
+    if (hm.kind != MBLS_MSGS_TABLE) { HIPCHK(c, dm.up(msgs ? msgs + msg_first : nullptr, msg_total)); b.ms.d_msgs = dm.as<uint8_t>(); }
+    if (hm.indexed()) { HIPCHK(c, dmi.up(hm.d_idx, 4 * n)); b.ms.d_idx = dmi.as<uint32_t>(); }
+    if (off) { HIPCHK(c, doff.up(off, 4 * (n + 1))); b.ks.d_off = doff.as<uint32_t>(); }
     if (moff) {                                                          // the table as given; the uploaded bytes start at msgs[moff[0]]
-        HIPCHK(c, dmo.up(moff, 8 * (n + 1))); d_moff = dmo.as<uint64_t>(); d_msgs -= msg_first;
+        HIPCHK(c, dmo.up(moff, 8 * (n_own + 1))); b.ms.d_moff = dmo.as<uint64_t>(); b.ms.d_msgs -= msg_first;
     }
-    HIPCHK(c, dr.alloc(n)); HIPCHK(c, dst.alloc(4 * n)); HIPCHK(c, dp.alloc(unit * total_keys));
-    bool tm = c->timing; c->timing = false;              // the phase timers assume the plain order
-    keysrc ks; ks.fmt = fmt; ks.d_off = off ? doff.as<uint32_t>() : nullptr; ks.indexed = indexed;
-    if (indexed) { ks.d_recs = tab->d_recs; ks.tsize = tab->size; ks.tab = tab; }
-    const uint64_t R = c->round_items;
-    const uint64_t n_all = n;
-    if (R && n > R && n % R) n -= n % R;                 // the rounds first (parts 1 and 2 below); the remainder as a full pass once the keys are there
-    int rc = verify_pipeline(c, ds.as<uint8_t>(), d_msgs, msg_len, d_moff, ks, n, k, mode, dr.as<uint8_t>(), nullptr, dst.as<uint32_t>(), c->hs_a, 1);
-    if (!rc) {
-        hipError_t e1 = hipSuccess;      // issued after the first two phases were queued: a copy from pageable memory may block the host
-        if (total_keys) e1 = hipMemcpyAsync(dp.p, indexed ? (const void*)(idx + key_first) : (const void*)(pks + unit * key_first), unit * total_keys, hipMemcpyHostToDevice, c->hs_b);
-        if (e1 == hipSuccess) e1 = hipEventRecord(c->hs_ev, c->hs_b);
-        if (e1 == hipSuccess) e1 = hipStreamWaitEvent(c->hs_a, c->hs_ev, 0);
-        if (e1 != hipSuccess) { snprintf(c->err, sizeof(c->err), "key upload failed: %s", hipGetErrorString(e1)); rc = MBLS_ERR_DEVICE; }
+    HIPCHK(c, dr.alloc(n)); HIPCHK(c, dst.alloc(4 * n)); b.d_results = dr.as<uint8_t>(); b.d_status = dst.as<uint32_t>();
+    auto keys_are_there = [&]() { if (indexed) b.ks.d_idx = dp.as<uint32_t>() - key_first; else b.ks.d_pks = dp.as<uint8_t>() - unit * key_first; };     // the table's offsets are absolute
+    const bool late_keys = !hm.indexed();        // (the indexed kinds upload their keys up front: the late upload has not been measured for them)
+    if (late_keys) HIPCHK(c, dp.alloc(unit * total_keys)); else { HIPCHK(c, dp.up(h_keys, unit * total_keys)); keys_are_there(); }
+    const bool tm = c->timing; c->timing = false;        // the phase timers assume the plain order, on the device entries
+    int rc;
+    if (!late_keys) rc = verify_device(c, b, mt, c->hs_a);
+    else {
+        const uint64_t R = c->round_items;
+        const uint64_t n_head = (R && n > R && n % R) ? n - n % R : n;   // the rounds first (parts 1 and 2 below); the remainder as a full pass once the keys are there
+        rc = verify_pipeline(c, slice(b, 0, n_head), c->hs_a, 1);
         if (!rc) {
-            if (indexed) ks.d_idx = dp.as<uint32_t>() - key_first; else ks.d_pks = dp.as<uint8_t>() - unit * key_first;     // the table's offsets are absolute
-            rc = verify_pipeline(c, ds.as<uint8_t>(), d_msgs, msg_len, d_moff, ks, n, k, mode, dr.as<uint8_t>(), nullptr, dst.as<uint32_t>(), c->hs_a, 2);
-            if (!rc && n_all > n)
-                rc = verify_pipeline_from(c, n, ds.as<uint8_t>(), d_msgs, msg_len, d_moff, ks, n_all, k, mode, dr.as<uint8_t>(), nullptr, dst.as<uint32_t>(), c->hs_a);
+            hipError_t e1 = hipSuccess;      // issued after the first two phases were queued: a copy from pageable memory may block the host
+            if (total_keys) e1 = hipMemcpyAsync(dp.p, h_keys, unit * total_keys, hipMemcpyHostToDevice, c->hs_b);
+            if (e1 == hipSuccess) e1 = hipEventRecord(c->hs_ev, c->hs_b);
+            if (e1 == hipSuccess) e1 = hipStreamWaitEvent(c->hs_a, c->hs_ev, 0);
+            if (e1 != hipSuccess) { snprintf(c->err, sizeof(c->err), "key upload failed: %s", hipGetErrorString(e1)); rc = MBLS_ERR_DEVICE; }
+        }
+        if (!rc) {
+            keys_are_there();
+            rc = verify_pipeline(c, slice(b, 0, n_head), c->hs_a, 2);
+            if (!rc && n_head < n) rc = verify_pipeline_one(c, slice(b, n_head, n), c->hs_a);
         }
     }
-    n = n_all;
     c->timing = tm;
-    if (rc) {         // part 1 may be running on the context's streams: nothing of this call is left in flight when it returns an error
+    if (rc) {         // passes may be running on the context's streams and its second track: nothing of this call is left in flight when it returns an error
         (void)hipStreamSynchronize(c->hs_a); (void)hipStreamSynchronize(c->hs_b); (void)hipStreamSynchronize(c->hs_c); (void)hipStreamSynchronize(c->hs_d);
+        (void)hipStreamSynchronize(c->t1_s);
         c->ws_pending = false;
         return rc;
     }
@@ -2083,11 +2116,11 @@ static int verify_host(mbls_ctx* c, const uint8_t* sigs, const uint8_t* msgs, ui
 }
 extern "C" int mbls_fast_aggregate_verify_batch(mbls_ctx* c, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
         const uint8_t* pks, int fmt, const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
-    return verify_host(c, sigs, msgs, msg_len, moff, pks, fmt, nullptr, nullptr, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
+    return verify_host(c, sigs, msgs_per_item(msgs, msg_len, moff), nullptr, pks, fmt, nullptr, nullptr, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
 }
 extern "C" int mbls_verify_batch(mbls_ctx* c, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, const uint8_t* pks, int fmt,
         uint64_t n, uint8_t* results, uint32_t* status) {
-    return verify_host(c, sigs, msgs, msg_len, moff, pks, fmt, nullptr, nullptr, nullptr, n, 1, MBLS_MODE_VERIFY, results, status);
+    return verify_host(c, sigs, msgs_per_item(msgs, msg_len, moff), nullptr, pks, fmt, nullptr, nullptr, nullptr, n, 1, MBLS_MODE_VERIFY, results, status);
 }
 
 // ---- resident key table
@@ -2195,129 +2228,53 @@ extern "C" int mbls_fast_aggregate_verify_batch_indexed_device(mbls_ctx* c, cons
         uint32_t* d_status, void* stream) {
     if (!c || !t) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    if (t->c != c) ARGFAIL(c, "key table belongs to another context");
-    keysrc ks; ks.indexed = true; ks.d_recs = t->d_recs; ks.tsize = t->size; ks.d_idx = d_idx; ks.d_off = d_off; ks.tab = t;
-    return verify_pipeline(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status, (hipStream_t)stream);
+    keysrc ks; const int rk = keys_of_table(c, t, d_idx, d_off, &ks); if (rk) return rk;
+    return verify_device(c, batch{d_sigs, msgs_per_item(d_msgs, msg_len, d_moff), ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status}, nullptr, (hipStream_t)stream);
 }
 extern "C" int mbls_fast_aggregate_verify_batch_indexed(mbls_ctx* c, const mbls_keytable* t, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
         const uint64_t* moff, const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
     if (!c || !t) return MBLS_ERR_ARGUMENT;
-    return verify_host(c, sigs, msgs, msg_len, moff, nullptr, MBLS_PK_UNCOMPRESSED, t, idx, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
+    return verify_host(c, sigs, msgs_per_item(msgs, msg_len, moff), nullptr, nullptr, MBLS_PK_UNCOMPRESSED, t, idx, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
 }
 
-// ---- shared message lists: the call carries n_msgs messages and one index per item (include/mbls.h). The list is hashed once -- by the same launch_hash, in the
-// form its size asks for (plan_shared) --, its points go to the context's table (k_h_export_tab), and the message phase of every pass is the gather (k_h_gather).
-// One-pass plans hash the list inside the pass, on its message stream beside the key sum and the signatures; plans of several passes hash it on the caller's stream
-// before the first pass. Everything is reserved before anything is queued: the workspace for the larger of the items' plan and the list, the table, the key staging.
-static int verify_shared_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_midx,
-                                const keysrc& ks, uint64_t n, uint32_t k, int mode, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, hipStream_t s) {
-    if (ks.fmt != MBLS_PK_COMPRESSED && ks.fmt != MBLS_PK_UNCOMPRESSED) return MBLS_ERR_ARGUMENT;
-    if (n == 0) return MBLS_OK;
-    if (n_msgs > 0xFFFFFFFFull) ARGFAIL(c, "message indices are 32-bit");
-    if (!d_sigs || !d_midx || !d_results || (n_msgs && !d_msgs && msg_len && !d_moff)) ARGFAIL(c, "null buffer");
-    HIPCHK(c, hipSetDevice(c->device));
-    mbls_shared_msgs_plan sp; plan_shared(ctx_limits(c), n, n_msgs, c->timing, c->timing, &sp);
-    uint64_t need = sp.list_workspace_items, need_items = 0;
-    for (uint32_t i = 0; i < sp.batch.n_passes; i++) {
-        const uint64_t e = sp.batch.pass[i].workspace_first + pass_ws_items(sp.batch.pass[i], ks, k, sp.batch.pass[i].items); if (e > need) need = e;
-        const uint64_t ei = sp.batch.pass[i].workspace_first + sp.batch.pass[i].items; if (ei > need_items) need_items = ei;
-    }
-    int rc = mbls_ctx_reserve(c, need); if (rc) return rc;
-    rc = reserve_msgs(c, n_msgs); if (rc) return rc;
-    if (!ks.indexed && ks.fmt == MBLS_PK_COMPRESSED && !ks.d_off && k > 1) { rc = reserve_keys(c, need_items * (uint64_t)k); if (rc) return rc; }
-    msgsrc ms; ms.d_idx = d_midx; ms.n_msgs = n_msgs; ms.tab = c->d_htab; ms.tstride = c->htab_cap; ms.flags = c->d_hflag;
-    if (sp.batch.mode == MBLS_BATCH_ONE_PASS) {
-        ms.list = &sp;
-        return verify_pipeline(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, 0, &ms);
-    }
-    rc = ws_acquire(c, s); if (rc) return rc;
-    rc = shared_hash_list(c, sp, d_msgs, msg_len, d_moff, n_msgs, s); if (rc) return rc;
-    return verify_pipeline(c, d_sigs, d_msgs, msg_len, d_moff, ks, n, k, mode, d_results, d_bitmap, d_status, s, 0, &ms);
-}
+// ---- shared message lists: the call carries n_msgs messages and one index per item (include/mbls.h); how they run: verify_device
 extern "C" int mbls_fast_aggregate_verify_batch_shared_msgs_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff,
         uint64_t n_msgs, const uint32_t* d_msg_idx, const uint8_t* d_pks, int fmt, const uint32_t* d_off, uint64_t n, uint32_t k, uint8_t* d_results, uint64_t* d_bitmap,
         uint32_t* d_status, void* stream) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    keysrc ks; ks.d_pks = d_pks; ks.fmt = fmt; ks.d_off = d_off;
-    return verify_shared_device(c, d_sigs, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status, (hipStream_t)stream);
+    return verify_device(c, batch{d_sigs, msgs_list(d_msgs, msg_len, d_moff, n_msgs, d_msg_idx), keys_wire(d_pks, fmt, d_off), n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap,
+                         d_status}, nullptr, (hipStream_t)stream);
 }
 extern "C" int mbls_verify_batch_shared_msgs_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs,
         const uint32_t* d_msg_idx, const uint8_t* d_pks, int fmt, uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    keysrc ks; ks.d_pks = d_pks; ks.fmt = fmt;
-    return verify_shared_device(c, d_sigs, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, ks, n, 1, MBLS_MODE_VERIFY, d_results, d_bitmap, d_status, (hipStream_t)stream);
+    return verify_device(c, batch{d_sigs, msgs_list(d_msgs, msg_len, d_moff, n_msgs, d_msg_idx), keys_wire(d_pks, fmt, nullptr), n, 1, MBLS_MODE_VERIFY, d_results, d_bitmap, d_status},
+                         nullptr, (hipStream_t)stream);
 }
 extern "C" int mbls_fast_aggregate_verify_batch_indexed_shared_msgs_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len,
         const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_msg_idx, const uint32_t* d_idx, const uint32_t* d_off, uint64_t n, uint32_t k, uint8_t* d_results,
         uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
     if (!c || !t) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    if (t->c != c) ARGFAIL(c, "key table belongs to another context");
-    keysrc ks; ks.indexed = true; ks.d_recs = t->d_recs; ks.tsize = t->size; ks.d_idx = d_idx; ks.d_off = d_off; ks.tab = t;
-    return verify_shared_device(c, d_sigs, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status, (hipStream_t)stream);
-}
-// Host buffers in, results out: the tables are checked here (a bad offset table or an index that names no message refuses the call, nothing enqueued), everything is
-// staged through the context's buffers, and the device pipeline above runs on the context's stream.
-static int verify_host_shared(mbls_ctx* c, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n_msgs, const uint32_t* msg_idx,
-                              const uint8_t* pks, int fmt, const mbls_keytable* tab, const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, int mode,
-                              uint8_t* results, uint32_t* status) {
-    if (!c) return MBLS_ERR_ARGUMENT;
-    mbls_lock lk(c->mu);
-    if (n == 0) return MBLS_OK;
-    if (n_msgs > 0xFFFFFFFFull) ARGFAIL(c, "message indices are 32-bit");
-    if (!sigs || !msg_idx || !results) ARGFAIL(c, "null buffer");
-    if (moff && !msg_offsets_ok(moff, n_msgs)) ARGFAIL(c, "msg_offsets must be non-decreasing, messages below 2^32 bytes");
-    for (uint64_t i = 0; i < n; i++) if (msg_idx[i] >= n_msgs) ARGFAIL(c, "msg_idx names no message of the list");
-    const uint64_t msg_first = moff ? moff[0] : 0;
-    const size_t msg_total = moff ? (size_t)(moff[n_msgs] - moff[0]) : (size_t)msg_len * n_msgs;
-    if (!msgs && msg_total) ARGFAIL(c, "null buffer");
-    if (fmt != MBLS_PK_COMPRESSED && fmt != MBLS_PK_UNCOMPRESSED) ARGFAIL(c, "pk_format");
-    if (tab && tab->c != c) ARGFAIL(c, "key table belongs to another context");
-    if (off && !offsets_ok(off, n)) ARGFAIL(c, "offsets must be non-decreasing");
-    HIPCHK(c, hipSetDevice(c->device));
-    const uint64_t key_first = off ? off[0] : 0;
-    const uint64_t total_keys = off ? (uint64_t)(off[n] - off[0]) : (uint64_t)k * n;
-    const bool indexed = tab != nullptr;
-    if (total_keys && !(indexed ? (const void*)idx : (const void*)pks)) ARGFAIL(c, "null key buffer");
-    const size_t unit = indexed ? 4 : (fmt == MBLS_PK_COMPRESSED ? 48 : 96);
-    sbuf ds(c, 0), dm(c, 1), dp(c, 2), doff(c, 3), dr(c, 4), dst(c, 5), dmo(c, 6), dmi(c, 7);
-    HIPCHK(c, ds.up(sigs, 96 * n)); HIPCHK(c, dm.up(msgs ? msgs + msg_first : nullptr, msg_total)); HIPCHK(c, dmi.up(msg_idx, 4 * n));
-    if (off) HIPCHK(c, doff.up(off, 4 * (n + 1)));
-    const uint64_t* d_moff = nullptr; const uint8_t* d_msgs = dm.as<uint8_t>();
-    if (moff) { HIPCHK(c, dmo.up(moff, 8 * (n_msgs + 1))); d_moff = dmo.as<uint64_t>(); d_msgs -= msg_first; }     // the table as given; the uploaded bytes start at msgs[moff[0]]
-    HIPCHK(c, dr.alloc(n)); HIPCHK(c, dst.alloc(4 * n));
-    HIPCHK(c, dp.up(total_keys ? (indexed ? (const void*)(idx + key_first) : (const void*)(pks + unit * key_first)) : nullptr, unit * total_keys));
-    keysrc ks; ks.fmt = fmt; ks.d_off = off ? doff.as<uint32_t>() : nullptr; ks.indexed = indexed;
-    if (indexed) { ks.d_recs = tab->d_recs; ks.tsize = tab->size; ks.tab = tab; ks.d_idx = dp.as<uint32_t>() - key_first; } else ks.d_pks = dp.as<uint8_t>() - unit * key_first;
-    const bool tm = c->timing; c->timing = false;        // the phase timers describe the device entries
-    const int rc = verify_shared_device(c, ds.as<uint8_t>(), d_msgs, msg_len, d_moff, n_msgs, dmi.as<uint32_t>(), ks, n, k, mode, dr.as<uint8_t>(), nullptr, dst.as<uint32_t>(), c->hs_a);
-    c->timing = tm;
-    if (rc) {         // nothing of this call is left in flight when it returns an error
-        (void)hipStreamSynchronize(c->hs_a); (void)hipStreamSynchronize(c->hs_b); (void)hipStreamSynchronize(c->hs_c); (void)hipStreamSynchronize(c->hs_d);
-        (void)hipStreamSynchronize(c->t1_s);
-        c->ws_pending = false;
-        return rc;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->hs_a));
-    c->ws_pending = false;
-    HIPCHK(c, dr.down(results, n));
-    if (status) HIPCHK(c, dst.down(status, 4 * n));
-    return MBLS_OK;
+    keysrc ks; const int rk = keys_of_table(c, t, d_idx, d_off, &ks); if (rk) return rk;
+    return verify_device(c, batch{d_sigs, msgs_list(d_msgs, msg_len, d_moff, n_msgs, d_msg_idx), ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status}, nullptr,
+                         (hipStream_t)stream);
 }
 extern "C" int mbls_fast_aggregate_verify_batch_shared_msgs(mbls_ctx* c, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n_msgs,
         const uint32_t* msg_idx, const uint8_t* pks, int fmt, const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
-    return verify_host_shared(c, sigs, msgs, msg_len, moff, n_msgs, msg_idx, pks, fmt, nullptr, nullptr, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
+    return verify_host(c, sigs, msgs_list(msgs, msg_len, moff, n_msgs, msg_idx), nullptr, pks, fmt, nullptr, nullptr, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
 }
 extern "C" int mbls_verify_batch_shared_msgs(mbls_ctx* c, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n_msgs,
         const uint32_t* msg_idx, const uint8_t* pks, int fmt, uint64_t n, uint8_t* results, uint32_t* status) {
-    return verify_host_shared(c, sigs, msgs, msg_len, moff, n_msgs, msg_idx, pks, fmt, nullptr, nullptr, nullptr, n, 1, MBLS_MODE_VERIFY, results, status);
+    return verify_host(c, sigs, msgs_list(msgs, msg_len, moff, n_msgs, msg_idx), nullptr, pks, fmt, nullptr, nullptr, nullptr, n, 1, MBLS_MODE_VERIFY, results, status);
 }
 extern "C" int mbls_fast_aggregate_verify_batch_indexed_shared_msgs(mbls_ctx* c, const mbls_keytable* t, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
         const uint64_t* moff, uint64_t n_msgs, const uint32_t* msg_idx, const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
     if (!c || !t) return MBLS_ERR_ARGUMENT;
-    return verify_host_shared(c, sigs, msgs, msg_len, moff, n_msgs, msg_idx, nullptr, MBLS_PK_UNCOMPRESSED, t, idx, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
+    return verify_host(c, sigs, msgs_list(msgs, msg_len, moff, n_msgs, msg_idx), nullptr, nullptr, MBLS_PK_UNCOMPRESSED, t, idx, off, n, k, MBLS_MODE_FAST_AGGREGATE, results,
+                       status);
 }
 
 // ---- resident message table (include/mbls.h, mbls_msgtable_*): the message side's key table. An append hashes its messages with launch_hash in the form THEIR count
@@ -2338,10 +2295,6 @@ static hipError_t msgtable_alloc(uint64_t cap, uint32_t** tab, uint32_t** flag, 
     if (e == hipSuccess) e = hipMalloc(st, stride * 4);
     if (e != hipSuccess) { if (*tab) (void)hipFree(*tab); if (*flag) (void)hipFree(*flag); if (*st) (void)hipFree(*st); *tab = *flag = *st = nullptr; }
     return e;
-}
-static int msgtable_acquire(mbls_ctx* c, const mbls_msgtable* t, hipStream_t s) {
-    if (t->pending && t->ev_stream != s) HIPCHK(c, hipStreamWaitEvent(s, t->ev, 0));
-    return MBLS_OK;
 }
 extern "C" int mbls_msgtable_create(mbls_ctx* c, uint64_t capacity_hint, mbls_msgtable** out) {
     if (!c || !out) return MBLS_ERR_ARGUMENT;
@@ -2482,93 +2435,42 @@ extern "C" int mbls_msgtable_clear(mbls_msgtable* t) {
     t->size = 0; t->pending = false; c->ws_pending = false;
     return MBLS_OK;
 }
-// the verification entries over a table: mbls_plan_batch's plan, every pass's message phase the gather; the table is read at the size it has now
-static int verify_msgtable_device(mbls_ctx* c, const mbls_msgtable* mt, const uint8_t* d_sigs, const uint32_t* d_midx, const keysrc& ks, uint64_t n, uint32_t k, int mode,
-                                  uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, hipStream_t s) {
-    if (ks.fmt != MBLS_PK_COMPRESSED && ks.fmt != MBLS_PK_UNCOMPRESSED) return MBLS_ERR_ARGUMENT;
-    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
-    if (n == 0) return MBLS_OK;
-    if (!d_sigs || !d_midx || !d_results) ARGFAIL(c, "null buffer");
-    HIPCHK(c, hipSetDevice(c->device));
-    // (verify_pipeline reserves the plan's workspace and key staging before it queues the first pass, as for the per-item entries: there is no list to size here)
-    int rc = msgtable_acquire(c, mt, s); if (rc) return rc;      // every stream of the call forks from s behind this
-    msgsrc ms; ms.d_idx = d_midx; ms.n_msgs = mt->size; ms.tab = mt->d_tab; ms.tstride = mtb_stride(mt->cap); ms.flags = mt->d_flag;
-    return verify_pipeline(c, d_sigs, nullptr, 0, nullptr, ks, n, k, mode, d_results, d_bitmap, d_status, s, 0, &ms);
-}
+// the verification entries over a table: mbls_plan_batch's plan, every pass's message phase the gather; the table is read at the size it has now (verify_device).
+// The host forms refuse an index that names no entry before anything is enqueued (verify_host).
 extern "C" int mbls_fast_aggregate_verify_batch_msgtable_device(mbls_ctx* c, const uint8_t* d_sigs, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint8_t* d_pks,
         int fmt, const uint32_t* d_off, uint64_t n, uint32_t k, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
     if (!c || !mt) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    keysrc ks; ks.d_pks = d_pks; ks.fmt = fmt; ks.d_off = d_off;
-    return verify_msgtable_device(c, mt, d_sigs, d_msg_idx, ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status, (hipStream_t)stream);
+    return verify_device(c, batch{d_sigs, msgs_in_table(d_msg_idx), keys_wire(d_pks, fmt, d_off), n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status}, mt,
+                         (hipStream_t)stream);
 }
 extern "C" int mbls_verify_batch_msgtable_device(mbls_ctx* c, const uint8_t* d_sigs, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint8_t* d_pks, int fmt,
         uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
     if (!c || !mt) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    keysrc ks; ks.d_pks = d_pks; ks.fmt = fmt;
-    return verify_msgtable_device(c, mt, d_sigs, d_msg_idx, ks, n, 1, MBLS_MODE_VERIFY, d_results, d_bitmap, d_status, (hipStream_t)stream);
+    return verify_device(c, batch{d_sigs, msgs_in_table(d_msg_idx), keys_wire(d_pks, fmt, nullptr), n, 1, MBLS_MODE_VERIFY, d_results, d_bitmap, d_status}, mt, (hipStream_t)stream);
 }
 extern "C" int mbls_fast_aggregate_verify_batch_indexed_msgtable_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const mbls_msgtable* mt,
         const uint32_t* d_msg_idx, const uint32_t* d_idx, const uint32_t* d_off, uint64_t n, uint32_t k, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
     if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    if (t->c != c) ARGFAIL(c, "key table belongs to another context");
-    keysrc ks; ks.indexed = true; ks.d_recs = t->d_recs; ks.tsize = t->size; ks.d_idx = d_idx; ks.d_off = d_off; ks.tab = t;
-    return verify_msgtable_device(c, mt, d_sigs, d_msg_idx, ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status, (hipStream_t)stream);
-}
-// Host buffers in, results out: an index that names no entry refuses the call before anything is enqueued
-static int verify_host_msgtable(mbls_ctx* c, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx, const uint8_t* pks, int fmt, const mbls_keytable* tab,
-                                const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, int mode, uint8_t* results, uint32_t* status) {
-    if (!c || !mt) return MBLS_ERR_ARGUMENT;
-    mbls_lock lk(c->mu);
-    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
-    if (n == 0) return MBLS_OK;
-    if (!sigs || !msg_idx || !results) ARGFAIL(c, "null buffer");
-    for (uint64_t i = 0; i < n; i++) if (mtb_names_nothing(msg_idx[i], mt->size)) ARGFAIL(c, "msg_idx names no entry of the message table");
-    if (fmt != MBLS_PK_COMPRESSED && fmt != MBLS_PK_UNCOMPRESSED) ARGFAIL(c, "pk_format");
-    if (tab && tab->c != c) ARGFAIL(c, "key table belongs to another context");
-    if (off && !offsets_ok(off, n)) ARGFAIL(c, "offsets must be non-decreasing");
-    HIPCHK(c, hipSetDevice(c->device));
-    const uint64_t key_first = off ? off[0] : 0;
-    const uint64_t total_keys = off ? (uint64_t)(off[n] - off[0]) : (uint64_t)k * n;
-    const bool indexed = tab != nullptr;
-    if (total_keys && !(indexed ? (const void*)idx : (const void*)pks)) ARGFAIL(c, "null key buffer");
-    const size_t unit = indexed ? 4 : (fmt == MBLS_PK_COMPRESSED ? 48 : 96);
-    sbuf ds(c, 0), dp(c, 2), doff(c, 3), dr(c, 4), dst(c, 5), dmi(c, 7);
-    HIPCHK(c, ds.up(sigs, 96 * n)); HIPCHK(c, dmi.up(msg_idx, 4 * n));
-    if (off) HIPCHK(c, doff.up(off, 4 * (n + 1)));
-    HIPCHK(c, dr.alloc(n)); HIPCHK(c, dst.alloc(4 * n));
-    HIPCHK(c, dp.up(total_keys ? (indexed ? (const void*)(idx + key_first) : (const void*)(pks + unit * key_first)) : nullptr, unit * total_keys));
-    keysrc ks; ks.fmt = fmt; ks.d_off = off ? doff.as<uint32_t>() : nullptr; ks.indexed = indexed;
-    if (indexed) { ks.d_recs = tab->d_recs; ks.tsize = tab->size; ks.tab = tab; ks.d_idx = dp.as<uint32_t>() - key_first; } else ks.d_pks = dp.as<uint8_t>() - unit * key_first;
-    const bool tm = c->timing; c->timing = false;        // the phase timers describe the device entries
-    const int rc = verify_msgtable_device(c, mt, ds.as<uint8_t>(), dmi.as<uint32_t>(), ks, n, k, mode, dr.as<uint8_t>(), nullptr, dst.as<uint32_t>(), c->hs_a);
-    c->timing = tm;
-    if (rc) {         // nothing of this call is left in flight when it returns an error
-        (void)hipStreamSynchronize(c->hs_a); (void)hipStreamSynchronize(c->hs_b); (void)hipStreamSynchronize(c->hs_c); (void)hipStreamSynchronize(c->hs_d);
-        (void)hipStreamSynchronize(c->t1_s);
-        c->ws_pending = false;
-        return rc;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->hs_a));
-    c->ws_pending = false;
-    HIPCHK(c, dr.down(results, n));
-    if (status) HIPCHK(c, dst.down(status, 4 * n));
-    return MBLS_OK;
+    keysrc ks; const int rk = keys_of_table(c, t, d_idx, d_off, &ks); if (rk) return rk;
+    return verify_device(c, batch{d_sigs, msgs_in_table(d_msg_idx), ks, n, k, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status}, mt, (hipStream_t)stream);
 }
 extern "C" int mbls_fast_aggregate_verify_batch_msgtable(mbls_ctx* c, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx, const uint8_t* pks, int fmt,
         const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
-    return verify_host_msgtable(c, sigs, mt, msg_idx, pks, fmt, nullptr, nullptr, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
+    if (!c || !mt) return MBLS_ERR_ARGUMENT;
+    return verify_host(c, sigs, msgs_in_table(msg_idx), mt, pks, fmt, nullptr, nullptr, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
 }
 extern "C" int mbls_verify_batch_msgtable(mbls_ctx* c, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx, const uint8_t* pks, int fmt, uint64_t n,
         uint8_t* results, uint32_t* status) {
-    return verify_host_msgtable(c, sigs, mt, msg_idx, pks, fmt, nullptr, nullptr, nullptr, n, 1, MBLS_MODE_VERIFY, results, status);
+    if (!c || !mt) return MBLS_ERR_ARGUMENT;
+    return verify_host(c, sigs, msgs_in_table(msg_idx), mt, pks, fmt, nullptr, nullptr, nullptr, n, 1, MBLS_MODE_VERIFY, results, status);
 }
 extern "C" int mbls_fast_aggregate_verify_batch_indexed_msgtable(mbls_ctx* c, const mbls_keytable* t, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx,
         const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
-    if (!c || !t) return MBLS_ERR_ARGUMENT;
-    return verify_host_msgtable(c, sigs, mt, msg_idx, nullptr, MBLS_PK_UNCOMPRESSED, t, idx, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
+    if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
+    return verify_host(c, sigs, msgs_in_table(msg_idx), mt, nullptr, MBLS_PK_UNCOMPRESSED, t, idx, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
 }
 
 // ---- batch helpers
@@ -4287,19 +4189,15 @@ static int multi_run(mbls_multi* m, const mbls_multi_keytable* mt, const uint8_t
     if (!m || (mt && mt->m != m)) return MBLS_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(m->mu);
     const uint64_t G = m->ctx.size();
-    const size_t unit = mt ? 4 : (fmt == MBLS_PK_COMPRESSED ? 48 : 96);
     std::vector<int> rcs(G, MBLS_OK);
     std::vector<std::thread> th;
+    // the call as a batch of HOST pointers: a shard is its slice
+    const batch all{sigs, msgs_per_item(msgs, msg_len, moff), mt ? keys_table(nullptr, 0, idx, off, nullptr) : keys_wire(pks, fmt, off), n, k, mode, results, nullptr, status};
     auto work = [&](uint64_t g) {
-        const uint64_t lo = shard_lo(n, g, G), hi = shard_lo(n, g + 1, G), cnt = hi - lo;
-        if (!cnt) return;
-        // uniform layouts advance the base pointers; offset tables are absolute, so their slice [lo, hi] goes with the unmoved base
-        const uint8_t* s_msgs = (moff || !msgs) ? msgs : msgs + (uint64_t)msg_len * lo;
-        const uint8_t* s_pks = (off || !pks) ? pks : pks + unit * (uint64_t)k * lo;
-        const uint32_t* s_idx = (off || !idx) ? idx : idx + (uint64_t)k * lo;
-        rcs[g] = verify_host(m->ctx[g], sigs ? sigs + 96 * lo : nullptr, s_msgs, msg_len, moff ? moff + lo : nullptr, s_pks, fmt,
-                             mt ? mt->tab[g] : nullptr, s_idx, off ? off + lo : nullptr, cnt, k, mode, results ? results + lo : nullptr,
-                             status ? status + lo : nullptr);
+        const uint64_t lo = shard_lo(n, g, G), hi = shard_lo(n, g + 1, G);
+        if (hi == lo) return;
+        const batch sh = slice(all, lo, hi);
+        rcs[g] = verify_host(m->ctx[g], sh.d_sigs, sh.ms, nullptr, sh.ks.d_pks, fmt, mt ? mt->tab[g] : nullptr, sh.ks.d_idx, sh.ks.d_off, sh.n, k, mode, sh.d_results, sh.d_status);
     };
     try { for (uint64_t g = 1; g < G; g++) th.emplace_back(work, g); } catch (...) { for (auto& t : th) t.join(); snprintf(m->err, sizeof(m->err), "cannot start a host thread"); return MBLS_ERR_DEVICE; }
     work(0);
@@ -4460,7 +4358,7 @@ extern "C" int mbls_multi_fast_aggregate_verify_bitmap(mbls_multi* m, const uint
     std::lock_guard<std::mutex> lk(m->mu);
     const uint64_t G = m->ctx.size();
     const uint64_t words = (n + 63) / 64, W = (words + G - 1) / G;
-    const size_t unit = fmt == MBLS_PK_COMPRESSED ? 48 : 96;
+    const batch all{sigs, msgs_per_item(msgs, msg_len, moff), keys_wire(pks, fmt, off), n, k, MBLS_MODE_FAST_AGGREGATE, nullptr, nullptr, status};   // HOST pointers: a shard is its slice
     std::vector<int> rcs(G, MBLS_OK); std::vector<std::thread> th;
     std::vector<const void*> d_send(G, nullptr); std::vector<void*> d_recv(G, nullptr); std::vector<hipStream_t> st(G, nullptr);
     auto work = [&](uint64_t g) {
@@ -4476,12 +4374,10 @@ extern "C" int mbls_multi_fast_aggregate_verify_bitmap(mbls_multi* m, const uint
         d_send[g] = m->d_bm_send[g]; d_recv[g] = m->d_bm_all[g]; st[g] = c->hs_a;
         if (hipMemsetAsync(m->d_bm_send[g], 0, 8 * W, c->hs_a) != hipSuccess) { rcs[g] = MBLS_ERR_DEVICE; return; }
         if (!cnt) return;
-        const uint8_t* s_msgs = (moff || !msgs) ? msgs : msgs + (uint64_t)msg_len * lo;
-        const uint8_t* s_pks = (off || !pks) ? pks : pks + unit * (uint64_t)k * lo;
+        const batch sh = slice(all, lo, hi);
         std::vector<uint8_t> res;
         try { res.resize(cnt); } catch (...) { rcs[g] = MBLS_ERR_DEVICE; return; }
-        rcs[g] = verify_host(c, sigs ? sigs + 96 * lo : nullptr, s_msgs, msg_len, moff ? moff + lo : nullptr, s_pks, fmt, nullptr, nullptr, off ? off + lo : nullptr, cnt, k,
-                             MBLS_MODE_FAST_AGGREGATE, res.data(), status ? status + lo : nullptr);
+        rcs[g] = verify_host(c, sh.d_sigs, sh.ms, nullptr, sh.ks.d_pks, fmt, nullptr, nullptr, sh.ks.d_off, cnt, k, MBLS_MODE_FAST_AGGREGATE, res.data(), sh.d_status);
         if (rcs[g]) return;
         // the shard's result bytes are still in the context's staging buffer (slot 4 of verify_host): pack them where they are
         hipLaunchKernelGGL(k_pack, dim3(nblk(cnt)), dim3(WG), 0, c->hs_a, (const uint8_t*)c->stage[4].p, m->d_bm_send[g], cnt);

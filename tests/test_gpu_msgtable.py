@@ -8,7 +8,7 @@ import random
 import pytest
 
 import shared_msgs_cases as smc
-from test_gpu_shared_msgs import case, dev_call, make_crossed, oracle_check_32, _msgs
+from test_gpu_shared_msgs import case, cuts_case, dev_call, make_crossed, oracle_check_32, _msgs
 
 pytestmark = pytest.mark.gpu
 
@@ -268,16 +268,19 @@ def test_host_forms_refuse_a_bad_index_and_leave_the_outputs_alone(engine):
         mt.close(); other.close()
 
 
-@pytest.mark.parametrize("n,tracks", [(300, None), (300, 0), (276, 64)])
-def test_the_cuts_on_small_rounds(engine, n, tracks):
+@pytest.mark.parametrize("n,tracks", [(300, None), (300, 0), (276, 64), (165, None), (165, 0), (144, 64)])
+def test_the_cuts_on_small_rounds(engine, mb, n, tracks):
     """rounds of 128 items: 300 items = two rounds + 44 (rounds, then the rest); with mbls_ctx_set_tracks(1, side_max) the two-halves mode (300 items) and the
-    round-beside-rest mode (276 items, side_max = 64) where the engine's limits allow two tracks: every pass gathers from the table"""
+    round-beside-rest mode (276 items, side_max = 64) where the engine's limits allow two tracks: every pass gathers from the table. Rounds of 64 items (165 = two
+    rounds + 37 and 144 = two rounds + 16 items, a table of five messages): the same three modes through the device entry AND the host entry, and the first 32
+    items against the oracle."""
     from milagro_bls_amd import _native as N
     ctx = N.default_context()
-    cs = case("cuts%d" % n, lambda: (smc.build(n, 2, _msgs(4, 17), [(5 * i + i // 64) % 4 for i in range(n)], seed=508 + n), False))
+    small = n < 200
+    cs = cuts_case(n)
     mt = new_table(cs.msgs)
     try:
-        ctx.set_round_items(128)
+        ctx.set_round_items(64 if small else 128)
         if tracks is not None:
             ctx.set_tracks(1, tracks)
         mode, passes, _ = N.plan_batch_shared_msgs(n, 0, ctx.limits())
@@ -286,7 +289,10 @@ def test_the_cuts_on_small_rounds(engine, n, tracks):
             assert mode == N.BATCH_ROUNDS_THEN_REST
         elif engine != "waves":
             assert mode == (N.BATCH_TWO_HALVES if tracks == 0 else N.BATCH_ROUND_BESIDE_REST)
-        check_table(cs, mt)
+        got, st, _ = check_table(cs, mt)
+        if small:
+            oracle_check_32(cs, got)
+            assert mb.fast_aggregate_verify_batch_msgtable(mt, cs.sigs, cs.idx, cs.pks, cs.n, cs.k, pk_format=1) == (got, st)
     finally:
         ctx.reset_tuning(); mt.close()
 

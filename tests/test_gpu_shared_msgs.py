@@ -237,24 +237,39 @@ def test_host_entries_refuse_bad_tables_and_leave_the_outputs_alone(engine):
     assert rc == N.OK and [bool(x) for x in res] == cs.want
 
 
-@pytest.mark.parametrize("n,tracks", [(300, None), (300, 0), (276, 64)])
-def test_the_cuts_on_small_rounds(engine, n, tracks):
+def cuts_case(n):
+    """the items of test_the_cuts_on_small_rounds (here and in tests/test_gpu_msgtable.py): below 200 items a list of 5 messages for rounds of 64 items, else 4 for 128"""
+    if n < 200:
+        return case("cuts%d" % n, lambda: (smc.build(n, 2, _msgs(5, 17), [(3 * i + i // 64) % 5 for i in range(n)], seed=508 + n), False))
+    return case("cuts%d" % n, lambda: (smc.build(n, 2, _msgs(4, 17), [(5 * i + i // 64) % 4 for i in range(n)], seed=508 + n), False))
+
+
+@pytest.mark.parametrize("n,tracks", [(300, None), (300, 0), (276, 64), (165, None), (165, 0), (144, 64)])
+def test_the_cuts_on_small_rounds(engine, mb, n, tracks):
     """rounds of 128 items: 300 items = two rounds + 44 (rounds, then the rest); with mbls_ctx_set_tracks(1, side_max) the two-halves mode (300 items) and the
-    round-beside-rest mode (276 items, side_max = 64) where the engine's limits allow two tracks -- the list of four messages is hashed once, before the first pass"""
+    round-beside-rest mode (276 items, side_max = 64) where the engine's limits allow two tracks -- the list of four messages is hashed once, before the first pass.
+    Rounds of 64 items (165 = two rounds + 37 and 144 = two rounds + 16 items, five messages): the same three modes through the device entries AND the host entries,
+    with the list and with the messages spelled out (the host entry that takes per-item messages queues its rounds in two parts around the key upload and the rest
+    as one pass behind them, whatever the tracks), and the first 32 items against the oracle."""
     from milagro_bls_amd import _native as N
     ctx = N.default_context()
-    cs = case("cuts%d" % n, lambda: (smc.build(n, 2, _msgs(4, 17), [(5 * i + i // 64) % 4 for i in range(n)], seed=508 + n), False))
+    small = n < 200
+    cs = cuts_case(n)
     try:
-        ctx.set_round_items(128)
+        ctx.set_round_items(64 if small else 128)
         if tracks is not None:
             ctx.set_tracks(1, tracks)
-        mode, passes, lst = N.plan_batch_shared_msgs(n, 4, ctx.limits())
+        mode, passes, lst = N.plan_batch_shared_msgs(n, cs.n_msgs, ctx.limits())
         assert len(passes) >= 2 and all(p["message"] == N.MESSAGE_GATHER for p in passes) and lst["list_pieces"] == 1
         if tracks is None:
             assert mode == N.BATCH_ROUNDS_THEN_REST
         elif engine != "waves":
             assert mode == (N.BATCH_TWO_HALVES if tracks == 0 else N.BATCH_ROUND_BESIDE_REST)
-        check_both(cs)
+        got, st, _ = check_both(cs)
+        if small:
+            oracle_check_32(cs, got)
+            assert mb.fast_aggregate_verify_batch_shared_msgs(cs.sigs, cs.list_bytes, cs.n_msgs, cs.idx, cs.pks, cs.n, cs.k, pk_format=1) == (got, st)
+            assert mb.fast_aggregate_verify_batch(cs.sigs, cs.spelled_bytes, cs.pks, cs.n, cs.k, pk_format=1) == (got, st)
     finally:
         ctx.reset_tuning()
 

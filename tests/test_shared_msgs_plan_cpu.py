@@ -1,6 +1,6 @@
 """The routing of the shared-message entries as data (include/mbls.h: mbls_plan_batch_shared_msgs, mbls_plan_shared_msgs_workspace_items -- pure functions, no GPU):
 the items' plan is mbls_plan_batch's with every message phase a gather, and the list is hashed in the form ITS size asks for. The entries act on the same function
-(verify_shared_device calls plan_shared), so what is asserted here is what the GPU runs; tests/test_gpu_shared_msgs.py compares results."""
+(verify_device calls plan_shared), so what is asserted here is what the GPU runs; tests/test_gpu_shared_msgs.py compares results."""
 import pytest
 
 from milagro_bls_amd import _native as N
