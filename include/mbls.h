@@ -754,6 +754,52 @@ int mbls_verify_multiple_shared_msgs_locate_rng(mbls_ctx* ctx, const uint8_t* si
                                                 const uint64_t* msg_offsets, uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result,
                                                 uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user);
 
+/* verify_multiple OVER THE RESIDENT MESSAGE TABLE, LOCATED PER SET. The shared-message entries above with the messages named by index into a resident message
+ * table (mbls_msgtable_*) in place of a list the call carries: NOTHING IS HASHED, no call table is written. d_msg_idx[n] / msg_idx[n] are TABLE indices. The table
+ * is read at the size T it has when the call is enqueued (under the context's lock, as the per-item `_msgtable` entries read it), and its last append on another
+ * stream is awaited on the caller's stream before the call's streams fork.
+ * A resident table outlives calls and may hold far more entries than one call names, so the table is not treated as the list: the grouping runs over the T
+ * entries (count, scan, scatter and per-entry key sums as above), then the entries that are NAMED are compacted on the device in increasing table index
+ * (mbls_vmt.h: flag, scan, named), and the Miller items are built from those -- one per named entry, D of them. D stays on the device and is never read back.
+ * ROUTING AND SIZING (mbls_ctx_set_vm_grouping as above). The Miller phase is sized by `bound`, what the host knows about D: the DEVICE entries never see the
+ * indices and use bound = min(n, T); the HOST entries (_rng) count D and the longest group exactly. Everything else is the rule above with bound in place of
+ * n_msgs: auto groups when 2 bound <= n, miller_items = max(bound, 1), the Miller form follows miller_items, tree levels follow the longest group (host) or n
+ * (device). Miller items at or above D hold the private entry and the point at infinity and contribute 1; waves that hold no item below D return before any
+ * arithmetic, on the wave form and on the lane forms. Per-set route: one gather straight from the resident table.
+ * mbls_plan_verify_multiple_msgtable is the pure function the entries act on (named = 0: "not known", the device entries' case; otherwise D as a host entry
+ * counts it). It fills mbls_vm_shared_msgs_plan with the list fields (list_*, table_entries) zero. MBLS_ERR_ARGUMENT for n = 0, a mode outside 0..2 or null
+ * pointers; the workspace functions then return 0.
+ * CONTRACT: that of the shared-message entries and their _locate forms with "list" read as "table": result and rejecting status bits of
+ * mbls_verify_multiple_aggregate_signatures_device on the spelled-out messages; per set, what the one-set call returns. An index at or above T (an empty table:
+ * every index) rejects its set with MBLS_ST_BAD_MSG_RANGE on the device entries and is refused (MBLS_ERR_ARGUMENT, nothing queued, outputs untouched) by the
+ * host entries; an entry flagged at its append (a bad range) rejects the call exactly when a set names it, and the _locate forms put the bit into the word of
+ * exactly the sets that name it. n = 0: result 1. A table of another context: MBLS_ERR_ARGUMENT.
+ * ALLOCATION: workspace (mbls_plan_verify_multiple_msgtable_workspace_items, _locate_workspace_items) and six words per table entry for the grouping, reserved
+ * once before the first kernel; mbls_ctx_reserve beforehand keeps the workspace allocation out of the call.
+ * OUT OF SCOPE: the verification stream (mbls_stream_*), the mbls_multi handle, the shard form (d_partial) and sets given by 48-byte wire-format keys. */
+int mbls_plan_verify_multiple_msgtable(const mbls_limits* limits, uint64_t n, uint64_t table_size, uint64_t named, int mode, mbls_vm_shared_msgs_plan* out);
+uint64_t mbls_plan_verify_multiple_msgtable_workspace_items(const mbls_limits* limits, uint64_t n, uint64_t table_size, uint64_t named, int mode);
+uint64_t mbls_plan_verify_multiple_msgtable_locate_workspace_items(const mbls_limits* limits, uint64_t n, uint64_t table_size, uint64_t named, int mode);
+int mbls_verify_multiple_msgtable_device(mbls_ctx* ctx, const uint8_t* d_sigs96, const uint8_t* d_apks96, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
+                                         const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream);
+/* keys by index into a resident key table, as mbls_verify_multiple_sets_indexed_device names them */
+int mbls_verify_multiple_sets_indexed_msgtable_device(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* d_sigs96, const uint32_t* d_key_idx,
+                                                      const uint32_t* d_offsets, uint32_t k, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
+                                                      const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream);
+/* host buffers, the reference's draw order as mbls_verify_multiple_shared_msgs_rng keeps it */
+int mbls_verify_multiple_msgtable_rng(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n,
+                                      uint8_t* result, mbls_scalar_source draw, void* user);
+/* the _locate forms: d_set_results (n bytes) REQUIRED, d_set_status (n words) optional; *d_result / *d_status byte for byte the entry above's under the same mode */
+int mbls_verify_multiple_msgtable_locate_device(mbls_ctx* ctx, const uint8_t* d_sigs96, const uint8_t* d_apks96, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
+                                                const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results,
+                                                uint32_t* d_set_status, void* stream);
+int mbls_verify_multiple_sets_indexed_msgtable_locate_device(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* d_sigs96, const uint32_t* d_key_idx,
+                                                             const uint32_t* d_offsets, uint32_t k, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
+                                                             const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results,
+                                                             uint32_t* d_set_status, void* stream);
+int mbls_verify_multiple_msgtable_locate_rng(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const mbls_msgtable* mt, const uint32_t* msg_idx,
+                                             uint64_t n, uint8_t* result, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user);
+
 /* ---- batch helpers used to build inputs and caches on the device ---- */
 /* n x PublicKey::from_bytes[_unchecked] / from_uncompressed_bytes: errs[i] = MBLS_OK / MBLS_ERR_* per key */
 int mbls_pk_decode_batch(mbls_ctx* ctx, const uint8_t* in, int in_format, int validate, uint64_t n, uint8_t* out96, uint8_t* errs);

@@ -11,6 +11,7 @@
 //     (one call of it per batch, batch after batch)      AggregateSignature::verify_multiple_aggregate_signatures_batches(rng, batches) -> vector<bool>, ONE call
 //     (the same over sets that share messages)            AggregateSignature::verify_multiple_aggregate_signatures_shared_msgs(rng, iter): one hash and, where it pays, one Miller loop per message
 //     (... and which sets of a rejected call)             AggregateSignature::verify_multiple_aggregate_signatures_shared_msgs_locate(rng, iter): the bool and one bool per set
+//     (... over a resident message table)                 MessageTable::verify_multiple_aggregate_signatures[_locate](rng, iter): messages by table index, nothing hashed
 //
 // Every curve / pairing operation runs in the HIP kernels; there is no CPU fallback: constructing the first object without a
 // GPU throws DeviceError. The only host arithmetic is SecretKey::key_generate (HKDF-SHA-256 + one reduction mod r), which the
@@ -508,6 +509,47 @@ public:
     }
     // size back to 0, capacity kept; refused (DeviceError) while a stream made over the table has calls that have not completed
     void clear() { detail::check(mbls_msgtable_clear(h_)); }
+    // AggregateSignature::verify_multiple_aggregate_signatures over sets (signature, aggregate key, entry index) whose messages are entries of this table
+    // (mbls_verify_multiple_msgtable_rng): the same bool as that method on the spelled-out messages, rng left in the same state, nothing hashed in the call.
+    // An index that names no entry throws (DeviceError). rng(): one random byte per call.
+    typedef std::tuple<const AggregateSignature*, const AggregatePublicKey*, uint32_t> IndexedSet;
+    template <typename Rng>
+    bool verify_multiple_aggregate_signatures(Rng&& rng, const std::vector<IndexedSet>& sets) const { return vm(rng, sets, nullptr); }
+    // The same, and in the same call (mbls_verify_multiple_msgtable_locate_rng) which sets of a rejected call are the bad ones, with the semantics of
+    // AggregateSignature::verify_multiple_aggregate_signatures_shared_msgs_locate.
+    template <typename Rng>
+    std::pair<bool, std::vector<bool>> verify_multiple_aggregate_signatures_locate(Rng&& rng, const std::vector<IndexedSet>& sets) const {
+        std::vector<bool> per_set;
+        const bool ok = vm(rng, sets, &per_set);
+        return {ok, per_set};
+    }
+private:
+    template <typename Rng>
+    bool vm(Rng& rng, const std::vector<IndexedSet>& sets, std::vector<bool>* per_set) const {
+        if (sets.empty()) return true;
+        Bytes sigs, apks; std::vector<uint32_t> idx;
+        for (auto& s : sets) {
+            sigs.insert(sigs.end(), std::get<0>(s)->point.begin(), std::get<0>(s)->point.end());
+            apks.insert(apks.end(), std::get<1>(s)->point.begin(), std::get<1>(s)->point.end());
+            idx.push_back(std::get<2>(s));
+        }
+        using R = typename std::remove_reference<Rng>::type;
+        struct src { R* rng; std::exception_ptr err; } u{&rng, nullptr};
+        mbls_scalar_source draw = [](void* user, uint64_t* out, uint64_t count) {
+            src* p = static_cast<src*>(user);
+            try { for (uint64_t i = 0; i < count; i++) out[i] = AggregateSignature::draw_scalar(*p->rng); }
+            catch (...) { p->err = std::current_exception(); for (uint64_t i = 0; i < count; i++) out[i] = 0; }        // never unwind through the C frames
+        };
+        uint8_t ok = 0;
+        std::vector<uint8_t> sres(per_set ? sets.size() : 0);
+        const int rc = per_set
+            ? mbls_verify_multiple_msgtable_locate_rng(detail::ctx(), sigs.data(), apks.data(), h_, idx.data(), sets.size(), &ok, sres.data(), nullptr, draw, &u)
+            : mbls_verify_multiple_msgtable_rng(detail::ctx(), sigs.data(), apks.data(), h_, idx.data(), sets.size(), &ok, draw, &u);
+        if (u.err) std::rethrow_exception(u.err);
+        detail::check(rc);
+        if (per_set) per_set->assign(sres.begin(), sres.end());
+        return ok == 1;
+    }
 };
 namespace detail {
 inline void flatten_items(const char* what, const std::vector<AggregateSignature>& sigs, const MessageTable& table, const std::vector<uint32_t>& msg_idx,

@@ -140,6 +140,29 @@ def plan_verify_multiple_shared_msgs_workspace_items(n, n_msgs, mode=0, limits=N
     return int(lib().mbls_plan_verify_multiple_shared_msgs_workspace_items(C.byref(L), n, n_msgs, mode))
 
 
+def plan_verify_multiple_msgtable(n, table_size, named=0, mode=0, limits=None):
+    """what the verify_multiple*_msgtable entries would do with n sets over a resident table of table_size entries of which `named` distinct ones are named
+    (0: not known -- the device entries) under `limits` and grouping mode (pure: no GPU) -> dict"""
+    L = limits if limits is not None else default_limits()
+    vp_ = VmSharedMsgsPlan()
+    rc = lib().mbls_plan_verify_multiple_msgtable(C.byref(L), n, table_size, named, mode, C.byref(vp_))
+    if rc != OK:
+        raise MblsError(rc, "mbls_plan_verify_multiple_msgtable")
+    return {f: getattr(vp_, f) for f, _ in VmSharedMsgsPlan._fields_ if f != "reserved"}
+
+
+def plan_verify_multiple_msgtable_workspace_items(n, table_size, named=0, mode=0, limits=None):
+    """workspace items such a call reserves (pure: no GPU; 0 for arguments the plan refuses)"""
+    L = limits if limits is not None else default_limits()
+    return int(lib().mbls_plan_verify_multiple_msgtable_workspace_items(C.byref(L), n, table_size, named, mode))
+
+
+def plan_verify_multiple_msgtable_locate_workspace_items(n, table_size, named=0, mode=0, limits=None):
+    """workspace items a mbls_verify_multiple*_msgtable_locate* call reserves (pure: no GPU)"""
+    L = limits if limits is not None else default_limits()
+    return int(lib().mbls_plan_verify_multiple_msgtable_locate_workspace_items(C.byref(L), n, table_size, named, mode))
+
+
 class StreamOpts(C.Structure):
     """include/mbls.h mbls_stream_opts (0 = default)"""
     _fields_ = [("round_items", C.c_uint64), ("round_keys", C.c_uint64), ("round_msg_bytes", C.c_uint64), ("depth", C.c_uint32), ("policy", C.c_uint32)]
@@ -285,6 +308,15 @@ SIGNATURES = {
                                                                               vp, vp, vp]),
     "mbls_verify_multiple_shared_msgs_locate": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp]),
     "mbls_verify_multiple_shared_msgs_locate_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, SCALAR_SOURCE, vp]),
+    "mbls_plan_verify_multiple_msgtable": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, vp]),
+    "mbls_plan_verify_multiple_msgtable_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int]),
+    "mbls_plan_verify_multiple_msgtable_locate_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int]),
+    "mbls_verify_multiple_msgtable_device": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]),
+    "mbls_verify_multiple_sets_indexed_msgtable_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp]),
+    "mbls_verify_multiple_msgtable_rng": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, SCALAR_SOURCE, vp]),
+    "mbls_verify_multiple_msgtable_locate_device": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp]),
+    "mbls_verify_multiple_sets_indexed_msgtable_locate_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp]),
+    "mbls_verify_multiple_msgtable_locate_rng": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, SCALAR_SOURCE, vp]),
     "mbls_plan_locate_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64]),
     "mbls_verify_multiple_batches_locate_device": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp,
                                                              vp, vp, vp]),

@@ -242,6 +242,25 @@ class AggregatePublicKey:
         return isinstance(other, AggregatePublicKey) and self.point == other.point
 
 
+
+def _reference_draw(rng, failed):
+    """The scalar source of the verify_multiple methods: src/aggregates.rs:280-287 -- 8 random bytes, big-endian i64, absolute value, retry on zero --, for the sets
+    the reference's loop reaches a draw for. An exception must not unwind through the C frames: the batch fails (zero scalars) and the caller raises failed[0]."""
+    def draw(_user, out, count):
+        try:
+            for i in range(count):
+                r = 0
+                while r == 0:
+                    v = int.from_bytes(bytes(rng.getrandbits(8) for _ in range(8)), "big", signed=True)
+                    r = abs(v) & 0xFFFFFFFFFFFFFFFF
+                out[i] = r
+        except BaseException as e:
+            failed.append(e)
+            for i in range(count):
+                out[i] = 0
+    return draw
+
+
 class AggregateSignature:
     """reference src/aggregates.rs:83-334."""
 
@@ -303,19 +322,7 @@ class AggregateSignature:
         if not sets:
             return bool(N.lib().mbls_verify_multiple_aggregate_signatures(_ctx().handle, None, None, None, 0, None, None, 0))
         failed = []
-
-        def draw(_user, out, count):                    # src/aggregates.rs:280-287, for the sets the reference's loop reaches a draw for
-            try:
-                for i in range(count):
-                    r = 0
-                    while r == 0:
-                        v = int.from_bytes(bytes(rng.getrandbits(8) for _ in range(8)), "big", signed=True)
-                        r = abs(v) & 0xFFFFFFFFFFFFFFFF
-                    out[i] = r
-            except BaseException as e:                  # an exception must not unwind through the C frames: the batch fails, the error is raised afterwards
-                failed.append(e)
-                for i in range(count):
-                    out[i] = 0
+        draw = _reference_draw(rng, failed)
         offs = [0]
         for s in sets:
             offs.append(offs[-1] + len(s[2]))
@@ -351,19 +358,7 @@ class AggregateSignature:
         if not sets:
             return (True, []) if locate else True
         failed = []
-
-        def draw(_user, out, count):                    # src/aggregates.rs:280-287, as verify_multiple_aggregate_signatures draws
-            try:
-                for i in range(count):
-                    r = 0
-                    while r == 0:
-                        v = int.from_bytes(bytes(rng.getrandbits(8) for _ in range(8)), "big", signed=True)
-                        r = abs(v) & 0xFFFFFFFFFFFFFFFF
-                    out[i] = r
-            except BaseException as e:                  # an exception must not unwind through the C frames: the batch fails, the error is raised afterwards
-                failed.append(e)
-                for i in range(count):
-                    out[i] = 0
+        draw = _reference_draw(rng, failed)
         index, listed, idx = {}, [], []
         for s in sets:
             m = bytes(s[2])
@@ -385,6 +380,42 @@ class AggregateSignature:
             rc = N.lib().mbls_verify_multiple_shared_msgs_locate_rng(ctx.handle, S, A, M, 0, moff, len(listed), midx, len(sets), res, sres, None, cb, None)
         else:
             rc = N.lib().mbls_verify_multiple_shared_msgs_rng(ctx.handle, S, A, M, 0, moff, len(listed), midx, len(sets), res, cb, None)
+        ctx.check(rc)
+        if failed:
+            raise failed[0]
+        if not locate:
+            return bool(bytes(res)[0])
+        return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:len(sets)]]
+
+    @staticmethod
+    def verify_multiple_aggregate_signatures_msgtable(rng, signature_sets, table):
+        """Not in the reference: verify_multiple_aggregate_signatures over sets (signature, aggregate_public_key, message_index) whose messages are entries of a
+        resident message table (_native.MsgTable): the same bool as that method on the spelled-out messages and `rng` left in the same state, with nothing
+        hashed in the call (mbls_verify_multiple_msgtable_rng). An index that names no entry of the table raises."""
+        return AggregateSignature._vm_msgtable(rng, signature_sets, table, False)
+
+    @staticmethod
+    def verify_multiple_aggregate_signatures_msgtable_locate(rng, signature_sets, table):
+        """verify_multiple_aggregate_signatures_msgtable, and in the same call (mbls_verify_multiple_msgtable_locate_rng) which sets of a rejected call are the bad
+        ones. Returns (bool, list[bool]) with the semantics of verify_multiple_aggregate_signatures_shared_msgs_locate."""
+        return AggregateSignature._vm_msgtable(rng, signature_sets, table, True)
+
+    @staticmethod
+    def _vm_msgtable(rng, signature_sets, table, locate):
+        sets = list(signature_sets)
+        if not sets:
+            return (True, []) if locate else True
+        failed = []
+        cb = N.SCALAR_SOURCE(_reference_draw(rng, failed))
+        midx = (C.c_uint32 * len(sets))(*[int(s[2]) for s in sets])
+        res = N.outbuf(1)
+        ctx = table.ctx
+        S, A = N.cbuf(b"".join(s[0].point for s in sets)), N.cbuf(b"".join(s[1].point for s in sets))
+        if locate:
+            sres = N.outbuf(len(sets))
+            rc = N.lib().mbls_verify_multiple_msgtable_locate_rng(ctx.handle, S, A, table.handle, midx, len(sets), res, sres, None, cb, None)
+        else:
+            rc = N.lib().mbls_verify_multiple_msgtable_rng(ctx.handle, S, A, table.handle, midx, len(sets), res, cb, None)
         ctx.check(rc)
         if failed:
             raise failed[0]
@@ -420,19 +451,7 @@ class AggregateSignature:
         for b in batches:
             boffs.append(boffs[-1] + len(b))
         failed = []
-
-        def draw(_user, out, count):                    # src/aggregates.rs:280-287
-            try:
-                for i in range(count):
-                    r = 0
-                    while r == 0:
-                        v = int.from_bytes(bytes(rng.getrandbits(8) for _ in range(8)), "big", signed=True)
-                        r = abs(v) & 0xFFFFFFFFFFFFFFFF
-                    out[i] = r
-            except BaseException as e:                  # an exception must not unwind through the C frames: the batches fail, the error is raised afterwards
-                failed.append(e)
-                for i in range(count):
-                    out[i] = 0
+        draw = _reference_draw(rng, failed)
         offs = [0]
         for s in sets:
             offs.append(offs[-1] + len(s[2]))

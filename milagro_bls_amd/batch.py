@@ -598,3 +598,72 @@ def verify_multiple_sets_indexed_shared_msgs_locate_device(table, d_sigs, d_key_
     ctx = ctx or table.ctx
     ctx.check(N.lib().mbls_verify_multiple_sets_indexed_shared_msgs_locate_device(ctx.handle, table.handle, d_sigs, d_key_idx, d_offsets, k, d_msgs, msg_len, d_msg_offsets,
                                                                                   n_msgs, d_msg_idx, d_rands, n, d_result, d_status, d_set_results, d_set_status, stream))
+
+
+# ---- verify_multiple over the resident message table, located per set (include/mbls.h, mbls_verify_multiple*_msgtable*): the sets' messages are entries of an
+# N.MsgTable, named by table index; nothing is hashed. The stream, the multi-device handle, the shard form and wire-key sets take per-set messages only.
+plan_verify_multiple_msgtable = N.plan_verify_multiple_msgtable
+plan_verify_multiple_msgtable_workspace_items = N.plan_verify_multiple_msgtable_workspace_items
+plan_verify_multiple_msgtable_locate_workspace_items = N.plan_verify_multiple_msgtable_locate_workspace_items
+
+
+def _scalar_source(draw):
+    """draw(count) -> `count` nonzero scalars, as the C callback the _rng entries take"""
+    def source(_user, out, count):
+        for i, v in enumerate(draw(int(count))):
+            out[i] = v
+    return N.SCALAR_SOURCE(source)
+
+
+def verify_multiple_msgtable_device(msg_table, d_sigs, d_apks, d_msg_idx, d_rands, n, d_result, d_status=None, stream=None, ctx=None):
+    """verify_multiple over device buffers with set i's message the entry d_msg_idx[i] of the resident table. Enqueues only: the bool at the device byte
+    d_result, the status word at d_status (optional). An index at or above the table's size rejects its set (MBLS_ST_BAD_MSG_RANGE)."""
+    ctx = ctx or msg_table.ctx
+    ctx.check(N.lib().mbls_verify_multiple_msgtable_device(ctx.handle, d_sigs, d_apks, msg_table.handle, d_msg_idx, d_rands, n, d_result, d_status, stream))
+
+
+def verify_multiple_sets_indexed_msgtable_device(table, msg_table, d_sigs, d_key_idx, d_msg_idx, d_rands, n, d_result, d_status=None, k=0, d_offsets=None, stream=None,
+                                                 ctx=None):
+    """The same over sets named by indices into a resident KeyTable: keys by key-table index, messages by message-table index. Enqueues only."""
+    ctx = ctx or table.ctx
+    ctx.check(N.lib().mbls_verify_multiple_sets_indexed_msgtable_device(ctx.handle, table.handle, d_sigs, d_key_idx, d_offsets, k, msg_table.handle, d_msg_idx, d_rands, n,
+                                                                        d_result, d_status, stream))
+
+
+def verify_multiple_msgtable_rng(msg_table, sigs, apks, msg_idx, n, draw, ctx=None):
+    """Host buffers and the reference's draw order (mbls_verify_multiple_msgtable_rng; draw as verify_multiple_shared_msgs_rng takes it). An index that names no
+    entry raises (MBLS_ERR_ARGUMENT). Returns the bool."""
+    ctx = ctx or msg_table.ctx
+    res = N.outbuf(1)
+    cb = _scalar_source(draw)
+    ctx.check(N.lib().mbls_verify_multiple_msgtable_rng(ctx.handle, N.cbuf(sigs), N.cbuf(apks), msg_table.handle, _midx(msg_idx, n), n, res, cb, None))
+    return bool(bytes(res)[0])
+
+
+def verify_multiple_msgtable_locate_device(msg_table, d_sigs, d_apks, d_msg_idx, d_rands, n, d_result, d_set_results, d_status=None, d_set_status=None, stream=None,
+                                           ctx=None):
+    """verify_multiple_msgtable_device, and in the same call one answer per SET: n result bytes at d_set_results (required), n status words at d_set_status
+    (optional), with the semantics of verify_multiple_shared_msgs_locate_device. Enqueues only."""
+    ctx = ctx or msg_table.ctx
+    ctx.check(N.lib().mbls_verify_multiple_msgtable_locate_device(ctx.handle, d_sigs, d_apks, msg_table.handle, d_msg_idx, d_rands, n, d_result, d_status, d_set_results,
+                                                                  d_set_status, stream))
+
+
+def verify_multiple_sets_indexed_msgtable_locate_device(table, msg_table, d_sigs, d_key_idx, d_msg_idx, d_rands, n, d_result, d_set_results, d_status=None,
+                                                        d_set_status=None, k=0, d_offsets=None, stream=None, ctx=None):
+    """The same over sets named by indices into a resident KeyTable. Enqueues only."""
+    ctx = ctx or table.ctx
+    ctx.check(N.lib().mbls_verify_multiple_sets_indexed_msgtable_locate_device(ctx.handle, table.handle, d_sigs, d_key_idx, d_offsets, k, msg_table.handle, d_msg_idx,
+                                                                               d_rands, n, d_result, d_status, d_set_results, d_set_status, stream))
+
+
+def verify_multiple_msgtable_locate_rng(msg_table, sigs, apks, msg_idx, n, draw, ctx=None):
+    """verify_multiple_msgtable_rng with one answer per set. A set at or behind the first signature outside G2 has no scalar and reads False. Returns
+    (bool, set_results, set_status)."""
+    ctx = ctx or msg_table.ctx
+    res = N.outbuf(1)
+    sres = N.outbuf(max(1, n))
+    sst = (C.c_uint32 * max(1, n))()
+    cb = _scalar_source(draw)
+    ctx.check(N.lib().mbls_verify_multiple_msgtable_locate_rng(ctx.handle, N.cbuf(sigs), N.cbuf(apks), msg_table.handle, _midx(msg_idx, n), n, res, sres, sst, cb, None))
+    return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:n]], list(sst)[:n]

@@ -16,6 +16,7 @@
 // lane-private memory; LDS is the shared register file of the wave.
 #pragma once
 #include "mbls_lanes.h"
+#include "mbls_vmt.h"
 #include "mbls_coop_prog.inc"
 
 #define COOP_SW 16                       // dwords per slot: 14 digits + 2 (16-byte aligned: a slot moves with four 128-bit LDS accesses)
@@ -122,6 +123,7 @@ MBLS_FN void coop_from_words(int32_t* out, fp w) {
 // partner_step: LOADW with bit 16 of its workspace slot set reads from item + partner_step instead (the other operand of a tree product).
 // POW: the instance that also knows the fixed-exponent step (its routine keeps a window table in AGPRs: the plain instance stays small
 // enough for two waves per SIMD).
+// live: see the first statement of the kernel.
 // LPI: lanes of a step one item uses -- 64: one item per wave, its slots in a static allocation (the latency path); 32 / 16: two / four
 // items per wave side by side, each with its own slots and flag words in the dynamic allocation (COOP_LDS_BYTES).
 #ifdef MBLS_COOP_PROFILE
@@ -134,8 +136,11 @@ __device__ unsigned long long mbls_coop_prof[16 * 4];
 #endif
 template <bool POW, int LPI>
 __global__ void __launch_bounds__(64) k_coop_t(coop_prog pg, mbls_ws ws, uint64_t first_item, uint64_t item_step, uint64_t partner_step, uint64_t n_items,
-                                             uint32_t* status, uint8_t* results, int res_mode) {
+                                             uint32_t* status, uint8_t* results, int res_mode, const uint32_t* live) {
 #if MBLS_DEVICE_ASM && !defined(MBLS_NO_FP2_ASM)
+    // live (optional): a device-side count of the items that have a pair at all (mbls_vmt.h: the named entries of a call over a resident table). A wave whose
+    // items all lie at or above it returns before any arithmetic -- what it would have written is in place already (k_vmt_heads). NULL: every item is live.
+    if (live && vmt_wave_idle((uint64_t)blockIdx.x * (64u / LPI), live[0])) return;
     extern __shared__ __attribute__((aligned(16))) int32_t coop_lds[];
     __shared__ __attribute__((aligned(16))) int32_t S1[LPI == 64 ? MBLS_COOP_MAX_SLOTS * COOP_SW : 16];
     __shared__ uint32_t flags1[64];

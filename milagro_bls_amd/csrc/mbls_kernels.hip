@@ -15,6 +15,7 @@
 #include <new>
 #include <mutex>
 #include <vector>
+#include <algorithm>
 #include <atomic>
 #include <dlfcn.h>
 #include <unistd.h>
@@ -24,6 +25,7 @@
 #include "mbls_vml.h"
 #include "mbls_vms.h"
 #include "mbls_vsl.h"
+#include "mbls_vmt.h"
 #include "mbls_mtb.h"
 #include "mbls_batch.h"
 #include "../../include/mbls.h"
@@ -703,6 +705,60 @@ __global__ void __launch_bounds__(MBLS_HB) k_vms_heads(mbls_ws ws, const uint32_
     ws_st(ws, MBLS_SLOT_APK, j, fp_select(some, a.x, o.x)); ws_st(ws, MBLS_SLOT_APK + 1, j, fp_select(some, a.y, o.y)); ws_st(ws, MBLS_SLOT_APK + 2, j, fp_select(some, a.z, o.z));
     if (some && st) atomicOr(st_or, st);
 }
+// ---- verify_multiple over the RESIDENT message table (mbls_verify_multiple*_msgtable*): the grouping above runs with the table as the list (n_msgs = T, the
+// table's size when the call is enqueued), and the table may hold far more entries than the call names -- so the Miller items are the entries that are NAMED,
+// compacted on the device (mbls_vmt.h): flag[j] = cnt[j] != 0, roff = the exclusive scan of the flags (k_vms_scan over the flag words), named[roff[j]] = j.
+// D = roff[T] stays on the device; the host sizes the Miller phase by a bound on it (vmt_bound).
+__global__ void MBLS_LB k_vmt_flag(const uint32_t* cnt, uint64_t T, uint32_t* flag) {
+    const uint64_t j = gid(); if (j >= T) return;
+    flag[j] = vmt_flag(cnt[j]);
+}
+__global__ void MBLS_LB k_vmt_named(const uint32_t* flag, const uint32_t* roff, uint64_t T, uint32_t* named) {
+    const uint64_t j = gid(); if (j >= T) return;
+    uint32_t slot;
+    if (vmt_named_slot(flag, roff, j, &slot) && (uint64_t)slot < T) named[slot] = (uint32_t)j;
+}
+// the twin of k_vms_heads. Miller item r < miller_items, D = *live: r < D -- H <- table entry named[r], APK <- the sum at the head of that entry's range (a
+// flagged entry rejects the check: some set names it); otherwise the private entry and the point at infinity (the pair is skipped and contributes 1), and slot F
+// <- 1, which is what a wave that returns early (k_coop_t's live count, k_vmt_miller) leaves for the product tree. Every slot the Miller loops read is written here.
+__global__ void __launch_bounds__(MBLS_HB) k_vmt_heads(mbls_ws ws, const uint32_t* tab, uint64_t tstride, const uint32_t* flags, uint64_t T, const uint32_t* off,
+                                                       const uint32_t* named, const uint32_t* live, uint64_t miller_items, uint64_t pbase, uint32_t* st_or) {
+    const uint64_t r = (uint64_t)blockIdx.x * MBLS_HB + threadIdx.x; if (r >= miller_items) return;
+    const uint64_t D = live[0];
+    if (r == 0 && vmt_overflow(D, miller_items)) atomicOr(st_or, MBLS_ST_BAD_MSG_RANGE);      // fail closed (vmt_bound makes this unreachable)
+    uint32_t idx; uint64_t pos;
+    const bool some = vmt_head(named, off, D, r, &idx, &pos) && (uint64_t)idx < T;
+    const uint32_t st = lane_h_gather(ws, r, tab, tstride, flags, some ? idx : MBLS_VMT_NO_ENTRY, T);
+    const uint64_t it = pbase + (some ? pos : 0);
+    g1j o; g1_set_inf(&o);
+    g1j a; a.x = ws_ld(ws, MBLS_SLOT_APK, it); a.y = ws_ld(ws, MBLS_SLOT_APK + 1, it); a.z = ws_ld(ws, MBLS_SLOT_APK + 2, it);
+    ws_st(ws, MBLS_SLOT_APK, r, fp_select(some, a.x, o.x)); ws_st(ws, MBLS_SLOT_APK + 1, r, fp_select(some, a.y, o.y)); ws_st(ws, MBLS_SLOT_APK + 2, r, fp_select(some, a.z, o.z));
+    if (!some) {
+        fp12 f; fp12_set_one(&f);
+        const fp* one = &f.c0.c0.c0;
+        for (int t = 0; t < 12; t++) ws_st(ws, MBLS_SLOT_F + t, r, one[t]);
+    }
+    if (some && st) atomicOr(st_or, st);
+}
+// the lane forms of the Miller loops over such Miller items (wv = the workspace seen from the launch's first item, which is Miller item `first`; cnt items):
+// k_miller_single's and k_miller_single2's body for the items below the live count; a wave without one returns after one ballot, as the locate phase's waves
+// without a candidate do -- it leaves its SIMD to the chains beside it, and whole idle rounds above a round of Miller items cost nothing (a call of one round
+// is not shortened: its live waves still take the lane form's time)
+template <int LPP> MBLS_FN void vmt_miller_body(const mbls_ws& wv, uint64_t cnt, uint64_t first, const uint32_t* live, uint32_t* spill) {
+    const uint64_t t = LPP == 2 ? gid() >> 1 : gid();
+    const bool on = t < cnt && !vmt_wave_idle(first + t, live[0]);
+    if (!__ballot(on)) return;
+    if (!on) return;
+    miller_single_body<LPP>(wv, cnt, 0, 0, spill);
+}
+__global__ void MBLS_LB k_vmt_miller(mbls_ws wv, uint64_t cnt, uint64_t first, const uint32_t* live) {
+    __shared__ uint32_t spill[154 * 64];
+    vmt_miller_body<1>(wv, cnt, first, live, spill);
+}
+__global__ void MBLS_LB k_vmt_miller2(mbls_ws wv, uint64_t cnt, uint64_t first, const uint32_t* live) {
+    __shared__ uint32_t spill[154 * 64];
+    vmt_miller_body<2>(wv, cnt, first, live, spill);
+}
 // the tail: one final exponentiation per batch with verify_multiple's reject mask (lane_final<true>: the body of k_final / k_final2, the fold of final_fold_batch)
 __global__ void MBLS_LB k_vmb_final(mbls_ws ws, uint32_t* status, uint8_t* results, uint64_t n) {
     __shared__ uint32_t accstore[154 * 64];
@@ -1172,8 +1228,9 @@ struct mbls_ctx {
     // call after every (re)allocation; message j: entry j + 1), one bad-range word per entry, and the status words of the list's own hash
     uint64_t htab_cap = 0; uint32_t* d_htab = nullptr; uint32_t* d_hflag = nullptr; uint32_t* d_hst = nullptr; bool h_empty_ready = false;
     // verify_multiple over a shared list, grouped by message (mbls_vms.h): per table entry the sets that name it, the cursor that hands out their positions and
-    // the exclusive scan (d_hgrp: [3][htab_cap], allocated with the table), and per workspace item the map position -> message (d_vmap: [cap], with the workspace)
-    uint32_t* d_hgrp = nullptr; uint32_t* d_vmap = nullptr;
+    // the exclusive scan, and over a resident table (mbls_vmt.h) the named flags, their scan and the named entries (d_hgrp: [MBLS_HGRP_ARRAYS][hgrp_cap], sized by
+    // reserve_groups for the list or the table of the call), and per workspace item the map position -> message (d_vmap: [cap], with the workspace)
+    uint32_t* d_hgrp = nullptr; uint64_t hgrp_cap = 0; uint32_t* d_vmap = nullptr;
     int vm_grouping = 0;               // mbls_ctx_set_vm_grouping: 0 auto (vms_grouped), 1 always one Miller loop per message, 2 never
     struct { void* p; size_t cap; } stage[MBLS_N_STAGE] = {};
     hipStream_t hs_a = nullptr, hs_b = nullptr, hs_c = nullptr, hs_d = nullptr;      // streams of the host-buffer entry points (hs_d: the signature phase while hs_b uploads keys)
@@ -1248,19 +1305,19 @@ static void launch_aggregate(mbls_ws ws, const uint8_t* d_pks, const uint32_t* d
 // one launch of the cooperative kernel: program `prog` on n_items items (64 / lpi of them per wave)
 enum { COOP_PAIRING2 = 0, COOP_VMTAIL, COOP_F12MUL, COOP_G2ADD, COOP_SMILLER, COOP_VMFINAL, COOP_HASHG2, COOP_MILLER1, COOP_PAIRING2X2, COOP_HASHG2X4 };
 static void coop_run(mbls_ctx* c, int prog, mbls_ws ws, uint64_t first_item, uint64_t item_step, uint64_t partner_step, uint64_t n_items, uint32_t* st, uint8_t* res,
-                     int res_mode, hipStream_t s) {
+                     int res_mode, hipStream_t s, const uint32_t* d_live = nullptr) {
     const coop_prog& pg = c->coop[prog];
     const uint64_t ipw = 64 / pg.lpi;
     const dim3 grid((unsigned)((n_items + ipw - 1) / ipw));
     const size_t lds = COOP_LDS_BYTES(pg);
     if (prog == COOP_HASHG2X4)
-        hipLaunchKernelGGL(k_coop_pow_x4, grid, dim3(64), lds, s, pg, ws, first_item, item_step, partner_step, n_items, st, res, res_mode);
+        hipLaunchKernelGGL(k_coop_pow_x4, grid, dim3(64), lds, s, pg, ws, first_item, item_step, partner_step, n_items, st, res, res_mode, d_live);
     else if (prog == COOP_HASHG2)
-        hipLaunchKernelGGL(k_coop_pow, grid, dim3(64), lds, s, pg, ws, first_item, item_step, partner_step, n_items, st, res, res_mode);
+        hipLaunchKernelGGL(k_coop_pow, grid, dim3(64), lds, s, pg, ws, first_item, item_step, partner_step, n_items, st, res, res_mode, d_live);
     else if (prog == COOP_PAIRING2X2)
-        hipLaunchKernelGGL(k_coop_x2, grid, dim3(64), lds, s, pg, ws, first_item, item_step, partner_step, n_items, st, res, res_mode);
+        hipLaunchKernelGGL(k_coop_x2, grid, dim3(64), lds, s, pg, ws, first_item, item_step, partner_step, n_items, st, res, res_mode, d_live);
     else
-        hipLaunchKernelGGL(k_coop, grid, dim3(64), lds, s, pg, ws, first_item, item_step, partner_step, n_items, st, res, res_mode);
+        hipLaunchKernelGGL(k_coop, grid, dim3(64), lds, s, pg, ws, first_item, item_step, partner_step, n_items, st, res, res_mode, d_live);
 }
 // which form the message phase of n items takes: lane pairs (k_hash2) where the caller reserved 2 n workspace items and the batch is above the wave engine's range
 // but at most hash2_max_items (5/16 of a round: 2 n lanes for the messages beside n for the keys, with the signatures behind them, are still resident together; at a
@@ -1489,14 +1546,23 @@ extern "C" int mbls_ctx_reserve_keys(mbls_ctx* c, uint64_t max_keys) {
     HIPCHK(c, hipSetDevice(c->device));
     return reserve_keys(c, max_keys);
 }
+// the group arrays of verify_multiple's grouped route alone, for `entries` messages of a list or entries of a resident table (+ 1: the scans' last word): a call
+// over a resident table needs these and no call table (288 bytes per entry that it would never read). Grow-only; growth drains the device like mbls_ctx_reserve.
+#define MBLS_HGRP_ARRAYS 6                    /* cnt, cur, off (mbls_vms.h); flag, roff, named (mbls_vmt.h) */
+static int reserve_groups(mbls_ctx* c, uint64_t entries) {
+    const uint64_t want = ((entries + 1 + WG - 1) / WG) * WG;
+    if (want <= c->hgrp_cap) return MBLS_OK;
+    if (c->d_hgrp) { (void)hipFree(c->d_hgrp); c->d_hgrp = nullptr; c->hgrp_cap = 0; }
+    HIPCHK(c, hipMalloc(&c->d_hgrp, (size_t)MBLS_HGRP_ARRAYS * want * 4));
+    c->hgrp_cap = want; return MBLS_OK;
+}
 // the table of hashed points of a shared message list: max_msgs messages + the entry of the empty message (grow-only; growth drains the device like mbls_ctx_reserve)
 static int reserve_msgs(mbls_ctx* c, uint64_t max_msgs) {
+    const int rg = reserve_groups(c, max_msgs); if (rg) return rg;
     const uint64_t want = ((max_msgs + 1 + WG - 1) / WG) * WG;
     if (want <= c->htab_cap) return MBLS_OK;
     if (c->d_htab) { (void)hipFree(c->d_htab); (void)hipFree(c->d_hflag); (void)hipFree(c->d_hst); c->d_htab = nullptr; c->d_hflag = nullptr; c->d_hst = nullptr; c->htab_cap = 0; }
-    if (c->d_hgrp) { (void)hipFree(c->d_hgrp); c->d_hgrp = nullptr; }
     c->h_empty_ready = false;
-    HIPCHK(c, hipMalloc(&c->d_hgrp, 3 * want * 4));
     HIPCHK(c, hipMalloc(&c->d_htab, (size_t)MBLS_H_DWORDS * want * 4));
     HIPCHK(c, hipMalloc(&c->d_hflag, want * 4));
     HIPCHK(c, hipMalloc(&c->d_hst, want * 4));
@@ -1725,6 +1791,27 @@ extern "C" uint64_t mbls_plan_verify_multiple_shared_msgs_workspace_items(const 
     if (!limits || !n || mode < 0 || mode > 2) return 0;
     mbls_vm_shared_msgs_plan vp; plan_vm_shared(*limits, n, n_msgs, mode, 0, &vp);
     return vp.workspace_items;
+}
+// verify_multiple over the resident message table (mbls_verify_multiple*_msgtable*): plan_vm_shared's rule with `bound` -- what the host knows about the number
+// of distinct entries the call names (mbls_vmt.h vmt_bound) -- in place of the list length, and no list: nothing is hashed, no call table is needed
+static void plan_vm_msgtable(const mbls_limits& L, uint64_t n, uint64_t table_size, uint64_t named, int mode, uint64_t longest, mbls_vm_shared_msgs_plan* vp) {
+    plan_vm_shared(L, n, vmt_bound(n, table_size, named), mode, longest, vp);
+    vp->list_message = 0; vp->list_pieces = 0; vp->list_piece_items = 0; vp->list_workspace_items = 0; vp->table_entries = 0;
+    vp->workspace_items = vmt_workspace_items(n, vmt_bound(n, table_size, named), vp->route == MBLS_VM_ROUTE_GROUPED);
+}
+extern "C" int mbls_plan_verify_multiple_msgtable(const mbls_limits* limits, uint64_t n, uint64_t table_size, uint64_t named, int mode, mbls_vm_shared_msgs_plan* out) {
+    if (!limits || !out || !n || mode < 0 || mode > 2) return MBLS_ERR_ARGUMENT;
+    plan_vm_msgtable(*limits, n, table_size, named, mode, 0, out); return MBLS_OK;
+}
+extern "C" uint64_t mbls_plan_verify_multiple_msgtable_workspace_items(const mbls_limits* limits, uint64_t n, uint64_t table_size, uint64_t named, int mode) {
+    if (!limits || !n || mode < 0 || mode > 2) return 0;
+    mbls_vm_shared_msgs_plan vp; plan_vm_msgtable(*limits, n, table_size, named, mode, 0, &vp);
+    return vp.workspace_items;
+}
+extern "C" uint64_t mbls_plan_verify_multiple_msgtable_locate_workspace_items(const mbls_limits* limits, uint64_t n, uint64_t table_size, uint64_t named, int mode) {
+    if (!limits || !n || mode < 0 || mode > 2) return 0;
+    mbls_vm_shared_msgs_plan vp; plan_vm_msgtable(*limits, n, table_size, named, mode, 0, &vp);
+    return vsl_workspace_items(n, vmt_bound(n, table_size, named), vp.route == MBLS_VM_ROUTE_GROUPED, 0);
 }
 #ifdef MBLS_COOP_PROFILE
 extern "C" int mbls_coop_profile_read(unsigned long long out[64], int reset) {     // dev builds only (not declared in mbls.h)
@@ -3065,9 +3152,18 @@ static void g2_tree(mbls_ctx* c, mbls_ws ws, uint64_t m, hipStream_t s) { g2_tre
 // m one-pair Miller loops over items [0, m) of ws (k_miller_single's layout), one lane per pair; half a round or less: two lanes per pair, products in
 // pairs (4.9 ms instead of 6.7). Above a round the whole rounds go first and what is left of the last one follows as a launch of its own in the form
 // its size allows (81 920 pairs: 6.7 + 4.9 ms instead of two rounds)
-static void launch_miller_single(mbls_ctx* c, mbls_ws ws, uint64_t m, hipStream_t s) {
+// d_live (calls over a resident message table): the device-side count of items that have a pair; the same cuts on k_vmt_miller / k_vmt_miller2
+static void launch_miller_single(mbls_ctx* c, mbls_ws ws, uint64_t m, hipStream_t s, const uint32_t* d_live = nullptr) {
     const uint64_t R = c->round_items;
     const uint64_t full = m > R ? (m / R) * R : 0, rest = m - full;
+    if (d_live) {
+        if (full) hipLaunchKernelGGL(k_vmt_miller, dim3(nblk(full)), dim3(WG), 0, s, ws, full, (uint64_t)0, d_live);
+        if (!rest) return;
+        mbls_ws wr = ws; wr.w += full;
+        if (2 * rest <= R) hipLaunchKernelGGL(k_vmt_miller2, dim3(nblk(2 * rest)), dim3(WG), 0, s, wr, rest, full, d_live);
+        else hipLaunchKernelGGL(k_vmt_miller, dim3(nblk(rest)), dim3(WG), 0, s, wr, rest, full, d_live);
+        return;
+    }
     if (full) hipLaunchKernelGGL(k_miller_single, dim3(nblk(full)), dim3(WG), 0, s, ws, full, 0, (uint64_t)0);
     if (!rest) return;
     mbls_ws wr = ws; wr.w += full;
@@ -3075,16 +3171,17 @@ static void launch_miller_single(mbls_ctx* c, mbls_ws ws, uint64_t m, hipStream_
     else hipLaunchKernelGGL(k_miller_single, dim3(nblk(rest)), dim3(WG), 0, s, wr, rest, 0, (uint64_t)0);
 }
 static int npairing_finish(mbls_ctx* c, uint64_t n, hipStream_t s, uint8_t* d_result, hipEvent_t s_miller_ev = nullptr, bool late_status = false,
-                           uint32_t* d_partial = nullptr, bool side_s_chain = false, uint64_t n_sets = 0, uint64_t keep_f_at = 0) {
+                           uint32_t* d_partial = nullptr, bool side_s_chain = false, uint64_t n_sets = 0, uint64_t keep_f_at = 0, const uint32_t* d_live = nullptr) {
+    // d_live (calls over a resident message table, grouped): the device-side count of Miller items that have a pair; waves without one return at once
     // n_sets (grouped shared-message route): the n Miller items are the MESSAGES; the signatures' sum tree and the status fold still cover all n_sets sets
     // keep_f_at (locate calls on the per-set route): the first shadow item -- the sets' Miller values are copied there before the product tree runs over them
     const uint64_t ns = n_sets ? n_sets : n;
     const bool s_miller_done = s_miller_ev != nullptr || side_s_chain;
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     if (2 * n <= c->coop_max_items)     // few pairs: one WAVE per Miller loop (program miller1, ~0.9 ms) instead of one lane (6.6 ms)
-        coop_run(c, COOP_MILLER1, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, n, (uint32_t*)nullptr, (uint8_t*)nullptr, COOP_RES_ITEM, s);
+        coop_run(c, COOP_MILLER1, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, n, (uint32_t*)nullptr, (uint8_t*)nullptr, COOP_RES_ITEM, s, d_live);
     else
-        launch_miller_single(c, ws, n, s);
+        launch_miller_single(c, ws, n, s, d_live);
     if (keep_f_at) hipLaunchKernelGGL(k_vml_keep_f, dim3(nblk(n)), dim3(WG), 0, s, ws, n, keep_f_at);
     if (side_s_chain) {
         HIPCHK(c, hipEventRecord(c->hs_ev2, s)); HIPCHK(c, hipStreamWaitEvent(c->hs_b, c->hs_ev2, 0));
@@ -3274,10 +3371,22 @@ struct vm_shared {
     // the _locate entries: the sets' answers as well (d_set_results required, d_set_status optional), shadow items behind phase one's workspace (mbls_vsl.h)
     bool locate = false; uint8_t* d_set_results = nullptr; uint32_t* d_set_status = nullptr;
     uint64_t shadow_first = 0;         // (set by vm_shared_plan_and_reserve)
+    // the _msgtable entries: a resident table in place of the list (n_msgs stays 0; d_midx holds TABLE indices). named: the distinct entries the sets name where the
+    // host has counted them (0: not known). Set by vm_shared_plan_and_reserve from the table as it is then: T, the bound on the named entries (mbls_vmt.h), its buffers.
+    const mbls_msgtable* mt = nullptr; uint64_t named = 0;
+    uint64_t T = 0, bound = 0; const uint32_t* tab = nullptr; uint64_t tstride = 0; const uint32_t* flags = nullptr;
+    // what the grouping runs over and what sizes the Miller phase: the list both times, or the table and the bound
+    uint64_t groups() const { return mt ? T : n_msgs; }
+    uint64_t sized_by() const { return mt ? bound : n_msgs; }
 };
 // the message phase of the shared-message entries on stream s_msg: the list is hashed once into the context's table (the existing path of section 5d); the
 // per-set route then gives every set its point (k_h_gather), the grouped route reads the table from its Miller items (k_vms_heads)
 static int vm_shared_message_phase(mbls_ctx* c, mbls_ws ws, const vm_shared& sh, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n, hipStream_t s_msg) {
+    if (sh.mt) {        // a resident table: nothing to hash; the per-set route gathers straight from it (the grouped route reads it from its Miller items, k_vmt_heads)
+        if (sh.vp.route == MBLS_VM_ROUTE_PER_SET)
+            hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, sh.tab, sh.tstride, sh.flags, sh.d_midx, sh.T, c->d_status, n);
+        return MBLS_OK;
+    }
     const int rc = shared_hash_list(c, sh.sp, d_msgs, msg_len, d_moff, sh.n_msgs, s_msg); if (rc) return rc;
     if (sh.vp.route == MBLS_VM_ROUTE_PER_SET)
         hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, (const uint32_t*)c->d_htab, c->htab_cap,
@@ -3285,6 +3394,17 @@ static int vm_shared_message_phase(mbls_ctx* c, mbls_ws ws, const vm_shared& sh,
     return MBLS_OK;
 }
 static int vm_shared_plan_and_reserve(mbls_ctx* c, vm_shared& sh, uint64_t n) {
+    if (sh.mt) {        // the table at the size it has now (the caller holds the context's lock); only the group arrays are reserved beside the workspace
+        if (sh.mt->c != c) ARGFAIL(c, "message table belongs to another context");
+        sh.T = sh.mt->size; sh.bound = vmt_bound(n, sh.T, sh.named);
+        sh.tab = sh.mt->d_tab; sh.tstride = mtb_stride(sh.mt->cap); sh.flags = sh.mt->d_flag;
+        memset(&sh.sp, 0, sizeof(sh.sp));
+        plan_vm_msgtable(ctx_limits(c), n, sh.T, sh.named, c->vm_grouping, sh.longest, &sh.vp);
+        const bool grouped = sh.vp.route == MBLS_VM_ROUTE_GROUPED;
+        sh.shadow_first = vsl_shadow_first(n, sh.bound, grouped, 0);
+        const int rc = mbls_ctx_reserve(c, sh.locate ? vsl_workspace_items(n, sh.bound, grouped, 0) : sh.vp.workspace_items); if (rc) return rc;
+        return reserve_groups(c, sh.T);
+    }
     plan_shared(ctx_limits(c), n, sh.n_msgs, false, false, &sh.sp);
     plan_vm_shared(ctx_limits(c), n, sh.n_msgs, c->vm_grouping, sh.longest, &sh.vp);
     const bool grouped = sh.vp.route == MBLS_VM_ROUTE_GROUPED;
@@ -3315,6 +3435,7 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
     }
     if (!d_rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
     if ((!d_sigs && !sigs_resident) || (!d_msgs && msg_len && !d_moff && !(sh && !sh->n_msgs))) ARGFAIL(c, "null buffer");
+    if (sh && sh->mt && d_partial) ARGFAIL(c, "the shard form takes per-set messages only");
     // batches of at most half a round: two lanes per message in the message phase (items [0, 2 n), slots no other chain touches)
     const bool pair_hash = !sh && n <= c->split_max_items && 2 * n <= c->round_items;
     // a shared list: the workspace (sets, Miller items, positions, the list's own hash) and the table are reserved here, once, before the first kernel
@@ -3326,6 +3447,10 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
     uint32_t* const cand = c->d_status + vsl_flags_first(n);
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     rc = ws_acquire(c, s); if (rc) return rc;
+    // a resident message table: its last append and the key table's are awaited on the caller's stream HERE, before anything is enqueued on a side stream -- every
+    // stream of the call forks from s behind them, and no fallible step is left once a side stream has work
+    const bool over_table = sh && sh->mt;
+    if (over_table) { rc = msgtable_acquire(c, sh->mt, s); if (rc) return rc; if (tab) { rc = table_acquire(c, tab, s); if (rc) return rc; } }
     if (loc) {
         HIPCHK(c, hipMemsetAsync(sh->d_set_results, 0, n, s));      // fail closed
         if (sh->d_set_status) HIPCHK(c, hipMemsetAsync(sh->d_set_status, 0, 4 * n, s));
@@ -3351,17 +3476,18 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
     };
     if (hash_first) { rc = message_phase(); if (rc) return rc; }
     if (tab) {      // sets given by indices into a resident key table: the indexed key sum (the keys were decoded and validated once)
-        rc = table_acquire(c, tab, s); if (rc) return rc;
+        if (!over_table) { rc = table_acquire(c, tab, s); if (rc) return rc; }
         hipLaunchKernelGGL(k_aggregate_indexed_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)tab->d_recs, tab->size, d_idx, d_pk_offsets, k, MBLS_MODE_VERIFY, c->d_status, n);
     } else if (!d_apks)    // sets given by their wire-format keys: AggregatePublicKey::aggregate on the device first (src/aggregates.rs:29-39)
         launch_aggregate(ws, d_pks, d_pk_offsets, k, pk_format, MBLS_MODE_VERIFY, c->d_status, n, s);
     hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, tab ? (const uint8_t*)nullptr : d_apks, d_rands, c->d_status, n);
     // one Miller loop per message: count, scan, scatter and the per-message sums of the blinded keys follow the keys on their stream (beside the list's hash and
     // the signature chain where the chains run side by side); the heads wait for the table further down
-    const uint64_t pbase = grouped ? vms_position_base(n, sh->n_msgs) : 0;
-    uint32_t* const g_cnt = c->d_hgrp; uint32_t* const g_cur = c->d_hgrp + c->htab_cap; uint32_t* const g_off = c->d_hgrp + 2 * c->htab_cap;
+    const uint64_t pbase = grouped ? vms_position_base(n, sh->sized_by()) : 0;
+    uint32_t* const g_cnt = c->d_hgrp; uint32_t* const g_cur = c->d_hgrp + c->hgrp_cap; uint32_t* const g_off = c->d_hgrp + 2 * c->hgrp_cap;
+    uint32_t* const g_flag = c->d_hgrp + 3 * c->hgrp_cap; uint32_t* const g_roff = c->d_hgrp + 4 * c->hgrp_cap; uint32_t* const g_named = c->d_hgrp + 5 * c->hgrp_cap;
     if (grouped) {
-        const uint64_t M = sh->n_msgs;
+        const uint64_t M = sh->groups();
         HIPCHK(c, hipMemsetAsync(g_cnt, 0, 4 * (M + 1), s)); HIPCHK(c, hipMemsetAsync(g_cur, 0, 4 * (M + 1), s)); HIPCHK(c, hipMemsetAsync(c->d_vmap, 0xFF, 4 * n, s));
         hipLaunchKernelGGL(k_vms_count, dim3(nblk(n)), dim3(WG), 0, s, sh->d_midx, M, n, g_cnt, c->d_status);
         hipLaunchKernelGGL(k_vms_scan, dim3(1), dim3(MBLS_VMS_SCAN_LANES), 0, s, (const uint32_t*)g_cnt, M, g_off);
@@ -3371,7 +3497,16 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
         uint64_t half = 1;
         for (uint32_t l = 0; l < sh->vp.tree_levels; l++, half *= 2)
             hipLaunchKernelGGL(k_g1_seg_tree_d, dim3(nblk(n)), dim3(WG), 0, s, wp, (const uint32_t*)c->d_vmap, (const uint32_t*)g_off, M, n, half);
+        if (over_table) {       // the entries the call names, in increasing table index; D = g_roff[M] stays on the device (mbls_vmt.h)
+            HIPCHK(c, hipMemsetAsync(g_roff, 0, 4 * (M + 1), s));
+            if (M) {
+                hipLaunchKernelGGL(k_vmt_flag, dim3(nblk(M)), dim3(WG), 0, s, (const uint32_t*)g_cnt, M, g_flag);
+                hipLaunchKernelGGL(k_vms_scan, dim3(1), dim3(MBLS_VMS_SCAN_LANES), 0, s, (const uint32_t*)g_flag, M, g_roff);
+                hipLaunchKernelGGL(k_vmt_named, dim3(nblk(M)), dim3(WG), 0, s, (const uint32_t*)g_flag, (const uint32_t*)g_roff, M, g_named);
+            }
+        }
     }
+    const uint32_t* const d_live = grouped && over_table ? g_roff + sh->T : nullptr;      // the Miller items that have a pair at all
     // small batches (their Miller loops run one WAVE per pair, see npairing_finish): the signature chain is what the call waits for -- two lanes per signature
     if (2 * n <= c->coop_max_items)
         hipLaunchKernelGGL(k_blind_sig2_d, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, c->d_status, n);
@@ -3393,17 +3528,20 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
         HIPCHK(c, hipStreamWaitEvent(s, c->hs_ev3, 0));
     } else
         hipLaunchKernelGGL(k_status_or, dim3(nblk(n)), dim3(WG), 0, s, c->d_status, n, c->d_scalar);
-    if (grouped)     // the table is complete: every Miller item gets its message's point and its group's key (a bad listed range some set names: the status word)
+    if (grouped && over_table)
+        hipLaunchKernelGGL(k_vmt_heads, dim3((unsigned)((n_miller + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s, ws, sh->tab, sh->tstride, sh->flags, sh->T, (const uint32_t*)g_off,
+                           (const uint32_t*)g_named, d_live, n_miller, pbase, c->d_scalar);
+    else if (grouped)     // the table is complete: every Miller item gets its message's point and its group's key (a bad listed range some set names: the status word)
         hipLaunchKernelGGL(k_vms_heads, dim3((unsigned)((n_miller + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s, ws, (const uint32_t*)c->d_htab, c->htab_cap,
                            (const uint32_t*)c->d_hflag, (const uint32_t*)g_off, (const uint32_t*)g_cnt, sh->n_msgs, n_miller, pbase, c->d_scalar);
     // a set whose signature is outside G2 (reference src/aggregates.rs:274-276), an undecodable member or a zero scalar makes the tail
     // answer false: the status bits are folded in on the device, the call only enqueues
-    rc = npairing_finish(c, n_miller, s, d_result, fork ? c->hs_ev : nullptr, fork, d_partial, side_s_chain, n, loc && !grouped ? shf : 0); if (rc) return rc;
+    rc = npairing_finish(c, n_miller, s, d_result, fork ? c->hs_ev : nullptr, fork, d_partial, side_s_chain, n, loc && !grouped ? shf : 0, d_live); if (rc) return rc;
     if (d_status_or) HIPCHK(c, hipMemcpyAsync(d_status_or, c->d_scalar, 4, hipMemcpyDeviceToDevice, s));
     if (loc && grouped) {      // phase two, enqueued whatever the verdict is: mark through msg_idx (candidates get their H), both pairs' Miller loops, product, final
         mbls_ws wsa = ws; wsa.w += shf;
-        hipLaunchKernelGGL(k_vsl_mark, dim3(nblk(n)), dim3(WG), 0, s, wsa, (const uint32_t*)c->d_htab, c->htab_cap, (const uint32_t*)c->d_hflag, sh->d_midx, sh->n_msgs, n,
-                           (const uint32_t*)c->d_status, (const uint8_t*)d_result, cand, sh->d_set_results, sh->d_set_status);
+        hipLaunchKernelGGL(k_vsl_mark, dim3(nblk(n)), dim3(WG), 0, s, wsa, over_table ? sh->tab : (const uint32_t*)c->d_htab, over_table ? sh->tstride : c->htab_cap,
+                           over_table ? sh->flags : (const uint32_t*)c->d_hflag, sh->d_midx, sh->groups(), n, (const uint32_t*)c->d_status, (const uint8_t*)d_result, cand, sh->d_set_results, sh->d_set_status);
         vsl_examine(c, ws, n, shf, true, c->d_status, cand, sh->d_set_results, sh->d_set_status, s);
         HIPCHK(c, hipGetLastError());
     } else if (loc) {          // the per-set route: the scheme of mbls_verify_multiple_batches_locate* with the call as the one batch that owns every set
@@ -3535,6 +3673,7 @@ static int vm_rng_phase1(mbls_ctx* c, vm_rng_stage& g, const uint8_t* sigs96, co
     int rc = sh ? vm_shared_plan_and_reserve(c, *sh, n) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     rc = ws_acquire(c, s); if (rc) return rc;
+    if (sh && sh->mt) { rc = msgtable_acquire(c, sh->mt, s); if (rc) return rc; }      // (before the fork: the message stream inherits the table's last append)
     hipStream_t s_sig = fork ? c->hs_b : s;
     if (hipMemsetAsync(c->d_status, 0, 4 * n, s) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
     if (fork) { (void)hipEventRecord(c->hs_ev, s); (void)hipStreamWaitEvent(c->hs_b, c->hs_ev, 0); (void)hipStreamWaitEvent(c->hs_c, c->hs_ev, 0); }
@@ -3585,15 +3724,17 @@ extern "C" int mbls_verify_multiple_aggregate_signatures_rng(mbls_ctx* c, const 
 static int vm_shared_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint8_t* d_apks, const uint32_t* d_key_idx, const uint32_t* d_offsets, uint32_t k,
                             const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n,
                             uint8_t* d_result, uint32_t* d_status_or, void* stream, uint64_t longest, bool locate = false, uint8_t* d_set_results = nullptr,
-                            uint32_t* d_set_status = nullptr) {
+                            uint32_t* d_set_status = nullptr, const mbls_msgtable* mt = nullptr) {
+    // mt (the _msgtable entries): d_midx holds indices into the resident table; d_msgs / msg_len / d_moff / n_msgs are not used (NULL / 0)
     if (!c || !d_result) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
+    if (mt && mt->c != c) ARGFAIL(c, "message table belongs to another context");
     if (locate && !d_set_results) ARGFAIL(c, "null set results");
     if (n && !(t ? (const void*)d_key_idx : (const void*)d_apks)) ARGFAIL(c, "null key buffer");
     if (t && t->c != c) ARGFAIL(c, "key table belongs to another context");
     if (n && !d_midx) ARGFAIL(c, "null buffer");
     if (n_msgs > 0xFFFFFFFFull || n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
-    vm_shared sh; sh.n_msgs = n_msgs; sh.d_midx = d_midx; sh.longest = longest;
+    vm_shared sh; sh.n_msgs = n_msgs; sh.d_midx = d_midx; sh.longest = longest; sh.mt = mt;
     sh.locate = locate; sh.d_set_results = d_set_results; sh.d_set_status = d_set_status;
     return verify_multiple_impl(c, d_sigs, t ? nullptr : d_apks, nullptr, MBLS_PK_UNCOMPRESSED, t ? d_offsets : nullptr, t ? k : 0, d_msgs, msg_len, d_moff, d_rands, n, d_result,
                                 d_status_or, stream, nullptr, t, t ? d_key_idx : nullptr, false, false, &sh);
@@ -3624,6 +3765,26 @@ static int vm_shared_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_
         if (++cnt[msg_idx[i]] > m) m = cnt[msg_idx[i]];
     }
     *longest = m;
+    return MBLS_OK;
+}
+// the same for the host entries over a resident table (the caller holds the context's lock: the table's size is the one the call is planned with): every index
+// names an entry of the table. -> the longest group and the number of distinct entries named, counted on a sorted copy of the indices (the table may be far
+// larger than the call)
+static int vm_msgtable_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint64_t* longest,
+                                  uint64_t* named) {
+    if (n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
+    if (!sigs96 || !apks96 || !msg_idx) ARGFAIL(c, "null buffer");
+    for (uint64_t i = 0; i < n; i++)
+        if (mtb_names_nothing(msg_idx[i], mt->size)) ARGFAIL(c, "msg_idx names no entry of the message table");
+    std::vector<uint32_t> idx;
+    try { idx.assign(msg_idx, msg_idx + n); } catch (...) { ARGFAIL(c, "out of host memory"); }
+    std::sort(idx.begin(), idx.end());
+    uint64_t m = 0, d = 0, run = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (i == 0 || idx[i] != idx[i - 1]) { d++; run = 0; }
+        if (++run > m) m = run;
+    }
+    *longest = m; *named = d;
     return MBLS_OK;
 }
 // locate: the sets' answers as well (set_results required, set_status optional), staged behind one another in one buffer: n words, then n bytes
@@ -3671,14 +3832,18 @@ extern "C" int mbls_verify_multiple_shared_msgs(mbls_ctx* c, const uint8_t* sigs
 // are judged one by one: the call goes on (it is rejected through its status bits whatever the product is) with the scalar 1 for the sets without one, which
 // changes nothing -- as mbls_verify_multiple_batches_locate_rng does.
 static int vm_shared_rng_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
-        uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user, bool locate, uint8_t* set_results, uint32_t* set_status) {
+        uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user, bool locate, uint8_t* set_results, uint32_t* set_status,
+        const mbls_msgtable* mt = nullptr) {
+    // mt (the _msgtable entries): msg_idx holds indices into the resident table, no list (msgs / moff NULL, msg_len = n_msgs = 0); the host counts the named entries
     if (!c || !result) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
     if (locate && !set_results) ARGFAIL(c, "null set results");
+    if (mt && mt->c != c) ARGFAIL(c, "message table belongs to another context");
     if (n == 0) { *result = 1; return MBLS_OK; }                            // empty iterator: true, the generator untouched
     if (!draw) ARGFAIL(c, "no scalar source");
-    vm_shared sh; sh.n_msgs = n_msgs;
-    int rc = vm_shared_host_check(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, n, &sh.longest); if (rc) return rc;
+    vm_shared sh; sh.n_msgs = n_msgs; sh.mt = mt;
+    int rc = mt ? vm_msgtable_host_check(c, sigs96, apks96, mt, msg_idx, n, &sh.longest, &sh.named)
+                : vm_shared_host_check(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, n, &sh.longest); if (rc) return rc;
     std::vector<uint64_t> rands; std::vector<uint32_t> st;
     try { rands.resize(n); st.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
     vm_rng_stage g(c);
@@ -3744,6 +3909,43 @@ extern "C" uint64_t mbls_plan_verify_multiple_shared_msgs_locate_workspace_items
     if (!limits || !n || mode < 0 || mode > 2) return 0;
     mbls_vm_shared_msgs_plan vp; plan_vm_shared(*limits, n, n_msgs, mode, 0, &vp);
     return vsl_workspace_items(n, n_msgs, vp.route == MBLS_VM_ROUTE_GROUPED, vp.list_workspace_items);
+}
+
+// ---- verify_multiple over the resident message table (include/mbls.h, mbls_verify_multiple*_msgtable*): the shared-message entries with a vm_shared that names a
+// table in place of a list -- verify_multiple_impl's grouped route over the table's T entries, the named entries compacted on the device (mbls_vmt.h; k_vmt_flag,
+// k_vmt_named, k_vmt_heads), or the per-set route with one gather from the table. Nothing is hashed.
+extern "C" int mbls_verify_multiple_msgtable_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
+        const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream) {
+    if (!mt) return MBLS_ERR_ARGUMENT;
+    return vm_shared_device(c, nullptr, d_sigs, d_apks, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, false, nullptr, nullptr, mt);
+}
+extern "C" int mbls_verify_multiple_sets_indexed_msgtable_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx, const uint32_t* d_offsets,
+        uint32_t k, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream) {
+    if (!t || !mt) return MBLS_ERR_ARGUMENT;
+    return vm_shared_device(c, t, d_sigs, nullptr, d_key_idx, d_offsets, k, nullptr, 0, nullptr, 0, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, false, nullptr, nullptr, mt);
+}
+extern "C" int mbls_verify_multiple_msgtable_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n,
+        uint8_t* result, mbls_scalar_source draw, void* user) {
+    if (!mt) return MBLS_ERR_ARGUMENT;
+    return vm_shared_rng_impl(c, sigs96, apks96, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, false, nullptr, nullptr, mt);
+}
+extern "C" int mbls_verify_multiple_msgtable_locate_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
+        const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
+    if (!mt || !d_set_results) return MBLS_ERR_ARGUMENT;
+    return vm_shared_device(c, nullptr, d_sigs, d_apks, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, true, d_set_results,
+                            d_set_status, mt);
+}
+extern "C" int mbls_verify_multiple_sets_indexed_msgtable_locate_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx,
+        const uint32_t* d_offsets, uint32_t k, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status,
+        uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
+    if (!t || !mt || !d_set_results) return MBLS_ERR_ARGUMENT;
+    return vm_shared_device(c, t, d_sigs, nullptr, d_key_idx, d_offsets, k, nullptr, 0, nullptr, 0, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, true, d_set_results,
+                            d_set_status, mt);
+}
+extern "C" int mbls_verify_multiple_msgtable_locate_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n,
+        uint8_t* result, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user) {
+    if (!mt) return MBLS_ERR_ARGUMENT;
+    return vm_shared_rng_impl(c, sigs96, apks96, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, true, set_results, set_status, mt);
 }
 
 // ---- B independent verify_multiple batches in ONE call (include/mbls.h, mbls_verify_multiple_batches*): what B consecutive calls of the entries above return,

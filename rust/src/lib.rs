@@ -176,6 +176,21 @@ extern "C" {
                                   results: *mut u8, status: *mut u32) -> c_int;
     fn mbls_fast_aggregate_verify_batch_indexed_msgtable(ctx: *mut MblsCtx, t: *const MblsKeyTable, sigs: *const u8, mt: *const mbls_msgtable, msg_idx: *const u32,
                                                          key_idx: *const u32, offsets: *const u32, n: u64, k: u32, results: *mut u8, status: *mut u32) -> c_int;
+    fn mbls_verify_multiple_msgtable_device(ctx: *mut MblsCtx, d_sigs96: *const u8, d_apks96: *const u8, mt: *const mbls_msgtable, d_msg_idx: *const u32, d_rands: *const u64,
+                                            n: u64, d_result: *mut u8, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_sets_indexed_msgtable_device(ctx: *mut MblsCtx, t: *const MblsKeyTable, d_sigs96: *const u8, d_key_idx: *const u32, d_offsets: *const u32, k: u32,
+                                                         mt: *const mbls_msgtable, d_msg_idx: *const u32, d_rands: *const u64, n: u64, d_result: *mut u8, d_status: *mut u32,
+                                                         stream: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_msgtable_rng(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, mt: *const mbls_msgtable, msg_idx: *const u32, n: u64, result: *mut u8,
+                                         draw: MblsScalarSource, user: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_msgtable_locate_device(ctx: *mut MblsCtx, d_sigs96: *const u8, d_apks96: *const u8, mt: *const mbls_msgtable, d_msg_idx: *const u32,
+                                                   d_rands: *const u64, n: u64, d_result: *mut u8, d_status: *mut u32, d_set_results: *mut u8, d_set_status: *mut u32,
+                                                   stream: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_sets_indexed_msgtable_locate_device(ctx: *mut MblsCtx, t: *const MblsKeyTable, d_sigs96: *const u8, d_key_idx: *const u32, d_offsets: *const u32,
+                                                                k: u32, mt: *const mbls_msgtable, d_msg_idx: *const u32, d_rands: *const u64, n: u64, d_result: *mut u8,
+                                                                d_status: *mut u32, d_set_results: *mut u8, d_set_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_msgtable_locate_rng(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, mt: *const mbls_msgtable, msg_idx: *const u32, n: u64,
+                                                result: *mut u8, set_results: *mut u8, set_status: *mut u32, draw: MblsScalarSource, user: *mut c_void) -> c_int;
     fn mbls_stream_create_msgtable(ctx: *mut MblsCtx, mode: c_int, pk_format: c_int, t: *const MblsKeyTable, mt: *mut mbls_msgtable, opts: *const mbls_stream_opts,
                                    out: *mut *mut mbls_stream) -> c_int;
     fn mbls_stream_submit_msgidx(s: *mut mbls_stream, sigs: *const u8, msg_idx: *const u32, pks: *const u8, key_idx: *const u32, pk_offsets: *const u32, n: u64, k: u32,
@@ -1263,6 +1278,58 @@ impl MessageTable {
         }
         res.truncate(n);
         res.into_iter().map(|b| b == 1).collect()
+    }
+    /// `AggregateSignature::verify_multiple_aggregate_signatures` over sets (signature, aggregate key, entry index) whose messages are entries of this table
+    /// (`mbls_verify_multiple_msgtable_rng`): the same bool as that function on the spelled-out messages, `rng` left in the same state, nothing hashed.
+    pub fn verify_multiple_aggregate_signatures<'a, R, I>(&self, rng: &mut R, signature_sets: I) -> bool
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, &'a AggregatePublicKey, u32)>,
+    {
+        self.vm_msgtable(rng, signature_sets, false).0
+    }
+    /// The same, and in the same call (`mbls_verify_multiple_msgtable_locate_rng`) which sets of a rejected call are the bad ones, with the semantics of
+    /// `AggregateSignature::verify_multiple_aggregate_signatures_shared_msgs_locate`.
+    pub fn verify_multiple_aggregate_signatures_locate<'a, R, I>(&self, rng: &mut R, signature_sets: I) -> (bool, Vec<bool>)
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, &'a AggregatePublicKey, u32)>,
+    {
+        self.vm_msgtable(rng, signature_sets, true)
+    }
+    fn vm_msgtable<'a, R, I>(&self, rng: &mut R, signature_sets: I, locate: bool) -> (bool, Vec<bool>)
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, &'a AggregatePublicKey, u32)>,
+    {
+        let sets: Vec<(&AggregateSignature, &AggregatePublicKey, u32)> = signature_sets.collect();
+        let n = sets.len();
+        if n == 0 {
+            return (true, Vec::new());
+        }
+        let (mut sigs, mut apks) = (Vec::new(), Vec::new());
+        let mut idx: Vec<u32> = Vec::with_capacity(n);
+        for (s, a, j) in &sets {
+            sigs.extend_from_slice(&s.point);
+            apks.extend_from_slice(&a.point);
+            idx.push(*j);
+        }
+        let mut st = DrawState { rng, panic: None };
+        let mut ok: u8 = 0;
+        let mut sres: Vec<u8> = vec![0; if locate { n } else { 0 }];
+        let rc = unsafe {
+            if locate {
+                mbls_verify_multiple_msgtable_locate_rng(ctx(), sigs.as_ptr(), apks.as_ptr(), self.h, idx.as_ptr(), n as u64, &mut ok, sres.as_mut_ptr(), std::ptr::null_mut(),
+                                                         draw_scalars::<R>, &mut st as *mut DrawState<R> as *mut c_void)
+            } else {
+                mbls_verify_multiple_msgtable_rng(ctx(), sigs.as_ptr(), apks.as_ptr(), self.h, idx.as_ptr(), n as u64, &mut ok, draw_scalars::<R>,
+                                                  &mut st as *mut DrawState<R> as *mut c_void)
+            }
+        };
+        if let Some(payload) = st.panic.take() {
+            std::panic::resume_unwind(payload);
+        }
+        (rc == 0 && ok == 1, sres.iter().map(|&b| rc == 0 && b == 1).collect())
     }
 }
 impl Drop for MessageTable {
