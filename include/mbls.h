@@ -311,6 +311,75 @@ int mbls_fast_aggregate_verify_batch_indexed_msgtable_device(mbls_ctx* ctx, cons
 int mbls_fast_aggregate_verify_batch_indexed_msgtable(mbls_ctx* ctx, const mbls_keytable* t, const uint8_t* sigs, const mbls_msgtable* mt, const uint32_t* msg_idx,
                                                       const uint32_t* key_idx, const uint32_t* offsets, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status);
 
+/* ---- committee table: fast_aggregate_verify by participation bits -------------------------------------------
+ * An Ethereum aggregate names a COMMITTEE -- an ordered member list fixed for an epoch -- and a bitfield of who signed, and nearly everyone signs. The _indexed
+ * entries make the caller expand every bitfield into uint32 indices (512 bytes per item of a 128-member committee instead of 16) and add 127 keys where one
+ * subtraction would do. A committee table lives on the key side, bound to ONE key table of the same context: committee `id` is an ordered list of key-table
+ * indices, kept in HBM with its full key sum (what the beacon state stores as the sync committee's aggregate_pubkey) and an ELIGIBLE flag, set only if every
+ * member is a valid, finite table entry. A verification item names a committee and carries a bitfield; on the device each item takes one of two routes:
+ *   direct:      the sum of the members whose bit is set (s additions),
+ *   complement:  the cached full sum minus the sum of the members whose bit is clear ((m - s) additions and one fix-up addition).
+ * Complement is taken only for an eligible committee -- only there are the MBLS_ST_BAD_PK_ENCODING / MBLS_ST_PK_INFINITY bits of every subset known to be zero,
+ * so the status word does not depend on the route -- and, in the automatic mode, when (m - s) + 1 < s: a count of additions, not a measurement.
+ * TABLE. mbls_committees_create binds the table to `keytable` (capacity_hint committees, 0: 64; growth keeps every id and drains the device, like the key
+ *   table's). Destroy a committee table before its key table: mbls_keytable_destroy unbinds the committee tables still bound to it, which then refuse appends
+ *   and verifications with MBLS_ERR_ARGUMENT and accept count, get, clear and destroy. A table whose context went first is an empty shell that only
+ *   mbls_committees_destroy accepts (mbls_committees_count is 0). Ids start at 0 and are stable until mbls_committees_clear.
+ * APPEND (host memory; a device-pointer append is out of scope). Committee first_id + c has members key_idx[offsets[c] .. offsets[c+1]), in that order; bit j of an
+ *   item's bitfield means member j. MBLS_ERR_ARGUMENT, and nothing appended, for: an offset table that runs backwards, an empty committee, a committee of more than
+ *   MBLS_COMMITTEE_MAX_MEMBERS members (the protocol's limit), an index at or above the key table's size at the time of the call. Duplicated members are allowed.
+ *   The member lists are stored on the device, the full sums are computed there by the indexed key-sum routine (in the context's workspace, ordered against its
+ *   other users) and k_cmt_build turns them into records. ORDERING is mbls_keytable_append_device's: the append waits on the device for pending appends to the key
+ *   table, and verifications on any stream wait on the device for the append. n_committees = 0 is MBLS_OK with *first_id = count.
+ * mbls_committees_get returns the cached sum as 96 uncompressed bytes (AggregatePublicKey::aggregate over the members, reference src/aggregates.rs:29-39; the
+ *   point at infinity in the reference's encoding), the member count and the eligible flag. Any of the three outputs may be NULL.
+ * mbls_committees_clear BLOCKS until every append and verification enqueued over the table has finished (it drains the device, like mbls_msgtable_clear), then
+ *   sets the count to 0 and keeps the capacity: the next append starts at id 0. The intended use is one clear per epoch boundary.
+ * VERIFICATION ENTRIES. The arguments of the _indexed / _indexed_msgtable entries with `key_idx, offsets, k` replaced by `committees, cmt_idx, bits, bits_stride`
+ *   (the key table is the one the committee table is bound to): item i uses committee cmt_idx[i] and the bits_stride bytes at bits + bits_stride * i; member j is
+ *   selected when (byte[j >> 3] >> (j & 7)) & 1 -- SSZ bit order, so a Bitvector or a Bitlist is passed as serialized. Bits at positions at or above the
+ *   committee's size are IGNORED: a Bitlist's delimiter bit may stay, and checking the Bitlist's length against the committee remains the caller's job.
+ *   bits_stride is a multiple of 4 and 8 * bits_stride covers the largest committee the table holds; d_bits of the device entries is 4-byte aligned (the host
+ *   entries stage the bytes and accept any alignment). Otherwise MBLS_ERR_ARGUMENT.
+ *   results[i], the bitmap and status[i] are bit for bit what mbls_fast_aggregate_verify_batch_indexed[_msgtable] returns for the same signatures and messages with
+ *   the selected members spelled out in member order through a ragged offset table -- on either route, under every routing mode: no bit set gives MBLS_ST_NO_KEYS,
+ *   a selected sum at infinity MBLS_ST_APK_INFINITY. The table is read at the count it has when the call is enqueued. DEVICE entries reject an item whose
+ *   cmt_idx[i] is at or above that count like an index outside the key table (MBLS_ST_BAD_PK_ENCODING among its bits, result 0: exactly the words of an item that
+ *   lists the one key index 0xFFFFFFFF); HOST entries refuse the call with MBLS_ERR_ARGUMENT before anything is enqueued. n = 0 is MBLS_OK with nothing written.
+ *   Routing of the batch is mbls_plan_batch(limits, n), workspace mbls_plan_workspace_items(limits, n, 0, 0) (the committee form never takes the eight-lane key
+ *   split: it is ragged, and complement lists are short).
+ * ALLOCATION. k_cmt_expand writes every item's index list into a scratch of the context: items x (largest committee) uint32, plus two words per item. A call
+ *   reserves it before it queues the first pass of its plan (growth drains the device, see mbls_ctx_reserve); mbls_ctx_reserve_committee_items(ctx, max_items,
+ *   max_members) beforehand keeps the allocation out of the call.
+ * ROUTE (mbls_ctx_set_committee_route; mbls_ctx_reset_tuning restores 0): 0 auto, 1 always direct, 2 complement whenever the committee is eligible.
+ *   mbls_plan_committee_route(m, s, eligible, mode) states the decision without a GPU -- the SAME function the kernel runs (csrc/mbls_cmt.h): 1 complement,
+ *   0 direct, MBLS_ERR_ARGUMENT for a mode outside 0..2, m = 0, m > MBLS_COMMITTEE_MAX_MEMBERS or s > m.
+ * OUT OF SCOPE: the verification stream, the shared-list message form, verify_multiple over committees, the mbls_multi handle, a device-pointer append. */
+#define MBLS_COMMITTEE_MAX_MEMBERS 2048
+typedef struct mbls_committees mbls_committees;
+int mbls_committees_create(mbls_ctx* ctx, mbls_keytable* keytable, uint64_t capacity_hint, mbls_committees** out);
+void mbls_committees_destroy(mbls_committees* t);
+uint64_t mbls_committees_count(const mbls_committees* t);
+uint32_t mbls_committees_max_members(const mbls_committees* t);     /* the largest committee the table holds (0: none): what 8 * bits_stride has to cover */
+int mbls_committees_clear(mbls_committees* t);
+int mbls_committees_append(mbls_committees* t, const uint32_t* key_idx, const uint32_t* offsets, uint64_t n_committees, uint64_t* first_id);
+int mbls_committees_get(mbls_committees* t, uint64_t id, uint8_t* sum96, uint32_t* n_members, uint32_t* eligible);
+int mbls_ctx_set_committee_route(mbls_ctx* ctx, int mode);
+int mbls_plan_committee_route(uint32_t m, uint32_t s, int eligible, int mode);
+int mbls_ctx_reserve_committee_items(mbls_ctx* ctx, uint64_t max_items, uint32_t max_members);
+int mbls_fast_aggregate_verify_batch_committee_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs, const uint8_t* d_msgs,
+                                                      uint32_t msg_len, const uint64_t* d_msg_offsets, const uint32_t* d_cmt_idx, const uint8_t* d_bits,
+                                                      uint32_t bits_stride, uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream);
+int mbls_fast_aggregate_verify_batch_committee(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
+                                               const uint64_t* msg_offsets, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_stride, uint64_t n,
+                                               uint8_t* results, uint32_t* status);
+int mbls_fast_aggregate_verify_batch_committee_msgtable_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs, const mbls_msgtable* mt,
+                                                               const uint32_t* d_msg_idx, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride,
+                                                               uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream);
+int mbls_fast_aggregate_verify_batch_committee_msgtable(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs, const mbls_msgtable* mt,
+                                                        const uint32_t* msg_idx, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_stride, uint64_t n,
+                                                        uint8_t* results, uint32_t* status);
+
 /* ---- verification stream: many small calls packed into full rounds ---------------------------------------
  * The verification entries run at their full rate only when one call carries a whole round (CUs x 4 x 64 items, 65 536 on MI355X). A
  * stream takes calls of ANY size, hands back a ticket per call, packs the items of many calls back to back into full-round launches of

@@ -619,6 +619,66 @@ inline std::vector<bool> fast_aggregate_verify_batch_indexed_msgtable(const mbls
     return out;
 }
 
+// Committee table (mbls_committees_*): ordered member lists over a resident key table of the library's context, each with its cached key sum; a verification names a
+// committee and carries the participation bits as serialized by SSZ (bit j = member j; bits at or above the committee's size are ignored). Destroy it before the key
+// table it was made over.
+class CommitteeTable {
+    mbls_committees* h_ = nullptr;
+public:
+    explicit CommitteeTable(mbls_keytable* key_table, uint64_t capacity_hint = 0) { detail::check(mbls_committees_create(detail::ctx(), key_table, capacity_hint, &h_)); }
+    CommitteeTable(const CommitteeTable&) = delete; CommitteeTable& operator=(const CommitteeTable&) = delete;
+    ~CommitteeTable() { mbls_committees_destroy(h_); }
+    mbls_committees* handle() const { return h_; }
+    uint64_t count() const { return mbls_committees_count(h_); }
+    uint32_t max_members() const { return mbls_committees_max_members(h_); }
+    // one committee per member list (key-table indices, in member order) -> the id of the first
+    uint64_t append(const std::vector<std::vector<uint32_t>>& committees) {
+        std::vector<uint32_t> flat, off{0};
+        for (const auto& c : committees) {
+            flat.insert(flat.end(), c.begin(), c.end());
+            if (flat.size() > 0xFFFFFFFFull) throw std::invalid_argument("CommitteeTable::append: member offsets are 32-bit");
+            off.push_back(uint32_t(flat.size()));
+        }
+        if (flat.empty()) flat.push_back(0);
+        uint64_t first = 0;
+        detail::check(mbls_committees_append(h_, flat.data(), off.data(), committees.size(), &first));
+        return first;
+    }
+    // the committee's full key sum (AggregatePublicKey::aggregate over its members), as cached on the device
+    AggregatePublicKey aggregate_pubkey(uint64_t id, uint32_t* n_members = nullptr, bool* eligible = nullptr) const {
+        AggregatePublicKey a; uint32_t m = 0, e = 0;
+        detail::check(mbls_committees_get(h_, id, a.point.data(), &m, &e));
+        if (n_members) *n_members = m;
+        if (eligible) *eligible = e != 0;
+        return a;
+    }
+    void clear() { detail::check(mbls_committees_clear(h_)); }
+};
+// n x AggregateSignature::fast_aggregate_verify over a committee table and a resident message table (mbls_fast_aggregate_verify_batch_committee_msgtable): item i =
+// (sigs[i], entry msg_idx[i], the members of committee cmt_idx[i] whose bit is set in bits[i]); the fields are laid out at one stride (16 bytes for 128 members)
+inline std::vector<bool> fast_aggregate_verify_batch_committee_msgtable(const CommitteeTable& committees, const std::vector<AggregateSignature>& sigs, const MessageTable& table,
+                                                                        const std::vector<uint32_t>& msg_idx, const std::vector<uint32_t>& cmt_idx,
+                                                                        const std::vector<Bytes>& bits) {
+    const size_t n = sigs.size();
+    if (msg_idx.size() != n || cmt_idx.size() != n || bits.size() != n)
+        throw std::invalid_argument("fast_aggregate_verify_batch_committee_msgtable: one message index, one committee id and one bitfield per signature");
+    // one stride for every field: the bytes that cover the table's largest committee, rounded up to 4 (bytes of a field beyond that hold only bits at or above
+    // every committee's size, which the entry ignores)
+    const size_t covering = (size_t(committees.max_members()) + 7) / 8;
+    const uint32_t stride = uint32_t(((covering ? covering : 1) + 3) / 4 * 4);
+    Bytes s, flat(size_t(stride) * (n ? n : 1), 0);
+    for (size_t i = 0; i < n; i++) {
+        s.insert(s.end(), sigs[i].point.begin(), sigs[i].point.end());
+        std::copy(bits[i].begin(), bits[i].begin() + std::min(bits[i].size(), size_t(stride)), flat.begin() + size_t(stride) * i);
+    }
+    std::vector<uint8_t> res(n ? n : 1);
+    detail::check(mbls_fast_aggregate_verify_batch_committee_msgtable(detail::ctx(), committees.handle(), s.data(), table.handle(), msg_idx.data(), cmt_idx.data(), flat.data(),
+                                                                      stride, n, res.data(), nullptr));
+    std::vector<bool> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = res[i] == 1;
+    return out;
+}
+
 class MultiGpu {
     mbls_multi* h_ = nullptr;
 public:

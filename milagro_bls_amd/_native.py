@@ -267,6 +267,20 @@ SIGNATURES = {
     "mbls_verify_batch_msgtable": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_uint64, vp, vp]),
     "mbls_fast_aggregate_verify_batch_indexed_msgtable_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp]),
     "mbls_fast_aggregate_verify_batch_indexed_msgtable": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
+    "mbls_committees_create": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(vp)]),
+    "mbls_committees_destroy": (None, [vp]),
+    "mbls_committees_count": (C.c_uint64, [vp]),
+    "mbls_committees_clear": (C.c_int, [vp]),
+    "mbls_committees_max_members": (C.c_uint32, [vp]),
+    "mbls_committees_append": (C.c_int, [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "mbls_committees_get": (C.c_int, [vp, C.c_uint64, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "mbls_ctx_set_committee_route": (C.c_int, [vp, C.c_int]),
+    "mbls_plan_committee_route": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
+    "mbls_ctx_reserve_committee_items": (C.c_int, [vp, C.c_uint64, C.c_uint32]),
+    "mbls_fast_aggregate_verify_batch_committee_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_committee": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_committee_msgtable_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_committee_msgtable": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp]),
     "mbls_aggregate_signatures_batch": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
     "mbls_aggregate_signatures_batch_device": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp, vp]),
     "mbls_pk_from_bytes": (C.c_int, [vp, vp, C.c_size_t, vp]),
@@ -448,6 +462,14 @@ class Context:
         """the table of hashed points for message lists of up to n_msgs messages (the *_shared_msgs entries)"""
         self.check(lib().mbls_ctx_reserve_msgs(self._h, n_msgs))
 
+    def reserve_committee_items(self, max_items, max_members):
+        """the scratch of the committee entries for batches of up to max_items items over committees of up to max_members members"""
+        self.check(lib().mbls_ctx_reserve_committee_items(self._h, max_items, max_members))
+
+    def set_committee_route(self, mode):
+        """committee entries: CMT_ROUTE_AUTO / CMT_ROUTE_DIRECT / CMT_ROUTE_COMPLEMENT"""
+        self.check(lib().mbls_ctx_set_committee_route(self._h, mode))
+
     def set_coop_max_items(self, n):
         """batches up to n items take the one-wave-per-item pairing check (0: never)"""
         self.check(lib().mbls_ctx_set_coop_max_items(self._h, n))
@@ -579,6 +601,72 @@ class MsgTable:
     def clear(self):
         """size back to 0, capacity kept; refused while a stream bound to the table has calls that have not completed"""
         self.ctx.check(lib().mbls_msgtable_clear(self._h))
+
+
+COMMITTEE_MAX_MEMBERS = 2048    # include/mbls.h MBLS_COMMITTEE_MAX_MEMBERS
+CMT_ROUTE_AUTO, CMT_ROUTE_DIRECT, CMT_ROUTE_COMPLEMENT = 0, 1, 2
+
+
+def plan_committee_route(m, s, eligible=True, mode=CMT_ROUTE_AUTO):
+    """the route an item with s of the m members of a committee selected takes under `mode` (pure: no GPU) -> True: complement, False: direct"""
+    rc = lib().mbls_plan_committee_route(m, s, int(bool(eligible)), mode)
+    if rc not in (0, 1):
+        raise MblsError(rc, "mbls_plan_committee_route")
+    return bool(rc)
+
+
+class CommitteeTable:
+    """Resident table of committees over a KeyTable (include/mbls.h, mbls_committees_*): ordered member lists with their cached key sums; verify by
+    committee id and participation bits. Destroy it before its key table."""
+
+    def __init__(self, keytable, capacity_hint=0, ctx=None):
+        self.ctx = ctx or keytable.ctx
+        self.keytable = keytable
+        self._h = vp()
+        self.ctx.check(lib().mbls_committees_create(self.ctx.handle, keytable.handle, capacity_hint, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().mbls_committees_destroy(self._h)
+            self._h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __len__(self):
+        return int(lib().mbls_committees_count(self._h))
+
+    @property
+    def max_members(self):
+        """the size of the largest committee the table holds: 8 * bits_stride must cover it"""
+        return int(lib().mbls_committees_max_members(self._h))
+
+    def append(self, key_idx, offsets):
+        """committees key_idx[offsets[c]:offsets[c+1]], c = 0 .. len(offsets) - 2 -> first_id"""
+        if len(offsets) < 1:
+            raise ValueError("offsets must have one entry more than there are committees (at least one)")
+        first = C.c_uint64(0)
+        idx = (C.c_uint32 * max(1, len(key_idx)))(*key_idx)
+        off = (C.c_uint32 * len(offsets))(*offsets)
+        self.ctx.check(lib().mbls_committees_append(self._h, idx, off, len(offsets) - 1, C.byref(first)))
+        return int(first.value)
+
+    def get(self, cid):
+        """-> (the committee's full key sum as 96 uncompressed bytes, member count, eligible)"""
+        out, m, el = outbuf(96), C.c_uint32(0), C.c_uint32(0)
+        self.ctx.check(lib().mbls_committees_get(self._h, cid, out, C.byref(m), C.byref(el)))
+        return bytes(out)[:96], int(m.value), bool(el.value)
+
+    def clear(self):
+        """count back to 0 (blocks until everything enqueued over the table has finished); the next append starts at id 0"""
+        self.ctx.check(lib().mbls_committees_clear(self._h))
 
 
 class MultiContext:

@@ -119,6 +119,41 @@ def fast_aggregate_verify_batch_indexed_msgtable(table, msg_table, sigs, msg_idx
     return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
 
 
+def _bits(bits, bits_stride, n):
+    bits = bytes(bits)
+    if len(bits) != bits_stride * n:
+        raise ValueError("bits must hold n = %d bitfields of bits_stride = %d bytes, got %d bytes" % (n, bits_stride, len(bits)))
+    return N.cbuf(bits)
+
+
+def fast_aggregate_verify_batch_committee(committees, sigs, msgs, cmt_idx, bits, bits_stride, n, msg_len=32, ctx=None, msg_offsets=None):
+    """fast_aggregate_verify_batch over a committee table (N.CommitteeTable): item i's keys are the members of committee cmt_idx[i] whose bit is set in the
+    bits_stride bytes at bits[bits_stride * i:] (SSZ bit order; bits at or above the committee's size are ignored). Same (results, status) as
+    fast_aggregate_verify_batch_indexed with the selected members spelled out; a committee id that names nothing raises (MBLS_ERR_ARGUMENT)."""
+    ctx = ctx or committees.ctx
+    res = N.outbuf(n)
+    st = (C.c_uint32 * max(1, n))()
+    ctx.check(N.lib().mbls_fast_aggregate_verify_batch_committee(ctx.handle, committees.handle, N.cbuf(sigs), N.cbuf(msgs), msg_len, _moff(msg_offsets),
+                                                                 _midx(cmt_idx, n), _bits(bits, bits_stride, n), bits_stride, n, res, st))
+    return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
+
+
+def fast_aggregate_verify_batch_committee_msgtable(committees, msg_table, sigs, msg_idx, cmt_idx, bits, bits_stride, n, ctx=None):
+    """The same with the messages by message-table index."""
+    ctx = ctx or committees.ctx
+    res = N.outbuf(n)
+    st = (C.c_uint32 * max(1, n))()
+    ctx.check(N.lib().mbls_fast_aggregate_verify_batch_committee_msgtable(ctx.handle, committees.handle, N.cbuf(sigs), msg_table.handle, _midx(msg_idx, n),
+                                                                          _midx(cmt_idx, n), _bits(bits, bits_stride, n), bits_stride, n, res, st))
+    return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
+
+
+def set_committee_route(mode, ctx=None):
+    """committee entries: N.CMT_ROUTE_AUTO (complement when eligible and cheaper), N.CMT_ROUTE_DIRECT, N.CMT_ROUTE_COMPLEMENT (whenever eligible)"""
+    ctx = ctx or _c()
+    ctx.check(N.lib().mbls_ctx_set_committee_route(ctx.handle, mode))
+
+
 def verify_batch_msgtable(msg_table, sigs, msg_idx, pks, n, pk_format=N.PK_COMPRESSED, ctx=None):
     """verify_batch (n x Signature::verify) over a resident message table: item i's message is entry msg_idx[i]."""
     ctx = ctx or msg_table.ctx

@@ -1,5 +1,5 @@
 // mbls_batch.h -- one description of a per-item verification batch on its way from an entry point to a pass (mbls_fast_aggregate_verify_batch*, mbls_verify_batch*
-// and their _indexed forms, with per-item messages, a shared list or a resident table): where the keys come from, where the messages come from, the items and the
+// their _indexed and _committee forms, with per-item messages, a shared list or a resident table): where the keys come from, where the messages come from, the items and the
 // outputs, and `slice`, the ONE place that knows how each pointer advances when a pass starts at item lo. Pure (no HIP call, no context): a header of its own, like
 // mbls_stream.h and mbls_mtb.h, so that a host compiler can build it for the CPU tests (tests/batch_emul/mbls_batch_harness.cpp).
 #ifndef MBLS_BATCH_H
@@ -12,6 +12,9 @@ struct keysrc {
     const uint8_t* d_pks = nullptr; int fmt = MBLS_PK_UNCOMPRESSED; const uint32_t* d_off = nullptr;      // wire bytes
     const uint32_t* d_recs = nullptr; uint64_t tsize = 0; const uint32_t* d_idx = nullptr; bool indexed = false;   // key table
     const mbls_keytable* tab = nullptr;
+    // committee table (mbls_cmt.h): keys of the table above (indexed, d_idx null), named per item by a committee and a bitfield
+    bool committee = false; const uint32_t* d_crecs = nullptr; uint64_t ccount = 0; const uint32_t* d_members = nullptr; uint32_t cmax = 0;
+    const uint32_t* d_cmt_idx = nullptr; const uint8_t* d_bits = nullptr; uint32_t bits_stride = 0; const mbls_committees* cmt = nullptr;
 };
 // wire keys: k per item back to back, or -- d_off -- keys [d_off[i], d_off[i + 1]) of d_pks
 static inline keysrc keys_wire(const uint8_t* d_pks, int fmt, const uint32_t* d_off) {
@@ -20,6 +23,13 @@ static inline keysrc keys_wire(const uint8_t* d_pks, int fmt, const uint32_t* d_
 // indices into the records of a key table (of `size` keys when the call was enqueued); `tab` is the handle readers order themselves against
 static inline keysrc keys_table(const uint32_t* d_recs, uint64_t size, const uint32_t* d_idx, const uint32_t* d_off, const mbls_keytable* tab) {
     keysrc ks; ks.indexed = true; ks.d_recs = d_recs; ks.tsize = size; ks.d_idx = d_idx; ks.d_off = d_off; ks.tab = tab; return ks;
+}
+// a committee per item and a bitfield of bits_stride bytes per item over the committee records d_crecs (ccount of them when the call was enqueued, the largest of
+// cmax members, their member lists in d_members); the keys are those of `keys` (keys_table with d_idx and d_off null)
+static inline keysrc keys_committee(keysrc keys, const uint32_t* d_crecs, uint64_t ccount, const uint32_t* d_members, uint32_t cmax, const uint32_t* d_cmt_idx,
+                                    const uint8_t* d_bits, uint32_t bits_stride, const mbls_committees* cmt) {
+    keysrc ks = keys; ks.committee = true; ks.d_crecs = d_crecs; ks.ccount = ccount; ks.d_members = d_members; ks.cmax = cmax; ks.d_cmt_idx = d_cmt_idx; ks.d_bits = d_bits;
+    ks.bits_stride = bits_stride; ks.cmt = cmt; return ks;
 }
 
 // where an item's message comes from: its own bytes, or index i of d_idx names one of n_msgs hashed points in a table -- the context's per-call table, which holds
@@ -60,7 +70,10 @@ static inline batch slice(const batch& b, uint64_t lo, uint64_t hi) {
     if (b.d_results) t.d_results = b.d_results + lo;
     if (b.d_bitmap) t.d_bitmap = b.d_bitmap + lo / 64;
     if (b.d_status) t.d_status = b.d_status + lo;
-    if (b.ks.d_off) t.ks.d_off = b.ks.d_off + lo;
+    if (b.ks.committee) {        // one committee id and one bitfield per item
+        if (b.ks.d_cmt_idx) t.ks.d_cmt_idx = b.ks.d_cmt_idx + lo;
+        if (b.ks.d_bits) t.ks.d_bits = b.ks.d_bits + (uint64_t)b.ks.bits_stride * lo;
+    } else if (b.ks.d_off) t.ks.d_off = b.ks.d_off + lo;
     else {
         const uint64_t unit = b.ks.fmt == MBLS_PK_COMPRESSED ? 48 : 96;
         if (b.ks.d_pks) t.ks.d_pks = b.ks.d_pks + unit * (uint64_t)b.k * lo;

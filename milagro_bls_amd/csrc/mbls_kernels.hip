@@ -28,6 +28,7 @@
 #include "mbls_vmt.h"
 #include "mbls_mtb.h"
 #include "mbls_batch.h"
+#include "mbls_cmt_lanes.h"
 #include "../../include/mbls.h"
 
 // The product library exists only with the generated routines: the host side below selects kernels (the fused subgroup verdict of
@@ -120,6 +121,27 @@ __global__ void MBLS_LB k_apk_combine(mbls_ws ws, uint64_t n, int mode, const ui
     ws_st(ws, MBLS_SLOT_APK, i, acc.x); ws_st(ws, MBLS_SLOT_APK + 1, i, acc.y); ws_st(ws, MBLS_SLOT_APK + 2, i, acc.z);
     if (st) atomicOr(status + i, st);
 }
+// Committee table (include/mbls.h "committee table", mbls_cmt.h, mbls_cmt_lanes.h). k_cmt_expand: one wave per item turns (committee, bitfield) into the item's
+// index list -- the selected members, or on the complement route the missing ones --, 64 members per step; k_aggregate_cmt_d is k_aggregate_indexed_d over those
+// lists with the complement's fix-up addition and the status word formed from the final point; k_cmt_build makes the records of an append from the sums
+// k_aggregate_indexed_d left in the workspace.
+__global__ void __launch_bounds__(WG) k_cmt_expand(const uint32_t* crecs, uint64_t ccount, const uint32_t* members, const uint32_t* cmt_idx, const uint8_t* bits,
+                                                   uint32_t bits_stride, int mode, uint32_t* list, uint64_t list_stride, uint32_t* cnt, uint32_t* route, uint64_t n) {
+    const uint64_t i = blockIdx.x; if (i >= n) return;
+    wave_cmt_expand(i, threadIdx.x, crecs, ccount, members, cmt_idx, bits, bits_stride, mode, list, list_stride, cnt, route);
+}
+__global__ void MBLS_LB k_aggregate_cmt_d(mbls_ws ws, const uint32_t* recs, uint64_t tsize, const uint32_t* list, uint64_t list_stride, const uint32_t* cnt,
+                                          const uint32_t* route, const uint32_t* crecs, const uint32_t* cmt_idx, uint32_t* status, uint64_t n) {
+    uint64_t i = gid(); if (i >= n) return;
+#if MBLS_DEVICE_ASM
+    uint32_t st = lane_aggregate_cmt(ws, i, threadIdx.x, recs, tsize, list, list_stride, cnt, route, crecs, cmt_idx);
+    if (st) atomicOr(status + i, st);
+#endif
+}
+__global__ void MBLS_LB k_cmt_build(mbls_ws ws, const uint32_t* st, const uint32_t* offsets, uint64_t member_base, uint32_t* crecs, uint64_t n) {
+    uint64_t c = gid(); if (c < n) lane_cmt_build(ws, c, st, offsets, member_base, crecs);
+}
+__global__ void MBLS_LB k_cmt_export(const uint32_t* rec, uint8_t* out96) { if (gid() == 0) lane_cmt_export(rec, out96); }
 __global__ void __launch_bounds__(WG, 2) k_pk_decompress(const uint8_t* pks48, uint64_t nkeys, uint32_t* keys_xy, uint8_t* flags) {
     uint64_t j = gid(); if (j >= nkeys) return;
     lane_pk_decompress(j, pks48, keys_xy, flags);
@@ -1245,6 +1267,11 @@ struct mbls_ctx {
     float phase_ms[MBLS_N_PHASES] = {};
     std::vector<struct mbls_keytable*> tables;     // the key tables created on this context (orphaned when it is destroyed)
     std::vector<struct mbls_msgtable*> msgtables;  // the message tables, likewise
+    std::vector<struct mbls_committees*> committees;   // the committee tables, likewise
+    // committee entries (mbls_cmt.h): the items' index lists k_cmt_expand writes for k_aggregate_cmt_d -- cmt_words uint32 in all, an item's list at a stride of the
+    // table's largest committee -- and the count and route words of cmt_items items (d_cmt_cnt: [2][cmt_items]); mbls_ctx_reserve_committee_items
+    uint32_t* d_cmt_list = nullptr; uint64_t cmt_words = 0; uint32_t* d_cmt_cnt = nullptr; uint64_t cmt_items = 0;
+    int cmt_route_mode = 0;            // mbls_ctx_set_committee_route: 0 auto (cmt_route), 1 always direct, 2 complement whenever eligible
     coop_prog coop[10] = {};           // the cooperative engine's microprograms in HBM (mbls_coop.h): pairing2, vmtail, f12mul, g2add, smiller, vmfinal, hashg2, miller1,
                                        // pairing2x2 (two items per wave), hashg2x4 (four)
     uint32_t* d_coop = nullptr;
@@ -1279,6 +1306,15 @@ struct mbls_msgtable {
     uint64_t size = 0, cap = 0;
     hipEvent_t ev = nullptr; hipStream_t ev_stream = nullptr; bool pending = false;   // the last asynchronous append
     std::atomic<long long> stream_calls{0};        // calls of streams bound to the table that have not completed (mbls_msgtable_clear refuses while there are any)
+};
+// committee table (mbls_cmt.h): the member lists back to back (key-table indices) and one record per committee
+struct mbls_committees {
+    mbls_ctx* c = nullptr;             // nullptr: the context was destroyed first
+    mbls_keytable* kt = nullptr;       // the key table the members index
+    uint32_t* d_members = nullptr; uint64_t n_members = 0, members_cap = 0;
+    uint32_t* d_recs = nullptr; uint64_t count = 0, cap = 0;      // [cap][MBLS_CMT_REC_DWORDS]
+    uint32_t max_members = 0;          // the largest committee the table holds
+    hipEvent_t ev = nullptr; hipStream_t ev_stream = nullptr; bool pending = false;   // the last asynchronous append
 };
 typedef std::lock_guard<std::recursive_mutex> mbls_lock;
 
@@ -1356,6 +1392,8 @@ static void ctx_free(mbls_ctx* c) {
     if (c->d_hst) (void)hipFree(c->d_hst);
     if (c->d_hgrp) (void)hipFree(c->d_hgrp);
     if (c->d_vmap) (void)hipFree(c->d_vmap);
+    if (c->d_cmt_list) (void)hipFree(c->d_cmt_list);
+    if (c->d_cmt_cnt) (void)hipFree(c->d_cmt_cnt);
     if (c->d_coop) (void)hipFree(c->d_coop);
     for (int i = 0; i < MBLS_N_STAGE; i++) if (c->stage[i].p) (void)hipFree(c->stage[i].p);
     for (int i = 0; i <= MBLS_N_PHASES; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1447,7 +1485,7 @@ extern "C" int mbls_ctx_set_coop_packing(mbls_ctx* c, uint64_t pairing_min_items
 }
 // every routing parameter back to its default (what mbls_ctx_create sets, environment included)
 static void ctx_default_tuning(mbls_ctx* c) {
-    c->vm_grouping = 0;
+    c->vm_grouping = 0; c->cmt_route_mode = 0;
     c->coop_max_items = MBLS_DEFAULT_COOP_MAX_ITEMS; c->coop_hash_max_items = MBLS_DEFAULT_COOP_HASH_MAX_ITEMS;
     c->coop_pack_min_items = 1024; c->coop_pack_max_items = 2048; c->coop_hash_pack_min_items = 768;
     hipDeviceProp_t prop;
@@ -1475,6 +1513,16 @@ extern "C" int mbls_ctx_set_vm_grouping(mbls_ctx* c, int mode) {
     if (!c || mode < 0 || mode > 2) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
     c->vm_grouping = mode; return MBLS_OK;
+}
+// committee entries: 0 auto (complement when eligible and (m - s) + 1 < s, mbls_cmt.h cmt_route), 1 always direct, 2 complement whenever eligible
+extern "C" int mbls_ctx_set_committee_route(mbls_ctx* c, int mode) {
+    if (!c || mode < 0 || mode > 2) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    c->cmt_route_mode = mode; return MBLS_OK;
+}
+extern "C" int mbls_plan_committee_route(uint32_t m, uint32_t s, int eligible, int mode) {
+    if (mode < 0 || mode > 2 || m == 0 || m > MBLS_CMT_MAX_MEMBERS || s > m) return MBLS_ERR_ARGUMENT;
+    return cmt_route(m, s, eligible != 0, mode);
 }
 // items per round of the one-lane kernels (default: CUs x 4 SIMDs x 64 lanes); batches above it have their remainder routed as a batch of its own
 extern "C" int mbls_ctx_set_round_items(mbls_ctx* c, uint64_t items) {
@@ -1514,6 +1562,13 @@ extern "C" void mbls_ctx_destroy(mbls_ctx* c) {
             t->d_tab = t->d_flag = t->d_st = nullptr; t->ev = nullptr; t->size = t->cap = 0; t->c = nullptr;
         }
         c->msgtables.clear();
+        for (mbls_committees* t : c->committees) {
+            if (t->d_members) (void)hipFree(t->d_members);
+            if (t->d_recs) (void)hipFree(t->d_recs);
+            if (t->ev) (void)hipEventDestroy(t->ev);
+            t->d_members = t->d_recs = nullptr; t->ev = nullptr; t->count = t->cap = t->n_members = t->members_cap = 0; t->max_members = 0; t->kt = nullptr; t->c = nullptr;
+        }
+        c->committees.clear();
     }
     ctx_free(c);
 }
@@ -1620,11 +1675,40 @@ static int msgtable_acquire(mbls_ctx* c, const mbls_msgtable* t, hipStream_t s) 
     if (t->pending && t->ev_stream != s) HIPCHK(c, hipStreamWaitEvent(s, t->ev, 0));
     return MBLS_OK;
 }
+static int committees_acquire(mbls_ctx* c, const mbls_committees* t, hipStream_t s) {
+    if (t && t->pending && t->ev_stream != s) HIPCHK(c, hipStreamWaitEvent(s, t->ev, 0));
+    return MBLS_OK;
+}
+// the scratch of the committee entries for `items` items of up to `members` members each (grow-only; growth frees and allocates, which drains the device)
+static int reserve_committee(mbls_ctx* c, uint64_t items, uint64_t members) {
+    if (!members) members = 1;
+    const uint64_t want_items = ((items + WG - 1) / WG) * WG, want_words = want_items * members;
+    if (want_items > c->cmt_items) {
+        if (c->d_cmt_cnt) { (void)hipFree(c->d_cmt_cnt); c->d_cmt_cnt = nullptr; c->cmt_items = 0; }
+        HIPCHK(c, hipMalloc(&c->d_cmt_cnt, want_items * 2 * 4));
+        c->cmt_items = want_items;
+    }
+    if (want_words > c->cmt_words) {
+        if (c->d_cmt_list) { (void)hipFree(c->d_cmt_list); c->d_cmt_list = nullptr; c->cmt_words = 0; }
+        HIPCHK(c, hipMalloc(&c->d_cmt_list, want_words * 4));
+        c->cmt_words = want_words;
+    }
+    return MBLS_OK;
+}
+extern "C" int mbls_ctx_reserve_committee_items(mbls_ctx* c, uint64_t max_items, uint32_t max_members) {
+    if (!c || max_members > MBLS_CMT_MAX_MEMBERS) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return reserve_committee(c, max_items, max_members);
+}
 // the key source of an _indexed entry: the table at the size it has now (the caller holds the context's lock)
 static int keys_of_table(mbls_ctx* c, const mbls_keytable* t, const uint32_t* d_idx, const uint32_t* d_off, keysrc* ks) {
     if (t->c != c) ARGFAIL(c, "key table belongs to another context");
     *ks = keys_table(t->d_recs, t->size, d_idx, d_off, t); return MBLS_OK;
 }
+// the key source of a _committee entry (defined with the committee table below), and what a host entry hands verify_host beside it: ids and bitfields in host memory
+static int keys_of_committees(mbls_ctx* c, const mbls_committees* t, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride, bool device_bits, keysrc* ks);
+struct host_committees { const mbls_committees* t; const uint32_t* cmt_idx; const uint8_t* bits; uint32_t bits_stride; };
 // The message source of a _msgtable entry. The entry hands over the indices alone (msgs_in_table): what the table holds lives in its handle until verify_device /
 // verify_host, under the context's lock and once they know the table is this context's, read it at the size it has then (msgs_of_table).
 static msgsrc msgs_in_table(const uint32_t* d_idx) { return msgs_table(nullptr, 0, nullptr, 0, d_idx); }
@@ -1840,7 +1924,7 @@ struct track {
 static bool pass_key_split(const mbls_pass_plan& pp, const keysrc& ks, uint32_t k) {
     const bool on_waves = pp.pairing == MBLS_PAIRING_WAVE || pp.pairing == MBLS_PAIRING_WAVE_X2;
     const bool staged = !ks.indexed && ks.fmt == MBLS_PK_COMPRESSED && !ks.d_off && k > 1;
-    return on_waves && !staged && !ks.d_off && k >= 4 * MBLS_KEY_SPLIT && k % MBLS_KEY_SPLIT == 0 &&
+    return on_waves && !staged && !ks.committee && !ks.d_off && k >= 4 * MBLS_KEY_SPLIT && k % MBLS_KEY_SPLIT == 0 &&
            (ks.indexed || (ks.fmt == MBLS_PK_UNCOMPRESSED && (((uintptr_t)ks.d_pks) & 3u) == 0));
 }
 static uint64_t pass_ws_items(const mbls_pass_plan& pp, const keysrc& ks, uint32_t k, uint64_t n) {
@@ -1884,7 +1968,7 @@ static int verify_pipeline_one(mbls_ctx* c, const batch& b, hipStream_t s, int p
     const int fmt = ks.fmt; const uint32_t* d_off = ks.d_off;
     if (!c || (fmt != MBLS_PK_COMPRESSED && fmt != MBLS_PK_UNCOMPRESSED)) return MBLS_ERR_ARGUMENT;
     if (n == 0) return MBLS_OK;
-    const bool have_keys = ks.indexed ? (ks.d_idx != nullptr) : (ks.d_pks != nullptr);
+    const bool have_keys = ks.committee ? (ks.d_cmt_idx != nullptr && ks.d_bits != nullptr) : ks.indexed ? (ks.d_idx != nullptr) : (ks.d_pks != nullptr);
     if (!d_sigs || (!ms.indexed() && !ms.d_msgs && ms.msg_len && !ms.d_moff) || (ms.indexed() && !ms.d_idx) || !d_results || (!have_keys && (k || d_off) && part != 1))
         ARGFAIL(c, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
@@ -1954,7 +2038,17 @@ static int verify_pipeline_one(mbls_ctx* c, const batch& b, hipStream_t s, int p
     }
     if (tm) HIPCHK(c, hipEventRecord(c->ev[0], s));
     if (ks.indexed) { rc = table_acquire(c, ks.tab, s); if (rc) return rc; }
-    if (key_split) {
+    if (ks.committee) {
+        // the items' lists in the scratch reserved for the whole plan (reserve_committee: nothing grows under a pass in flight), at the pass's workspace offset
+        const uint64_t ls = ks.cmax ? ks.cmax : 1;
+        if ((tk.ws_off + n) * ls > c->cmt_words || tk.ws_off + n > c->cmt_items) ARGFAIL(c, "internal: the committee scratch of a pass was not reserved");
+        rc = committees_acquire(c, ks.cmt, s); if (rc) return rc;
+        uint32_t* const list = c->d_cmt_list + tk.ws_off * ls; uint32_t* const cnt = c->d_cmt_cnt + tk.ws_off; uint32_t* const route = c->d_cmt_cnt + c->cmt_items + tk.ws_off;
+        hipLaunchKernelGGL(k_cmt_expand, dim3((unsigned)n), dim3(WG), 0, s, ks.d_crecs, ks.ccount, ks.d_members, ks.d_cmt_idx, ks.d_bits, ks.bits_stride, c->cmt_route_mode,
+                           list, ls, cnt, route, n);
+        hipLaunchKernelGGL(k_aggregate_cmt_d, dim3(g), dim3(WG), 0, s, ws, ks.d_recs, ks.tsize, (const uint32_t*)list, ls, (const uint32_t*)cnt, (const uint32_t*)route,
+                           ks.d_crecs, ks.d_cmt_idx, st, n);
+    } else if (key_split) {
         mbls_ws wsub = ws; wsub.w += n;                                  // sub-item t = workspace item n + t (APK slots only; nothing else uses them up there)
         uint32_t* st_sub = c->d_status + tk.ws_off + n;                  // their status words: behind the items' own
         HIPCHK(c, hipMemsetAsync(st_sub, 0, 4 * nsub, s));
@@ -2068,6 +2162,13 @@ extern "C" int mbls_ctx_set_tracks(mbls_ctx* c, uint64_t min_rest_items, uint64_
 static int verify_device(mbls_ctx* c, batch b, const mbls_msgtable* mt, hipStream_t s) {
     msgsrc& ms = b.ms;
     if (b.ks.fmt != MBLS_PK_COMPRESSED && b.ks.fmt != MBLS_PK_UNCOMPRESSED) return MBLS_ERR_ARGUMENT;
+    if (b.ks.committee && b.n) {          // the scratch of k_cmt_expand for the whole plan (the extent of its passes), before anything is queued
+        HIPCHK(c, hipSetDevice(c->device));
+        mbls_batch_plan bp; plan_batch(ctx_limits(c), b.n, c->timing, c->timing, &bp);
+        uint64_t extent = 0;
+        for (uint32_t i = 0; i < bp.n_passes; i++) { const uint64_t e = bp.pass[i].workspace_first + bp.pass[i].items; if (e > extent) extent = e; }
+        const int rr = reserve_committee(c, extent, b.ks.cmax); if (rr) return rr;
+    }
     if (mt) {
         if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
         ms = msgs_of_table(mt, ms.d_idx);
@@ -2124,7 +2225,8 @@ static bool msg_offsets_ok(const uint64_t* off, uint64_t n) {
 // enqueued), everything is staged through the context's buffers, and the pipeline runs on the context's stream. With per-item messages the keys (or key indices)
 // are 99 % of the bytes: they are uploaded on a second stream while the signature and message phases run.
 static int verify_host(mbls_ctx* c, const uint8_t* sigs, msgsrc hm, const mbls_msgtable* mt, const uint8_t* pks, int fmt, const mbls_keytable* tab,
-                       const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, int mode, uint8_t* results, uint32_t* status) {
+                       const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, int mode, uint8_t* results, uint32_t* status,
+                       const host_committees* hc = nullptr) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
     if (mt) {            // the table's size and buffers are read under the lock: an append or a clear on another thread comes before or after the whole call
@@ -2146,6 +2248,11 @@ static int verify_host(mbls_ctx* c, const uint8_t* sigs, msgsrc hm, const mbls_m
     if (fmt != MBLS_PK_COMPRESSED && fmt != MBLS_PK_UNCOMPRESSED) ARGFAIL(c, "pk_format");
     keysrc ks = keys_wire(nullptr, fmt, nullptr);
     if (tab) { const int rk = keys_of_table(c, tab, nullptr, nullptr, &ks); if (rk) return rk; }
+    if (hc) {            // keys by committee and bitfield (pks, tab, idx, off null, k = 0): the table read under the lock, an id that names nothing refuses the call
+        const int rk = keys_of_committees(c, hc->t, nullptr, nullptr, hc->bits_stride, false, &ks); if (rk) return rk;
+        if (!hc->cmt_idx || !hc->bits) ARGFAIL(c, "null buffer");
+        for (uint64_t i = 0; i < n; i++) if ((uint64_t)hc->cmt_idx[i] >= hc->t->count) ARGFAIL(c, "cmt_idx names no committee of the table");
+    }
     if (off && !offsets_ok(off, n)) ARGFAIL(c, "offsets must be non-decreasing");
     HIPCHK(c, hipSetDevice(c->device));
     // like the messages, a key offset table may start anywhere (a shard of a larger batch): only keys [off[0], off[n]) are uploaded
@@ -2166,8 +2273,11 @@ static int verify_host(mbls_ctx* c, const uint8_t* sigs, msgsrc hm, const mbls_m
     }
     HIPCHK(c, dr.alloc(n)); HIPCHK(c, dst.alloc(4 * n)); b.d_results = dr.as<uint8_t>(); b.d_status = dst.as<uint32_t>();
     auto keys_are_there = [&]() { if (indexed) b.ks.d_idx = dp.as<uint32_t>() - key_first; else b.ks.d_pks = dp.as<uint8_t>() - unit * key_first; };     // the table's offsets are absolute
-    const bool late_keys = !hm.indexed();        // (the indexed kinds upload their keys up front: the late upload has not been measured for them)
-    if (late_keys) HIPCHK(c, dp.alloc(unit * total_keys)); else { HIPCHK(c, dp.up(h_keys, unit * total_keys)); keys_are_there(); }
+    const bool late_keys = !hm.indexed() && !hc; // (the indexed kinds and the committee form upload their keys up front: the late upload has not been measured for them)
+    if (hc) {            // the ids and the bitfields take the two key slots
+        HIPCHK(c, dp.up(hc->cmt_idx, 4 * n)); HIPCHK(c, doff.up(hc->bits, (size_t)hc->bits_stride * n));
+        b.ks.d_cmt_idx = dp.as<uint32_t>(); b.ks.d_bits = doff.as<uint8_t>();
+    } else if (late_keys) HIPCHK(c, dp.alloc(unit * total_keys)); else { HIPCHK(c, dp.up(h_keys, unit * total_keys)); keys_are_there(); }
     const bool tm = c->timing; c->timing = false;        // the phase timers assume the plain order, on the device entries
     int rc;
     if (!late_keys) rc = verify_device(c, b, mt, c->hs_a);
@@ -2233,6 +2343,7 @@ extern "C" void mbls_keytable_destroy(mbls_keytable* t) {
         if (t->d_recs) (void)hipFree(t->d_recs);
         if (t->ev) (void)hipEventDestroy(t->ev);
         for (size_t i = 0; i < c->tables.size(); i++) if (c->tables[i] == t) { c->tables.erase(c->tables.begin() + i); break; }
+        for (mbls_committees* ct : c->committees) if (ct->kt == t) ct->kt = nullptr;      // committee tables still bound to it: unbound, they refuse appends and verifications
     }
     delete t;
 }
@@ -2558,6 +2669,188 @@ extern "C" int mbls_fast_aggregate_verify_batch_indexed_msgtable(mbls_ctx* c, co
         const uint32_t* idx, const uint32_t* off, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status) {
     if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
     return verify_host(c, sigs, msgs_in_table(msg_idx), mt, nullptr, MBLS_PK_UNCOMPRESSED, t, idx, off, n, k, MBLS_MODE_FAST_AGGREGATE, results, status);
+}
+
+// ---- committee table (include/mbls.h, mbls_committees_*; arithmetic: mbls_cmt.h, device bodies: mbls_cmt_lanes.h). The member lists of every committee lie back to
+// back in d_members, one record per committee holds where its list starts, its size, the eligible flag and the full key sum. An append uploads the lists, sums them
+// with k_aggregate_indexed_d in the context's workspace and lets k_cmt_build write the records; ordering is the key table's (event, readers wait on the device).
+extern "C" int mbls_committees_create(mbls_ctx* c, mbls_keytable* kt, uint64_t capacity_hint, mbls_committees** out) {
+    if (!c || !kt || !out) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (kt->c != c) ARGFAIL(c, "key table belongs to another context");
+    if (capacity_hint > 0xFFFFFFFFull) ARGFAIL(c, "committee ids are 32-bit");
+    HIPCHK(c, hipSetDevice(c->device));
+    mbls_committees* t = new (std::nothrow) mbls_committees();
+    if (!t) return MBLS_ERR_DEVICE;
+    t->c = c; t->kt = kt; t->cap = capacity_hint ? capacity_hint : 64; t->members_cap = t->cap * 128;
+    hipError_t e = hipMalloc(&t->d_recs, t->cap * MBLS_CMT_REC_DWORDS * 4);
+    if (e == hipSuccess) e = hipMalloc(&t->d_members, t->members_cap * 4);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
+    bool listed = false;
+    if (e == hipSuccess) { try { c->committees.push_back(t); listed = true; } catch (...) { } }
+    if (!listed) {
+        if (t->d_recs) (void)hipFree(t->d_recs);
+        if (t->d_members) (void)hipFree(t->d_members);
+        if (t->ev) (void)hipEventDestroy(t->ev);
+        delete t;
+        if (e != hipSuccess) HIPCHK(c, e);
+        return MBLS_ERR_DEVICE;
+    }
+    *out = t; return MBLS_OK;
+}
+extern "C" void mbls_committees_destroy(mbls_committees* t) {
+    if (!t) return;
+    if (t->c) {
+        mbls_ctx* c = t->c;
+        mbls_lock lk(c->mu); (void)hipSetDevice(c->device); (void)hipDeviceSynchronize();
+        if (t->d_recs) (void)hipFree(t->d_recs);
+        if (t->d_members) (void)hipFree(t->d_members);
+        if (t->ev) (void)hipEventDestroy(t->ev);
+        for (size_t i = 0; i < c->committees.size(); i++) if (c->committees[i] == t) { c->committees.erase(c->committees.begin() + i); break; }
+    }
+    delete t;
+}
+extern "C" uint64_t mbls_committees_count(const mbls_committees* t) { if (!t || !t->c) return 0; mbls_lock lk(t->c->mu); return t->count; }
+extern "C" uint32_t mbls_committees_max_members(const mbls_committees* t) { if (!t || !t->c) return 0; mbls_lock lk(t->c->mu); return t->max_members; }
+extern "C" int mbls_committees_clear(mbls_committees* t) {
+    if (!t || !t->c) return MBLS_ERR_ARGUMENT;
+    mbls_ctx* c = t->c;
+    mbls_lock lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());           // every append and verification enqueued over the table
+    t->count = 0; t->n_members = 0; t->max_members = 0; t->pending = false; c->ws_pending = false;
+    return MBLS_OK;
+}
+// room for `need` uint32 / `need` records of 40 dwords: new buffer, the device drained on both sides of the copy (keytable_grow's rule)
+static int committees_grow(mbls_ctx* c, uint32_t** buf, uint64_t* cap, uint64_t used, uint64_t need, uint64_t unit_dwords) {
+    if (need <= *cap) return MBLS_OK;
+    const uint64_t ncap = *cap * 2 > need ? *cap * 2 : need;
+    uint32_t* nb = nullptr;
+    HIPCHK(c, hipMalloc(&nb, ncap * unit_dwords * 4));
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess && used) e = hipMemcpy(nb, *buf, used * unit_dwords * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { (void)hipFree(nb); HIPCHK(c, e); }
+    (void)hipFree(*buf); *buf = nb; *cap = ncap;
+    return MBLS_OK;
+}
+extern "C" int mbls_committees_append(mbls_committees* t, const uint32_t* key_idx, const uint32_t* offsets, uint64_t n, uint64_t* first_id) {
+    if (!t || !t->c) return MBLS_ERR_ARGUMENT;
+    mbls_ctx* c = t->c;
+    mbls_lock lk(c->mu);
+    if (!n) { if (first_id) *first_id = t->count; return MBLS_OK; }
+    if (!key_idx || !offsets) ARGFAIL(c, "null buffer");
+    if (!t->kt || t->kt->c != c) ARGFAIL(c, "the committee table's key table is gone");
+    if (t->count + n > 0xFFFFFFFFull) ARGFAIL(c, "committee ids are 32-bit");
+    uint32_t maxm = t->max_members;
+    for (uint64_t i = 0; i < n; i++) {
+        if (offsets[i + 1] < offsets[i]) ARGFAIL(c, "offsets must be non-decreasing");
+        const uint32_t m = offsets[i + 1] - offsets[i];
+        if (m == 0) ARGFAIL(c, "empty committee");
+        if (m > MBLS_CMT_MAX_MEMBERS) ARGFAIL(c, "a committee has more than MBLS_COMMITTEE_MAX_MEMBERS members");
+        if (m > maxm) maxm = m;
+    }
+    const uint64_t total = (uint64_t)offsets[n] - offsets[0], tsize = t->kt->size;
+    const uint32_t* idx = key_idx + offsets[0];
+    for (uint64_t j = 0; j < total; j++) if ((uint64_t)idx[j] >= tsize) ARGFAIL(c, "a member index is outside the key table");
+    if (t->n_members + total > 0xFFFFFFFFull) ARGFAIL(c, "member positions are 32-bit");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->hs_a;
+    int rc = mbls_ctx_reserve(c, n); if (rc) return rc;
+    rc = committees_grow(c, &t->d_recs, &t->cap, t->count, t->count + n, MBLS_CMT_REC_DWORDS); if (rc) return rc;
+    rc = committees_grow(c, &t->d_members, &t->members_cap, t->n_members, t->n_members + total, 1); if (rc) return rc;
+    // the offsets as the kernels want them: relative to the append's first member
+    std::vector<uint32_t> rel;
+    try { rel.resize(n + 1); } catch (...) { return MBLS_ERR_DEVICE; }
+    for (uint64_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0];
+    sbuf doff(c, 3);
+    HIPCHK(c, doff.up(rel.data(), 4 * (n + 1)));
+    rc = ws_acquire(c, s); if (rc) return rc;
+    rc = table_acquire(c, t->kt, s); if (rc) return rc;              // pending appends to the key table
+    rc = committees_acquire(c, t, s); if (rc) return rc;
+    uint32_t* const d_new = t->d_members + t->n_members;
+    HIPCHK(c, hipMemcpyAsync(d_new, idx, 4 * total, hipMemcpyHostToDevice, s));
+    mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
+    HIPCHK(c, hipMemsetAsync(c->d_status, 0, 4 * n, s));
+    hipLaunchKernelGGL(k_aggregate_indexed_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)t->kt->d_recs, t->kt->size, (const uint32_t*)d_new,
+                       (const uint32_t*)doff.as<uint32_t>(), 0u, MBLS_MODE_VERIFY, c->d_status, n);
+    hipLaunchKernelGGL(k_cmt_build, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)c->d_status, (const uint32_t*)doff.as<uint32_t>(), t->n_members,
+                       t->d_recs + t->count * MBLS_CMT_REC_DWORDS, n);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(t->ev, s)); t->ev_stream = s; t->pending = true;
+    // the staged offsets and the caller's indices are read until the kernels have run
+    HIPCHK(c, hipStreamSynchronize(s));
+    c->ws_pending = false; t->pending = false;
+    if (first_id) *first_id = t->count;
+    t->count += n; t->n_members += total; t->max_members = maxm;
+    return MBLS_OK;
+}
+extern "C" int mbls_committees_get(mbls_committees* t, uint64_t id, uint8_t* sum96, uint32_t* n_members, uint32_t* eligible) {
+    if (!t || !t->c) return MBLS_ERR_ARGUMENT;
+    mbls_ctx* c = t->c;
+    mbls_lock lk(c->mu);
+    if (id >= t->count) ARGFAIL(c, "committees_get: no such committee");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->hs_a;
+    sbuf dout(c, 0); HIPCHK(c, dout.alloc(96));
+    int rc = committees_acquire(c, t, s); if (rc) return rc;
+    const uint32_t* rec = t->d_recs + id * MBLS_CMT_REC_DWORDS;
+    hipLaunchKernelGGL(k_cmt_export, dim3(1), dim3(WG), 0, s, rec, dout.as<uint8_t>());
+    HIPCHK(c, hipGetLastError());
+    uint32_t head[4];
+    HIPCHK(c, hipMemcpyAsync(head, rec, sizeof(head), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (sum96) HIPCHK(c, dout.down(sum96, 96));
+    if (n_members) *n_members = head[1];
+    if (eligible) *eligible = head[2];
+    return MBLS_OK;
+}
+// the key source of a _committee entry: the table and its key table at the sizes they have now (the caller holds the context's lock)
+static int keys_of_committees(mbls_ctx* c, const mbls_committees* t, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride, bool device_bits, keysrc* ks) {
+    if (t->c != c) ARGFAIL(c, "committee table belongs to another context");
+    if (!t->kt || t->kt->c != c) ARGFAIL(c, "the committee table's key table is gone");
+    if (bits_stride % 4) ARGFAIL(c, "bits_stride must be a multiple of 4");
+    if ((uint64_t)8 * bits_stride < t->max_members) ARGFAIL(c, "bits_stride does not cover the table's largest committee");
+    if (device_bits && (((uintptr_t)d_bits) & 3u)) ARGFAIL(c, "d_bits must be 4-byte aligned");
+    keysrc kt; const int rk = keys_of_table(c, t->kt, nullptr, nullptr, &kt); if (rk) return rk;
+    *ks = keys_committee(kt, t->d_recs, t->count, t->d_members, t->max_members, d_cmt_idx, d_bits, bits_stride, t);
+    return MBLS_OK;
+}
+// a committee call on the device: the table read at the sizes it has now, then the one way into the pipeline (verify_device reserves the scratch of the plan)
+static int verify_committee_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, msgsrc ms, const mbls_msgtable* mt, const uint32_t* d_cmt_idx,
+                                   const uint8_t* d_bits, uint32_t bits_stride, uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, hipStream_t s) {
+    keysrc ks; const int rk = keys_of_committees(c, t, d_cmt_idx, d_bits, bits_stride, true, &ks); if (rk) return rk;
+    if (n == 0) return MBLS_OK;
+    if (!d_cmt_idx || !d_bits) ARGFAIL(c, "null buffer");
+    return verify_device(c, batch{d_sigs, ms, ks, n, 0, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status}, mt, s);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_committee_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len,
+        const uint64_t* d_moff, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride, uint64_t n, uint8_t* d_results, uint64_t* d_bitmap,
+        uint32_t* d_status, void* stream) {
+    if (!c || !t) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    return verify_committee_device(c, t, d_sigs, msgs_per_item(d_msgs, msg_len, d_moff), nullptr, d_cmt_idx, d_bits, bits_stride, n, d_results, d_bitmap, d_status,
+                                   (hipStream_t)stream);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_committee_msgtable_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const mbls_msgtable* mt,
+        const uint32_t* d_msg_idx, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride, uint64_t n, uint8_t* d_results, uint64_t* d_bitmap,
+        uint32_t* d_status, void* stream) {
+    if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    return verify_committee_device(c, t, d_sigs, msgs_in_table(d_msg_idx), mt, d_cmt_idx, d_bits, bits_stride, n, d_results, d_bitmap, d_status, (hipStream_t)stream);
+}
+// the host forms: verify_host with the committee description in place of keys
+extern "C" int mbls_fast_aggregate_verify_batch_committee(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
+        const uint64_t* moff, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_stride, uint64_t n, uint8_t* results, uint32_t* status) {
+    if (!c || !t) return MBLS_ERR_ARGUMENT;
+    const host_committees hc = {t, cmt_idx, bits, bits_stride};
+    return verify_host(c, sigs, msgs_per_item(msgs, msg_len, moff), nullptr, nullptr, MBLS_PK_UNCOMPRESSED, nullptr, nullptr, nullptr, n, 0, MBLS_MODE_FAST_AGGREGATE, results, status, &hc);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_committee_msgtable(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs, const mbls_msgtable* mt,
+        const uint32_t* msg_idx, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_stride, uint64_t n, uint8_t* results, uint32_t* status) {
+    if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
+    const host_committees hc = {t, cmt_idx, bits, bits_stride};
+    return verify_host(c, sigs, msgs_in_table(msg_idx), mt, nullptr, MBLS_PK_UNCOMPRESSED, nullptr, nullptr, nullptr, n, 0, MBLS_MODE_FAST_AGGREGATE, results, status, &hc);
 }
 
 // ---- batch helpers

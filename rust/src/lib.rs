@@ -55,6 +55,11 @@ pub struct mbls_msgtable {
 }
 #[allow(non_camel_case_types)]
 #[repr(C)]
+pub struct mbls_committees {
+    _p: [u8; 0],
+}
+#[allow(non_camel_case_types)]
+#[repr(C)]
 pub struct mbls_stream {
     _p: [u8; 0],
 }
@@ -176,6 +181,23 @@ extern "C" {
                                   results: *mut u8, status: *mut u32) -> c_int;
     fn mbls_fast_aggregate_verify_batch_indexed_msgtable(ctx: *mut MblsCtx, t: *const MblsKeyTable, sigs: *const u8, mt: *const mbls_msgtable, msg_idx: *const u32,
                                                          key_idx: *const u32, offsets: *const u32, n: u64, k: u32, results: *mut u8, status: *mut u32) -> c_int;
+    // committee table: ordered member lists over a key table with their cached key sums; verify by committee id and participation bits
+    fn mbls_committees_create(ctx: *mut MblsCtx, keytable: *mut MblsKeyTable, capacity_hint: u64, out: *mut *mut mbls_committees) -> c_int;
+    fn mbls_committees_destroy(t: *mut mbls_committees);
+    fn mbls_committees_count(t: *const mbls_committees) -> u64;
+    fn mbls_committees_clear(t: *mut mbls_committees) -> c_int;
+    fn mbls_committees_max_members(t: *const mbls_committees) -> u32;
+    fn mbls_committees_append(t: *mut mbls_committees, key_idx: *const u32, offsets: *const u32, n_committees: u64, first_id: *mut u64) -> c_int;
+    fn mbls_committees_get(t: *mut mbls_committees, id: u64, sum96: *mut u8, n_members: *mut u32, eligible: *mut u32) -> c_int;
+    fn mbls_ctx_set_committee_route(ctx: *mut MblsCtx, mode: c_int) -> c_int;
+    fn mbls_plan_committee_route(m: u32, s: u32, eligible: c_int, mode: c_int) -> c_int;
+    fn mbls_ctx_reserve_committee_items(ctx: *mut MblsCtx, max_items: u64, max_members: u32) -> c_int;
+    fn mbls_fast_aggregate_verify_batch_committee(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs: *const u8, msgs: *const u8, msg_len: u32,
+                                                  msg_offsets: *const u64, cmt_idx: *const u32, bits: *const u8, bits_stride: u32, n: u64, results: *mut u8,
+                                                  status: *mut u32) -> c_int;
+    fn mbls_fast_aggregate_verify_batch_committee_msgtable(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs: *const u8, mt: *const mbls_msgtable,
+                                                           msg_idx: *const u32, cmt_idx: *const u32, bits: *const u8, bits_stride: u32, n: u64, results: *mut u8,
+                                                           status: *mut u32) -> c_int;
     fn mbls_verify_multiple_msgtable_device(ctx: *mut MblsCtx, d_sigs96: *const u8, d_apks96: *const u8, mt: *const mbls_msgtable, d_msg_idx: *const u32, d_rands: *const u64,
                                             n: u64, d_result: *mut u8, d_status: *mut u32, stream: *mut c_void) -> c_int;
     fn mbls_verify_multiple_sets_indexed_msgtable_device(ctx: *mut MblsCtx, t: *const MblsKeyTable, d_sigs96: *const u8, d_key_idx: *const u32, d_offsets: *const u32, k: u32,
@@ -1402,6 +1424,131 @@ impl MessageTableStream {
     }
     pub fn flush(&self) {
         unsafe { mbls_stream_flush(self.h) };
+    }
+}
+/// Committees resident in GPU memory (`mbls_committees_*`; not part of the reference's API): ordered member lists of `KeyTable` indices, each kept with its full
+/// key sum -- what the beacon state stores as a sync committee's `aggregate_pubkey`. A verification names a committee and carries the participation bits as SSZ
+/// serializes them (bit j = member j; bits at or above the committee's size are ignored; checking a Bitlist's length stays with the caller); on the device the
+/// aggregate key is the sum of the signers or, where most signed, the cached sum minus the absentees. Same bools as `KeyTable::fast_aggregate_verify_msgtable` with
+/// the signers spelled out. Drop it before the key table it was made over. (Like the rest of this crate: source only, never compiled.)
+pub struct CommitteeTable {
+    h: *mut mbls_committees,
+}
+unsafe impl Send for CommitteeTable {}
+unsafe impl Sync for CommitteeTable {}
+impl CommitteeTable {
+    pub fn new(keys: &KeyTable, capacity_hint: u64) -> Self {
+        let mut h: *mut mbls_committees = std::ptr::null_mut();
+        let rc = unsafe { mbls_committees_create(ctx(), keys.h, capacity_hint, &mut h) };
+        if rc != 0 {
+            err(rc);
+        }
+        CommitteeTable { h }
+    }
+    pub fn len(&self) -> u64 {
+        unsafe { mbls_committees_count(self.h) }
+    }
+    pub fn is_empty(&self) -> bool {
+        self.len() == 0
+    }
+    /// One committee per member list (key-table indices, in member order); returns the id of the first.
+    pub fn append(&mut self, committees: &[&[u32]]) -> u64 {
+        let mut flat: Vec<u32> = Vec::new();
+        let mut off: Vec<u32> = vec![0];
+        for c in committees {
+            flat.extend_from_slice(c);
+            off.push(flat.len() as u32);
+        }
+        let mut first = 0u64;
+        let rc = unsafe { mbls_committees_append(self.h, flat.as_ptr(), off.as_ptr(), committees.len() as u64, &mut first) };
+        if rc != 0 {
+            err(rc);
+        }
+        first
+    }
+    /// The committee's full key sum as 96 uncompressed bytes, its member count, and whether every member is a valid, finite key.
+    pub fn aggregate_pubkey(&self, id: u64) -> ([u8; 96], u32, bool) {
+        let mut p = [0u8; 96];
+        let (mut m, mut e) = (0u32, 0u32);
+        let rc = unsafe { mbls_committees_get(self.h, id, p.as_mut_ptr(), &mut m, &mut e) };
+        if rc != 0 {
+            err(rc);
+        }
+        (p, m, e != 0)
+    }
+    /// Count back to 0 (waits for everything enqueued over the table); the next append starts at id 0.
+    pub fn clear(&mut self) -> bool {
+        unsafe { mbls_committees_clear(self.h) == 0 }
+    }
+    /// 0: the cheaper route per item, 1: always sum the signers, 2: cached sum minus the absentees wherever the committee allows it.
+    pub fn set_route(mode: i32) -> bool {
+        unsafe { mbls_ctx_set_committee_route(ctx(), mode as c_int) == 0 }
+    }
+    /// Reserves the per-call scratch for batches of `max_items` items over committees of up to `max_members` members.
+    pub fn reserve(max_items: u64, max_members: u32) -> bool {
+        unsafe { mbls_ctx_reserve_committee_items(ctx(), max_items, max_members) == 0 }
+    }
+    /// `true`: an item with `s` of `m` members selected takes the complement route under `mode` (pure: no GPU).
+    pub fn plan_route(m: u32, s: u32, eligible: bool, mode: i32) -> bool {
+        unsafe { mbls_plan_committee_route(m, s, eligible as c_int, mode as c_int) == 1 }
+    }
+    /// Every bitfield at one stride: the bytes that cover the table's largest committee, rounded up to 4 (bytes of a field beyond that hold only bits at or
+    /// above every committee's size, which the entries ignore).
+    fn flatten_bits(&self, bits: &[&[u8]]) -> (Vec<u8>, u32) {
+        let largest = unsafe { mbls_committees_max_members(self.h) } as usize;
+        let stride = (((largest + 7) / 8).max(1) + 3) / 4 * 4;
+        let mut flat = vec![0u8; stride * bits.len().max(1)];
+        for (i, b) in bits.iter().enumerate() {
+            let n = b.len().min(stride);
+            flat[stride * i..stride * i + n].copy_from_slice(&b[..n]);
+        }
+        (flat, stride as u32)
+    }
+    /// n x `AggregateSignature::fast_aggregate_verify`: item i = (signatures[i], messages[i], the members of committee committee_ids[i] whose bit is set in bits[i]).
+    pub fn fast_aggregate_verify(&self, signatures: &[AggregateSignature], messages: &[&[u8]], committee_ids: &[u32], bits: &[&[u8]]) -> Vec<bool> {
+        let n = signatures.len();
+        assert!(messages.len() == n && committee_ids.len() == n && bits.len() == n);
+        let sigs: Vec<u8> = signatures.iter().flat_map(|s| s.point.iter().copied()).collect();
+        let mut msgs: Vec<u8> = Vec::new();
+        let mut moff: Vec<u64> = vec![0];
+        for m in messages {
+            msgs.extend_from_slice(m);
+            moff.push(msgs.len() as u64);
+        }
+        let (flat, stride) = self.flatten_bits(bits);
+        let mut res = vec![0u8; n.max(1)];
+        let rc = unsafe {
+            mbls_fast_aggregate_verify_batch_committee(ctx(), self.h, sigs.as_ptr(), msgs.as_ptr(), 0, moff.as_ptr(), committee_ids.as_ptr(), flat.as_ptr(), stride, n as u64,
+                                                       res.as_mut_ptr(), std::ptr::null_mut())
+        };
+        if rc != 0 {
+            err(rc);
+        }
+        res.truncate(n);
+        res.into_iter().map(|b| b == 1).collect()
+    }
+    /// The same with the messages named by index into a `MessageTable`.
+    pub fn fast_aggregate_verify_msgtable(&self, signatures: &[AggregateSignature], table: &MessageTable, message_indices: &[u32], committee_ids: &[u32],
+                                          bits: &[&[u8]]) -> Vec<bool> {
+        let n = signatures.len();
+        assert!(message_indices.len() == n && committee_ids.len() == n && bits.len() == n);
+        let sigs: Vec<u8> = signatures.iter().flat_map(|s| s.point.iter().copied()).collect();
+        let (flat, stride) = self.flatten_bits(bits);
+        let mut res = vec![0u8; n.max(1)];
+        let rc = unsafe {
+            mbls_fast_aggregate_verify_batch_committee_msgtable(ctx(), self.h, sigs.as_ptr(), table.h, message_indices.as_ptr(), committee_ids.as_ptr(), flat.as_ptr(), stride,
+                                                                n as u64, res.as_mut_ptr(), std::ptr::null_mut())
+        };
+        if rc != 0 {
+            err(rc);
+        }
+        res.truncate(n);
+        res.into_iter().map(|b| b == 1).collect()
+    }
+}
+impl Drop for CommitteeTable {
+    fn drop(&mut self) {
+        unsafe { mbls_committees_destroy(self.h) }
     }
 }
 impl Drop for MessageTableStream {
