@@ -354,7 +354,8 @@ int mbls_fast_aggregate_verify_batch_indexed_msgtable(mbls_ctx* ctx, const mbls_
  * ROUTE (mbls_ctx_set_committee_route; mbls_ctx_reset_tuning restores 0): 0 auto, 1 always direct, 2 complement whenever the committee is eligible.
  *   mbls_plan_committee_route(m, s, eligible, mode) states the decision without a GPU -- the SAME function the kernel runs (csrc/mbls_cmt.h): 1 complement,
  *   0 direct, MBLS_ERR_ARGUMENT for a mode outside 0..2, m = 0, m > MBLS_COMMITTEE_MAX_MEMBERS or s > m.
- * OUT OF SCOPE: the verification stream, the shared-list message form, verify_multiple over committees, the mbls_multi handle, a device-pointer append. */
+ * OUT OF SCOPE: the verification stream, the shared-list message form, the mbls_multi handle, a device-pointer append. (verify_multiple over committees:
+ * mbls_verify_multiple_committee_msgtable*, below.) */
 #define MBLS_COMMITTEE_MAX_MEMBERS 2048
 typedef struct mbls_committees mbls_committees;
 int mbls_committees_create(mbls_ctx* ctx, mbls_keytable* keytable, uint64_t capacity_hint, mbls_committees** out);
@@ -868,6 +869,55 @@ int mbls_verify_multiple_sets_indexed_msgtable_locate_device(mbls_ctx* ctx, cons
                                                              uint32_t* d_set_status, void* stream);
 int mbls_verify_multiple_msgtable_locate_rng(mbls_ctx* ctx, const uint8_t* sigs96, const uint8_t* apks96, const mbls_msgtable* mt, const uint32_t* msg_idx,
                                              uint64_t n, uint8_t* result, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user);
+
+/* verify_multiple OVER COMMITTEE BITFIELDS AND THE RESIDENT MESSAGE TABLE. A consensus client verifies gossip with verify_multiple_aggregate_signatures, and a
+ * gossip batch mixes two kinds of set: an aggregate over a committee's bitfield, and sets under ONE validator key (a SignedAggregateAndProof's selection proof and
+ * its aggregator's signature, an unaggregated attestation). These entries are mbls_verify_multiple_sets_indexed_msgtable[_locate]_device with `d_key_idx,
+ * d_offsets, k` replaced by `committees, d_cmt_idx, d_bits, bits_stride` -- the key table is the one the committee table is bound to --, and take both kinds in
+ * one call. Set i is described by the word cmt_idx[i] and the bits_stride bytes at bits + bits_stride * i (csrc/mbls_vmc.h):
+ *   bit 31 clear: a COMMITTEE set. The word is a committee id, the bytes its SSZ bitfield, every rule the committee section's above: bits at or above the
+ *     committee's size are ignored, the route is cmt_route's under mbls_ctx_set_committee_route, an id at or above the count lists the one index 0xFFFFFFFF.
+ *   bit 31 set (MBLS_VM_SET_SINGLE_KEY | index): a SINGLE-KEY set. The low 31 bits are an index into the key table; the set's key list is that one index on the
+ *     direct route and its bitfield bytes are NOT READ (they are still bits_stride bytes of the buffer). An index at or above the key table's size rejects the
+ *     set through the key sum (MBLS_ST_BAD_PK_ENCODING) like any index outside the table; 0xFFFFFFFF therefore still rejects.
+ * The committee entries of the section above do not change: they keep treating a bit-31 id as one that names no committee.
+ * KEY PHASE. k_vmc_expand (one wave per set) writes every set's index list -- the selected members, the missing ones on the complement route, or the one key --,
+ * count and route word; the committee entries' key sum over those lists leaves each set's sum where the indexed key sum leaves it. Everything behind it --
+ * blinding, grouping by table entry, heads, Miller loops, tail, both phase-two routes of the _locate forms -- is the _msgtable entries' above, unchanged.
+ * CONTRACT. *d_result, *d_status, and for the _locate forms every byte of d_set_results and every word of d_set_status, are those of
+ * mbls_verify_multiple_sets_indexed_msgtable[_locate]_device on the same signatures, scalars and message indices with every set's signers spelled out in member
+ * order through a ragged offset table (a single-key set spells out as its one index), under every mode of mbls_ctx_set_vm_grouping and of
+ * mbls_ctx_set_committee_route. The status bits of the key phase are therefore verify_multiple's: MBLS_ST_BAD_PK_ENCODING and MBLS_ST_PK_INFINITY of the LISTED
+ * members of an ineligible committee (which always goes direct), as the indexed key sum reports them. Like those entries -- and unlike fast_aggregate_verify --
+ * the key phase does not flag an empty bitfield or a sum at infinity (no MBLS_ST_NO_KEYS, no MBLS_ST_APK_INFINITY): such a set's key is the point at infinity,
+ * its pairing contributes 1, and the call is rejected through the product unless its signature is the point at infinity too.
+ * ARGUMENTS: the committee entries' checks (one context for all three tables, the key table alive, bits_stride a multiple of 4 that covers
+ * mbls_committees_max_members, d_bits 4-byte aligned) and the _msgtable entries' (d_rands and, for _locate, d_set_results not NULL); otherwise MBLS_ERR_ARGUMENT.
+ * n = 0 answers as mbls_verify_multiple_msgtable_device does (result 1, status 0). The tables are read at the sizes they have when the call is enqueued.
+ * HOST ENTRIES (_rng) keep the reference's order exactly as mbls_verify_multiple_msgtable_rng does: signatures decoded and tested first, `draw` called at most
+ * once, for the sets in front of the first bad signature. They refuse with MBLS_ERR_ARGUMENT, nothing queued and the outputs untouched: a committee id at or
+ * above the count, a single-key index at or above the key table's size, a message index at or above the message table's size.
+ * ORDERING AND ALLOCATION are the committee section's: the list scratch -- n x (largest committee) words plus two words per set -- is reserved for the n sets
+ * before the first kernel of the call (mbls_ctx_reserve_committee_items beforehand keeps that out of the call); the last appends to the committee table, its key
+ * table and the message table are awaited on the caller's stream before any side stream has work, and no fallible step is left once one has.
+ * PLANNING. Routing and workspace are mbls_plan_verify_multiple_msgtable, _workspace_items and _locate_workspace_items, UNCHANGED: the committee source adds
+ * no workspace item (its scratch is the committee entries').
+ * OUT OF SCOPE: the verification stream, the shared-list and per-set message forms over committees, mbls_verify_multiple_batches over committees, the mbls_multi
+ * handle and the shard form, sets that span several committees, a device-pointer append. */
+#define MBLS_VM_SET_SINGLE_KEY 0x80000000u
+int mbls_verify_multiple_committee_msgtable_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96, const uint32_t* d_cmt_idx,
+                                                   const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
+                                                   const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream);
+int mbls_verify_multiple_committee_msgtable_locate_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96, const uint32_t* d_cmt_idx,
+                                                          const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
+                                                          const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results,
+                                                          uint32_t* d_set_status, void* stream);
+int mbls_verify_multiple_committee_msgtable_rng(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs96, const uint32_t* cmt_idx,
+                                                const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n,
+                                                uint8_t* result, mbls_scalar_source draw, void* user);
+int mbls_verify_multiple_committee_msgtable_locate_rng(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs96, const uint32_t* cmt_idx,
+                                                       const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n,
+                                                       uint8_t* result, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user);
 
 /* ---- batch helpers used to build inputs and caches on the device ---- */
 /* n x PublicKey::from_bytes[_unchecked] / from_uncompressed_bytes: errs[i] = MBLS_OK / MBLS_ERR_* per key */

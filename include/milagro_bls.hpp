@@ -653,6 +653,64 @@ public:
         return a;
     }
     void clear() { detail::check(mbls_committees_clear(h_)); }
+    // AggregateSignature::verify_multiple_aggregate_signatures over a gossip batch whose keys and messages are resident (mbls_verify_multiple_committee_msgtable_rng).
+    // A set is a signature, an entry of `table` and either a committee of this table with the participation bits as serialized by SSZ (GossipSet::aggregate) or ONE
+    // key of the key table the committees are bound to (GossipSet::single_key: a selection proof, an aggregator's signature, an unaggregated attestation). The same
+    // bool as verify_multiple_aggregate_signatures on the spelled-out aggregate keys and messages, rng left in the same state. A committee id, key index or entry
+    // index that names nothing throws (DeviceError). rng(): one random byte per call.
+    struct GossipSet {
+        const AggregateSignature* signature; uint32_t word; Bytes bits; uint32_t msg_index;
+        static GossipSet aggregate(const AggregateSignature* sig, uint32_t committee_id, const Bytes& bits, uint32_t msg_index) {
+            if (committee_id & MBLS_VM_SET_SINGLE_KEY) throw std::invalid_argument("GossipSet::aggregate: committee ids have 31 bits");
+            return GossipSet{sig, committee_id, bits, msg_index};
+        }
+        static GossipSet single_key(const AggregateSignature* sig, uint32_t key_index, uint32_t msg_index) {
+            if (key_index & MBLS_VM_SET_SINGLE_KEY) throw std::invalid_argument("GossipSet::single_key: key indices have 31 bits");
+            return GossipSet{sig, MBLS_VM_SET_SINGLE_KEY | key_index, Bytes(), msg_index};
+        }
+    };
+    template <typename Rng>
+    bool verify_multiple_aggregate_signatures(Rng&& rng, const std::vector<GossipSet>& sets, const MessageTable& table) const { return vm(rng, sets, table, nullptr); }
+    // The same, and in the same call (mbls_verify_multiple_committee_msgtable_locate_rng) which sets of a rejected call are the bad ones, with the semantics of
+    // AggregateSignature::verify_multiple_aggregate_signatures_shared_msgs_locate.
+    template <typename Rng>
+    std::pair<bool, std::vector<bool>> verify_multiple_aggregate_signatures_locate(Rng&& rng, const std::vector<GossipSet>& sets, const MessageTable& table) const {
+        std::vector<bool> per_set;
+        const bool ok = vm(rng, sets, table, &per_set);
+        return {ok, per_set};
+    }
+private:
+    template <typename Rng>
+    bool vm(Rng& rng, const std::vector<GossipSet>& sets, const MessageTable& table, std::vector<bool>* per_set) const {
+        if (sets.empty()) return true;
+        const size_t n = sets.size();
+        const size_t covering = (size_t(max_members()) + 7) / 8;                   // one stride for every field, as fast_aggregate_verify_batch_committee_msgtable lays them out
+        const uint32_t stride = uint32_t(((covering ? covering : 1) + 3) / 4 * 4);
+        Bytes sigs, flat(size_t(stride) * n, 0); std::vector<uint32_t> words, idx;
+        for (size_t i = 0; i < n; i++) {
+            const GossipSet& s = sets[i];
+            sigs.insert(sigs.end(), s.signature->point.begin(), s.signature->point.end());
+            std::copy(s.bits.begin(), s.bits.begin() + std::min(s.bits.size(), size_t(stride)), flat.begin() + size_t(stride) * i);
+            words.push_back(s.word); idx.push_back(s.msg_index);
+        }
+        using R = typename std::remove_reference<Rng>::type;
+        struct src { R* rng; std::exception_ptr err; } u{&rng, nullptr};
+        mbls_scalar_source draw = [](void* user, uint64_t* out, uint64_t count) {
+            src* p = static_cast<src*>(user);
+            try { for (uint64_t i = 0; i < count; i++) out[i] = AggregateSignature::draw_scalar(*p->rng); }
+            catch (...) { p->err = std::current_exception(); for (uint64_t i = 0; i < count; i++) out[i] = 0; }        // never unwind through the C frames
+        };
+        uint8_t ok = 0;
+        std::vector<uint8_t> sres(per_set ? n : 0);
+        const int rc = per_set
+            ? mbls_verify_multiple_committee_msgtable_locate_rng(detail::ctx(), h_, sigs.data(), words.data(), flat.data(), stride, table.handle(), idx.data(), n, &ok,
+                                                                 sres.data(), nullptr, draw, &u)
+            : mbls_verify_multiple_committee_msgtable_rng(detail::ctx(), h_, sigs.data(), words.data(), flat.data(), stride, table.handle(), idx.data(), n, &ok, draw, &u);
+        if (u.err) std::rethrow_exception(u.err);
+        detail::check(rc);
+        if (per_set) per_set->assign(sres.begin(), sres.end());
+        return ok == 1;
+    }
 };
 // n x AggregateSignature::fast_aggregate_verify over a committee table and a resident message table (mbls_fast_aggregate_verify_batch_committee_msgtable): item i =
 // (sigs[i], entry msg_idx[i], the members of committee cmt_idx[i] whose bit is set in bits[i]); the fields are laid out at one stride (16 bytes for 128 members)

@@ -4,6 +4,6 @@ The package holds only what the verification path needs: csrc/ (HIP kernels + th
 declared in include/mbls.h), `api` (host-side mirror of the reference's types, reference src/lib.rs:17-22)
 and `batch` (batch / device-pointer entry points). There is no CPU fallback."""
 from ._native import Context, MblsError, default_context, PK_COMPRESSED, PK_UNCOMPRESSED  # noqa: F401
-from .api import (AggregatePublicKey, AggregateSignature, AmclError, Keypair, PublicKey, SecretKey, Signature,  # noqa: F401
+from .api import (AggregatePublicKey, AggregateSignature, AmclError, Keypair, PublicKey, SecretKey, Signature, SingleKey,  # noqa: F401
                   G1_BYTES, G2_BYTES, SECRET_KEY_BYTES)
 from . import batch  # noqa: F401

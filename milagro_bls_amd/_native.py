@@ -331,6 +331,10 @@ SIGNATURES = {
     "mbls_verify_multiple_msgtable_locate_device": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp]),
     "mbls_verify_multiple_sets_indexed_msgtable_locate_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp]),
     "mbls_verify_multiple_msgtable_locate_rng": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, SCALAR_SOURCE, vp]),
+    "mbls_verify_multiple_committee_msgtable_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp]),
+    "mbls_verify_multiple_committee_msgtable_locate_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp]),
+    "mbls_verify_multiple_committee_msgtable_rng": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, SCALAR_SOURCE, vp]),
+    "mbls_verify_multiple_committee_msgtable_locate_rng": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, SCALAR_SOURCE, vp]),
     "mbls_plan_locate_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64]),
     "mbls_verify_multiple_batches_locate_device": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp,
                                                              vp, vp, vp]),
@@ -605,6 +609,7 @@ class MsgTable:
 
 COMMITTEE_MAX_MEMBERS = 2048    # include/mbls.h MBLS_COMMITTEE_MAX_MEMBERS
 CMT_ROUTE_AUTO, CMT_ROUTE_DIRECT, CMT_ROUTE_COMPLEMENT = 0, 1, 2
+VM_SET_SINGLE_KEY = 0x80000000   # mbls_verify_multiple_committee_msgtable*: a set under one key of the key table (the low 31 bits are its index)
 
 
 def plan_committee_route(m, s, eligible=True, mode=CMT_ROUTE_AUTO):

@@ -243,6 +243,18 @@ class AggregatePublicKey:
 
 
 
+class SingleKey:
+    """In a set of verify_multiple_aggregate_signatures_committee: the set is signed by ONE key, entry `index` of the key table the committees are bound to (a
+    selection proof, an aggregator's signature, an unaggregated attestation)."""
+    __slots__ = ("index",)
+
+    def __init__(self, index):
+        index = int(index)
+        if not 0 <= index < N.VM_SET_SINGLE_KEY:
+            raise ValueError("a key index has 31 bits")
+        self.index = index
+
+
 def _reference_draw(rng, failed):
     """The scalar source of the verify_multiple methods: src/aggregates.rs:280-287 -- 8 random bytes, big-endian i64, absolute value, retry on zero --, for the sets
     the reference's loop reaches a draw for. An exception must not unwind through the C frames: the batch fails (zero scalars) and the caller raises failed[0]."""
@@ -416,6 +428,61 @@ class AggregateSignature:
             rc = N.lib().mbls_verify_multiple_msgtable_locate_rng(ctx.handle, S, A, table.handle, midx, len(sets), res, sres, None, cb, None)
         else:
             rc = N.lib().mbls_verify_multiple_msgtable_rng(ctx.handle, S, A, table.handle, midx, len(sets), res, cb, None)
+        ctx.check(rc)
+        if failed:
+            raise failed[0]
+        if not locate:
+            return bool(bytes(res)[0])
+        return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:len(sets)]]
+
+    @staticmethod
+    def verify_multiple_aggregate_signatures_committee(rng, signature_sets, committees, table):
+        """Not in the reference: verify_multiple_aggregate_signatures over a gossip batch whose keys are resident (mbls_verify_multiple_committee_msgtable_rng). A set
+        is (signature, committee_id, bits_bytes, message_index) -- the aggregate over the members of committee `committee_id` of `committees`
+        (_native.CommitteeTable) whose bit is set, SSZ bit order, bits at or above the committee's size ignored -- or (signature, SingleKey(index), None,
+        message_index): one key of the key table the committees are bound to. Messages are entries of `table` (_native.MsgTable). The same bool as
+        verify_multiple_aggregate_signatures on the spelled-out aggregate keys and messages, `rng` left in the same state. A committee id, key index or message
+        index that names nothing raises."""
+        return AggregateSignature._vm_committee(rng, signature_sets, committees, table, False)
+
+    @staticmethod
+    def verify_multiple_aggregate_signatures_committee_locate(rng, signature_sets, committees, table):
+        """verify_multiple_aggregate_signatures_committee, and in the same call (mbls_verify_multiple_committee_msgtable_locate_rng) which sets of a rejected call
+        are the bad ones. Returns (bool, list[bool]) with the semantics of verify_multiple_aggregate_signatures_shared_msgs_locate."""
+        return AggregateSignature._vm_committee(rng, signature_sets, committees, table, True)
+
+    @staticmethod
+    def _vm_committee(rng, signature_sets, committees, table, locate):
+        sets = list(signature_sets)
+        if not sets:
+            return (True, []) if locate else True
+        stride = max(4, (committees.max_members + 31) // 32 * 4)
+        words, fields = [], []
+        for s in sets:
+            if isinstance(s[1], SingleKey):
+                words.append(N.VM_SET_SINGLE_KEY | s[1].index)
+                fields.append(bytes(stride))
+            else:
+                cid, field = int(s[1]), bytes(s[2])
+                if not 0 <= cid < N.VM_SET_SINGLE_KEY:
+                    raise ValueError("committee id out of range")
+                if len(field) > stride and any(field[stride:]):
+                    raise ValueError("a bitfield names members beyond the table's largest committee")
+                words.append(cid)
+                fields.append(field[:stride].ljust(stride, b"\0"))
+        failed = []
+        cb = N.SCALAR_SOURCE(_reference_draw(rng, failed))
+        cidx = (C.c_uint32 * len(sets))(*words)
+        midx = (C.c_uint32 * len(sets))(*[int(s[3]) for s in sets])
+        res = N.outbuf(1)
+        ctx = committees.ctx
+        S, B = N.cbuf(b"".join(s[0].point for s in sets)), N.cbuf(b"".join(fields))
+        if locate:
+            sres = N.outbuf(len(sets))
+            rc = N.lib().mbls_verify_multiple_committee_msgtable_locate_rng(ctx.handle, committees.handle, S, cidx, B, stride, table.handle, midx, len(sets), res, sres,
+                                                                           None, cb, None)
+        else:
+            rc = N.lib().mbls_verify_multiple_committee_msgtable_rng(ctx.handle, committees.handle, S, cidx, B, stride, table.handle, midx, len(sets), res, cb, None)
         ctx.check(rc)
         if failed:
             raise failed[0]

@@ -702,3 +702,49 @@ def verify_multiple_msgtable_locate_rng(msg_table, sigs, apks, msg_idx, n, draw,
     cb = _scalar_source(draw)
     ctx.check(N.lib().mbls_verify_multiple_msgtable_locate_rng(ctx.handle, N.cbuf(sigs), N.cbuf(apks), msg_table.handle, _midx(msg_idx, n), n, res, sres, sst, cb, None))
     return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:n]], list(sst)[:n]
+
+
+# ---- verify_multiple over committee bitfields and the resident message table (include/mbls.h, mbls_verify_multiple_committee_msgtable*): set i is the word
+# cmt_idx[i] -- a committee id, or VM_SET_SINGLE_KEY | key-table index -- and bits_stride bytes of bitfield (not read for a single-key set). Routing and workspace
+# are plan_verify_multiple_msgtable*, unchanged.
+VM_SET_SINGLE_KEY = N.VM_SET_SINGLE_KEY
+
+
+def verify_multiple_committee_msgtable_device(committees, msg_table, d_sigs, d_cmt_idx, d_bits, bits_stride, d_msg_idx, d_rands, n, d_result, d_status=None, stream=None,
+                                              ctx=None):
+    """verify_multiple_sets_indexed_msgtable_device with every set's signers named by committee and bitfield (or by one key index) over an N.CommitteeTable.
+    Enqueues only: the bool at the device byte d_result, the status word at d_status (optional)."""
+    ctx = ctx or committees.ctx
+    ctx.check(N.lib().mbls_verify_multiple_committee_msgtable_device(ctx.handle, committees.handle, d_sigs, d_cmt_idx, d_bits, bits_stride, msg_table.handle, d_msg_idx,
+                                                                     d_rands, n, d_result, d_status, stream))
+
+
+def verify_multiple_committee_msgtable_locate_device(committees, msg_table, d_sigs, d_cmt_idx, d_bits, bits_stride, d_msg_idx, d_rands, n, d_result, d_set_results,
+                                                     d_status=None, d_set_status=None, stream=None, ctx=None):
+    """The same, and in the same call one answer per SET: n result bytes at d_set_results (required), n status words at d_set_status (optional). Enqueues only."""
+    ctx = ctx or committees.ctx
+    ctx.check(N.lib().mbls_verify_multiple_committee_msgtable_locate_device(ctx.handle, committees.handle, d_sigs, d_cmt_idx, d_bits, bits_stride, msg_table.handle,
+                                                                            d_msg_idx, d_rands, n, d_result, d_status, d_set_results, d_set_status, stream))
+
+
+def verify_multiple_committee_msgtable_rng(committees, msg_table, sigs, cmt_idx, bits, bits_stride, msg_idx, n, draw, ctx=None):
+    """Host buffers and the reference's draw order (mbls_verify_multiple_committee_msgtable_rng; draw as verify_multiple_msgtable_rng takes it). A word or a message
+    index that names nothing raises (MBLS_ERR_ARGUMENT). Returns the bool."""
+    ctx = ctx or committees.ctx
+    res = N.outbuf(1)
+    cb = _scalar_source(draw)
+    ctx.check(N.lib().mbls_verify_multiple_committee_msgtable_rng(ctx.handle, committees.handle, N.cbuf(sigs), _midx(cmt_idx, n), _bits(bits, bits_stride, n), bits_stride,
+                                                                  msg_table.handle, _midx(msg_idx, n), n, res, cb, None))
+    return bool(bytes(res)[0])
+
+
+def verify_multiple_committee_msgtable_locate_rng(committees, msg_table, sigs, cmt_idx, bits, bits_stride, msg_idx, n, draw, ctx=None):
+    """verify_multiple_committee_msgtable_rng with one answer per set. Returns (bool, set_results, set_status)."""
+    ctx = ctx or committees.ctx
+    res = N.outbuf(1)
+    sres = N.outbuf(max(1, n))
+    sst = (C.c_uint32 * max(1, n))()
+    cb = _scalar_source(draw)
+    ctx.check(N.lib().mbls_verify_multiple_committee_msgtable_locate_rng(ctx.handle, committees.handle, N.cbuf(sigs), _midx(cmt_idx, n), _bits(bits, bits_stride, n),
+                                                                         bits_stride, msg_table.handle, _midx(msg_idx, n), n, res, sres, sst, cb, None))
+    return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:n]], list(sst)[:n]

@@ -3,9 +3,11 @@
 //   lane_aggregate_cmt  one lane per item: the indexed key sum over that list, the complement's fix-up, status  (k_aggregate_cmt_d)
 //   lane_cmt_build      one lane per appended committee: key sum + status of the append -> the committee record  (k_cmt_build)
 //   lane_cmt_export     the cached sum of one committee as 96 uncompressed bytes                                 (k_cmt_export)
+//   wave_vmc_expand     one WAVE per set of a verify_multiple call: committee set or single-key set (mbls_vmc.h)  (k_vmc_expand)
 #pragma once
 #include "mbls_ops.h"
 #include "mbls_cmt.h"
+#include "mbls_vmc.h"
 
 // the per-item words k_cmt_expand leaves for k_aggregate_cmt_d beside the list: cnt[i] entries listed; route[i] bit 0 complement, bit 1 nobody selected
 #define MBLS_CMT_RT_COMPLEMENT 1u
@@ -38,6 +40,19 @@ MBLS_FN void wave_cmt_expand(uint64_t i, uint32_t lane, const uint32_t* crecs, u
         out += cmt_popcount(ballot);
     }
     if (lane == 0) { cnt[i] = out; route[i] = (comp ? MBLS_CMT_RT_COMPLEMENT : 0u) | (s == 0 ? MBLS_CMT_RT_NOBODY : 0u); }
+}
+
+static_assert(MBLS_VMC_RT_COMPLEMENT == MBLS_CMT_RT_COMPLEMENT && MBLS_VMC_RT_NOBODY == MBLS_CMT_RT_NOBODY, "mbls_vmc.h restates the route word");
+// Set i of a verify_multiple call over committees (mbls_vmc.h): a single-key set lists its one key index on the direct route and never touches its bitfield bytes;
+// every other word is an item of the committee entries and runs wave_cmt_expand, unchanged (a bit-31-clear id at or above the count names no committee there).
+MBLS_FN void wave_vmc_expand(uint64_t i, uint32_t lane, const uint32_t* crecs, uint64_t ccount, const uint32_t* members, const uint32_t* cmt_idx, const uint8_t* bits,
+                             uint32_t bits_stride, int mode, uint32_t* list, uint64_t list_stride, uint32_t* cnt, uint32_t* route) {
+    const uint32_t word = cmt_idx[i];
+    if (vmc_is_single(word)) {
+        if (lane == 0) { list[list_stride * i] = vmc_key_index(word); cnt[i] = vmc_single_count(); route[i] = vmc_single_route(); }
+        return;
+    }
+    wave_cmt_expand(i, lane, crecs, ccount, members, cmt_idx, bits, bits_stride, mode, list, list_stride, cnt, route);
 }
 
 #if MBLS_DEVICE_ASM && !defined(MBLS_NO_FP2_ASM)

@@ -138,6 +138,22 @@ __global__ void MBLS_LB k_aggregate_cmt_d(mbls_ws ws, const uint32_t* recs, uint
     if (st) atomicOr(status + i, st);
 #endif
 }
+// verify_multiple over committees (mbls_vmc.h): k_vmc_expand is k_cmt_expand with the single-key sets of a gossip batch beside the committee sets; k_aggregate_vmc_d
+// is k_aggregate_cmt_d's body with the status word cut to what verify_multiple's key phase reports (vmc_key_status: the indexed key sum of those entries flags
+// neither the empty list nor the sum at infinity). A complement set is always a committee set, so cmt_idx[i] is a committee id wherever the body reads it as one.
+__global__ void __launch_bounds__(WG) k_vmc_expand(const uint32_t* crecs, uint64_t ccount, const uint32_t* members, const uint32_t* cmt_idx, const uint8_t* bits,
+                                                   uint32_t bits_stride, int mode, uint32_t* list, uint64_t list_stride, uint32_t* cnt, uint32_t* route, uint64_t n) {
+    const uint64_t i = blockIdx.x; if (i >= n) return;
+    wave_vmc_expand(i, threadIdx.x, crecs, ccount, members, cmt_idx, bits, bits_stride, mode, list, list_stride, cnt, route);
+}
+__global__ void MBLS_LB k_aggregate_vmc_d(mbls_ws ws, const uint32_t* recs, uint64_t tsize, const uint32_t* list, uint64_t list_stride, const uint32_t* cnt,
+                                          const uint32_t* route, const uint32_t* crecs, const uint32_t* cmt_idx, uint32_t* status, uint64_t n) {
+    uint64_t i = gid(); if (i >= n) return;
+#if MBLS_DEVICE_ASM
+    uint32_t st = vmc_key_status(lane_aggregate_cmt(ws, i, threadIdx.x, recs, tsize, list, list_stride, cnt, route, crecs, cmt_idx));
+    if (st) atomicOr(status + i, st);
+#endif
+}
 __global__ void MBLS_LB k_cmt_build(mbls_ws ws, const uint32_t* st, const uint32_t* offsets, uint64_t member_base, uint32_t* crecs, uint64_t n) {
     uint64_t c = gid(); if (c < n) lane_cmt_build(ws, c, st, offsets, member_base, crecs);
 }
@@ -1224,7 +1240,7 @@ __global__ void __launch_bounds__(WG) k_valu_bench(uint32_t* sink, uint32_t iter
 // Host-buffer entries stage through grow-only device buffers and two streams that the context owns (no allocation or stream
 // creation per call once the sizes have been seen); device-pointer entries only enqueue, and order their use of the
 // workspace against earlier calls on other streams with an event.
-#define MBLS_N_STAGE 10
+#define MBLS_N_STAGE 11
 // measured crossovers (scripts/throughput_vs_n.py, 128 keys, device-resident): one wave per item wins up to ~5 k items (10.3 ms at 4 096, ~11.8 at
 // 5 120); the lane path with four lanes per item in the Miller loop and two in the message phase and the final exponentiation (products in pairs)
 // needs 12.2-12.7 ms for anything up to a quarter of a round
@@ -3705,10 +3721,26 @@ static int vm_shared_plan_and_reserve(mbls_ctx* c, vm_shared& sh, uint64_t n) {
     int rc = mbls_ctx_reserve(c, sh.locate ? vsl_workspace_items(n, sh.n_msgs, grouped, sh.sp.list_workspace_items) : sh.vp.workspace_items); if (rc) return rc;
     return reserve_msgs(c, sh.n_msgs);
 }
+// the key source of mbls_verify_multiple_committee_msgtable*: one descriptor word and one bitfield per set (mbls_vmc.h) over a committee table, read at the sizes
+// vm_committee_of found under the context's lock
+struct vm_committee {
+    const mbls_committees* t = nullptr; const mbls_keytable* kt = nullptr;
+    const uint32_t* d_cmt_idx = nullptr; const uint8_t* d_bits = nullptr; uint32_t bits_stride = 0;
+    const uint32_t* d_crecs = nullptr; uint64_t ccount = 0; const uint32_t* d_members = nullptr; uint32_t cmax = 0; const uint32_t* d_recs = nullptr; uint64_t tsize = 0;
+    uint64_t list_stride() const { return cmax ? cmax : 1; }
+};
+// the committee entries' checks (keys_of_committees: one context, key table alive, bits_stride, alignment of device bitfields); the caller holds the context's lock
+static int vm_committee_of(mbls_ctx* c, const mbls_committees* t, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride, bool device_bits, vm_committee* vc) {
+    keysrc ks; const int rk = keys_of_committees(c, t, d_cmt_idx, d_bits, bits_stride, device_bits, &ks); if (rk) return rk;
+    vc->t = t; vc->kt = t->kt; vc->d_cmt_idx = d_cmt_idx; vc->d_bits = d_bits; vc->bits_stride = bits_stride;
+    vc->d_crecs = ks.d_crecs; vc->ccount = ks.ccount; vc->d_members = ks.d_members; vc->cmax = ks.cmax; vc->d_recs = ks.d_recs; vc->tsize = ks.tsize;
+    return MBLS_OK;
+}
 static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_pks, int pk_format,
         const uint32_t* d_pk_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n,
         uint8_t* d_result, uint32_t* d_status_or, void* stream, uint32_t* d_partial = nullptr, const mbls_keytable* tab = nullptr, const uint32_t* d_idx = nullptr,
-        bool sigs_resident = false, bool hash_enqueued = false, vm_shared* sh = nullptr) {
+        bool sigs_resident = false, bool hash_enqueued = false, vm_shared* sh = nullptr, const vm_committee* vc = nullptr) {
+    // vc (the _committee_msgtable entries: sh names a resident message table): the third key source beside tab / d_apks / d_pks, which are then null
     // sigs_resident: k_sig (decode + subgroup test) has run over these signatures on this workspace and the host has seen every one pass: d_sigs is not read.
     // hash_enqueued (batches whose chains run side by side only): the message phase is already on the context's message stream.
     if (!c || (!d_result && !d_partial)) return MBLS_ERR_ARGUMENT;
@@ -3733,6 +3765,12 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
     const bool pair_hash = !sh && n <= c->split_max_items && 2 * n <= c->round_items;
     // a shared list: the workspace (sets, Miller items, positions, the list's own hash) and the table are reserved here, once, before the first kernel
     int rc = sh ? vm_shared_plan_and_reserve(c, *sh, n) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
+    // the committee source: the sets' index lists, count and route words for all n sets, reserved here with the workspace (grow-only: nothing when
+    // mbls_ctx_reserve_committee_items or the first half of an _rng call has been there)
+    if (vc) {
+        if (!(sh && sh->mt) || d_partial) ARGFAIL(c, "internal: the committee source runs over a resident message table only");
+        rc = reserve_committee(c, n, vc->cmax); if (rc) return rc;
+    }
     const bool grouped = sh && sh->vp.route == MBLS_VM_ROUTE_GROUPED;
     const uint64_t n_miller = grouped ? sh->vp.miller_items : n;
     const bool loc = sh && sh->locate;
@@ -3744,6 +3782,7 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
     // stream of the call forks from s behind them, and no fallible step is left once a side stream has work
     const bool over_table = sh && sh->mt;
     if (over_table) { rc = msgtable_acquire(c, sh->mt, s); if (rc) return rc; if (tab) { rc = table_acquire(c, tab, s); if (rc) return rc; } }
+    if (vc) { rc = committees_acquire(c, vc->t, s); if (rc) return rc; rc = table_acquire(c, vc->kt, s); if (rc) return rc; }
     if (loc) {
         HIPCHK(c, hipMemsetAsync(sh->d_set_results, 0, n, s));      // fail closed
         if (sh->d_set_status) HIPCHK(c, hipMemsetAsync(sh->d_set_status, 0, 4 * n, s));
@@ -3768,12 +3807,19 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
         launch_hash(c, ws, d_msgs, msg_len, d_moff, c->d_status, n, s_msg, pair_hash); return MBLS_OK;
     };
     if (hash_first) { rc = message_phase(); if (rc) return rc; }
-    if (tab) {      // sets given by indices into a resident key table: the indexed key sum (the keys were decoded and validated once)
+    if (vc) {       // sets given by committee and bitfield, or by one key index (mbls_vmc.h): every set's list, then the indexed key sum over it with the complement's fix-up
+        const uint64_t ls = vc->list_stride();
+        uint32_t* const cnt = c->d_cmt_cnt; uint32_t* const route = c->d_cmt_cnt + c->cmt_items;
+        hipLaunchKernelGGL(k_vmc_expand, dim3((unsigned)n), dim3(WG), 0, s, vc->d_crecs, vc->ccount, vc->d_members, vc->d_cmt_idx, vc->d_bits, vc->bits_stride, c->cmt_route_mode,
+                           c->d_cmt_list, ls, cnt, route, n);
+        hipLaunchKernelGGL(k_aggregate_vmc_d, dim3(nblk(n)), dim3(WG), 0, s, ws, vc->d_recs, vc->tsize, (const uint32_t*)c->d_cmt_list, ls, (const uint32_t*)cnt, (const uint32_t*)route,
+                           vc->d_crecs, vc->d_cmt_idx, c->d_status, n);
+    } else if (tab) {      // sets given by indices into a resident key table: the indexed key sum (the keys were decoded and validated once)
         if (!over_table) { rc = table_acquire(c, tab, s); if (rc) return rc; }
         hipLaunchKernelGGL(k_aggregate_indexed_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)tab->d_recs, tab->size, d_idx, d_pk_offsets, k, MBLS_MODE_VERIFY, c->d_status, n);
     } else if (!d_apks)    // sets given by their wire-format keys: AggregatePublicKey::aggregate on the device first (src/aggregates.rs:29-39)
         launch_aggregate(ws, d_pks, d_pk_offsets, k, pk_format, MBLS_MODE_VERIFY, c->d_status, n, s);
-    hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, tab ? (const uint8_t*)nullptr : d_apks, d_rands, c->d_status, n);
+    hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, tab || vc ? (const uint8_t*)nullptr : d_apks, d_rands, c->d_status, n);
     // one Miller loop per message: count, scan, scatter and the per-message sums of the blinded keys follow the keys on their stream (beside the list's hash and
     // the signature chain where the chains run side by side); the heads wait for the table further down
     const uint64_t pbase = grouped ? vms_position_base(n, sh->sized_by()) : 0;
@@ -3942,28 +3988,36 @@ extern "C" int mbls_verify_multiple_aggregate_signatures(mbls_ctx* c, const uint
 // tests its signatures (they stay in the workspace), starts the message phase and reads the verdicts back; phase 2 takes the scalars and runs the rest -- up to the
 // bool (d_partial == nullptr) or up to the shard's record. The caller holds the context's lock across both.
 struct vm_rng_stage {
-    sbuf ds, da, dm, dr, dmo, dout, dmi;
+    sbuf ds, da, dm, dr, dmo, dout, dmi, dci;       // (dci: the sets' descriptor words of the committee form, whose bitfields travel in da -- it has no aggregate keys)
     const uint8_t* d_msgs = nullptr; const uint64_t* d_moff = nullptr;
-    vm_rng_stage(mbls_ctx* c) : ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dmo(c, 6), dout(c, 4), dmi(c, 7) {}
+    vm_rng_stage(mbls_ctx* c) : ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dmo(c, 6), dout(c, 4), dmi(c, 7), dci(c, 10) {}
 };
 static void vm_rng_drain(mbls_ctx* c) { (void)hipStreamSynchronize(c->hs_a); (void)hipStreamSynchronize(c->hs_b); (void)hipStreamSynchronize(c->hs_c); c->ws_pending = false; }
 // sigs96 / apks96: the shard's own sets; msgs: the buffer the (absolute) offsets of moff[0 .. n] point into, or n x msg_len bytes. -> MBLS_OK and st[0 .. n) (status words)
 // sh (the shared-message form): msgs / moff describe the sh->n_msgs LISTED messages, msg_idx the sets' indices (uploaded here; sh->d_midx is set)
+// hc / vc (the committee form): apks96 is null; the sets' words and bitfields are uploaded here (vc's device pointers are set) and the list scratch of the whole call
+// is reserved with the workspace
 static int vm_rng_phase1(mbls_ctx* c, vm_rng_stage& g, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, size_t n,
-                         size_t out_bytes, uint32_t* st, vm_shared* sh = nullptr, const uint32_t* msg_idx = nullptr) {
+                         size_t out_bytes, uint32_t* st, vm_shared* sh = nullptr, const uint32_t* msg_idx = nullptr, const host_committees* hc = nullptr,
+                         vm_committee* vc = nullptr) {
     if (hipSetDevice(c->device) != hipSuccess) return MBLS_ERR_DEVICE;
     if (g.dout.alloc(out_bytes) != hipSuccess) return MBLS_ERR_DEVICE;
     if (n == 0) return MBLS_OK;
     const size_t nm = sh ? (size_t)sh->n_msgs : n;                          // messages the buffers describe
     const uint64_t msg_first = moff ? moff[0] : 0;
     const size_t msg_total = moff ? (size_t)(moff[nm] - moff[0]) : (size_t)msg_len * nm;
-    if (g.ds.up(sigs96, 96 * n) != hipSuccess || g.da.up(apks96, 96 * n) != hipSuccess || g.dm.up(msgs ? msgs + msg_first : nullptr, msg_total) != hipSuccess ||
+    if (g.ds.up(sigs96, 96 * n) != hipSuccess || (!hc && g.da.up(apks96, 96 * n) != hipSuccess) || g.dm.up(msgs ? msgs + msg_first : nullptr, msg_total) != hipSuccess ||
         g.dr.alloc(8 * n) != hipSuccess || (moff && g.dmo.up(moff, 8 * (nm + 1)) != hipSuccess)) return MBLS_ERR_DEVICE;
+    if (hc) {
+        if (g.da.up(hc->bits, (size_t)hc->bits_stride * n) != hipSuccess || g.dci.up(hc->cmt_idx, 4 * n) != hipSuccess) return MBLS_ERR_DEVICE;
+        vc->d_bits = g.da.as<uint8_t>(); vc->d_cmt_idx = g.dci.as<uint32_t>();
+    }
     g.d_msgs = g.dm.as<uint8_t>() - msg_first; g.d_moff = moff ? g.dmo.as<uint64_t>() : nullptr;
     if (sh) { if (g.dmi.up(msg_idx, 4 * n) != hipSuccess) return MBLS_ERR_DEVICE; sh->d_midx = g.dmi.as<uint32_t>(); }
     hipStream_t s = c->hs_a;
     const bool pair_hash = !sh && n <= c->split_max_items && 2 * n <= c->round_items, fork = 2 * n <= c->round_items;       // as verify_multiple_impl decides
     int rc = sh ? vm_shared_plan_and_reserve(c, *sh, n) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
+    if (vc) { rc = reserve_committee(c, n, vc->cmax); if (rc) return rc; }
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     rc = ws_acquire(c, s); if (rc) return rc;
     if (sh && sh->mt) { rc = msgtable_acquire(c, sh->mt, s); if (rc) return rc; }      // (before the fork: the message stream inherits the table's last append)
@@ -3978,11 +4032,11 @@ static int vm_rng_phase1(mbls_ctx* c, vm_rng_stage& g, const uint8_t* sigs96, co
     return MBLS_OK;
 }
 // rands[0 .. n): the shard's scalars. d_partial == false: the bool is left in g.dout (1 byte); true: the shard's record (MBLS_VM_PARTIAL_BYTES). Enqueues on hs_a.
-static int vm_rng_phase2(mbls_ctx* c, vm_rng_stage& g, uint32_t msg_len, const uint64_t* rands, size_t n, bool partial, vm_shared* sh = nullptr) {
+static int vm_rng_phase2(mbls_ctx* c, vm_rng_stage& g, uint32_t msg_len, const uint64_t* rands, size_t n, bool partial, vm_shared* sh = nullptr, const vm_committee* vc = nullptr) {
     if (hipSetDevice(c->device) != hipSuccess) return MBLS_ERR_DEVICE;
     if (n && g.dr.up(rands, 8 * n) != hipSuccess) return MBLS_ERR_DEVICE;
-    return verify_multiple_impl(c, nullptr, g.da.as<uint8_t>(), nullptr, 0, nullptr, 0, g.d_msgs, msg_len, g.d_moff, g.dr.as<uint64_t>(), n, partial ? nullptr : g.dout.as<uint8_t>(),
-                                nullptr, c->hs_a, partial ? g.dout.as<uint32_t>() : nullptr, nullptr, nullptr, true, true, sh);
+    return verify_multiple_impl(c, nullptr, vc ? nullptr : g.da.as<uint8_t>(), nullptr, 0, nullptr, 0, g.d_msgs, msg_len, g.d_moff, g.dr.as<uint64_t>(), n,
+                                partial ? nullptr : g.dout.as<uint8_t>(), nullptr, c->hs_a, partial ? g.dout.as<uint32_t>() : nullptr, nullptr, nullptr, true, true, sh, vc);
 }
 extern "C" int mbls_verify_multiple_aggregate_signatures_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs,
         uint32_t msg_len, const uint64_t* moff, size_t n, mbls_scalar_source draw, void* user) {
@@ -4064,9 +4118,10 @@ static int vm_shared_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_
 // names an entry of the table. -> the longest group and the number of distinct entries named, counted on a sorted copy of the indices (the table may be far
 // larger than the call)
 static int vm_msgtable_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint64_t* longest,
-                                  uint64_t* named) {
+                                  uint64_t* named, bool keys_elsewhere = false) {
+    // keys_elsewhere (the committee form): the sets have no aggregate keys, apks96 is null
     if (n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
-    if (!sigs96 || !apks96 || !msg_idx) ARGFAIL(c, "null buffer");
+    if (!sigs96 || (!apks96 && !keys_elsewhere) || !msg_idx) ARGFAIL(c, "null buffer");
     for (uint64_t i = 0; i < n; i++)
         if (mtb_names_nothing(msg_idx[i], mt->size)) ARGFAIL(c, "msg_idx names no entry of the message table");
     std::vector<uint32_t> idx;
@@ -4126,16 +4181,26 @@ extern "C" int mbls_verify_multiple_shared_msgs(mbls_ctx* c, const uint8_t* sigs
 // changes nothing -- as mbls_verify_multiple_batches_locate_rng does.
 static int vm_shared_rng_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
         uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user, bool locate, uint8_t* set_results, uint32_t* set_status,
-        const mbls_msgtable* mt = nullptr) {
+        const mbls_msgtable* mt = nullptr, const host_committees* hc = nullptr) {
     // mt (the _msgtable entries): msg_idx holds indices into the resident table, no list (msgs / moff NULL, msg_len = n_msgs = 0); the host counts the named entries
+    // hc (the _committee_msgtable entries, over mt): the sets' keys by descriptor word and bitfield (mbls_vmc.h) in host memory, apks96 null; a word that names
+    // nothing refuses the call
     if (!c || !result) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
     if (locate && !set_results) ARGFAIL(c, "null set results");
     if (mt && mt->c != c) ARGFAIL(c, "message table belongs to another context");
+    vm_committee vcs; vm_committee* const vc = hc ? &vcs : nullptr;
+    if (hc) { const int rk = vm_committee_of(c, hc->t, nullptr, nullptr, hc->bits_stride, false, vc); if (rk) return rk; }
     if (n == 0) { *result = 1; return MBLS_OK; }                            // empty iterator: true, the generator untouched
     if (!draw) ARGFAIL(c, "no scalar source");
     vm_shared sh; sh.n_msgs = n_msgs; sh.mt = mt;
-    int rc = mt ? vm_msgtable_host_check(c, sigs96, apks96, mt, msg_idx, n, &sh.longest, &sh.named)
+    if (hc) {
+        if (!hc->cmt_idx || !hc->bits) ARGFAIL(c, "null buffer");
+        for (uint64_t i = 0; i < n; i++)
+            if (vmc_names_nothing(hc->cmt_idx[i], vc->ccount, vc->tsize))
+                ARGFAIL(c, vmc_is_single(hc->cmt_idx[i]) ? "cmt_idx names no key of the key table" : "cmt_idx names no committee of the table");
+    }
+    int rc = mt ? vm_msgtable_host_check(c, sigs96, apks96, mt, msg_idx, n, &sh.longest, &sh.named, hc != nullptr)
                 : vm_shared_host_check(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, n, &sh.longest); if (rc) return rc;
     std::vector<uint64_t> rands; std::vector<uint32_t> st;
     try { rands.resize(n); st.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
@@ -4146,14 +4211,14 @@ static int vm_shared_rng_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t*
         HIPCHK(c, dset.alloc(5 * n));
         sh.locate = true; sh.d_set_status = dset.as<uint32_t>(); sh.d_set_results = dset.as<uint8_t>() + 4 * n;
     }
-    rc = vm_rng_phase1(c, g, sigs96, apks96, msgs, msg_len, moff, n, 8, st.data(), &sh, msg_idx); if (rc) return rc;
+    rc = vm_rng_phase1(c, g, sigs96, apks96, msgs, msg_len, moff, n, 8, st.data(), &sh, msg_idx, hc, vc); if (rc) return rc;
     size_t reached = n;                                                     // the sets the reference's loop draws a scalar for
     for (size_t i = 0; i < n; i++)
         if (st[i] & (MBLS_ST_BAD_SIG_ENCODING | MBLS_ST_SIG_NOT_IN_G2)) { reached = i; break; }
     if (reached) draw(user, rands.data(), (uint64_t)reached);
     if (reached < n && !locate) { vm_rng_drain(c); *result = 0; return MBLS_OK; }     // src/aggregates.rs:273-275
     for (size_t i = reached; i < n; i++) rands[i] = 1;
-    rc = vm_rng_phase2(c, g, msg_len, rands.data(), n, false, &sh);
+    rc = vm_rng_phase2(c, g, msg_len, rands.data(), n, false, &sh, vc);
     std::fill(rands.begin(), rands.end(), 0);
     if (rc) { vm_rng_drain(c); return rc; }
     if (hipStreamSynchronize(c->hs_a) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
@@ -4239,6 +4304,48 @@ extern "C" int mbls_verify_multiple_msgtable_locate_rng(mbls_ctx* c, const uint8
         uint8_t* result, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user) {
     if (!mt) return MBLS_ERR_ARGUMENT;
     return vm_shared_rng_impl(c, sigs96, apks96, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, true, set_results, set_status, mt);
+}
+
+// ---- verify_multiple over committee bitfields and the resident message table (include/mbls.h, mbls_verify_multiple_committee_msgtable*; the set descriptor is
+// mbls_vmc.h): the _sets_indexed_msgtable entries with every set's signers named by a committee id and its bitfield, or by one key index -- verify_multiple_impl's
+// third key source (k_vmc_expand, k_aggregate_vmc_d); everything behind the key sum is the entries' above.
+static int vm_committee_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride,
+                               const mbls_msgtable* mt, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status_or, void* stream,
+                               bool locate, uint8_t* d_set_results, uint32_t* d_set_status) {
+    if (!c || !t || !mt || !d_result) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
+    if (locate && !d_set_results) ARGFAIL(c, "null set results");
+    vm_committee vc; const int rk = vm_committee_of(c, t, d_cmt_idx, d_bits, bits_stride, true, &vc); if (rk) return rk;
+    if (n && (!d_cmt_idx || !d_bits)) ARGFAIL(c, "null key buffer");
+    if (n && !d_midx) ARGFAIL(c, "null buffer");
+    if (n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
+    vm_shared sh; sh.d_midx = d_midx; sh.mt = mt; sh.locate = locate; sh.d_set_results = d_set_results; sh.d_set_status = d_set_status;
+    return verify_multiple_impl(c, d_sigs, nullptr, nullptr, MBLS_PK_UNCOMPRESSED, nullptr, 0, nullptr, 0, nullptr, d_rands, n, d_result, d_status_or, stream, nullptr, nullptr,
+                                nullptr, false, false, &sh, &vc);
+}
+extern "C" int mbls_verify_multiple_committee_msgtable_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx, const uint8_t* d_bits,
+        uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream) {
+    return vm_committee_device(c, t, d_sigs, d_cmt_idx, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_result, d_status, stream, false, nullptr, nullptr);
+}
+extern "C" int mbls_verify_multiple_committee_msgtable_locate_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx,
+        const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result,
+        uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
+    if (!d_set_results) return MBLS_ERR_ARGUMENT;
+    return vm_committee_device(c, t, d_sigs, d_cmt_idx, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_result, d_status, stream, true, d_set_results, d_set_status);
+}
+extern "C" int mbls_verify_multiple_committee_msgtable_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_idx, const uint8_t* bits,
+        uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user) {
+    if (!t || !mt) return MBLS_ERR_ARGUMENT;
+    const host_committees hc = {t, cmt_idx, bits, bits_stride};
+    return vm_shared_rng_impl(c, sigs96, nullptr, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, false, nullptr, nullptr, mt, &hc);
+}
+extern "C" int mbls_verify_multiple_committee_msgtable_locate_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_idx, const uint8_t* bits,
+        uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint8_t* result, uint8_t* set_results, uint32_t* set_status,
+        mbls_scalar_source draw, void* user) {
+    if (!t || !mt) return MBLS_ERR_ARGUMENT;
+    const host_committees hc = {t, cmt_idx, bits, bits_stride};
+    return vm_shared_rng_impl(c, sigs96, nullptr, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, true, set_results, set_status, mt, &hc);
 }
 
 // ---- B independent verify_multiple batches in ONE call (include/mbls.h, mbls_verify_multiple_batches*): what B consecutive calls of the entries above return,

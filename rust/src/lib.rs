@@ -213,6 +213,19 @@ extern "C" {
                                                                 d_status: *mut u32, d_set_results: *mut u8, d_set_status: *mut u32, stream: *mut c_void) -> c_int;
     fn mbls_verify_multiple_msgtable_locate_rng(ctx: *mut MblsCtx, sigs96: *const u8, apks96: *const u8, mt: *const mbls_msgtable, msg_idx: *const u32, n: u64,
                                                 result: *mut u8, set_results: *mut u8, set_status: *mut u32, draw: MblsScalarSource, user: *mut c_void) -> c_int;
+    // verify_multiple over committee bitfields and the resident message table: a set is a committee id with its bitfield, or MBLS_VM_SET_SINGLE_KEY | key index
+    fn mbls_verify_multiple_committee_msgtable_device(ctx: *mut MblsCtx, committees: *const mbls_committees, d_sigs96: *const u8, d_cmt_idx: *const u32, d_bits: *const u8,
+                                                      bits_stride: u32, mt: *const mbls_msgtable, d_msg_idx: *const u32, d_rands: *const u64, n: u64, d_result: *mut u8,
+                                                      d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_committee_msgtable_locate_device(ctx: *mut MblsCtx, committees: *const mbls_committees, d_sigs96: *const u8, d_cmt_idx: *const u32,
+                                                             d_bits: *const u8, bits_stride: u32, mt: *const mbls_msgtable, d_msg_idx: *const u32, d_rands: *const u64, n: u64,
+                                                             d_result: *mut u8, d_status: *mut u32, d_set_results: *mut u8, d_set_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_committee_msgtable_rng(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs96: *const u8, cmt_idx: *const u32, bits: *const u8,
+                                                   bits_stride: u32, mt: *const mbls_msgtable, msg_idx: *const u32, n: u64, result: *mut u8, draw: MblsScalarSource,
+                                                   user: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_committee_msgtable_locate_rng(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs96: *const u8, cmt_idx: *const u32, bits: *const u8,
+                                                          bits_stride: u32, mt: *const mbls_msgtable, msg_idx: *const u32, n: u64, result: *mut u8, set_results: *mut u8,
+                                                          set_status: *mut u32, draw: MblsScalarSource, user: *mut c_void) -> c_int;
     fn mbls_stream_create_msgtable(ctx: *mut MblsCtx, mode: c_int, pk_format: c_int, t: *const MblsKeyTable, mt: *mut mbls_msgtable, opts: *const mbls_stream_opts,
                                    out: *mut *mut mbls_stream) -> c_int;
     fn mbls_stream_submit_msgidx(s: *mut mbls_stream, sigs: *const u8, msg_idx: *const u32, pks: *const u8, key_idx: *const u32, pk_offsets: *const u32, n: u64, k: u32,
@@ -1545,6 +1558,83 @@ impl CommitteeTable {
         res.truncate(n);
         res.into_iter().map(|b| b == 1).collect()
     }
+    /// `AggregateSignature::verify_multiple_aggregate_signatures` over a gossip batch whose keys and messages are resident
+    /// (`mbls_verify_multiple_committee_msgtable_rng`): every set is a signature, a `GossipKeys` -- a committee of this table with its participation bits, or ONE
+    /// key of the key table the committees are bound to -- and an entry index of `table`. The same bool as that function on the spelled-out aggregate keys and
+    /// messages, `rng` left in the same state. A committee id, key index or entry index that names nothing gives false.
+    pub fn verify_multiple_aggregate_signatures<'a, R, I>(&self, rng: &mut R, signature_sets: I, table: &MessageTable) -> bool
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, GossipKeys<'a>, u32)>,
+    {
+        self.vm_committee(rng, signature_sets, table, false).0
+    }
+    /// The same, and in the same call (`mbls_verify_multiple_committee_msgtable_locate_rng`) which sets of a rejected call are the bad ones, with the semantics of
+    /// `AggregateSignature::verify_multiple_aggregate_signatures_shared_msgs_locate`.
+    pub fn verify_multiple_aggregate_signatures_locate<'a, R, I>(&self, rng: &mut R, signature_sets: I, table: &MessageTable) -> (bool, Vec<bool>)
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, GossipKeys<'a>, u32)>,
+    {
+        self.vm_committee(rng, signature_sets, table, true)
+    }
+    fn vm_committee<'a, R, I>(&self, rng: &mut R, signature_sets: I, table: &MessageTable, locate: bool) -> (bool, Vec<bool>)
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, GossipKeys<'a>, u32)>,
+    {
+        let sets: Vec<(&AggregateSignature, GossipKeys, u32)> = signature_sets.collect();
+        let n = sets.len();
+        if n == 0 {
+            return (true, Vec::new());
+        }
+        let mut sigs = Vec::new();
+        let (mut words, mut idx): (Vec<u32>, Vec<u32>) = (Vec::with_capacity(n), Vec::with_capacity(n));
+        let mut fields: Vec<&[u8]> = Vec::with_capacity(n);
+        for (s, k, j) in &sets {
+            sigs.extend_from_slice(&s.point);
+            match *k {
+                GossipKeys::Committee { id, bits } => {
+                    assert!(id & VM_SET_SINGLE_KEY == 0, "committee ids have 31 bits");
+                    words.push(id);
+                    fields.push(bits);
+                }
+                GossipKeys::SingleKey(index) => {
+                    assert!(index & VM_SET_SINGLE_KEY == 0, "key indices have 31 bits");
+                    words.push(VM_SET_SINGLE_KEY | index);
+                    fields.push(&[]);
+                }
+            }
+            idx.push(*j);
+        }
+        let (flat, stride) = self.flatten_bits(&fields);
+        let mut st = DrawState { rng, panic: None };
+        let mut ok: u8 = 0;
+        let mut sres: Vec<u8> = vec![0; if locate { n } else { 0 }];
+        let rc = unsafe {
+            if locate {
+                mbls_verify_multiple_committee_msgtable_locate_rng(ctx(), self.h, sigs.as_ptr(), words.as_ptr(), flat.as_ptr(), stride, table.h, idx.as_ptr(), n as u64, &mut ok,
+                                                                   sres.as_mut_ptr(), std::ptr::null_mut(), draw_scalars::<R>, &mut st as *mut DrawState<R> as *mut c_void)
+            } else {
+                mbls_verify_multiple_committee_msgtable_rng(ctx(), self.h, sigs.as_ptr(), words.as_ptr(), flat.as_ptr(), stride, table.h, idx.as_ptr(), n as u64, &mut ok,
+                                                            draw_scalars::<R>, &mut st as *mut DrawState<R> as *mut c_void)
+            }
+        };
+        if let Some(payload) = st.panic.take() {
+            std::panic::resume_unwind(payload);
+        }
+        (rc == 0 && ok == 1, sres.iter().map(|&b| rc == 0 && b == 1).collect())
+    }
+}
+/// `MBLS_VM_SET_SINGLE_KEY` of include/mbls.h: bit 31 of a set's descriptor word marks a set under one key of the key table.
+pub const VM_SET_SINGLE_KEY: u32 = 0x8000_0000;
+/// The keys of one set of `CommitteeTable::verify_multiple_aggregate_signatures`.
+#[derive(Clone, Copy)]
+pub enum GossipKeys<'a> {
+    /// the members of committee `id` whose bit is set in `bits` (SSZ bit order; bits at or above the committee's size are ignored)
+    Committee { id: u32, bits: &'a [u8] },
+    /// entry `index` of the key table the committee table is bound to: a selection proof, an aggregator's signature, an unaggregated attestation
+    SingleKey(u32),
 }
 impl Drop for CommitteeTable {
     fn drop(&mut self) {
