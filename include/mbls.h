@@ -381,6 +381,59 @@ int mbls_fast_aggregate_verify_batch_committee_msgtable(mbls_ctx* ctx, const mbl
                                                         const uint32_t* msg_idx, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_stride, uint64_t n,
                                                         uint8_t* results, uint32_t* status);
 
+/* ---- committee spans: fast_aggregate_verify over several committees per item -------------------------------
+ * Since Electra (EIP-7549) an on-chain attestation names up to 64 committees of its slot (committee_bits) and carries ONE bitfield, the concatenation of those
+ * committees' participation bits (aggregation_bits), under one signature over one signing root. The committee entries above serve one committee per item; these
+ * entries serve the span, without the caller expanding the field into uint32 indices (about 128 KB per item at mainnet sizes against 4 KB of bits) and without
+ * the device adding every one of those keys.
+ * ITEM. Item i names the committees c_0 .. c_(q-1) = cmt_ids[cmt_off[i] .. cmt_off[i + 1]) of `committees` -- cmt_off holds n + 1 ABSOLUTE offsets into the
+ *   n_cmt_ids ids, like the offsets of a ragged key table --, q <= MBLS_SPAN_MAX_COMMITTEES; an id may appear more than once. With m_t the size of c_t,
+ *   o_t = m_0 + ... + m_(t-1) and M = o_q, member j of c_t is selected when bit o_t + j of the bits_stride bytes at bits + bits_stride * i is set (SSZ bit order,
+ *   as above). Bits at or above M are IGNORED: a Bitlist's delimiter may stay. 8 * bits_stride >= M is required of every item; bits_stride is a multiple of 4, and
+ *   d_bits of the device entries is 4-byte aligned.
+ * KEY SUM. Every segment takes its own route, from the SAME function as the committee entries (csrc/mbls_cmt.h cmt_route(m_t, s_t, eligible_t, mode), under
+ *   mbls_ctx_set_committee_route). The item's key sum is the sum of the selected members of its direct segments plus, for every complement segment, the cached
+ *   sum of c_t minus the sum of its missing members.
+ *   results[i], the bitmap and status[i] are bit for bit what mbls_fast_aggregate_verify_batch_indexed[_msgtable] returns for the same signature and message with
+ *   the selected members spelled out in (segment, member) order -- on every mix of routes, under all three route modes: MBLS_ST_NO_KEYS exactly when no member of
+ *   the whole item is selected (q = 0 included), MBLS_ST_APK_INFINITY from the final point, MBLS_ST_PK_INFINITY / MBLS_ST_BAD_PK_ENCODING only as the direct
+ *   segments of ineligible committees produce them. A span of one committee returns exactly the _committee[_msgtable] entry's outputs.
+ * MALFORMED ITEMS: an id at or above the table's count, q > 64, cmt_off[i + 1] < cmt_off[i], cmt_off[i + 1] > n_cmt_ids, or M > 8 * bits_stride. DEVICE entries
+ *   reject such an item like an item that lists the one key index 0xFFFFFFFF (the committee entries' convention, the same words: MBLS_ST_BAD_PK_ENCODING among its
+ *   bits, result 0), and read nothing outside cmt_ids, the item's field or the table: the offsets are checked before the ids, the ids before the records, M before
+ *   the field. HOST entries refuse the call with MBLS_ERR_ARGUMENT before anything is enqueued and leave the outputs unwritten. n = 0 is MBLS_OK.
+ * ROUTING of the batch is mbls_plan_batch(limits, n), the workspace mbls_plan_workspace_items(limits, n, 0, 0): the span form adds no workspace item.
+ * ALLOCATION. k_cms_expand leaves two lists per item -- the selected members of direct segments, the missing members of complement segments -- in one region of
+ *   stride = min(8 * bits_stride, 64 * mbls_committees_max_members) uint32 (they never exceed M entries together and grow from its two ends), a record of 5 words
+ *   and a parked point of 36 words. A call reserves this for the extent of its plan before it queues anything: 4 * stride + 164 bytes per item of a round. This is
+ *   LARGE at mainnet sizes: with bits_stride = 4 096 a full round of 65 536 items takes 8 GiB; size bits_stride to the attestations at hand (64 committees of 128
+ *   members need 1 024 bytes: 2 GiB per round) or lower mbls_ctx_set_round_items. An allocation that fails is MBLS_ERR_DEVICE, nothing enqueued.
+ *   mbls_ctx_reserve_committee_span_items(ctx, max_items, max_item_members) beforehand keeps the allocation out of the call (max_item_members: the stride, at most
+ *   64 * MBLS_COMMITTEE_MAX_MEMBERS). mbls_ctx_reserve_committee_items and its limit are unchanged.
+ * mbls_plan_committee_span states, without a GPU, what the kernel decides for one item from the same header functions (csrc/mbls_cms.h): sizes[t] and eligible[t]
+ *   of the q segments, the item's field (bits_bytes bytes, any alignment) and the route mode in; the mask of the segments that go complement (bit t: segment t)
+ *   and the entries of the direct and of the missing list out. MBLS_ERR_ARGUMENT for q > 64, a size of 0 or above MBLS_COMMITTEE_MAX_MEMBERS, M > 8 * bits_bytes,
+ *   a mode outside 0..2 or a null output.
+ * OUT OF SCOPE: verify_multiple over spans, the verification stream, the shared-list message form, the mbls_multi handle. */
+#define MBLS_SPAN_MAX_COMMITTEES 64
+int mbls_fast_aggregate_verify_batch_committee_span_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs, const uint8_t* d_msgs,
+                                                           uint32_t msg_len, const uint64_t* d_msg_offsets, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids,
+                                                           const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride, uint64_t n, uint8_t* d_results,
+                                                           uint64_t* d_bitmap, uint32_t* d_status, void* stream);
+int mbls_fast_aggregate_verify_batch_committee_span(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
+                                                    const uint64_t* msg_offsets, const uint32_t* cmt_ids, uint64_t n_cmt_ids, const uint32_t* cmt_off,
+                                                    const uint8_t* bits, uint32_t bits_stride, uint64_t n, uint8_t* results, uint32_t* status);
+int mbls_fast_aggregate_verify_batch_committee_span_msgtable_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs, const mbls_msgtable* mt,
+                                                                    const uint32_t* d_msg_idx, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids,
+                                                                    const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride, uint64_t n,
+                                                                    uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream);
+int mbls_fast_aggregate_verify_batch_committee_span_msgtable(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs, const mbls_msgtable* mt,
+                                                             const uint32_t* msg_idx, const uint32_t* cmt_ids, uint64_t n_cmt_ids, const uint32_t* cmt_off,
+                                                             const uint8_t* bits, uint32_t bits_stride, uint64_t n, uint8_t* results, uint32_t* status);
+int mbls_ctx_reserve_committee_span_items(mbls_ctx* ctx, uint64_t max_items, uint32_t max_item_members);
+int mbls_plan_committee_span(const uint32_t* sizes, const uint8_t* eligible, uint32_t q, const uint8_t* bits, uint32_t bits_bytes, int mode,
+                             uint64_t* complement_mask, uint32_t* n_direct_listed, uint32_t* n_missing_listed);
+
 /* ---- verification stream: many small calls packed into full rounds ---------------------------------------
  * The verification entries run at their full rate only when one call carries a whole round (CUs x 4 x 64 items, 65 536 on MI355X). A
  * stream takes calls of ANY size, hands back a ticket per call, packs the items of many calls back to back into full-round launches of
@@ -903,7 +956,7 @@ int mbls_verify_multiple_msgtable_locate_rng(mbls_ctx* ctx, const uint8_t* sigs9
  * PLANNING. Routing and workspace are mbls_plan_verify_multiple_msgtable, _workspace_items and _locate_workspace_items, UNCHANGED: the committee source adds
  * no workspace item (its scratch is the committee entries').
  * OUT OF SCOPE: the verification stream, the shared-list and per-set message forms over committees, mbls_verify_multiple_batches over committees, the mbls_multi
- * handle and the shard form, sets that span several committees, a device-pointer append. */
+ * handle and the shard form, a device-pointer append. (fast_aggregate_verify over sets that span several committees: "committee spans" above.) */
 #define MBLS_VM_SET_SINGLE_KEY 0x80000000u
 int mbls_verify_multiple_committee_msgtable_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96, const uint32_t* d_cmt_idx,
                                                    const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx,

@@ -653,6 +653,38 @@ public:
         return a;
     }
     void clear() { detail::check(mbls_committees_clear(h_)); }
+    // AggregateSignature::fast_aggregate_verify over attestations that span several committees (mbls_fast_aggregate_verify_batch_committee_span_msgtable): an
+    // Electra attestation names the committees of its committee_bits, in order, and carries aggregation_bits -- the concatenation of their participation bits, as
+    // serialized by SSZ (a Bitlist's delimiter may stay) -- under one signature over one entry of `table`. One bool per item: what fast_aggregate_verify gives on
+    // the selected members spelled out. More than MBLS_SPAN_MAX_COMMITTEES ids, an id that names no committee, a field shorter than the committees' members or an
+    // entry index that names nothing throws (DeviceError). status, when given, receives the items' MBLS_ST_* words.
+    struct SpanItem { const AggregateSignature* signature; std::vector<uint32_t> committee_ids; Bytes aggregation_bits; uint32_t msg_index; };
+    std::vector<bool> fast_aggregate_verify_spans(const std::vector<SpanItem>& items, const MessageTable& table, std::vector<uint32_t>* status = nullptr) const {
+        const size_t n = items.size();
+        if (status) status->assign(n, 0);
+        if (!n) return {};
+        size_t widest = 1;
+        for (const auto& it : items) widest = std::max(widest, it.aggregation_bits.size());
+        const uint32_t stride = uint32_t((widest + 3) / 4 * 4);                         // one stride for every field, a multiple of 4
+        Bytes sigs, flat(size_t(stride) * n, 0); std::vector<uint32_t> ids, off{0}, idx, st(n, 0);
+        for (size_t i = 0; i < n; i++) {
+            const SpanItem& it = items[i];
+            sigs.insert(sigs.end(), it.signature->point.begin(), it.signature->point.end());
+            std::copy(it.aggregation_bits.begin(), it.aggregation_bits.end(), flat.begin() + size_t(stride) * i);
+            ids.insert(ids.end(), it.committee_ids.begin(), it.committee_ids.end());
+            if (ids.size() > 0xFFFFFFFFull) throw std::invalid_argument("fast_aggregate_verify_spans: span offsets are 32-bit");
+            off.push_back(uint32_t(ids.size())); idx.push_back(it.msg_index);
+        }
+        const uint64_t n_ids = ids.size();
+        if (ids.empty()) ids.push_back(0);
+        std::vector<uint8_t> res(n, 0);
+        detail::check(mbls_fast_aggregate_verify_batch_committee_span_msgtable(detail::ctx(), h_, sigs.data(), table.handle(), idx.data(), ids.data(), n_ids, off.data(),
+                                                                               flat.data(), stride, n, res.data(), st.data()));
+        if (status) *status = st;
+        std::vector<bool> out(n);
+        for (size_t i = 0; i < n; i++) out[i] = res[i] != 0;
+        return out;
+    }
     // AggregateSignature::verify_multiple_aggregate_signatures over a gossip batch whose keys and messages are resident (mbls_verify_multiple_committee_msgtable_rng).
     // A set is a signature, an entry of `table` and either a committee of this table with the participation bits as serialized by SSZ (GossipSet::aggregate) or ONE
     // key of the key table the committees are bound to (GossipSet::single_key: a selection proof, an aggregator's signature, an unaggregated attestation). The same

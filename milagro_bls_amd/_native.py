@@ -281,6 +281,12 @@ SIGNATURES = {
     "mbls_fast_aggregate_verify_batch_committee": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp]),
     "mbls_fast_aggregate_verify_batch_committee_msgtable_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp]),
     "mbls_fast_aggregate_verify_batch_committee_msgtable": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_committee_span_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_committee_span": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint64, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_committee_span_msgtable_device": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp]),
+    "mbls_fast_aggregate_verify_batch_committee_span_msgtable": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint64, vp, vp]),
+    "mbls_ctx_reserve_committee_span_items": (C.c_int, [vp, C.c_uint64, C.c_uint32]),
+    "mbls_plan_committee_span": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mbls_aggregate_signatures_batch": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
     "mbls_aggregate_signatures_batch_device": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp, vp]),
     "mbls_pk_from_bytes": (C.c_int, [vp, vp, C.c_size_t, vp]),
@@ -470,6 +476,10 @@ class Context:
         """the scratch of the committee entries for batches of up to max_items items over committees of up to max_members members"""
         self.check(lib().mbls_ctx_reserve_committee_items(self._h, max_items, max_members))
 
+    def reserve_committee_span_items(self, max_items, max_item_members):
+        """the scratch of the committee-span entries for batches of up to max_items items whose list regions take max_item_members words each"""
+        self.check(lib().mbls_ctx_reserve_committee_span_items(self._h, max_items, max_item_members))
+
     def set_committee_route(self, mode):
         """committee entries: CMT_ROUTE_AUTO / CMT_ROUTE_DIRECT / CMT_ROUTE_COMPLEMENT"""
         self.check(lib().mbls_ctx_set_committee_route(self._h, mode))
@@ -618,6 +628,28 @@ def plan_committee_route(m, s, eligible=True, mode=CMT_ROUTE_AUTO):
     if rc not in (0, 1):
         raise MblsError(rc, "mbls_plan_committee_route")
     return bool(rc)
+
+
+SPAN_MAX_COMMITTEES = 64        # include/mbls.h MBLS_SPAN_MAX_COMMITTEES
+
+
+def plan_committee_span(sizes, eligible, bits, mode=CMT_ROUTE_AUTO):
+    """what the span kernel decides for one item (pure: no GPU): segment t has sizes[t] members and is eligible[t]; `bits` is the item's field (bytes, SSZ bit
+    order) -> (complement mask: bit t set when segment t takes the complement route, entries of the direct list, entries of the missing list)"""
+    q = len(sizes)
+    if len(eligible) != q:
+        raise ValueError("one eligible flag per segment")
+    bits = bytes(bits)
+    for s in sizes:
+        if not 0 <= s <= 0xFFFFFFFF:
+            raise ValueError("segment sizes are uint32")
+    sz = (C.c_uint32 * max(1, q))(*sizes)
+    el = (C.c_uint8 * max(1, q))(*[1 if e else 0 for e in eligible])
+    mask, nd, nm = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0)
+    rc = lib().mbls_plan_committee_span(sz, el, q, cbuf(bits) if bits else None, len(bits), mode, C.byref(mask), C.byref(nd), C.byref(nm))
+    if rc != 0:
+        raise MblsError(rc, "mbls_plan_committee_span")
+    return int(mask.value), int(nd.value), int(nm.value)
 
 
 class CommitteeTable:

@@ -148,6 +148,50 @@ def fast_aggregate_verify_batch_committee_msgtable(committees, msg_table, sigs, 
     return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
 
 
+def _span(cmt_id_lists, fields, bits_stride):
+    """a list of id lists and one bitfield per item -> (ids, n_ids, absolute offsets, the fields padded to bits_stride bytes each)"""
+    if len(cmt_id_lists) != len(fields):
+        raise ValueError("one id list and one bitfield per item")
+    ids, off = [], [0]
+    for l in cmt_id_lists:
+        ids.extend(l)
+        off.append(len(ids))
+    buf = bytearray()
+    for f in fields:
+        f = bytes(f)
+        if len(f) > bits_stride:
+            raise ValueError("a bitfield of %d bytes does not fit bits_stride = %d" % (len(f), bits_stride))
+        buf += f + bytes(bits_stride - len(f))
+    return (C.c_uint32 * max(1, len(ids)))(*ids), len(ids), (C.c_uint32 * len(off))(*off), N.cbuf(bytes(buf))
+
+
+def fast_aggregate_verify_batch_committee_span(committees, sigs, msgs, cmt_id_lists, fields, bits_stride, msg_len=32, ctx=None, msg_offsets=None):
+    """fast_aggregate_verify_batch over spans of committees (include/mbls.h, "committee spans"): item i names the committees cmt_id_lists[i] (at most
+    N.SPAN_MAX_COMMITTEES) and fields[i] is ONE bitfield over their concatenated members (SSZ bit order; an Electra attestation's aggregation_bits; shorter fields
+    are zero-padded to bits_stride bytes, a multiple of 4). Same (results, status) as fast_aggregate_verify_batch_indexed with the selected members spelled out in
+    (segment, member) order; a malformed item raises (MBLS_ERR_ARGUMENT)."""
+    ctx = ctx or committees.ctx
+    n = len(cmt_id_lists)
+    ids, n_ids, off, bits = _span(cmt_id_lists, fields, bits_stride)
+    res = N.outbuf(n)
+    st = (C.c_uint32 * max(1, n))()
+    ctx.check(N.lib().mbls_fast_aggregate_verify_batch_committee_span(ctx.handle, committees.handle, N.cbuf(sigs), N.cbuf(msgs), msg_len, _moff(msg_offsets), ids, n_ids,
+                                                                      off, bits, bits_stride, n, res, st))
+    return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
+
+
+def fast_aggregate_verify_batch_committee_span_msgtable(committees, msg_table, sigs, msg_idx, cmt_id_lists, fields, bits_stride, ctx=None):
+    """The same with the messages by message-table index."""
+    ctx = ctx or committees.ctx
+    n = len(cmt_id_lists)
+    ids, n_ids, off, bits = _span(cmt_id_lists, fields, bits_stride)
+    res = N.outbuf(n)
+    st = (C.c_uint32 * max(1, n))()
+    ctx.check(N.lib().mbls_fast_aggregate_verify_batch_committee_span_msgtable(ctx.handle, committees.handle, N.cbuf(sigs), msg_table.handle, _midx(msg_idx, n), ids,
+                                                                               n_ids, off, bits, bits_stride, n, res, st))
+    return [bool(x) for x in bytes(res)[:n]], list(st)[:n]
+
+
 def set_committee_route(mode, ctx=None):
     """committee entries: N.CMT_ROUTE_AUTO (complement when eligible and cheaper), N.CMT_ROUTE_DIRECT, N.CMT_ROUTE_COMPLEMENT (whenever eligible)"""
     ctx = ctx or _c()

@@ -15,6 +15,9 @@ struct keysrc {
     // committee table (mbls_cmt.h): keys of the table above (indexed, d_idx null), named per item by a committee and a bitfield
     bool committee = false; const uint32_t* d_crecs = nullptr; uint64_t ccount = 0; const uint32_t* d_members = nullptr; uint32_t cmax = 0;
     const uint32_t* d_cmt_idx = nullptr; const uint8_t* d_bits = nullptr; uint32_t bits_stride = 0; const mbls_committees* cmt = nullptr;
+    // committee spans (mbls_cms.h): the committee kind with, per item, ids [d_cmt_span_off[i], d_cmt_span_off[i + 1]) of d_cmt_ids (n_cmt_ids of them) and ONE bitfield
+    // over their concatenated members (d_cmt_idx null)
+    bool span = false; const uint32_t* d_cmt_ids = nullptr; uint64_t n_cmt_ids = 0; const uint32_t* d_cmt_span_off = nullptr;
 };
 // wire keys: k per item back to back, or -- d_off -- keys [d_off[i], d_off[i + 1]) of d_pks
 static inline keysrc keys_wire(const uint8_t* d_pks, int fmt, const uint32_t* d_off) {
@@ -30,6 +33,13 @@ static inline keysrc keys_committee(keysrc keys, const uint32_t* d_crecs, uint64
                                     const uint8_t* d_bits, uint32_t bits_stride, const mbls_committees* cmt) {
     keysrc ks = keys; ks.committee = true; ks.d_crecs = d_crecs; ks.ccount = ccount; ks.d_members = d_members; ks.cmax = cmax; ks.d_cmt_idx = d_cmt_idx; ks.d_bits = d_bits;
     ks.bits_stride = bits_stride; ks.cmt = cmt; return ks;
+}
+// a span of committees per item: keys_committee with the id of item i replaced by the ids d_cmt_ids[d_cmt_span_off[i] .. d_cmt_span_off[i + 1]) -- absolute offsets
+// into an array of n_cmt_ids ids, like d_off into the keys
+static inline keysrc keys_committee_span(keysrc keys, const uint32_t* d_crecs, uint64_t ccount, const uint32_t* d_members, uint32_t cmax, const uint32_t* d_cmt_ids,
+                                         uint64_t n_cmt_ids, const uint32_t* d_cmt_span_off, const uint8_t* d_bits, uint32_t bits_stride, const mbls_committees* cmt) {
+    keysrc ks = keys_committee(keys, d_crecs, ccount, d_members, cmax, nullptr, d_bits, bits_stride, cmt);
+    ks.span = true; ks.d_cmt_ids = d_cmt_ids; ks.n_cmt_ids = n_cmt_ids; ks.d_cmt_span_off = d_cmt_span_off; return ks;
 }
 
 // where an item's message comes from: its own bytes, or index i of d_idx names one of n_msgs hashed points in a table -- the context's per-call table, which holds
@@ -70,8 +80,9 @@ static inline batch slice(const batch& b, uint64_t lo, uint64_t hi) {
     if (b.d_results) t.d_results = b.d_results + lo;
     if (b.d_bitmap) t.d_bitmap = b.d_bitmap + lo / 64;
     if (b.d_status) t.d_status = b.d_status + lo;
-    if (b.ks.committee) {        // one committee id and one bitfield per item
+    if (b.ks.committee) {        // one committee id -- a span: one range of the (unmoved) id array, its offsets absolute -- and one bitfield per item
         if (b.ks.d_cmt_idx) t.ks.d_cmt_idx = b.ks.d_cmt_idx + lo;
+        if (b.ks.d_cmt_span_off) t.ks.d_cmt_span_off = b.ks.d_cmt_span_off + lo;
         if (b.ks.d_bits) t.ks.d_bits = b.ks.d_bits + (uint64_t)b.ks.bits_stride * lo;
     } else if (b.ks.d_off) t.ks.d_off = b.ks.d_off + lo;
     else {

@@ -29,6 +29,7 @@
 #include "mbls_mtb.h"
 #include "mbls_batch.h"
 #include "mbls_cmt_lanes.h"
+#include "mbls_cms_launch.h"
 #include "../../include/mbls.h"
 
 // The product library exists only with the generated routines: the host side below selects kernels (the fused subgroup verdict of
@@ -1288,6 +1289,10 @@ struct mbls_ctx {
     // table's largest committee -- and the count and route words of cmt_items items (d_cmt_cnt: [2][cmt_items]); mbls_ctx_reserve_committee_items
     uint32_t* d_cmt_list = nullptr; uint64_t cmt_words = 0; uint32_t* d_cmt_cnt = nullptr; uint64_t cmt_items = 0;
     int cmt_route_mode = 0;            // mbls_ctx_set_committee_route: 0 auto (cmt_route), 1 always direct, 2 complement whenever eligible
+    // committee spans (mbls_cms.h): the items' list regions k_cms_expand writes for k_aggregate_cms_d -- cms_words uint32 in all, an item's region at the stride of
+    // the call (cms_stride) --, and for cms_items items the records (d_cms_rec: [cms_items][MBLS_CMS_REC_DWORDS]) and the parked points (d_cms_park:
+    // [MBLS_CMS_PARK_DWORDS][cms_items]); mbls_ctx_reserve_committee_span_items
+    uint32_t* d_cms_list = nullptr; uint64_t cms_words = 0; uint32_t* d_cms_rec = nullptr; uint32_t* d_cms_park = nullptr; uint64_t cms_items = 0;
     coop_prog coop[10] = {};           // the cooperative engine's microprograms in HBM (mbls_coop.h): pairing2, vmtail, f12mul, g2add, smiller, vmfinal, hashg2, miller1,
                                        // pairing2x2 (two items per wave), hashg2x4 (four)
     uint32_t* d_coop = nullptr;
@@ -1330,6 +1335,7 @@ struct mbls_committees {
     uint32_t* d_members = nullptr; uint64_t n_members = 0, members_cap = 0;
     uint32_t* d_recs = nullptr; uint64_t count = 0, cap = 0;      // [cap][MBLS_CMT_REC_DWORDS]
     uint32_t max_members = 0;          // the largest committee the table holds
+    std::vector<uint32_t> sizes;       // every committee's member count, by id: what the host entries of the span form check an item's field against
     hipEvent_t ev = nullptr; hipStream_t ev_stream = nullptr; bool pending = false;   // the last asynchronous append
 };
 typedef std::lock_guard<std::recursive_mutex> mbls_lock;
@@ -1410,6 +1416,9 @@ static void ctx_free(mbls_ctx* c) {
     if (c->d_vmap) (void)hipFree(c->d_vmap);
     if (c->d_cmt_list) (void)hipFree(c->d_cmt_list);
     if (c->d_cmt_cnt) (void)hipFree(c->d_cmt_cnt);
+    if (c->d_cms_list) (void)hipFree(c->d_cms_list);
+    if (c->d_cms_rec) (void)hipFree(c->d_cms_rec);
+    if (c->d_cms_park) (void)hipFree(c->d_cms_park);
     if (c->d_coop) (void)hipFree(c->d_coop);
     for (int i = 0; i < MBLS_N_STAGE; i++) if (c->stage[i].p) (void)hipFree(c->stage[i].p);
     for (int i = 0; i <= MBLS_N_PHASES; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1717,6 +1726,36 @@ extern "C" int mbls_ctx_reserve_committee_items(mbls_ctx* c, uint64_t max_items,
     HIPCHK(c, hipSetDevice(c->device));
     return reserve_committee(c, max_items, max_members);
 }
+// the scratch of the span entries for `items` items whose list regions take `stride` words each (grow-only, like reserve_committee)
+static int reserve_committee_span(mbls_ctx* c, uint64_t items, uint64_t stride) {
+    if (!stride) stride = 1;
+    const uint64_t want_items = ((items + WG - 1) / WG) * WG, want_words = want_items * stride;
+    if (want_items > c->cms_items) {
+        if (c->d_cms_rec) { (void)hipFree(c->d_cms_rec); c->d_cms_rec = nullptr; }
+        if (c->d_cms_park) { (void)hipFree(c->d_cms_park); c->d_cms_park = nullptr; }
+        c->cms_items = 0;
+        HIPCHK(c, hipMalloc(&c->d_cms_rec, want_items * MBLS_CMS_REC_DWORDS * 4));
+        HIPCHK(c, hipMalloc(&c->d_cms_park, want_items * MBLS_CMS_PARK_DWORDS * 4));
+        c->cms_items = want_items;
+    }
+    if (want_words > c->cms_words) {
+        if (c->d_cms_list) { (void)hipFree(c->d_cms_list); c->d_cms_list = nullptr; c->cms_words = 0; }
+        HIPCHK(c, hipMalloc(&c->d_cms_list, want_words * 4));
+        c->cms_words = want_words;
+    }
+    return MBLS_OK;
+}
+extern "C" int mbls_ctx_reserve_committee_span_items(mbls_ctx* c, uint64_t max_items, uint32_t max_item_members) {
+    if (!c || max_item_members > MBLS_CMS_MAX_COMMITTEES * MBLS_CMT_MAX_MEMBERS) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return reserve_committee_span(c, max_items, max_item_members);
+}
+extern "C" int mbls_plan_committee_span(const uint32_t* sizes, const uint8_t* eligible, uint32_t q, const uint8_t* bits, uint32_t bits_bytes, int mode,
+                                        uint64_t* complement_mask, uint32_t* n_direct_listed, uint32_t* n_missing_listed) {
+    if (!complement_mask || !n_direct_listed || !n_missing_listed || (q && (!sizes || !eligible)) || (bits_bytes && !bits)) return MBLS_ERR_ARGUMENT;
+    return cms_plan_item(sizes, eligible, q, bits, bits_bytes, mode, complement_mask, n_direct_listed, n_missing_listed) ? MBLS_ERR_ARGUMENT : MBLS_OK;
+}
 // the key source of an _indexed entry: the table at the size it has now (the caller holds the context's lock)
 static int keys_of_table(mbls_ctx* c, const mbls_keytable* t, const uint32_t* d_idx, const uint32_t* d_off, keysrc* ks) {
     if (t->c != c) ARGFAIL(c, "key table belongs to another context");
@@ -1724,7 +1763,14 @@ static int keys_of_table(mbls_ctx* c, const mbls_keytable* t, const uint32_t* d_
 }
 // the key source of a _committee entry (defined with the committee table below), and what a host entry hands verify_host beside it: ids and bitfields in host memory
 static int keys_of_committees(mbls_ctx* c, const mbls_committees* t, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride, bool device_bits, keysrc* ks);
-struct host_committees { const mbls_committees* t; const uint32_t* cmt_idx; const uint8_t* bits; uint32_t bits_stride; };
+// (the span form: cmt_idx null, item i names ids cmt_ids[cmt_off[i] .. cmt_off[i + 1]) of n_cmt_ids)
+struct host_committees {
+    const mbls_committees* t; const uint32_t* cmt_idx; const uint8_t* bits; uint32_t bits_stride;
+    bool span = false; const uint32_t* cmt_ids = nullptr; uint64_t n_cmt_ids = 0; const uint32_t* cmt_off = nullptr;
+};
+static int keys_of_committee_span(mbls_ctx* c, const mbls_committees* t, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits,
+                                  uint32_t bits_stride, bool device_bits, keysrc* ks);
+static int committee_span_items_ok(mbls_ctx* c, const host_committees& hc, uint64_t n);
 // The message source of a _msgtable entry. The entry hands over the indices alone (msgs_in_table): what the table holds lives in its handle until verify_device /
 // verify_host, under the context's lock and once they know the table is this context's, read it at the size it has then (msgs_of_table).
 static msgsrc msgs_in_table(const uint32_t* d_idx) { return msgs_table(nullptr, 0, nullptr, 0, d_idx); }
@@ -1984,7 +2030,8 @@ static int verify_pipeline_one(mbls_ctx* c, const batch& b, hipStream_t s, int p
     const int fmt = ks.fmt; const uint32_t* d_off = ks.d_off;
     if (!c || (fmt != MBLS_PK_COMPRESSED && fmt != MBLS_PK_UNCOMPRESSED)) return MBLS_ERR_ARGUMENT;
     if (n == 0) return MBLS_OK;
-    const bool have_keys = ks.committee ? (ks.d_cmt_idx != nullptr && ks.d_bits != nullptr) : ks.indexed ? (ks.d_idx != nullptr) : (ks.d_pks != nullptr);
+    const bool have_keys = ks.span ? (ks.d_cmt_span_off != nullptr && (ks.d_cmt_ids != nullptr || !ks.n_cmt_ids) && (ks.d_bits != nullptr || !ks.bits_stride))
+                         : ks.committee ? (ks.d_cmt_idx != nullptr && ks.d_bits != nullptr) : ks.indexed ? (ks.d_idx != nullptr) : (ks.d_pks != nullptr);
     if (!d_sigs || (!ms.indexed() && !ms.d_msgs && ms.msg_len && !ms.d_moff) || (ms.indexed() && !ms.d_idx) || !d_results || (!have_keys && (k || d_off) && part != 1))
         ARGFAIL(c, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
@@ -2054,7 +2101,16 @@ static int verify_pipeline_one(mbls_ctx* c, const batch& b, hipStream_t s, int p
     }
     if (tm) HIPCHK(c, hipEventRecord(c->ev[0], s));
     if (ks.indexed) { rc = table_acquire(c, ks.tab, s); if (rc) return rc; }
-    if (ks.committee) {
+    if (ks.span) {
+        // the items' list regions, records and parked points in the span scratch reserved for the whole plan (reserve_committee_span), at the pass's workspace offset
+        const uint64_t ls = cms_stride(ks.bits_stride, ks.cmax);
+        if ((tk.ws_off + n) * ls > c->cms_words || tk.ws_off + n > c->cms_items) ARGFAIL(c, "internal: the span scratch of a pass was not reserved");
+        rc = committees_acquire(c, ks.cmt, s); if (rc) return rc;
+        uint32_t* const list = c->d_cms_list + tk.ws_off * ls; uint32_t* const irec = c->d_cms_rec + tk.ws_off * MBLS_CMS_REC_DWORDS;
+        mbls_cms_launch_expand(ks.d_crecs, ks.ccount, ks.d_members, ks.d_cmt_ids, ks.n_cmt_ids, ks.d_cmt_span_off, ks.d_bits, ks.bits_stride, c->cmt_route_mode, list, ls,
+                               irec, n, s);
+        mbls_cms_launch_aggregate(ws, ks.d_recs, ks.tsize, list, ls, irec, ks.d_crecs, ks.d_cmt_ids, ks.d_cmt_span_off, c->d_cms_park + tk.ws_off, c->cms_items, st, n, s);
+    } else if (ks.committee) {
         // the items' lists in the scratch reserved for the whole plan (reserve_committee: nothing grows under a pass in flight), at the pass's workspace offset
         const uint64_t ls = ks.cmax ? ks.cmax : 1;
         if ((tk.ws_off + n) * ls > c->cmt_words || tk.ws_off + n > c->cmt_items) ARGFAIL(c, "internal: the committee scratch of a pass was not reserved");
@@ -2178,12 +2234,12 @@ extern "C" int mbls_ctx_set_tracks(mbls_ctx* c, uint64_t min_rest_items, uint64_
 static int verify_device(mbls_ctx* c, batch b, const mbls_msgtable* mt, hipStream_t s) {
     msgsrc& ms = b.ms;
     if (b.ks.fmt != MBLS_PK_COMPRESSED && b.ks.fmt != MBLS_PK_UNCOMPRESSED) return MBLS_ERR_ARGUMENT;
-    if (b.ks.committee && b.n) {          // the scratch of k_cmt_expand for the whole plan (the extent of its passes), before anything is queued
+    if (b.ks.committee && b.n) {          // the scratch of k_cmt_expand / k_cms_expand for the whole plan (the extent of its passes), before anything is queued
         HIPCHK(c, hipSetDevice(c->device));
         mbls_batch_plan bp; plan_batch(ctx_limits(c), b.n, c->timing, c->timing, &bp);
         uint64_t extent = 0;
         for (uint32_t i = 0; i < bp.n_passes; i++) { const uint64_t e = bp.pass[i].workspace_first + bp.pass[i].items; if (e > extent) extent = e; }
-        const int rr = reserve_committee(c, extent, b.ks.cmax); if (rr) return rr;
+        const int rr = b.ks.span ? reserve_committee_span(c, extent, cms_stride(b.ks.bits_stride, b.ks.cmax)) : reserve_committee(c, extent, b.ks.cmax); if (rr) return rr;
     }
     if (mt) {
         if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
@@ -2264,7 +2320,10 @@ static int verify_host(mbls_ctx* c, const uint8_t* sigs, msgsrc hm, const mbls_m
     if (fmt != MBLS_PK_COMPRESSED && fmt != MBLS_PK_UNCOMPRESSED) ARGFAIL(c, "pk_format");
     keysrc ks = keys_wire(nullptr, fmt, nullptr);
     if (tab) { const int rk = keys_of_table(c, tab, nullptr, nullptr, &ks); if (rk) return rk; }
-    if (hc) {            // keys by committee and bitfield (pks, tab, idx, off null, k = 0): the table read under the lock, an id that names nothing refuses the call
+    if (hc && hc->span) {        // keys by committee span: every item's shape is checked here (cms_range_ok, the ids, cms_field_ok), a malformed item refuses the call
+        const int rk = keys_of_committee_span(c, hc->t, nullptr, hc->n_cmt_ids, nullptr, nullptr, hc->bits_stride, false, &ks); if (rk) return rk;
+        const int ri = committee_span_items_ok(c, *hc, n); if (ri) return ri;
+    } else if (hc) {     // keys by committee and bitfield (pks, tab, idx, off null, k = 0): the table read under the lock, an id that names nothing refuses the call
         const int rk = keys_of_committees(c, hc->t, nullptr, nullptr, hc->bits_stride, false, &ks); if (rk) return rk;
         if (!hc->cmt_idx || !hc->bits) ARGFAIL(c, "null buffer");
         for (uint64_t i = 0; i < n; i++) if ((uint64_t)hc->cmt_idx[i] >= hc->t->count) ARGFAIL(c, "cmt_idx names no committee of the table");
@@ -2278,7 +2337,7 @@ static int verify_host(mbls_ctx* c, const uint8_t* sigs, msgsrc hm, const mbls_m
     if (total_keys && !(indexed ? (const void*)idx : (const void*)pks)) ARGFAIL(c, "null key buffer");
     const size_t unit = indexed ? 4 : (fmt == MBLS_PK_COMPRESSED ? 48 : 96);
     const void* h_keys = total_keys ? (indexed ? (const void*)(idx + key_first) : (const void*)(pks + unit * key_first)) : nullptr;
-    sbuf ds(c, 0), dm(c, 1), dp(c, 2), doff(c, 3), dr(c, 4), dst(c, 5), dmo(c, 6), dmi(c, 7);
+    sbuf ds(c, 0), dm(c, 1), dp(c, 2), doff(c, 3), dr(c, 4), dst(c, 5), dmo(c, 6), dmi(c, 7), dso(c, 8);
     batch b{nullptr, hm, ks, n, k, mode, nullptr, nullptr, nullptr};       // the same batch with DEVICE pointers
     HIPCHK(c, ds.up(sigs, 96 * n)); b.d_sigs = ds.as<uint8_t>();
     if (hm.kind != MBLS_MSGS_TABLE) { HIPCHK(c, dm.up(msgs ? msgs + msg_first : nullptr, msg_total)); b.ms.d_msgs = dm.as<uint8_t>(); }
@@ -2290,7 +2349,10 @@ static int verify_host(mbls_ctx* c, const uint8_t* sigs, msgsrc hm, const mbls_m
     HIPCHK(c, dr.alloc(n)); HIPCHK(c, dst.alloc(4 * n)); b.d_results = dr.as<uint8_t>(); b.d_status = dst.as<uint32_t>();
     auto keys_are_there = [&]() { if (indexed) b.ks.d_idx = dp.as<uint32_t>() - key_first; else b.ks.d_pks = dp.as<uint8_t>() - unit * key_first; };     // the table's offsets are absolute
     const bool late_keys = !hm.indexed() && !hc; // (the indexed kinds and the committee form upload their keys up front: the late upload has not been measured for them)
-    if (hc) {            // the ids and the bitfields take the two key slots
+    if (hc && hc->span) {       // the ids and the bitfields take the two key slots, the span offsets one of their own
+        HIPCHK(c, dp.up(hc->cmt_ids, 4 * hc->n_cmt_ids)); HIPCHK(c, doff.up(hc->bits, (size_t)hc->bits_stride * n)); HIPCHK(c, dso.up(hc->cmt_off, 4 * (n + 1)));
+        b.ks.d_cmt_ids = dp.as<uint32_t>(); b.ks.d_bits = doff.as<uint8_t>(); b.ks.d_cmt_span_off = dso.as<uint32_t>();
+    } else if (hc) {     // the ids and the bitfields take the two key slots
         HIPCHK(c, dp.up(hc->cmt_idx, 4 * n)); HIPCHK(c, doff.up(hc->bits, (size_t)hc->bits_stride * n));
         b.ks.d_cmt_idx = dp.as<uint32_t>(); b.ks.d_bits = doff.as<uint8_t>();
     } else if (late_keys) HIPCHK(c, dp.alloc(unit * total_keys)); else { HIPCHK(c, dp.up(h_keys, unit * total_keys)); keys_are_there(); }
@@ -2734,7 +2796,7 @@ extern "C" int mbls_committees_clear(mbls_committees* t) {
     mbls_lock lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());           // every append and verification enqueued over the table
-    t->count = 0; t->n_members = 0; t->max_members = 0; t->pending = false; c->ws_pending = false;
+    t->count = 0; t->n_members = 0; t->max_members = 0; t->pending = false; c->ws_pending = false; t->sizes.clear();
     return MBLS_OK;
 }
 // room for `need` uint32 / `need` records of 40 dwords: new buffer, the device drained on both sides of the copy (keytable_grow's rule)
@@ -2777,7 +2839,7 @@ extern "C" int mbls_committees_append(mbls_committees* t, const uint32_t* key_id
     rc = committees_grow(c, &t->d_members, &t->members_cap, t->n_members, t->n_members + total, 1); if (rc) return rc;
     // the offsets as the kernels want them: relative to the append's first member
     std::vector<uint32_t> rel;
-    try { rel.resize(n + 1); } catch (...) { return MBLS_ERR_DEVICE; }
+    try { rel.resize(n + 1); t->sizes.reserve(t->count + n); } catch (...) { return MBLS_ERR_DEVICE; }
     for (uint64_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0];
     sbuf doff(c, 3);
     HIPCHK(c, doff.up(rel.data(), 4 * (n + 1)));
@@ -2798,6 +2860,7 @@ extern "C" int mbls_committees_append(mbls_committees* t, const uint32_t* key_id
     HIPCHK(c, hipStreamSynchronize(s));
     c->ws_pending = false; t->pending = false;
     if (first_id) *first_id = t->count;
+    for (uint64_t i = 0; i < n; i++) t->sizes.push_back(offsets[i + 1] - offsets[i]);       // (reserved above: nothing throws here)
     t->count += n; t->n_members += total; t->max_members = maxm;
     return MBLS_OK;
 }
@@ -2866,6 +2929,76 @@ extern "C" int mbls_fast_aggregate_verify_batch_committee_msgtable(mbls_ctx* c, 
         const uint32_t* msg_idx, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_stride, uint64_t n, uint8_t* results, uint32_t* status) {
     if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
     const host_committees hc = {t, cmt_idx, bits, bits_stride};
+    return verify_host(c, sigs, msgs_in_table(msg_idx), mt, nullptr, MBLS_PK_UNCOMPRESSED, nullptr, nullptr, nullptr, n, 0, MBLS_MODE_FAST_AGGREGATE, results, status, &hc);
+}
+
+// ---- committee spans (include/mbls.h, "committee spans"; arithmetic: mbls_cms.h, device bodies: mbls_cms_lanes.h): the committee entries with, per item, a range of
+// committee ids and one bitfield over their concatenated members. The key source is the committee form's with the span fields; the pass launches k_cms_expand and
+// k_aggregate_cms_d where the committee form launches its two kernels, and verify_device reserves the span scratch for the plan's extent.
+static int keys_of_committee_span(mbls_ctx* c, const mbls_committees* t, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits,
+                                  uint32_t bits_stride, bool device_bits, keysrc* ks) {
+    if (t->c != c) ARGFAIL(c, "committee table belongs to another context");
+    if (!t->kt || t->kt->c != c) ARGFAIL(c, "the committee table's key table is gone");
+    if (bits_stride % 4) ARGFAIL(c, "bits_stride must be a multiple of 4");
+    if (n_cmt_ids > 0xFFFFFFFFull) ARGFAIL(c, "span offsets are 32-bit");
+    if (device_bits && (((uintptr_t)d_bits) & 3u)) ARGFAIL(c, "d_bits must be 4-byte aligned");
+    keysrc kt; const int rk = keys_of_table(c, t->kt, nullptr, nullptr, &kt); if (rk) return rk;
+    *ks = keys_committee_span(kt, t->d_recs, t->count, t->d_members, t->max_members, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, t);
+    return MBLS_OK;
+}
+// the host entries' statement of "malformed": what wave_cms_expand rejects per item refuses the whole call here (the caller holds the context's lock)
+static int committee_span_items_ok(mbls_ctx* c, const host_committees& hc, uint64_t n) {
+    if (!hc.cmt_off || (hc.n_cmt_ids && !hc.cmt_ids) || (hc.bits_stride && !hc.bits)) ARGFAIL(c, "null buffer");
+    for (uint64_t i = 0; i < n; i++) {
+        uint32_t q = 0;
+        if (!cms_range_ok(hc.cmt_off[i], hc.cmt_off[i + 1], hc.n_cmt_ids, &q)) ARGFAIL(c, "cmt_off must be non-decreasing, inside cmt_ids, at most MBLS_SPAN_MAX_COMMITTEES ids per item");
+        uint64_t M = 0;
+        for (uint32_t u = 0; u < q; u++) {
+            const uint32_t cid = hc.cmt_ids[(uint64_t)hc.cmt_off[i] + u];
+            if ((uint64_t)cid >= hc.t->count) ARGFAIL(c, "cmt_ids names no committee of the table");
+            M += hc.t->sizes[cid];
+        }
+        if (!cms_field_ok(M, hc.bits_stride)) ARGFAIL(c, "bits_stride does not cover an item's committees");
+    }
+    return MBLS_OK;
+}
+static int verify_committee_span_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, msgsrc ms, const mbls_msgtable* mt, const uint32_t* d_cmt_ids,
+                                        uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride, uint64_t n, uint8_t* d_results,
+                                        uint64_t* d_bitmap, uint32_t* d_status, hipStream_t s) {
+    keysrc ks; const int rk = keys_of_committee_span(c, t, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, true, &ks); if (rk) return rk;
+    if (n == 0) return MBLS_OK;
+    if (!d_cmt_off || (n_cmt_ids && !d_cmt_ids) || (bits_stride && !d_bits)) ARGFAIL(c, "null buffer");
+    return verify_device(c, batch{d_sigs, ms, ks, n, 0, MBLS_MODE_FAST_AGGREGATE, d_results, d_bitmap, d_status}, mt, s);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_committee_span_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_len,
+        const uint64_t* d_moff, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride, uint64_t n,
+        uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
+    if (!c || !t) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    return verify_committee_span_device(c, t, d_sigs, msgs_per_item(d_msgs, msg_len, d_moff), nullptr, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, n, d_results,
+                                        d_bitmap, d_status, (hipStream_t)stream);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_committee_span_msgtable_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const mbls_msgtable* mt,
+        const uint32_t* d_msg_idx, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride, uint64_t n,
+        uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream) {
+    if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    return verify_committee_span_device(c, t, d_sigs, msgs_in_table(d_msg_idx), mt, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, n, d_results, d_bitmap, d_status,
+                                        (hipStream_t)stream);
+}
+// the host forms: verify_host with the span description in place of keys
+extern "C" int mbls_fast_aggregate_verify_batch_committee_span(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
+        const uint64_t* moff, const uint32_t* cmt_ids, uint64_t n_cmt_ids, const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride, uint64_t n,
+        uint8_t* results, uint32_t* status) {
+    if (!c || !t) return MBLS_ERR_ARGUMENT;
+    host_committees hc = {t, nullptr, bits, bits_stride}; hc.span = true; hc.cmt_ids = cmt_ids; hc.n_cmt_ids = n_cmt_ids; hc.cmt_off = cmt_off;
+    return verify_host(c, sigs, msgs_per_item(msgs, msg_len, moff), nullptr, nullptr, MBLS_PK_UNCOMPRESSED, nullptr, nullptr, nullptr, n, 0, MBLS_MODE_FAST_AGGREGATE, results, status, &hc);
+}
+extern "C" int mbls_fast_aggregate_verify_batch_committee_span_msgtable(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs, const mbls_msgtable* mt,
+        const uint32_t* msg_idx, const uint32_t* cmt_ids, uint64_t n_cmt_ids, const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride, uint64_t n,
+        uint8_t* results, uint32_t* status) {
+    if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
+    host_committees hc = {t, nullptr, bits, bits_stride}; hc.span = true; hc.cmt_ids = cmt_ids; hc.n_cmt_ids = n_cmt_ids; hc.cmt_off = cmt_off;
     return verify_host(c, sigs, msgs_in_table(msg_idx), mt, nullptr, MBLS_PK_UNCOMPRESSED, nullptr, nullptr, nullptr, n, 0, MBLS_MODE_FAST_AGGREGATE, results, status, &hc);
 }
 

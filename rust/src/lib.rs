@@ -198,6 +198,16 @@ extern "C" {
     fn mbls_fast_aggregate_verify_batch_committee_msgtable(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs: *const u8, mt: *const mbls_msgtable,
                                                            msg_idx: *const u32, cmt_idx: *const u32, bits: *const u8, bits_stride: u32, n: u64, results: *mut u8,
                                                            status: *mut u32) -> c_int;
+    // committee spans: an item names up to 64 committees (cmt_ids[cmt_off[i] .. cmt_off[i + 1])) and carries one bitfield over their concatenated members
+    fn mbls_fast_aggregate_verify_batch_committee_span(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs: *const u8, msgs: *const u8, msg_len: u32,
+                                                       msg_offsets: *const u64, cmt_ids: *const u32, n_cmt_ids: u64, cmt_off: *const u32, bits: *const u8,
+                                                       bits_stride: u32, n: u64, results: *mut u8, status: *mut u32) -> c_int;
+    fn mbls_fast_aggregate_verify_batch_committee_span_msgtable(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs: *const u8, mt: *const mbls_msgtable,
+                                                                msg_idx: *const u32, cmt_ids: *const u32, n_cmt_ids: u64, cmt_off: *const u32, bits: *const u8,
+                                                                bits_stride: u32, n: u64, results: *mut u8, status: *mut u32) -> c_int;
+    fn mbls_ctx_reserve_committee_span_items(ctx: *mut MblsCtx, max_items: u64, max_item_members: u32) -> c_int;
+    fn mbls_plan_committee_span(sizes: *const u32, eligible: *const u8, q: u32, bits: *const u8, bits_bytes: u32, mode: c_int, complement_mask: *mut u64,
+                                n_direct_listed: *mut u32, n_missing_listed: *mut u32) -> c_int;
     fn mbls_verify_multiple_msgtable_device(ctx: *mut MblsCtx, d_sigs96: *const u8, d_apks96: *const u8, mt: *const mbls_msgtable, d_msg_idx: *const u32, d_rands: *const u64,
                                             n: u64, d_result: *mut u8, d_status: *mut u32, stream: *mut c_void) -> c_int;
     fn mbls_verify_multiple_sets_indexed_msgtable_device(ctx: *mut MblsCtx, t: *const MblsKeyTable, d_sigs96: *const u8, d_key_idx: *const u32, d_offsets: *const u32, k: u32,
@@ -1558,6 +1568,84 @@ impl CommitteeTable {
         res.truncate(n);
         res.into_iter().map(|b| b == 1).collect()
     }
+    /// The ids of every item back to back with their absolute offsets, and every field at one stride: the widest field, rounded up to 4.
+    fn flatten_spans(committee_ids: &[&[u32]], bits: &[&[u8]]) -> (Vec<u32>, u64, Vec<u32>, Vec<u8>, u32) {
+        let mut ids: Vec<u32> = Vec::new();
+        let mut off: Vec<u32> = vec![0];
+        for l in committee_ids {
+            ids.extend_from_slice(l);
+            off.push(ids.len() as u32);
+        }
+        let n_ids = ids.len() as u64;
+        if ids.is_empty() {
+            ids.push(0);
+        }
+        let stride = (bits.iter().map(|b| b.len()).max().unwrap_or(0).max(1) + 3) / 4 * 4;
+        let mut flat = vec![0u8; stride * bits.len().max(1)];
+        for (i, b) in bits.iter().enumerate() {
+            flat[stride * i..stride * i + b.len()].copy_from_slice(b);
+        }
+        (ids, n_ids, off, flat, stride as u32)
+    }
+    /// n x `AggregateSignature::fast_aggregate_verify` over attestations that span several committees (`mbls_fast_aggregate_verify_batch_committee_span`): item i =
+    /// (signatures[i], messages[i], the committees committee_ids[i] in order -- at most `SPAN_MAX_COMMITTEES` --, bits[i]: ONE bitfield over their concatenated
+    /// members, an Electra attestation's aggregation_bits as SSZ serializes them). A malformed item (an id that names nothing, too many ids, a field shorter than
+    /// the committees' members) refuses the whole call.
+    pub fn fast_aggregate_verify_spans(&self, signatures: &[AggregateSignature], messages: &[&[u8]], committee_ids: &[&[u32]], bits: &[&[u8]]) -> Vec<bool> {
+        let n = signatures.len();
+        assert!(messages.len() == n && committee_ids.len() == n && bits.len() == n);
+        let sigs: Vec<u8> = signatures.iter().flat_map(|s| s.point.iter().copied()).collect();
+        let mut msgs: Vec<u8> = Vec::new();
+        let mut moff: Vec<u64> = vec![0];
+        for m in messages {
+            msgs.extend_from_slice(m);
+            moff.push(msgs.len() as u64);
+        }
+        let (ids, n_ids, off, flat, stride) = Self::flatten_spans(committee_ids, bits);
+        let mut res = vec![0u8; n.max(1)];
+        let rc = unsafe {
+            mbls_fast_aggregate_verify_batch_committee_span(ctx(), self.h, sigs.as_ptr(), msgs.as_ptr(), 0, moff.as_ptr(), ids.as_ptr(), n_ids, off.as_ptr(), flat.as_ptr(),
+                                                            stride, n as u64, res.as_mut_ptr(), std::ptr::null_mut())
+        };
+        if rc != 0 {
+            err(rc);
+        }
+        res.truncate(n);
+        res.into_iter().map(|b| b == 1).collect()
+    }
+    /// The same with the messages named by index into a `MessageTable`.
+    pub fn fast_aggregate_verify_spans_msgtable(&self, signatures: &[AggregateSignature], table: &MessageTable, message_indices: &[u32], committee_ids: &[&[u32]],
+                                                bits: &[&[u8]]) -> Vec<bool> {
+        let n = signatures.len();
+        assert!(message_indices.len() == n && committee_ids.len() == n && bits.len() == n);
+        let sigs: Vec<u8> = signatures.iter().flat_map(|s| s.point.iter().copied()).collect();
+        let (ids, n_ids, off, flat, stride) = Self::flatten_spans(committee_ids, bits);
+        let mut res = vec![0u8; n.max(1)];
+        let rc = unsafe {
+            mbls_fast_aggregate_verify_batch_committee_span_msgtable(ctx(), self.h, sigs.as_ptr(), table.h, message_indices.as_ptr(), ids.as_ptr(), n_ids, off.as_ptr(),
+                                                                     flat.as_ptr(), stride, n as u64, res.as_mut_ptr(), std::ptr::null_mut())
+        };
+        if rc != 0 {
+            err(rc);
+        }
+        res.truncate(n);
+        res.into_iter().map(|b| b == 1).collect()
+    }
+    /// Reserves the span entries' scratch for batches of `max_items` items whose list regions take `max_item_members` words each.
+    pub fn reserve_spans(max_items: u64, max_item_members: u32) -> bool {
+        unsafe { mbls_ctx_reserve_committee_span_items(ctx(), max_items, max_item_members) == 0 }
+    }
+    /// What the span kernel decides for one item (pure: no GPU): `(complement mask, entries of the direct list, entries of the missing list)`, `None` for
+    /// arguments the C entry refuses.
+    pub fn plan_span(sizes: &[u32], eligible: &[bool], bits: &[u8], mode: i32) -> Option<(u64, u32, u32)> {
+        assert!(sizes.len() == eligible.len());
+        let el: Vec<u8> = eligible.iter().map(|&e| e as u8).collect();
+        let (mut mask, mut nd, mut nm) = (0u64, 0u32, 0u32);
+        let rc = unsafe {
+            mbls_plan_committee_span(sizes.as_ptr(), el.as_ptr(), sizes.len() as u32, bits.as_ptr(), bits.len() as u32, mode as c_int, &mut mask, &mut nd, &mut nm)
+        };
+        if rc == 0 { Some((mask, nd, nm)) } else { None }
+    }
     /// `AggregateSignature::verify_multiple_aggregate_signatures` over a gossip batch whose keys and messages are resident
     /// (`mbls_verify_multiple_committee_msgtable_rng`): every set is a signature, a `GossipKeys` -- a committee of this table with its participation bits, or ONE
     /// key of the key table the committees are bound to -- and an entry index of `table`. The same bool as that function on the spelled-out aggregate keys and
@@ -1628,6 +1716,8 @@ impl CommitteeTable {
 }
 /// `MBLS_VM_SET_SINGLE_KEY` of include/mbls.h: bit 31 of a set's descriptor word marks a set under one key of the key table.
 pub const VM_SET_SINGLE_KEY: u32 = 0x8000_0000;
+/// `MBLS_SPAN_MAX_COMMITTEES`: the committees one item of the span entries may name (the protocol's MAX_COMMITTEES_PER_SLOT).
+pub const SPAN_MAX_COMMITTEES: usize = 64;
 /// The keys of one set of `CommitteeTable::verify_multiple_aggregate_signatures`.
 #[derive(Clone, Copy)]
 pub enum GossipKeys<'a> {
