@@ -414,7 +414,8 @@ int mbls_fast_aggregate_verify_batch_committee_msgtable(mbls_ctx* ctx, const mbl
  *   of the q segments, the item's field (bits_bytes bytes, any alignment) and the route mode in; the mask of the segments that go complement (bit t: segment t)
  *   and the entries of the direct and of the missing list out. MBLS_ERR_ARGUMENT for q > 64, a size of 0 or above MBLS_COMMITTEE_MAX_MEMBERS, M > 8 * bits_bytes,
  *   a mode outside 0..2 or a null output.
- * OUT OF SCOPE: verify_multiple over spans, the verification stream, the shared-list message form, the mbls_multi handle. */
+ * OUT OF SCOPE: the verification stream, the shared-list message form, the mbls_multi handle. (verify_multiple over spans:
+ * mbls_verify_multiple_committee_span_msgtable* below.) */
 #define MBLS_SPAN_MAX_COMMITTEES 64
 int mbls_fast_aggregate_verify_batch_committee_span_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs, const uint8_t* d_msgs,
                                                            uint32_t msg_len, const uint64_t* d_msg_offsets, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids,
@@ -956,7 +957,8 @@ int mbls_verify_multiple_msgtable_locate_rng(mbls_ctx* ctx, const uint8_t* sigs9
  * PLANNING. Routing and workspace are mbls_plan_verify_multiple_msgtable, _workspace_items and _locate_workspace_items, UNCHANGED: the committee source adds
  * no workspace item (its scratch is the committee entries').
  * OUT OF SCOPE: the verification stream, the shared-list and per-set message forms over committees, mbls_verify_multiple_batches over committees, the mbls_multi
- * handle and the shard form, a device-pointer append. (fast_aggregate_verify over sets that span several committees: "committee spans" above.) */
+ * handle and the shard form, a device-pointer append. (fast_aggregate_verify over sets that span several committees: "committee spans" above; verify_multiple
+ * over such sets: the section below.) */
 #define MBLS_VM_SET_SINGLE_KEY 0x80000000u
 int mbls_verify_multiple_committee_msgtable_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96, const uint32_t* d_cmt_idx,
                                                    const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
@@ -971,6 +973,59 @@ int mbls_verify_multiple_committee_msgtable_rng(mbls_ctx* ctx, const mbls_commit
 int mbls_verify_multiple_committee_msgtable_locate_rng(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs96, const uint32_t* cmt_idx,
                                                        const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n,
                                                        uint8_t* result, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user);
+
+/* verify_multiple OVER COMMITTEE SPANS AND THE RESIDENT MESSAGE TABLE. A block is imported through verify_multiple_aggregate_signatures: up to 8 attestations that
+ * each name up to 64 committees and carry one field over all of them (EIP-7549), the sync aggregate (one 512-member committee) and a few sets under one validator
+ * key (proposer signature, randao reveal, exits). These entries are the _committee_msgtable entries above with `d_cmt_idx` replaced by the span entries'
+ * `d_cmt_ids, n_cmt_ids, d_cmt_off` (csrc/mbls_vcs.h). Set i names cmt_ids[cmt_off[i] .. cmt_off[i + 1]) and the bits_stride bytes at bits + bits_stride * i; every
+ * rule of "committee spans" applies unchanged: absolute offsets, q <= MBLS_SPAN_MAX_COMMITTEES, SSZ bit order, bits at or above M ignored, bits_stride a multiple
+ * of 4, d_bits 4-byte aligned, the same id twice allowed, every segment on its own route from cmt_route under mbls_ctx_set_committee_route.
+ * A SINGLE-KEY set is a set of EXACTLY ONE id with bit 31 set (MBLS_VM_SET_SINGLE_KEY | key index): its list is that one index on the direct route, its field bytes
+ *   are NOT READ, an index outside the key table rejects the set through the key sum. A bit-31 id inside a set of two or more ids names no committee: malformed.
+ * MALFORMED SETS: an id at or above the committee count, q > 64, offsets that run backwards or past n_cmt_ids, M > 8 * bits_stride. DEVICE entries reject such a
+ *   set like a set that lists the key index 0xFFFFFFFF, reading in the span section's order (offsets before ids, ids before records, M before the field). HOST
+ *   entries (_rng) refuse the call with MBLS_ERR_ARGUMENT, nothing queued, the outputs untouched; so they do for a single-key index or a message index that names
+ *   nothing. n = 0 answers as mbls_verify_multiple_msgtable_device does. The _rng entries keep the reference's draw order exactly as
+ *   mbls_verify_multiple_committee_msgtable_rng does.
+ * CONTRACT. *d_result, *d_status, and for _locate every set byte and every set word, equal mbls_verify_multiple_sets_indexed_msgtable[_locate]_device on the same
+ *   signatures, scalars and message indices with every set's selected members spelled out in (segment, member) order -- under every mode of
+ *   mbls_ctx_set_vm_grouping and mbls_ctx_set_committee_route and every split factor below. As above the key phase flags neither an empty selection nor a sum at
+ *   infinity. A set of one plain committee returns what the _committee_msgtable entry returns. Everything behind the key sum is verify_multiple over the message
+ *   table, unchanged.
+ * KEY PHASE AND SPLIT. k_vcs_expand (one wave per set) leaves the span entries' direct list, missing list and record in the span scratch
+ *   (mbls_ctx_reserve_committee_span_items, reserved for all n sets before the first kernel). With split factor P = 1 one lane per set sums both lists, as the
+ *   span entries do: the throughput form. A block is a dozen sets, and one lane would walk a chain of up to 8 192 additions while the chip idles: with
+ *   P in {2, 4, 8, 16} each list is cut into P chunks -- chunk p of L entries is [floor(p L / P), floor((p + 1) L / P)) --, 2 P n lanes sum one chunk each into
+ *   workspace items BEHIND what the call reserves otherwise, and one lane per set adds the partial sums and the cached sums of the complement segments.
+ *   mbls_ctx_set_vm_span_split(ctx, 0 | 1 | 2 | 4 | 8 | 16): 0 (default; mbls_ctx_reset_tuning) chooses by rule -- P = 1 above 4 096 sets or once 2 n reaches a
+ *   round, else the largest P whose lanes fill at most half a round (4 P n <= round_items) and whose chunks of a full region (stride words =
+ *   min(8 * bits_stride, 64 * mbls_committees_max_members)) hold at least 8 entries --; another value is the factor asked for, halved until 2 P n fits a round;
+ *   anything else is MBLS_ERR_ARGUMENT. Measured (profiles/vm_committee_span_throughput.json): a block of 12 sets at 45 % participation 47.7 -> 6.5 ms.
+ * PLANNING. mbls_plan_verify_multiple_span(limits, n, table_size, stride_words, locate, split_mode, &split, &workspace_items), without a GPU (the name leaves the
+ *   "committee" out: the committee entries above have, and keep, no planning symbol of their own): the factor
+ *   P a call takes, and the workspace items it reserves -- mbls_plan_verify_multiple_msgtable[_locate]_workspace_items(limits, n, table_size, 0, 0) plus 2 P n for
+ *   P > 1 (nothing for P = 1: the one-lane form parks its intermediate point in the span scratch). Under mbls_ctx_set_vm_grouping other than 0 the first term is
+ *   that function's under the mode.
+ * OUT OF SCOPE: the verification stream, the shared-list and per-set message forms, mbls_verify_multiple_batches over spans, the mbls_multi handle and the shard
+ * form, a device-pointer append, splitting the chain of up to 64 cached sums. */
+int mbls_verify_multiple_committee_span_msgtable_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96, const uint32_t* d_cmt_ids,
+                                                        uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride,
+                                                        const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result,
+                                                        uint32_t* d_status, void* stream);
+int mbls_verify_multiple_committee_span_msgtable_locate_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96, const uint32_t* d_cmt_ids,
+                                                               uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride,
+                                                               const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n,
+                                                               uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream);
+int mbls_verify_multiple_committee_span_msgtable_rng(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs96, const uint32_t* cmt_ids,
+                                                     uint64_t n_cmt_ids, const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt,
+                                                     const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user);
+int mbls_verify_multiple_committee_span_msgtable_locate_rng(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs96, const uint32_t* cmt_ids,
+                                                            uint64_t n_cmt_ids, const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride,
+                                                            const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint8_t* result, uint8_t* set_results,
+                                                            uint32_t* set_status, mbls_scalar_source draw, void* user);
+int mbls_ctx_set_vm_span_split(mbls_ctx* ctx, int mode);
+int mbls_plan_verify_multiple_span(const mbls_limits* limits, uint64_t n, uint64_t table_size, uint64_t stride_words, int locate, int split_mode,
+                                             uint32_t* split, uint64_t* workspace_items);
 
 /* ---- batch helpers used to build inputs and caches on the device ---- */
 /* n x PublicKey::from_bytes[_unchecked] / from_uncompressed_bytes: errs[i] = MBLS_OK / MBLS_ERR_* per key */

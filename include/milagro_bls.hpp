@@ -711,7 +711,69 @@ public:
         const bool ok = vm(rng, sets, table, &per_set);
         return {ok, per_set};
     }
+    // AggregateSignature::verify_multiple_aggregate_signatures over a BLOCK's sets (mbls_verify_multiple_committee_span_msgtable_rng): an attestation names the
+    // committees of its committee_bits, in order, with aggregation_bits over their concatenated members (SpanSet::attestation; at most MBLS_SPAN_MAX_COMMITTEES
+    // ids -- the sync aggregate is a span of one committee), and a proposer signature, a randao reveal or an exit is under ONE key (SpanSet::single_key). The same
+    // bool as verify_multiple_aggregate_signatures on the spelled-out aggregate keys and messages, rng left in the same state. A malformed set, a key index or an
+    // entry index that names nothing throws (DeviceError).
+    struct SpanSet {
+        const AggregateSignature* signature; std::vector<uint32_t> committee_ids; Bytes aggregation_bits; uint32_t msg_index;
+        static SpanSet attestation(const AggregateSignature* sig, const std::vector<uint32_t>& committee_ids, const Bytes& aggregation_bits, uint32_t msg_index) {
+            for (uint32_t id : committee_ids) if (id & MBLS_VM_SET_SINGLE_KEY) throw std::invalid_argument("SpanSet::attestation: committee ids have 31 bits");
+            return SpanSet{sig, committee_ids, aggregation_bits, msg_index};
+        }
+        static SpanSet single_key(const AggregateSignature* sig, uint32_t key_index, uint32_t msg_index) {
+            if (key_index & MBLS_VM_SET_SINGLE_KEY) throw std::invalid_argument("SpanSet::single_key: key indices have 31 bits");
+            return SpanSet{sig, {MBLS_VM_SET_SINGLE_KEY | key_index}, Bytes(), msg_index};
+        }
+    };
+    // (the element type is deduced, so that a braced list -- `{}` for no sets -- keeps naming the GossipSet overloads above)
+    template <typename Rng, typename Set, typename = typename std::enable_if<std::is_same<Set, SpanSet>::value>::type>
+    bool verify_multiple_aggregate_signatures(Rng&& rng, const std::vector<Set>& sets, const MessageTable& table) const { return vm_span(rng, sets, table, nullptr); }
+    template <typename Rng, typename Set, typename = typename std::enable_if<std::is_same<Set, SpanSet>::value>::type>
+    std::pair<bool, std::vector<bool>> verify_multiple_aggregate_signatures_locate(Rng&& rng, const std::vector<Set>& sets, const MessageTable& table) const {
+        std::vector<bool> per_set;
+        const bool ok = vm_span(rng, sets, table, &per_set);
+        return {ok, per_set};
+    }
 private:
+    template <typename Rng>
+    bool vm_span(Rng& rng, const std::vector<SpanSet>& sets, const MessageTable& table, std::vector<bool>* per_set) const {
+        if (sets.empty()) return true;
+        const size_t n = sets.size();
+        size_t widest = 1;
+        for (const auto& s : sets) widest = std::max(widest, s.aggregation_bits.size());
+        const uint32_t stride = uint32_t((widest + 3) / 4 * 4);                         // one stride for every field, a multiple of 4
+        Bytes sigs, flat(size_t(stride) * n, 0); std::vector<uint32_t> ids, off{0}, idx;
+        for (size_t i = 0; i < n; i++) {
+            const SpanSet& s = sets[i];
+            sigs.insert(sigs.end(), s.signature->point.begin(), s.signature->point.end());
+            std::copy(s.aggregation_bits.begin(), s.aggregation_bits.end(), flat.begin() + size_t(stride) * i);
+            ids.insert(ids.end(), s.committee_ids.begin(), s.committee_ids.end());
+            if (ids.size() > 0xFFFFFFFFull) throw std::invalid_argument("verify_multiple_aggregate_signatures: span offsets are 32-bit");
+            off.push_back(uint32_t(ids.size())); idx.push_back(s.msg_index);
+        }
+        const uint64_t n_ids = ids.size();
+        if (ids.empty()) ids.push_back(0);
+        using R = typename std::remove_reference<Rng>::type;
+        struct src { R* rng; std::exception_ptr err; } u{&rng, nullptr};
+        mbls_scalar_source draw = [](void* user, uint64_t* out, uint64_t count) {
+            src* p = static_cast<src*>(user);
+            try { for (uint64_t i = 0; i < count; i++) out[i] = AggregateSignature::draw_scalar(*p->rng); }
+            catch (...) { p->err = std::current_exception(); for (uint64_t i = 0; i < count; i++) out[i] = 0; }        // never unwind through the C frames
+        };
+        uint8_t ok = 0;
+        std::vector<uint8_t> sres(per_set ? n : 0);
+        const int rc = per_set
+            ? mbls_verify_multiple_committee_span_msgtable_locate_rng(detail::ctx(), h_, sigs.data(), ids.data(), n_ids, off.data(), flat.data(), stride, table.handle(),
+                                                                      idx.data(), n, &ok, sres.data(), nullptr, draw, &u)
+            : mbls_verify_multiple_committee_span_msgtable_rng(detail::ctx(), h_, sigs.data(), ids.data(), n_ids, off.data(), flat.data(), stride, table.handle(), idx.data(),
+                                                               n, &ok, draw, &u);
+        if (u.err) std::rethrow_exception(u.err);
+        detail::check(rc);
+        if (per_set) per_set->assign(sres.begin(), sres.end());
+        return ok == 1;
+    }
     template <typename Rng>
     bool vm(Rng& rng, const std::vector<GossipSet>& sets, const MessageTable& table, std::vector<bool>* per_set) const {
         if (sets.empty()) return true;

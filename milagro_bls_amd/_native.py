@@ -341,6 +341,12 @@ SIGNATURES = {
     "mbls_verify_multiple_committee_msgtable_locate_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp]),
     "mbls_verify_multiple_committee_msgtable_rng": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, SCALAR_SOURCE, vp]),
     "mbls_verify_multiple_committee_msgtable_locate_rng": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, SCALAR_SOURCE, vp]),
+    "mbls_verify_multiple_committee_span_msgtable_device": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp]),
+    "mbls_verify_multiple_committee_span_msgtable_locate_device": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp]),
+    "mbls_verify_multiple_committee_span_msgtable_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, SCALAR_SOURCE, vp]),
+    "mbls_verify_multiple_committee_span_msgtable_locate_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, SCALAR_SOURCE, vp]),
+    "mbls_ctx_set_vm_span_split": (C.c_int, [vp, C.c_int]),
+    "mbls_plan_verify_multiple_span": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "mbls_plan_locate_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64]),
     "mbls_verify_multiple_batches_locate_device": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp,
                                                              vp, vp, vp]),
@@ -650,6 +656,20 @@ def plan_committee_span(sizes, eligible, bits, mode=CMT_ROUTE_AUTO):
     if rc != 0:
         raise MblsError(rc, "mbls_plan_committee_span")
     return int(mask.value), int(nd.value), int(nm.value)
+
+
+VM_SPAN_SPLITS = (0, 1, 2, 4, 8, 16)      # mbls_ctx_set_vm_span_split: 0 auto
+
+
+def plan_verify_multiple_committee_span(n, table_size, stride_words, locate=False, split_mode=0, limits=None):
+    """verify_multiple over committee spans (pure: no GPU): n sets over a message table of table_size entries, regions of stride_words words (min(8 * bits_stride,
+    64 * the table's largest committee)) -> (split factor P of the key phase, workspace items the call reserves)"""
+    L = limits if limits is not None else default_limits()
+    split, items = C.c_uint32(0), C.c_uint64(0)
+    rc = lib().mbls_plan_verify_multiple_span(C.byref(L), n, table_size, stride_words, int(bool(locate)), split_mode, C.byref(split), C.byref(items))
+    if rc != 0:
+        raise MblsError(rc, "mbls_plan_verify_multiple_span")
+    return int(split.value), int(items.value)
 
 
 class CommitteeTable:

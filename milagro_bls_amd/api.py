@@ -491,6 +491,62 @@ class AggregateSignature:
         return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:len(sets)]]
 
     @staticmethod
+    def verify_multiple_aggregate_signatures_committee_span(rng, signature_sets, committees, table):
+        """Not in the reference: verify_multiple_aggregate_signatures over a block's sets (mbls_verify_multiple_committee_span_msgtable_rng). A set is
+        (signature, committee_ids, field_bytes, message_index) -- the aggregate over the selected members of the committees `committee_ids` (at most 64) of
+        `committees` (_native.CommitteeTable), `field_bytes` ONE bitfield over their concatenated members (an Electra attestation's aggregation_bits; SSZ bit order,
+        bits at or above the members' total ignored) -- or (signature, SingleKey(index), None, message_index). Messages are entries of `table` (_native.MsgTable).
+        The same bool as verify_multiple_aggregate_signatures on the spelled-out aggregate keys and messages, `rng` left in the same state. A malformed set, a key
+        index or a message index that names nothing raises."""
+        return AggregateSignature._vm_committee_span(rng, signature_sets, committees, table, False)
+
+    @staticmethod
+    def verify_multiple_aggregate_signatures_committee_span_locate(rng, signature_sets, committees, table):
+        """verify_multiple_aggregate_signatures_committee_span, and in the same call (mbls_verify_multiple_committee_span_msgtable_locate_rng) which sets of a
+        rejected call are the bad ones. Returns (bool, list[bool]) with the semantics of verify_multiple_aggregate_signatures_shared_msgs_locate."""
+        return AggregateSignature._vm_committee_span(rng, signature_sets, committees, table, True)
+
+    @staticmethod
+    def _vm_committee_span(rng, signature_sets, committees, table, locate):
+        sets = list(signature_sets)
+        if not sets:
+            return (True, []) if locate else True
+        id_lists, fields = [], []
+        for s in sets:
+            if isinstance(s[1], SingleKey):
+                id_lists.append([N.VM_SET_SINGLE_KEY | s[1].index])
+                fields.append(b"")
+            else:
+                ids = [int(x) for x in s[1]]
+                if any(not 0 <= x < N.VM_SET_SINGLE_KEY for x in ids):
+                    raise ValueError("committee id out of range")
+                id_lists.append(ids)
+                fields.append(bytes(s[2]))
+        stride = max(4, (max(len(f) for f in fields) + 3) // 4 * 4)
+        n = len(sets)
+        ids = (C.c_uint32 * max(1, sum(map(len, id_lists))))(*[x for l in id_lists for x in l])
+        off = (C.c_uint32 * (n + 1))(*([0] + [sum(map(len, id_lists[:i + 1])) for i in range(n)]))
+        failed = []
+        cb = N.SCALAR_SOURCE(_reference_draw(rng, failed))
+        midx = (C.c_uint32 * n)(*[int(s[3]) for s in sets])
+        res = N.outbuf(1)
+        ctx = committees.ctx
+        S, B = N.cbuf(b"".join(s[0].point for s in sets)), N.cbuf(b"".join(f.ljust(stride, b"\0") for f in fields))
+        n_ids = sum(map(len, id_lists))
+        if locate:
+            sres = N.outbuf(n)
+            rc = N.lib().mbls_verify_multiple_committee_span_msgtable_locate_rng(ctx.handle, committees.handle, S, ids, n_ids, off, B, stride, table.handle, midx, n, res,
+                                                                                sres, None, cb, None)
+        else:
+            rc = N.lib().mbls_verify_multiple_committee_span_msgtable_rng(ctx.handle, committees.handle, S, ids, n_ids, off, B, stride, table.handle, midx, n, res, cb, None)
+        ctx.check(rc)
+        if failed:
+            raise failed[0]
+        if not locate:
+            return bool(bytes(res)[0])
+        return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:n]]
+
+    @staticmethod
     def verify_multiple_aggregate_signatures_batches(rng, batches):
         """Not in the reference: what calling verify_multiple_aggregate_signatures(rng, batch) once per batch, in order, returns -- as ONE call on the GPU
         (mbls_verify_multiple_batches_rng), which costs about what one such call costs. `batches`: an iterable of iterables of

@@ -792,3 +792,60 @@ def verify_multiple_committee_msgtable_locate_rng(committees, msg_table, sigs, c
     ctx.check(N.lib().mbls_verify_multiple_committee_msgtable_locate_rng(ctx.handle, committees.handle, N.cbuf(sigs), _midx(cmt_idx, n), _bits(bits, bits_stride, n),
                                                                          bits_stride, msg_table.handle, _midx(msg_idx, n), n, res, sres, sst, cb, None))
     return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:n]], list(sst)[:n]
+
+
+# ---- verify_multiple over committee spans and the resident message table (include/mbls.h, mbls_verify_multiple_committee_span_msgtable*): set i names the ids
+# cmt_ids[cmt_off[i] .. cmt_off[i + 1]) and one field over their concatenated members -- or is the one id VM_SET_SINGLE_KEY | key-table index, whose field is not read.
+plan_verify_multiple_committee_span = N.plan_verify_multiple_committee_span
+
+
+def set_vm_span_split(mode, ctx=None):
+    """the key phase of the entries below: 0 auto (csrc/mbls_vcs.h vcs_split), else the lanes each of a set's two key lists is cut over: 1, 2, 4, 8 or 16"""
+    ctx = ctx or _c()
+    ctx.check(N.lib().mbls_ctx_set_vm_span_split(ctx.handle, mode))
+
+
+def verify_multiple_committee_span_msgtable_device(committees, msg_table, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, d_msg_idx, d_rands, n, d_result,
+                                                   d_status=None, stream=None, ctx=None):
+    """verify_multiple_sets_indexed_msgtable_device with every set's signers named by a span of committees and one field (or by one key index) over an
+    N.CommitteeTable. Enqueues only: the bool at the device byte d_result, the status word at d_status (optional)."""
+    ctx = ctx or committees.ctx
+    ctx.check(N.lib().mbls_verify_multiple_committee_span_msgtable_device(ctx.handle, committees.handle, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride,
+                                                                          msg_table.handle, d_msg_idx, d_rands, n, d_result, d_status, stream))
+
+
+def verify_multiple_committee_span_msgtable_locate_device(committees, msg_table, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, d_msg_idx, d_rands, n,
+                                                          d_result, d_set_results, d_status=None, d_set_status=None, stream=None, ctx=None):
+    """The same, and in the same call one answer per SET: n result bytes at d_set_results (required), n status words at d_set_status (optional). Enqueues only."""
+    ctx = ctx or committees.ctx
+    ctx.check(N.lib().mbls_verify_multiple_committee_span_msgtable_locate_device(ctx.handle, committees.handle, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits,
+                                                                                 bits_stride, msg_table.handle, d_msg_idx, d_rands, n, d_result, d_status, d_set_results,
+                                                                                 d_set_status, stream))
+
+
+def verify_multiple_committee_span_msgtable_rng(committees, msg_table, sigs, cmt_id_lists, fields, bits_stride, msg_idx, draw, ctx=None):
+    """Host buffers and the reference's draw order (mbls_verify_multiple_committee_span_msgtable_rng; draw as verify_multiple_msgtable_rng takes it): set i names the
+    ids cmt_id_lists[i] with the field fields[i] (as fast_aggregate_verify_batch_committee_span takes them), or is [VM_SET_SINGLE_KEY | key index] with any field. A
+    malformed set, a key index or a message index that names nothing raises (MBLS_ERR_ARGUMENT). Returns the bool."""
+    ctx = ctx or committees.ctx
+    n = len(cmt_id_lists)
+    ids, n_ids, off, bits = _span(cmt_id_lists, fields, bits_stride)
+    res = N.outbuf(1)
+    cb = _scalar_source(draw)
+    ctx.check(N.lib().mbls_verify_multiple_committee_span_msgtable_rng(ctx.handle, committees.handle, N.cbuf(sigs), ids, n_ids, off, bits, bits_stride, msg_table.handle,
+                                                                       _midx(msg_idx, n), n, res, cb, None))
+    return bool(bytes(res)[0])
+
+
+def verify_multiple_committee_span_msgtable_locate_rng(committees, msg_table, sigs, cmt_id_lists, fields, bits_stride, msg_idx, draw, ctx=None):
+    """verify_multiple_committee_span_msgtable_rng with one answer per set. Returns (bool, set_results, set_status)."""
+    ctx = ctx or committees.ctx
+    n = len(cmt_id_lists)
+    ids, n_ids, off, bits = _span(cmt_id_lists, fields, bits_stride)
+    res = N.outbuf(1)
+    sres = N.outbuf(max(1, n))
+    sst = (C.c_uint32 * max(1, n))()
+    cb = _scalar_source(draw)
+    ctx.check(N.lib().mbls_verify_multiple_committee_span_msgtable_locate_rng(ctx.handle, committees.handle, N.cbuf(sigs), ids, n_ids, off, bits, bits_stride,
+                                                                              msg_table.handle, _midx(msg_idx, n), n, res, sres, sst, cb, None))
+    return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:n]], list(sst)[:n]

@@ -30,6 +30,7 @@
 #include "mbls_batch.h"
 #include "mbls_cmt_lanes.h"
 #include "mbls_cms_launch.h"
+#include "mbls_vcs_launch.h"
 #include "../../include/mbls.h"
 
 // The product library exists only with the generated routines: the host side below selects kernels (the fused subgroup verdict of
@@ -1289,6 +1290,7 @@ struct mbls_ctx {
     // table's largest committee -- and the count and route words of cmt_items items (d_cmt_cnt: [2][cmt_items]); mbls_ctx_reserve_committee_items
     uint32_t* d_cmt_list = nullptr; uint64_t cmt_words = 0; uint32_t* d_cmt_cnt = nullptr; uint64_t cmt_items = 0;
     int cmt_route_mode = 0;            // mbls_ctx_set_committee_route: 0 auto (cmt_route), 1 always direct, 2 complement whenever eligible
+    int vm_span_split = 0;             // mbls_ctx_set_vm_span_split: 0 auto (mbls_vcs.h vcs_split), else the split factor 1, 2, 4, 8 or 16
     // committee spans (mbls_cms.h): the items' list regions k_cms_expand writes for k_aggregate_cms_d -- cms_words uint32 in all, an item's region at the stride of
     // the call (cms_stride) --, and for cms_items items the records (d_cms_rec: [cms_items][MBLS_CMS_REC_DWORDS]) and the parked points (d_cms_park:
     // [MBLS_CMS_PARK_DWORDS][cms_items]); mbls_ctx_reserve_committee_span_items
@@ -1510,7 +1512,7 @@ extern "C" int mbls_ctx_set_coop_packing(mbls_ctx* c, uint64_t pairing_min_items
 }
 // every routing parameter back to its default (what mbls_ctx_create sets, environment included)
 static void ctx_default_tuning(mbls_ctx* c) {
-    c->vm_grouping = 0; c->cmt_route_mode = 0;
+    c->vm_grouping = 0; c->cmt_route_mode = 0; c->vm_span_split = 0;
     c->coop_max_items = MBLS_DEFAULT_COOP_MAX_ITEMS; c->coop_hash_max_items = MBLS_DEFAULT_COOP_HASH_MAX_ITEMS;
     c->coop_pack_min_items = 1024; c->coop_pack_max_items = 2048; c->coop_hash_pack_min_items = 768;
     hipDeviceProp_t prop;
@@ -1544,6 +1546,12 @@ extern "C" int mbls_ctx_set_committee_route(mbls_ctx* c, int mode) {
     if (!c || mode < 0 || mode > 2) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
     c->cmt_route_mode = mode; return MBLS_OK;
+}
+// verify_multiple over committee spans: 0 auto (mbls_vcs.h vcs_split), else the lanes each of a set's two key lists is cut over: 1, 2, 4, 8 or 16
+extern "C" int mbls_ctx_set_vm_span_split(mbls_ctx* c, int mode) {
+    if (!c || !vcs_split_mode_ok(mode)) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    c->vm_span_split = mode; return MBLS_OK;
 }
 extern "C" int mbls_plan_committee_route(uint32_t m, uint32_t s, int eligible, int mode) {
     if (mode < 0 || mode > 2 || m == 0 || m > MBLS_CMT_MAX_MEMBERS || s > m) return MBLS_ERR_ARGUMENT;
@@ -1958,6 +1966,17 @@ extern "C" uint64_t mbls_plan_verify_multiple_msgtable_locate_workspace_items(co
     if (!limits || !n || mode < 0 || mode > 2) return 0;
     mbls_vm_shared_msgs_plan vp; plan_vm_msgtable(*limits, n, table_size, named, mode, 0, &vp);
     return vsl_workspace_items(n, vmt_bound(n, table_size, named), vp.route == MBLS_VM_ROUTE_GROUPED, 0);
+}
+// verify_multiple over committee spans (mbls_verify_multiple_committee_span_msgtable*): the split factor of the key phase (mbls_vcs.h vcs_split) and what the call
+// reserves -- the message-table entries' figure plus the partial sums' items (vcs_extra_items: 2 P n under a split, none without)
+extern "C" int mbls_plan_verify_multiple_span(const mbls_limits* limits, uint64_t n, uint64_t table_size, uint64_t stride_words, int locate, int split_mode,
+                                                        uint32_t* split, uint64_t* workspace_items) {
+    if (!limits || !n || !split || !workspace_items || !vcs_split_mode_ok(split_mode)) return MBLS_ERR_ARGUMENT;
+    const uint32_t P = vcs_split(n, stride_words ? stride_words : 1, limits, split_mode);
+    mbls_vm_shared_msgs_plan vp; plan_vm_msgtable(*limits, n, table_size, 0, 0, 0, &vp);
+    const uint64_t w = locate ? vsl_workspace_items(n, vmt_bound(n, table_size, 0), vp.route == MBLS_VM_ROUTE_GROUPED, 0) : vp.workspace_items;
+    *split = P; *workspace_items = w + vcs_extra_items(n, P);
+    return MBLS_OK;
 }
 #ifdef MBLS_COOP_PROFILE
 extern "C" int mbls_coop_profile_read(unsigned long long out[64], int reset) {     // dev builds only (not declared in mbls.h)
@@ -3813,6 +3832,8 @@ struct vm_shared {
     // the _locate entries: the sets' answers as well (d_set_results required, d_set_status optional), shadow items behind phase one's workspace (mbls_vsl.h)
     bool locate = false; uint8_t* d_set_results = nullptr; uint32_t* d_set_status = nullptr;
     uint64_t shadow_first = 0;         // (set by vm_shared_plan_and_reserve)
+    // the span key source under a split (mbls_vcs.h): workspace items behind what the call plans today; base_items (set by vm_shared_plan_and_reserve): that figure
+    uint64_t extra_items = 0, base_items = 0;
     // the _msgtable entries: a resident table in place of the list (n_msgs stays 0; d_midx holds TABLE indices). named: the distinct entries the sets name where the
     // host has counted them (0: not known). Set by vm_shared_plan_and_reserve from the table as it is then: T, the bound on the named entries (mbls_vmt.h), its buffers.
     const mbls_msgtable* mt = nullptr; uint64_t named = 0;
@@ -3844,7 +3865,8 @@ static int vm_shared_plan_and_reserve(mbls_ctx* c, vm_shared& sh, uint64_t n) {
         plan_vm_msgtable(ctx_limits(c), n, sh.T, sh.named, c->vm_grouping, sh.longest, &sh.vp);
         const bool grouped = sh.vp.route == MBLS_VM_ROUTE_GROUPED;
         sh.shadow_first = vsl_shadow_first(n, sh.bound, grouped, 0);
-        const int rc = mbls_ctx_reserve(c, sh.locate ? vsl_workspace_items(n, sh.bound, grouped, 0) : sh.vp.workspace_items); if (rc) return rc;
+        sh.base_items = sh.locate ? vsl_workspace_items(n, sh.bound, grouped, 0) : sh.vp.workspace_items;
+        const int rc = mbls_ctx_reserve(c, sh.base_items + sh.extra_items); if (rc) return rc;
         return reserve_groups(c, sh.T);
     }
     plan_shared(ctx_limits(c), n, sh.n_msgs, false, false, &sh.sp);
@@ -3861,12 +3883,50 @@ struct vm_committee {
     const uint32_t* d_cmt_idx = nullptr; const uint8_t* d_bits = nullptr; uint32_t bits_stride = 0;
     const uint32_t* d_crecs = nullptr; uint64_t ccount = 0; const uint32_t* d_members = nullptr; uint32_t cmax = 0; const uint32_t* d_recs = nullptr; uint64_t tsize = 0;
     uint64_t list_stride() const { return cmax ? cmax : 1; }
+    // the span form (mbls_vcs.h; d_cmt_idx null): set i names ids d_cmt_ids[d_cmt_off[i] .. d_cmt_off[i + 1]) of n_cmt_ids
+    bool span = false; const uint32_t* d_cmt_ids = nullptr; uint64_t n_cmt_ids = 0; const uint32_t* d_cmt_off = nullptr;
+    uint64_t span_stride() const { return cms_stride(bits_stride, cmax); }
 };
+// for spans, the split factor of the call's key phase (it sizes the workspace: asked before that is reserved)
+static uint32_t vm_committee_split(const mbls_ctx* c, const vm_committee& vc, uint64_t n) {
+    const mbls_limits L = ctx_limits(c);
+    return vc.span ? vcs_split(n, vc.span_stride(), &L, c->vm_span_split) : 1u;
+}
 // the committee entries' checks (keys_of_committees: one context, key table alive, bits_stride, alignment of device bitfields); the caller holds the context's lock
 static int vm_committee_of(mbls_ctx* c, const mbls_committees* t, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride, bool device_bits, vm_committee* vc) {
     keysrc ks; const int rk = keys_of_committees(c, t, d_cmt_idx, d_bits, bits_stride, device_bits, &ks); if (rk) return rk;
     vc->t = t; vc->kt = t->kt; vc->d_cmt_idx = d_cmt_idx; vc->d_bits = d_bits; vc->bits_stride = bits_stride;
     vc->d_crecs = ks.d_crecs; vc->ccount = ks.ccount; vc->d_members = ks.d_members; vc->cmax = ks.cmax; vc->d_recs = ks.d_recs; vc->tsize = ks.tsize;
+    return MBLS_OK;
+}
+// the span form: the span entries' checks (keys_of_committee_span: no bound between bits_stride and the largest committee -- every set's M is checked on its own)
+static int vm_committee_span_of(mbls_ctx* c, const mbls_committees* t, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits,
+                                uint32_t bits_stride, bool device_bits, vm_committee* vc) {
+    keysrc ks; const int rk = keys_of_committee_span(c, t, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, device_bits, &ks); if (rk) return rk;
+    if (ks.ccount > (uint64_t)MBLS_VMC_SINGLE_KEY) ARGFAIL(c, "committee ids have 31 bits beside single-key sets");
+    vc->t = t; vc->kt = t->kt; vc->d_bits = d_bits; vc->bits_stride = bits_stride;
+    vc->d_crecs = ks.d_crecs; vc->ccount = ks.ccount; vc->d_members = ks.d_members; vc->cmax = ks.cmax; vc->d_recs = ks.d_recs; vc->tsize = ks.tsize;
+    vc->span = true; vc->d_cmt_ids = d_cmt_ids; vc->n_cmt_ids = n_cmt_ids; vc->d_cmt_off = d_cmt_off;
+    return MBLS_OK;
+}
+// the host entries' statement of "malformed" (what k_vcs_expand rejects per set refuses the whole call here), and a single-key index that names no key
+static int vm_committee_span_sets_ok(mbls_ctx* c, const host_committees& hc, const vm_committee& vc, uint64_t n) {
+    if (!hc.cmt_off || (hc.n_cmt_ids && !hc.cmt_ids) || (hc.bits_stride && !hc.bits)) ARGFAIL(c, "null buffer");
+    for (uint64_t i = 0; i < n; i++) {
+        uint32_t q = 0;
+        if (!cms_range_ok(hc.cmt_off[i], hc.cmt_off[i + 1], hc.n_cmt_ids, &q)) ARGFAIL(c, "cmt_off must be non-decreasing, inside cmt_ids, at most MBLS_SPAN_MAX_COMMITTEES ids per set");
+        const uint32_t* ids = hc.cmt_ids + hc.cmt_off[i];
+        if (q == 1u && vcs_is_single(q, ids[0])) {
+            if (vcs_single_names_nothing(ids[0], vc.tsize)) ARGFAIL(c, "cmt_ids names no key of the key table");
+            continue;
+        }
+        uint64_t M = 0;
+        for (uint32_t u = 0; u < q; u++) {
+            if (!vcs_id_ok(ids[u], vc.ccount)) ARGFAIL(c, "cmt_ids names no committee of the table");
+            M += hc.t->sizes[ids[u]];
+        }
+        if (!cms_field_ok(M, hc.bits_stride)) ARGFAIL(c, "bits_stride does not cover a set's committees");
+    }
     return MBLS_OK;
 }
 static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_pks, int pk_format,
@@ -3897,12 +3957,15 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
     // batches of at most half a round: two lanes per message in the message phase (items [0, 2 n), slots no other chain touches)
     const bool pair_hash = !sh && n <= c->split_max_items && 2 * n <= c->round_items;
     // a shared list: the workspace (sets, Miller items, positions, the list's own hash) and the table are reserved here, once, before the first kernel
+    // the span form of the committee source under a split: the partial sums' workspace items behind the call's own (mbls_vcs.h)
+    const uint32_t span_split = vc && sh ? vm_committee_split(c, *vc, n) : 1u;
+    if (vc && sh) sh->extra_items = vcs_extra_items(n, span_split);
     int rc = sh ? vm_shared_plan_and_reserve(c, *sh, n) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
-    // the committee source: the sets' index lists, count and route words for all n sets, reserved here with the workspace (grow-only: nothing when
-    // mbls_ctx_reserve_committee_items or the first half of an _rng call has been there)
+    // the committee source: the sets' index lists, count and route words for all n sets (spans: their regions, records and parked points), reserved here with the
+    // workspace (grow-only: nothing when mbls_ctx_reserve_committee[_span]_items or the first half of an _rng call has been there)
     if (vc) {
         if (!(sh && sh->mt) || d_partial) ARGFAIL(c, "internal: the committee source runs over a resident message table only");
-        rc = reserve_committee(c, n, vc->cmax); if (rc) return rc;
+        rc = vc->span ? reserve_committee_span(c, n, vc->span_stride()) : reserve_committee(c, n, vc->cmax); if (rc) return rc;
     }
     const bool grouped = sh && sh->vp.route == MBLS_VM_ROUTE_GROUPED;
     const uint64_t n_miller = grouped ? sh->vp.miller_items : n;
@@ -3940,7 +4003,18 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
         launch_hash(c, ws, d_msgs, msg_len, d_moff, c->d_status, n, s_msg, pair_hash); return MBLS_OK;
     };
     if (hash_first) { rc = message_phase(); if (rc) return rc; }
-    if (vc) {       // sets given by committee and bitfield, or by one key index (mbls_vmc.h): every set's list, then the indexed key sum over it with the complement's fix-up
+    if (vc && vc->span) {   // sets given by committee span, or by one key index (mbls_vcs.h): every set's two lists and record, then the span key sum -- one lane per
+        // set, or under a split one lane per chunk of a list (workspace items and status words behind the call's own and its extra lane) and one combining lane per set
+        const uint64_t ls = vc->span_stride();
+        mbls_vcs_launch_expand(vc->d_crecs, vc->ccount, vc->d_members, vc->d_cmt_ids, vc->n_cmt_ids, vc->d_cmt_off, vc->d_bits, vc->bits_stride, c->cmt_route_mode,
+                               c->d_cms_list, ls, c->d_cms_rec, n, s);
+        if (span_split > 1u)
+            mbls_vcs_launch_split(ws, sh->base_items + 1, span_split, vc->d_recs, vc->tsize, c->d_cms_list, ls, c->d_cms_rec, vc->d_crecs, vc->d_cmt_ids, vc->d_cmt_off,
+                                  c->d_status + sh->base_items + 1, c->d_status, n, s);
+        else
+            mbls_vcs_launch_aggregate(ws, vc->d_recs, vc->tsize, c->d_cms_list, ls, c->d_cms_rec, vc->d_crecs, vc->d_cmt_ids, vc->d_cmt_off, c->d_cms_park, c->cms_items,
+                                      c->d_status, n, s);
+    } else if (vc) {       // sets given by committee and bitfield, or by one key index (mbls_vmc.h): every set's list, then the indexed key sum over it with the complement's fix-up
         const uint64_t ls = vc->list_stride();
         uint32_t* const cnt = c->d_cmt_cnt; uint32_t* const route = c->d_cmt_cnt + c->cmt_items;
         hipLaunchKernelGGL(k_vmc_expand, dim3((unsigned)n), dim3(WG), 0, s, vc->d_crecs, vc->ccount, vc->d_members, vc->d_cmt_idx, vc->d_bits, vc->bits_stride, c->cmt_route_mode,
@@ -4121,9 +4195,10 @@ extern "C" int mbls_verify_multiple_aggregate_signatures(mbls_ctx* c, const uint
 // tests its signatures (they stay in the workspace), starts the message phase and reads the verdicts back; phase 2 takes the scalars and runs the rest -- up to the
 // bool (d_partial == nullptr) or up to the shard's record. The caller holds the context's lock across both.
 struct vm_rng_stage {
-    sbuf ds, da, dm, dr, dmo, dout, dmi, dci;       // (dci: the sets' descriptor words of the committee form, whose bitfields travel in da -- it has no aggregate keys)
+    sbuf ds, da, dm, dr, dmo, dout, dmi, dci, dso;  // (dci: the sets' descriptor words of the committee form, whose bitfields travel in da -- it has no aggregate keys;
+                                                    //  dso: the span form's offsets, its ids in dci)
     const uint8_t* d_msgs = nullptr; const uint64_t* d_moff = nullptr;
-    vm_rng_stage(mbls_ctx* c) : ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dmo(c, 6), dout(c, 4), dmi(c, 7), dci(c, 10) {}
+    vm_rng_stage(mbls_ctx* c) : ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dmo(c, 6), dout(c, 4), dmi(c, 7), dci(c, 10), dso(c, 5) {}
 };
 static void vm_rng_drain(mbls_ctx* c) { (void)hipStreamSynchronize(c->hs_a); (void)hipStreamSynchronize(c->hs_b); (void)hipStreamSynchronize(c->hs_c); c->ws_pending = false; }
 // sigs96 / apks96: the shard's own sets; msgs: the buffer the (absolute) offsets of moff[0 .. n] point into, or n x msg_len bytes. -> MBLS_OK and st[0 .. n) (status words)
@@ -4141,7 +4216,11 @@ static int vm_rng_phase1(mbls_ctx* c, vm_rng_stage& g, const uint8_t* sigs96, co
     const size_t msg_total = moff ? (size_t)(moff[nm] - moff[0]) : (size_t)msg_len * nm;
     if (g.ds.up(sigs96, 96 * n) != hipSuccess || (!hc && g.da.up(apks96, 96 * n) != hipSuccess) || g.dm.up(msgs ? msgs + msg_first : nullptr, msg_total) != hipSuccess ||
         g.dr.alloc(8 * n) != hipSuccess || (moff && g.dmo.up(moff, 8 * (nm + 1)) != hipSuccess)) return MBLS_ERR_DEVICE;
-    if (hc) {
+    if (hc && hc->span) {       // the ids take the descriptor words' slot, the span offsets one of their own
+        if (g.da.up(hc->bits, (size_t)hc->bits_stride * n) != hipSuccess || g.dci.up(hc->cmt_ids, 4 * hc->n_cmt_ids) != hipSuccess ||
+            g.dso.up(hc->cmt_off, 4 * (n + 1)) != hipSuccess) return MBLS_ERR_DEVICE;
+        vc->d_bits = g.da.as<uint8_t>(); vc->d_cmt_ids = g.dci.as<uint32_t>(); vc->d_cmt_off = g.dso.as<uint32_t>();
+    } else if (hc) {
         if (g.da.up(hc->bits, (size_t)hc->bits_stride * n) != hipSuccess || g.dci.up(hc->cmt_idx, 4 * n) != hipSuccess) return MBLS_ERR_DEVICE;
         vc->d_bits = g.da.as<uint8_t>(); vc->d_cmt_idx = g.dci.as<uint32_t>();
     }
@@ -4149,8 +4228,9 @@ static int vm_rng_phase1(mbls_ctx* c, vm_rng_stage& g, const uint8_t* sigs96, co
     if (sh) { if (g.dmi.up(msg_idx, 4 * n) != hipSuccess) return MBLS_ERR_DEVICE; sh->d_midx = g.dmi.as<uint32_t>(); }
     hipStream_t s = c->hs_a;
     const bool pair_hash = !sh && n <= c->split_max_items && 2 * n <= c->round_items, fork = 2 * n <= c->round_items;       // as verify_multiple_impl decides
+    if (vc && sh) sh->extra_items = vcs_extra_items(n, vm_committee_split(c, *vc, n));      // (the whole call's workspace, as verify_multiple_impl will ask for it)
     int rc = sh ? vm_shared_plan_and_reserve(c, *sh, n) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
-    if (vc) { rc = reserve_committee(c, n, vc->cmax); if (rc) return rc; }
+    if (vc) { rc = vc->span ? reserve_committee_span(c, n, vc->span_stride()) : reserve_committee(c, n, vc->cmax); if (rc) return rc; }
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     rc = ws_acquire(c, s); if (rc) return rc;
     if (sh && sh->mt) { rc = msgtable_acquire(c, sh->mt, s); if (rc) return rc; }      // (before the fork: the message stream inherits the table's last append)
@@ -4323,11 +4403,13 @@ static int vm_shared_rng_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t*
     if (locate && !set_results) ARGFAIL(c, "null set results");
     if (mt && mt->c != c) ARGFAIL(c, "message table belongs to another context");
     vm_committee vcs; vm_committee* const vc = hc ? &vcs : nullptr;
-    if (hc) { const int rk = vm_committee_of(c, hc->t, nullptr, nullptr, hc->bits_stride, false, vc); if (rk) return rk; }
+    if (hc && hc->span) { const int rk = vm_committee_span_of(c, hc->t, nullptr, hc->n_cmt_ids, nullptr, nullptr, hc->bits_stride, false, vc); if (rk) return rk; }
+    else if (hc) { const int rk = vm_committee_of(c, hc->t, nullptr, nullptr, hc->bits_stride, false, vc); if (rk) return rk; }
     if (n == 0) { *result = 1; return MBLS_OK; }                            // empty iterator: true, the generator untouched
     if (!draw) ARGFAIL(c, "no scalar source");
     vm_shared sh; sh.n_msgs = n_msgs; sh.mt = mt;
-    if (hc) {
+    if (hc && hc->span) { const int ri = vm_committee_span_sets_ok(c, *hc, *vc, n); if (ri) return ri; }
+    else if (hc) {
         if (!hc->cmt_idx || !hc->bits) ARGFAIL(c, "null buffer");
         for (uint64_t i = 0; i < n; i++)
             if (vmc_names_nothing(hc->cmt_idx[i], vc->ccount, vc->tsize))
@@ -4478,6 +4560,52 @@ extern "C" int mbls_verify_multiple_committee_msgtable_locate_rng(mbls_ctx* c, c
         mbls_scalar_source draw, void* user) {
     if (!t || !mt) return MBLS_ERR_ARGUMENT;
     const host_committees hc = {t, cmt_idx, bits, bits_stride};
+    return vm_shared_rng_impl(c, sigs96, nullptr, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, true, set_results, set_status, mt, &hc);
+}
+
+// ---- verify_multiple over committee spans and the resident message table (include/mbls.h, mbls_verify_multiple_committee_span_msgtable*; rules: mbls_vcs.h): the
+// entries above with every set's signers named by a range of committee ids and one field over their concatenated members, or by one key index. The key source is
+// verify_multiple_impl's committee source in its span form: k_vcs_expand, then k_aggregate_vcs_d or, under a split, k_vcs_partial_d and k_vcs_combine (mbls_vcs.hip).
+static int vm_committee_span_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids, const uint32_t* d_cmt_off,
+                                    const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n,
+                                    uint8_t* d_result, uint32_t* d_status_or, void* stream, bool locate, uint8_t* d_set_results, uint32_t* d_set_status) {
+    if (!c || !t || !mt || !d_result) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
+    if (locate && !d_set_results) ARGFAIL(c, "null set results");
+    vm_committee vc; const int rk = vm_committee_span_of(c, t, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, true, &vc); if (rk) return rk;
+    if (n && (!d_cmt_off || (n_cmt_ids && !d_cmt_ids) || (bits_stride && !d_bits))) ARGFAIL(c, "null key buffer");
+    if (n && !d_midx) ARGFAIL(c, "null buffer");
+    if (n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
+    vm_shared sh; sh.d_midx = d_midx; sh.mt = mt; sh.locate = locate; sh.d_set_results = d_set_results; sh.d_set_status = d_set_status;
+    return verify_multiple_impl(c, d_sigs, nullptr, nullptr, MBLS_PK_UNCOMPRESSED, nullptr, 0, nullptr, 0, nullptr, d_rands, n, d_result, d_status_or, stream, nullptr, nullptr,
+                                nullptr, false, false, &sh, &vc);
+}
+extern "C" int mbls_verify_multiple_committee_span_msgtable_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids,
+        const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n,
+        uint8_t* d_result, uint32_t* d_status, void* stream) {
+    return vm_committee_span_device(c, t, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_result, d_status, stream, false, nullptr,
+                                    nullptr);
+}
+extern "C" int mbls_verify_multiple_committee_span_msgtable_locate_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_ids,
+        uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands,
+        uint64_t n, uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
+    if (!d_set_results) return MBLS_ERR_ARGUMENT;
+    return vm_committee_span_device(c, t, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_result, d_status, stream, true,
+                                    d_set_results, d_set_status);
+}
+extern "C" int mbls_verify_multiple_committee_span_msgtable_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_ids, uint64_t n_cmt_ids,
+        const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint8_t* result,
+        mbls_scalar_source draw, void* user) {
+    if (!t || !mt) return MBLS_ERR_ARGUMENT;
+    const host_committees hc = {t, nullptr, bits, bits_stride, true, cmt_ids, n_cmt_ids, cmt_off};
+    return vm_shared_rng_impl(c, sigs96, nullptr, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, false, nullptr, nullptr, mt, &hc);
+}
+extern "C" int mbls_verify_multiple_committee_span_msgtable_locate_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_ids,
+        uint64_t n_cmt_ids, const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint8_t* result,
+        uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user) {
+    if (!t || !mt) return MBLS_ERR_ARGUMENT;
+    const host_committees hc = {t, nullptr, bits, bits_stride, true, cmt_ids, n_cmt_ids, cmt_off};
     return vm_shared_rng_impl(c, sigs96, nullptr, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, true, set_results, set_status, mt, &hc);
 }
 

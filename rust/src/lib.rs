@@ -74,6 +74,23 @@ pub struct mbls_stream_opts {
     pub depth: u32,
     pub policy: u32,
 }
+/// include/mbls.h `mbls_limits`: the routing limits the plan functions take (`mbls_default_limits` fills them for a device's round)
+#[allow(non_camel_case_types)]
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct mbls_limits {
+    pub round_items: u64,
+    pub coop_max_items: u64,
+    pub coop_hash_max_items: u64,
+    pub coop_pack_min_items: u64,
+    pub coop_pack_max_items: u64,
+    pub coop_hash_pack_min_items: u64,
+    pub split_max_items: u64,
+    pub fork_max_items: u64,
+    pub hash2_max_items: u64,
+    pub tracks_min_rest: u64,
+    pub tracks_side_max: u64,
+}
 extern "C" {
     fn mbls_ctx_create(out: *mut *mut MblsCtx, device_id: c_int) -> c_int;
     fn mbls_last_error(ctx: *mut MblsCtx) -> *const c_char;
@@ -236,6 +253,24 @@ extern "C" {
     fn mbls_verify_multiple_committee_msgtable_locate_rng(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs96: *const u8, cmt_idx: *const u32, bits: *const u8,
                                                           bits_stride: u32, mt: *const mbls_msgtable, msg_idx: *const u32, n: u64, result: *mut u8, set_results: *mut u8,
                                                           set_status: *mut u32, draw: MblsScalarSource, user: *mut c_void) -> c_int;
+    // verify_multiple over committee spans and the resident message table: a set is a range of committee ids with one field, or the one id MBLS_VM_SET_SINGLE_KEY | key index
+    fn mbls_verify_multiple_committee_span_msgtable_device(ctx: *mut MblsCtx, committees: *const mbls_committees, d_sigs96: *const u8, d_cmt_ids: *const u32, n_cmt_ids: u64,
+                                                           d_cmt_off: *const u32, d_bits: *const u8, bits_stride: u32, mt: *const mbls_msgtable, d_msg_idx: *const u32,
+                                                           d_rands: *const u64, n: u64, d_result: *mut u8, d_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_committee_span_msgtable_locate_device(ctx: *mut MblsCtx, committees: *const mbls_committees, d_sigs96: *const u8, d_cmt_ids: *const u32,
+                                                                  n_cmt_ids: u64, d_cmt_off: *const u32, d_bits: *const u8, bits_stride: u32, mt: *const mbls_msgtable,
+                                                                  d_msg_idx: *const u32, d_rands: *const u64, n: u64, d_result: *mut u8, d_status: *mut u32,
+                                                                  d_set_results: *mut u8, d_set_status: *mut u32, stream: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_committee_span_msgtable_rng(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs96: *const u8, cmt_ids: *const u32, n_cmt_ids: u64,
+                                                        cmt_off: *const u32, bits: *const u8, bits_stride: u32, mt: *const mbls_msgtable, msg_idx: *const u32, n: u64,
+                                                        result: *mut u8, draw: MblsScalarSource, user: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_committee_span_msgtable_locate_rng(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs96: *const u8, cmt_ids: *const u32, n_cmt_ids: u64,
+                                                               cmt_off: *const u32, bits: *const u8, bits_stride: u32, mt: *const mbls_msgtable, msg_idx: *const u32, n: u64,
+                                                               result: *mut u8, set_results: *mut u8, set_status: *mut u32, draw: MblsScalarSource,
+                                                               user: *mut c_void) -> c_int;
+    fn mbls_ctx_set_vm_span_split(ctx: *mut MblsCtx, mode: c_int) -> c_int;
+    fn mbls_plan_verify_multiple_span(limits: *const mbls_limits, n: u64, table_size: u64, stride_words: u64, locate: c_int, split_mode: c_int, split: *mut u32,
+                                                workspace_items: *mut u64) -> c_int;
     fn mbls_stream_create_msgtable(ctx: *mut MblsCtx, mode: c_int, pk_format: c_int, t: *const MblsKeyTable, mt: *mut mbls_msgtable, opts: *const mbls_stream_opts,
                                    out: *mut *mut mbls_stream) -> c_int;
     fn mbls_stream_submit_msgidx(s: *mut mbls_stream, sigs: *const u8, msg_idx: *const u32, pks: *const u8, key_idx: *const u32, pk_offsets: *const u32, n: u64, k: u32,
@@ -1713,6 +1748,100 @@ impl CommitteeTable {
         }
         (rc == 0 && ok == 1, sres.iter().map(|&b| rc == 0 && b == 1).collect())
     }
+    /// `AggregateSignature::verify_multiple_aggregate_signatures` over a block's sets (`mbls_verify_multiple_committee_span_msgtable_rng`): every set is a
+    /// signature, a `SpanKeys` -- the committees an attestation names with ONE field over their concatenated members, or ONE key of the key table -- and an entry
+    /// index of `table`. The same bool as that function on the spelled-out aggregate keys and messages, `rng` left in the same state. A malformed set, a key index
+    /// or an entry index that names nothing gives false.
+    pub fn verify_multiple_aggregate_signatures_spans<'a, R, I>(&self, rng: &mut R, signature_sets: I, table: &MessageTable) -> bool
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, SpanKeys<'a>, u32)>,
+    {
+        self.vm_committee_span(rng, signature_sets, table, false).0
+    }
+    /// The same, and in the same call (`mbls_verify_multiple_committee_span_msgtable_locate_rng`) which sets of a rejected call are the bad ones.
+    pub fn verify_multiple_aggregate_signatures_spans_locate<'a, R, I>(&self, rng: &mut R, signature_sets: I, table: &MessageTable) -> (bool, Vec<bool>)
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, SpanKeys<'a>, u32)>,
+    {
+        self.vm_committee_span(rng, signature_sets, table, true)
+    }
+    fn vm_committee_span<'a, R, I>(&self, rng: &mut R, signature_sets: I, table: &MessageTable, locate: bool) -> (bool, Vec<bool>)
+    where
+        R: Rng + ?Sized,
+        I: Iterator<Item = (&'a AggregateSignature, SpanKeys<'a>, u32)>,
+    {
+        let sets: Vec<(&AggregateSignature, SpanKeys, u32)> = signature_sets.collect();
+        let n = sets.len();
+        if n == 0 {
+            return (true, Vec::new());
+        }
+        let mut sigs = Vec::new();
+        let (mut ids, mut off, mut idx): (Vec<u32>, Vec<u32>, Vec<u32>) = (Vec::new(), vec![0], Vec::with_capacity(n));
+        let mut fields: Vec<&[u8]> = Vec::with_capacity(n);
+        for (s, k, j) in &sets {
+            sigs.extend_from_slice(&s.point);
+            match *k {
+                SpanKeys::Committees { ids: c, bits } => {
+                    assert!(c.iter().all(|id| id & VM_SET_SINGLE_KEY == 0), "committee ids have 31 bits");
+                    ids.extend_from_slice(c);
+                    fields.push(bits);
+                }
+                SpanKeys::SingleKey(index) => {
+                    assert!(index & VM_SET_SINGLE_KEY == 0, "key indices have 31 bits");
+                    ids.push(VM_SET_SINGLE_KEY | index);
+                    fields.push(&[]);
+                }
+            }
+            off.push(ids.len() as u32);
+            idx.push(*j);
+        }
+        let stride = ((fields.iter().map(|f| f.len()).max().unwrap_or(0).max(1) + 3) / 4 * 4) as u32;        // one stride for every field, a multiple of 4
+        let mut flat = vec![0u8; stride as usize * n];
+        for (i, f) in fields.iter().enumerate() {
+            flat[stride as usize * i..stride as usize * i + f.len()].copy_from_slice(f);
+        }
+        let n_ids = ids.len() as u64;
+        if ids.is_empty() {
+            ids.push(0);
+        }
+        let mut st = DrawState { rng, panic: None };
+        let mut ok: u8 = 0;
+        let mut sres: Vec<u8> = vec![0; if locate { n } else { 0 }];
+        let rc = unsafe {
+            if locate {
+                mbls_verify_multiple_committee_span_msgtable_locate_rng(ctx(), self.h, sigs.as_ptr(), ids.as_ptr(), n_ids, off.as_ptr(), flat.as_ptr(), stride, table.h,
+                                                                        idx.as_ptr(), n as u64, &mut ok, sres.as_mut_ptr(), std::ptr::null_mut(), draw_scalars::<R>,
+                                                                        &mut st as *mut DrawState<R> as *mut c_void)
+            } else {
+                mbls_verify_multiple_committee_span_msgtable_rng(ctx(), self.h, sigs.as_ptr(), ids.as_ptr(), n_ids, off.as_ptr(), flat.as_ptr(), stride, table.h, idx.as_ptr(),
+                                                                 n as u64, &mut ok, draw_scalars::<R>, &mut st as *mut DrawState<R> as *mut c_void)
+            }
+        };
+        if let Some(payload) = st.panic.take() {
+            std::panic::resume_unwind(payload);
+        }
+        (rc == 0 && ok == 1, sres.iter().map(|&b| rc == 0 && b == 1).collect())
+    }
+    /// The split factor of the key phase of the span form above: 0 auto, else 1, 2, 4, 8 or 16 lanes per key list (`mbls_ctx_set_vm_span_split`).
+    pub fn set_vm_span_split(mode: u32) -> bool {
+        unsafe { mbls_ctx_set_vm_span_split(ctx(), mode as c_int) == 0 }
+    }
+    /// What a call of the span form over `n` sets takes, without a GPU (`mbls_plan_verify_multiple_span`): (split factor, workspace items).
+    pub fn plan_verify_multiple_spans(limits: &mbls_limits, n: u64, table_size: u64, stride_words: u64, locate: bool, split_mode: u32) -> Option<(u32, u64)> {
+        let (mut split, mut items) = (0u32, 0u64);
+        let rc = unsafe { mbls_plan_verify_multiple_span(limits, n, table_size, stride_words, locate as c_int, split_mode as c_int, &mut split, &mut items) };
+        if rc == 0 { Some((split, items)) } else { None }
+    }
+}
+/// The keys of one set of `CommitteeTable::verify_multiple_aggregate_signatures_spans`.
+#[derive(Clone, Copy)]
+pub enum SpanKeys<'a> {
+    /// the selected members of the committees `ids` (at most `SPAN_MAX_COMMITTEES`), `bits` ONE field over their concatenated members (SSZ bit order)
+    Committees { ids: &'a [u32], bits: &'a [u8] },
+    /// entry `index` of the key table the committee table is bound to: a proposer signature, a randao reveal, an exit
+    SingleKey(u32),
 }
 /// `MBLS_VM_SET_SINGLE_KEY` of include/mbls.h: bit 31 of a set's descriptor word marks a set under one key of the key table.
 pub const VM_SET_SINGLE_KEY: u32 = 0x8000_0000;
