@@ -1040,8 +1040,20 @@ int mbls_sig_check_batch(mbls_ctx* ctx, const uint8_t* in96, uint64_t n, uint8_t
  * scalar's other uses (digit extraction, sign / zero handling) are selections as well. mbls_ctx_set_secret_ops(ctx, 1) (environment MBLS_UNSAFE_SECRET_OPS
  * for new contexts) switches both to the faster forms that read ONE record at a key-dependent address -- for building test and bench inputs from throw-away
  * keys only (measured at 2^16: signing 14.5 instead of 15.3 ms, sk -> pk 0.9 instead of 2.7 ms). This is NOT a claim of resistance against power or fault analysis, and a GPU shared with an attacker's kernels
- * is not a place for long-term keys either way. What the calls leave behind is wiped: the staged keys, the digit / selection buffers and the workspace slots
- * of the partial products and tables are zeroed on the stream before the call's workspace is released.
+ * is not a place for long-term keys either way.
+ * WHAT THE CALLS LEAVE BEHIND (tests/test_gpu_secret_residue.py reads every device allocation of the context back -- mbls_ctx_residue_read below -- after the
+ * same call on two key sets that differ in every digit, and holds the two images EQUAL but for the staged output; the list is what that test holds to zero).
+ * Zeroed on the stream before the call's workspace is released, for the items of the largest chunk (which every chunk reuses):
+ *   signing   workspace slots 3..6 (psi^j(H)), 25..30 (the partial products and their sums), 43..48 (the sum tree's parked operands), 49..102 (the window
+ *             tables and the selected records) of items [0, 4 * chunk);
+ *   sk -> pk  d_sksel (constant-time form: the selected multiples) or d_skidx (variable-time form: the keys' hexadecimal digits), workspace slots 0..2 (the
+ *             key sum) and the status words of items [0, chunk) -- MBLS_ST_PK_INFINITY there marks a key with a digit 0;
+ *   the host entries (mbls_sign_batch, mbls_sk_to_pk_batch, mbls_sign, mbls_pk_from_secret_key) besides: the staged keys, stage[0] bytes [0, 32 n), also when
+ *             the device entry returns an error. Their staged OUTPUT -- stage[2] bytes [0, 96 n) / stage[1] bytes [0, 48 n or 96 n) -- stays until the next call.
+ * Nothing else the context owns depends on the keys once the call's stream work is done. NOT claimed: LDS and registers after a kernel has ended (the spill
+ * area of k_sign_blind and the tree levels, the accumulators of k_sk_select); memory the context has returned to the allocator with hipFree (a growing
+ * workspace or staging buffer is freed as it is); a call that fails in the HIP runtime midway (the wipes are stream work like the rest); the caller's own
+ * buffers of the device entries.
  * n x Signature::new / PublicKey::from_secret_key. Secret keys are NOT range-checked here: any 32-byte big-endian value gives [sk mod r] H(msg) /
  * [sk mod r] G1. The device entries use the context's workspace (four items per signature, in chunks of 65 536 signatures) and wait for its
  * previous user like the verification entries; they only enqueue. */
@@ -1099,6 +1111,16 @@ int mbls_fp_mul_batch(mbls_ctx* ctx, const uint8_t* a48, const uint8_t* b48, uin
  * int32 register contents in[w * n + i], w < n_in, and leaves the registers the probe lists in out[w * n + i], w < n_out; no value is interpreted or checked. MBLS_ERR_DEVICE if the library was built without the generated routines. */
 int mbls_dform_probe_shape(int op, uint32_t* n_in, uint32_t* n_out);
 int mbls_dform_probe(mbls_ctx* ctx, int op, const int32_t* in, uint64_t n, int32_t* out);
+/* test probe: what a call LEFT in device memory (tests/test_gpu_secret_residue.py; "SECRET KEYS ON THE DEVICE" above). Reads only: no kernel is launched, no
+ * secret is taken. mbls_ctx_residue_regions lists every device allocation the context owns: names[MBLS_RESIDUE_NAME_BYTES * i] (NUL-terminated) and bytes[i]
+ * for region i < *n_regions, in an order that never changes -- "d_w" (the workspace: word-major, row 12 * slot + limb of *cap items of 4 bytes), "d_status",
+ * "d_results", "d_scalar", "d_skidx", "d_sksel", the key staging, the shared-message and grouping tables, the committee and span scratches, "d_coop", "d_gtab",
+ * then "stage[0]" .. the staging buffers of the host entries. A region that is not allocated yet has 0 bytes. names = bytes = NULL: the count alone;
+ * max_regions below the count: MBLS_ERR_ARGUMENT. Key tables, message tables and committee tables are objects of their own and are not listed.
+ * mbls_ctx_residue_read drains the device (hipDeviceSynchronize, under the context's lock) and copies [offset, offset + bytes) of region `region` to out. */
+#define MBLS_RESIDUE_NAME_BYTES 16
+int mbls_ctx_residue_regions(mbls_ctx* ctx, char* names, uint64_t* bytes, uint32_t max_regions, uint32_t* n_regions, uint64_t* cap);
+int mbls_ctx_residue_read(mbls_ctx* ctx, uint32_t region, uint64_t offset, uint64_t bytes, uint8_t* out);
 /* integer-ALU calibration: runs `iters` dependent Fp multiplications per lane on n lanes, returns elapsed ms */
 int mbls_fp_mul_bench(mbls_ctx* ctx, uint64_t n_lanes, uint32_t iters, float* ms_out);
 

@@ -18,6 +18,7 @@ ERR_DEVICE = 100
 ERR_ARGUMENT = 101
 PENDING = 102                   # mbls_stream_query: the call is not done
 PK_COMPRESSED, PK_UNCOMPRESSED = 0, 1
+RESIDUE_NAME_BYTES = 16           # MBLS_RESIDUE_NAME_BYTES
 VM_PARTIAL_BYTES = 896          # include/mbls.h MBLS_VM_PARTIAL_BYTES
 N_PHASES = 6
 PHASE_NAMES = ("aggregate", "sig", "hash", "miller", "final", "pack")
@@ -372,6 +373,8 @@ SIGNATURES = {
     "mbls_final_exp_probe": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_int]),
     "mbls_dform_probe_shape": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mbls_dform_probe": (C.c_int, [vp, C.c_int, vp, C.c_uint64, vp]),
+    "mbls_ctx_residue_regions": (C.c_int, [vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "mbls_ctx_residue_read": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_uint64, vp]),
     "mbls_fp_mul_bench": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]),
     "mbls_valu_bench": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "mbls_multi_create": (C.c_int, [C.POINTER(vp), C.POINTER(C.c_int), C.c_int]),
@@ -515,6 +518,23 @@ class Context:
     def set_secret_ops(self, variable_time):
         """False (default): signing / sk -> pk look their tables up by scan + selection (constant-time access); True: by key-dependent address (throw-away keys only)"""
         self.check(lib().mbls_ctx_set_secret_ops(self._h, int(bool(variable_time))))
+
+    def residue_regions(self):
+        """test probe (include/mbls.h, mbls_ctx_residue_regions): ([(name, bytes)] of every device allocation the context owns, in the table's order; the
+        workspace's capacity in items)"""
+        cnt, cap = C.c_uint32(0), C.c_uint64(0)
+        self.check(lib().mbls_ctx_residue_regions(self._h, None, None, 0, C.byref(cnt), C.byref(cap)))
+        names = C.create_string_buffer(RESIDUE_NAME_BYTES * cnt.value)
+        sizes = (C.c_uint64 * cnt.value)()
+        self.check(lib().mbls_ctx_residue_regions(self._h, names, sizes, cnt.value, C.byref(cnt), C.byref(cap)))
+        raw = names.raw
+        return [(raw[RESIDUE_NAME_BYTES * i:RESIDUE_NAME_BYTES * (i + 1)].split(b"\0", 1)[0].decode(), int(sizes[i])) for i in range(cnt.value)], int(cap.value)
+
+    def residue_read(self, region, offset, nbytes):
+        """test probe (mbls_ctx_residue_read): bytes [offset, offset + nbytes) of region `region` (an index of residue_regions) once the device has drained"""
+        out = (C.c_uint8 * max(1, nbytes))()
+        self.check(lib().mbls_ctx_residue_read(self._h, region, offset, nbytes, out))
+        return bytes(memoryview(out)[:nbytes])
 
     def reset_tuning(self):
         """every routing parameter (engine crossovers, packing, round, lane shaping) back to the library's defaults"""

@@ -1297,7 +1297,7 @@ struct mbls_ctx {
     uint32_t* d_cms_list = nullptr; uint64_t cms_words = 0; uint32_t* d_cms_rec = nullptr; uint32_t* d_cms_park = nullptr; uint64_t cms_items = 0;
     coop_prog coop[10] = {};           // the cooperative engine's microprograms in HBM (mbls_coop.h): pairing2, vmtail, f12mul, g2add, smiller, vmfinal, hashg2, miller1,
                                        // pairing2x2 (two items per wave), hashg2x4 (four)
-    uint32_t* d_coop = nullptr;
+    uint32_t* d_coop = nullptr; size_t coop_bytes = 0;
     // measured crossovers (scripts/coop_sweep.py, 128 keys, device-resident): one wave per item for the pairing check wins up to ~10 k items
     // (19.7 ms at 10 240 against 22.5), for the message phase as well up to ~6 k (13.3 ms at 6 144 against 14.0; four items per wave above 768)
     uint64_t coop_hash_max_items = MBLS_DEFAULT_COOP_HASH_MAX_ITEMS;
@@ -1480,7 +1480,7 @@ extern "C" int mbls_ctx_create(mbls_ctx** out, int device_id) {
                                       COOP_DIM(MILLER1), COOP_DIM(PAIRING2X2), COOP_DIM(HASHG2X4)};
         size_t total = 0;
         for (int p = 0; p < NP; p++) for (int a = 0; a < 3; a++) total += (cnt[p][a] + 3) & ~(size_t)3;       // 16-byte aligned pieces (the rows are read as uint4)
-        ok = hipMalloc(&c->d_coop, total * 4) == hipSuccess;
+        ok = hipMalloc(&c->d_coop, total * 4) == hipSuccess; c->coop_bytes = ok ? total * 4 : 0;
         size_t at = 0;
         for (int p = 0; p < NP && ok; p++) {
             const uint32_t* dp[3];
@@ -3066,6 +3066,11 @@ static void g2_tree_levels(mbls_ctx* c, mbls_ws ws, uint64_t m, int levels, hipS
 static hipError_t ws_wipe(mbls_ctx* c, int slot_lo, int slot_hi, uint64_t m, hipStream_t s) {
     return hipMemset2DAsync(c->d_w + (size_t)slot_lo * 12 * c->cap, c->cap * 4, 0, m * 4, (size_t)(slot_hi - slot_lo) * 12, s);
 }
+// the error path of the host entries: the device entry refused or failed, the staged secret keys go all the same. What the device entry said stays the call's
+// answer (the context's error text included), so nothing here is checked: after a failure of the runtime itself the fill may fail as well (include/mbls.h).
+static void staged_keys_wipe(mbls_ctx* c, void* d_keys, size_t bytes) {
+    (void)hipMemsetAsync(d_keys, 0, bytes, c->hs_a); (void)hipStreamSynchronize(c->hs_a);
+}
 // [sk] H(msg) for n (secret key, message) pairs: the pipeline's message phase, the four-lane windowed multiplication (k_sign_blind), two
 // levels of the G2 sum tree, compression -- in chunks of MBLS_SIGN_CHUNK signatures (four workspace items each). Enqueues only.
 #define MBLS_SIGN_CHUNK 65536ull
@@ -3092,6 +3097,9 @@ extern "C" int mbls_sign_batch_device(mbls_ctx* c, const uint8_t* d_sks, const u
     HIPCHK(c, ws_wipe(c, MBLS_SLOT_SIG, MBLS_SLOT_SIG + 4, 4 * chunk, s));
     HIPCHK(c, ws_wipe(c, MBLS_SLOT_S, MBLS_SLOT_S + 6, 4 * chunk, s));
     HIPCHK(c, ws_wipe(c, MBLS_SLOT_KREC, MBLS_SLOT_KREC + 48 + 6, 4 * chunk, s));        // the tables and (constant-time form) the record each window selected: 49..102
+    // a tree level on lanes (k_g2_tree_d, above MBLS_COOP_TREE_PAIRS pairs) parks the partner's running sum -- [a_2] psi^2(H), [a_3] psi^3(H), then
+    // [a_1] psi(H) + [a_3] psi^3(H) -- in the staging slots of the lane's own item (tools/gen_tower_d.py prog_g2_tree_start): 43..48
+    HIPCHK(c, ws_wipe(c, MBLS_SLOT_G2TMP, MBLS_SLOT_G2TMP + 6, 4 * chunk, s));
     return ws_release(c, s);
 }
 extern "C" int mbls_sign_batch(mbls_ctx* c, const uint8_t* sks, const uint8_t* msgs, uint32_t msg_len, uint64_t n, uint8_t* sigs) {
@@ -3099,8 +3107,10 @@ extern "C" int mbls_sign_batch(mbls_ctx* c, const uint8_t* sks, const uint8_t* m
     mbls_lock lk(c->mu);
     if (!n) return MBLS_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    sbuf dk(c, 0), dm(c, 1), dout(c, 2); HIPCHK(c, dk.up(sks, 32 * n)); HIPCHK(c, dm.up(msgs, (size_t)msg_len * n)); HIPCHK(c, dout.alloc(96 * n));
-    int rc = mbls_sign_batch_device(c, dk.as<uint8_t>(), dm.as<uint8_t>(), msg_len, n, dout.as<uint8_t>(), c->hs_a); if (rc) return rc;
+    // the keys go up LAST: nothing between their upload and the device entry can fail
+    sbuf dk(c, 0), dm(c, 1), dout(c, 2); HIPCHK(c, dm.up(msgs, (size_t)msg_len * n)); HIPCHK(c, dout.alloc(96 * n)); HIPCHK(c, dk.up(sks, 32 * n));
+    int rc = mbls_sign_batch_device(c, dk.as<uint8_t>(), dm.as<uint8_t>(), msg_len, n, dout.as<uint8_t>(), c->hs_a);
+    if (rc) { staged_keys_wipe(c, dk.p, 32 * n); return rc; }
     HIPCHK(c, hipMemsetAsync(dk.p, 0, 32 * n, c->hs_a));                  // the staged secret keys
     HIPCHK(c, hipStreamSynchronize(c->hs_a)); HIPCHK(c, dout.down(sigs, 96 * n)); return MBLS_OK;
 }
@@ -3164,6 +3174,10 @@ extern "C" int mbls_sk_to_pk_batch_device(mbls_ctx* c, const uint8_t* d_sks, int
     HIPCHK(c, hipGetLastError());
     if (ct) HIPCHK(c, hipMemsetAsync(c->d_sksel, 0, chunk * 64 * MBLS_KEYREC_DWORDS * 4, s));            // the selected multiples are functions of the keys
     else HIPCHK(c, hipMemsetAsync(c->d_skidx, 0, chunk * 64 * 4, s));            // the hexadecimal digits of the secret keys
+    // the key sum leaves [sk] G1 (Jacobian) in slot APK of the items, and in their status words MBLS_ST_PK_INFINITY for every key with a hexadecimal digit 0 (record
+    // 16 j of the table is the point at infinity): which keys have NO such digit is a function of the keys
+    HIPCHK(c, ws_wipe(c, MBLS_SLOT_APK, MBLS_SLOT_APK + 3, chunk, s));
+    HIPCHK(c, hipMemsetAsync(c->d_status, 0, 4 * chunk, s));
     return ws_release(c, s);
 }
 // 1: table lookups that depend on a secret key (the window tables of signing, the generator table of sk -> pk) go back to the faster forms that read ONE record
@@ -3177,8 +3191,9 @@ extern "C" int mbls_sk_to_pk_batch(mbls_ctx* c, const uint8_t* sks, int fmt, uin
     mbls_lock lk(c->mu);
     if (!n) return MBLS_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    sbuf dk(c, 0), dout(c, 1); HIPCHK(c, dk.up(sks, 32 * n)); HIPCHK(c, dout.alloc((fmt ? 96 : 48) * n));
-    int rc = mbls_sk_to_pk_batch_device(c, dk.as<uint8_t>(), fmt, n, dout.as<uint8_t>(), c->hs_a); if (rc) return rc;
+    sbuf dk(c, 0), dout(c, 1); HIPCHK(c, dout.alloc((fmt ? 96 : 48) * n)); HIPCHK(c, dk.up(sks, 32 * n));             // the keys last, as in mbls_sign_batch
+    int rc = mbls_sk_to_pk_batch_device(c, dk.as<uint8_t>(), fmt, n, dout.as<uint8_t>(), c->hs_a);
+    if (rc) { staged_keys_wipe(c, dk.p, 32 * n); return rc; }
     HIPCHK(c, hipMemsetAsync(dk.p, 0, 32 * n, c->hs_a));                  // the staged secret keys
     HIPCHK(c, hipStreamSynchronize(c->hs_a)); HIPCHK(c, dout.down(pks, (fmt ? 96 : 48) * n)); return MBLS_OK;
 }
@@ -3452,6 +3467,65 @@ extern "C" int mbls_dform_probe(mbls_ctx* c, int op, const int32_t* in, uint64_t
     HIPCHK(c, hipStreamSynchronize(c->hs_a)); HIPCHK(c, dran.down(&ran, 4));
     if (!ran) { snprintf(c->err, sizeof(c->err), "this build has no generated digit-form routines: nothing ran"); return MBLS_ERR_DEVICE; }
     HIPCHK(c, dout.down(out, bout)); return MBLS_OK;
+}
+// Test probe (include/mbls.h, "what the secret-key entries leave behind"): every device allocation the context owns, by name and size, and a copy of a byte
+// range of one of them to the host once the device has drained. Reads only: no kernel, no secret. tests/test_secret_residue_cpu.py holds this table against the
+// device pointers of struct mbls_ctx -- a new allocation goes here too (an allocation that does not exist yet is listed with 0 bytes, so the indices are stable).
+struct residue_region { const char* name; const void* p; uint64_t bytes; };
+#define RESIDUE_REGION(member, bytes) {#member, (const void*)c->member, (uint64_t)(c->member ? (bytes) : 0)}
+#define MBLS_RESIDUE_REGIONS (20 + MBLS_N_STAGE)
+static void residue_table(const mbls_ctx* c, residue_region* r) {
+    const residue_region fixed[20] = {
+        RESIDUE_REGION(d_w, (uint64_t)MBLS_SLOT_TOTAL * 12 * c->cap * 4),
+        RESIDUE_REGION(d_status, c->cap * 4),
+        RESIDUE_REGION(d_results, c->cap),
+        RESIDUE_REGION(d_scalar, 64),
+        RESIDUE_REGION(d_skidx, c->skidx_cap * 64 * 4),
+        RESIDUE_REGION(d_sksel, c->sksel_cap * 64 * MBLS_KEYREC_DWORDS * 4),
+        RESIDUE_REGION(d_keys_xy, c->key_cap * 96),
+        RESIDUE_REGION(d_key_flags, c->key_cap),
+        RESIDUE_REGION(d_htab, (uint64_t)MBLS_H_DWORDS * c->htab_cap * 4),
+        RESIDUE_REGION(d_hflag, c->htab_cap * 4),
+        RESIDUE_REGION(d_hst, c->htab_cap * 4),
+        RESIDUE_REGION(d_hgrp, (uint64_t)MBLS_HGRP_ARRAYS * c->hgrp_cap * 4),
+        RESIDUE_REGION(d_vmap, c->cap * 4),
+        RESIDUE_REGION(d_cmt_list, c->cmt_words * 4),
+        RESIDUE_REGION(d_cmt_cnt, c->cmt_items * 2 * 4),
+        RESIDUE_REGION(d_cms_list, c->cms_words * 4),
+        RESIDUE_REGION(d_cms_rec, c->cms_items * MBLS_CMS_REC_DWORDS * 4),
+        RESIDUE_REGION(d_cms_park, c->cms_items * MBLS_CMS_PARK_DWORDS * 4),
+        RESIDUE_REGION(d_coop, c->coop_bytes),
+        RESIDUE_REGION(d_gtab, (uint64_t)1024 * MBLS_KEYREC_DWORDS * 4),
+    };
+    static const char* const stage_names[MBLS_N_STAGE] = {"stage[0]", "stage[1]", "stage[2]", "stage[3]", "stage[4]", "stage[5]", "stage[6]", "stage[7]", "stage[8]",
+                                                          "stage[9]", "stage[10]"};
+    for (int i = 0; i < 20; i++) r[i] = fixed[i];
+    for (int i = 0; i < MBLS_N_STAGE; i++) r[20 + i] = residue_region{stage_names[i], c->stage[i].p, c->stage[i].p ? (uint64_t)c->stage[i].cap : 0};
+}
+extern "C" int mbls_ctx_residue_regions(mbls_ctx* c, char* names, uint64_t* bytes, uint32_t max_regions, uint32_t* n_regions, uint64_t* cap) {
+    if (!c || !n_regions) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    *n_regions = MBLS_RESIDUE_REGIONS;
+    if (cap) *cap = c->cap;
+    if (!names && !bytes) return MBLS_OK;                // the count alone
+    if (!names || !bytes || max_regions < MBLS_RESIDUE_REGIONS) ARGFAIL(c, "residue_regions: room for fewer regions than the context has");
+    residue_region r[MBLS_RESIDUE_REGIONS]; residue_table(c, r);
+    for (int i = 0; i < MBLS_RESIDUE_REGIONS; i++) {
+        memset(names + MBLS_RESIDUE_NAME_BYTES * i, 0, MBLS_RESIDUE_NAME_BYTES); strncpy(names + MBLS_RESIDUE_NAME_BYTES * i, r[i].name, MBLS_RESIDUE_NAME_BYTES - 1);
+        bytes[i] = r[i].bytes;
+    }
+    return MBLS_OK;
+}
+extern "C" int mbls_ctx_residue_read(mbls_ctx* c, uint32_t region, uint64_t offset, uint64_t bytes, uint8_t* out) {
+    if (!c || (!out && bytes)) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (region >= MBLS_RESIDUE_REGIONS) ARGFAIL(c, "residue_read: no such region");
+    residue_region r[MBLS_RESIDUE_REGIONS]; residue_table(c, r);
+    if (offset > r[region].bytes || bytes > r[region].bytes - offset) ARGFAIL(c, "residue_read: the range leaves the region");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());                   // every stream of the context, and the caller's: what is read is what the calls so far left behind
+    if (bytes) HIPCHK(c, hipMemcpy(out, (const uint8_t*)r[region].p + offset, bytes, hipMemcpyDeviceToHost));
+    return MBLS_OK;
 }
 extern "C" int mbls_fp_mul_bench(mbls_ctx* c, uint64_t n_lanes, uint32_t iters, float* ms_out) {
     if (!c || !ms_out || !n_lanes) return MBLS_ERR_ARGUMENT;

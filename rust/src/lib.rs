@@ -286,6 +286,11 @@ extern "C" {
     fn mbls_fast_aggregate_verify_batch_indexed_shared_msgs(ctx: *mut MblsCtx, t: *const MblsKeyTable, sigs: *const u8, msgs: *const u8, msg_len: u32,
                                                             msg_offsets: *const u64, n_msgs: u64, msg_idx: *const u32, key_idx: *const u32, offsets: *const u32,
                                                             n: u64, k: u32, results: *mut u8, status: *mut u32) -> c_int;
+    // test probes of what the secret-key entries leave in device memory (include/mbls.h): every allocation of the context by name and size, and a copy of one
+    #[allow(dead_code)]
+    fn mbls_ctx_residue_regions(ctx: *mut MblsCtx, names: *mut c_char, bytes: *mut u64, max_regions: u32, n_regions: *mut u32, cap: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn mbls_ctx_residue_read(ctx: *mut MblsCtx, region: u32, offset: u64, bytes: u64, out: *mut u8) -> c_int;
 }
 #[repr(C)]
 pub struct MblsMulti {
