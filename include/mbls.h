@@ -354,8 +354,8 @@ int mbls_fast_aggregate_verify_batch_indexed_msgtable(mbls_ctx* ctx, const mbls_
  * ROUTE (mbls_ctx_set_committee_route; mbls_ctx_reset_tuning restores 0): 0 auto, 1 always direct, 2 complement whenever the committee is eligible.
  *   mbls_plan_committee_route(m, s, eligible, mode) states the decision without a GPU -- the SAME function the kernel runs (csrc/mbls_cmt.h): 1 complement,
  *   0 direct, MBLS_ERR_ARGUMENT for a mode outside 0..2, m = 0, m > MBLS_COMMITTEE_MAX_MEMBERS or s > m.
- * OUT OF SCOPE: the verification stream, the shared-list message form, the mbls_multi handle, a device-pointer append. (verify_multiple over committees:
- * mbls_verify_multiple_committee_msgtable*, below.) */
+ * OUT OF SCOPE: the shared-list message form, the mbls_multi handle, a device-pointer append. (verify_multiple over committees:
+ * mbls_verify_multiple_committee_msgtable*, below; the verification stream over committees: mbls_stream_create_committee, below.) */
 #define MBLS_COMMITTEE_MAX_MEMBERS 2048
 typedef struct mbls_committees mbls_committees;
 int mbls_committees_create(mbls_ctx* ctx, mbls_keytable* keytable, uint64_t capacity_hint, mbls_committees** out);
@@ -504,6 +504,40 @@ int mbls_stream_submit_msgidx_device(mbls_stream* s, const uint8_t* d_sigs, cons
                                      uint64_t* ticket);
 int mbls_stream_submit_msgidx(mbls_stream* s, const uint8_t* sigs, const uint32_t* msg_idx, const uint8_t* pks, const uint32_t* key_idx, const uint32_t* pk_offsets,
                               uint64_t n, uint32_t k, uint8_t* results, uint32_t* status, uint64_t* ticket);
+/* A stream over a committee table and a message table (see "committee table"): the smallest item -- a committee id, a participation bitfield as SSZ serializes
+ * it, a message-table index -- for the caller with the smallest calls. Mode fast_aggregate_verify only. The stream is bound to ONE committee table, through it to
+ * that table's key table, and to ONE message table, all of the stream's context; policies, depth, threading, ticket order, flush / wait / query, lifetimes and
+ * mbls_stream_get_stats are the stream's above, unchanged.
+ * CREATE. bits_stride is fixed at creation: a multiple of 4 with 8 * bits_stride >= mbls_committees_max_members(committees) at that moment. MBLS_ERR_ARGUMENT for a
+ *   null table, a committee table whose key table is gone, tables of another context, a stride that is not a multiple of 4 or does not cover the largest committee.
+ * CALL. n >= 1 items; item i has its 96-byte signature, msg_idx[i], cmt_idx[i] and the bits_len bytes at bits + bits_len * i. bits_len is a value of the CALL, any
+ *   number in 1 .. bits_stride -- not necessarily a multiple of 4, and d_bits of a device submit needs no alignment: calls of different producers carry fields of
+ *   different lengths (a Bitlist of a 127-member committee is 16 bytes, of a 128-member one 17), and the gather of a round re-strides them on the device
+ *   (k_stream_gather_cmt). bits_len = 0 or above the stride is MBLS_ERR_ARGUMENT at submit, and the call gets no ticket.
+ * RESULT. Per-call results, status words and bitmap are byte for byte what mbls_fast_aggregate_verify_batch_committee_msgtable_device returns on the same
+ *   signatures, indices and ids with every field ZERO-EXTENDED to bits_stride bytes -- every MBLS_ST_* bit, under every mbls_ctx_set_committee_route mode, on every
+ *   engine. A field shorter than its committee therefore selects nobody beyond its last byte. BOTH submit forms reject on the device as that entry does -- an id at
+ *   or above the table's count like a key index outside the key table, a message index at or above the message table's size with MBLS_ST_BAD_MSG_RANGE --; they do
+ *   not refuse the call.
+ * CUTTING. A committee call is the shape {n, k = 0, msg_len = 4}: rounds are cut exactly as mbls_stream_cut cuts such shapes; round_msg_bytes defaults to
+ *   4 x round_items, round_keys plays no part.
+ * ALLOCATION. Everything at creation: a slot holds 96 + 4 + 4 + bits_stride bytes per item (and as many pinned bytes per item as the stride, through which the
+ *   fields of host submits are zero-extended); the context's workspace for every round size, and its committee scratch as
+ *   mbls_ctx_reserve_committee_items(ctx, round_items, min(8 * bits_stride, MBLS_COMMITTEE_MAX_MEMBERS)). No round allocates. A slot never shows a round the bits
+ *   of the round before: every byte of every item's stride is written. mbls_stream_stats.gathered_bytes counts 96 + 4 + 4 + bits_len per item.
+ * TABLES. Both are read at the size they have when the call's round launches. While calls of the stream are pending mbls_committees_clear (and
+ *   mbls_msgtable_clear) are refused with MBLS_ERR_ARGUMENT, so an id valid at submit stays valid. While the stream lives, mbls_committees_append refuses a committee
+ *   of more than 8 * bits_stride members (the smallest stride among the table's streams; MBLS_ERR_ARGUMENT, nothing appended, the message names the stride): such a
+ *   committee would make every later round fail the entry's argument check. Destroying the stream releases both interlocks. DESTROY A STREAM BEFORE ITS TABLES.
+ * mbls_stream_submit[_device] and mbls_stream_submit_msgidx[_device] on such a stream, and the two entries below on any other stream, are MBLS_ERR_ARGUMENT; the
+ *   message names the right entry.
+ * OUT OF SCOPE: committee spans in a stream, per-item message bytes or a shared message list in a committee stream, verify_multiple in a stream, the mbls_multi
+ *   handle. */
+int mbls_stream_create_committee(mbls_ctx* ctx, mbls_committees* committees, mbls_msgtable* mt, uint32_t bits_stride, const mbls_stream_opts* opts, mbls_stream** out);
+int mbls_stream_submit_committee_device(mbls_stream* s, const uint8_t* d_sigs, const uint32_t* d_msg_idx, const uint32_t* d_cmt_idx, const uint8_t* d_bits,
+                                        uint32_t bits_len, uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream, uint64_t* ticket);
+int mbls_stream_submit_committee(mbls_stream* s, const uint8_t* sigs, const uint32_t* msg_idx, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_len,
+                                 uint64_t n, uint8_t* results, uint32_t* status, uint64_t* ticket);
 int mbls_stream_flush(mbls_stream* s);
 int mbls_stream_wait(mbls_stream* s, uint64_t ticket);
 int mbls_stream_query(mbls_stream* s, uint64_t ticket);

@@ -888,6 +888,7 @@ public:
 class VerifyStream {
     struct Call { Bytes s, m, p; std::vector<uint64_t> moff; std::vector<uint32_t> koff, midx; std::vector<uint8_t> res; uint64_t ticket = 0; size_t n = 0; };
     mbls_stream* h_ = nullptr;
+    uint32_t bits_stride_ = 0;               // a committee stream's (Call: the ids travel in koff, the fields in p)
     std::mutex mu_;
     std::deque<std::shared_ptr<Call>> live_;
     void check(int rc) const { if (rc != MBLS_OK) throw DeviceError(std::string("mbls_stream: ") + mbls_stream_last_error(h_)); }
@@ -911,6 +912,15 @@ public:
         mbls_stream_opts o{}; o.round_items = round_items; o.policy = policy;
         if (mbls_stream_create_msgtable(detail::ctx(), MBLS_STREAM_FAST_AGGREGATE_VERIFY, MBLS_PK_UNCOMPRESSED, nullptr, table.handle(), &o, &h_) != MBLS_OK)
             throw DeviceError(std::string("mbls_stream_create_msgtable: ") + mbls_last_error(detail::ctx()));
+    }
+    // a stream over a committee table and a message table (mbls_stream_create_committee): its calls name a committee and an entry per item and carry the
+    // participation bits (submit_committee below). bits_stride: a multiple of 4 whose 8 x covers the table's largest committee, now and for every later append.
+    // Destroy the stream before both tables.
+    VerifyStream(CommitteeTable& committees, MessageTable& table, uint32_t bits_stride, uint32_t policy = MBLS_STREAM_WORK_CONSERVING, uint64_t round_items = 0)
+        : bits_stride_(bits_stride) {
+        mbls_stream_opts o{}; o.round_items = round_items; o.policy = policy;
+        if (mbls_stream_create_committee(detail::ctx(), committees.handle(), table.handle(), bits_stride, &o, &h_) != MBLS_OK)
+            throw DeviceError(std::string("mbls_stream_create_committee: ") + mbls_last_error(detail::ctx()));
     }
     VerifyStream(const VerifyStream&) = delete; VerifyStream& operator=(const VerifyStream&) = delete;
     ~VerifyStream() { mbls_stream_destroy(h_); }
@@ -950,6 +960,32 @@ public:
         std::lock_guard<std::mutex> g(mu_);
         while (!live_.empty() && mbls_stream_query(h_, live_.front()->ticket) != MBLS_PENDING) live_.pop_front();
         check(mbls_stream_submit_msgidx(h_, c->s.data(), c->midx.data(), c->p.data(), nullptr, c->koff.data(), n, 0, c->res.data(), nullptr, &c->ticket));
+        live_.push_back(c);
+        return Ticket(this, c);
+    }
+    // a committee stream's call: item i is signature i over entry msg_idx[i] by the members of committee cmt_idx[i] whose bit is set in fields[i] (SSZ bit order, a
+    // Bitlist's delimiter may stay). The fields of ONE call travel at one length -- the longest of them, shorter ones zero-extended --, which may differ from call
+    // to call and need not be a multiple of 4; it must not exceed the stream's bits_stride. An id or an entry index that names nothing rejects its item. status,
+    // when given, receives the items' MBLS_ST_* words once the ticket is done (it must stay valid until then).
+    Ticket submit_committee(const std::vector<AggregateSignature>& sigs, const std::vector<uint32_t>& msg_idx, const std::vector<uint32_t>& cmt_idx,
+                            const std::vector<Bytes>& fields, std::vector<uint32_t>* status = nullptr) {
+        const size_t n = sigs.size();
+        if (n == 0 || msg_idx.size() != n || cmt_idx.size() != n || fields.size() != n)
+            throw std::invalid_argument("one message index, one committee id and one field per signature, at least one item");
+        size_t len = 1;
+        for (const auto& f : fields) len = std::max(len, f.size());
+        if (len > bits_stride_) throw std::invalid_argument("VerifyStream::submit_committee: a field is longer than the stream's bits_stride");
+        auto c = std::make_shared<Call>();
+        c->n = n; c->res.resize(n); c->midx = msg_idx; c->koff = cmt_idx; c->p.assign(len * n, 0);
+        for (size_t i = 0; i < n; i++) {
+            c->s.insert(c->s.end(), sigs[i].point.begin(), sigs[i].point.end());
+            std::copy(fields[i].begin(), fields[i].end(), c->p.begin() + len * i);
+        }
+        if (status) status->assign(n, 0);
+        std::lock_guard<std::mutex> g(mu_);
+        while (!live_.empty() && mbls_stream_query(h_, live_.front()->ticket) != MBLS_PENDING) live_.pop_front();
+        check(mbls_stream_submit_committee(h_, c->s.data(), c->midx.data(), c->koff.data(), c->p.data(), uint32_t(len), n, c->res.data(), status ? status->data() : nullptr,
+                                           &c->ticket));
         live_.push_back(c);
         return Ticket(this, c);
     }

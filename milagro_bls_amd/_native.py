@@ -403,6 +403,9 @@ SIGNATURES = {
     "mbls_stream_create_msgtable": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(vp)]),
     "mbls_stream_submit_msgidx_device": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_uint64)]),
     "mbls_stream_submit_msgidx": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(C.c_uint64)]),
+    "mbls_stream_create_committee": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.POINTER(vp)]),
+    "mbls_stream_submit_committee_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, C.POINTER(C.c_uint64)]),
+    "mbls_stream_submit_committee": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
     "mbls_stream_flush": (C.c_int, [vp]),
     "mbls_stream_wait": (C.c_int, [vp, C.c_uint64]),
     "mbls_stream_query": (C.c_int, [vp, C.c_uint64]),

@@ -1339,6 +1339,8 @@ struct mbls_committees {
     uint32_t max_members = 0;          // the largest committee the table holds
     std::vector<uint32_t> sizes;       // every committee's member count, by id: what the host entries of the span form check an item's field against
     hipEvent_t ev = nullptr; hipStream_t ev_stream = nullptr; bool pending = false;   // the last asynchronous append
+    std::atomic<long long> stream_calls{0};        // calls of streams bound to the table that have not completed (mbls_committees_clear refuses while there are any)
+    std::vector<uint64_t> stream_bits;             // 8 * bits_stride of every stream bound to the table: mbls_committees_append keeps every committee inside the smallest
 };
 typedef std::lock_guard<std::recursive_mutex> mbls_lock;
 
@@ -2809,10 +2811,31 @@ extern "C" void mbls_committees_destroy(mbls_committees* t) {
 }
 extern "C" uint64_t mbls_committees_count(const mbls_committees* t) { if (!t || !t->c) return 0; mbls_lock lk(t->c->mu); return t->count; }
 extern "C" uint32_t mbls_committees_max_members(const mbls_committees* t) { if (!t || !t->c) return 0; mbls_lock lk(t->c->mu); return t->max_members; }
+// the two interlocks of a committee stream (mbls_stream.hip; not exported): the count of its calls that have not completed, which mbls_committees_clear consults,
+// and the stream's 8 * bits_stride, which mbls_committees_append keeps every committee inside. Binding checks what mbls_stream_create_committee has to refuse, under
+// the context's lock, so no append slips between the check and the binding.
+extern "C" __attribute__((visibility("hidden"))) void mblsi_committees_stream_calls(mbls_committees* t, long long delta) { if (t) t->stream_calls.fetch_add(delta); }
+extern "C" __attribute__((visibility("hidden"))) int mblsi_committees_stream_bind(mbls_ctx* c, mbls_committees* t, uint32_t bits_stride) {
+    if (!c || !t) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (t->c != c) ARGFAIL(c, "committee table belongs to another context");
+    if (!t->kt || t->kt->c != c) ARGFAIL(c, "the committee table's key table is gone");
+    if (bits_stride % 4) ARGFAIL(c, "bits_stride must be a multiple of 4");
+    if ((uint64_t)8 * bits_stride < t->max_members) ARGFAIL(c, "bits_stride does not cover the table's largest committee");
+    try { t->stream_bits.push_back((uint64_t)8 * bits_stride); } catch (...) { return MBLS_ERR_DEVICE; }
+    return MBLS_OK;
+}
+extern "C" __attribute__((visibility("hidden"))) void mblsi_committees_stream_unbind(mbls_committees* t, uint32_t bits_stride) {
+    if (!t || !t->c) return;
+    mbls_lock lk(t->c->mu);
+    for (size_t i = 0; i < t->stream_bits.size(); i++)
+        if (t->stream_bits[i] == (uint64_t)8 * bits_stride) { t->stream_bits.erase(t->stream_bits.begin() + i); break; }
+}
 extern "C" int mbls_committees_clear(mbls_committees* t) {
     if (!t || !t->c) return MBLS_ERR_ARGUMENT;
     mbls_ctx* c = t->c;
     mbls_lock lk(c->mu);
+    if (t->stream_calls.load() > 0) ARGFAIL(c, "committees_clear: a stream bound to the table has calls that have not completed");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());           // every append and verification enqueued over the table
     t->count = 0; t->n_members = 0; t->max_members = 0; t->pending = false; c->ws_pending = false; t->sizes.clear();
@@ -2847,6 +2870,12 @@ extern "C" int mbls_committees_append(mbls_committees* t, const uint32_t* key_id
         if (m > MBLS_CMT_MAX_MEMBERS) ARGFAIL(c, "a committee has more than MBLS_COMMITTEE_MAX_MEMBERS members");
         if (m > maxm) maxm = m;
     }
+    for (const uint64_t bits : t->stream_bits)
+        if (maxm > bits) {          // every later round of that stream would fail the entry's argument check
+            snprintf(c->err, sizeof(c->err), "invalid argument: a committee of %u members does not fit the bits_stride of a stream bound to the table (%llu bytes, %llu bits)",
+                     maxm, (unsigned long long)(bits / 8), (unsigned long long)bits);
+            return MBLS_ERR_ARGUMENT;
+        }
     const uint64_t total = (uint64_t)offsets[n] - offsets[0], tsize = t->kt->size;
     const uint32_t* idx = key_idx + offsets[0];
     for (uint64_t j = 0; j < total; j++) if ((uint64_t)idx[j] >= tsize) ARGFAIL(c, "a member index is outside the key table");

@@ -1,6 +1,7 @@
 // mbls_stream.h -- the pure parts of the verification stream (include/mbls.h, "verification stream"), in a header of their own so that a
 // host compiler can build them for the CPU tests (tests/host_emul/mbls_stream_harness.cpp): the cutting rule that packs calls into rounds,
-// the layout decision of a round, and the bit arithmetic of the scatter into a caller's bitmap. mbls_stream.hip runs exactly these.
+// the layout decision of a round, the bit arithmetic of the scatter into a caller's bitmap, and one destination dword of a committee call's re-strided bitfield
+// (tests/stream_cmt_emul/mbls_stream_cmt_harness.cpp). mbls_stream.hip runs exactly these.
 #ifndef MBLS_STREAM_H
 #define MBLS_STREAM_H
 #include <stdint.h>
@@ -80,5 +81,20 @@ MBLS_SFN uint64_t stream_bitmap_word(const uint8_t* round_res, uint64_t round_fi
     for (uint64_t b = lo; b < hi; b++) bits |= (uint64_t)(round_res[round_first + (b - call_first)] != 0) << (b - wlo);
     *whole = lo == wlo && hi == wlo + 64;
     return bits;
+}
+
+// ---- gather of a committee call's bitfields (k_stream_gather_cmt): a call carries fields of bits_len bytes at any address, the round's slot holds fields of
+// bits_stride bytes (a multiple of 4, 4-byte aligned). Destination dword j of an item is bytes [4 j, 4 j + 4) of its field, little-endian, with every byte at or
+// beyond bits_len zero: nothing outside [0, bits_len) of the field is read. `fast` (one decision per tile): the tile's first field and bits_len are both multiples
+// of 4, so every field is 4-byte aligned and made of whole dwords.
+MBLS_SFN int stream_bits_fast(const uint8_t* first_field, uint32_t bits_len) { return ((((uintptr_t)first_field) | bits_len) & 3u) == 0; }
+MBLS_SFN uint32_t stream_bits_dword(const uint8_t* field, uint32_t bits_len, uint32_t j, int fast) {
+    const uint64_t b0 = 4 * (uint64_t)j;
+    if (b0 >= bits_len) return 0;
+    if (fast) return *(const uint32_t*)(field + b0);
+    const uint32_t left = bits_len - (uint32_t)b0, nb = left < 4 ? left : 4;
+    uint32_t v = 0;
+    for (uint32_t t = 0; t < nb; t++) v |= (uint32_t)field[b0 + t] << (8 * t);
+    return v;
 }
 #endif

@@ -2,6 +2,8 @@
 // public device entries out. Built on the public ABI only: mbls_ctx_get_limits, mbls_ctx_reserve[_keys], mbls_plan_workspace_items and the
 // three *_device verification entries (a message-table stream: their `_msgtable_device` forms), so every result comes out of the same verify_pipeline the parity
 // tests pin. One hook below the ABI, not exported from the library: a message table counts the calls its streams hold (mblsi_msgtable_stream_calls), which mbls_msgtable_clear consults.
+// A committee stream (mbls_stream_create_committee) launches mbls_fast_aggregate_verify_batch_committee_msgtable_device over the slot; its device pieces are staged
+// by k_stream_gather_cmt, which re-strides every call's bitfields to the stream's stride, and its table is held by two more such hooks (mblsi_committees_stream_*).
 //
 // Per stream: depth + 1 staging SLOTS (one round each: the open one and up to depth launched), one LAUNCHER thread that cuts the queue of
 // submitted calls into the open slot (stream_take, the rule mbls_stream_cut states as data), gathers the round's inputs into the slot on the
@@ -25,39 +27,78 @@
 
 // the table's count of calls that streams bound to it have taken and not completed (mbls_kernels.hip; mbls_msgtable_clear refuses while there are any)
 extern "C" __attribute__((visibility("hidden"))) void mblsi_msgtable_stream_calls(mbls_msgtable* t, long long delta);
+// a committee stream's two interlocks with its table (mbls_kernels.hip): the same count, which mbls_committees_clear consults, and the binding of the stream's
+// bits_stride, which checks the table against the stream's context and stride and from then on keeps mbls_committees_append inside it
+extern "C" __attribute__((visibility("hidden"))) void mblsi_committees_stream_calls(mbls_committees* t, long long delta);
+extern "C" __attribute__((visibility("hidden"))) int mblsi_committees_stream_bind(mbls_ctx* ctx, mbls_committees* t, uint32_t bits_stride);
+extern "C" __attribute__((visibility("hidden"))) void mblsi_committees_stream_unbind(mbls_committees* t, uint32_t bits_stride);
 
 namespace {
 
 constexpr unsigned SWG = 64;                        // one wave per workgroup, like the rest of the library
 constexpr uint64_t GATHER_TILE = 128 * 1024;         // bytes per gather tile (a multiple of 16: tiles of one segment keep its alignment)
 constexpr uint64_t SCATTER_TILE = 4096;              // items per scatter tile, cut at multiples of this in the CALL's item space (so at bitmap words)
+constexpr uint64_t CMT_TILE = 256;                   // items per gather tile of a committee piece
 
 struct gtile { const uint8_t* src; uint8_t* dst; uint64_t bytes; };
 struct stile { uint8_t* res; uint32_t* st; uint64_t* bm; uint64_t call_first, items, round_first; };
+// a tile of a committee piece: the caller's four arrays at the tile's first item, and where its items lie in the round
+struct ctile { const uint8_t* sigs; const uint32_t* midx; const uint32_t* cid; const uint8_t* bits; uint32_t bits_len, items; uint64_t round_first; };
 
-}  // namespace
-
-// One workgroup per tile: 16-byte loads and stores where source and destination are both 16-byte aligned, dwords where both are 4-byte
-// aligned, bytes otherwise (ragged messages start anywhere).
-__global__ __launch_bounds__(SWG) void k_stream_gather(const gtile* __restrict__ tiles) {
-    const gtile t = tiles[blockIdx.x];
-    const unsigned l = threadIdx.x;
-    const uintptr_t a = (uintptr_t)t.src | (uintptr_t)t.dst;
+// the wave's copy of one segment: 16-byte loads and stores where source and destination are both 16-byte aligned, dwords where both are 4-byte aligned, bytes
+// otherwise (ragged messages start anywhere)
+__device__ __forceinline__ void wave_copy(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint64_t bytes, unsigned l) {
+    const uintptr_t a = (uintptr_t)src | (uintptr_t)dst;
     uint64_t done = 0;
     if ((a & 15) == 0) {
-        const uint64_t n16 = t.bytes / 16;
-        const uint4* s = (const uint4*)t.src; uint4* d = (uint4*)t.dst;
+        const uint64_t n16 = bytes / 16;
+        const uint4* s = (const uint4*)src; uint4* d = (uint4*)dst;
 #pragma unroll 4
         for (uint64_t i = l; i < n16; i += SWG) d[i] = s[i];
         done = 16 * n16;
     } else if ((a & 3) == 0) {
-        const uint64_t n4 = t.bytes / 4;
-        const uint32_t* s = (const uint32_t*)t.src; uint32_t* d = (uint32_t*)t.dst;
+        const uint64_t n4 = bytes / 4;
+        const uint32_t* s = (const uint32_t*)src; uint32_t* d = (uint32_t*)dst;
 #pragma unroll 4
         for (uint64_t i = l; i < n4; i += SWG) d[i] = s[i];
         done = 4 * n4;
     }
-    for (uint64_t i = done + l; i < t.bytes; i += SWG) t.dst[i] = t.src[i];
+    for (uint64_t i = done + l; i < bytes; i += SWG) dst[i] = src[i];
+}
+
+// every destination dword of a tile's fields, lanes over consecutive dwords (T: the width the dword count fits)
+template <typename T>
+__device__ __forceinline__ void wave_restride(const ctile& t, uint32_t* __restrict__ dst, uint32_t dwords_per_item, int fast, unsigned l) {
+    const T nd = (T)t.items * dwords_per_item;
+    for (T w = l; w < nd; w += SWG) {
+        const T i = w / dwords_per_item;
+        dst[w] = stream_bits_dword(t.bits + (uint64_t)t.bits_len * i, t.bits_len, (uint32_t)(w - i * dwords_per_item), fast);
+    }
+}
+
+}  // namespace
+
+// One workgroup per tile (wave_copy).
+__global__ __launch_bounds__(SWG) void k_stream_gather(const gtile* __restrict__ tiles) {
+    const gtile t = tiles[blockIdx.x];
+    wave_copy(t.src, t.dst, t.bytes, threadIdx.x);
+}
+
+// One workgroup per tile of at most CMT_TILE items of a committee piece: signatures, message indices and committee ids copied to the round's arrays at
+// round_first (wave_copy), the bitfields re-strided from bits_len bytes at any address to the slot's bits_stride (stream_bits_dword: every dword of every
+// item's stride is written, so a slot never shows a round the bits of the round before).
+__global__ __launch_bounds__(SWG) void k_stream_gather_cmt(const ctile* __restrict__ tiles, uint8_t* __restrict__ d_sigs, uint32_t* __restrict__ d_midx,
+                                                           uint32_t* __restrict__ d_cid, uint8_t* __restrict__ d_bits, uint32_t bits_stride) {
+    const ctile t = tiles[blockIdx.x];
+    const unsigned l = threadIdx.x;
+    wave_copy(t.sigs, d_sigs + 96 * t.round_first, 96ull * t.items, l);
+    wave_copy((const uint8_t*)t.midx, (uint8_t*)(d_midx + t.round_first), 4ull * t.items, l);
+    wave_copy((const uint8_t*)t.cid, (uint8_t*)(d_cid + t.round_first), 4ull * t.items, l);
+    const uint32_t dpi = bits_stride / 4;
+    const int fast = stream_bits_fast(t.bits, t.bits_len);
+    uint32_t* dst = (uint32_t*)(d_bits + (uint64_t)bits_stride * t.round_first);
+    if ((uint64_t)t.items * dpi < 0xFFFFFF00ull) wave_restride<uint32_t>(t, dst, dpi, fast, l);
+    else wave_restride<uint64_t>(t, dst, dpi, fast, l);
 }
 
 // One workgroup per tile of a device piece: result bytes and status words to caller + first, the accept bits into the caller's bitmap (words
@@ -85,7 +126,8 @@ namespace {
 struct call_rec {
     uint64_t ticket = 0; bool host = false; bool split = false;
     mbls_stream_call_shape shape{};
-    const uint8_t* sigs = nullptr; const uint8_t* msgs = nullptr; const uint8_t* keys = nullptr;   // keys: bytes or indices
+    const uint8_t* sigs = nullptr; const uint8_t* msgs = nullptr; const uint8_t* keys = nullptr;   // keys: bytes or indices (a committee call: its committee ids)
+    const uint8_t* bits = nullptr; uint32_t bits_len = 0;                     // a committee call: its bitfields, bits_len bytes per item
     uint8_t* res = nullptr; uint64_t* bm = nullptr; uint32_t* st = nullptr;
     hipEvent_t ev = nullptr;                                                 // device submits: recorded on the caller's stream
 };
@@ -94,6 +136,7 @@ struct piece_rec { std::shared_ptr<call_rec> c; uint64_t first, items, round_fir
 struct slot {
     uint8_t *d_sigs = nullptr, *d_msgs = nullptr, *d_keys = nullptr, *d_res = nullptr, *d_meta = nullptr; uint32_t* d_st = nullptr;
     uint8_t *h_meta = nullptr, *h_res = nullptr; uint32_t* h_st = nullptr;      // pinned
+    uint32_t* d_cid = nullptr; uint8_t* h_bits = nullptr;                       // a committee stream: the round's committee ids (its fields lie in d_keys); pinned: host pieces' fields, zero-extended
     hipEvent_t gev = nullptr, done = nullptr;
     std::vector<piece_rec> pieces;
     mbls_stream_fill fill{};
@@ -107,6 +150,7 @@ struct slot {
 struct mbls_stream {
     mbls_ctx* ctx = nullptr; const mbls_keytable* tab = nullptr;
     mbls_msgtable* mt = nullptr;                     // non-null: a message-table stream -- a call's "message bytes" are its uint32 table indices (msg_len = 4)
+    mbls_committees* cm = nullptr; uint32_t bits_stride = 0; bool cm_bound = false;   // cm non-null: a committee stream (mt is set too) -- a call's keys are committee ids and bitfields
     int mode = 0, fmt = MBLS_PK_UNCOMPRESSED, dev = 0; size_t unit = 96;
     mbls_stream_opts o{};
     uint64_t meta_bytes = 0;
@@ -136,11 +180,12 @@ int fail(mbls_stream* s, int rc, const char* fmt, ...) {
     return rc;
 }
 
-uint64_t meta_capacity(const mbls_stream_opts& o, size_t unit) {
+uint64_t meta_capacity(const mbls_stream_opts& o, size_t unit, bool committee) {
     const uint64_t R = o.round_items;
     const uint64_t bytes = 96 * R + o.round_msg_bytes + unit * o.round_keys;
     const uint64_t ng = bytes / GATHER_TILE + 3 * R + 3, ns = 2 * R + R / SCATTER_TILE + 1;      // (a piece takes at most items / tile + 2 scatter tiles)
-    return ng * sizeof(gtile) + ns * sizeof(stile) + 4 * (R + 1) + 8 * (R + 1) + 64;
+    const uint64_t nc = committee ? R + R / CMT_TILE + 1 : 0;                                    // (and at most items / tile + 1 committee tiles)
+    return ng * sizeof(gtile) + ns * sizeof(stile) + nc * sizeof(ctile) + 4 * (R + 1) + 8 * (R + 1) + 64;
 }
 
 // The round in the open slot: gather, the device entry, scatter, completion event. Runs on the launcher thread without the stream's lock.
@@ -164,10 +209,29 @@ int launch_round(mbls_stream* s, slot& sl) {
         for (uint64_t o = 0; o < bytes; o += GATHER_TILE) gt.push_back(gtile{src + o, dst + o, std::min(GATHER_TILE, bytes - o)});
     };
     hipEvent_t last_ev = nullptr;
+    std::vector<ctile> ct;
+    const uint64_t bs = s->bits_stride;
     for (const piece_rec& p : sl.pieces) {
         const call_rec& c = *p.c; const mbls_stream_call_shape& sh = c.shape;
         if (!c.host && c.ev != last_ev) { if (e == hipSuccess) e = hipStreamWaitEvent(s->gs, c.ev, 0); last_ev = c.ev; }
         any_host |= c.host;
+        if (s->cm && !c.host) {       // a device piece of a committee call: one record per CMT_TILE items, the four arrays in one kernel (k_stream_gather_cmt)
+            const uint32_t* midx = (const uint32_t*)c.msgs; const uint32_t* cid = (const uint32_t*)c.keys;
+            for (uint64_t a = p.first; a < p.first + p.items; a += CMT_TILE)
+                ct.push_back(ctile{c.sigs + 96 * a, midx + a, cid + a, c.bits + (uint64_t)c.bits_len * a, c.bits_len,
+                                   (uint32_t)std::min(CMT_TILE, p.first + p.items - a), p.round_first + (a - p.first)});
+            gathered += (96 + 4 + 4 + (uint64_t)c.bits_len) * p.items;
+        } else if (s->cm) {           // a host piece: three plain copies, and the fields zero-extended to the stride on their way through pinned memory
+            seg(true, c.sigs + 96 * p.first, sl.d_sigs + 96 * p.round_first, 96 * p.items);
+            seg(true, c.msgs + 4 * p.first, sl.d_msgs + 4 * p.round_first, 4 * p.items);
+            seg(true, c.keys + 4 * p.first, (uint8_t*)(sl.d_cid + p.round_first), 4 * p.items);
+            uint8_t* hb = sl.h_bits + bs * p.round_first; const uint8_t* src = c.bits + (uint64_t)c.bits_len * p.first;
+            if (c.bits_len == bs) memcpy(hb, src, bs * p.items);
+            else for (uint64_t i = 0; i < p.items; i++) { memcpy(hb + bs * i, src + (uint64_t)c.bits_len * i, c.bits_len); memset(hb + bs * i + c.bits_len, 0, bs - c.bits_len); }
+            seg(true, hb, sl.d_keys + bs * p.round_first, bs * p.items);
+            gathered -= (bs - c.bits_len) * p.items;                // (the statistic counts the bytes the call carries)
+        }
+        if (!s->cm) {
         seg(c.host, c.sigs + 96 * p.first, sl.d_sigs + 96 * p.round_first, 96 * p.items);
         const uint64_t m0 = sh.msg_offsets ? sh.msg_offsets[p.first] : (uint64_t)sh.msg_len * p.first;
         const uint64_t mb = sh.msg_offsets ? sh.msg_offsets[p.first + p.items] - m0 : (uint64_t)sh.msg_len * p.items;
@@ -181,6 +245,7 @@ int launch_round(mbls_stream* s, slot& sl) {
             if (!lay.msgs_uniform) moff[p.round_first + i] = msg_cur + (sh.msg_offsets ? sh.msg_offsets[p.first + i] - m0 : (uint64_t)sh.msg_len * i);
         }
         key_cur += kc; msg_cur += mb;
+        }
         if (!c.host)
             for (uint64_t a = p.first; a < p.first + p.items;) {
                 const uint64_t b = std::min(p.first + p.items, (a / SCATTER_TILE + 1) * SCATTER_TILE);
@@ -192,14 +257,20 @@ int launch_round(mbls_stream* s, slot& sl) {
     if (!lay.msgs_uniform) moff[n] = msg_cur;
     auto up = [](uint64_t x, uint64_t a) { return (x + a - 1) / a * a; };
     const uint64_t at_g = 0, at_s = up(at_g + gt.size() * sizeof(gtile), 16), at_k = up(at_s + stv.size() * sizeof(stile), 8), at_m = up(at_k + pkoff.size() * 4, 8);
-    const uint64_t off = at_m + moff.size() * 8;
+    const uint64_t at_c = up(at_m + moff.size() * 8, 16), off = at_c + ct.size() * sizeof(ctile);
     if (off > s->meta_bytes) return fail(s, MBLS_ERR_DEVICE, "internal: round meta of %llu bytes exceeds the slot's %llu", (unsigned long long)off, (unsigned long long)s->meta_bytes);
     if (!gt.empty()) memcpy(sl.h_meta + at_g, gt.data(), gt.size() * sizeof(gtile));
     if (!stv.empty()) memcpy(sl.h_meta + at_s, stv.data(), stv.size() * sizeof(stile));
     if (!pkoff.empty()) memcpy(sl.h_meta + at_k, pkoff.data(), pkoff.size() * 4);
     if (!moff.empty()) memcpy(sl.h_meta + at_m, moff.data(), moff.size() * 8);
+    if (!ct.empty()) memcpy(sl.h_meta + at_c, ct.data(), ct.size() * sizeof(ctile));
     if (e == hipSuccess && off) e = hipMemcpyAsync(sl.d_meta, sl.h_meta, off, hipMemcpyHostToDevice, s->gs);
     if (e == hipSuccess && !gt.empty()) { hipLaunchKernelGGL(k_stream_gather, dim3((unsigned)gt.size()), dim3(SWG), 0, s->gs, (const gtile*)(sl.d_meta + at_g)); e = hipGetLastError(); }
+    if (e == hipSuccess && !ct.empty()) {
+        hipLaunchKernelGGL(k_stream_gather_cmt, dim3((unsigned)ct.size()), dim3(SWG), 0, s->gs, (const ctile*)(sl.d_meta + at_c), sl.d_sigs, (uint32_t*)sl.d_msgs, sl.d_cid, sl.d_keys,
+                           s->bits_stride);
+        e = hipGetLastError();
+    }
     if (e == hipSuccess) e = hipEventRecord(sl.gev, s->gs);
     if (e == hipSuccess) e = hipStreamWaitEvent(s->hs, sl.gev, 0);
     if (e != hipSuccess) return fail(s, MBLS_ERR_DEVICE, "gather: %s", hipGetErrorString(e));
@@ -207,7 +278,10 @@ int launch_round(mbls_stream* s, slot& sl) {
     const uint32_t* d_pkoff = lay.keys_uniform ? nullptr : (const uint32_t*)(sl.d_meta + at_k);
     const uint32_t msg_len = lay.msgs_uniform ? lay.msg_len : 0, k = lay.keys_uniform ? lay.k : 0;
     int rc;
-    if (s->mt) {         // the staged "message bytes" are the items' table indices, dense in round order (every call has msg_len = 4 and no offsets)
+    if (s->cm)           // the round's four arrays, dense in round order, every field at the stream's stride
+        rc = mbls_fast_aggregate_verify_batch_committee_msgtable_device(s->ctx, s->cm, sl.d_sigs, s->mt, (const uint32_t*)sl.d_msgs, sl.d_cid, sl.d_keys, s->bits_stride, n,
+                                                                        sl.d_res, nullptr, sl.d_st, s->hs);
+    else if (s->mt) {    // the staged "message bytes" are the items' table indices, dense in round order (every call has msg_len = 4 and no offsets)
         const uint32_t* d_midx = (const uint32_t*)sl.d_msgs;
         if (s->mode == MBLS_STREAM_VERIFY)
             rc = mbls_verify_batch_msgtable_device(s->ctx, sl.d_sigs, s->mt, d_midx, sl.d_keys, s->fmt, n, sl.d_res, nullptr, sl.d_st, s->hs);
@@ -314,6 +388,7 @@ void completer_main(mbls_stream* s) {
         while (!s->calls.empty() && s->calls.front()->ticket <= s->completed_through && s->calls.front()->ticket < s->cursor) {
             if (s->calls.front()->ev) s->ev_pool.push_back(s->calls.front()->ev);
             if (s->mt) mblsi_msgtable_stream_calls(s->mt, -1);
+            if (s->cm) mblsi_committees_stream_calls(s->cm, -1);
             s->calls.pop_front(); s->base++;
         }
         s->inflight.pop_front(); s->free_slots.push_back(si);
@@ -325,7 +400,8 @@ void free_stream(mbls_stream* s) {
     for (slot& sl : s->slots) {
         for (uint8_t* p : {sl.d_sigs, sl.d_msgs, sl.d_keys, sl.d_res, sl.d_meta}) if (p) (void)hipFree(p);
         if (sl.d_st) (void)hipFree(sl.d_st);
-        for (void* p : {(void*)sl.h_meta, (void*)sl.h_res, (void*)sl.h_st}) if (p) (void)hipHostFree(p);
+        if (sl.d_cid) (void)hipFree(sl.d_cid);
+        for (void* p : {(void*)sl.h_meta, (void*)sl.h_res, (void*)sl.h_st, (void*)sl.h_bits}) if (p) (void)hipHostFree(p);
         if (sl.gev) (void)hipEventDestroy(sl.gev);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
@@ -333,13 +409,47 @@ void free_stream(mbls_stream* s) {
     for (auto& c : s->calls) if (c->ev) (void)hipEventDestroy(c->ev);
     if (s->hs) (void)hipStreamDestroy(s->hs);
     if (s->gs) (void)hipStreamDestroy(s->gs);
+    if (s->cm_bound) mblsi_committees_stream_unbind(s->cm, s->bits_stride);
     delete s;
+}
+
+// the call joins the queue: a device submit zeroes its bitmap words and records its event on the caller's stream first
+int enqueue(mbls_stream* s, const std::shared_ptr<call_rec>& c, void* stream, uint64_t* ticket) {
+    const uint64_t n = c->shape.n;
+    if (!c->host) {
+        {
+            std::lock_guard<std::mutex> g(s->mu);
+            if (!s->ev_pool.empty()) { c->ev = s->ev_pool.back(); s->ev_pool.pop_back(); }
+        }
+        hipError_t e = hipSetDevice(s->dev);
+        if (e == hipSuccess && !c->ev) e = hipEventCreateWithFlags(&c->ev, hipEventDisableTiming);
+        if (e == hipSuccess && c->bm) e = hipMemsetAsync(c->bm, 0, 8 * ((n + 63) / 64), (hipStream_t)stream);
+        if (e == hipSuccess) e = hipEventRecord(c->ev, (hipStream_t)stream);
+        if (e != hipSuccess) {
+            if (c->ev) { std::lock_guard<std::mutex> g(s->mu); s->ev_pool.push_back(c->ev); }
+            return fail(s, MBLS_ERR_DEVICE, "submit: %s", hipGetErrorString(e));
+        }
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->dead || s->closing) {
+        if (c->ev) s->ev_pool.push_back(c->ev);
+        return s->dead ? fail(s, MBLS_ERR_DEVICE, "the stream met a device error") : fail(s, MBLS_ERR_ARGUMENT, "the stream is being destroyed");
+    }
+    c->ticket = ++s->last_ticket;
+    s->calls.push_back(c);
+    if (s->mt) mblsi_msgtable_stream_calls(s->mt, 1);
+    if (s->cm) mblsi_committees_stream_calls(s->cm, 1);
+    s->stats.calls++; s->stats.items += n;
+    *ticket = c->ticket;
+    s->cv_launch.notify_one();
+    return MBLS_OK;
 }
 
 int submit(mbls_stream* s, bool msgidx, bool host, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, const uint8_t* pks,
            const uint32_t* idx, const uint32_t* poff, uint64_t n, uint32_t k, uint8_t* res, uint64_t* bm, uint32_t* st, void* stream, uint64_t* ticket) {
     if (!s) return MBLS_ERR_ARGUMENT;
     if (!ticket) return fail(s, MBLS_ERR_ARGUMENT, "null ticket pointer");
+    if (s->cm) return fail(s, MBLS_ERR_ARGUMENT, "a committee stream takes committee ids and bitfields (mbls_stream_submit_committee[_device])");
     if (msgidx != (s->mt != nullptr))
         return fail(s, MBLS_ERR_ARGUMENT, s->mt ? "a message-table stream takes message indices (mbls_stream_submit_msgidx[_device])"
                                                 : "this stream takes messages, not message-table indices (mbls_stream_submit[_device])");
@@ -364,32 +474,29 @@ int submit(mbls_stream* s, bool msgidx, bool host, const uint8_t* sigs, const ui
     if (key_total && !(s->tab ? (const void*)idx : (const void*)pks)) return fail(s, MBLS_ERR_ARGUMENT, "null key buffer");
     auto c = std::make_shared<call_rec>();
     c->host = host; c->shape = sh; c->sigs = sigs; c->msgs = msgs; c->keys = s->tab ? (const uint8_t*)idx : pks; c->res = res; c->bm = bm; c->st = st;
-    if (!host) {
-        {
-            std::lock_guard<std::mutex> g(s->mu);
-            if (!s->ev_pool.empty()) { c->ev = s->ev_pool.back(); s->ev_pool.pop_back(); }
-        }
-        hipError_t e = hipSetDevice(s->dev);
-        if (e == hipSuccess && !c->ev) e = hipEventCreateWithFlags(&c->ev, hipEventDisableTiming);
-        if (e == hipSuccess && bm) e = hipMemsetAsync(bm, 0, 8 * ((n + 63) / 64), (hipStream_t)stream);
-        if (e == hipSuccess) e = hipEventRecord(c->ev, (hipStream_t)stream);
-        if (e != hipSuccess) {
-            if (c->ev) { std::lock_guard<std::mutex> g(s->mu); s->ev_pool.push_back(c->ev); }
-            return fail(s, MBLS_ERR_DEVICE, "submit: %s", hipGetErrorString(e));
-        }
-    }
-    std::lock_guard<std::mutex> g(s->mu);
-    if (s->dead || s->closing) {
-        if (c->ev) s->ev_pool.push_back(c->ev);
-        return s->dead ? fail(s, MBLS_ERR_DEVICE, "the stream met a device error") : fail(s, MBLS_ERR_ARGUMENT, "the stream is being destroyed");
-    }
-    c->ticket = ++s->last_ticket;
-    s->calls.push_back(c);
-    if (s->mt) mblsi_msgtable_stream_calls(s->mt, 1);
-    s->stats.calls++; s->stats.items += n;
-    *ticket = c->ticket;
-    s->cv_launch.notify_one();
-    return MBLS_OK;
+    return enqueue(s, c, stream, ticket);
+}
+
+// a committee call: the shape {n, k = 0, msg_len = 4} -- the message indices are its "message bytes", as on a message-table stream; ids and fields ride along
+int submit_cmt(mbls_stream* s, bool host, const uint8_t* sigs, const uint32_t* msg_idx, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_len, uint64_t n,
+               uint8_t* res, uint64_t* bm, uint32_t* st, void* stream, uint64_t* ticket) {
+    if (!s) return MBLS_ERR_ARGUMENT;
+    if (!ticket) return fail(s, MBLS_ERR_ARGUMENT, "null ticket pointer");
+    if (!s->cm)
+        return fail(s, MBLS_ERR_ARGUMENT, s->mt ? "this is not a committee stream: a message-table stream takes mbls_stream_submit_msgidx[_device]"
+                                                : "this is not a committee stream: it takes messages and keys (mbls_stream_submit[_device])");
+    if (n == 0) return fail(s, MBLS_ERR_ARGUMENT, "a call holds at least one item");
+    if (!sigs || !res || !msg_idx || !cmt_idx || !bits) return fail(s, MBLS_ERR_ARGUMENT, "null buffer");
+    if (bits_len == 0 || bits_len > s->bits_stride)
+        return fail(s, MBLS_ERR_ARGUMENT, "bits_len is %u; a field holds 1 to %u bytes (the stream's bits_stride)", bits_len, s->bits_stride);
+    mbls_stream_call_shape sh{n, 0, 4, nullptr, nullptr, 0};
+    int what = 0;
+    if (stream_check_call(s->o, sh, &what))
+        return fail(s, MBLS_ERR_ARGUMENT, "an item takes 4 message bytes; a round holds %llu (mbls_stream_opts.round_msg_bytes)", (unsigned long long)s->o.round_msg_bytes);
+    auto c = std::make_shared<call_rec>();
+    c->host = host; c->shape = sh; c->sigs = sigs; c->msgs = (const uint8_t*)msg_idx; c->keys = (const uint8_t*)cmt_idx; c->bits = bits; c->bits_len = bits_len;
+    c->res = res; c->bm = bm; c->st = st;
+    return enqueue(s, c, stream, ticket);
 }
 
 }  // namespace
@@ -414,7 +521,8 @@ extern "C" int mbls_stream_cut(const mbls_stream_opts* o, const mbls_stream_call
     return np <= max_pieces || !out ? MBLS_OK : MBLS_ERR_ARGUMENT;
 }
 
-static int stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, mbls_msgtable* mt, const mbls_stream_opts* opts, mbls_stream** out) {
+static int stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, mbls_msgtable* mt, mbls_committees* cm, uint32_t bits_stride,
+                         const mbls_stream_opts* opts, mbls_stream** out) {
     if (!ctx || !out) return MBLS_ERR_ARGUMENT;
     *out = nullptr;
     if (mode != MBLS_STREAM_FAST_AGGREGATE_VERIFY && mode != MBLS_STREAM_VERIFY) return MBLS_ERR_ARGUMENT;
@@ -436,26 +544,36 @@ static int stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keyt
     mbls_stream* s = new (std::nothrow) mbls_stream();
     if (!s) return MBLS_ERR_DEVICE;
     s->ctx = ctx; s->tab = t; s->mt = mt; s->mode = mode; s->fmt = t ? MBLS_PK_UNCOMPRESSED : pk_format; s->o = o;
-    s->unit = t ? 4 : (pk_format == MBLS_PK_COMPRESSED ? 48 : 96);
+    s->unit = cm ? 0 : t ? 4 : (pk_format == MBLS_PK_COMPRESSED ? 48 : 96);
+    if (cm) {            // the table against this context and stride, and from here on its appends against the stride (released by free_stream)
+        rc = mblsi_committees_stream_bind(ctx, cm, bits_stride);
+        if (rc) { delete s; return rc; }
+        s->cm = cm; s->bits_stride = bits_stride; s->cm_bound = true;
+    }
     // every round size's workspace up front (a partial round on the wave engine may take the eight-lane key sum, n + 8 n items): no round grows it
     uint64_t ws = 0;
     const uint32_t kmax = (uint32_t)std::min<uint64_t>(o.round_keys, 0xFFFFFFFFull);
     for (uint64_t n = 1; n <= o.round_items; n++) {
         ws = std::max(ws, mbls_plan_workspace_items(&L, n, kmax, 1));
         if (kmax >= 32) ws = std::max(ws, mbls_plan_workspace_items(&L, n, 32, 1));
+        if (cm) ws = std::max(ws, mbls_plan_workspace_items(&L, n, 0, 0));
     }
     rc = mbls_ctx_reserve(ctx, ws);                       // (leaves the context's device current on this thread)
-    if (!rc && !t && pk_format == MBLS_PK_COMPRESSED) rc = mbls_ctx_reserve_keys(ctx, o.round_keys);
-    if (rc) { delete s; return rc; }
+    if (!rc && !t && !cm && pk_format == MBLS_PK_COMPRESSED) rc = mbls_ctx_reserve_keys(ctx, o.round_keys);
+    // the index lists k_cmt_expand writes for a full round of the largest committees the stride admits
+    if (!rc && cm) rc = mbls_ctx_reserve_committee_items(ctx, o.round_items, (uint32_t)std::min<uint64_t>(8ull * bits_stride, MBLS_COMMITTEE_MAX_MEMBERS));
+    if (rc) { free_stream(s); return rc; }
     hipError_t e = hipGetDevice(&s->dev);
-    s->meta_bytes = meta_capacity(o, s->unit);
+    s->meta_bytes = meta_capacity(o, s->unit, cm != nullptr);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->hs, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->gs, hipStreamNonBlocking);
     s->slots.resize(o.depth + 1);
     for (slot& sl : s->slots) {
         if (e == hipSuccess) e = hipMalloc(&sl.d_sigs, 96 * o.round_items);
         if (e == hipSuccess) e = hipMalloc(&sl.d_msgs, std::max<uint64_t>(o.round_msg_bytes, 16));
-        if (e == hipSuccess) e = hipMalloc(&sl.d_keys, std::max<uint64_t>(s->unit * o.round_keys, 16));
+        if (e == hipSuccess) e = hipMalloc(&sl.d_keys, std::max<uint64_t>(cm ? (uint64_t)bits_stride * o.round_items : s->unit * o.round_keys, 16));
+        if (e == hipSuccess && cm) e = hipMalloc(&sl.d_cid, 4 * o.round_items);
+        if (e == hipSuccess && cm) e = hipHostMalloc((void**)&sl.h_bits, std::max<uint64_t>((uint64_t)bits_stride * o.round_items, 16), hipHostMallocDefault);
         if (e == hipSuccess) e = hipMalloc(&sl.d_res, o.round_items);
         if (e == hipSuccess) e = hipMalloc(&sl.d_st, 4 * o.round_items);
         if (e == hipSuccess) e = hipMalloc(&sl.d_meta, s->meta_bytes);
@@ -481,11 +599,17 @@ static int stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keyt
 }
 
 extern "C" int mbls_stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, const mbls_stream_opts* opts, mbls_stream** out) {
-    return stream_create(ctx, mode, pk_format, t, nullptr, opts, out);
+    return stream_create(ctx, mode, pk_format, t, nullptr, nullptr, 0, opts, out);
 }
 extern "C" int mbls_stream_create_msgtable(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, mbls_msgtable* mt, const mbls_stream_opts* opts, mbls_stream** out) {
     if (!mt) return MBLS_ERR_ARGUMENT;
-    return stream_create(ctx, mode, pk_format, t, mt, opts, out);
+    return stream_create(ctx, mode, pk_format, t, mt, nullptr, 0, opts, out);
+}
+// a committee stream: fast_aggregate_verify over the committee table (and through it its key table) and the message table
+extern "C" int mbls_stream_create_committee(mbls_ctx* ctx, mbls_committees* committees, mbls_msgtable* mt, uint32_t bits_stride, const mbls_stream_opts* opts,
+                                            mbls_stream** out) {
+    if (!committees || !mt) return MBLS_ERR_ARGUMENT;
+    return stream_create(ctx, MBLS_STREAM_FAST_AGGREGATE_VERIFY, MBLS_PK_UNCOMPRESSED, nullptr, mt, committees, bits_stride, opts, out);
 }
 
 extern "C" void mbls_stream_destroy(mbls_stream* s) {
@@ -528,6 +652,16 @@ extern "C" int mbls_stream_submit_msgidx_device(mbls_stream* s, const uint8_t* d
 extern "C" int mbls_stream_submit_msgidx(mbls_stream* s, const uint8_t* sigs, const uint32_t* msg_idx, const uint8_t* pks, const uint32_t* key_idx,
                                          const uint32_t* pk_offsets, uint64_t n, uint32_t k, uint8_t* results, uint32_t* status, uint64_t* ticket) {
     return submit(s, true, true, sigs, (const uint8_t*)msg_idx, 4, nullptr, pks, key_idx, pk_offsets, n, k, results, nullptr, status, nullptr, ticket);
+}
+
+// committee streams: the index array travels as the call's message bytes, the ids and fields beside it
+extern "C" int mbls_stream_submit_committee_device(mbls_stream* s, const uint8_t* d_sigs, const uint32_t* d_msg_idx, const uint32_t* d_cmt_idx, const uint8_t* d_bits,
+                                                   uint32_t bits_len, uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream, uint64_t* ticket) {
+    return submit_cmt(s, false, d_sigs, d_msg_idx, d_cmt_idx, d_bits, bits_len, n, d_results, d_bitmap, d_status, stream, ticket);
+}
+extern "C" int mbls_stream_submit_committee(mbls_stream* s, const uint8_t* sigs, const uint32_t* msg_idx, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_len,
+                                            uint64_t n, uint8_t* results, uint32_t* status, uint64_t* ticket) {
+    return submit_cmt(s, true, sigs, msg_idx, cmt_idx, bits, bits_len, n, results, nullptr, status, nullptr, ticket);
 }
 
 extern "C" int mbls_stream_flush(mbls_stream* s) {

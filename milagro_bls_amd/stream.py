@@ -9,6 +9,12 @@ Over a resident message table (N.MsgTable) a call names its messages by table in
 
     with VerifyStream(ctx, pk_format=PK_UNCOMPRESSED, msg_table=mt) as vs:
         t = vs.submit_device(d_sigs, d_msg_idx, d_pks, n, k, d_results)                 # uint32 indices where the messages were
+
+Over a committee table (N.CommitteeTable) and a message table an item is a signature, a message index, a committee id and its SSZ bitfield:
+
+    with VerifyStream(ctx, committees=ct, msg_table=mt, bits_stride=16) as vs:
+        t = vs.submit_committee_device(d_sigs, d_msg_idx, d_cmt_idx, d_bits, bits_len, n, d_results)
+        h = vs.submit_committee(sigs, msg_idx, cmt_idx, bits, bits_len, n)               # bits_len: per call, 1 .. bits_stride, any alignment
 """
 import ctypes as C
 from collections import deque
@@ -57,14 +63,24 @@ class VerifyStream:
     msg_table given (a MsgTable) -- as uint32 indices into it: submit / submit_device then take the index array where they took the messages."""
 
     def __init__(self, ctx=None, mode=N.STREAM_FAST_AGGREGATE_VERIFY, pk_format=N.PK_UNCOMPRESSED, table=None, round_items=0, round_keys=0, round_msg_bytes=0,
-                 depth=0, policy=N.STREAM_WORK_CONSERVING, msg_table=None):
+                 depth=0, policy=N.STREAM_WORK_CONSERVING, msg_table=None, committees=None, bits_stride=0):
         self.ctx = ctx or N.default_context()          # held: the stream is destroyed before its context
         self.table = table
         self.indexed = table is not None
         self._h = N.vp()
         o = N.StreamOpts(round_items, round_keys, round_msg_bytes, depth, policy)
         self.msg_table = msg_table                     # held: the stream is destroyed before its message table
+        self.committees = committees                   # held likewise: a committee stream (submit_committee / submit_committee_device only)
+        self.bits_stride = bits_stride
+        self._live = deque()                           # (ticket, buffers) kept alive until the call completes
         th = table.handle if table is not None else None
+        if committees is not None:
+            if msg_table is None or table is not None or mode != N.STREAM_FAST_AGGREGATE_VERIFY:
+                raise ValueError("a committee stream is fast_aggregate_verify over committees= and msg_table=: no key table of its own, no other mode")
+            rc = N.lib().mbls_stream_create_committee(self.ctx.handle, committees.handle, msg_table.handle, bits_stride, C.byref(o), C.byref(self._h))
+            if rc != N.OK:
+                raise N.MblsError(rc, "mbls_stream_create_committee: " + self.ctx.last_error())
+            return
         if msg_table is not None:
             rc = N.lib().mbls_stream_create_msgtable(self.ctx.handle, mode, pk_format, th, msg_table.handle, C.byref(o), C.byref(self._h))
         else:
@@ -143,6 +159,28 @@ class VerifyStream:
             return HostTicket(self, t.value, res, st, n)
         self.check(N.lib().mbls_stream_submit(self._h, sp, mp, msg_len, mo, None if self.indexed else kp, kp if self.indexed else None, po, n, k, res, st, C.byref(t)))
         self._keep(t.value, (sa, ma, ka, mo, po, res, st))
+        return HostTicket(self, t.value, res, st, n)
+
+    def submit_committee_device(self, sigs, msg_idx, cmt_idx, bits, bits_len, n, results, bitmap=None, status=None, stream=None):
+        """a committee stream's device call: uint32 message-table indices and committee ids, n fields of bits_len bytes back to back (any address, any
+        bits_len in 1 .. bits_stride) -> ticket"""
+        hs = getattr(stream, "cuda_stream", stream)
+        t = C.c_uint64(0)
+        self.check(N.lib().mbls_stream_submit_committee_device(self._h, _ptr(sigs), _ptr(msg_idx), _ptr(cmt_idx), _ptr(bits), bits_len, n, _ptr(results), _ptr(bitmap),
+                                                               _ptr(status), hs, C.byref(t)))
+        self._keep(t.value, (sigs, msg_idx, cmt_idx, bits, results, bitmap, status))
+        return t.value
+
+    def submit_committee(self, sigs, msg_idx, cmt_idx, bits, bits_len, n):
+        """the same from host memory (bits: any bytes-like or uint8 array of n * bits_len bytes) -> HostTicket"""
+        import numpy as np
+        (sa, sp), (ma, mp), (ca, cp), (ba, bp) = _host(sigs, np.uint8), _host(msg_idx, np.uint32), _host(cmt_idx, np.uint32), _host(bits, np.uint8)
+        if ba.size != n * bits_len:
+            raise ValueError("bits holds %d bytes, the call needs n * bits_len = %d" % (ba.size, n * bits_len))
+        res, st = N.outbuf(n), (C.c_uint32 * max(1, n))()
+        t = C.c_uint64(0)
+        self.check(N.lib().mbls_stream_submit_committee(self._h, sp, mp, cp, bp, bits_len, n, res, st, C.byref(t)))
+        self._keep(t.value, (sa, ma, ca, ba, res, st))
         return HostTicket(self, t.value, res, st, n)
 
     def flush(self):

@@ -275,6 +275,10 @@ extern "C" {
                                    out: *mut *mut mbls_stream) -> c_int;
     fn mbls_stream_submit_msgidx(s: *mut mbls_stream, sigs: *const u8, msg_idx: *const u32, pks: *const u8, key_idx: *const u32, pk_offsets: *const u32, n: u64, k: u32,
                                  results: *mut u8, status: *mut u32, ticket: *mut u64) -> c_int;
+    fn mbls_stream_create_committee(ctx: *mut MblsCtx, committees: *mut mbls_committees, mt: *mut mbls_msgtable, bits_stride: u32, opts: *const mbls_stream_opts,
+                                    out: *mut *mut mbls_stream) -> c_int;
+    fn mbls_stream_submit_committee(s: *mut mbls_stream, sigs: *const u8, msg_idx: *const u32, cmt_idx: *const u32, bits: *const u8, bits_len: u32, n: u64,
+                                    results: *mut u8, status: *mut u32, ticket: *mut u64) -> c_int;
     fn mbls_stream_flush(s: *mut mbls_stream) -> c_int;
     fn mbls_stream_wait(s: *mut mbls_stream, ticket: u64) -> c_int;
     fn mbls_stream_destroy(s: *mut mbls_stream);
@@ -1866,6 +1870,61 @@ impl Drop for CommitteeTable {
     }
 }
 impl Drop for MessageTableStream {
+    fn drop(&mut self) {
+        unsafe { mbls_stream_destroy(self.h) }
+    }
+}
+/// A verification stream over a `CommitteeTable` and a `MessageTable` (`mbls_stream_create_committee`): an item is a signature, an entry index, a committee id and
+/// the committee's participation bits as SSZ serializes them; calls of any size, each with fields of its own byte length, are packed into full-round launches.
+/// While the stream lives the committee table refuses a committee of more than `8 * bits_stride` members, and both tables refuse `clear` while calls are pending.
+/// Drop the stream before both tables. (Like the rest of this crate: source only, never compiled.)
+pub struct CommitteeStream {
+    h: *mut mbls_stream,
+    bits_stride: u32,
+}
+unsafe impl Send for CommitteeStream {}
+unsafe impl Sync for CommitteeStream {}
+impl CommitteeStream {
+    /// `bits_stride`: a multiple of 4 with `8 * bits_stride` at least the table's largest committee
+    pub fn new(committees: &mut CommitteeTable, table: &mut MessageTable, bits_stride: u32, opts: mbls_stream_opts) -> Self {
+        let mut h: *mut mbls_stream = std::ptr::null_mut();
+        let rc = unsafe { mbls_stream_create_committee(ctx(), committees.h, table.h, bits_stride, &opts, &mut h) };
+        if rc != 0 {
+            err(rc);
+        }
+        CommitteeStream { h, bits_stride }
+    }
+    /// n x fast_aggregate_verify: item i = (signatures[i], entry message_indices[i], the members of committee committee_ids[i] whose bit is set in bits[i]). The
+    /// fields of one call travel at the length of its longest (at most `bits_stride` bytes); an id or an index that names nothing rejects its item.
+    pub fn verify(&self, signatures: &[AggregateSignature], message_indices: &[u32], committee_ids: &[u32], bits: &[&[u8]]) -> Vec<bool> {
+        let n = signatures.len();
+        assert!(n > 0 && message_indices.len() == n && committee_ids.len() == n && bits.len() == n);
+        let len = bits.iter().map(|b| b.len()).max().unwrap_or(1).max(1);
+        assert!(len <= self.bits_stride as usize);
+        let sigs: Vec<u8> = signatures.iter().flat_map(|s| s.point.iter().copied()).collect();
+        let mut flat = vec![0u8; len * n];
+        for (i, b) in bits.iter().enumerate() {
+            flat[len * i..len * i + b.len()].copy_from_slice(b);
+        }
+        let mut res = vec![0u8; n];
+        let mut ticket = 0u64;
+        let mut rc = unsafe {
+            mbls_stream_submit_committee(self.h, sigs.as_ptr(), message_indices.as_ptr(), committee_ids.as_ptr(), flat.as_ptr(), len as u32, n as u64, res.as_mut_ptr(),
+                                         std::ptr::null_mut(), &mut ticket)
+        };
+        if rc == 0 {
+            rc = unsafe { mbls_stream_wait(self.h, ticket) };       // the buffers above stay valid until the call completes
+        }
+        if rc != 0 {
+            err(rc);
+        }
+        res.into_iter().map(|b| b == 1).collect()
+    }
+    pub fn flush(&self) {
+        unsafe { mbls_stream_flush(self.h) };
+    }
+}
+impl Drop for CommitteeStream {
     fn drop(&mut self) {
         unsafe { mbls_stream_destroy(self.h) }
     }
