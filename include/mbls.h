@@ -990,9 +990,9 @@ int mbls_verify_multiple_msgtable_locate_rng(mbls_ctx* ctx, const uint8_t* sigs9
  * table and the message table are awaited on the caller's stream before any side stream has work, and no fallible step is left once one has.
  * PLANNING. Routing and workspace are mbls_plan_verify_multiple_msgtable, _workspace_items and _locate_workspace_items, UNCHANGED: the committee source adds
  * no workspace item (its scratch is the committee entries').
- * OUT OF SCOPE: the verification stream, the shared-list and per-set message forms over committees, mbls_verify_multiple_batches over committees, the mbls_multi
+ * OUT OF SCOPE: the verification stream, the shared-list and per-set message forms over committees, the mbls_multi
  * handle and the shard form, a device-pointer append. (fast_aggregate_verify over sets that span several committees: "committee spans" above; verify_multiple
- * over such sets: the section below.) */
+ * over such sets: the section below; many batches per call over committees: mbls_verify_multiple_batches_committee_msgtable*, below.) */
 #define MBLS_VM_SET_SINGLE_KEY 0x80000000u
 int mbls_verify_multiple_committee_msgtable_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96, const uint32_t* d_cmt_idx,
                                                    const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
@@ -1040,8 +1040,9 @@ int mbls_verify_multiple_committee_msgtable_locate_rng(mbls_ctx* ctx, const mbls
  *   P a call takes, and the workspace items it reserves -- mbls_plan_verify_multiple_msgtable[_locate]_workspace_items(limits, n, table_size, 0, 0) plus 2 P n for
  *   P > 1 (nothing for P = 1: the one-lane form parks its intermediate point in the span scratch). Under mbls_ctx_set_vm_grouping other than 0 the first term is
  *   that function's under the mode.
- * OUT OF SCOPE: the verification stream, the shared-list and per-set message forms, mbls_verify_multiple_batches over spans, the mbls_multi handle and the shard
- * form, a device-pointer append, splitting the chain of up to 64 cached sums. */
+ * OUT OF SCOPE: the verification stream, the shared-list and per-set message forms, mbls_verify_multiple_batches over spans (over plain
+ * committees: mbls_verify_multiple_batches_committee_msgtable*, below), the mbls_multi handle and the shard form, a device-pointer append, splitting the chain of
+ * up to 64 cached sums. */
 int mbls_verify_multiple_committee_span_msgtable_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96, const uint32_t* d_cmt_ids,
                                                         uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride,
                                                         const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result,
@@ -1060,6 +1061,75 @@ int mbls_verify_multiple_committee_span_msgtable_locate_rng(mbls_ctx* ctx, const
 int mbls_ctx_set_vm_span_split(mbls_ctx* ctx, int mode);
 int mbls_plan_verify_multiple_span(const mbls_limits* limits, uint64_t n, uint64_t table_size, uint64_t stride_words, int locate, int split_mode,
                                              uint32_t* split, uint64_t* workspace_items);
+
+/* MANY verify_multiple BATCHES PER CALL OVER COMMITTEE BITFIELDS AND THE RESIDENT MESSAGE TABLE. A consensus client verifies gossip in many small
+ * verify_multiple_aggregate_signatures batches and retries a rejected batch set by set. These entries answer PER BATCH, with per-set location, on the cheapest
+ * inputs the library has: the sets are those of mbls_verify_multiple_committee_msgtable[_locate]_device (`committees, d_sigs96, d_cmt_idx, d_bits, bits_stride, mt,
+ * d_msg_idx, d_rands, n_sets`: committee set or single-key set, the route under mbls_ctx_set_committee_route, an id that names nothing lists 0xFFFFFFFF), the
+ * batches those of mbls_verify_multiple_batches[_locate]_device (`d_batch_offsets` / `sets_per_batch`, `n_batches`, `d_results`, `d_status`, for _locate
+ * `d_set_results` (required) and `d_set_status`); every rule of both sections holds unchanged, those about a faulty device-side batch table included.
+ * max_groups (device entries): the caller's bound on the number of distinct (batch, table entry) pairs of the call; 0 makes no promise.
+ * CONTRACT. d_results[b], d_status[b], and for _locate every byte of d_set_results and every word of d_set_status, equal
+ *   mbls_verify_multiple_batches[_locate]_indexed_device on the same signatures, scalars and batch table with every set's signers spelled out in member order (a
+ *   single-key set as its one index) and every set's message spelled out as the bytes of its table entry -- under every mode of mbls_ctx_set_vm_grouping, every mode
+ *   of mbls_ctx_set_committee_route and every max_groups the call does not exceed. Items 1-6 of "WHICH SETS OF A REJECTED BATCH" therefore carry over. No value
+ *   crosses a batch boundary. A message index at or above the table's size rejects its set, and with it its batch, with MBLS_ST_BAD_MSG_RANGE (device entries).
+ *   The device entries only enqueue, nothing is read back, and every fallible step (reserves, table acquires) comes before the first kernel on a side stream.
+ * ROUTING (mbls_ctx_set_vm_grouping: 0 auto, 1 grouped, 2 per set). bound = the smallest of n_sets, n_batches x table size, n_batches x sets_per_batch where that
+ *   is given, and max_groups where that is nonzero (host entries: their exact count). The table-size term holds only where no batch can be larger than
+ *   MBLS_VBG_MAX_SETS -- sets_per_batch, or n_sets under a ragged device-side table, is at most that --: a larger batch has one group per set. Auto groups when 2 x bound <= n_sets -- the rule of the shared-message
+ *   entries, a count and not a measurement.
+ *   PER SET: mbls_verify_multiple_batches' path with the key phase the committee entries' (k_vmc_expand, the committee key sum) and the message phase the gather
+ *   from the table; n_sets + n_batches Miller items.
+ *   GROUPED (csrc/mbls_vbg.h, csrc/mbls_vbg.hip): inside a batch prod_i e([r_i] apk_i, H(m_i)) = prod_j e(sum_{i: m_i = j} [r_i] apk_i, H(m_j)), so a batch walks
+ *   one Miller loop per DISTINCT entry it names plus its signature pair: n_batches + bound Miller items, of which n_batches + (the groups there are) are walked.
+ *   One wave per batch (k_vbg_group) finds every set's leader -- the lowest set of its batch that names the same entry --, numbers the batch's groups in leader
+ *   order and gives every set the position lo_b + start_b[group] + rank, without atomics tickets; the blinded keys move to their positions and are summed per
+ *   group; a Miller item takes H from the table and its key from the head of its range. A batch of more than MBLS_VBG_MAX_SETS sets is not grouped (each valid set
+ *   is its own group: the verdict is the same). A batch whose groups reach beyond `bound` -- max_groups was too small -- is rejected with MBLS_ST_BAD_MSG_RANGE,
+ *   its neighbours in front are untouched, nothing outside the call's workspace is read or written. _locate has no Miller value per set here: two shadow items per
+ *   set and mbls_vsl.h's rule with the set's BATCH verdict in the place of the call's, both pairs' Miller loops in one launch, waves without a candidate idle.
+ * HOST ENTRIES (_rng) draw exactly as mbls_verify_multiple_batches[_locate]_rng do. They refuse, with nothing queued and the outputs untouched, a batch table that
+ *   is not sound and a committee id, key index or message index that names nothing; they count the groups themselves and take no max_groups.
+ * n_batches = 0 and n_sets = 0 answer as mbls_verify_multiple_batches_device does.
+ * PLANNING. mbls_plan_verify_multiple_batches_committee(limits, n_sets, n_batches, sets_per_batch (0: a ragged device-side table), table_size, max_groups, mode,
+ *   locate, &plan), without a GPU: what a call reserves and acts on. MBLS_ERR_ARGUMENT for n_sets = 0, n_batches = 0, a mode outside 0..2, a uniform layout with
+ *   n_batches x sets_per_batch != n_sets.
+ * OUT OF SCOPE: committee spans per set, the verification stream, the mbls_multi handle, wire keys. */
+#define MBLS_VBG_MAX_SETS 1024u
+typedef struct mbls_vm_batches_committee_plan {
+    int32_t route;                 /* MBLS_VM_ROUTE_* */
+    int32_t miller;                /* MBLS_PAIRING_WAVE, _LANES2 or _LANE: the form of the one-pair Miller loops, by miller_items */
+    uint32_t tree_levels;          /* per set: levels of the per-batch trees; grouped: levels of the per-group key sums */
+    uint32_t product_levels;       /* levels of the per-batch product trees (per set: over the sets; grouped: over the group items) */
+    uint64_t bound;                /* the bound on the distinct (batch, entry) pairs */
+    uint64_t miller_items;         /* per set: n_sets + n_batches; grouped: n_batches + bound */
+    uint64_t workspace_items;      /* what the call reserves (mbls_ctx_reserve) */
+} mbls_vm_batches_committee_plan;
+int mbls_plan_verify_multiple_batches_committee(const mbls_limits* limits, uint64_t n_sets, uint64_t n_batches, uint32_t sets_per_batch, uint64_t table_size,
+                                                uint64_t max_groups, int mode, int locate, mbls_vm_batches_committee_plan* out);
+int mbls_verify_multiple_batches_committee_msgtable_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96, const uint32_t* d_cmt_idx,
+                                                           const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
+                                                           const uint64_t* d_rands, uint64_t n_sets, const uint32_t* d_batch_offsets, uint32_t sets_per_batch,
+                                                           uint64_t n_batches, uint64_t max_groups, uint8_t* d_results, uint32_t* d_status, void* stream);
+int mbls_verify_multiple_batches_committee_msgtable_locate_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96,
+                                                                  const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt,
+                                                                  const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n_sets,
+                                                                  const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint64_t max_groups,
+                                                                  uint8_t* d_results, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream);
+int mbls_verify_multiple_batches_committee_msgtable_rng(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs96, const uint32_t* cmt_idx,
+                                                        const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n_sets,
+                                                        const uint32_t* batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint8_t* results,
+                                                        mbls_scalar_source draw, void* user);
+int mbls_verify_multiple_batches_committee_msgtable_locate_rng(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs96, const uint32_t* cmt_idx,
+                                                               const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx,
+                                                               uint64_t n_sets, const uint32_t* batch_offsets, uint32_t sets_per_batch, uint64_t n_batches,
+                                                               uint8_t* results, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user);
+/* test probe: the grouping of the grouped route alone (set map, k_vbg_group, the scan of the group counts) on host buffers and ANY batch table, faulty ones
+ * included. Arrays over the sets: n_sets words each (0xFFFFFFFF: none); group_count: n_batches; group_off: n_batches + 1. */
+int mbls_vbg_group_probe(mbls_ctx* ctx, const uint32_t* msg_idx, uint64_t n_sets, uint64_t table_size, const uint32_t* batch_offsets, uint32_t sets_per_batch,
+                         uint64_t n_batches, uint32_t* set_pos, uint32_t* set_status, uint32_t* pos_lo, uint32_t* pos_hi, uint32_t* group_head, uint32_t* group_entry,
+                         uint32_t* group_count, uint32_t* group_off);
 
 /* ---- batch helpers used to build inputs and caches on the device ---- */
 /* n x PublicKey::from_bytes[_unchecked] / from_uncompressed_bytes: errs[i] = MBLS_OK / MBLS_ERR_* per key */

@@ -711,6 +711,22 @@ public:
         const bool ok = vm(rng, sets, table, &per_set);
         return {ok, per_set};
     }
+    // verify_multiple_aggregate_signatures(rng, batch, table) once per batch of `batches`, in order, as ONE call on the GPU
+    // (mbls_verify_multiple_batches_committee_msgtable_rng): one bool per batch, a bad batch rejects itself and nothing else, and the sets of a batch that name one
+    // entry of `table` share one Miller loop. rng is left where AggregateSignature::verify_multiple_aggregate_signatures_batches leaves it on the spelled-out sets.
+    template <typename Rng>
+    std::vector<bool> verify_multiple_aggregate_signatures_batches(Rng&& rng, const std::vector<std::vector<GossipSet>>& batches, const MessageTable& table) const {
+        return vm_batches(rng, batches, table, nullptr);
+    }
+    // The same, and in the same call (mbls_verify_multiple_batches_committee_msgtable_locate_rng) which sets of the rejected batches are the bad ones, with the
+    // semantics of AggregateSignature::verify_multiple_aggregate_signatures_batches_locate.
+    template <typename Rng>
+    std::pair<std::vector<bool>, std::vector<std::vector<bool>>> verify_multiple_aggregate_signatures_batches_locate(
+            Rng&& rng, const std::vector<std::vector<GossipSet>>& batches, const MessageTable& table) const {
+        std::vector<std::vector<bool>> per_set;
+        std::vector<bool> ok = vm_batches(rng, batches, table, &per_set);
+        return {ok, per_set};
+    }
     // AggregateSignature::verify_multiple_aggregate_signatures over a BLOCK's sets (mbls_verify_multiple_committee_span_msgtable_rng): an attestation names the
     // committees of its committee_bits, in order, with aggregation_bits over their concatenated members (SpanSet::attestation; at most MBLS_SPAN_MAX_COMMITTEES
     // ids -- the sync aggregate is a span of one committee), and a proposer signature, a randao reveal or an exit is under ONE key (SpanSet::single_key). The same
@@ -773,6 +789,45 @@ private:
         detail::check(rc);
         if (per_set) per_set->assign(sres.begin(), sres.end());
         return ok == 1;
+    }
+    template <typename Rng>
+    std::vector<bool> vm_batches(Rng& rng, const std::vector<std::vector<GossipSet>>& batches, const MessageTable& table, std::vector<std::vector<bool>>* per_set) const {
+        if (batches.empty()) return {};
+        const size_t nb = batches.size();
+        const size_t covering = (size_t(max_members()) + 7) / 8;
+        const uint32_t stride = uint32_t(((covering ? covering : 1) + 3) / 4 * 4);
+        Bytes sigs, flat; std::vector<uint32_t> words, idx, boff{0};
+        for (const auto& b : batches) {
+            for (const GossipSet& s : b) {
+                sigs.insert(sigs.end(), s.signature->point.begin(), s.signature->point.end());
+                flat.resize(flat.size() + stride, 0);
+                std::copy(s.bits.begin(), s.bits.begin() + std::min(s.bits.size(), size_t(stride)), flat.end() - stride);
+                words.push_back(s.word); idx.push_back(s.msg_index);
+            }
+            if (words.size() > 0xFFFFFFFEull) throw std::invalid_argument("verify_multiple_aggregate_signatures_batches: set indices are 32-bit");
+            boff.push_back(uint32_t(words.size()));
+        }
+        const size_t n = words.size();
+        using R = typename std::remove_reference<Rng>::type;
+        struct src { R* rng; std::exception_ptr err; } u{&rng, nullptr};
+        mbls_scalar_source draw = [](void* user, uint64_t* out, uint64_t count) {
+            src* p = static_cast<src*>(user);
+            try { for (uint64_t i = 0; i < count; i++) out[i] = AggregateSignature::draw_scalar(*p->rng); }
+            catch (...) { p->err = std::current_exception(); for (uint64_t i = 0; i < count; i++) out[i] = 0; }        // never unwind through the C frames
+        };
+        std::vector<uint8_t> res(nb, 0), sres(per_set ? std::max<size_t>(n, 1) : 0, 0);
+        const int rc = per_set
+            ? mbls_verify_multiple_batches_committee_msgtable_locate_rng(detail::ctx(), h_, sigs.data(), words.data(), flat.data(), stride, table.handle(), idx.data(), n,
+                                                                         boff.data(), 0, nb, res.data(), sres.data(), nullptr, draw, &u)
+            : mbls_verify_multiple_batches_committee_msgtable_rng(detail::ctx(), h_, sigs.data(), words.data(), flat.data(), stride, table.handle(), idx.data(), n,
+                                                                  boff.data(), 0, nb, res.data(), draw, &u);
+        if (u.err) std::rethrow_exception(u.err);
+        detail::check(rc);
+        if (per_set) {
+            per_set->clear();
+            for (size_t b = 0; b < nb; b++) per_set->emplace_back(sres.begin() + boff[b], sres.begin() + boff[b + 1]);
+        }
+        return std::vector<bool>(res.begin(), res.end());
     }
     template <typename Rng>
     bool vm(Rng& rng, const std::vector<GossipSet>& sets, const MessageTable& table, std::vector<bool>* per_set) const {

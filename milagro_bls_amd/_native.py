@@ -164,6 +164,27 @@ def plan_verify_multiple_msgtable_locate_workspace_items(n, table_size, named=0,
     return int(lib().mbls_plan_verify_multiple_msgtable_locate_workspace_items(C.byref(L), n, table_size, named, mode))
 
 
+class VmBatchesCommitteePlan(C.Structure):
+    """include/mbls.h mbls_vm_batches_committee_plan"""
+    _fields_ = [("route", C.c_int32), ("miller", C.c_int32), ("tree_levels", C.c_uint32), ("product_levels", C.c_uint32), ("bound", C.c_uint64),
+                ("miller_items", C.c_uint64), ("workspace_items", C.c_uint64)]
+
+
+VBG_MAX_SETS = 1024              # include/mbls.h MBLS_VBG_MAX_SETS: a batch with more sets is not grouped
+VBG_NONE = 0xFFFFFFFF
+
+
+def plan_verify_multiple_batches_committee(n_sets, n_batches, sets_per_batch=0, table_size=0, max_groups=0, mode=0, locate=False, limits=None):
+    """what the verify_multiple_batches_committee_msgtable entries would do with n_sets sets in n_batches batches (sets_per_batch 0: a ragged device-side table)
+    over a resident table of table_size entries under the caller's bound max_groups (0: none), `limits` and grouping mode (pure: no GPU) -> dict"""
+    L = limits if limits is not None else default_limits()
+    vp_ = VmBatchesCommitteePlan()
+    rc = lib().mbls_plan_verify_multiple_batches_committee(C.byref(L), n_sets, n_batches, sets_per_batch, table_size, max_groups, mode, 1 if locate else 0, C.byref(vp_))
+    if rc != OK:
+        raise MblsError(rc, "mbls_plan_verify_multiple_batches_committee")
+    return {f: getattr(vp_, f) for f, _ in VmBatchesCommitteePlan._fields_}
+
+
 class StreamOpts(C.Structure):
     """include/mbls.h mbls_stream_opts (0 = default)"""
     _fields_ = [("round_items", C.c_uint64), ("round_keys", C.c_uint64), ("round_msg_bytes", C.c_uint64), ("depth", C.c_uint32), ("policy", C.c_uint32)]
@@ -348,6 +369,15 @@ SIGNATURES = {
     "mbls_verify_multiple_committee_span_msgtable_locate_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, SCALAR_SOURCE, vp]),
     "mbls_ctx_set_vm_span_split": (C.c_int, [vp, C.c_int]),
     "mbls_plan_verify_multiple_span": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "mbls_plan_verify_multiple_batches_committee": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_int, vp]),
+    "mbls_verify_multiple_batches_committee_msgtable_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp,
+                                                                         vp, vp]),
+    "mbls_verify_multiple_batches_committee_msgtable_locate_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64,
+                                                                                vp, vp, vp, vp, vp]),
+    "mbls_verify_multiple_batches_committee_msgtable_rng": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, SCALAR_SOURCE, vp]),
+    "mbls_verify_multiple_batches_committee_msgtable_locate_rng": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp, vp,
+                                                                             SCALAR_SOURCE, vp]),
+    "mbls_vbg_group_probe": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mbls_plan_locate_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64]),
     "mbls_verify_multiple_batches_locate_device": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp,
                                                              vp, vp, vp]),

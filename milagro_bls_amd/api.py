@@ -600,6 +600,70 @@ class AggregateSignature:
         per_set = [bool(x) for x in bytes(sres)[:len(sets)]]
         return out, [per_set[boffs[b]:boffs[b + 1]] for b in range(len(batches))]
 
+    @staticmethod
+    def verify_multiple_aggregate_signatures_committee_batches(rng, batches, committees, table):
+        """Not in the reference: verify_multiple_aggregate_signatures_committee once per batch, in order, as ONE call on the GPU
+        (mbls_verify_multiple_batches_committee_msgtable_rng). `batches`: an iterable of iterables of the sets that method takes. Returns list[bool], one per
+        batch; a bad batch rejects itself and nothing else. Inside a batch the sets that name one table entry share one Miller loop. `rng` is left exactly where
+        verify_multiple_aggregate_signatures_batches leaves it on the spelled-out sets. A committee id, key index or message index that names nothing raises."""
+        return AggregateSignature._vm_committee_batches(rng, batches, committees, table, False)
+
+    @staticmethod
+    def verify_multiple_aggregate_signatures_committee_batches_locate(rng, batches, committees, table):
+        """verify_multiple_aggregate_signatures_committee_batches, and in the same call (mbls_verify_multiple_batches_committee_msgtable_locate_rng) which sets of
+        the rejected batches are the bad ones. Returns (list[bool], list[list[bool]]) with the semantics of verify_multiple_aggregate_signatures_batches_locate."""
+        return AggregateSignature._vm_committee_batches(rng, batches, committees, table, True)
+
+    @staticmethod
+    def _vm_committee_batches(rng, batches, committees, table, locate):
+        batches = [list(b) for b in batches]
+        if not batches:
+            return ([], []) if locate else []
+        sets = [s for b in batches for s in b]
+        boffs = [0]
+        for b in batches:
+            boffs.append(boffs[-1] + len(b))
+        stride = max(4, (committees.max_members + 31) // 32 * 4)
+        words, fields = [], []
+        for s in sets:
+            if isinstance(s[1], SingleKey):
+                words.append(N.VM_SET_SINGLE_KEY | s[1].index)
+                fields.append(bytes(stride))
+            else:
+                cid, field = int(s[1]), bytes(s[2])
+                if not 0 <= cid < N.VM_SET_SINGLE_KEY:
+                    raise ValueError("committee id out of range")
+                if len(field) > stride and any(field[stride:]):
+                    raise ValueError("a bitfield names members beyond the table's largest committee")
+                words.append(cid)
+                fields.append(field[:stride].ljust(stride, b"\0"))
+        n = len(sets)
+        failed = []
+        cb = N.SCALAR_SOURCE(_reference_draw(rng, failed))
+        cidx = (C.c_uint32 * max(1, n))(*words)
+        midx = (C.c_uint32 * max(1, n))(*[int(s[3]) for s in sets])
+        boff = (C.c_uint32 * len(boffs))(*boffs)
+        res = N.outbuf(len(batches))
+        ctx = committees.ctx
+        S, B = N.cbuf(b"".join(s[0].point for s in sets)), N.cbuf(b"".join(fields))
+        if locate:
+            sres = N.outbuf(max(1, n))
+            if not sets:
+                C.memset(sres, 1, 1)
+            rc = N.lib().mbls_verify_multiple_batches_committee_msgtable_locate_rng(ctx.handle, committees.handle, S, cidx, B, stride, table.handle, midx, n, boff, 0,
+                                                                                   len(batches), res, sres, None, cb, None)
+        else:
+            rc = N.lib().mbls_verify_multiple_batches_committee_msgtable_rng(ctx.handle, committees.handle, S, cidx, B, stride, table.handle, midx, n, boff, 0,
+                                                                            len(batches), res, cb, None)
+        if failed:
+            raise failed[0]
+        ctx.check(rc)
+        out = [bool(x) for x in bytes(res)[:len(batches)]]
+        if not locate:
+            return out
+        per_set = [bool(x) for x in bytes(sres)[:n]]
+        return out, [per_set[boffs[b]:boffs[b + 1]] for b in range(len(batches))]
+
     @classmethod
     def from_bytes(cls, data):
         out = N.outbuf(96)

@@ -794,6 +794,78 @@ def verify_multiple_committee_msgtable_locate_rng(committees, msg_table, sigs, c
     return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:n]], list(sst)[:n]
 
 
+# ---- many verify_multiple batches per call over committee bitfields and the resident message table (include/mbls.h,
+# mbls_verify_multiple_batches_committee_msgtable*): the sets of the entries above, the batches of verify_multiple_batches*; one bool and one status word per batch,
+# for _locate per set as well. Grouped route: one Miller loop per distinct (batch, table entry) pair.
+plan_verify_multiple_batches_committee = N.plan_verify_multiple_batches_committee
+VBG_MAX_SETS = N.VBG_MAX_SETS
+
+
+def verify_multiple_batches_committee_msgtable_device(committees, msg_table, d_sigs, d_cmt_idx, d_bits, bits_stride, d_msg_idx, d_rands, n_sets, n_batches, d_results,
+                                                      d_status=None, d_batch_offsets=None, sets_per_batch=0, max_groups=0, stream=None, ctx=None):
+    """verify_multiple_batches_indexed_device with every set's signers named by committee and bitfield (or by one key index) and its message by an index into the
+    resident table. max_groups: the caller's bound on the distinct (batch, entry) pairs of the call (0: none). Enqueues only: n_batches result bytes at d_results,
+    n_batches status words at d_status (optional)."""
+    ctx = ctx or committees.ctx
+    ctx.check(N.lib().mbls_verify_multiple_batches_committee_msgtable_device(ctx.handle, committees.handle, d_sigs, d_cmt_idx, d_bits, bits_stride, msg_table.handle,
+                                                                             d_msg_idx, d_rands, n_sets, d_batch_offsets, sets_per_batch, n_batches, max_groups,
+                                                                             d_results, d_status, stream))
+
+
+def verify_multiple_batches_committee_msgtable_locate_device(committees, msg_table, d_sigs, d_cmt_idx, d_bits, bits_stride, d_msg_idx, d_rands, n_sets, n_batches,
+                                                             d_results, d_set_results, d_status=None, d_set_status=None, d_batch_offsets=None, sets_per_batch=0,
+                                                             max_groups=0, stream=None, ctx=None):
+    """The same, and in the same call one answer per SET, as verify_multiple_batches_locate_indexed_device gives it: n_sets result bytes at d_set_results
+    (required), n_sets status words at d_set_status (optional). Enqueues only."""
+    ctx = ctx or committees.ctx
+    ctx.check(N.lib().mbls_verify_multiple_batches_committee_msgtable_locate_device(ctx.handle, committees.handle, d_sigs, d_cmt_idx, d_bits, bits_stride,
+                                                                                    msg_table.handle, d_msg_idx, d_rands, n_sets, d_batch_offsets, sets_per_batch,
+                                                                                    n_batches, max_groups, d_results, d_status, d_set_results, d_set_status, stream))
+
+
+def verify_multiple_batches_committee_msgtable_rng(committees, msg_table, sigs, cmt_idx, bits, bits_stride, msg_idx, n_sets, n_batches, draw, batch_offsets=None,
+                                                   sets_per_batch=0, ctx=None):
+    """Host buffers and the draw order of verify_multiple_batches_rng (draw as verify_multiple_msgtable_rng takes it). A word or a message index that names
+    nothing, or a batch table that is not sound, raises (MBLS_ERR_ARGUMENT). Returns list[bool], one per batch."""
+    ctx = ctx or committees.ctx
+    res = N.outbuf(max(1, n_batches))
+    cb = _scalar_source(draw)
+    ctx.check(N.lib().mbls_verify_multiple_batches_committee_msgtable_rng(ctx.handle, committees.handle, N.cbuf(sigs), _midx(cmt_idx, n_sets),
+                                                                          _bits(bits, bits_stride, n_sets), bits_stride, msg_table.handle, _midx(msg_idx, n_sets), n_sets,
+                                                                          _boff(batch_offsets), sets_per_batch, n_batches, res, cb, None))
+    return [bool(x) for x in bytes(res)[:n_batches]]
+
+
+def verify_multiple_batches_committee_msgtable_locate_rng(committees, msg_table, sigs, cmt_idx, bits, bits_stride, msg_idx, n_sets, n_batches, draw, batch_offsets=None,
+                                                          sets_per_batch=0, ctx=None):
+    """verify_multiple_batches_committee_msgtable_rng with one answer per set. Returns (results, set_results, set_status)."""
+    ctx = ctx or committees.ctx
+    res = N.outbuf(max(1, n_batches))
+    sres = N.outbuf(max(1, n_sets))
+    sst = (C.c_uint32 * max(1, n_sets))()
+    cb = _scalar_source(draw)
+    ctx.check(N.lib().mbls_verify_multiple_batches_committee_msgtable_locate_rng(ctx.handle, committees.handle, N.cbuf(sigs), _midx(cmt_idx, n_sets),
+                                                                                 _bits(bits, bits_stride, n_sets), bits_stride, msg_table.handle,
+                                                                                 _midx(msg_idx, n_sets), n_sets, _boff(batch_offsets), sets_per_batch, n_batches, res, sres,
+                                                                                 sst, cb, None))
+    return [bool(x) for x in bytes(res)[:n_batches]], [bool(x) for x in bytes(sres)[:n_sets]], list(sst)[:n_sets]
+
+
+def vbg_group_probe(msg_idx, table_size, n_batches, batch_offsets=None, sets_per_batch=0, ctx=None):
+    """test probe (mbls_vbg_group_probe): the grouping of the grouped route alone, on ANY batch table -> dict of lists: pos, status, pos_lo, pos_hi, head, entry
+    (one word per set), count (per batch), off (n_batches + 1)"""
+    ctx = ctx or _c()
+    n = len(msg_idx)
+    outs = [(C.c_uint32 * max(1, n))() for _ in range(6)]
+    cnt, off = (C.c_uint32 * max(1, n_batches))(), (C.c_uint32 * (n_batches + 1))()
+    ctx.check(N.lib().mbls_vbg_group_probe(ctx.handle, (C.c_uint32 * max(1, n))(*msg_idx), n, table_size, _boff(batch_offsets), sets_per_batch, n_batches, outs[0],
+                                           outs[1], outs[2], outs[3], outs[4], outs[5], cnt, off))
+    names = ("pos", "status", "pos_lo", "pos_hi", "head", "entry")
+    d = {k: list(o)[:n] for k, o in zip(names, outs)}
+    d["count"], d["off"] = list(cnt)[:n_batches], list(off)
+    return d
+
+
 # ---- verify_multiple over committee spans and the resident message table (include/mbls.h, mbls_verify_multiple_committee_span_msgtable*): set i names the ids
 # cmt_ids[cmt_off[i] .. cmt_off[i + 1]) and one field over their concatenated members -- or is the one id VM_SET_SINGLE_KEY | key-table index, whose field is not read.
 plan_verify_multiple_committee_span = N.plan_verify_multiple_committee_span

@@ -31,6 +31,7 @@
 #include "mbls_cmt_lanes.h"
 #include "mbls_cms_launch.h"
 #include "mbls_vcs_launch.h"
+#include "mbls_vbg_launch.h"
 #include "../../include/mbls.h"
 
 // The product library exists only with the generated routines: the host side below selects kernels (the fused subgroup verdict of
@@ -5011,6 +5012,346 @@ extern "C" int mbls_verify_multiple_batches_locate_rng(mbls_ctx* c, const uint8_
         const uint64_t* moff, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, uint8_t* set_results, uint32_t* set_status,
         mbls_scalar_source draw, void* user) {
     return vmb_rng_impl(c, sigs96, apks96, msgs, msg_len, moff, n, boff, spb, B, results, draw, user, true, set_results, set_status);
+}
+
+// ---- B verify_multiple batches in one call over committee bitfields and the resident message table (include/mbls.h, mbls_verify_multiple_batches_committee_msgtable*;
+// rules: mbls_vbg.h). The sets are the _committee_msgtable entries', the batches vmb_impl's, and every output is what vmb_impl writes for the spelled-out sets.
+// PER-SET ROUTE: vmb_impl's chains with the key phase the committee source's (k_vmc_expand, k_aggregate_vmc_d) and the message phase the gather from the table.
+// GROUPED ROUTE: one Miller loop per distinct (batch, entry) pair -- the kernels of mbls_vbg.hip. Workspace: the sets [0, n), over which the Miller items
+// [0, B + bound) are laid once the blinded keys have moved to the positions [pbase, pbase + n); the tail's items [tail, tail + 2 B); for _locate the shadows
+// A(i) = shf + i and B(i) = shf + n + i of mbls_vsl.h. The signature chain is vmb_impl's. Enqueues only; every fallible step comes before the first kernel on a
+// side stream.
+static void plan_vm_batches_committee(const mbls_limits& L, uint64_t n, uint64_t B, uint32_t spb, uint64_t T, uint64_t max_groups, int mode, bool locate,
+                                      uint64_t longest_known, mbls_vm_batches_committee_plan* vp) {
+    memset(vp, 0, sizeof(*vp));
+    const uint64_t longest = vbg_longest(n, spb, longest_known), bound = vbg_bound(n, B, T, spb, max_groups, longest);
+    const bool grouped = n && vbg_grouped(n, bound, mode);
+    vp->route = grouped ? MBLS_VM_ROUTE_GROUPED : MBLS_VM_ROUTE_PER_SET;
+    vp->bound = bound;
+    vp->miller_items = vbg_miller_items(n, B, bound, grouped);
+    vp->tree_levels = grouped ? vbg_key_levels(longest) : vmb_levels(longest);
+    vp->product_levels = grouped ? vbg_product_levels(longest, bound) : vmb_levels(longest);
+    vp->workspace_items = vbg_workspace_items(n, B, bound, grouped, locate);
+    const uint64_t m = vp->miller_items, R = L.round_items;
+    if (2 * m <= L.coop_max_items) vp->miller = MBLS_PAIRING_WAVE;
+    else {
+        const uint64_t full = (R && m > R) ? (m / R) * R : 0, rest = m - full;
+        vp->miller = (rest && 2 * rest <= R) ? MBLS_PAIRING_LANES2 : MBLS_PAIRING_LANE;
+    }
+}
+extern "C" int mbls_plan_verify_multiple_batches_committee(const mbls_limits* limits, uint64_t n_sets, uint64_t n_batches, uint32_t sets_per_batch, uint64_t table_size,
+        uint64_t max_groups, int mode, int locate, mbls_vm_batches_committee_plan* out) {
+    if (!limits || !out || !n_sets || !n_batches || mode < 0 || mode > 2) return MBLS_ERR_ARGUMENT;
+    if (n_sets > 0xFFFFFFFEull || n_batches > 0xFFFFFFFEull || table_size > 0xFFFFFFFFull) return MBLS_ERR_ARGUMENT;
+    if (sets_per_batch && (uint64_t)sets_per_batch * n_batches != n_sets) return MBLS_ERR_ARGUMENT;
+    plan_vm_batches_committee(*limits, n_sets, n_batches, sets_per_batch, table_size, max_groups, mode, locate != 0, 0, out); return MBLS_OK;
+}
+static int vbg_impl(mbls_ctx* c, const uint8_t* d_sigs, const vm_committee& vc, const mbls_msgtable* mt, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n,
+        const uint32_t* d_boff, uint32_t spb, uint64_t B, uint64_t longest, uint64_t max_groups, uint8_t* d_results, uint32_t* d_status, void* stream,
+        bool sigs_resident = false, const vmb_locate* loc = nullptr) {
+    if (!c || !mt) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
+    if (!d_results) ARGFAIL(c, "null results");
+    if (loc && !loc->d_set_results) ARGFAIL(c, "null set results");
+    if (n > 0xFFFFFFFEull || B > 0xFFFFFFFEull) ARGFAIL(c, "set and batch indices are 32-bit");
+    if (!d_boff && (uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch");
+    if (n && !d_rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
+    if (n && ((!d_sigs && !sigs_resident) || !d_midx || !vc.d_cmt_idx || !vc.d_bits)) ARGFAIL(c, "null buffer");
+    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t T = mt->size;
+    mbls_vm_batches_committee_plan vp;
+    plan_vm_batches_committee(ctx_limits(c), n, B, d_boff ? 0u : spb, T, max_groups, c->vm_grouping, loc != nullptr, longest, &vp);
+    const bool grouped = vp.route == MBLS_VM_ROUTE_GROUPED;
+    const uint64_t bound = vp.bound, n_miller = vp.miller_items;
+    int rc = mbls_ctx_reserve(c, vp.workspace_items); if (rc) return rc;
+    if (n) { rc = reserve_committee(c, n, vc.cmax); if (rc) return rc; }
+    if (grouped) { rc = reserve_groups(c, vbg_group_words(n, B)); if (rc) return rc; }
+    uint32_t* map = nullptr;
+    sbuf dmap(c, 9);
+    if (d_boff) { HIPCHK(c, dmap.alloc(4 * (n ? n : 1))); map = dmap.as<uint32_t>(); }
+    mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
+    const uint64_t pbase = vbg_position_base(n, B, bound), tail = grouped ? vbg_tail_first(n, B, bound) : n;
+    const uint64_t shf = grouped ? vbg_shadow_first(n, B, bound) : vml_shadow_first(n, B, false);     // locate mode: the first shadow item
+    mbls_ws wv = ws; wv.w += tail;                                  // the batches' view: item b of wv = the batch's pair value, item B + b its sets' product
+    rc = ws_acquire(c, s); if (rc) return rc;
+    rc = msgtable_acquire(c, mt, s); if (rc) return rc;
+    rc = committees_acquire(c, vc.t, s); if (rc) return rc;
+    rc = table_acquire(c, vc.kt, s); if (rc) return rc;
+    const uint32_t* const tab = mt->d_tab; const uint64_t tstride = mtb_stride(mt->cap); const uint32_t* const flags = mt->d_flag;
+    uint32_t* st_set = c->d_status;                                 // (cap >= n + 2 B words; locate: 2 n + 2 B)
+    uint32_t* st_batch = d_status ? d_status : c->d_status + n;
+    uint32_t* owned = c->d_status + n + B;
+    uint32_t* cand = c->d_status + vml_flags_first(n, B);
+    mbls_vbg_arrays ga = {};
+    if (grouped) {
+        const uint64_t gc = c->hgrp_cap;
+        ga.pos = c->d_hgrp; ga.rlo = c->d_hgrp + gc; ga.rhi = c->d_hgrp + 2 * gc; ga.head = c->d_hgrp + 3 * gc; ga.entry = c->d_hgrp + 4 * gc;
+        ga.gcount = c->d_hgrp + 5 * gc; ga.goff = ga.gcount + B;   // (goff[0 .. B], then the live word: 2 B + 2 words)
+    }
+    uint32_t* const d_live = grouped ? ga.goff + B + 1 : nullptr;
+    if (n && !sigs_resident) HIPCHK(c, hipMemsetAsync(st_set, 0, 4 * n, s));          // (resident: cleared before k_sig)
+    HIPCHK(c, hipMemsetAsync(c->d_status + n, 0, 8 * B, s));
+    if (d_status) HIPCHK(c, hipMemsetAsync(d_status, 0, 4 * B, s));
+    if (map) HIPCHK(c, hipMemsetAsync(map, 0xFF, 4 * (n ? n : 1), s));
+    HIPCHK(c, hipMemsetAsync(d_results, 0, B, s));                  // false until the tail kernel has spoken (fail closed)
+    if (loc && n) {
+        HIPCHK(c, hipMemsetAsync(loc->d_set_results, 0, n, s));
+        if (loc->d_set_status) HIPCHK(c, hipMemsetAsync(loc->d_set_status, 0, 4 * n, s));
+        HIPCHK(c, hipMemsetAsync(cand, 0, 4 * n, s));
+    }
+    if (grouped) {
+        HIPCHK(c, hipMemsetAsync(c->d_hgrp, 0xFF, 4 * 5 * c->hgrp_cap, s));      // positions, ranges, group records: none
+        HIPCHK(c, hipMemsetAsync(ga.gcount, 0, 4 * (2 * B + 2), s));
+    }
+    // the map before the chains fork: the signatures' trees and the grouping both read it
+    if (n && map) hipLaunchKernelGGL(k_vmb_set_map, dim3(nblk(B)), dim3(WG), 0, s, d_boff, B, n, map);
+    const bool fork = n && 2 * n <= c->round_items;
+    hipStream_t s_sig = fork ? c->hs_b : s, s_msg = fork ? c->hs_c : s;
+    if (fork) { HIPCHK(c, hipEventRecord(c->hs_ev, s)); HIPCHK(c, hipStreamWaitEvent(s_sig, c->hs_ev, 0)); HIPCHK(c, hipStreamWaitEvent(s_msg, c->hs_ev, 0)); }
+    if (!longest) longest = d_boff ? n : spb;
+    if (n) {
+        // the message phase of the per-set route: every set takes its entry's point (the grouped route reads the table from its Miller items)
+        if (!grouped) hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, tab, tstride, flags, d_midx, T, st_set, n);
+        // the key phase: the committee source of verify_multiple_impl
+        const uint64_t ls = vc.list_stride();
+        uint32_t* const cnt = c->d_cmt_cnt; uint32_t* const route = c->d_cmt_cnt + c->cmt_items;
+        hipLaunchKernelGGL(k_vmc_expand, dim3((unsigned)n), dim3(WG), 0, s, vc.d_crecs, vc.ccount, vc.d_members, vc.d_cmt_idx, vc.d_bits, vc.bits_stride, c->cmt_route_mode,
+                           c->d_cmt_list, ls, cnt, route, n);
+        hipLaunchKernelGGL(k_aggregate_vmc_d, dim3(nblk(n)), dim3(WG), 0, s, ws, vc.d_recs, vc.tsize, (const uint32_t*)c->d_cmt_list, ls, (const uint32_t*)cnt, (const uint32_t*)route,
+                           vc.d_crecs, vc.d_cmt_idx, st_set, n);
+        hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint8_t*)nullptr, d_rands, st_set, n);
+        if (grouped) {      // groups, their offsets, the keys to their positions, the per-group sums: behind the keys on their stream
+            mbls_vbg_launch_group(d_midx, T, d_boff, spb, B, n, (const uint32_t*)map, ga, st_set, s);
+            hipLaunchKernelGGL(k_vms_scan, dim3(1), dim3(MBLS_VMS_SCAN_LANES), 0, s, (const uint32_t*)ga.gcount, B, ga.goff);
+            if (loc) hipLaunchKernelGGL(k_vsl_keep_key, dim3(nblk(n)), dim3(WG), 0, s, ws, n, shf);      // [r_i] apk_i -> A(i), before the heads are written over the sets' items
+            mbls_vbg_launch_scatter(ws, (const uint32_t*)ga.pos, n, pbase, s);
+            mbls_ws wp = ws; wp.w += pbase;
+            mbls_vbg_launch_key_trees(wp, (const uint32_t*)ga.rlo, (const uint32_t*)ga.rhi, n, vp.tree_levels, s);
+        }
+        if (2 * n <= c->coop_max_items)
+            hipLaunchKernelGGL(k_blind_sig2_d, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, st_set, n);
+        else
+            hipLaunchKernelGGL(k_blind_sig_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, st_set, n);
+        if (loc) hipLaunchKernelGGL(k_vml_keep_sig, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, n, grouped ? shf + n : shf);
+        for (uint64_t half = 1; half < longest; half *= 2)         // S_b: the per-batch sums of the blinded signatures, left at the head of each range
+            hipLaunchKernelGGL(k_g2_seg_tree_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, (const uint32_t*)map, d_boff, spb, B, n, half);
+    }
+    if (fork) {
+        HIPCHK(c, hipEventRecord(c->hs_ev2, s_sig)); HIPCHK(c, hipEventRecord(c->hs_ev3, s_msg));
+        HIPCHK(c, hipStreamWaitEvent(s, c->hs_ev2, 0)); HIPCHK(c, hipStreamWaitEvent(s, c->hs_ev3, 0));
+    }
+    if (grouped) {
+        if (n) hipLaunchKernelGGL(k_vmb_status_fold, dim3(nblk(n)), dim3(WG), 0, s, (const uint32_t*)map, d_boff, spb, B, n, (const uint32_t*)st_set, st_batch, owned);
+        // (the heads leave the live Miller items, B + min(D, bound), in *d_live: waves above them return at once)
+        mbls_vbg_launch_heads(ws, tab, tstride, flags, T, ga, d_boff, spb, B, n, bound, pbase, c->d_vmap, st_batch, d_live, s);
+        if (2 * n_miller <= c->coop_max_items)
+            coop_run(c, COOP_MILLER1, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, n_miller, (uint32_t*)nullptr, (uint8_t*)nullptr, COOP_RES_ITEM, s, (const uint32_t*)d_live);
+        else
+            launch_miller_single(c, ws, n_miller, s, (const uint32_t*)d_live);
+        if (bound) {
+            mbls_ws wg = ws; wg.w += B;                             // the group items' view
+            uint64_t half = 1;
+            for (uint32_t l = 0; l < vp.product_levels; l++, half *= 2)
+                hipLaunchKernelGGL(k_f12_seg_tree_d, dim3(nblk(bound)), dim3(WG), 0, s, wg, (const uint32_t*)c->d_vmap, (const uint32_t*)ga.goff, 0u, B, bound, half);
+        }
+        mbls_vbg_launch_gather(ws, ga, d_boff, spb, B, n, bound, tail, st_batch, (const uint32_t*)owned, s);
+    } else {
+        // the B signature pairs join the sets: one Miller loop per workspace item [0, n + B)
+        hipLaunchKernelGGL(k_vmb_sigpair_setup, dim3(nblk(B)), dim3(WG), 0, s, ws, d_boff, spb, B, n);
+        if (2 * (n + B) <= c->coop_max_items)
+            coop_run(c, COOP_MILLER1, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, n + B, (uint32_t*)nullptr, (uint8_t*)nullptr, COOP_RES_ITEM, s);
+        else
+            launch_miller_single(c, ws, n + B, s);
+        if (n) {
+            hipLaunchKernelGGL(k_vmb_status_fold, dim3(nblk(n)), dim3(WG), 0, s, (const uint32_t*)map, d_boff, spb, B, n, (const uint32_t*)st_set, st_batch, owned);
+            if (loc) hipLaunchKernelGGL(k_vml_keep_f, dim3(nblk(n)), dim3(WG), 0, s, ws, n, shf);
+            for (uint64_t half = 1; half < longest; half *= 2)     // the per-batch products of the sets' Miller values
+                hipLaunchKernelGGL(k_f12_seg_tree_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)map, d_boff, spb, B, n, half);
+        }
+        hipLaunchKernelGGL(k_vmb_gather, dim3(nblk(B)), dim3(WG), 0, s, ws, d_boff, spb, B, n, st_batch, (const uint32_t*)owned);
+    }
+    hipLaunchKernelGGL(k_f12_tree_d, dim3(nblk(B)), dim3(WG), 0, s, wv, 2 * B, B);      // batch b <- (its signature pair) x (its sets' product)
+    if (B <= c->split_max_items && 2 * B <= c->round_items) hipLaunchKernelGGL(k_vmb_final2, dim3(nblk(2 * B)), dim3(WG), 0, s, wv, st_batch, d_results, B);
+    else hipLaunchKernelGGL(k_vmb_final, dim3(nblk(B)), dim3(WG), 0, s, wv, st_batch, d_results, B);
+    if (loc && n && grouped) {     // phase two of mbls_vsl.h with the set's batch in the place of the call: mark, both pairs' Miller loops, product, final
+        mbls_ws wsa = ws; wsa.w += shf;
+        mbls_vbg_launch_mark(wsa, tab, tstride, flags, d_midx, T, (const uint32_t*)map, d_boff, spb, B, n, (const uint32_t*)st_set, (const uint32_t*)owned,
+                             (const uint8_t*)d_results, cand, loc->d_set_results, loc->d_set_status, s);
+        vsl_examine(c, ws, n, shf, true, st_set, cand, loc->d_set_results, loc->d_set_status, s);
+    } else if (loc && n) {         // vmb_impl's phase two
+        hipLaunchKernelGGL(k_vml_mark, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)map, d_boff, spb, B, n, (const uint32_t*)st_set, (const uint32_t*)owned,
+                           (const uint8_t*)d_results, cand, loc->d_set_results, loc->d_set_status, shf);
+        vsl_examine(c, ws, n, shf, false, st_set, cand, loc->d_set_results, loc->d_set_status, s);
+    }
+    HIPCHK(c, hipGetLastError());
+    return ws_release(c, s);
+}
+static int vbg_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride,
+                      const mbls_msgtable* mt, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n, const uint32_t* d_boff, uint32_t spb, uint64_t B,
+                      uint64_t max_groups, uint8_t* d_results, uint32_t* d_status, void* stream, const vmb_locate* loc) {
+    if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
+    vm_committee vc; const int rk = vm_committee_of(c, t, d_cmt_idx, d_bits, bits_stride, true, &vc); if (rk) return rk;
+    return vbg_impl(c, d_sigs, vc, mt, d_midx, d_rands, n, d_boff, spb, B, 0, max_groups, d_results, d_status, stream, false, loc);
+}
+extern "C" int mbls_verify_multiple_batches_committee_msgtable_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx,
+        const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, const uint32_t* d_batch_offsets,
+        uint32_t sets_per_batch, uint64_t n_batches, uint64_t max_groups, uint8_t* d_results, uint32_t* d_status, void* stream) {
+    return vbg_device(c, t, d_sigs, d_cmt_idx, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, max_groups, d_results, d_status,
+                      stream, nullptr);
+}
+extern "C" int mbls_verify_multiple_batches_committee_msgtable_locate_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx,
+        const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, const uint32_t* d_batch_offsets,
+        uint32_t sets_per_batch, uint64_t n_batches, uint64_t max_groups, uint8_t* d_results, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status,
+        void* stream) {
+    if (!d_set_results) return MBLS_ERR_ARGUMENT;
+    vmb_locate loc; loc.d_set_results = d_set_results; loc.d_set_status = d_set_status;
+    return vbg_device(c, t, d_sigs, d_cmt_idx, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, max_groups, d_results, d_status,
+                      stream, &loc);
+}
+// host buffers, the draw order of vmb_rng_impl: the signatures of ALL batches are decoded and tested first, `draw` is asked once for the scalars of the sets in front
+// of each batch's first signature outside G2, the rest runs without a second subgroup test. A committee id, key index or message index that names nothing, or a batch
+// table that is not sound, refuses the call with nothing queued and the outputs untouched. The host counts the distinct (batch, entry) pairs itself.
+static int vbg_rng_impl(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_stride,
+        const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, mbls_scalar_source draw, void* user,
+        bool locate, uint8_t* set_results, uint32_t* set_status) {
+    if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
+    if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
+    if (!results) ARGFAIL(c, "null results");
+    if (locate && !set_results) ARGFAIL(c, "null set results");
+    if (n > 0xFFFFFFFEull || B > 0xFFFFFFFEull) ARGFAIL(c, "set and batch indices are 32-bit");
+    uint64_t longest = spb;
+    if (boff) { if (!vmb_offsets_ok(boff, B, n, &longest)) ARGFAIL(c, "batch_offsets must start at 0, be non-decreasing and end at n_sets"); }
+    else if ((uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch");
+    vm_committee vc; const int rk = vm_committee_of(c, t, nullptr, nullptr, bits_stride, false, &vc); if (rk) return rk;
+    if (n == 0) { memset(results, 1, B); return MBLS_OK; }                  // empty iterators: true, the generator untouched
+    if (!sigs96 || !cmt_idx || !bits || !msg_idx) ARGFAIL(c, "null buffer");
+    if (!draw) ARGFAIL(c, "null scalar source");
+    const uint64_t T = mt->size;
+    for (uint64_t i = 0; i < n; i++) {
+        if (vmc_names_nothing(cmt_idx[i], vc.ccount, vc.tsize))
+            ARGFAIL(c, vmc_is_single(cmt_idx[i]) ? "cmt_idx names no key of the key table" : "cmt_idx names no committee of the table");
+        if ((uint64_t)msg_idx[i] >= T) ARGFAIL(c, "msg_idx names no entry of the message table");
+    }
+    std::vector<uint64_t> rands, drawn, reach; std::vector<uint32_t> st, seen;
+    try { rands.resize(n); drawn.resize(n); st.resize(n); reach.resize(B); } catch (...) { ARGFAIL(c, "out of host memory"); }
+    // the distinct (batch, entry) pairs, counted the way the wave counts them: a set without an earlier set of its batch naming the same entry
+    uint64_t groups = 0;
+    for (uint64_t b = 0; b < B; b++) {
+        const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
+        if (!vbg_batch_grouped(hi - lo)) { groups += hi - lo; continue; }
+        try { seen.assign(msg_idx + lo, msg_idx + hi); } catch (...) { ARGFAIL(c, "out of host memory"); }
+        std::sort(seen.begin(), seen.end());
+        groups += (uint64_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // everything that may allocate comes before the first kernel: the workspace of the WHOLE call, the committee scratch, the group arrays, the staging
+    mbls_vm_batches_committee_plan vp;
+    plan_vm_batches_committee(ctx_limits(c), n, B, boff ? 0u : spb, T, groups, c->vm_grouping, locate, longest, &vp);
+    int rc = mbls_ctx_reserve(c, vp.workspace_items); if (rc) return rc;
+    rc = reserve_committee(c, n, vc.cmax); if (rc) return rc;
+    if (vp.route == MBLS_VM_ROUTE_GROUPED) { rc = reserve_groups(c, vbg_group_words(n, B)); if (rc) return rc; }
+    sbuf ds(c, 0), da(c, 1), dr(c, 3), dbo(c, 5), dres(c, 4), dmi(c, 7), dset(c, 8), dmap(c, 9), dci(c, 10);
+    HIPCHK(c, ds.up(sigs96, 96 * n)); HIPCHK(c, da.up(bits, (size_t)bits_stride * n)); HIPCHK(c, dci.up(cmt_idx, 4 * n)); HIPCHK(c, dmi.up(msg_idx, 4 * n));
+    HIPCHK(c, dr.alloc(8 * n)); HIPCHK(c, dres.alloc(B));
+    if (boff) { HIPCHK(c, dbo.up(boff, 4 * (B + 1))); HIPCHK(c, dmap.alloc(4 * n)); }
+    vmb_locate loc;
+    if (locate) { HIPCHK(c, dset.alloc(5 * n)); loc.d_set_status = dset.as<uint32_t>(); loc.d_set_results = dset.as<uint8_t>() + 4 * n; }
+    vc.d_cmt_idx = dci.as<uint32_t>(); vc.d_bits = da.as<uint8_t>();
+    // the signatures: decoded and tested, the verdicts read back (vm_rng_phase1's signature half)
+    hipStream_t s = c->hs_a;
+    mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
+    rc = ws_acquire(c, s); if (rc) return rc;
+    if (hipMemsetAsync(c->d_status, 0, 4 * n, s) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
+    if (2 * n <= c->coop_max_items) hipLaunchKernelGGL(k_sig2, dim3(nblk(2 * n)), dim3(WG), 0, s, ws, (const uint8_t*)ds.as<uint8_t>(), c->d_status, (uint64_t)n);
+    else hipLaunchKernelGGL(k_sig, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint8_t*)ds.as<uint8_t>(), c->d_status, (uint64_t)n, 1);
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(st.data(), c->d_status, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
+    uint64_t total = 0;
+    for (uint64_t b = 0; b < B; b++) {
+        const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
+        uint64_t r = hi;
+        for (uint64_t i = lo; i < hi; i++) if (st[i] & (MBLS_ST_BAD_SIG_ENCODING | MBLS_ST_SIG_NOT_IN_G2)) { r = i; break; }
+        reach[b] = r - lo; total += r - lo;
+    }
+    if (total) draw(user, drawn.data(), total);
+    uint64_t at = 0;
+    for (uint64_t b = 0; b < B; b++) {
+        const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
+        for (uint64_t i = lo; i < hi; i++) rands[i] = i - lo < reach[b] ? drawn[at++] : 1;
+    }
+    hipError_t e = dr.up(rands.data(), 8 * n);
+    std::fill(rands.begin(), rands.end(), 0); std::fill(drawn.begin(), drawn.end(), 0);
+    if (e != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
+    rc = vbg_impl(c, nullptr, vc, mt, dmi.as<uint32_t>(), dr.as<uint64_t>(), n, boff ? dbo.as<uint32_t>() : nullptr, spb, B, longest ? longest : 1, groups,
+                  dres.as<uint8_t>(), nullptr, s, true, locate ? &loc : nullptr);
+    if (rc) { vm_rng_drain(c); return rc; }
+    if (hipStreamSynchronize(s) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
+    c->ws_pending = false;
+    HIPCHK(c, dres.down(results, B));
+    if (locate) {
+        std::vector<uint32_t> sst;
+        try { sst.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
+        HIPCHK(c, hipMemcpy(set_results, loc.d_set_results, n, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(sst.data(), loc.d_set_status, 4 * n, hipMemcpyDeviceToHost));
+        for (uint64_t b = 0; b < B; b++) {
+            const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
+            for (uint64_t i = lo + reach[b]; i < hi; i++) { set_results[i] = 0; sst[i] = st[i]; }
+        }
+        if (set_status) memcpy(set_status, sst.data(), 4 * n);
+    }
+    return MBLS_OK;
+}
+extern "C" int mbls_verify_multiple_batches_committee_msgtable_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_idx, const uint8_t* bits,
+        uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results,
+        mbls_scalar_source draw, void* user) {
+    return vbg_rng_impl(c, t, sigs96, cmt_idx, bits, bits_stride, mt, msg_idx, n, boff, spb, B, results, draw, user, false, nullptr, nullptr);
+}
+extern "C" int mbls_verify_multiple_batches_committee_msgtable_locate_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_idx,
+        const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B,
+        uint8_t* results, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user) {
+    return vbg_rng_impl(c, t, sigs96, cmt_idx, bits, bits_stride, mt, msg_idx, n, boff, spb, B, results, draw, user, true, set_results, set_status);
+}
+// test probe: steps 1-2 of the grouped route alone (k_vmb_set_map for a ragged table, k_vbg_group, k_vms_scan) on caller-given indices and batch table -- any
+// table, faulty ones included -- with host buffers; every array over the sets has n_sets words, group_count n_batches, group_off n_batches + 1
+extern "C" int mbls_vbg_group_probe(mbls_ctx* c, const uint32_t* msg_idx, uint64_t n, uint64_t table_size, const uint32_t* boff, uint32_t spb, uint64_t B,
+        uint32_t* set_pos, uint32_t* set_status, uint32_t* pos_lo, uint32_t* pos_hi, uint32_t* group_head, uint32_t* group_entry, uint32_t* group_count,
+        uint32_t* group_off) {
+    if (!c) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    if (!B || (n && !msg_idx) || !set_pos || !set_status || !pos_lo || !pos_hi || !group_head || !group_entry || !group_count || !group_off) ARGFAIL(c, "null buffer");
+    if (n > 0xFFFFFFFEull || B > 0xFFFFFFFEull || table_size > 0xFFFFFFFFull) ARGFAIL(c, "set and batch indices are 32-bit");
+    if (!boff && (uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t nn = n ? n : 1;
+    sbuf dmi(c, 7), dbo(c, 5), dmap(c, 9), darr(c, 8), dgc(c, 4);
+    HIPCHK(c, dmi.up(msg_idx, 4 * n)); if (!n) HIPCHK(c, dmi.alloc(4));
+    if (boff) { HIPCHK(c, dbo.up(boff, 4 * (B + 1))); HIPCHK(c, dmap.alloc(4 * nn)); }
+    HIPCHK(c, darr.alloc(4 * 6 * nn)); HIPCHK(c, dgc.alloc(4 * (2 * B + 1)));
+    hipStream_t s = c->hs_a;
+    uint32_t* const a = darr.as<uint32_t>();
+    mbls_vbg_arrays ga = {a, a + nn, a + 2 * nn, a + 3 * nn, a + 4 * nn, dgc.as<uint32_t>(), dgc.as<uint32_t>() + B};
+    uint32_t* const st = a + 5 * nn;
+    uint32_t* const map = boff ? dmap.as<uint32_t>() : nullptr;
+    HIPCHK(c, hipMemsetAsync(a, 0xFF, 4 * 5 * nn, s)); HIPCHK(c, hipMemsetAsync(st, 0, 4 * nn, s)); HIPCHK(c, hipMemsetAsync(ga.gcount, 0, 4 * (2 * B + 1), s));
+    if (map) {
+        HIPCHK(c, hipMemsetAsync(map, 0xFF, 4 * nn, s));
+        if (n) hipLaunchKernelGGL(k_vmb_set_map, dim3(nblk(B)), dim3(WG), 0, s, (const uint32_t*)dbo.as<uint32_t>(), B, n, map);
+    }
+    mbls_vbg_launch_group(dmi.as<uint32_t>(), table_size, boff ? (const uint32_t*)dbo.as<uint32_t>() : nullptr, spb, B, n, (const uint32_t*)map, ga, st, s);
+    hipLaunchKernelGGL(k_vms_scan, dim3(1), dim3(MBLS_VMS_SCAN_LANES), 0, s, (const uint32_t*)ga.gcount, B, ga.goff);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    uint32_t* const outs[6] = {set_pos, pos_lo, pos_hi, group_head, group_entry, set_status};
+    for (int u = 0; u < 6 && n; u++) HIPCHK(c, hipMemcpy(outs[u], a + (uint64_t)u * nn, 4 * n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(group_count, ga.gcount, 4 * B, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(group_off, ga.goff, 4 * (B + 1), hipMemcpyDeviceToHost));
+    return MBLS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ several GPUs behind one handle
