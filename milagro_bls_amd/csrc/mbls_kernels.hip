@@ -28,6 +28,8 @@
 #include "mbls_vmt.h"
 #include "mbls_mtb.h"
 #include "mbls_batch.h"
+#include "mbls_vmd.h"
+#include "mbls_vmr.h"
 #include "mbls_cmt_lanes.h"
 #include "mbls_cms_launch.h"
 #include "mbls_vcs_launch.h"
@@ -3927,121 +3929,107 @@ extern "C" int mbls_aggregate_verify_batch(mbls_ctx* c, const uint8_t* sigs, con
     if (status) HIPCHK(c, dst.down(status, 4 * n));
     return MBLS_OK;
 }
-// the message list of mbls_verify_multiple*_shared_msgs: d_msgs / msg_len / d_moff then describe the n_msgs LISTED messages, set i's is message d_midx[i]
+// what a call over a message list (mbls_verify_multiple*_shared_msgs: the description's ms then describes the n_msgs LISTED messages, set i's is message d_idx[i])
+// or over a resident table (the _msgtable entries: d_idx holds TABLE indices) derives under the context's lock -- vm_shared_plan_and_reserve sets every field
 struct vm_shared {
-    uint64_t n_msgs = 0; const uint32_t* d_midx = nullptr;
-    uint64_t longest = 0;              // the longest group where the host has counted it (host entries); 0: a device-side index table
     mbls_shared_msgs_plan sp;          // the list hash (plan_shared)
     mbls_vm_shared_msgs_plan vp;       // the route (plan_vm_shared)
-    // the _locate entries: the sets' answers as well (d_set_results required, d_set_status optional), shadow items behind phase one's workspace (mbls_vsl.h)
-    bool locate = false; uint8_t* d_set_results = nullptr; uint32_t* d_set_status = nullptr;
-    uint64_t shadow_first = 0;         // (set by vm_shared_plan_and_reserve)
-    // the span key source under a split (mbls_vcs.h): workspace items behind what the call plans today; base_items (set by vm_shared_plan_and_reserve): that figure
+    uint64_t shadow_first = 0;         // the _locate entries: the first shadow item, behind phase one's workspace (mbls_vsl.h)
+    // the span key source under a split (mbls_vcs.h): workspace items behind what the call plans today (set by the caller); base_items: that figure
     uint64_t extra_items = 0, base_items = 0;
-    // the _msgtable entries: a resident table in place of the list (n_msgs stays 0; d_midx holds TABLE indices). named: the distinct entries the sets name where the
-    // host has counted them (0: not known). Set by vm_shared_plan_and_reserve from the table as it is then: T, the bound on the named entries (mbls_vmt.h), its buffers.
-    const mbls_msgtable* mt = nullptr; uint64_t named = 0;
+    // what the grouping runs over (T) and what sizes the Miller phase (bound): the list both times, or the table as it is then and the bound on the named entries
+    // (mbls_vmt.h); the table's buffers
     uint64_t T = 0, bound = 0; const uint32_t* tab = nullptr; uint64_t tstride = 0; const uint32_t* flags = nullptr;
-    // what the grouping runs over and what sizes the Miller phase: the list both times, or the table and the bound
-    uint64_t groups() const { return mt ? T : n_msgs; }
-    uint64_t sized_by() const { return mt ? bound : n_msgs; }
 };
 // the message phase of the shared-message entries on stream s_msg: the list is hashed once into the context's table (the existing path of section 5d); the
 // per-set route then gives every set its point (k_h_gather), the grouped route reads the table from its Miller items (k_vms_heads)
-static int vm_shared_message_phase(mbls_ctx* c, mbls_ws ws, const vm_shared& sh, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n, hipStream_t s_msg) {
-    if (sh.mt) {        // a resident table: nothing to hash; the per-set route gathers straight from it (the grouped route reads it from its Miller items, k_vmt_heads)
+static int vm_shared_message_phase(mbls_ctx* c, mbls_ws ws, const vm_call& d, const vm_shared& sh, hipStream_t s_msg) {
+    const uint64_t n = d.n;
+    if (d.mt) {        // a resident table: nothing to hash; the per-set route gathers straight from it (the grouped route reads it from its Miller items, k_vmt_heads)
         if (sh.vp.route == MBLS_VM_ROUTE_PER_SET)
-            hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, sh.tab, sh.tstride, sh.flags, sh.d_midx, sh.T, c->d_status, n);
+            hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, sh.tab, sh.tstride, sh.flags, d.ms.d_idx, sh.T, c->d_status, n);
         return MBLS_OK;
     }
-    const int rc = shared_hash_list(c, sh.sp, d_msgs, msg_len, d_moff, sh.n_msgs, s_msg); if (rc) return rc;
+    const int rc = shared_hash_list(c, sh.sp, d.ms.d_msgs, d.ms.msg_len, d.ms.d_moff, d.ms.n_msgs, s_msg); if (rc) return rc;
     if (sh.vp.route == MBLS_VM_ROUTE_PER_SET)
         hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, (const uint32_t*)c->d_htab, c->htab_cap,
-                           (const uint32_t*)c->d_hflag, sh.d_midx, sh.n_msgs, c->d_status, n);
+                           (const uint32_t*)c->d_hflag, d.ms.d_idx, d.ms.n_msgs, c->d_status, n);
     return MBLS_OK;
 }
-static int vm_shared_plan_and_reserve(mbls_ctx* c, vm_shared& sh, uint64_t n) {
-    if (sh.mt) {        // the table at the size it has now (the caller holds the context's lock); only the group arrays are reserved beside the workspace
-        if (sh.mt->c != c) ARGFAIL(c, "message table belongs to another context");
-        sh.T = sh.mt->size; sh.bound = vmt_bound(n, sh.T, sh.named);
-        sh.tab = sh.mt->d_tab; sh.tstride = mtb_stride(sh.mt->cap); sh.flags = sh.mt->d_flag;
+static int vm_shared_plan_and_reserve(mbls_ctx* c, const vm_call& d, vm_shared& sh) {
+    const uint64_t n = d.n;
+    if (d.mt) {        // the table at the size it has now (the caller holds the context's lock); only the group arrays are reserved beside the workspace
+        if (d.mt->c != c) ARGFAIL(c, "message table belongs to another context");
+        sh.T = d.mt->size; sh.bound = vmt_bound(n, sh.T, d.named);
+        sh.tab = d.mt->d_tab; sh.tstride = mtb_stride(d.mt->cap); sh.flags = d.mt->d_flag;
         memset(&sh.sp, 0, sizeof(sh.sp));
-        plan_vm_msgtable(ctx_limits(c), n, sh.T, sh.named, c->vm_grouping, sh.longest, &sh.vp);
+        plan_vm_msgtable(ctx_limits(c), n, sh.T, d.named, c->vm_grouping, d.longest, &sh.vp);
         const bool grouped = sh.vp.route == MBLS_VM_ROUTE_GROUPED;
         sh.shadow_first = vsl_shadow_first(n, sh.bound, grouped, 0);
-        sh.base_items = sh.locate ? vsl_workspace_items(n, sh.bound, grouped, 0) : sh.vp.workspace_items;
+        sh.base_items = d.locate ? vsl_workspace_items(n, sh.bound, grouped, 0) : sh.vp.workspace_items;
         const int rc = mbls_ctx_reserve(c, sh.base_items + sh.extra_items); if (rc) return rc;
         return reserve_groups(c, sh.T);
     }
-    plan_shared(ctx_limits(c), n, sh.n_msgs, false, false, &sh.sp);
-    plan_vm_shared(ctx_limits(c), n, sh.n_msgs, c->vm_grouping, sh.longest, &sh.vp);
+    sh.T = sh.bound = d.ms.n_msgs;
+    plan_shared(ctx_limits(c), n, d.ms.n_msgs, false, false, &sh.sp);
+    plan_vm_shared(ctx_limits(c), n, d.ms.n_msgs, c->vm_grouping, d.longest, &sh.vp);
     const bool grouped = sh.vp.route == MBLS_VM_ROUTE_GROUPED;
-    sh.shadow_first = vsl_shadow_first(n, sh.n_msgs, grouped, sh.sp.list_workspace_items);
-    int rc = mbls_ctx_reserve(c, sh.locate ? vsl_workspace_items(n, sh.n_msgs, grouped, sh.sp.list_workspace_items) : sh.vp.workspace_items); if (rc) return rc;
-    return reserve_msgs(c, sh.n_msgs);
+    sh.shadow_first = vsl_shadow_first(n, d.ms.n_msgs, grouped, sh.sp.list_workspace_items);
+    int rc = mbls_ctx_reserve(c, d.locate ? vsl_workspace_items(n, d.ms.n_msgs, grouped, sh.sp.list_workspace_items) : sh.vp.workspace_items); if (rc) return rc;
+    return reserve_msgs(c, d.ms.n_msgs);
 }
-// the key source of mbls_verify_multiple_committee_msgtable*: one descriptor word and one bitfield per set (mbls_vmc.h) over a committee table, read at the sizes
-// vm_committee_of found under the context's lock
-struct vm_committee {
-    const mbls_committees* t = nullptr; const mbls_keytable* kt = nullptr;
-    const uint32_t* d_cmt_idx = nullptr; const uint8_t* d_bits = nullptr; uint32_t bits_stride = 0;
-    const uint32_t* d_crecs = nullptr; uint64_t ccount = 0; const uint32_t* d_members = nullptr; uint32_t cmax = 0; const uint32_t* d_recs = nullptr; uint64_t tsize = 0;
-    uint64_t list_stride() const { return cmax ? cmax : 1; }
-    // the span form (mbls_vcs.h; d_cmt_idx null): set i names ids d_cmt_ids[d_cmt_off[i] .. d_cmt_off[i + 1]) of n_cmt_ids
-    bool span = false; const uint32_t* d_cmt_ids = nullptr; uint64_t n_cmt_ids = 0; const uint32_t* d_cmt_off = nullptr;
-    uint64_t span_stride() const { return cms_stride(bits_stride, cmax); }
-};
+// the committee key source of mbls_verify_multiple_committee_msgtable* (one descriptor word and one bitfield per set, mbls_vmc.h) and its span form (mbls_vcs.h):
+// the stride of a set's index list, and of a set's region of the span scratch
+static uint64_t keys_list_stride(const keysrc& ks) { return ks.cmax ? ks.cmax : 1; }
+static uint64_t keys_span_stride(const keysrc& ks) { return cms_stride(ks.bits_stride, ks.cmax); }
 // for spans, the split factor of the call's key phase (it sizes the workspace: asked before that is reserved)
-static uint32_t vm_committee_split(const mbls_ctx* c, const vm_committee& vc, uint64_t n) {
+static uint32_t vm_committee_split(const mbls_ctx* c, const keysrc& ks, uint64_t n) {
     const mbls_limits L = ctx_limits(c);
-    return vc.span ? vcs_split(n, vc.span_stride(), &L, c->vm_span_split) : 1u;
+    return ks.span ? vcs_split(n, keys_span_stride(ks), &L, c->vm_span_split) : 1u;
 }
-// the committee entries' checks (keys_of_committees: one context, key table alive, bits_stride, alignment of device bitfields); the caller holds the context's lock
-static int vm_committee_of(mbls_ctx* c, const mbls_committees* t, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride, bool device_bits, vm_committee* vc) {
-    keysrc ks; const int rk = keys_of_committees(c, t, d_cmt_idx, d_bits, bits_stride, device_bits, &ks); if (rk) return rk;
-    vc->t = t; vc->kt = t->kt; vc->d_cmt_idx = d_cmt_idx; vc->d_bits = d_bits; vc->bits_stride = bits_stride;
-    vc->d_crecs = ks.d_crecs; vc->ccount = ks.ccount; vc->d_members = ks.d_members; vc->cmax = ks.cmax; vc->d_recs = ks.d_recs; vc->tsize = ks.tsize;
-    return MBLS_OK;
-}
-// the span form: the span entries' checks (keys_of_committee_span: no bound between bits_stride and the largest committee -- every set's M is checked on its own)
-static int vm_committee_span_of(mbls_ctx* c, const mbls_committees* t, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits,
-                                uint32_t bits_stride, bool device_bits, vm_committee* vc) {
-    keysrc ks; const int rk = keys_of_committee_span(c, t, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, device_bits, &ks); if (rk) return rk;
-    if (ks.ccount > (uint64_t)MBLS_VMC_SINGLE_KEY) ARGFAIL(c, "committee ids have 31 bits beside single-key sets");
-    vc->t = t; vc->kt = t->kt; vc->d_bits = d_bits; vc->bits_stride = bits_stride;
-    vc->d_crecs = ks.d_crecs; vc->ccount = ks.ccount; vc->d_members = ks.d_members; vc->cmax = ks.cmax; vc->d_recs = ks.d_recs; vc->tsize = ks.tsize;
-    vc->span = true; vc->d_cmt_ids = d_cmt_ids; vc->n_cmt_ids = n_cmt_ids; vc->d_cmt_off = d_cmt_off;
+// The key source of an entry that named its handle alone (keys_in_table, keys_in_committees, keys_in_committee_span), read at the sizes the handle has now (the
+// caller holds the context's lock) with the checks of keys_of_table / keys_of_committees (one context, key table alive, bits_stride, alignment of device
+// bitfields) / keys_of_committee_span (no bound between bits_stride and the largest committee -- every set's M is checked on its own)
+static int vm_keys_resolve(mbls_ctx* c, keysrc* ks, bool device_bits) {
+    if (ks->span) {
+        const int rk = keys_of_committee_span(c, ks->cmt, ks->d_cmt_ids, ks->n_cmt_ids, ks->d_cmt_span_off, ks->d_bits, ks->bits_stride, device_bits, ks); if (rk) return rk;
+        if (ks->ccount > (uint64_t)MBLS_VMC_SINGLE_KEY) ARGFAIL(c, "committee ids have 31 bits beside single-key sets");
+        return MBLS_OK;
+    }
+    if (ks->committee) return keys_of_committees(c, ks->cmt, ks->d_cmt_idx, ks->d_bits, ks->bits_stride, device_bits, ks);
+    if (ks->indexed) return keys_of_table(c, ks->tab, ks->d_idx, ks->d_off, ks);
     return MBLS_OK;
 }
 // the host entries' statement of "malformed" (what k_vcs_expand rejects per set refuses the whole call here), and a single-key index that names no key
-static int vm_committee_span_sets_ok(mbls_ctx* c, const host_committees& hc, const vm_committee& vc, uint64_t n) {
+static int vm_committee_span_sets_ok(mbls_ctx* c, const host_committees& hc, const keysrc& ks, uint64_t n) {
     if (!hc.cmt_off || (hc.n_cmt_ids && !hc.cmt_ids) || (hc.bits_stride && !hc.bits)) ARGFAIL(c, "null buffer");
     for (uint64_t i = 0; i < n; i++) {
         uint32_t q = 0;
         if (!cms_range_ok(hc.cmt_off[i], hc.cmt_off[i + 1], hc.n_cmt_ids, &q)) ARGFAIL(c, "cmt_off must be non-decreasing, inside cmt_ids, at most MBLS_SPAN_MAX_COMMITTEES ids per set");
         const uint32_t* ids = hc.cmt_ids + hc.cmt_off[i];
         if (q == 1u && vcs_is_single(q, ids[0])) {
-            if (vcs_single_names_nothing(ids[0], vc.tsize)) ARGFAIL(c, "cmt_ids names no key of the key table");
+            if (vcs_single_names_nothing(ids[0], ks.tsize)) ARGFAIL(c, "cmt_ids names no key of the key table");
             continue;
         }
         uint64_t M = 0;
         for (uint32_t u = 0; u < q; u++) {
-            if (!vcs_id_ok(ids[u], vc.ccount)) ARGFAIL(c, "cmt_ids names no committee of the table");
+            if (!vcs_id_ok(ids[u], ks.ccount)) ARGFAIL(c, "cmt_ids names no committee of the table");
             M += hc.t->sizes[ids[u]];
         }
         if (!cms_field_ok(M, hc.bits_stride)) ARGFAIL(c, "bits_stride does not cover a set's committees");
     }
     return MBLS_OK;
 }
-static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_pks, int pk_format,
-        const uint32_t* d_pk_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n,
-        uint8_t* d_result, uint32_t* d_status_or, void* stream, uint32_t* d_partial = nullptr, const mbls_keytable* tab = nullptr, const uint32_t* d_idx = nullptr,
-        bool sigs_resident = false, bool hash_enqueued = false, vm_shared* sh = nullptr, const vm_committee* vc = nullptr) {
-    // vc (the _committee_msgtable entries: sh names a resident message table): the third key source beside tab / d_apks / d_pks, which are then null
-    // sigs_resident: k_sig (decode + subgroup test) has run over these signatures on this workspace and the host has seen every one pass: d_sigs is not read.
-    // hash_enqueued (batches whose chains run side by side only): the message phase is already on the context's message stream.
-    if (!c || (!d_result && !d_partial)) return MBLS_ERR_ARGUMENT;
+static int verify_multiple_impl(mbls_ctx* c, const vm_call& d, void* stream) {
+    // the key source is one of five (vm_key_kind); the committee kinds run over a resident message table only
+    // d.sigs_resident: k_sig (decode + subgroup test) has run over these signatures on this workspace and the host has seen every one pass: d.d_sigs is not read.
+    // d.hash_enqueued (batches whose chains run side by side only): the message phase is already on the context's message stream.
+    if (!c || (!d.d_result && !d.d_partial)) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
+    const uint64_t n = d.n; const keysrc& ks = d.ks; const int keys = vm_key_kind(d);
+    const bool committee = keys == VM_KEYS_SPAN || keys == VM_KEYS_COMMITTEE, shared = d.ms.indexed();
+    uint8_t* const d_result = d.d_result; uint32_t* const d_partial = d.d_partial; const uint64_t* const d_rands = d.d_rands;
+    vm_shared sh;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(c, hipSetDevice(c->device));
     if (n == 0 && d_partial) {     // an empty shard contributes (1, infinity, no status bits)
@@ -4052,44 +4040,44 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
     }
     if (n == 0) {     // empty iterator: S' = infinity, product of no pairings = 1 -> e(inf, -G1) = 1 -> true
         HIPCHK(c, hipMemsetAsync(d_result, 1, 1, s));
-        if (d_status_or) HIPCHK(c, hipMemsetAsync(d_status_or, 0, 4, s));
+        if (d.d_status_or) HIPCHK(c, hipMemsetAsync(d.d_status_or, 0, 4, s));
         return MBLS_OK;
     }
     if (!d_rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
-    if ((!d_sigs && !sigs_resident) || (!d_msgs && msg_len && !d_moff && !(sh && !sh->n_msgs))) ARGFAIL(c, "null buffer");
-    if (sh && sh->mt && d_partial) ARGFAIL(c, "the shard form takes per-set messages only");
+    if ((!d.d_sigs && !d.sigs_resident) || (!d.ms.d_msgs && d.ms.msg_len && !d.ms.d_moff && !(shared && !d.ms.n_msgs))) ARGFAIL(c, "null buffer");
+    if (d.mt && d_partial) ARGFAIL(c, "the shard form takes per-set messages only");
     // batches of at most half a round: two lanes per message in the message phase (items [0, 2 n), slots no other chain touches)
-    const bool pair_hash = !sh && n <= c->split_max_items && 2 * n <= c->round_items;
+    const bool pair_hash = !shared && n <= c->split_max_items && 2 * n <= c->round_items;
     // a shared list: the workspace (sets, Miller items, positions, the list's own hash) and the table are reserved here, once, before the first kernel
     // the span form of the committee source under a split: the partial sums' workspace items behind the call's own (mbls_vcs.h)
-    const uint32_t span_split = vc && sh ? vm_committee_split(c, *vc, n) : 1u;
-    if (vc && sh) sh->extra_items = vcs_extra_items(n, span_split);
-    int rc = sh ? vm_shared_plan_and_reserve(c, *sh, n) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
+    const uint32_t span_split = committee && shared ? vm_committee_split(c, ks, n) : 1u;
+    if (committee && shared) sh.extra_items = vcs_extra_items(n, span_split);
+    int rc = shared ? vm_shared_plan_and_reserve(c, d, sh) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
     // the committee source: the sets' index lists, count and route words for all n sets (spans: their regions, records and parked points), reserved here with the
     // workspace (grow-only: nothing when mbls_ctx_reserve_committee[_span]_items or the first half of an _rng call has been there)
-    if (vc) {
-        if (!(sh && sh->mt) || d_partial) ARGFAIL(c, "internal: the committee source runs over a resident message table only");
-        rc = vc->span ? reserve_committee_span(c, n, vc->span_stride()) : reserve_committee(c, n, vc->cmax); if (rc) return rc;
+    if (committee) {
+        if (!d.mt || d_partial) ARGFAIL(c, "internal: the committee source runs over a resident message table only");
+        rc = ks.span ? reserve_committee_span(c, n, keys_span_stride(ks)) : reserve_committee(c, n, ks.cmax); if (rc) return rc;
     }
-    const bool grouped = sh && sh->vp.route == MBLS_VM_ROUTE_GROUPED;
-    const uint64_t n_miller = grouped ? sh->vp.miller_items : n;
-    const bool loc = sh && sh->locate;
-    const uint64_t shf = loc ? sh->shadow_first : 0;                // locate mode: the first shadow item; the candidate flags (cap >= 2 n words)
+    const bool grouped = shared && sh.vp.route == MBLS_VM_ROUTE_GROUPED;
+    const uint64_t n_miller = grouped ? sh.vp.miller_items : n;
+    const bool loc = shared && d.locate;
+    const uint64_t shf = loc ? sh.shadow_first : 0;                // locate mode: the first shadow item; the candidate flags (cap >= 2 n words)
     uint32_t* const cand = c->d_status + vsl_flags_first(n);
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     rc = ws_acquire(c, s); if (rc) return rc;
     // a resident message table: its last append and the key table's are awaited on the caller's stream HERE, before anything is enqueued on a side stream -- every
     // stream of the call forks from s behind them, and no fallible step is left once a side stream has work
-    const bool over_table = sh && sh->mt;
-    if (over_table) { rc = msgtable_acquire(c, sh->mt, s); if (rc) return rc; if (tab) { rc = table_acquire(c, tab, s); if (rc) return rc; } }
-    if (vc) { rc = committees_acquire(c, vc->t, s); if (rc) return rc; rc = table_acquire(c, vc->kt, s); if (rc) return rc; }
+    const bool over_table = d.mt != nullptr;
+    if (over_table) { rc = msgtable_acquire(c, d.mt, s); if (rc) return rc; if (keys == VM_KEYS_TABLE) { rc = table_acquire(c, ks.tab, s); if (rc) return rc; } }
+    if (committee) { rc = committees_acquire(c, ks.cmt, s); if (rc) return rc; rc = table_acquire(c, ks.tab, s); if (rc) return rc; }
     if (loc) {
-        HIPCHK(c, hipMemsetAsync(sh->d_set_results, 0, n, s));      // fail closed
-        if (sh->d_set_status) HIPCHK(c, hipMemsetAsync(sh->d_set_status, 0, 4 * n, s));
+        HIPCHK(c, hipMemsetAsync(d.d_set_results, 0, n, s));      // fail closed
+        if (d.d_set_status) HIPCHK(c, hipMemsetAsync(d.d_set_status, 0, 4 * n, s));
         HIPCHK(c, hipMemsetAsync(cand, 0, 4 * n, s));
     }
     HIPCHK(c, hipMemsetAsync(c->d_scalar, 0, 64, s));
-    if (!sigs_resident) HIPCHK(c, hipMemsetAsync(c->d_status, 0, 4 * n, s));      // (resident: cleared before k_sig, and the message phase may be writing its bits)
+    if (!d.sigs_resident) HIPCHK(c, hipMemsetAsync(c->d_status, 0, 4 * n, s));      // (resident: cleared before k_sig, and the message phase may be writing its bits)
     if (d_partial) HIPCHK(c, hipMemsetAsync(d_partial, 0, MBLS_VM_PARTIAL_BYTES, s));       // not a record until k_vm_export has spoken
     else HIPCHK(c, hipMemsetAsync(d_result, 0, 1, s));                      // false until the tail kernel has spoken (fail closed)
     // Three independent chains: keys (aggregate, [r]apk), signatures (decode, subgroup check, [r]sig, sum tree), messages (hash). Below
@@ -4101,51 +4089,51 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
     if (fork) { HIPCHK(c, hipEventRecord(c->hs_ev, s)); HIPCHK(c, hipStreamWaitEvent(s_sig, c->hs_ev, 0)); HIPCHK(c, hipStreamWaitEvent(s_msg, c->hs_ev, 0)); }
     // side by side, the message phase is the chain the sets' Miller loops wait for: it is ENQUEUED first (behind the ~20 launches of the signature chain's sum tree
     // it started 0.26 ms late: 2^14 sets 9.47 -> 9.2 ms)
-    const bool hash_first = fork && !hash_enqueued;
+    const bool hash_first = fork && !d.hash_enqueued;
     auto message_phase = [&]() -> int {
-        if (sh) return vm_shared_message_phase(c, ws, *sh, d_msgs, msg_len, d_moff, n, s_msg);
-        launch_hash(c, ws, d_msgs, msg_len, d_moff, c->d_status, n, s_msg, pair_hash); return MBLS_OK;
+        if (shared) return vm_shared_message_phase(c, ws, d, sh, s_msg);
+        launch_hash(c, ws, d.ms.d_msgs, d.ms.msg_len, d.ms.d_moff, c->d_status, n, s_msg, pair_hash); return MBLS_OK;
     };
     if (hash_first) { rc = message_phase(); if (rc) return rc; }
-    if (vc && vc->span) {   // sets given by committee span, or by one key index (mbls_vcs.h): every set's two lists and record, then the span key sum -- one lane per
+    if (keys == VM_KEYS_SPAN) {   // sets given by committee span, or by one key index (mbls_vcs.h): every set's two lists and record, then the span key sum -- one lane per
         // set, or under a split one lane per chunk of a list (workspace items and status words behind the call's own and its extra lane) and one combining lane per set
-        const uint64_t ls = vc->span_stride();
-        mbls_vcs_launch_expand(vc->d_crecs, vc->ccount, vc->d_members, vc->d_cmt_ids, vc->n_cmt_ids, vc->d_cmt_off, vc->d_bits, vc->bits_stride, c->cmt_route_mode,
+        const uint64_t ls = keys_span_stride(ks);
+        mbls_vcs_launch_expand(ks.d_crecs, ks.ccount, ks.d_members, ks.d_cmt_ids, ks.n_cmt_ids, ks.d_cmt_span_off, ks.d_bits, ks.bits_stride, c->cmt_route_mode,
                                c->d_cms_list, ls, c->d_cms_rec, n, s);
         if (span_split > 1u)
-            mbls_vcs_launch_split(ws, sh->base_items + 1, span_split, vc->d_recs, vc->tsize, c->d_cms_list, ls, c->d_cms_rec, vc->d_crecs, vc->d_cmt_ids, vc->d_cmt_off,
-                                  c->d_status + sh->base_items + 1, c->d_status, n, s);
+            mbls_vcs_launch_split(ws, sh.base_items + 1, span_split, ks.d_recs, ks.tsize, c->d_cms_list, ls, c->d_cms_rec, ks.d_crecs, ks.d_cmt_ids, ks.d_cmt_span_off,
+                                  c->d_status + sh.base_items + 1, c->d_status, n, s);
         else
-            mbls_vcs_launch_aggregate(ws, vc->d_recs, vc->tsize, c->d_cms_list, ls, c->d_cms_rec, vc->d_crecs, vc->d_cmt_ids, vc->d_cmt_off, c->d_cms_park, c->cms_items,
+            mbls_vcs_launch_aggregate(ws, ks.d_recs, ks.tsize, c->d_cms_list, ls, c->d_cms_rec, ks.d_crecs, ks.d_cmt_ids, ks.d_cmt_span_off, c->d_cms_park, c->cms_items,
                                       c->d_status, n, s);
-    } else if (vc) {       // sets given by committee and bitfield, or by one key index (mbls_vmc.h): every set's list, then the indexed key sum over it with the complement's fix-up
-        const uint64_t ls = vc->list_stride();
+    } else if (keys == VM_KEYS_COMMITTEE) {       // sets given by committee and bitfield, or by one key index (mbls_vmc.h): every set's list, then the indexed key sum over it with the complement's fix-up
+        const uint64_t ls = keys_list_stride(ks);
         uint32_t* const cnt = c->d_cmt_cnt; uint32_t* const route = c->d_cmt_cnt + c->cmt_items;
-        hipLaunchKernelGGL(k_vmc_expand, dim3((unsigned)n), dim3(WG), 0, s, vc->d_crecs, vc->ccount, vc->d_members, vc->d_cmt_idx, vc->d_bits, vc->bits_stride, c->cmt_route_mode,
+        hipLaunchKernelGGL(k_vmc_expand, dim3((unsigned)n), dim3(WG), 0, s, ks.d_crecs, ks.ccount, ks.d_members, ks.d_cmt_idx, ks.d_bits, ks.bits_stride, c->cmt_route_mode,
                            c->d_cmt_list, ls, cnt, route, n);
-        hipLaunchKernelGGL(k_aggregate_vmc_d, dim3(nblk(n)), dim3(WG), 0, s, ws, vc->d_recs, vc->tsize, (const uint32_t*)c->d_cmt_list, ls, (const uint32_t*)cnt, (const uint32_t*)route,
-                           vc->d_crecs, vc->d_cmt_idx, c->d_status, n);
-    } else if (tab) {      // sets given by indices into a resident key table: the indexed key sum (the keys were decoded and validated once)
-        if (!over_table) { rc = table_acquire(c, tab, s); if (rc) return rc; }
-        hipLaunchKernelGGL(k_aggregate_indexed_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)tab->d_recs, tab->size, d_idx, d_pk_offsets, k, MBLS_MODE_VERIFY, c->d_status, n);
-    } else if (!d_apks)    // sets given by their wire-format keys: AggregatePublicKey::aggregate on the device first (src/aggregates.rs:29-39)
-        launch_aggregate(ws, d_pks, d_pk_offsets, k, pk_format, MBLS_MODE_VERIFY, c->d_status, n, s);
-    hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, tab || vc ? (const uint8_t*)nullptr : d_apks, d_rands, c->d_status, n);
+        hipLaunchKernelGGL(k_aggregate_vmc_d, dim3(nblk(n)), dim3(WG), 0, s, ws, ks.d_recs, ks.tsize, (const uint32_t*)c->d_cmt_list, ls, (const uint32_t*)cnt, (const uint32_t*)route,
+                           ks.d_crecs, ks.d_cmt_idx, c->d_status, n);
+    } else if (keys == VM_KEYS_TABLE) {      // sets given by indices into a resident key table: the indexed key sum (the keys were decoded and validated once)
+        if (!over_table) { rc = table_acquire(c, ks.tab, s); if (rc) return rc; }
+        hipLaunchKernelGGL(k_aggregate_indexed_d, dim3(nblk(n)), dim3(WG), 0, s, ws, ks.d_recs, ks.tsize, ks.d_idx, ks.d_off, d.k, MBLS_MODE_VERIFY, c->d_status, n);
+    } else if (keys == VM_KEYS_WIRE)    // sets given by their wire-format keys: AggregatePublicKey::aggregate on the device first (src/aggregates.rs:29-39)
+        launch_aggregate(ws, ks.d_pks, ks.d_off, d.k, ks.fmt, MBLS_MODE_VERIFY, c->d_status, n, s);
+    hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, keys == VM_KEYS_APKS ? d.d_apks : (const uint8_t*)nullptr, d_rands, c->d_status, n);
     // one Miller loop per message: count, scan, scatter and the per-message sums of the blinded keys follow the keys on their stream (beside the list's hash and
     // the signature chain where the chains run side by side); the heads wait for the table further down
-    const uint64_t pbase = grouped ? vms_position_base(n, sh->sized_by()) : 0;
+    const uint64_t pbase = grouped ? vms_position_base(n, sh.bound) : 0;
     uint32_t* const g_cnt = c->d_hgrp; uint32_t* const g_cur = c->d_hgrp + c->hgrp_cap; uint32_t* const g_off = c->d_hgrp + 2 * c->hgrp_cap;
     uint32_t* const g_flag = c->d_hgrp + 3 * c->hgrp_cap; uint32_t* const g_roff = c->d_hgrp + 4 * c->hgrp_cap; uint32_t* const g_named = c->d_hgrp + 5 * c->hgrp_cap;
     if (grouped) {
-        const uint64_t M = sh->groups();
+        const uint64_t M = sh.T;
         HIPCHK(c, hipMemsetAsync(g_cnt, 0, 4 * (M + 1), s)); HIPCHK(c, hipMemsetAsync(g_cur, 0, 4 * (M + 1), s)); HIPCHK(c, hipMemsetAsync(c->d_vmap, 0xFF, 4 * n, s));
-        hipLaunchKernelGGL(k_vms_count, dim3(nblk(n)), dim3(WG), 0, s, sh->d_midx, M, n, g_cnt, c->d_status);
+        hipLaunchKernelGGL(k_vms_count, dim3(nblk(n)), dim3(WG), 0, s, d.ms.d_idx, M, n, g_cnt, c->d_status);
         hipLaunchKernelGGL(k_vms_scan, dim3(1), dim3(MBLS_VMS_SCAN_LANES), 0, s, (const uint32_t*)g_cnt, M, g_off);
         if (loc) hipLaunchKernelGGL(k_vsl_keep_key, dim3(nblk(n)), dim3(WG), 0, s, ws, n, shf);      // [r_i] apk_i -> A(i), before heads and trees run over the sets' items
-        hipLaunchKernelGGL(k_vms_scatter, dim3(nblk(n)), dim3(WG), 0, s, ws, sh->d_midx, M, n, (const uint32_t*)g_off, g_cur, c->d_vmap, pbase);
+        hipLaunchKernelGGL(k_vms_scatter, dim3(nblk(n)), dim3(WG), 0, s, ws, d.ms.d_idx, M, n, (const uint32_t*)g_off, g_cur, c->d_vmap, pbase);
         mbls_ws wp = ws; wp.w += pbase;
         uint64_t half = 1;
-        for (uint32_t l = 0; l < sh->vp.tree_levels; l++, half *= 2)
+        for (uint32_t l = 0; l < sh.vp.tree_levels; l++, half *= 2)
             hipLaunchKernelGGL(k_g1_seg_tree_d, dim3(nblk(n)), dim3(WG), 0, s, wp, (const uint32_t*)c->d_vmap, (const uint32_t*)g_off, M, n, half);
         if (over_table) {       // the entries the call names, in increasing table index; D = g_roff[M] stays on the device (mbls_vmt.h)
             HIPCHK(c, hipMemsetAsync(g_roff, 0, 4 * (M + 1), s));
@@ -4156,12 +4144,12 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
             }
         }
     }
-    const uint32_t* const d_live = grouped && over_table ? g_roff + sh->T : nullptr;      // the Miller items that have a pair at all
+    const uint32_t* const d_live = grouped && over_table ? g_roff + sh.T : nullptr;      // the Miller items that have a pair at all
     // small batches (their Miller loops run one WAVE per pair, see npairing_finish): the signature chain is what the call waits for -- two lanes per signature
     if (2 * n <= c->coop_max_items)
-        hipLaunchKernelGGL(k_blind_sig2_d, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, c->d_status, n);
+        hipLaunchKernelGGL(k_blind_sig2_d, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, d.sigs_resident ? (const uint8_t*)nullptr : d.d_sigs, d_rands, c->d_status, n);
     else
-        hipLaunchKernelGGL(k_blind_sig_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, c->d_status, n);
+        hipLaunchKernelGGL(k_blind_sig_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, d.sigs_resident ? (const uint8_t*)nullptr : d.d_sigs, d_rands, c->d_status, n);
     // locate mode: ([r_i] sig_i, -G1) -> the set's shadow item (grouped: B(i)), before the sum tree runs over slot S
     if (loc) hipLaunchKernelGGL(k_vml_keep_sig, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, n, grouped ? shf + n : shf);
     const bool side_s_chain = !fork && s != c->hs_b;                  // the sum tree waits for the product tree's company (npairing_finish)
@@ -4172,32 +4160,32 @@ static int verify_multiple_impl(mbls_ctx* c, const uint8_t* d_sigs, const uint8_
             coop_run(c, COOP_SMILLER, ws, (uint64_t)0, (uint64_t)1, (uint64_t)0, (uint64_t)1, (uint32_t*)nullptr, (uint8_t*)nullptr, COOP_RES_ITEM, s_sig);
         HIPCHK(c, hipEventRecord(c->hs_ev, s_sig));                  // ... and its Miller value (awaited just before the tail)
     }
-    if (!(hash_enqueued && fork) && !hash_first) { rc = message_phase(); if (rc) return rc; }
+    if (!(d.hash_enqueued && fork) && !hash_first) { rc = message_phase(); if (rc) return rc; }
     if (fork) {      // the sets' Miller loops need the keys (this stream) and the messages; the signature chain is awaited before the tail (hs_ev)
         HIPCHK(c, hipEventRecord(c->hs_ev3, s_msg));
         HIPCHK(c, hipStreamWaitEvent(s, c->hs_ev3, 0));
     } else
         hipLaunchKernelGGL(k_status_or, dim3(nblk(n)), dim3(WG), 0, s, c->d_status, n, c->d_scalar);
     if (grouped && over_table)
-        hipLaunchKernelGGL(k_vmt_heads, dim3((unsigned)((n_miller + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s, ws, sh->tab, sh->tstride, sh->flags, sh->T, (const uint32_t*)g_off,
+        hipLaunchKernelGGL(k_vmt_heads, dim3((unsigned)((n_miller + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s, ws, sh.tab, sh.tstride, sh.flags, sh.T, (const uint32_t*)g_off,
                            (const uint32_t*)g_named, d_live, n_miller, pbase, c->d_scalar);
     else if (grouped)     // the table is complete: every Miller item gets its message's point and its group's key (a bad listed range some set names: the status word)
         hipLaunchKernelGGL(k_vms_heads, dim3((unsigned)((n_miller + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s, ws, (const uint32_t*)c->d_htab, c->htab_cap,
-                           (const uint32_t*)c->d_hflag, (const uint32_t*)g_off, (const uint32_t*)g_cnt, sh->n_msgs, n_miller, pbase, c->d_scalar);
+                           (const uint32_t*)c->d_hflag, (const uint32_t*)g_off, (const uint32_t*)g_cnt, d.ms.n_msgs, n_miller, pbase, c->d_scalar);
     // a set whose signature is outside G2 (reference src/aggregates.rs:274-276), an undecodable member or a zero scalar makes the tail
     // answer false: the status bits are folded in on the device, the call only enqueues
     rc = npairing_finish(c, n_miller, s, d_result, fork ? c->hs_ev : nullptr, fork, d_partial, side_s_chain, n, loc && !grouped ? shf : 0, d_live); if (rc) return rc;
-    if (d_status_or) HIPCHK(c, hipMemcpyAsync(d_status_or, c->d_scalar, 4, hipMemcpyDeviceToDevice, s));
+    if (d.d_status_or) HIPCHK(c, hipMemcpyAsync(d.d_status_or, c->d_scalar, 4, hipMemcpyDeviceToDevice, s));
     if (loc && grouped) {      // phase two, enqueued whatever the verdict is: mark through msg_idx (candidates get their H), both pairs' Miller loops, product, final
         mbls_ws wsa = ws; wsa.w += shf;
-        hipLaunchKernelGGL(k_vsl_mark, dim3(nblk(n)), dim3(WG), 0, s, wsa, over_table ? sh->tab : (const uint32_t*)c->d_htab, over_table ? sh->tstride : c->htab_cap,
-                           over_table ? sh->flags : (const uint32_t*)c->d_hflag, sh->d_midx, sh->groups(), n, (const uint32_t*)c->d_status, (const uint8_t*)d_result, cand, sh->d_set_results, sh->d_set_status);
-        vsl_examine(c, ws, n, shf, true, c->d_status, cand, sh->d_set_results, sh->d_set_status, s);
+        hipLaunchKernelGGL(k_vsl_mark, dim3(nblk(n)), dim3(WG), 0, s, wsa, over_table ? sh.tab : (const uint32_t*)c->d_htab, over_table ? sh.tstride : c->htab_cap,
+                           over_table ? sh.flags : (const uint32_t*)c->d_hflag, d.ms.d_idx, sh.T, n, (const uint32_t*)c->d_status, (const uint8_t*)d_result, cand, d.d_set_results, d.d_set_status);
+        vsl_examine(c, ws, n, shf, true, c->d_status, cand, d.d_set_results, d.d_set_status, s);
         HIPCHK(c, hipGetLastError());
     } else if (loc) {          // the per-set route: the scheme of mbls_verify_multiple_batches_locate* with the call as the one batch that owns every set
         hipLaunchKernelGGL(k_vml_mark, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)n, (uint64_t)1, n,
-                           (const uint32_t*)c->d_status, (const uint32_t*)nullptr, (const uint8_t*)d_result, cand, sh->d_set_results, sh->d_set_status, shf);
-        vsl_examine(c, ws, n, shf, false, c->d_status, cand, sh->d_set_results, sh->d_set_status, s);
+                           (const uint32_t*)c->d_status, (const uint32_t*)nullptr, (const uint8_t*)d_result, cand, d.d_set_results, d.d_set_status, shf);
+        vsl_examine(c, ws, n, shf, false, c->d_status, cand, d.d_set_results, d.d_set_status, s);
         HIPCHK(c, hipGetLastError());
     }
     return ws_release(c, s);
@@ -4210,12 +4198,10 @@ extern "C" int mbls_verify_multiple_sets_indexed_device(mbls_ctx* c, const mbls_
     if (!c || !t || (!d_result && !d_partial)) return MBLS_ERR_ARGUMENT;
     if (n && !d_key_idx) return MBLS_ERR_ARGUMENT;
     if (((uintptr_t)d_partial) & 3) return MBLS_ERR_ARGUMENT;
-    {
-        mbls_lock lk(c->mu);
-        if (t->c != c) ARGFAIL(c, "key table belongs to another context");
-    }
-    return verify_multiple_impl(c, d_sigs, nullptr, nullptr, MBLS_PK_UNCOMPRESSED, d_offsets, k, d_msgs, msg_len, d_moff, d_rands, n, d_partial ? nullptr : d_result,
-                                d_partial ? nullptr : d_status_or, stream, (uint32_t*)d_partial, t, d_key_idx);
+    mbls_lock lk(c->mu);
+    keysrc ks; const int rk = keys_of_table(c, t, d_key_idx, d_offsets, &ks); if (rk) return rk;
+    const vm_call d = vm_sets(d_sigs, d_rands, n).keys(ks, k).msgs(msgs_per_item(d_msgs, msg_len, d_moff));
+    return verify_multiple_impl(c, d_partial ? d.out_partial((uint32_t*)d_partial) : d.out(d_result, d_status_or), stream);
 }
 // One shard of a verify_multiple that is spread over several devices or processes: everything up to the shard's
 // Miller product and signature sum, left as one MBLS_VM_PARTIAL_BYTES record in device memory. Enqueues only.
@@ -4226,8 +4212,8 @@ extern "C" int mbls_verify_multiple_partial_device(mbls_ctx* c, const uint8_t* d
     if (n && !d_apks && !d_pks) return MBLS_ERR_ARGUMENT;
     if (!d_apks && pk_format != MBLS_PK_COMPRESSED && pk_format != MBLS_PK_UNCOMPRESSED) return MBLS_ERR_ARGUMENT;
     if (((uintptr_t)d_partial) & 3) return MBLS_ERR_ARGUMENT;
-    return verify_multiple_impl(c, d_sigs, d_apks, d_apks ? nullptr : d_pks, pk_format, d_apks ? nullptr : d_pk_offsets, k, d_msgs, msg_len, d_moff, d_rands, n,
-                                nullptr, nullptr, stream, (uint32_t*)d_partial);
+    const vm_call d = vm_sets(d_sigs, d_rands, n).msgs(msgs_per_item(d_msgs, msg_len, d_moff)).out_partial((uint32_t*)d_partial);
+    return verify_multiple_impl(c, d_apks ? d.keys_apks(d_apks) : d.keys(keys_wire(d_pks, pk_format, d_pk_offsets), k), stream);
 }
 // The exchange step's second half: G records (the shards' in any fixed order -- every participant that uses the same order computes the same
 // bool) -> product and sum trees over the records, then the tail of the one-device check: the Miller loop of (S, -G1), the product, ONE final
@@ -4260,7 +4246,7 @@ extern "C" int mbls_verify_multiple_aggregate_signatures_device(mbls_ctx* c, con
         uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status_or, void* stream) {
     if (!c) return MBLS_ERR_ARGUMENT;
     if (n && !d_apks) return MBLS_ERR_ARGUMENT;
-    return verify_multiple_impl(c, d_sigs, d_apks, nullptr, 0, nullptr, 0, d_msgs, msg_len, d_moff, d_rands, n, d_result, d_status_or, stream);
+    return verify_multiple_impl(c, vm_sets(d_sigs, d_rands, n).keys_apks(d_apks).msgs(msgs_per_item(d_msgs, msg_len, d_moff)).out(d_result, d_status_or), stream);
 }
 extern "C" int mbls_verify_multiple_sets_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_pks, int pk_format, const uint32_t* d_pk_offsets,
         uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n, uint8_t* d_result,
@@ -4268,7 +4254,8 @@ extern "C" int mbls_verify_multiple_sets_device(mbls_ctx* c, const uint8_t* d_si
     if (!c) return MBLS_ERR_ARGUMENT;
     if (pk_format != MBLS_PK_COMPRESSED && pk_format != MBLS_PK_UNCOMPRESSED) return MBLS_ERR_ARGUMENT;
     if (n && !d_pks) return MBLS_ERR_ARGUMENT;
-    return verify_multiple_impl(c, d_sigs, nullptr, d_pks, pk_format, d_pk_offsets, k, d_msgs, msg_len, d_moff, d_rands, n, d_result, d_status_or, stream);
+    return verify_multiple_impl(c, vm_sets(d_sigs, d_rands, n).keys(keys_wire(d_pks, pk_format, d_pk_offsets), k).msgs(msgs_per_item(d_msgs, msg_len, d_moff))
+                                       .out(d_result, d_status_or), stream);
 }
 extern "C" int mbls_verify_multiple_aggregate_signatures(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs,
         uint32_t msg_len, const uint64_t* moff, const uint64_t* rands, size_t n) {
@@ -4305,55 +4292,65 @@ struct vm_rng_stage {
     vm_rng_stage(mbls_ctx* c) : ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dmo(c, 6), dout(c, 4), dmi(c, 7), dci(c, 10), dso(c, 5) {}
 };
 static void vm_rng_drain(mbls_ctx* c) { (void)hipStreamSynchronize(c->hs_a); (void)hipStreamSynchronize(c->hs_b); (void)hipStreamSynchronize(c->hs_c); c->ws_pending = false; }
-// sigs96 / apks96: the shard's own sets; msgs: the buffer the (absolute) offsets of moff[0 .. n] point into, or n x msg_len bytes. -> MBLS_OK and st[0 .. n) (status words)
-// sh (the shared-message form): msgs / moff describe the sh->n_msgs LISTED messages, msg_idx the sets' indices (uploaded here; sh->d_midx is set)
-// hc / vc (the committee form): apks96 is null; the sets' words and bitfields are uploaded here (vc's device pointers are set) and the list scratch of the whole call
-// is reserved with the workspace
-static int vm_rng_phase1(mbls_ctx* c, vm_rng_stage& g, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, size_t n,
-                         size_t out_bytes, uint32_t* st, vm_shared* sh = nullptr, const uint32_t* msg_idx = nullptr, const host_committees* hc = nullptr,
-                         vm_committee* vc = nullptr) {
+// the signature half of an _rng call on stream s (fork: on the context's signature stream, with the message stream forked beside it): the sets' status words
+// cleared, the signatures decoded and tested -- they stay in the workspace; the verdicts are complete on that stream
+static int vm_rng_signatures(mbls_ctx* c, mbls_ws ws, const uint8_t* d_sigs, uint64_t n, hipStream_t s, bool fork) {
+    hipStream_t s_sig = fork ? c->hs_b : s;
+    if (hipMemsetAsync(c->d_status, 0, 4 * n, s) != hipSuccess) return MBLS_ERR_DEVICE;
+    if (fork) { (void)hipEventRecord(c->hs_ev, s); (void)hipStreamWaitEvent(c->hs_b, c->hs_ev, 0); (void)hipStreamWaitEvent(c->hs_c, c->hs_ev, 0); }
+    if (2 * n <= c->coop_max_items) hipLaunchKernelGGL(k_sig2, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, d_sigs, c->d_status, n);
+    else hipLaunchKernelGGL(k_sig, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, d_sigs, c->d_status, n, 1);
+    return MBLS_OK;
+}
+// h: the shard's own sets in host memory; its messages: the buffer the (absolute) offsets of moff[0 .. n] point into, or n x msg_len bytes -- over a list, the
+// n_msgs LISTED messages, and the sets' indices are uploaded here. The committee forms (h.hc; no aggregate keys): the sets' words and bitfields are uploaded here
+// and the list scratch of the whole call is reserved with the workspace. d: the call as its entry resolved it (key source, table, locate outputs); its device
+// pointers are set here. -> MBLS_OK and st[0 .. n) (status words)
+static int vm_rng_phase1(mbls_ctx* c, vm_rng_stage& g, const vm_host& h, size_t out_bytes, uint32_t* st, vm_call* d) {
+    const size_t n = (size_t)h.n; const host_committees* const hc = h.hc; const uint64_t* const moff = h.ms.d_moff;
+    const bool shared = h.ms.indexed();
+    d->n = n;
     if (hipSetDevice(c->device) != hipSuccess) return MBLS_ERR_DEVICE;
     if (g.dout.alloc(out_bytes) != hipSuccess) return MBLS_ERR_DEVICE;
     if (n == 0) return MBLS_OK;
-    const size_t nm = sh ? (size_t)sh->n_msgs : n;                          // messages the buffers describe
+    const size_t nm = shared ? (size_t)h.ms.n_msgs : n;                     // messages the buffers describe
     const uint64_t msg_first = moff ? moff[0] : 0;
-    const size_t msg_total = moff ? (size_t)(moff[nm] - moff[0]) : (size_t)msg_len * nm;
-    if (g.ds.up(sigs96, 96 * n) != hipSuccess || (!hc && g.da.up(apks96, 96 * n) != hipSuccess) || g.dm.up(msgs ? msgs + msg_first : nullptr, msg_total) != hipSuccess ||
-        g.dr.alloc(8 * n) != hipSuccess || (moff && g.dmo.up(moff, 8 * (nm + 1)) != hipSuccess)) return MBLS_ERR_DEVICE;
+    const size_t msg_total = moff ? (size_t)(moff[nm] - moff[0]) : (size_t)h.ms.msg_len * nm;
+    if (g.ds.up(h.sigs96, 96 * n) != hipSuccess || (!hc && g.da.up(h.apks96, 96 * n) != hipSuccess) ||
+        g.dm.up(h.ms.d_msgs ? h.ms.d_msgs + msg_first : nullptr, msg_total) != hipSuccess || g.dr.alloc(8 * n) != hipSuccess ||
+        (moff && g.dmo.up(moff, 8 * (nm + 1)) != hipSuccess)) return MBLS_ERR_DEVICE;
     if (hc && hc->span) {       // the ids take the descriptor words' slot, the span offsets one of their own
         if (g.da.up(hc->bits, (size_t)hc->bits_stride * n) != hipSuccess || g.dci.up(hc->cmt_ids, 4 * hc->n_cmt_ids) != hipSuccess ||
             g.dso.up(hc->cmt_off, 4 * (n + 1)) != hipSuccess) return MBLS_ERR_DEVICE;
-        vc->d_bits = g.da.as<uint8_t>(); vc->d_cmt_ids = g.dci.as<uint32_t>(); vc->d_cmt_off = g.dso.as<uint32_t>();
+        d->ks.d_bits = g.da.as<uint8_t>(); d->ks.d_cmt_ids = g.dci.as<uint32_t>(); d->ks.d_cmt_span_off = g.dso.as<uint32_t>();
     } else if (hc) {
         if (g.da.up(hc->bits, (size_t)hc->bits_stride * n) != hipSuccess || g.dci.up(hc->cmt_idx, 4 * n) != hipSuccess) return MBLS_ERR_DEVICE;
-        vc->d_bits = g.da.as<uint8_t>(); vc->d_cmt_idx = g.dci.as<uint32_t>();
-    }
-    g.d_msgs = g.dm.as<uint8_t>() - msg_first; g.d_moff = moff ? g.dmo.as<uint64_t>() : nullptr;
-    if (sh) { if (g.dmi.up(msg_idx, 4 * n) != hipSuccess) return MBLS_ERR_DEVICE; sh->d_midx = g.dmi.as<uint32_t>(); }
+        d->ks.d_bits = g.da.as<uint8_t>(); d->ks.d_cmt_idx = g.dci.as<uint32_t>();
+    } else d->d_apks = g.da.as<uint8_t>();
+    d->ms = h.ms; d->ms.d_msgs = g.dm.as<uint8_t>() - msg_first; d->ms.d_moff = moff ? g.dmo.as<uint64_t>() : nullptr;
+    if (shared) { if (g.dmi.up(h.ms.d_idx, 4 * n) != hipSuccess) return MBLS_ERR_DEVICE; d->ms.d_idx = g.dmi.as<uint32_t>(); }
     hipStream_t s = c->hs_a;
-    const bool pair_hash = !sh && n <= c->split_max_items && 2 * n <= c->round_items, fork = 2 * n <= c->round_items;       // as verify_multiple_impl decides
-    if (vc && sh) sh->extra_items = vcs_extra_items(n, vm_committee_split(c, *vc, n));      // (the whole call's workspace, as verify_multiple_impl will ask for it)
-    int rc = sh ? vm_shared_plan_and_reserve(c, *sh, n) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
-    if (vc) { rc = vc->span ? reserve_committee_span(c, n, vc->span_stride()) : reserve_committee(c, n, vc->cmax); if (rc) return rc; }
+    const bool pair_hash = !shared && n <= c->split_max_items && 2 * n <= c->round_items, fork = 2 * n <= c->round_items;       // as verify_multiple_impl decides
+    vm_shared sh;
+    if (hc && shared) sh.extra_items = vcs_extra_items(n, vm_committee_split(c, d->ks, n));      // (the whole call's workspace, as verify_multiple_impl will ask for it)
+    int rc = shared ? vm_shared_plan_and_reserve(c, *d, sh) : mbls_ctx_reserve(c, pair_hash ? 2 * n : n); if (rc) return rc;
+    if (hc) { rc = hc->span ? reserve_committee_span(c, n, keys_span_stride(d->ks)) : reserve_committee(c, n, d->ks.cmax); if (rc) return rc; }
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     rc = ws_acquire(c, s); if (rc) return rc;
-    if (sh && sh->mt) { rc = msgtable_acquire(c, sh->mt, s); if (rc) return rc; }      // (before the fork: the message stream inherits the table's last append)
+    if (d->mt) { rc = msgtable_acquire(c, d->mt, s); if (rc) return rc; }      // (before the fork: the message stream inherits the table's last append)
     hipStream_t s_sig = fork ? c->hs_b : s;
-    if (hipMemsetAsync(c->d_status, 0, 4 * n, s) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
-    if (fork) { (void)hipEventRecord(c->hs_ev, s); (void)hipStreamWaitEvent(c->hs_b, c->hs_ev, 0); (void)hipStreamWaitEvent(c->hs_c, c->hs_ev, 0); }
-    if (2 * n <= c->coop_max_items) hipLaunchKernelGGL(k_sig2, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, (const uint8_t*)g.ds.as<uint8_t>(), c->d_status, (uint64_t)n);
-    else hipLaunchKernelGGL(k_sig, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, (const uint8_t*)g.ds.as<uint8_t>(), c->d_status, (uint64_t)n, 1);
-    if (fork && sh) { rc = vm_shared_message_phase(c, ws, *sh, g.d_msgs, msg_len, g.d_moff, n, c->hs_c); if (rc) { vm_rng_drain(c); return rc; } }
-    else if (fork) launch_hash(c, ws, g.d_msgs, msg_len, g.d_moff, c->d_status, n, c->hs_c, pair_hash);       // the message phase does not wait for the host
+    if (vm_rng_signatures(c, ws, g.ds.as<uint8_t>(), n, s, fork)) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
+    if (fork && shared) { rc = vm_shared_message_phase(c, ws, *d, sh, c->hs_c); if (rc) { vm_rng_drain(c); return rc; } }
+    else if (fork) launch_hash(c, ws, d->ms.d_msgs, d->ms.msg_len, d->ms.d_moff, c->d_status, n, c->hs_c, pair_hash);       // the message phase does not wait for the host
     if (hipStreamSynchronize(s_sig) != hipSuccess || hipMemcpy(st, c->d_status, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
     return MBLS_OK;
 }
-// rands[0 .. n): the shard's scalars. d_partial == false: the bool is left in g.dout (1 byte); true: the shard's record (MBLS_VM_PARTIAL_BYTES). Enqueues on hs_a.
-static int vm_rng_phase2(mbls_ctx* c, vm_rng_stage& g, uint32_t msg_len, const uint64_t* rands, size_t n, bool partial, vm_shared* sh = nullptr, const vm_committee* vc = nullptr) {
+// rands[0 .. n): the shard's scalars. partial == false: the bool is left in g.dout (1 byte); true: the shard's record (MBLS_VM_PARTIAL_BYTES). Enqueues on hs_a.
+static int vm_rng_phase2(mbls_ctx* c, vm_rng_stage& g, const uint64_t* rands, bool partial, const vm_call& d) {
     if (hipSetDevice(c->device) != hipSuccess) return MBLS_ERR_DEVICE;
-    if (n && g.dr.up(rands, 8 * n) != hipSuccess) return MBLS_ERR_DEVICE;
-    return verify_multiple_impl(c, nullptr, vc ? nullptr : g.da.as<uint8_t>(), nullptr, 0, nullptr, 0, g.d_msgs, msg_len, g.d_moff, g.dr.as<uint64_t>(), n,
-                                partial ? nullptr : g.dout.as<uint8_t>(), nullptr, c->hs_a, partial ? g.dout.as<uint32_t>() : nullptr, nullptr, nullptr, true, true, sh, vc);
+    if (d.n && g.dr.up(rands, 8 * d.n) != hipSuccess) return MBLS_ERR_DEVICE;
+    const vm_call h = d.second_half(g.dr.as<uint64_t>(), true);
+    return verify_multiple_impl(c, partial ? h.out_partial(g.dout.as<uint32_t>()) : h.out(g.dout.as<uint8_t>(), nullptr), c->hs_a);
 }
 extern "C" int mbls_verify_multiple_aggregate_signatures_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs,
         uint32_t msg_len, const uint64_t* moff, size_t n, mbls_scalar_source draw, void* user) {
@@ -4366,14 +4363,12 @@ extern "C" int mbls_verify_multiple_aggregate_signatures_rng(mbls_ctx* c, const 
     mbls_lock lk(c->mu);
     std::vector<uint64_t> rands; std::vector<uint32_t> st;
     try { rands.resize(n); st.resize(n); } catch (...) { return 0; }
-    vm_rng_stage g(c);
-    if (vm_rng_phase1(c, g, sigs96, apks96, msgs, msg_len, moff, n, 8, st.data())) return 0;
-    size_t reached = n;                                                     // the sets the reference's loop draws a scalar for
-    for (size_t i = 0; i < n; i++)
-        if (st[i] & (MBLS_ST_BAD_SIG_ENCODING | MBLS_ST_SIG_NOT_IN_G2)) { reached = i; break; }
+    vm_rng_stage g(c); vm_call d;
+    if (vm_rng_phase1(c, g, vm_host_sets(sigs96, n).keys_apks(apks96).msgs(msgs_per_item(msgs, msg_len, moff)), 8, st.data(), &d)) return 0;
+    const size_t reached = (size_t)vmr_reach(st.data(), 0, n);              // the sets the reference's loop draws a scalar for
     if (reached) draw(user, rands.data(), (uint64_t)reached);
     if (reached < n) { vm_rng_drain(c); return 0; }                         // :273-275 (only the message phase is left to wait for)
-    const int rc = vm_rng_phase2(c, g, msg_len, rands.data(), n, false);
+    const int rc = vm_rng_phase2(c, g, rands.data(), false, d);
     std::fill(rands.begin(), rands.end(), 0);
     if (rc) { vm_rng_drain(c); return 0; }
     uint8_t r = 0;
@@ -4385,42 +4380,47 @@ extern "C" int mbls_verify_multiple_aggregate_signatures_rng(mbls_ctx* c, const 
 
 // ---- verify_multiple over a shared message list (include/mbls.h, mbls_verify_multiple*_shared_msgs): the entries above with the sets' messages named by index in
 // a list that is hashed once. Grouped route: one Miller loop per message (the kernels of the k_vms_* family, mbls_vms.h); per-set route: every set gathers its point.
-static int vm_shared_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint8_t* d_apks, const uint32_t* d_key_idx, const uint32_t* d_offsets, uint32_t k,
-                            const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n,
-                            uint8_t* d_result, uint32_t* d_status_or, void* stream, uint64_t longest, bool locate = false, uint8_t* d_set_results = nullptr,
-                            uint32_t* d_set_status = nullptr, const mbls_msgtable* mt = nullptr) {
-    // mt (the _msgtable entries): d_midx holds indices into the resident table; d_msgs / msg_len / d_moff / n_msgs are not used (NULL / 0)
-    if (!c || !d_result) return MBLS_ERR_ARGUMENT;
+// The one way in for the device entries over a list or a resident table. d names its key handle alone (keys_in_table, keys_in_committees, keys_in_committee_span:
+// the entry has seen the handles non-null); what the handle holds is read here, under the lock, where each entry's checks have always stood.
+static int vm_shared_device(mbls_ctx* c, vm_call d, void* stream) {
+    if (!c || !d.d_result) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    if (mt && mt->c != c) ARGFAIL(c, "message table belongs to another context");
-    if (locate && !d_set_results) ARGFAIL(c, "null set results");
-    if (n && !(t ? (const void*)d_key_idx : (const void*)d_apks)) ARGFAIL(c, "null key buffer");
-    if (t && t->c != c) ARGFAIL(c, "key table belongs to another context");
-    if (n && !d_midx) ARGFAIL(c, "null buffer");
-    if (n_msgs > 0xFFFFFFFFull || n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
-    vm_shared sh; sh.n_msgs = n_msgs; sh.d_midx = d_midx; sh.longest = longest; sh.mt = mt;
-    sh.locate = locate; sh.d_set_results = d_set_results; sh.d_set_status = d_set_status;
-    return verify_multiple_impl(c, d_sigs, t ? nullptr : d_apks, nullptr, MBLS_PK_UNCOMPRESSED, t ? d_offsets : nullptr, t ? k : 0, d_msgs, msg_len, d_moff, d_rands, n, d_result,
-                                d_status_or, stream, nullptr, t, t ? d_key_idx : nullptr, false, false, &sh);
+    const uint64_t n = d.n; const int keys = vm_key_kind(d);
+    if (d.mt && d.mt->c != c) ARGFAIL(c, "message table belongs to another context");
+    if (d.locate && !d.d_set_results) ARGFAIL(c, "null set results");
+    if (keys == VM_KEYS_SPAN) {
+        const int rk = vm_keys_resolve(c, &d.ks, true); if (rk) return rk;
+        if (n && (!d.ks.d_cmt_span_off || (d.ks.n_cmt_ids && !d.ks.d_cmt_ids) || (d.ks.bits_stride && !d.ks.d_bits))) ARGFAIL(c, "null key buffer");
+    } else if (keys == VM_KEYS_COMMITTEE) {
+        const int rk = vm_keys_resolve(c, &d.ks, true); if (rk) return rk;
+        if (n && (!d.ks.d_cmt_idx || !d.ks.d_bits)) ARGFAIL(c, "null key buffer");
+    } else {
+        if (n && !(keys == VM_KEYS_TABLE ? (const void*)d.ks.d_idx : (const void*)d.d_apks)) ARGFAIL(c, "null key buffer");
+        const int rk = vm_keys_resolve(c, &d.ks, true); if (rk) return rk;
+    }
+    if (n && !d.ms.d_idx) ARGFAIL(c, "null buffer");
+    if (d.ms.n_msgs > 0xFFFFFFFFull || n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
+    return verify_multiple_impl(c, d, stream);
 }
 extern "C" int mbls_verify_multiple_shared_msgs_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff,
         uint64_t n_msgs, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream) {
-    return vm_shared_device(c, nullptr, d_sigs, d_apks, nullptr, nullptr, 0, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, d_rands, n, d_result, d_status, stream, 0);
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys_apks(d_apks).msgs(msgs_list(d_msgs, msg_len, d_moff, n_msgs, d_msg_idx)).out(d_result, d_status), stream);
 }
 extern "C" int mbls_verify_multiple_sets_indexed_shared_msgs_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx, const uint32_t* d_offsets,
         uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n,
         uint8_t* d_result, uint32_t* d_status, void* stream) {
     if (!t) return MBLS_ERR_ARGUMENT;
-    return vm_shared_device(c, t, d_sigs, nullptr, d_key_idx, d_offsets, k, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, d_rands, n, d_result, d_status, stream, 0);
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_table(t, d_key_idx, d_offsets), k).msgs(msgs_list(d_msgs, msg_len, d_moff, n_msgs, d_msg_idx))
+                                   .out(d_result, d_status), stream);
 }
 // the host entries' checks (nothing is queued when they fail; the outputs stay untouched): the list's offset table, every index inside the list. -> the longest group
-static int vm_shared_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n_msgs,
-                                const uint32_t* msg_idx, uint64_t n, uint64_t* longest) {
+static int vm_shared_host_check(mbls_ctx* c, const vm_host& h, uint64_t* longest) {
+    const uint64_t n_msgs = h.ms.n_msgs, n = h.n; const uint64_t* const moff = h.ms.d_moff; const uint32_t* const msg_idx = h.ms.d_idx;
     if (n_msgs > 0xFFFFFFFFull || n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
-    if (!sigs96 || !apks96 || !msg_idx) ARGFAIL(c, "null buffer");
+    if (!h.sigs96 || !h.apks96 || !msg_idx) ARGFAIL(c, "null buffer");
     if (moff && !msg_offsets_ok(moff, n_msgs)) ARGFAIL(c, "msg_offsets must be non-decreasing, messages below 2^32 bytes");
-    const size_t msg_total = moff ? (size_t)(moff[n_msgs] - moff[0]) : (size_t)msg_len * n_msgs;
-    if (!msgs && msg_total) ARGFAIL(c, "null buffer");
+    const size_t msg_total = moff ? (size_t)(moff[n_msgs] - moff[0]) : (size_t)h.ms.msg_len * n_msgs;
+    if (!h.ms.d_msgs && msg_total) ARGFAIL(c, "null buffer");
     std::vector<uint32_t> cnt;
     try { cnt.assign(n_msgs, 0); } catch (...) { ARGFAIL(c, "out of host memory"); }
     uint64_t m = 0;
@@ -4433,14 +4433,13 @@ static int vm_shared_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_
 }
 // the same for the host entries over a resident table (the caller holds the context's lock: the table's size is the one the call is planned with): every index
 // names an entry of the table. -> the longest group and the number of distinct entries named, counted on a sorted copy of the indices (the table may be far
-// larger than the call)
-static int vm_msgtable_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint64_t* longest,
-                                  uint64_t* named, bool keys_elsewhere = false) {
-    // keys_elsewhere (the committee form): the sets have no aggregate keys, apks96 is null
+// larger than the call). The committee forms (h.hc) have no aggregate keys: apks96 is null
+static int vm_msgtable_host_check(mbls_ctx* c, const vm_host& h, uint64_t* longest, uint64_t* named) {
+    const uint64_t n = h.n; const uint32_t* const msg_idx = h.ms.d_idx;
     if (n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
-    if (!sigs96 || (!apks96 && !keys_elsewhere) || !msg_idx) ARGFAIL(c, "null buffer");
+    if (!h.sigs96 || (!h.apks96 && !h.hc) || !msg_idx) ARGFAIL(c, "null buffer");
     for (uint64_t i = 0; i < n; i++)
-        if (mtb_names_nothing(msg_idx[i], mt->size)) ARGFAIL(c, "msg_idx names no entry of the message table");
+        if (mtb_names_nothing(msg_idx[i], h.mt->size)) ARGFAIL(c, "msg_idx names no entry of the message table");
     std::vector<uint32_t> idx;
     try { idx.assign(msg_idx, msg_idx + n); } catch (...) { ARGFAIL(c, "out of host memory"); }
     std::sort(idx.begin(), idx.end());
@@ -4453,108 +4452,107 @@ static int vm_msgtable_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint
     return MBLS_OK;
 }
 // locate: the sets' answers as well (set_results required, set_status optional), staged behind one another in one buffer: n words, then n bytes
-static int vm_shared_host_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
-        uint64_t n_msgs, const uint32_t* msg_idx, const uint64_t* rands, uint64_t n, uint8_t* result, uint32_t* status, bool locate, uint8_t* set_results,
-        uint32_t* set_status) {
-    if (!c || !result) return MBLS_ERR_ARGUMENT;
+static int vm_shared_host_impl(mbls_ctx* c, const vm_host& h) {
+    if (!c || !h.result) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    if (locate && !set_results) ARGFAIL(c, "null set results");
-    if (n == 0) { *result = 1; if (status) *status = 0; return MBLS_OK; }
-    if (!rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
+    const uint64_t n = h.n, n_msgs = h.ms.n_msgs; const uint64_t* const moff = h.ms.d_moff;
+    if (h.locate && !h.set_results) ARGFAIL(c, "null set results");
+    if (n == 0) { *h.result = 1; if (h.status) *h.status = 0; return MBLS_OK; }
+    if (!h.rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
     uint64_t longest = 0;
-    int rc = vm_shared_host_check(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, n, &longest); if (rc) return rc;
+    int rc = vm_shared_host_check(c, h, &longest); if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t msg_first = moff ? moff[0] : 0;
-    const size_t msg_total = moff ? (size_t)(moff[n_msgs] - moff[0]) : (size_t)msg_len * n_msgs;
+    const size_t msg_total = moff ? (size_t)(moff[n_msgs] - moff[0]) : (size_t)h.ms.msg_len * n_msgs;
     sbuf ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dmo(c, 6), dres(c, 4), dmi(c, 7), dset(c, 8);
-    HIPCHK(c, ds.up(sigs96, 96 * n)); HIPCHK(c, da.up(apks96, 96 * n)); HIPCHK(c, dm.up(msgs ? msgs + msg_first : nullptr, msg_total)); HIPCHK(c, dr.up(rands, 8 * n));
-    HIPCHK(c, dmi.up(msg_idx, 4 * n)); HIPCHK(c, dres.alloc(8));
+    HIPCHK(c, ds.up(h.sigs96, 96 * n)); HIPCHK(c, da.up(h.apks96, 96 * n)); HIPCHK(c, dm.up(h.ms.d_msgs ? h.ms.d_msgs + msg_first : nullptr, msg_total));
+    HIPCHK(c, dr.up(h.rands, 8 * n)); HIPCHK(c, dmi.up(h.ms.d_idx, 4 * n)); HIPCHK(c, dres.alloc(8));
     if (moff) HIPCHK(c, dmo.up(moff, 8 * (n_msgs + 1)));
     uint32_t* d_sst = nullptr; uint8_t* d_sres = nullptr;
-    if (locate) { HIPCHK(c, dset.alloc(5 * n)); d_sst = dset.as<uint32_t>(); d_sres = dset.as<uint8_t>() + 4 * n; }
-    rc = vm_shared_device(c, nullptr, ds.as<uint8_t>(), da.as<uint8_t>(), nullptr, nullptr, 0, dm.as<uint8_t>() - msg_first, msg_len, moff ? dmo.as<uint64_t>() : nullptr, n_msgs,
-                          dmi.as<uint32_t>(), dr.as<uint64_t>(), n, dres.as<uint8_t>(), dres.as<uint32_t>() + 1, c->hs_a, longest, locate, d_sres, d_sst);
+    if (h.locate) { HIPCHK(c, dset.alloc(5 * n)); d_sst = dset.as<uint32_t>(); d_sres = dset.as<uint8_t>() + 4 * n; }
+    const vm_call d = vm_sets(ds.as<uint8_t>(), dr.as<uint64_t>(), n).keys_apks(da.as<uint8_t>())
+                          .msgs(msgs_list(dm.as<uint8_t>() - msg_first, h.ms.msg_len, moff ? dmo.as<uint64_t>() : nullptr, n_msgs, dmi.as<uint32_t>()))
+                          .out(dres.as<uint8_t>(), dres.as<uint32_t>() + 1).counted(longest);
+    rc = vm_shared_device(c, h.locate ? d.out_sets(d_sres, d_sst) : d, c->hs_a);
     if (rc) { vm_rng_drain(c); return rc; }
     HIPCHK(c, hipStreamSynchronize(c->hs_a));
     c->ws_pending = false;
     uint32_t out[2] = {0, 0};
     HIPCHK(c, dres.down(out, 8));
-    if (locate) {
-        HIPCHK(c, hipMemcpy(set_results, d_sres, n, hipMemcpyDeviceToHost));
-        if (set_status) HIPCHK(c, hipMemcpy(set_status, d_sst, 4 * n, hipMemcpyDeviceToHost));
+    if (h.locate) {
+        HIPCHK(c, hipMemcpy(h.set_results, d_sres, n, hipMemcpyDeviceToHost));
+        if (h.set_status) HIPCHK(c, hipMemcpy(h.set_status, d_sst, 4 * n, hipMemcpyDeviceToHost));
     }
-    *result = (uint8_t)(out[0] & 0xFF); if (status) *status = out[1];
+    *h.result = (uint8_t)(out[0] & 0xFF); if (h.status) *h.status = out[1];
     return MBLS_OK;
 }
 extern "C" int mbls_verify_multiple_shared_msgs(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
         uint64_t n_msgs, const uint32_t* msg_idx, const uint64_t* rands, uint64_t n, uint8_t* result, uint32_t* status) {
-    return vm_shared_host_impl(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, rands, n, result, status, false, nullptr, nullptr);
+    return vm_shared_host_impl(c, vm_host_sets(sigs96, n).keys_apks(apks96).msgs(msgs_list(msgs, msg_len, moff, n_msgs, msg_idx)).scalars(rands).out(result, status));
 }
 // the reference's order, as mbls_verify_multiple_aggregate_signatures_rng keeps it (vm_rng_phase1 / vm_rng_phase2 with the list): signatures decoded and tested
 // first, `draw` called once for the sets in front of the first bad signature, no second subgroup test
 // locate: the sets' answers as well. A set at or behind the first signature outside G2 has no scalar (the reference never draws one) and cannot be examined: its
-// answer is 0 and its word what the signature phase found, set on the host from the verdicts phase 1 read back. The sets in front of it have their scalars and
-// are judged one by one: the call goes on (it is rejected through its status bits whatever the product is) with the scalar 1 for the sets without one, which
-// changes nothing -- as mbls_verify_multiple_batches_locate_rng does.
-static int vm_shared_rng_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
-        uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user, bool locate, uint8_t* set_results, uint32_t* set_status,
-        const mbls_msgtable* mt = nullptr, const host_committees* hc = nullptr) {
-    // mt (the _msgtable entries): msg_idx holds indices into the resident table, no list (msgs / moff NULL, msg_len = n_msgs = 0); the host counts the named entries
-    // hc (the _committee_msgtable entries, over mt): the sets' keys by descriptor word and bitfield (mbls_vmc.h) in host memory, apks96 null; a word that names
-    // nothing refuses the call
-    if (!c || !result) return MBLS_ERR_ARGUMENT;
+// answer is 0 and its word what the signature phase found, set on the host from the verdicts phase 1 read back (vmr_close). The sets in front of it have their
+// scalars and are judged one by one: the call goes on (it is rejected through its status bits whatever the product is) with the scalar 1 for the sets without
+// one, which changes nothing -- as mbls_verify_multiple_batches_locate_rng does.
+// h.mt (the _msgtable entries): the sets' indices name entries of the resident table, no list; the host counts the named entries
+// h.hc (the _committee_msgtable and _committee_span_msgtable entries, over h.mt): the sets' keys by descriptor word and bitfield (mbls_vmc.h) or by span
+// (mbls_vcs.h) in host memory; a word or id that names nothing refuses the call
+static int vm_shared_rng_impl(mbls_ctx* c, const vm_host& h) {
+    if (!c || !h.result) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    if (locate && !set_results) ARGFAIL(c, "null set results");
-    if (mt && mt->c != c) ARGFAIL(c, "message table belongs to another context");
-    vm_committee vcs; vm_committee* const vc = hc ? &vcs : nullptr;
-    if (hc && hc->span) { const int rk = vm_committee_span_of(c, hc->t, nullptr, hc->n_cmt_ids, nullptr, nullptr, hc->bits_stride, false, vc); if (rk) return rk; }
-    else if (hc) { const int rk = vm_committee_of(c, hc->t, nullptr, nullptr, hc->bits_stride, false, vc); if (rk) return rk; }
-    if (n == 0) { *result = 1; return MBLS_OK; }                            // empty iterator: true, the generator untouched
-    if (!draw) ARGFAIL(c, "no scalar source");
-    vm_shared sh; sh.n_msgs = n_msgs; sh.mt = mt;
-    if (hc && hc->span) { const int ri = vm_committee_span_sets_ok(c, *hc, *vc, n); if (ri) return ri; }
+    const uint64_t n = h.n; const host_committees* const hc = h.hc;
+    if (h.locate && !h.set_results) ARGFAIL(c, "null set results");
+    if (h.mt && h.mt->c != c) ARGFAIL(c, "message table belongs to another context");
+    vm_call d;
+    if (hc) {
+        d.ks = hc->span ? keys_in_committee_span(hc->t, nullptr, hc->n_cmt_ids, nullptr, nullptr, hc->bits_stride) : keys_in_committees(hc->t, nullptr, nullptr, hc->bits_stride);
+        const int rk = vm_keys_resolve(c, &d.ks, false); if (rk) return rk;
+    }
+    if (n == 0) { *h.result = 1; return MBLS_OK; }                          // empty iterator: true, the generator untouched
+    if (!h.draw) ARGFAIL(c, "no scalar source");
+    if (hc && hc->span) { const int ri = vm_committee_span_sets_ok(c, *hc, d.ks, n); if (ri) return ri; }
     else if (hc) {
         if (!hc->cmt_idx || !hc->bits) ARGFAIL(c, "null buffer");
         for (uint64_t i = 0; i < n; i++)
-            if (vmc_names_nothing(hc->cmt_idx[i], vc->ccount, vc->tsize))
+            if (vmc_names_nothing(hc->cmt_idx[i], d.ks.ccount, d.ks.tsize))
                 ARGFAIL(c, vmc_is_single(hc->cmt_idx[i]) ? "cmt_idx names no key of the key table" : "cmt_idx names no committee of the table");
     }
-    int rc = mt ? vm_msgtable_host_check(c, sigs96, apks96, mt, msg_idx, n, &sh.longest, &sh.named, hc != nullptr)
-                : vm_shared_host_check(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, n, &sh.longest); if (rc) return rc;
+    d.mt = h.mt;
+    int rc = h.mt ? vm_msgtable_host_check(c, h, &d.longest, &d.named) : vm_shared_host_check(c, h, &d.longest); if (rc) return rc;
     std::vector<uint64_t> rands; std::vector<uint32_t> st;
     try { rands.resize(n); st.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
     vm_rng_stage g(c);
     sbuf dset(c, 8);
-    if (locate) {       // (the workspace of the WHOLE call, shadows included, is reserved by phase 1: growing it later would lose the decoded signatures)
+    if (h.locate) {     // (the workspace of the WHOLE call, shadows included, is reserved by phase 1: growing it later would lose the decoded signatures)
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, dset.alloc(5 * n));
-        sh.locate = true; sh.d_set_status = dset.as<uint32_t>(); sh.d_set_results = dset.as<uint8_t>() + 4 * n;
+        d = d.out_sets(dset.as<uint8_t>() + 4 * n, dset.as<uint32_t>());
     }
-    rc = vm_rng_phase1(c, g, sigs96, apks96, msgs, msg_len, moff, n, 8, st.data(), &sh, msg_idx, hc, vc); if (rc) return rc;
-    size_t reached = n;                                                     // the sets the reference's loop draws a scalar for
-    for (size_t i = 0; i < n; i++)
-        if (st[i] & (MBLS_ST_BAD_SIG_ENCODING | MBLS_ST_SIG_NOT_IN_G2)) { reached = i; break; }
-    if (reached) draw(user, rands.data(), (uint64_t)reached);
-    if (reached < n && !locate) { vm_rng_drain(c); *result = 0; return MBLS_OK; }     // src/aggregates.rs:273-275
-    for (size_t i = reached; i < n; i++) rands[i] = 1;
-    rc = vm_rng_phase2(c, g, msg_len, rands.data(), n, false, &sh, vc);
+    rc = vm_rng_phase1(c, g, h, 8, st.data(), &d); if (rc) return rc;
+    const uint64_t reached = vmr_reach(st.data(), 0, n);                    // the sets the reference's loop draws a scalar for
+    if (reached) h.draw(h.user, rands.data(), reached);
+    if (reached < n && !h.locate) { vm_rng_drain(c); *h.result = 0; return MBLS_OK; }     // src/aggregates.rs:273-275
+    for (uint64_t i = reached; i < n; i++) rands[i] = 1;
+    rc = vm_rng_phase2(c, g, rands.data(), false, d);
     std::fill(rands.begin(), rands.end(), 0);
     if (rc) { vm_rng_drain(c); return rc; }
     if (hipStreamSynchronize(c->hs_a) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
     c->ws_pending = false;
     uint8_t r = 0;
     HIPCHK(c, g.dout.down(&r, 1));
-    if (locate) {
-        HIPCHK(c, hipMemcpy(set_results, sh.d_set_results, n, hipMemcpyDeviceToHost));
-        if (set_status) HIPCHK(c, hipMemcpy(set_status, sh.d_set_status, 4 * n, hipMemcpyDeviceToHost));
-        for (size_t i = reached; i < n; i++) { set_results[i] = 0; if (set_status) set_status[i] = st[i]; }
+    if (h.locate) {
+        HIPCHK(c, hipMemcpy(h.set_results, d.d_set_results, n, hipMemcpyDeviceToHost));
+        if (h.set_status) HIPCHK(c, hipMemcpy(h.set_status, d.d_set_status, 4 * n, hipMemcpyDeviceToHost));
+        vmr_close(st.data(), &reached, nullptr, (uint32_t)n, 1, h.set_results, h.set_status);
     }
-    *result = r;
+    *h.result = r;
     return MBLS_OK;
 }
 extern "C" int mbls_verify_multiple_shared_msgs_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
         uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user) {
-    return vm_shared_rng_impl(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, n, result, draw, user, false, nullptr, nullptr);
+    return vm_shared_rng_impl(c, vm_host_sets(sigs96, n).keys_apks(apks96).msgs(msgs_list(msgs, msg_len, moff, n_msgs, msg_idx)).source(draw, user).out(result, nullptr));
 }
 // ---- which sets of a rejected call over a shared message list (include/mbls.h, mbls_verify_multiple*_shared_msgs_locate*): the entries above with one bool and
 // one status word per SET beside the call's own. Phase one is unchanged; the shadows, the mark rule and phase two are described at k_vsl_keep_key.
@@ -4562,24 +4560,26 @@ extern "C" int mbls_verify_multiple_shared_msgs_locate_device(mbls_ctx* c, const
         const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status,
         uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
     if (!d_set_results) return MBLS_ERR_ARGUMENT;
-    return vm_shared_device(c, nullptr, d_sigs, d_apks, nullptr, nullptr, 0, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, true,
-                            d_set_results, d_set_status);
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys_apks(d_apks).msgs(msgs_list(d_msgs, msg_len, d_moff, n_msgs, d_msg_idx)).out(d_result, d_status)
+                                   .out_sets(d_set_results, d_set_status), stream);
 }
 extern "C" int mbls_verify_multiple_sets_indexed_shared_msgs_locate_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx,
         const uint32_t* d_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, uint64_t n_msgs, const uint32_t* d_msg_idx,
         const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
     if (!t || !d_set_results) return MBLS_ERR_ARGUMENT;
-    return vm_shared_device(c, t, d_sigs, nullptr, d_key_idx, d_offsets, k, d_msgs, msg_len, d_moff, n_msgs, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, true,
-                            d_set_results, d_set_status);
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_table(t, d_key_idx, d_offsets), k).msgs(msgs_list(d_msgs, msg_len, d_moff, n_msgs, d_msg_idx))
+                                   .out(d_result, d_status).out_sets(d_set_results, d_set_status), stream);
 }
 extern "C" int mbls_verify_multiple_shared_msgs_locate(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
         uint64_t n_msgs, const uint32_t* msg_idx, const uint64_t* rands, uint64_t n, uint8_t* result, uint32_t* status, uint8_t* set_results, uint32_t* set_status) {
-    return vm_shared_host_impl(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, rands, n, result, status, true, set_results, set_status);
+    return vm_shared_host_impl(c, vm_host_sets(sigs96, n).keys_apks(apks96).msgs(msgs_list(msgs, msg_len, moff, n_msgs, msg_idx)).scalars(rands).out(result, status)
+                                      .out_sets(set_results, set_status));
 }
 extern "C" int mbls_verify_multiple_shared_msgs_locate_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len,
         const uint64_t* moff, uint64_t n_msgs, const uint32_t* msg_idx, uint64_t n, uint8_t* result, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw,
         void* user) {
-    return vm_shared_rng_impl(c, sigs96, apks96, msgs, msg_len, moff, n_msgs, msg_idx, n, result, draw, user, true, set_results, set_status);
+    return vm_shared_rng_impl(c, vm_host_sets(sigs96, n).keys_apks(apks96).msgs(msgs_list(msgs, msg_len, moff, n_msgs, msg_idx)).source(draw, user).out(result, nullptr)
+                                     .out_sets(set_results, set_status));
 }
 // what a locate call over a shared list reserves before its first kernel: mbls_vsl.h's figure under the route and the list hash the limits choose
 extern "C" uint64_t mbls_plan_verify_multiple_shared_msgs_locate_workspace_items(const mbls_limits* limits, uint64_t n, uint64_t n_msgs, int mode) {
@@ -4588,129 +4588,101 @@ extern "C" uint64_t mbls_plan_verify_multiple_shared_msgs_locate_workspace_items
     return vsl_workspace_items(n, n_msgs, vp.route == MBLS_VM_ROUTE_GROUPED, vp.list_workspace_items);
 }
 
-// ---- verify_multiple over the resident message table (include/mbls.h, mbls_verify_multiple*_msgtable*): the shared-message entries with a vm_shared that names a
-// table in place of a list -- verify_multiple_impl's grouped route over the table's T entries, the named entries compacted on the device (mbls_vmt.h; k_vmt_flag,
+// ---- verify_multiple over the resident message table (include/mbls.h, mbls_verify_multiple*_msgtable*): the shared-message entries with a description that names
+// a table in place of a list -- verify_multiple_impl's grouped route over the table's T entries, the named entries compacted on the device (mbls_vmt.h; k_vmt_flag,
 // k_vmt_named, k_vmt_heads), or the per-set route with one gather from the table. Nothing is hashed.
 extern "C" int mbls_verify_multiple_msgtable_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
         const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream) {
     if (!mt) return MBLS_ERR_ARGUMENT;
-    return vm_shared_device(c, nullptr, d_sigs, d_apks, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, false, nullptr, nullptr, mt);
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys_apks(d_apks).msgs_in(mt, d_msg_idx, 0).out(d_result, d_status), stream);
 }
 extern "C" int mbls_verify_multiple_sets_indexed_msgtable_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx, const uint32_t* d_offsets,
         uint32_t k, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream) {
     if (!t || !mt) return MBLS_ERR_ARGUMENT;
-    return vm_shared_device(c, t, d_sigs, nullptr, d_key_idx, d_offsets, k, nullptr, 0, nullptr, 0, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, false, nullptr, nullptr, mt);
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_table(t, d_key_idx, d_offsets), k).msgs_in(mt, d_msg_idx, 0).out(d_result, d_status), stream);
 }
 extern "C" int mbls_verify_multiple_msgtable_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n,
         uint8_t* result, mbls_scalar_source draw, void* user) {
     if (!mt) return MBLS_ERR_ARGUMENT;
-    return vm_shared_rng_impl(c, sigs96, apks96, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, false, nullptr, nullptr, mt);
+    return vm_shared_rng_impl(c, vm_host_sets(sigs96, n).keys_apks(apks96).msgs_in(mt, msg_idx).source(draw, user).out(result, nullptr));
 }
 extern "C" int mbls_verify_multiple_msgtable_locate_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
         const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
     if (!mt || !d_set_results) return MBLS_ERR_ARGUMENT;
-    return vm_shared_device(c, nullptr, d_sigs, d_apks, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, true, d_set_results,
-                            d_set_status, mt);
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys_apks(d_apks).msgs_in(mt, d_msg_idx, 0).out(d_result, d_status).out_sets(d_set_results, d_set_status), stream);
 }
 extern "C" int mbls_verify_multiple_sets_indexed_msgtable_locate_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx,
         const uint32_t* d_offsets, uint32_t k, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status,
         uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
     if (!t || !mt || !d_set_results) return MBLS_ERR_ARGUMENT;
-    return vm_shared_device(c, t, d_sigs, nullptr, d_key_idx, d_offsets, k, nullptr, 0, nullptr, 0, d_msg_idx, d_rands, n, d_result, d_status, stream, 0, true, d_set_results,
-                            d_set_status, mt);
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_table(t, d_key_idx, d_offsets), k).msgs_in(mt, d_msg_idx, 0).out(d_result, d_status)
+                                   .out_sets(d_set_results, d_set_status), stream);
 }
 extern "C" int mbls_verify_multiple_msgtable_locate_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n,
         uint8_t* result, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user) {
     if (!mt) return MBLS_ERR_ARGUMENT;
-    return vm_shared_rng_impl(c, sigs96, apks96, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, true, set_results, set_status, mt);
+    return vm_shared_rng_impl(c, vm_host_sets(sigs96, n).keys_apks(apks96).msgs_in(mt, msg_idx).source(draw, user).out(result, nullptr).out_sets(set_results, set_status));
 }
 
 // ---- verify_multiple over committee bitfields and the resident message table (include/mbls.h, mbls_verify_multiple_committee_msgtable*; the set descriptor is
 // mbls_vmc.h): the _sets_indexed_msgtable entries with every set's signers named by a committee id and its bitfield, or by one key index -- verify_multiple_impl's
-// third key source (k_vmc_expand, k_aggregate_vmc_d); everything behind the key sum is the entries' above.
-static int vm_committee_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride,
-                               const mbls_msgtable* mt, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status_or, void* stream,
-                               bool locate, uint8_t* d_set_results, uint32_t* d_set_status) {
-    if (!c || !t || !mt || !d_result) return MBLS_ERR_ARGUMENT;
-    mbls_lock lk(c->mu);
-    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
-    if (locate && !d_set_results) ARGFAIL(c, "null set results");
-    vm_committee vc; const int rk = vm_committee_of(c, t, d_cmt_idx, d_bits, bits_stride, true, &vc); if (rk) return rk;
-    if (n && (!d_cmt_idx || !d_bits)) ARGFAIL(c, "null key buffer");
-    if (n && !d_midx) ARGFAIL(c, "null buffer");
-    if (n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
-    vm_shared sh; sh.d_midx = d_midx; sh.mt = mt; sh.locate = locate; sh.d_set_results = d_set_results; sh.d_set_status = d_set_status;
-    return verify_multiple_impl(c, d_sigs, nullptr, nullptr, MBLS_PK_UNCOMPRESSED, nullptr, 0, nullptr, 0, nullptr, d_rands, n, d_result, d_status_or, stream, nullptr, nullptr,
-                                nullptr, false, false, &sh, &vc);
-}
+// committee key source (k_vmc_expand, k_aggregate_vmc_d); everything behind the key sum is the entries' above.
 extern "C" int mbls_verify_multiple_committee_msgtable_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx, const uint8_t* d_bits,
         uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result, uint32_t* d_status, void* stream) {
-    return vm_committee_device(c, t, d_sigs, d_cmt_idx, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_result, d_status, stream, false, nullptr, nullptr);
+    if (!t || !mt) return MBLS_ERR_ARGUMENT;
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_committees(t, d_cmt_idx, d_bits, bits_stride), 0).msgs_in(mt, d_msg_idx, 0).out(d_result, d_status), stream);
 }
 extern "C" int mbls_verify_multiple_committee_msgtable_locate_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx,
         const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result,
         uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
-    if (!d_set_results) return MBLS_ERR_ARGUMENT;
-    return vm_committee_device(c, t, d_sigs, d_cmt_idx, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_result, d_status, stream, true, d_set_results, d_set_status);
+    if (!t || !mt || !d_set_results) return MBLS_ERR_ARGUMENT;
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_committees(t, d_cmt_idx, d_bits, bits_stride), 0).msgs_in(mt, d_msg_idx, 0).out(d_result, d_status)
+                                   .out_sets(d_set_results, d_set_status), stream);
 }
 extern "C" int mbls_verify_multiple_committee_msgtable_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_idx, const uint8_t* bits,
         uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint8_t* result, mbls_scalar_source draw, void* user) {
     if (!t || !mt) return MBLS_ERR_ARGUMENT;
     const host_committees hc = {t, cmt_idx, bits, bits_stride};
-    return vm_shared_rng_impl(c, sigs96, nullptr, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, false, nullptr, nullptr, mt, &hc);
+    return vm_shared_rng_impl(c, vm_host_sets(sigs96, n).keys(&hc).msgs_in(mt, msg_idx).source(draw, user).out(result, nullptr));
 }
 extern "C" int mbls_verify_multiple_committee_msgtable_locate_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_idx, const uint8_t* bits,
         uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint8_t* result, uint8_t* set_results, uint32_t* set_status,
         mbls_scalar_source draw, void* user) {
     if (!t || !mt) return MBLS_ERR_ARGUMENT;
     const host_committees hc = {t, cmt_idx, bits, bits_stride};
-    return vm_shared_rng_impl(c, sigs96, nullptr, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, true, set_results, set_status, mt, &hc);
+    return vm_shared_rng_impl(c, vm_host_sets(sigs96, n).keys(&hc).msgs_in(mt, msg_idx).source(draw, user).out(result, nullptr).out_sets(set_results, set_status));
 }
 
 // ---- verify_multiple over committee spans and the resident message table (include/mbls.h, mbls_verify_multiple_committee_span_msgtable*; rules: mbls_vcs.h): the
 // entries above with every set's signers named by a range of committee ids and one field over their concatenated members, or by one key index. The key source is
 // verify_multiple_impl's committee source in its span form: k_vcs_expand, then k_aggregate_vcs_d or, under a split, k_vcs_partial_d and k_vcs_combine (mbls_vcs.hip).
-static int vm_committee_span_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids, const uint32_t* d_cmt_off,
-                                    const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n,
-                                    uint8_t* d_result, uint32_t* d_status_or, void* stream, bool locate, uint8_t* d_set_results, uint32_t* d_set_status) {
-    if (!c || !t || !mt || !d_result) return MBLS_ERR_ARGUMENT;
-    mbls_lock lk(c->mu);
-    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
-    if (locate && !d_set_results) ARGFAIL(c, "null set results");
-    vm_committee vc; const int rk = vm_committee_span_of(c, t, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, true, &vc); if (rk) return rk;
-    if (n && (!d_cmt_off || (n_cmt_ids && !d_cmt_ids) || (bits_stride && !d_bits))) ARGFAIL(c, "null key buffer");
-    if (n && !d_midx) ARGFAIL(c, "null buffer");
-    if (n > 0xFFFFFFFFull) ARGFAIL(c, "message indices and positions are 32-bit");
-    vm_shared sh; sh.d_midx = d_midx; sh.mt = mt; sh.locate = locate; sh.d_set_results = d_set_results; sh.d_set_status = d_set_status;
-    return verify_multiple_impl(c, d_sigs, nullptr, nullptr, MBLS_PK_UNCOMPRESSED, nullptr, 0, nullptr, 0, nullptr, d_rands, n, d_result, d_status_or, stream, nullptr, nullptr,
-                                nullptr, false, false, &sh, &vc);
-}
 extern "C" int mbls_verify_multiple_committee_span_msgtable_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_ids, uint64_t n_cmt_ids,
         const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n,
         uint8_t* d_result, uint32_t* d_status, void* stream) {
-    return vm_committee_span_device(c, t, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_result, d_status, stream, false, nullptr,
-                                    nullptr);
+    if (!t || !mt) return MBLS_ERR_ARGUMENT;
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_committee_span(t, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride), 0).msgs_in(mt, d_msg_idx, 0)
+                                   .out(d_result, d_status), stream);
 }
 extern "C" int mbls_verify_multiple_committee_span_msgtable_locate_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_ids,
         uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands,
         uint64_t n, uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
-    if (!d_set_results) return MBLS_ERR_ARGUMENT;
-    return vm_committee_span_device(c, t, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_result, d_status, stream, true,
-                                    d_set_results, d_set_status);
+    if (!t || !mt || !d_set_results) return MBLS_ERR_ARGUMENT;
+    return vm_shared_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_committee_span(t, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride), 0).msgs_in(mt, d_msg_idx, 0)
+                                   .out(d_result, d_status).out_sets(d_set_results, d_set_status), stream);
 }
 extern "C" int mbls_verify_multiple_committee_span_msgtable_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_ids, uint64_t n_cmt_ids,
         const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint8_t* result,
         mbls_scalar_source draw, void* user) {
     if (!t || !mt) return MBLS_ERR_ARGUMENT;
     const host_committees hc = {t, nullptr, bits, bits_stride, true, cmt_ids, n_cmt_ids, cmt_off};
-    return vm_shared_rng_impl(c, sigs96, nullptr, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, false, nullptr, nullptr, mt, &hc);
+    return vm_shared_rng_impl(c, vm_host_sets(sigs96, n).keys(&hc).msgs_in(mt, msg_idx).source(draw, user).out(result, nullptr));
 }
 extern "C" int mbls_verify_multiple_committee_span_msgtable_locate_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_ids,
         uint64_t n_cmt_ids, const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, uint8_t* result,
         uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user) {
     if (!t || !mt) return MBLS_ERR_ARGUMENT;
     const host_committees hc = {t, nullptr, bits, bits_stride, true, cmt_ids, n_cmt_ids, cmt_off};
-    return vm_shared_rng_impl(c, sigs96, nullptr, nullptr, 0, nullptr, 0, msg_idx, n, result, draw, user, true, set_results, set_status, mt, &hc);
+    return vm_shared_rng_impl(c, vm_host_sets(sigs96, n).keys(&hc).msgs_in(mt, msg_idx).source(draw, user).out(result, nullptr).out_sets(set_results, set_status));
 }
 
 // ---- B independent verify_multiple batches in ONE call (include/mbls.h, mbls_verify_multiple_batches*): what B consecutive calls of the entries above return,
@@ -4726,27 +4698,24 @@ extern "C" int mbls_verify_multiple_committee_span_msgtable_locate_rng(mbls_ctx*
 // trees run over them (k_vml_keep_sig, k_vml_keep_f), and phase two behind the per-batch tail: mark (k_vml_mark), then for the candidates -- the sets of rejected
 // batches whose own word carries no rejecting bit -- the Miller loop of (sig, -G1), the product with f_i and a final exponentiation each. Enqueued whatever the
 // verdicts are: the host never learns how many candidates there are, and waves without one return at once.
-struct vmb_locate { uint8_t* d_set_results = nullptr; uint32_t* d_set_status = nullptr; };
-struct vmb_keys {
-    const uint8_t* d_apks = nullptr; const uint8_t* d_pks = nullptr; int pk_format = MBLS_PK_UNCOMPRESSED; const uint32_t* d_pk_offsets = nullptr; uint32_t k = 0;
-    const mbls_keytable* tab = nullptr; const uint32_t* d_idx = nullptr;
-};
-static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands,
-        uint64_t n, const uint32_t* d_boff, uint32_t spb, uint64_t B, uint64_t longest, uint8_t* d_results, uint32_t* d_status, void* stream,
-        bool sigs_resident = false, bool hash_enqueued = false, const vmb_locate* loc = nullptr) {
+static int vmb_impl(mbls_ctx* c, const vm_call& d, void* stream) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
+    const uint64_t n = d.n, B = d.B; const uint32_t spb = d.spb; const uint32_t* const d_boff = d.d_boff; const uint64_t* const d_rands = d.d_rands;
+    uint8_t* const d_results = d.d_result; uint32_t* const d_status = d.d_status_or; const bool loc = d.locate;
+    uint64_t longest = d.longest;
     if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
     if (!d_results) ARGFAIL(c, "null results");
-    if (loc && !loc->d_set_results) ARGFAIL(c, "null set results");
+    if (loc && !d.d_set_results) ARGFAIL(c, "null set results");
     if (n > 0xFFFFFFFEull || B > 0xFFFFFFFEull) ARGFAIL(c, "set and batch indices are 32-bit");
     if (!d_boff && (uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch");
     if (n && !d_rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
-    if (n && ((!d_sigs && !sigs_resident) || (!d_msgs && msg_len && !d_moff))) ARGFAIL(c, "null buffer");
-    if (n && !ks.tab && !ks.d_apks && !ks.d_pks) ARGFAIL(c, "null keys");
-    if (n && ks.tab && !ks.d_idx) ARGFAIL(c, "null key indices");
-    if (ks.tab && ks.tab->c != c) ARGFAIL(c, "key table belongs to another context");
-    if (!ks.tab && !ks.d_apks && ks.pk_format != MBLS_PK_COMPRESSED && ks.pk_format != MBLS_PK_UNCOMPRESSED) ARGFAIL(c, "pk_format");
+    if (n && ((!d.d_sigs && !d.sigs_resident) || (!d.ms.d_msgs && d.ms.msg_len && !d.ms.d_moff))) ARGFAIL(c, "null buffer");
+    if (n && !d.ks.indexed && !d.d_apks && !d.ks.d_pks) ARGFAIL(c, "null keys");
+    if (n && d.ks.indexed && !d.ks.d_idx) ARGFAIL(c, "null key indices");
+    keysrc ks = d.ks; const int keys = vm_key_kind(d);
+    { const int rk = vm_keys_resolve(c, &ks, true); if (rk) return rk; }
+    if (keys == VM_KEYS_WIRE && ks.fmt != MBLS_PK_COMPRESSED && ks.fmt != MBLS_PK_UNCOMPRESSED) ARGFAIL(c, "pk_format");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const bool pair_hash = n && n <= c->split_max_items && 2 * n <= c->round_items;       // as verify_multiple_impl decides
@@ -4758,43 +4727,43 @@ static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, cons
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     mbls_ws wv = ws; wv.w += n;                                    // the batches' view: item b of wv = workspace item n + b
     rc = ws_acquire(c, s); if (rc) return rc;
-    if (ks.tab) { rc = table_acquire(c, ks.tab, s); if (rc) return rc; }
+    if (keys == VM_KEYS_TABLE) { rc = table_acquire(c, ks.tab, s); if (rc) return rc; }
     uint32_t* st_set = c->d_status;                                // (cap >= n + 2 B words)
     uint32_t* st_batch = d_status ? d_status : c->d_status + n;
     uint32_t* owned = c->d_status + n + B;
-    if (n && !sigs_resident) HIPCHK(c, hipMemsetAsync(st_set, 0, 4 * n, s));          // (resident: cleared before k_sig, and the message phase may be writing its bits)
+    if (n && !d.sigs_resident) HIPCHK(c, hipMemsetAsync(st_set, 0, 4 * n, s));          // (resident: cleared before k_sig, and the message phase may be writing its bits)
     HIPCHK(c, hipMemsetAsync(c->d_status + n, 0, 8 * B, s));
     if (d_status) HIPCHK(c, hipMemsetAsync(d_status, 0, 4 * B, s));
     if (map) HIPCHK(c, hipMemsetAsync(map, 0xFF, 4 * (n ? n : 1), s));                // every entry the map kernel does not write reads as "no owner"
     HIPCHK(c, hipMemsetAsync(d_results, 0, B, s));                 // false until the tail kernel has spoken (fail closed)
     uint32_t* cand = c->d_status + vml_flags_first(n, B);          // (locate mode: cap >= 2 n + 2 B words)
     if (loc && n) {
-        HIPCHK(c, hipMemsetAsync(loc->d_set_results, 0, n, s));
-        if (loc->d_set_status) HIPCHK(c, hipMemsetAsync(loc->d_set_status, 0, 4 * n, s));
+        HIPCHK(c, hipMemsetAsync(d.d_set_results, 0, n, s));
+        if (d.d_set_status) HIPCHK(c, hipMemsetAsync(d.d_set_status, 0, 4 * n, s));
         HIPCHK(c, hipMemsetAsync(cand, 0, 4 * n, s));
     }
     // the three chains side by side below half a round, as in verify_multiple_impl
     const bool fork = n && 2 * n <= c->round_items;
     hipStream_t s_sig = fork ? c->hs_b : s, s_msg = fork ? c->hs_c : s;
     if (fork) { HIPCHK(c, hipEventRecord(c->hs_ev, s)); HIPCHK(c, hipStreamWaitEvent(s_sig, c->hs_ev, 0)); HIPCHK(c, hipStreamWaitEvent(s_msg, c->hs_ev, 0)); }
-    const bool hash_first = fork && !hash_enqueued;
-    if (hash_first) launch_hash(c, ws, d_msgs, msg_len, d_moff, st_set, n, s_msg, pair_hash);
+    const bool hash_first = fork && !d.hash_enqueued;
+    if (hash_first) launch_hash(c, ws, d.ms.d_msgs, d.ms.msg_len, d.ms.d_moff, st_set, n, s_msg, pair_hash);
     if (n) {
-        if (ks.tab)
-            hipLaunchKernelGGL(k_aggregate_indexed_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)ks.tab->d_recs, ks.tab->size, ks.d_idx, ks.d_pk_offsets, ks.k, MBLS_MODE_VERIFY, st_set, n);
-        else if (!ks.d_apks)
-            launch_aggregate(ws, ks.d_pks, ks.d_pk_offsets, ks.k, ks.pk_format, MBLS_MODE_VERIFY, st_set, n, s);
-        hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (ks.tab || !ks.d_apks) ? (const uint8_t*)nullptr : ks.d_apks, d_rands, st_set, n);
+        if (keys == VM_KEYS_TABLE)
+            hipLaunchKernelGGL(k_aggregate_indexed_d, dim3(nblk(n)), dim3(WG), 0, s, ws, ks.d_recs, ks.tsize, ks.d_idx, ks.d_off, d.k, MBLS_MODE_VERIFY, st_set, n);
+        else if (keys == VM_KEYS_WIRE)
+            launch_aggregate(ws, ks.d_pks, ks.d_off, d.k, ks.fmt, MBLS_MODE_VERIFY, st_set, n, s);
+        hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, keys == VM_KEYS_APKS ? d.d_apks : (const uint8_t*)nullptr, d_rands, st_set, n);
         if (map) hipLaunchKernelGGL(k_vmb_set_map, dim3(nblk(B)), dim3(WG), 0, s_sig, d_boff, B, n, map);
         if (2 * n <= c->coop_max_items)      // small calls: the signature chain is what the call waits for -- two lanes per signature
-            hipLaunchKernelGGL(k_blind_sig2_d, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, st_set, n);
+            hipLaunchKernelGGL(k_blind_sig2_d, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, d.sigs_resident ? (const uint8_t*)nullptr : d.d_sigs, d_rands, st_set, n);
         else
-            hipLaunchKernelGGL(k_blind_sig_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, st_set, n);
+            hipLaunchKernelGGL(k_blind_sig_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, d.sigs_resident ? (const uint8_t*)nullptr : d.d_sigs, d_rands, st_set, n);
         if (!longest) longest = d_boff ? n : spb;
         if (loc) hipLaunchKernelGGL(k_vml_keep_sig, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, n, sh);
         for (uint64_t half = 1; half < longest; half *= 2)         // S_b: the per-batch sums of the blinded signatures, left at the head of each range
             hipLaunchKernelGGL(k_g2_seg_tree_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, (const uint32_t*)map, d_boff, spb, B, n, half);
-        if (!(hash_enqueued && fork) && !hash_first) launch_hash(c, ws, d_msgs, msg_len, d_moff, st_set, n, s_msg, pair_hash);
+        if (!(d.hash_enqueued && fork) && !hash_first) launch_hash(c, ws, d.ms.d_msgs, d.ms.msg_len, d.ms.d_moff, st_set, n, s_msg, pair_hash);
     }
     if (fork) {
         HIPCHK(c, hipEventRecord(c->hs_ev2, s_sig)); HIPCHK(c, hipEventRecord(c->hs_ev3, s_msg));
@@ -4818,7 +4787,7 @@ static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, cons
     else hipLaunchKernelGGL(k_vmb_final, dim3(nblk(B)), dim3(WG), 0, s, wv, st_batch, d_results, B);
     if (loc && n) {
         hipLaunchKernelGGL(k_vml_mark, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)map, d_boff, spb, B, n, (const uint32_t*)st_set, (const uint32_t*)owned,
-                           (const uint8_t*)d_results, cand, loc->d_set_results, loc->d_set_status, sh);
+                           (const uint8_t*)d_results, cand, d.d_set_results, d.d_set_status, sh);
         // the candidates' Miller loops over the shadow items, cut at rounds as launch_miller_single cuts: whole rounds, then the rest in the form its size allows
         const uint64_t R = c->round_items;
         const uint64_t full = n > R ? (n / R) * R : 0, rest = n - full;
@@ -4831,9 +4800,9 @@ static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, cons
         }
         hipLaunchKernelGGL(k_vml_product, dim3(nblk(n)), dim3(WG), 0, s, ws, n, sh, (const uint32_t*)cand);
         if (n <= c->split_max_items && 2 * n <= c->round_items)
-            hipLaunchKernelGGL(k_vml_final2, dim3(nblk(2 * n)), dim3(WG), 0, s, ws, (const uint32_t*)st_set, (const uint32_t*)cand, loc->d_set_results, loc->d_set_status, n);
+            hipLaunchKernelGGL(k_vml_final2, dim3(nblk(2 * n)), dim3(WG), 0, s, ws, (const uint32_t*)st_set, (const uint32_t*)cand, d.d_set_results, d.d_set_status, n);
         else
-            hipLaunchKernelGGL(k_vml_final, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)st_set, (const uint32_t*)cand, loc->d_set_results, loc->d_set_status, n);
+            hipLaunchKernelGGL(k_vml_final, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)st_set, (const uint32_t*)cand, d.d_set_results, d.d_set_status, n);
     }
     HIPCHK(c, hipGetLastError());
     return ws_release(c, s);
@@ -4841,34 +4810,31 @@ static int vmb_impl(mbls_ctx* c, const uint8_t* d_sigs, const vmb_keys& ks, cons
 extern "C" int mbls_verify_multiple_batches_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_pks, int pk_format,
         const uint32_t* d_pk_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n,
         const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint8_t* d_results, uint32_t* d_status, void* stream) {
-    vmb_keys ks; ks.d_apks = d_apks;
-    if (!d_apks) { ks.d_pks = d_pks; ks.pk_format = pk_format; ks.d_pk_offsets = d_pk_offsets; ks.k = k; }
-    return vmb_impl(c, d_sigs, ks, d_msgs, msg_len, d_moff, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, 0, d_results, d_status, stream);
+    const vm_call d = vm_sets(d_sigs, d_rands, n).msgs(msgs_per_item(d_msgs, msg_len, d_moff)).batches(d_batch_offsets, sets_per_batch, n_batches, 0).out(d_results, d_status);
+    return vmb_impl(c, d_apks ? d.keys_apks(d_apks) : d.keys(keys_wire(d_pks, pk_format, d_pk_offsets), k), stream);
 }
 extern "C" int mbls_verify_multiple_batches_indexed_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx, const uint32_t* d_offsets,
         uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n, const uint32_t* d_batch_offsets,
         uint32_t sets_per_batch, uint64_t n_batches, uint8_t* d_results, uint32_t* d_status, void* stream) {
     if (!c || !t) return MBLS_ERR_ARGUMENT;
-    vmb_keys ks; ks.tab = t; ks.d_idx = d_key_idx; ks.d_pk_offsets = d_offsets; ks.k = k;
-    return vmb_impl(c, d_sigs, ks, d_msgs, msg_len, d_moff, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, 0, d_results, d_status, stream);
+    return vmb_impl(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_table(t, d_key_idx, d_offsets), k).msgs(msgs_per_item(d_msgs, msg_len, d_moff))
+                           .batches(d_batch_offsets, sets_per_batch, n_batches, 0).out(d_results, d_status), stream);
 }
 extern "C" int mbls_verify_multiple_batches_locate_device(mbls_ctx* c, const uint8_t* d_sigs, const uint8_t* d_apks, const uint8_t* d_pks, int pk_format,
         const uint32_t* d_pk_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n,
         const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint8_t* d_results, uint32_t* d_status, uint8_t* d_set_results,
         uint32_t* d_set_status, void* stream) {
-    vmb_keys ks; ks.d_apks = d_apks;
-    if (!d_apks) { ks.d_pks = d_pks; ks.pk_format = pk_format; ks.d_pk_offsets = d_pk_offsets; ks.k = k; }
-    vmb_locate loc; loc.d_set_results = d_set_results; loc.d_set_status = d_set_status;
-    return vmb_impl(c, d_sigs, ks, d_msgs, msg_len, d_moff, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, 0, d_results, d_status, stream, false, false, &loc);
+    const vm_call d = vm_sets(d_sigs, d_rands, n).msgs(msgs_per_item(d_msgs, msg_len, d_moff)).batches(d_batch_offsets, sets_per_batch, n_batches, 0).out(d_results, d_status)
+                          .out_sets(d_set_results, d_set_status);
+    return vmb_impl(c, d_apks ? d.keys_apks(d_apks) : d.keys(keys_wire(d_pks, pk_format, d_pk_offsets), k), stream);
 }
 extern "C" int mbls_verify_multiple_batches_locate_indexed_device(mbls_ctx* c, const mbls_keytable* t, const uint8_t* d_sigs, const uint32_t* d_key_idx,
         const uint32_t* d_offsets, uint32_t k, const uint8_t* d_msgs, uint32_t msg_len, const uint64_t* d_moff, const uint64_t* d_rands, uint64_t n,
         const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint8_t* d_results, uint32_t* d_status, uint8_t* d_set_results,
         uint32_t* d_set_status, void* stream) {
     if (!c || !t) return MBLS_ERR_ARGUMENT;
-    vmb_keys ks; ks.tab = t; ks.d_idx = d_key_idx; ks.d_pk_offsets = d_offsets; ks.k = k;
-    vmb_locate loc; loc.d_set_results = d_set_results; loc.d_set_status = d_set_status;
-    return vmb_impl(c, d_sigs, ks, d_msgs, msg_len, d_moff, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, 0, d_results, d_status, stream, false, false, &loc);
+    return vmb_impl(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_table(t, d_key_idx, d_offsets), k).msgs(msgs_per_item(d_msgs, msg_len, d_moff))
+                           .batches(d_batch_offsets, sets_per_batch, n_batches, 0).out(d_results, d_status).out_sets(d_set_results, d_set_status), stream);
 }
 // what a locate call reserves before its first kernel (include/mbls.h): mbls_vml.h's figure under the limits' choice of the message phase
 extern "C" uint64_t mbls_plan_locate_workspace_items(const mbls_limits* limits, uint64_t n_sets, uint64_t n_batches) {
@@ -4877,62 +4843,85 @@ extern "C" uint64_t mbls_plan_locate_workspace_items(const mbls_limits* limits, 
     return vml_workspace_items(n_sets, n_batches, pair_hash);
 }
 // the host checks shared by the two host entries: the batch table (first 0, non-decreasing, last n) or the uniform count, the message table, the buffers
-static int vmb_host_check(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, uint64_t n,
-                          const uint32_t* boff, uint32_t spb, uint64_t B, const uint8_t* results, uint64_t* longest) {
-    if (!results) ARGFAIL(c, "null results");
+static int vmb_host_check(mbls_ctx* c, const vm_host& h, uint64_t* longest) {
+    const uint64_t n = h.n, B = h.B; const uint32_t* const boff = h.boff; const uint64_t* const moff = h.ms.d_moff;
+    if (!h.result) ARGFAIL(c, "null results");
     if (n > 0xFFFFFFFEull || B > 0xFFFFFFFEull) ARGFAIL(c, "set and batch indices are 32-bit");
     if (boff) { if (!vmb_offsets_ok(boff, B, n, longest)) ARGFAIL(c, "batch_offsets must start at 0, be non-decreasing and end at n_sets"); }
-    else { if ((uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch"); *longest = spb; }
+    else { if ((uint64_t)h.spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch"); *longest = h.spb; }
     if (moff && !msg_offsets_ok(moff, n)) ARGFAIL(c, "msg_offsets must be non-decreasing, messages below 2^32 bytes");
-    const size_t msg_total = moff ? (size_t)(moff[n] - moff[0]) : (size_t)msg_len * n;
-    if (n && (!sigs96 || !apks96 || (!msgs && msg_total))) ARGFAIL(c, "null buffer");
+    const size_t msg_total = moff ? (size_t)(moff[n] - moff[0]) : (size_t)h.ms.msg_len * n;
+    if (n && (!h.sigs96 || !h.apks96 || (!h.ms.d_msgs && msg_total))) ARGFAIL(c, "null buffer");
     return MBLS_OK;
 }
 // locate: the sets' answers as well (set_results required, set_status optional), staged behind one another in one buffer: n words, then n bytes
-static int vmb_host_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
-        const uint64_t* rands, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, uint32_t* status, bool locate, uint8_t* set_results,
-        uint32_t* set_status) {
+static int vmb_host_impl(mbls_ctx* c, const vm_host& h) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
+    const uint64_t n = h.n, B = h.B; const uint64_t* const moff = h.ms.d_moff;
     if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
     uint64_t longest = 0;
-    int rc = vmb_host_check(c, sigs96, apks96, msgs, msg_len, moff, n, boff, spb, B, results, &longest); if (rc) return rc;
-    if (locate && !set_results) ARGFAIL(c, "null set results");
-    if (n && !rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
+    int rc = vmb_host_check(c, h, &longest); if (rc) return rc;
+    if (h.locate && !h.set_results) ARGFAIL(c, "null set results");
+    if (n && !h.rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t msg_first = moff ? moff[0] : 0;
-    const size_t msg_total = moff ? (size_t)(moff[n] - moff[0]) : (size_t)msg_len * n;
+    const size_t msg_total = moff ? (size_t)(moff[n] - moff[0]) : (size_t)h.ms.msg_len * n;
     sbuf ds(c, 0), da(c, 1), dm(c, 2), dr(c, 3), dbo(c, 5), dmo(c, 6), dres(c, 7), dst(c, 8);
-    HIPCHK(c, ds.up(sigs96, 96 * n)); HIPCHK(c, da.up(apks96, 96 * n)); HIPCHK(c, dm.up(msgs ? msgs + msg_first : nullptr, msg_total)); HIPCHK(c, dr.up(rands, 8 * n));
-    if (boff) HIPCHK(c, dbo.up(boff, 4 * (B + 1)));
+    HIPCHK(c, ds.up(h.sigs96, 96 * n)); HIPCHK(c, da.up(h.apks96, 96 * n)); HIPCHK(c, dm.up(h.ms.d_msgs ? h.ms.d_msgs + msg_first : nullptr, msg_total));
+    HIPCHK(c, dr.up(h.rands, 8 * n));
+    if (h.boff) HIPCHK(c, dbo.up(h.boff, 4 * (B + 1)));
     if (moff) HIPCHK(c, dmo.up(moff, 8 * (n + 1)));
     HIPCHK(c, dres.alloc(B)); HIPCHK(c, dst.alloc(4 * B));
     sbuf dset(c, 4);
-    vmb_locate loc;
-    if (locate) { HIPCHK(c, dset.alloc(5 * n)); loc.d_set_status = dset.as<uint32_t>(); loc.d_set_results = dset.as<uint8_t>() + 4 * n; }
-    vmb_keys ks; ks.d_apks = da.as<uint8_t>();
-    rc = vmb_impl(c, ds.as<uint8_t>(), ks, dm.as<uint8_t>() - msg_first, msg_len, moff ? dmo.as<uint64_t>() : nullptr, dr.as<uint64_t>(), n,
-                  boff ? dbo.as<uint32_t>() : nullptr, spb, B, longest ? longest : 1, dres.as<uint8_t>(), dst.as<uint32_t>(), c->hs_a, false, false,
-                  locate ? &loc : nullptr);
+    vm_call d = vm_sets(ds.as<uint8_t>(), dr.as<uint64_t>(), n).keys_apks(da.as<uint8_t>())
+                    .msgs(msgs_per_item(dm.as<uint8_t>() - msg_first, h.ms.msg_len, moff ? dmo.as<uint64_t>() : nullptr))
+                    .batches(h.boff ? dbo.as<uint32_t>() : nullptr, h.spb, B, 0).counted(longest ? longest : 1).out(dres.as<uint8_t>(), dst.as<uint32_t>());
+    if (h.locate) { HIPCHK(c, dset.alloc(5 * n)); d = d.out_sets(dset.as<uint8_t>() + 4 * n, dset.as<uint32_t>()); }
+    rc = vmb_impl(c, d, c->hs_a);
     if (rc) { vm_rng_drain(c); return rc; }
     HIPCHK(c, hipStreamSynchronize(c->hs_a));
     c->ws_pending = false;
-    HIPCHK(c, dres.down(results, B));
-    if (status) HIPCHK(c, dst.down(status, 4 * B));
-    if (locate) {
-        HIPCHK(c, hipMemcpy(set_results, loc.d_set_results, n, hipMemcpyDeviceToHost));
-        if (set_status) HIPCHK(c, hipMemcpy(set_status, loc.d_set_status, 4 * n, hipMemcpyDeviceToHost));
+    HIPCHK(c, dres.down(h.result, B));
+    if (h.status) HIPCHK(c, dst.down(h.status, 4 * B));
+    if (h.locate) {
+        HIPCHK(c, hipMemcpy(h.set_results, d.d_set_results, n, hipMemcpyDeviceToHost));
+        if (h.set_status) HIPCHK(c, hipMemcpy(h.set_status, d.d_set_status, 4 * n, hipMemcpyDeviceToHost));
     }
     return MBLS_OK;
 }
 extern "C" int mbls_verify_multiple_batches(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
         const uint64_t* rands, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, uint32_t* status) {
-    return vmb_host_impl(c, sigs96, apks96, msgs, msg_len, moff, rands, n, boff, spb, B, results, status, false, nullptr, nullptr);
+    return vmb_host_impl(c, vm_host_sets(sigs96, n).keys_apks(apks96).msgs(msgs_per_item(msgs, msg_len, moff)).scalars(rands).batches(boff, spb, B).out(results, status));
 }
 extern "C" int mbls_verify_multiple_batches_locate(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
         const uint64_t* rands, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, uint32_t* status, uint8_t* set_results,
         uint32_t* set_status) {
-    return vmb_host_impl(c, sigs96, apks96, msgs, msg_len, moff, rands, n, boff, spb, B, results, status, true, set_results, set_status);
+    return vmb_host_impl(c, vm_host_sets(sigs96, n).keys_apks(apks96).msgs(msgs_per_item(msgs, msg_len, moff)).scalars(rands).batches(boff, spb, B).out(results, status)
+                                .out_sets(set_results, set_status));
+}
+// the second half of the batches' _rng entries, once the verdicts of the signature phase are in st: reach[b] for every batch, `draw` asked ONCE for exactly the
+// scalars the reference's loops would have drawn (mbls_vmr.h), spread over the sets and uploaded to d_rands; the host copies are zeroed behind the upload
+static int vmb_rng_scalars(mbls_ctx* c, const vm_host& h, const uint32_t* st, std::vector<uint64_t>& reach, sbuf& dr) {
+    std::vector<uint64_t> rands, drawn;
+    try { rands.resize(h.n); drawn.resize(h.n); reach.resize(h.B); } catch (...) { vm_rng_drain(c); ARGFAIL(c, "out of host memory"); }
+    const uint64_t total = vmr_plan(st, h.boff, h.spb, h.B, reach.data());
+    if (total) h.draw(h.user, drawn.data(), total);
+    vmr_spread(drawn.data(), reach.data(), h.boff, h.spb, h.B, rands.data());
+    const hipError_t e = dr.up(rands.data(), 8 * h.n);
+    std::fill(rands.begin(), rands.end(), 0); std::fill(drawn.begin(), drawn.end(), 0);
+    if (e != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
+    return MBLS_OK;
+}
+// ... and of their locate forms, once the call has run: the sets' answers come down, those at or behind their batch's reach are closed on the host (vmr_close)
+static int vmb_rng_sets_down(mbls_ctx* c, const vm_host& h, const vm_call& d, const uint32_t* st, const std::vector<uint64_t>& reach) {
+    std::vector<uint32_t> sst;
+    try { sst.resize(h.n); } catch (...) { ARGFAIL(c, "out of host memory"); }
+    HIPCHK(c, hipMemcpy(h.set_results, d.d_set_results, h.n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(sst.data(), d.d_set_status, 4 * h.n, hipMemcpyDeviceToHost));
+    vmr_close(st, reach.data(), h.boff, h.spb, h.B, h.set_results, sst.data());
+    if (h.set_status) memcpy(h.set_status, sst.data(), 4 * h.n);
+    return MBLS_OK;
 }
 // The reference's order, generalised to B batches: B consecutive reference calls sharing one generator test batch b's signatures one by one and draw a scalar
 // for every set in front of its first signature outside G2 (all of its sets when there is none), batch after batch (src/aggregates.rs:272-287). Here the
@@ -4941,77 +4930,48 @@ extern "C" int mbls_verify_multiple_batches_locate(mbls_ctx* c, const uint8_t* s
 // sets behind the bad one never had a scalar drawn and get the scalar 1, which changes nothing (the batch is rejected whatever its pairing product is).
 // locate: the sets' answers as well. A set at or behind its batch's first signature outside G2 has no scalar (the reference never draws one): it cannot be
 // examined -- its answer is 0 and its word what the signature phase found, set on the host from the verdicts phase 1 read back.
-static int vmb_rng_impl(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
-        uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, mbls_scalar_source draw, void* user, bool locate, uint8_t* set_results,
-        uint32_t* set_status) {
+static int vmb_rng_impl(mbls_ctx* c, const vm_host& h) {
     if (!c) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
+    const uint64_t n = h.n, B = h.B;
     if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
     uint64_t longest = 0;
-    int rc = vmb_host_check(c, sigs96, apks96, msgs, msg_len, moff, n, boff, spb, B, results, &longest); if (rc) return rc;
-    if (locate && !set_results) ARGFAIL(c, "null set results");
-    if (n == 0) { memset(results, 1, B); return MBLS_OK; }                  // empty iterators: true, the generator untouched
-    if (!draw) ARGFAIL(c, "null scalar source");
-    std::vector<uint64_t> rands, drawn; std::vector<uint32_t> st;
-    try { rands.resize(n); drawn.resize(n); st.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
+    int rc = vmb_host_check(c, h, &longest); if (rc) return rc;
+    if (h.locate && !h.set_results) ARGFAIL(c, "null set results");
+    if (n == 0) { memset(h.result, 1, B); return MBLS_OK; }                 // empty iterators: true, the generator untouched
+    if (!h.draw) ARGFAIL(c, "null scalar source");
+    std::vector<uint32_t> st; std::vector<uint64_t> reach;
+    try { st.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
     HIPCHK(c, hipSetDevice(c->device));
     // everything that may allocate comes before the first kernel: the workspace of the WHOLE call (phase 1 alone would reserve less, and growing it later would
     // lose the decoded signatures), the staging of the table, the results and the map
     const bool pair_hash = n <= c->split_max_items && 2 * n <= c->round_items;
-    rc = mbls_ctx_reserve(c, locate ? vml_workspace_items(n, B, pair_hash) : vmb_workspace_items(n, B, pair_hash)); if (rc) return rc;
+    rc = mbls_ctx_reserve(c, h.locate ? vml_workspace_items(n, B, pair_hash) : vmb_workspace_items(n, B, pair_hash)); if (rc) return rc;
     sbuf dbo(c, 5), dres(c, 7), dmap(c, 9), dset(c, 8);
-    if (boff) { HIPCHK(c, dbo.up(boff, 4 * (B + 1))); HIPCHK(c, dmap.alloc(4 * n)); }
+    if (h.boff) { HIPCHK(c, dbo.up(h.boff, 4 * (B + 1))); HIPCHK(c, dmap.alloc(4 * n)); }
     HIPCHK(c, dres.alloc(B));
-    vmb_locate loc;
-    if (locate) { HIPCHK(c, dset.alloc(5 * n)); loc.d_set_status = dset.as<uint32_t>(); loc.d_set_results = dset.as<uint8_t>() + 4 * n; }
+    vm_call d;
+    if (h.locate) { HIPCHK(c, dset.alloc(5 * n)); d = d.out_sets(dset.as<uint8_t>() + 4 * n, dset.as<uint32_t>()); }
     vm_rng_stage g(c);
-    rc = vm_rng_phase1(c, g, sigs96, apks96, msgs, msg_len, moff, n, 8, st.data()); if (rc) return rc;
-    uint64_t total = 0;
-    std::vector<uint64_t> reach;
-    try { reach.resize(B); } catch (...) { vm_rng_drain(c); ARGFAIL(c, "out of host memory"); }
-    for (uint64_t b = 0; b < B; b++) {
-        const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
-        uint64_t r = hi;
-        for (uint64_t i = lo; i < hi; i++) if (st[i] & (MBLS_ST_BAD_SIG_ENCODING | MBLS_ST_SIG_NOT_IN_G2)) { r = i; break; }
-        reach[b] = r - lo; total += r - lo;
-    }
-    if (total) draw(user, drawn.data(), total);
-    uint64_t pos = 0;
-    for (uint64_t b = 0; b < B; b++) {
-        const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
-        for (uint64_t i = lo; i < hi; i++) rands[i] = i - lo < reach[b] ? drawn[pos++] : 1;
-    }
-    hipError_t e = g.dr.up(rands.data(), 8 * n);
-    std::fill(rands.begin(), rands.end(), 0); std::fill(drawn.begin(), drawn.end(), 0);
-    if (e != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
-    vmb_keys ks; ks.d_apks = g.da.as<uint8_t>();
-    rc = vmb_impl(c, nullptr, ks, g.d_msgs, msg_len, g.d_moff, g.dr.as<uint64_t>(), n, boff ? dbo.as<uint32_t>() : nullptr, spb, B, longest ? longest : 1,
-                  dres.as<uint8_t>(), nullptr, c->hs_a, true, true, locate ? &loc : nullptr);
+    rc = vm_rng_phase1(c, g, h, 8, st.data(), &d); if (rc) return rc;
+    rc = vmb_rng_scalars(c, h, st.data(), reach, g.dr); if (rc) return rc;
+    rc = vmb_impl(c, d.second_half(g.dr.as<uint64_t>(), true).batches(h.boff ? dbo.as<uint32_t>() : nullptr, h.spb, B, 0).counted(longest ? longest : 1)
+                      .out(dres.as<uint8_t>(), nullptr), c->hs_a);
     if (rc) { vm_rng_drain(c); return rc; }
     if (hipStreamSynchronize(c->hs_a) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
     c->ws_pending = false;
-    HIPCHK(c, dres.down(results, B));
-    if (locate) {
-        std::vector<uint32_t> sst;
-        try { sst.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
-        HIPCHK(c, hipMemcpy(set_results, loc.d_set_results, n, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(sst.data(), loc.d_set_status, 4 * n, hipMemcpyDeviceToHost));
-        for (uint64_t b = 0; b < B; b++) {
-            const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
-            for (uint64_t i = lo + reach[b]; i < hi; i++) { set_results[i] = 0; sst[i] = st[i]; }
-        }
-        if (set_status) memcpy(set_status, sst.data(), 4 * n);
-    }
-    return MBLS_OK;
+    HIPCHK(c, dres.down(h.result, B));
+    return h.locate ? vmb_rng_sets_down(c, h, d, st.data(), reach) : MBLS_OK;
 }
 extern "C" int mbls_verify_multiple_batches_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff,
         uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, mbls_scalar_source draw, void* user) {
-    return vmb_rng_impl(c, sigs96, apks96, msgs, msg_len, moff, n, boff, spb, B, results, draw, user, false, nullptr, nullptr);
+    return vmb_rng_impl(c, vm_host_sets(sigs96, n).keys_apks(apks96).msgs(msgs_per_item(msgs, msg_len, moff)).source(draw, user).batches(boff, spb, B).out(results, nullptr));
 }
 extern "C" int mbls_verify_multiple_batches_locate_rng(mbls_ctx* c, const uint8_t* sigs96, const uint8_t* apks96, const uint8_t* msgs, uint32_t msg_len,
         const uint64_t* moff, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, uint8_t* set_results, uint32_t* set_status,
         mbls_scalar_source draw, void* user) {
-    return vmb_rng_impl(c, sigs96, apks96, msgs, msg_len, moff, n, boff, spb, B, results, draw, user, true, set_results, set_status);
+    return vmb_rng_impl(c, vm_host_sets(sigs96, n).keys_apks(apks96).msgs(msgs_per_item(msgs, msg_len, moff)).source(draw, user).batches(boff, spb, B).out(results, nullptr)
+                               .out_sets(set_results, set_status));
 }
 
 // ---- B verify_multiple batches in one call over committee bitfields and the resident message table (include/mbls.h, mbls_verify_multiple_batches_committee_msgtable*;
@@ -5046,28 +5006,30 @@ extern "C" int mbls_plan_verify_multiple_batches_committee(const mbls_limits* li
     if (sets_per_batch && (uint64_t)sets_per_batch * n_batches != n_sets) return MBLS_ERR_ARGUMENT;
     plan_vm_batches_committee(*limits, n_sets, n_batches, sets_per_batch, table_size, max_groups, mode, locate != 0, 0, out); return MBLS_OK;
 }
-static int vbg_impl(mbls_ctx* c, const uint8_t* d_sigs, const vm_committee& vc, const mbls_msgtable* mt, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n,
-        const uint32_t* d_boff, uint32_t spb, uint64_t B, uint64_t longest, uint64_t max_groups, uint8_t* d_results, uint32_t* d_status, void* stream,
-        bool sigs_resident = false, const vmb_locate* loc = nullptr) {
-    if (!c || !mt) return MBLS_ERR_ARGUMENT;
+static int vbg_impl(mbls_ctx* c, const vm_call& d, void* stream) {
+    if (!c || !d.mt) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
+    const uint64_t n = d.n, B = d.B, max_groups = d.max_groups; const uint32_t spb = d.spb; const uint32_t* const d_boff = d.d_boff; const uint64_t* const d_rands = d.d_rands;
+    const keysrc& ks = d.ks; const mbls_msgtable* const mt = d.mt; const uint32_t* const d_midx = d.ms.d_idx;
+    uint8_t* const d_results = d.d_result; uint32_t* const d_status = d.d_status_or; const bool loc = d.locate;
+    uint64_t longest = d.longest;
     if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
     if (!d_results) ARGFAIL(c, "null results");
-    if (loc && !loc->d_set_results) ARGFAIL(c, "null set results");
+    if (loc && !d.d_set_results) ARGFAIL(c, "null set results");
     if (n > 0xFFFFFFFEull || B > 0xFFFFFFFEull) ARGFAIL(c, "set and batch indices are 32-bit");
     if (!d_boff && (uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch");
     if (n && !d_rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
-    if (n && ((!d_sigs && !sigs_resident) || !d_midx || !vc.d_cmt_idx || !vc.d_bits)) ARGFAIL(c, "null buffer");
+    if (n && ((!d.d_sigs && !d.sigs_resident) || !d_midx || !ks.d_cmt_idx || !ks.d_bits)) ARGFAIL(c, "null buffer");
     if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const uint64_t T = mt->size;
     mbls_vm_batches_committee_plan vp;
-    plan_vm_batches_committee(ctx_limits(c), n, B, d_boff ? 0u : spb, T, max_groups, c->vm_grouping, loc != nullptr, longest, &vp);
+    plan_vm_batches_committee(ctx_limits(c), n, B, d_boff ? 0u : spb, T, max_groups, c->vm_grouping, loc, longest, &vp);
     const bool grouped = vp.route == MBLS_VM_ROUTE_GROUPED;
     const uint64_t bound = vp.bound, n_miller = vp.miller_items;
     int rc = mbls_ctx_reserve(c, vp.workspace_items); if (rc) return rc;
-    if (n) { rc = reserve_committee(c, n, vc.cmax); if (rc) return rc; }
+    if (n) { rc = reserve_committee(c, n, ks.cmax); if (rc) return rc; }
     if (grouped) { rc = reserve_groups(c, vbg_group_words(n, B)); if (rc) return rc; }
     uint32_t* map = nullptr;
     sbuf dmap(c, 9);
@@ -5078,8 +5040,8 @@ static int vbg_impl(mbls_ctx* c, const uint8_t* d_sigs, const vm_committee& vc, 
     mbls_ws wv = ws; wv.w += tail;                                  // the batches' view: item b of wv = the batch's pair value, item B + b its sets' product
     rc = ws_acquire(c, s); if (rc) return rc;
     rc = msgtable_acquire(c, mt, s); if (rc) return rc;
-    rc = committees_acquire(c, vc.t, s); if (rc) return rc;
-    rc = table_acquire(c, vc.kt, s); if (rc) return rc;
+    rc = committees_acquire(c, ks.cmt, s); if (rc) return rc;
+    rc = table_acquire(c, ks.tab, s); if (rc) return rc;
     const uint32_t* const tab = mt->d_tab; const uint64_t tstride = mtb_stride(mt->cap); const uint32_t* const flags = mt->d_flag;
     uint32_t* st_set = c->d_status;                                 // (cap >= n + 2 B words; locate: 2 n + 2 B)
     uint32_t* st_batch = d_status ? d_status : c->d_status + n;
@@ -5092,14 +5054,14 @@ static int vbg_impl(mbls_ctx* c, const uint8_t* d_sigs, const vm_committee& vc, 
         ga.gcount = c->d_hgrp + 5 * gc; ga.goff = ga.gcount + B;   // (goff[0 .. B], then the live word: 2 B + 2 words)
     }
     uint32_t* const d_live = grouped ? ga.goff + B + 1 : nullptr;
-    if (n && !sigs_resident) HIPCHK(c, hipMemsetAsync(st_set, 0, 4 * n, s));          // (resident: cleared before k_sig)
+    if (n && !d.sigs_resident) HIPCHK(c, hipMemsetAsync(st_set, 0, 4 * n, s));          // (resident: cleared before k_sig)
     HIPCHK(c, hipMemsetAsync(c->d_status + n, 0, 8 * B, s));
     if (d_status) HIPCHK(c, hipMemsetAsync(d_status, 0, 4 * B, s));
     if (map) HIPCHK(c, hipMemsetAsync(map, 0xFF, 4 * (n ? n : 1), s));
     HIPCHK(c, hipMemsetAsync(d_results, 0, B, s));                  // false until the tail kernel has spoken (fail closed)
     if (loc && n) {
-        HIPCHK(c, hipMemsetAsync(loc->d_set_results, 0, n, s));
-        if (loc->d_set_status) HIPCHK(c, hipMemsetAsync(loc->d_set_status, 0, 4 * n, s));
+        HIPCHK(c, hipMemsetAsync(d.d_set_results, 0, n, s));
+        if (d.d_set_status) HIPCHK(c, hipMemsetAsync(d.d_set_status, 0, 4 * n, s));
         HIPCHK(c, hipMemsetAsync(cand, 0, 4 * n, s));
     }
     if (grouped) {
@@ -5116,12 +5078,12 @@ static int vbg_impl(mbls_ctx* c, const uint8_t* d_sigs, const vm_committee& vc, 
         // the message phase of the per-set route: every set takes its entry's point (the grouped route reads the table from its Miller items)
         if (!grouped) hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, tab, tstride, flags, d_midx, T, st_set, n);
         // the key phase: the committee source of verify_multiple_impl
-        const uint64_t ls = vc.list_stride();
+        const uint64_t ls = keys_list_stride(ks);
         uint32_t* const cnt = c->d_cmt_cnt; uint32_t* const route = c->d_cmt_cnt + c->cmt_items;
-        hipLaunchKernelGGL(k_vmc_expand, dim3((unsigned)n), dim3(WG), 0, s, vc.d_crecs, vc.ccount, vc.d_members, vc.d_cmt_idx, vc.d_bits, vc.bits_stride, c->cmt_route_mode,
+        hipLaunchKernelGGL(k_vmc_expand, dim3((unsigned)n), dim3(WG), 0, s, ks.d_crecs, ks.ccount, ks.d_members, ks.d_cmt_idx, ks.d_bits, ks.bits_stride, c->cmt_route_mode,
                            c->d_cmt_list, ls, cnt, route, n);
-        hipLaunchKernelGGL(k_aggregate_vmc_d, dim3(nblk(n)), dim3(WG), 0, s, ws, vc.d_recs, vc.tsize, (const uint32_t*)c->d_cmt_list, ls, (const uint32_t*)cnt, (const uint32_t*)route,
-                           vc.d_crecs, vc.d_cmt_idx, st_set, n);
+        hipLaunchKernelGGL(k_aggregate_vmc_d, dim3(nblk(n)), dim3(WG), 0, s, ws, ks.d_recs, ks.tsize, (const uint32_t*)c->d_cmt_list, ls, (const uint32_t*)cnt, (const uint32_t*)route,
+                           ks.d_crecs, ks.d_cmt_idx, st_set, n);
         hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint8_t*)nullptr, d_rands, st_set, n);
         if (grouped) {      // groups, their offsets, the keys to their positions, the per-group sums: behind the keys on their stream
             mbls_vbg_launch_group(d_midx, T, d_boff, spb, B, n, (const uint32_t*)map, ga, st_set, s);
@@ -5132,9 +5094,9 @@ static int vbg_impl(mbls_ctx* c, const uint8_t* d_sigs, const vm_committee& vc, 
             mbls_vbg_launch_key_trees(wp, (const uint32_t*)ga.rlo, (const uint32_t*)ga.rhi, n, vp.tree_levels, s);
         }
         if (2 * n <= c->coop_max_items)
-            hipLaunchKernelGGL(k_blind_sig2_d, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, st_set, n);
+            hipLaunchKernelGGL(k_blind_sig2_d, dim3(nblk(2 * n)), dim3(WG), 0, s_sig, ws, d.sigs_resident ? (const uint8_t*)nullptr : d.d_sigs, d_rands, st_set, n);
         else
-            hipLaunchKernelGGL(k_blind_sig_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, sigs_resident ? (const uint8_t*)nullptr : d_sigs, d_rands, st_set, n);
+            hipLaunchKernelGGL(k_blind_sig_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, d.sigs_resident ? (const uint8_t*)nullptr : d.d_sigs, d_rands, st_set, n);
         if (loc) hipLaunchKernelGGL(k_vml_keep_sig, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, n, grouped ? shf + n : shf);
         for (uint64_t half = 1; half < longest; half *= 2)         // S_b: the per-batch sums of the blinded signatures, left at the head of each range
             hipLaunchKernelGGL(k_g2_seg_tree_d, dim3(nblk(n)), dim3(WG), 0, s_sig, ws, (const uint32_t*)map, d_boff, spb, B, n, half);
@@ -5179,72 +5141,71 @@ static int vbg_impl(mbls_ctx* c, const uint8_t* d_sigs, const vm_committee& vc, 
     if (loc && n && grouped) {     // phase two of mbls_vsl.h with the set's batch in the place of the call: mark, both pairs' Miller loops, product, final
         mbls_ws wsa = ws; wsa.w += shf;
         mbls_vbg_launch_mark(wsa, tab, tstride, flags, d_midx, T, (const uint32_t*)map, d_boff, spb, B, n, (const uint32_t*)st_set, (const uint32_t*)owned,
-                             (const uint8_t*)d_results, cand, loc->d_set_results, loc->d_set_status, s);
-        vsl_examine(c, ws, n, shf, true, st_set, cand, loc->d_set_results, loc->d_set_status, s);
+                             (const uint8_t*)d_results, cand, d.d_set_results, d.d_set_status, s);
+        vsl_examine(c, ws, n, shf, true, st_set, cand, d.d_set_results, d.d_set_status, s);
     } else if (loc && n) {         // vmb_impl's phase two
         hipLaunchKernelGGL(k_vml_mark, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint32_t*)map, d_boff, spb, B, n, (const uint32_t*)st_set, (const uint32_t*)owned,
-                           (const uint8_t*)d_results, cand, loc->d_set_results, loc->d_set_status, shf);
-        vsl_examine(c, ws, n, shf, false, st_set, cand, loc->d_set_results, loc->d_set_status, s);
+                           (const uint8_t*)d_results, cand, d.d_set_results, d.d_set_status, shf);
+        vsl_examine(c, ws, n, shf, false, st_set, cand, d.d_set_results, d.d_set_status, s);
     }
     HIPCHK(c, hipGetLastError());
     return ws_release(c, s);
 }
-static int vbg_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_stride,
-                      const mbls_msgtable* mt, const uint32_t* d_midx, const uint64_t* d_rands, uint64_t n, const uint32_t* d_boff, uint32_t spb, uint64_t B,
-                      uint64_t max_groups, uint8_t* d_results, uint32_t* d_status, void* stream, const vmb_locate* loc) {
-    if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
+// the device entries: the committee table read at the sizes it has now, then vbg_impl
+static int vbg_device(mbls_ctx* c, vm_call d, void* stream) {
+    if (!c || !d.ks.cmt || !d.mt) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
-    if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
-    vm_committee vc; const int rk = vm_committee_of(c, t, d_cmt_idx, d_bits, bits_stride, true, &vc); if (rk) return rk;
-    return vbg_impl(c, d_sigs, vc, mt, d_midx, d_rands, n, d_boff, spb, B, 0, max_groups, d_results, d_status, stream, false, loc);
+    if (d.mt->c != c) ARGFAIL(c, "message table belongs to another context");
+    const int rk = vm_keys_resolve(c, &d.ks, true); if (rk) return rk;
+    return vbg_impl(c, d, stream);
 }
 extern "C" int mbls_verify_multiple_batches_committee_msgtable_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx,
         const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, const uint32_t* d_batch_offsets,
         uint32_t sets_per_batch, uint64_t n_batches, uint64_t max_groups, uint8_t* d_results, uint32_t* d_status, void* stream) {
-    return vbg_device(c, t, d_sigs, d_cmt_idx, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, max_groups, d_results, d_status,
-                      stream, nullptr);
+    return vbg_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_committees(t, d_cmt_idx, d_bits, bits_stride), 0).msgs_in(mt, d_msg_idx, 0)
+                             .batches(d_batch_offsets, sets_per_batch, n_batches, max_groups).out(d_results, d_status), stream);
 }
 extern "C" int mbls_verify_multiple_batches_committee_msgtable_locate_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_idx,
         const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, const uint32_t* d_batch_offsets,
         uint32_t sets_per_batch, uint64_t n_batches, uint64_t max_groups, uint8_t* d_results, uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status,
         void* stream) {
     if (!d_set_results) return MBLS_ERR_ARGUMENT;
-    vmb_locate loc; loc.d_set_results = d_set_results; loc.d_set_status = d_set_status;
-    return vbg_device(c, t, d_sigs, d_cmt_idx, d_bits, bits_stride, mt, d_msg_idx, d_rands, n, d_batch_offsets, sets_per_batch, n_batches, max_groups, d_results, d_status,
-                      stream, &loc);
+    return vbg_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_committees(t, d_cmt_idx, d_bits, bits_stride), 0).msgs_in(mt, d_msg_idx, 0)
+                             .batches(d_batch_offsets, sets_per_batch, n_batches, max_groups).out(d_results, d_status).out_sets(d_set_results, d_set_status), stream);
 }
 // host buffers, the draw order of vmb_rng_impl: the signatures of ALL batches are decoded and tested first, `draw` is asked once for the scalars of the sets in front
 // of each batch's first signature outside G2, the rest runs without a second subgroup test. A committee id, key index or message index that names nothing, or a batch
 // table that is not sound, refuses the call with nothing queued and the outputs untouched. The host counts the distinct (batch, entry) pairs itself.
-static int vbg_rng_impl(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_stride,
-        const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results, mbls_scalar_source draw, void* user,
-        bool locate, uint8_t* set_results, uint32_t* set_status) {
-    if (!c || !t || !mt) return MBLS_ERR_ARGUMENT;
+static int vbg_rng_impl(mbls_ctx* c, const vm_host& h) {
+    const host_committees* const hc = h.hc; const mbls_msgtable* const mt = h.mt;
+    if (!c || !hc->t || !mt) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
+    const uint64_t n = h.n, B = h.B; const uint32_t spb = h.spb; const uint32_t* const boff = h.boff; const uint32_t* const msg_idx = h.ms.d_idx;
     if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
     if (B == 0) { if (n) ARGFAIL(c, "sets without batches"); return MBLS_OK; }
-    if (!results) ARGFAIL(c, "null results");
-    if (locate && !set_results) ARGFAIL(c, "null set results");
+    if (!h.result) ARGFAIL(c, "null results");
+    if (h.locate && !h.set_results) ARGFAIL(c, "null set results");
     if (n > 0xFFFFFFFEull || B > 0xFFFFFFFEull) ARGFAIL(c, "set and batch indices are 32-bit");
     uint64_t longest = spb;
     if (boff) { if (!vmb_offsets_ok(boff, B, n, &longest)) ARGFAIL(c, "batch_offsets must start at 0, be non-decreasing and end at n_sets"); }
     else if ((uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch");
-    vm_committee vc; const int rk = vm_committee_of(c, t, nullptr, nullptr, bits_stride, false, &vc); if (rk) return rk;
-    if (n == 0) { memset(results, 1, B); return MBLS_OK; }                  // empty iterators: true, the generator untouched
-    if (!sigs96 || !cmt_idx || !bits || !msg_idx) ARGFAIL(c, "null buffer");
-    if (!draw) ARGFAIL(c, "null scalar source");
+    keysrc ks = keys_in_committees(hc->t, nullptr, nullptr, hc->bits_stride);
+    const int rk = vm_keys_resolve(c, &ks, false); if (rk) return rk;
+    if (n == 0) { memset(h.result, 1, B); return MBLS_OK; }                 // empty iterators: true, the generator untouched
+    if (!h.sigs96 || !hc->cmt_idx || !hc->bits || !msg_idx) ARGFAIL(c, "null buffer");
+    if (!h.draw) ARGFAIL(c, "null scalar source");
     const uint64_t T = mt->size;
     for (uint64_t i = 0; i < n; i++) {
-        if (vmc_names_nothing(cmt_idx[i], vc.ccount, vc.tsize))
-            ARGFAIL(c, vmc_is_single(cmt_idx[i]) ? "cmt_idx names no key of the key table" : "cmt_idx names no committee of the table");
+        if (vmc_names_nothing(hc->cmt_idx[i], ks.ccount, ks.tsize))
+            ARGFAIL(c, vmc_is_single(hc->cmt_idx[i]) ? "cmt_idx names no key of the key table" : "cmt_idx names no committee of the table");
         if ((uint64_t)msg_idx[i] >= T) ARGFAIL(c, "msg_idx names no entry of the message table");
     }
-    std::vector<uint64_t> rands, drawn, reach; std::vector<uint32_t> st, seen;
-    try { rands.resize(n); drawn.resize(n); st.resize(n); reach.resize(B); } catch (...) { ARGFAIL(c, "out of host memory"); }
+    std::vector<uint64_t> reach; std::vector<uint32_t> st, seen;
+    try { st.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
     // the distinct (batch, entry) pairs, counted the way the wave counts them: a set without an earlier set of its batch naming the same entry
-    uint64_t groups = 0;
+    uint64_t groups = 0, lo, hi;
     for (uint64_t b = 0; b < B; b++) {
-        const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
+        vmr_batch_range(boff, spb, b, &lo, &hi);
         if (!vbg_batch_grouped(hi - lo)) { groups += hi - lo; continue; }
         try { seen.assign(msg_idx + lo, msg_idx + hi); } catch (...) { ARGFAIL(c, "out of host memory"); }
         std::sort(seen.begin(), seen.end());
@@ -5253,69 +5214,44 @@ static int vbg_rng_impl(mbls_ctx* c, const mbls_committees* t, const uint8_t* si
     HIPCHK(c, hipSetDevice(c->device));
     // everything that may allocate comes before the first kernel: the workspace of the WHOLE call, the committee scratch, the group arrays, the staging
     mbls_vm_batches_committee_plan vp;
-    plan_vm_batches_committee(ctx_limits(c), n, B, boff ? 0u : spb, T, groups, c->vm_grouping, locate, longest, &vp);
+    plan_vm_batches_committee(ctx_limits(c), n, B, boff ? 0u : spb, T, groups, c->vm_grouping, h.locate, longest, &vp);
     int rc = mbls_ctx_reserve(c, vp.workspace_items); if (rc) return rc;
-    rc = reserve_committee(c, n, vc.cmax); if (rc) return rc;
+    rc = reserve_committee(c, n, ks.cmax); if (rc) return rc;
     if (vp.route == MBLS_VM_ROUTE_GROUPED) { rc = reserve_groups(c, vbg_group_words(n, B)); if (rc) return rc; }
     sbuf ds(c, 0), da(c, 1), dr(c, 3), dbo(c, 5), dres(c, 4), dmi(c, 7), dset(c, 8), dmap(c, 9), dci(c, 10);
-    HIPCHK(c, ds.up(sigs96, 96 * n)); HIPCHK(c, da.up(bits, (size_t)bits_stride * n)); HIPCHK(c, dci.up(cmt_idx, 4 * n)); HIPCHK(c, dmi.up(msg_idx, 4 * n));
+    HIPCHK(c, ds.up(h.sigs96, 96 * n)); HIPCHK(c, da.up(hc->bits, (size_t)hc->bits_stride * n)); HIPCHK(c, dci.up(hc->cmt_idx, 4 * n)); HIPCHK(c, dmi.up(msg_idx, 4 * n));
     HIPCHK(c, dr.alloc(8 * n)); HIPCHK(c, dres.alloc(B));
     if (boff) { HIPCHK(c, dbo.up(boff, 4 * (B + 1))); HIPCHK(c, dmap.alloc(4 * n)); }
-    vmb_locate loc;
-    if (locate) { HIPCHK(c, dset.alloc(5 * n)); loc.d_set_status = dset.as<uint32_t>(); loc.d_set_results = dset.as<uint8_t>() + 4 * n; }
-    vc.d_cmt_idx = dci.as<uint32_t>(); vc.d_bits = da.as<uint8_t>();
-    // the signatures: decoded and tested, the verdicts read back (vm_rng_phase1's signature half)
+    ks.d_cmt_idx = dci.as<uint32_t>(); ks.d_bits = da.as<uint8_t>();
+    vm_call d = vm_sets(nullptr, dr.as<uint64_t>(), n).keys(ks, 0).msgs_in(mt, dmi.as<uint32_t>(), 0).second_half(dr.as<uint64_t>(), false)
+                    .batches(boff ? dbo.as<uint32_t>() : nullptr, spb, B, groups).counted(longest ? longest : 1).out(dres.as<uint8_t>(), nullptr);
+    if (h.locate) { HIPCHK(c, dset.alloc(5 * n)); d = d.out_sets(dset.as<uint8_t>() + 4 * n, dset.as<uint32_t>()); }
+    // the signatures: decoded and tested, the verdicts read back
     hipStream_t s = c->hs_a;
     mbls_ws ws; ws.w = c->d_w; ws.stride = c->cap;
     rc = ws_acquire(c, s); if (rc) return rc;
-    if (hipMemsetAsync(c->d_status, 0, 4 * n, s) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
-    if (2 * n <= c->coop_max_items) hipLaunchKernelGGL(k_sig2, dim3(nblk(2 * n)), dim3(WG), 0, s, ws, (const uint8_t*)ds.as<uint8_t>(), c->d_status, (uint64_t)n);
-    else hipLaunchKernelGGL(k_sig, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint8_t*)ds.as<uint8_t>(), c->d_status, (uint64_t)n, 1);
-    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(st.data(), c->d_status, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
-    uint64_t total = 0;
-    for (uint64_t b = 0; b < B; b++) {
-        const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
-        uint64_t r = hi;
-        for (uint64_t i = lo; i < hi; i++) if (st[i] & (MBLS_ST_BAD_SIG_ENCODING | MBLS_ST_SIG_NOT_IN_G2)) { r = i; break; }
-        reach[b] = r - lo; total += r - lo;
-    }
-    if (total) draw(user, drawn.data(), total);
-    uint64_t at = 0;
-    for (uint64_t b = 0; b < B; b++) {
-        const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
-        for (uint64_t i = lo; i < hi; i++) rands[i] = i - lo < reach[b] ? drawn[at++] : 1;
-    }
-    hipError_t e = dr.up(rands.data(), 8 * n);
-    std::fill(rands.begin(), rands.end(), 0); std::fill(drawn.begin(), drawn.end(), 0);
-    if (e != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
-    rc = vbg_impl(c, nullptr, vc, mt, dmi.as<uint32_t>(), dr.as<uint64_t>(), n, boff ? dbo.as<uint32_t>() : nullptr, spb, B, longest ? longest : 1, groups,
-                  dres.as<uint8_t>(), nullptr, s, true, locate ? &loc : nullptr);
+    if (vm_rng_signatures(c, ws, ds.as<uint8_t>(), n, s, false) || hipStreamSynchronize(s) != hipSuccess ||
+        hipMemcpy(st.data(), c->d_status, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
+    rc = vmb_rng_scalars(c, h, st.data(), reach, dr); if (rc) return rc;
+    rc = vbg_impl(c, d, s);
     if (rc) { vm_rng_drain(c); return rc; }
     if (hipStreamSynchronize(s) != hipSuccess) { vm_rng_drain(c); return MBLS_ERR_DEVICE; }
     c->ws_pending = false;
-    HIPCHK(c, dres.down(results, B));
-    if (locate) {
-        std::vector<uint32_t> sst;
-        try { sst.resize(n); } catch (...) { ARGFAIL(c, "out of host memory"); }
-        HIPCHK(c, hipMemcpy(set_results, loc.d_set_results, n, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(sst.data(), loc.d_set_status, 4 * n, hipMemcpyDeviceToHost));
-        for (uint64_t b = 0; b < B; b++) {
-            const uint64_t lo = boff ? boff[b] : (uint64_t)spb * b, hi = boff ? boff[b + 1] : lo + spb;
-            for (uint64_t i = lo + reach[b]; i < hi; i++) { set_results[i] = 0; sst[i] = st[i]; }
-        }
-        if (set_status) memcpy(set_status, sst.data(), 4 * n);
-    }
-    return MBLS_OK;
+    HIPCHK(c, dres.down(h.result, B));
+    return h.locate ? vmb_rng_sets_down(c, h, d, st.data(), reach) : MBLS_OK;
 }
 extern "C" int mbls_verify_multiple_batches_committee_msgtable_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_idx, const uint8_t* bits,
         uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B, uint8_t* results,
         mbls_scalar_source draw, void* user) {
-    return vbg_rng_impl(c, t, sigs96, cmt_idx, bits, bits_stride, mt, msg_idx, n, boff, spb, B, results, draw, user, false, nullptr, nullptr);
+    const host_committees hc = {t, cmt_idx, bits, bits_stride};
+    return vbg_rng_impl(c, vm_host_sets(sigs96, n).keys(&hc).msgs_in(mt, msg_idx).source(draw, user).batches(boff, spb, B).out(results, nullptr));
 }
 extern "C" int mbls_verify_multiple_batches_committee_msgtable_locate_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_idx,
         const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B,
         uint8_t* results, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user) {
-    return vbg_rng_impl(c, t, sigs96, cmt_idx, bits, bits_stride, mt, msg_idx, n, boff, spb, B, results, draw, user, true, set_results, set_status);
+    const host_committees hc = {t, cmt_idx, bits, bits_stride};
+    return vbg_rng_impl(c, vm_host_sets(sigs96, n).keys(&hc).msgs_in(mt, msg_idx).source(draw, user).batches(boff, spb, B).out(results, nullptr)
+                               .out_sets(set_results, set_status));
 }
 // test probe: steps 1-2 of the grouped route alone (k_vmb_set_map for a ragged table, k_vbg_group, k_vms_scan) on caller-given indices and batch table -- any
 // table, faulty ones included -- with host buffers; every array over the sets has n_sets words, group_count n_batches, group_off n_batches + 1
@@ -5600,8 +5536,10 @@ extern "C" int mbls_multi_verify_multiple_aggregate_signatures_rng(mbls_multi* m
         if (hipSetDevice(c->device) != hipSuccess) rcs[g] = MBLS_ERR_DEVICE;
         if (!rcs[g] && !m->d_rec_all[g] && hipMalloc(&m->d_rec_all[g], G * MBLS_VM_PARTIAL_BYTES) != hipSuccess) { m->d_rec_all[g] = nullptr; rcs[g] = MBLS_ERR_DEVICE; }
         // (offset tables are absolute: phase 1 stages the shard's message bytes from its first offset on)
-        if (!rcs[g]) rcs[g] = vm_rng_phase1(c, sg, sigs96 + 96 * lo, apks96 + 96 * lo, moff ? msgs : (msgs ? msgs + (uint64_t)msg_len * lo : nullptr), msg_len,
-                                            moff ? moff + lo : nullptr, cnt, MBLS_VM_PARTIAL_BYTES, stw.data() + lo);
+        vm_call d;
+        if (!rcs[g]) rcs[g] = vm_rng_phase1(c, sg, vm_host_sets(sigs96 + 96 * lo, cnt).keys_apks(apks96 + 96 * lo)
+                                                .msgs(msgs_per_item(moff ? msgs : (msgs ? msgs + (uint64_t)msg_len * lo : nullptr), msg_len, moff ? moff + lo : nullptr)),
+                                            MBLS_VM_PARTIAL_BYTES, stw.data() + lo, &d);
         int mine;
         {
             std::unique_lock<std::mutex> ul(bm);
@@ -5610,7 +5548,7 @@ extern "C" int mbls_multi_verify_multiple_aggregate_signatures_rng(mbls_multi* m
             mine = go;
         }
         if (mine < 0 || rcs[g]) { if (cnt) vm_rng_drain(c); return; }
-        rcs[g] = vm_rng_phase2(c, sg, msg_len, rands.data() + lo, cnt, true);
+        rcs[g] = vm_rng_phase2(c, sg, rands.data() + lo, true, d);
         const bool synced = hipStreamSynchronize(c->hs_a) == hipSuccess;
         (void)hipStreamSynchronize(c->hs_b); (void)hipStreamSynchronize(c->hs_c);
         c->ws_pending = false;
@@ -5629,10 +5567,8 @@ extern "C" int mbls_multi_verify_multiple_aggregate_signatures_rng(mbls_multi* m
         cv.wait(ul, [&] { return arrived == G; });
     }
     for (uint64_t g = 0; g < G; g++) if (rcs[g]) proceed = false;
-    size_t reached = n;
     if (proceed) {
-        for (size_t i = 0; i < n; i++)
-            if (stw[i] & (MBLS_ST_BAD_SIG_ENCODING | MBLS_ST_SIG_NOT_IN_G2)) { reached = i; break; }
+        const size_t reached = (size_t)vmr_reach(stw.data(), 0, n);
         if (reached) draw(user, rands.data(), (uint64_t)reached);
         if (reached < n) proceed = false;                                   // :273-275
     }

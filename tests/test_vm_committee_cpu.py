@@ -130,7 +130,7 @@ def test_the_committee_source_plans_with_the_msgtable_functions():
         src = f.read()
     impl = src[src.index("static int verify_multiple_impl("):src.index("// verify_multiple over sets named by indices into a resident key table")]
     assert impl.count("mbls_ctx_reserve(") == 1 and impl.count("vm_shared_plan_and_reserve(") == 1          # the one reservation of the workspace, source or no source
-    assert "reserve_committee(c, n, vc->cmax)" in impl
+    assert "reserve_committee(c, n, ks.cmax)" in impl
     # the same values, whatever the sets' kinds: the functions do not know the key source
     L = N.default_limits()
     for n, T, named, mode in ((1, 1, 0, 0), (65, 3, 0, 0), (200, 8, 3, 1), (65536, 512, 0, 0), (65536, 512, 512, 2), (1024, 8, 8, 0)):

@@ -224,4 +224,4 @@ def test_locate_mode_adds_to_the_sequence_and_changes_none_of_it():
     assert "k_vsl_mark" not in head and "vsl_examine" not in head and "k_vml_mark" not in head
     assert "k_vsl_mark" in tail and "k_vml_mark" in tail and tail.count("vsl_examine(") == 2
     assert "loc && !grouped ? shf : 0" in body                                            # the Miller values are kept on the per-set route only, in locate mode only
-    assert "sh.locate ? vsl_workspace_items(" in src and ": sh.vp.workspace_items)" in src
+    assert "d.locate ? vsl_workspace_items(" in src and ": sh.vp.workspace_items)" in src
