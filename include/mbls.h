@@ -531,8 +531,8 @@ int mbls_stream_submit_msgidx(mbls_stream* s, const uint8_t* sigs, const uint32_
  *   committee would make every later round fail the entry's argument check. Destroying the stream releases both interlocks. DESTROY A STREAM BEFORE ITS TABLES.
  * mbls_stream_submit[_device] and mbls_stream_submit_msgidx[_device] on such a stream, and the two entries below on any other stream, are MBLS_ERR_ARGUMENT; the
  *   message names the right entry.
- * OUT OF SCOPE: committee spans in a stream, per-item message bytes or a shared message list in a committee stream, verify_multiple in a stream, the mbls_multi
- *   handle. */
+ * OUT OF SCOPE: committee spans in a stream, per-item message bytes or a shared message list in a committee stream, the mbls_multi handle. (verify_multiple in a
+ *   stream: mbls_stream_create_vm_committee, below.) */
 int mbls_stream_create_committee(mbls_ctx* ctx, mbls_committees* committees, mbls_msgtable* mt, uint32_t bits_stride, const mbls_stream_opts* opts, mbls_stream** out);
 int mbls_stream_submit_committee_device(mbls_stream* s, const uint8_t* d_sigs, const uint32_t* d_msg_idx, const uint32_t* d_cmt_idx, const uint8_t* d_bits,
                                         uint32_t bits_len, uint64_t n, uint8_t* d_results, uint64_t* d_bitmap, uint32_t* d_status, void* stream, uint64_t* ticket);
@@ -550,6 +550,46 @@ typedef struct mbls_stream_call_shape { uint64_t n; uint32_t k, msg_len; const u
 typedef struct mbls_stream_piece { uint64_t call, first, items, round, round_first; } mbls_stream_piece;
 int mbls_stream_cut(const mbls_stream_opts* opts, const mbls_stream_call_shape* calls, uint64_t n_calls,
                     mbls_stream_piece* out, uint64_t max_pieces, uint64_t* n_pieces);
+/* A verify_multiple stream over a committee table and a message table: the gossip caller, many threads each holding ONE small verify_multiple batch. A CALL IS A
+ * BATCH; a ROUND is one call of mbls_verify_multiple_batches_committee_msgtable_locate_device (below, "MANY verify_multiple BATCHES PER CALL") over the round's
+ * slot, with a ragged batch table the launcher builds on the host. Binding to the tables, policies, depth, threading, ticket order, flush / wait / query, lifetimes
+ * and mbls_stream_get_stats are the committee stream's above, unchanged; create refuses what mbls_stream_create_committee refuses.
+ * CALL. n_sets >= 1 sets, those of mbls_verify_multiple_committee_msgtable_locate_device: set i is cmt_idx[i] (a committee id, or MBLS_VM_SET_SINGLE_KEY | key
+ *   index), the bits_len bytes at bits + bits_len * i, msg_idx[i] and the scalar rands[i]. bits_len is a value of the CALL, 0 .. bits_stride, at any alignment;
+ *   bits_len = 0 allows bits = NULL (every field is zero: a batch of single-key sets only). The scalars come from the caller, as in every _device entry: NULL is
+ *   MBLS_ERR_ARGUMENT, a zero scalar rejects its call with MBLS_ST_BAD_SCALAR. Outputs: one byte (required) and one optional status word per CALL, n_sets bytes and
+ *   n_sets optional words per SET (both set arrays may be NULL). n_sets = 0 is MBLS_ERR_ARGUMENT and the call gets no ticket.
+ * RESULT. Every output of a call is byte for byte what mbls_verify_multiple_batches_committee_msgtable_locate_device writes for that call alone as one batch
+ *   (n_batches = 1, sets_per_batch = n_sets) on the same signatures, ids, indices and scalars with every field ZERO-EXTENDED to bits_stride -- under every mode of
+ *   mbls_ctx_set_vm_grouping and mbls_ctx_set_committee_route, however the stream packed the round. No output of a call depends on any other call of its round.
+ *   BOTH submit forms reject on the device as that entry does (an id, key index or message index that names nothing); the stream does not refuse the call.
+ * CUTTING. A call is never split (a batch's verdict is one pairing product). It costs n_sets + 1 of round_items -- its sets plus its signature pair, so the
+ *   per-set route's Miller launch stays within a round --, a call that does not fit the open round closes it, and a call with n_sets + 1 > round_items is refused at
+ *   submit (MBLS_ERR_ARGUMENT, the message names the capacity). round_keys and round_msg_bytes play no part. stats.pieces == stats.calls, split_calls == 0,
+ *   stats.items counts sets, gathered_bytes counts 96 + 4 + 4 + 8 + bits_len per set. mbls_stream_cut_vm is the rule as data (pure, no GPU): call j of
+ *   call_sets[j] sets is piece j = {j, 0, call_sets[j], its round, its first set in the round}, with a forced launch after call j where flush_after[j] != 0
+ *   (flush_after may be NULL); only opts->round_items is read. MBLS_ERR_ARGUMENT for null pointers, round_items = 0, no calls, a call of 0 sets or of more than
+ *   round_items - 1, or more pieces than max_pieces (out = NULL with max_pieces = 0 counts).
+ * max_groups of a round is the sum over its calls of: the exact count of distinct message indices the call names (host submits, counted at submit; n_sets for a
+ *   call of more than MBLS_VBG_MAX_SETS sets, which is not grouped), and n_sets for device submits -- the host cannot see their indices, and a wrong promise by one
+ *   caller would reject innocent calls behind it in the group space. A per-call hint for device submits is OUT OF SCOPE.
+ * ALLOCATION. Everything at creation: a slot holds 96 + 4 + 4 + 8 + bits_stride bytes per set (and as many pinned bytes per set, the mirrors through which host
+ *   submits are staged: every run of neighbouring host calls goes up in one copy per array); the context's workspace for every (n_sets, n_batches) a round can
+ *   hold on both routes with locate (mbls_plan_verify_multiple_batches_committee), the committee scratch as a committee stream reserves it, and the entry's own
+ *   staging (set map, group arrays). No round allocates. A slot never shows a round the bits or scalars of the round before.
+ * TABLES. The committee stream's interlocks: mbls_committees_clear and mbls_msgtable_clear are refused while calls are pending, mbls_committees_append refuses a
+ *   committee of more than 8 * bits_stride members while the stream lives. DESTROY A STREAM BEFORE ITS TABLES.
+ * The other submit entries on such a stream, and the two below on any other stream, are MBLS_ERR_ARGUMENT; the message names the right entry.
+ * OUT OF SCOPE: committee spans per set, per-set message bytes or a shared message list, a group-count promise for device submits, the mbls_multi handle, wire keys. */
+int mbls_stream_create_vm_committee(mbls_ctx* ctx, mbls_committees* committees, mbls_msgtable* mt, uint32_t bits_stride, const mbls_stream_opts* opts,
+                                    mbls_stream** out);
+int mbls_stream_submit_vm_device(mbls_stream* s, const uint8_t* d_sigs96, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_len,
+                                 const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n_sets, uint8_t* d_result, uint32_t* d_status, uint8_t* d_set_results,
+                                 uint32_t* d_set_status, void* stream, uint64_t* ticket);
+int mbls_stream_submit_vm(mbls_stream* s, const uint8_t* sigs96, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_len, const uint32_t* msg_idx,
+                          const uint64_t* rands, uint64_t n_sets, uint8_t* result, uint32_t* status, uint8_t* set_results, uint32_t* set_status, uint64_t* ticket);
+int mbls_stream_cut_vm(const mbls_stream_opts* opts, const uint64_t* call_sets, const uint32_t* flush_after, uint64_t n_calls,
+                       mbls_stream_piece* out, uint64_t max_pieces, uint64_t* n_pieces);
 
 /* ---- several GPUs behind one handle ------------------------------------------------------------------------
  * Items are independent (reference src/aggregates.rs:177-215 keeps no state between calls), so a batch shards embarrassingly:
@@ -1095,7 +1135,8 @@ int mbls_plan_verify_multiple_span(const mbls_limits* limits, uint64_t n, uint64
  * PLANNING. mbls_plan_verify_multiple_batches_committee(limits, n_sets, n_batches, sets_per_batch (0: a ragged device-side table), table_size, max_groups, mode,
  *   locate, &plan), without a GPU: what a call reserves and acts on. MBLS_ERR_ARGUMENT for n_sets = 0, n_batches = 0, a mode outside 0..2, a uniform layout with
  *   n_batches x sets_per_batch != n_sets.
- * OUT OF SCOPE: committee spans per set, the verification stream, the mbls_multi handle, wire keys. */
+ * OUT OF SCOPE: committee spans per set, the mbls_multi handle, wire keys. (One batch per caller, coalesced into such calls: the verify_multiple stream,
+ *   mbls_stream_create_vm_committee, above.) */
 #define MBLS_VBG_MAX_SETS 1024u
 typedef struct mbls_vm_batches_committee_plan {
     int32_t route;                 /* MBLS_VM_ROUTE_* */

@@ -1048,4 +1048,68 @@ public:
     void wait(uint64_t ticket) const { check(mbls_stream_wait(h_, ticket)); }
     mbls_stream_stats stats() const { mbls_stream_stats st{}; check(mbls_stream_get_stats(h_, &st)); return st; }
 };
+
+// A verify_multiple stream over a committee table and a message table (include/mbls.h, mbls_stream_create_vm_committee): the gossip caller, many threads each
+// holding ONE small batch. A call is one batch of CommitteeTable::GossipSet and is never split; the stream packs the batches of many callers into one call of
+// mbls_verify_multiple_batches_committee_msgtable_locate_device per round and answers per batch and per set. submit() draws one scalar per set from rng AT
+// SUBMIT, in set order, by the reference's rule (AggregateSignature::draw_scalar) -- the one difference from the _rng entries: nothing is read back before the
+// draw, so a batch with a signature outside G2 still consumes a scalar for every set. Destroy the stream before both tables.
+class VerifyMultipleStream {
+    struct Call { Bytes s, f; std::vector<uint32_t> words, midx, sst; std::vector<uint64_t> rands; std::vector<uint8_t> sres; uint8_t res = 0; uint32_t st = 0;
+                  uint64_t ticket = 0; size_t n = 0; };
+    mbls_stream* h_ = nullptr;
+    uint32_t bits_stride_ = 0;
+    std::mutex mu_;
+    std::deque<std::shared_ptr<Call>> live_;
+    void check(int rc) const { if (rc != MBLS_OK) throw DeviceError(std::string("mbls_stream: ") + mbls_stream_last_error(h_)); }
+public:
+    class Ticket {
+        VerifyMultipleStream* vs_; std::shared_ptr<Call> c_;
+    public:
+        Ticket(VerifyMultipleStream* vs, std::shared_ptr<Call> c) : vs_(vs), c_(std::move(c)) {}
+        uint64_t id() const { return c_->ticket; }
+        bool ready() const { return mbls_stream_query(vs_->h_, c_->ticket) != MBLS_PENDING; }
+        // the batch's bool, and which sets of a rejected batch are the good ones (every set of an accepted batch: true)
+        std::pair<bool, std::vector<bool>> get() const { vs_->wait(c_->ticket); return {c_->res == 1, std::vector<bool>(c_->sres.begin(), c_->sres.end())}; }
+        // the batch's MBLS_ST_* word and the sets' words, once the call is done
+        std::pair<uint32_t, std::vector<uint32_t>> status() const { vs_->wait(c_->ticket); return {c_->st, c_->sst}; }
+    };
+    // bits_stride: a multiple of 4 whose 8 x covers the table's largest committee, now and for every later append; round_items 0 = the device's round
+    VerifyMultipleStream(CommitteeTable& committees, MessageTable& table, uint32_t bits_stride, uint32_t policy = MBLS_STREAM_WORK_CONSERVING, uint64_t round_items = 0)
+        : bits_stride_(bits_stride) {
+        mbls_stream_opts o{}; o.round_items = round_items; o.policy = policy;
+        if (mbls_stream_create_vm_committee(detail::ctx(), committees.handle(), table.handle(), bits_stride, &o, &h_) != MBLS_OK)
+            throw DeviceError(std::string("mbls_stream_create_vm_committee: ") + mbls_last_error(detail::ctx()));
+    }
+    VerifyMultipleStream(const VerifyMultipleStream&) = delete; VerifyMultipleStream& operator=(const VerifyMultipleStream&) = delete;
+    ~VerifyMultipleStream() { mbls_stream_destroy(h_); }
+    mbls_stream* handle() const { return h_; }
+    // one batch: at least one set and fewer than round_items of them. The fields travel at the length of the longest (a batch of single-key sets only: 0 bytes),
+    // which must not exceed the stream's bits_stride. A committee id, key index or entry index that names nothing rejects the batch and names its set.
+    template <typename Rng>
+    Ticket submit(Rng&& rng, const std::vector<CommitteeTable::GossipSet>& sets) {
+        const size_t n = sets.size();
+        if (n == 0) throw std::invalid_argument("VerifyMultipleStream::submit: a batch holds at least one set");
+        size_t len = 0;
+        for (const auto& s : sets) len = std::max(len, s.bits.size());
+        if (len > bits_stride_) throw std::invalid_argument("VerifyMultipleStream::submit: a field is longer than the stream's bits_stride");
+        auto c = std::make_shared<Call>();
+        c->n = n; c->sres.assign(n, 0); c->sst.assign(n, 0); c->f.assign(len * n, 0);
+        for (size_t i = 0; i < n; i++) {
+            c->s.insert(c->s.end(), sets[i].signature->point.begin(), sets[i].signature->point.end());
+            std::copy(sets[i].bits.begin(), sets[i].bits.end(), c->f.begin() + len * i);
+            c->words.push_back(sets[i].word); c->midx.push_back(sets[i].msg_index);
+            c->rands.push_back(AggregateSignature::draw_scalar(rng));
+        }
+        std::lock_guard<std::mutex> g(mu_);
+        while (!live_.empty() && mbls_stream_query(h_, live_.front()->ticket) != MBLS_PENDING) live_.pop_front();
+        check(mbls_stream_submit_vm(h_, c->s.data(), c->words.data(), len ? c->f.data() : nullptr, uint32_t(len), c->midx.data(), c->rands.data(), n, &c->res, &c->st,
+                                    c->sres.data(), c->sst.data(), &c->ticket));
+        live_.push_back(c);
+        return Ticket(this, c);
+    }
+    void flush() { check(mbls_stream_flush(h_)); }
+    void wait(uint64_t ticket) const { check(mbls_stream_wait(h_, ticket)); }
+    mbls_stream_stats stats() const { mbls_stream_stats st{}; check(mbls_stream_get_stats(h_, &st)); return st; }
+};
 }  // namespace milagro_bls

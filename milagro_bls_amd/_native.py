@@ -233,6 +233,21 @@ def stream_cut(calls, round_items, round_keys, round_msg_bytes):
     return [{f: getattr(out[i], f) for f, _ in StreamPiece._fields_} for i in range(cnt.value)]
 
 
+def stream_cut_vm(call_sets, round_items, flush_after=None):
+    """how a verify_multiple stream cuts a sequence of calls (one batch each, never split) into rounds (pure: no GPU) -> [piece dicts]. call_sets: the sets per
+    call; flush_after: None or one flag per call (a launch is forced after the call)"""
+    o = StreamOpts(round_items, 0, 0, 1, STREAM_FULL_ROUNDS)
+    n = len(call_sets)
+    sets = (C.c_uint64 * max(1, n))(*call_sets)
+    fl = None if flush_after is None else (C.c_uint32 * max(1, n))(*[int(bool(f)) for f in flush_after])
+    out = (StreamPiece * max(1, n))()
+    cnt = C.c_uint64(0)
+    rc = lib().mbls_stream_cut_vm(C.byref(o), sets, fl, n, out, n, C.byref(cnt))
+    if rc != OK:
+        raise MblsError(rc, "mbls_stream_cut_vm")
+    return [{f: getattr(out[i], f) for f, _ in StreamPiece._fields_} for i in range(cnt.value)]
+
+
 # mbls_scalar_source (include/mbls.h): void draw(void* user, uint64_t* out, uint64_t count)
 SCALAR_SOURCE = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64)
 SIGNATURES = {
@@ -441,6 +456,10 @@ SIGNATURES = {
     "mbls_stream_query": (C.c_int, [vp, C.c_uint64]),
     "mbls_stream_get_stats": (C.c_int, [vp, vp]),
     "mbls_stream_cut": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "mbls_stream_create_vm_committee": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.POINTER(vp)]),
+    "mbls_stream_submit_vm_device": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, C.POINTER(C.c_uint64)]),
+    "mbls_stream_submit_vm": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(C.c_uint64)]),
+    "mbls_stream_cut_vm": (C.c_int, [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "mbls_enable_phase_timing": (C.c_int, [vp, C.c_int]),
     "mbls_last_phase_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
 }

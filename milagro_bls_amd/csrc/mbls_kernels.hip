@@ -5173,6 +5173,17 @@ extern "C" int mbls_verify_multiple_batches_committee_msgtable_locate_device(mbl
     return vbg_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_committees(t, d_cmt_idx, d_bits, bits_stride), 0).msgs_in(mt, d_msg_idx, 0)
                              .batches(d_batch_offsets, sets_per_batch, n_batches, max_groups).out(d_results, d_status).out_sets(d_set_results, d_set_status), stream);
 }
+// the grow-only staging vbg_impl takes beside the workspace and the committee scratch, for calls of up to max_sets sets in up to max_batches batches: the set map
+// of a ragged batch table and the group arrays of the grouped route. Not exported: a verify_multiple stream (mbls_stream.hip) reserves both at creation, so that
+// no round of it allocates.
+extern "C" __attribute__((visibility("hidden"))) int mblsi_vbg_reserve_staging(mbls_ctx* c, uint64_t max_sets, uint64_t max_batches) {
+    if (!c) return MBLS_ERR_ARGUMENT;
+    mbls_lock lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    sbuf dmap(c, 9);
+    HIPCHK(c, dmap.alloc(4 * (max_sets ? max_sets : 1)));
+    return reserve_groups(c, vbg_group_words(max_sets, max_batches));
+}
 // host buffers, the draw order of vmb_rng_impl: the signatures of ALL batches are decoded and tested first, `draw` is asked once for the scalars of the sets in front
 // of each batch's first signature outside G2, the rest runs without a second subgroup test. A committee id, key index or message index that names nothing, or a batch
 // table that is not sound, refuses the call with nothing queued and the outputs untouched. The host counts the distinct (batch, entry) pairs itself.

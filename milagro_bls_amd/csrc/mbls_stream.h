@@ -1,7 +1,8 @@
 // mbls_stream.h -- the pure parts of the verification stream (include/mbls.h, "verification stream"), in a header of their own so that a
 // host compiler can build them for the CPU tests (tests/host_emul/mbls_stream_harness.cpp): the cutting rule that packs calls into rounds,
 // the layout decision of a round, the bit arithmetic of the scatter into a caller's bitmap, and one destination dword of a committee call's re-strided bitfield
-// (tests/stream_cmt_emul/mbls_stream_cmt_harness.cpp). mbls_stream.hip runs exactly these.
+// (tests/stream_cmt_emul/mbls_stream_cmt_harness.cpp), and the whole-call rule and the batch table of a verify_multiple stream
+// (tests/stream_vm_emul/mbls_stream_vm_harness.cpp). mbls_stream.hip runs exactly these.
 #ifndef MBLS_STREAM_H
 #define MBLS_STREAM_H
 #include <stdint.h>
@@ -42,6 +43,29 @@ MBLS_SFN uint64_t stream_take(const mbls_stream_opts& o, mbls_stream_fill& f, co
     }
     f.items += t;
     return t;
+}
+
+// ---- whole calls (a verify_multiple stream, mbls_stream_create_vm_committee): a call is ONE batch and a batch's verdict is one pairing product, so a call is
+// never split. A call of n_sets sets costs n_sets + 1 of round_items -- its sets plus its signature pair, the Miller items of the per-set route, so that launch
+// stays within a round. A call joins the open round when its cost fits what is left; otherwise it closes the round and opens the next one. A call that costs more
+// than an empty round holds is refused at submit (stream_vm_fits). mbls_stream_cut_vm states this rule as data.
+struct mbls_stream_vm_fill { uint64_t cost, sets, calls; };
+MBLS_SFN uint64_t stream_vm_cost(uint64_t n_sets) { return n_sets + 1; }
+MBLS_SFN int stream_vm_fits(const mbls_stream_opts& o, uint64_t n_sets) { return n_sets >= 1 && n_sets < o.round_items; }
+// 1: the call joined the open round (f advanced: it is batch f.calls - 1 and its sets start at the old f.sets); 0: it does not fit, the round is closed
+MBLS_SFN int stream_take_whole(const mbls_stream_opts& o, mbls_stream_vm_fill& f, uint64_t n_sets) {
+    const uint64_t cost = stream_vm_cost(n_sets);
+    if (cost > o.round_items - f.cost) return 0;
+    f.cost += cost; f.sets += n_sets; f.calls++;
+    return 1;
+}
+// no further call fits: the smallest one costs 2
+MBLS_SFN int stream_vm_full(const mbls_stream_opts& o, const mbls_stream_vm_fill& f) { return o.round_items - f.cost < 2; }
+// the ragged batch table of a round whose calls hold call_sets[0 .. n_calls) sets: off[0 .. n_calls], off[b] the first set of batch b, off[n_calls] the round's sets
+MBLS_SFN void stream_vm_offsets(const uint64_t* call_sets, uint64_t n_calls, uint32_t* off) {
+    uint64_t at = 0;
+    for (uint64_t b = 0; b < n_calls; b++) { off[b] = (uint32_t)at; at += call_sets[b]; }
+    off[n_calls] = (uint32_t)at;
 }
 
 // the call as a whole: offsets non-decreasing (messages below 2^32 bytes, as the host entries require), and no item larger than an empty round.

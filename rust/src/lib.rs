@@ -287,6 +287,11 @@ extern "C" {
                                     out: *mut *mut mbls_stream) -> c_int;
     fn mbls_stream_submit_committee(s: *mut mbls_stream, sigs: *const u8, msg_idx: *const u32, cmt_idx: *const u32, bits: *const u8, bits_len: u32, n: u64,
                                     results: *mut u8, status: *mut u32, ticket: *mut u64) -> c_int;
+    // a verify_multiple stream over the same two tables: a call is one batch of sets, never split
+    fn mbls_stream_create_vm_committee(ctx: *mut MblsCtx, committees: *mut mbls_committees, mt: *mut mbls_msgtable, bits_stride: u32, opts: *const mbls_stream_opts,
+                                       out: *mut *mut mbls_stream) -> c_int;
+    fn mbls_stream_submit_vm(s: *mut mbls_stream, sigs96: *const u8, cmt_idx: *const u32, bits: *const u8, bits_len: u32, msg_idx: *const u32, rands: *const u64,
+                             n_sets: u64, result: *mut u8, status: *mut u32, set_results: *mut u8, set_status: *mut u32, ticket: *mut u64) -> c_int;
     fn mbls_stream_flush(s: *mut mbls_stream) -> c_int;
     fn mbls_stream_wait(s: *mut mbls_stream, ticket: u64) -> c_int;
     fn mbls_stream_destroy(s: *mut mbls_stream);
@@ -2012,6 +2017,87 @@ impl CommitteeStream {
     }
 }
 impl Drop for CommitteeStream {
+    fn drop(&mut self) {
+        unsafe { mbls_stream_destroy(self.h) }
+    }
+}
+/// A verify_multiple stream over a `CommitteeTable` and a `MessageTable` (`mbls_stream_create_vm_committee`): many threads, each holding ONE small gossip batch.
+/// A call is one batch and is never split; the stream packs the batches of many callers into one launch per round and answers per batch and per set. The
+/// interlocks with the tables are `CommitteeStream`'s. Drop the stream before both tables. (Like the rest of this crate: source only, never compiled.)
+pub struct VerifyMultipleStream {
+    h: *mut mbls_stream,
+    bits_stride: u32,
+}
+unsafe impl Send for VerifyMultipleStream {}
+unsafe impl Sync for VerifyMultipleStream {}
+impl VerifyMultipleStream {
+    /// `bits_stride`: a multiple of 4 with `8 * bits_stride` at least the table's largest committee
+    pub fn new(committees: &mut CommitteeTable, table: &mut MessageTable, bits_stride: u32, opts: mbls_stream_opts) -> Self {
+        let mut h: *mut mbls_stream = std::ptr::null_mut();
+        let rc = unsafe { mbls_stream_create_vm_committee(ctx(), committees.h, table.h, bits_stride, &opts, &mut h) };
+        if rc != 0 {
+            err(rc);
+        }
+        VerifyMultipleStream { h, bits_stride }
+    }
+    /// One batch of `CommitteeTable::verify_multiple_aggregate_signatures_locate`'s sets -> (the batch's bool, which sets of a rejected batch are good). One scalar
+    /// per set is drawn from `rng` before the submit, in set order, by the reference's rule; unlike the `_rng` entries nothing is read back before the draw, so a
+    /// batch with a signature outside G2 still consumes a scalar for every set. The fields travel at the length of the longest (at most `bits_stride` bytes; a
+    /// batch of single-key sets only: 0). A committee id, key index or entry index that names nothing rejects the batch and names its set.
+    pub fn verify<'a, R: Rng + ?Sized>(&self, rng: &mut R, sets: &[(&'a AggregateSignature, GossipKeys<'a>, u32)]) -> (bool, Vec<bool>) {
+        let n = sets.len();
+        assert!(n > 0);
+        let mut sigs = Vec::new();
+        let (mut words, mut idx, mut rands): (Vec<u32>, Vec<u32>, Vec<u64>) = (Vec::with_capacity(n), Vec::with_capacity(n), Vec::with_capacity(n));
+        let mut fields: Vec<&[u8]> = Vec::with_capacity(n);
+        for (s, k, j) in sets {
+            sigs.extend_from_slice(&s.point);
+            match *k {
+                GossipKeys::Committee { id, bits } => {
+                    assert!(id & VM_SET_SINGLE_KEY == 0, "committee ids have 31 bits");
+                    words.push(id);
+                    fields.push(bits);
+                }
+                GossipKeys::SingleKey(index) => {
+                    assert!(index & VM_SET_SINGLE_KEY == 0, "key indices have 31 bits");
+                    words.push(VM_SET_SINGLE_KEY | index);
+                    fields.push(&[]);
+                }
+            }
+            idx.push(*j);
+            let mut rand = 0u64;
+            while rand == 0 {
+                let mut rand_bytes = [0u8; 8];
+                rng.fill(&mut rand_bytes);
+                rand = i64::from_be_bytes(rand_bytes).wrapping_abs() as u64;
+            }
+            rands.push(rand);
+        }
+        let len = fields.iter().map(|b| b.len()).max().unwrap_or(0);
+        assert!(len <= self.bits_stride as usize);
+        let mut flat = vec![0u8; len * n];
+        for (i, b) in fields.iter().enumerate() {
+            flat[len * i..len * i + b.len()].copy_from_slice(b);
+        }
+        let (mut ok, mut st, mut ticket) = (0u8, 0u32, 0u64);
+        let mut sres = vec![0u8; n];
+        let mut rc = unsafe {
+            mbls_stream_submit_vm(self.h, sigs.as_ptr(), words.as_ptr(), if len > 0 { flat.as_ptr() } else { std::ptr::null() }, len as u32, idx.as_ptr(), rands.as_ptr(),
+                                  n as u64, &mut ok, &mut st, sres.as_mut_ptr(), std::ptr::null_mut(), &mut ticket)
+        };
+        if rc == 0 {
+            rc = unsafe { mbls_stream_wait(self.h, ticket) };       // the buffers above stay valid until the call completes
+        }
+        if rc != 0 {
+            err(rc);
+        }
+        (ok == 1, sres.into_iter().map(|b| b == 1).collect())
+    }
+    pub fn flush(&self) {
+        unsafe { mbls_stream_flush(self.h) };
+    }
+}
+impl Drop for VerifyMultipleStream {
     fn drop(&mut self) {
         unsafe { mbls_stream_destroy(self.h) }
     }
