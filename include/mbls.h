@@ -580,7 +580,7 @@ int mbls_stream_cut(const mbls_stream_opts* opts, const mbls_stream_call_shape* 
  * TABLES. The committee stream's interlocks: mbls_committees_clear and mbls_msgtable_clear are refused while calls are pending, mbls_committees_append refuses a
  *   committee of more than 8 * bits_stride members while the stream lives. DESTROY A STREAM BEFORE ITS TABLES.
  * The other submit entries on such a stream, and the two below on any other stream, are MBLS_ERR_ARGUMENT; the message names the right entry.
- * OUT OF SCOPE: committee spans per set, per-set message bytes or a shared message list, a group-count promise for device submits, the mbls_multi handle, wire keys. */
+ * OUT OF SCOPE: spans in a stream, per-set message bytes or a shared message list, a group-count promise for device submits, the mbls_multi handle, wire keys. */
 int mbls_stream_create_vm_committee(mbls_ctx* ctx, mbls_committees* committees, mbls_msgtable* mt, uint32_t bits_stride, const mbls_stream_opts* opts,
                                     mbls_stream** out);
 int mbls_stream_submit_vm_device(mbls_stream* s, const uint8_t* d_sigs96, const uint32_t* d_cmt_idx, const uint8_t* d_bits, uint32_t bits_len,
@@ -1080,9 +1080,8 @@ int mbls_verify_multiple_committee_msgtable_locate_rng(mbls_ctx* ctx, const mbls
  *   P a call takes, and the workspace items it reserves -- mbls_plan_verify_multiple_msgtable[_locate]_workspace_items(limits, n, table_size, 0, 0) plus 2 P n for
  *   P > 1 (nothing for P = 1: the one-lane form parks its intermediate point in the span scratch). Under mbls_ctx_set_vm_grouping other than 0 the first term is
  *   that function's under the mode.
- * OUT OF SCOPE: the verification stream, the shared-list and per-set message forms, mbls_verify_multiple_batches over spans (over plain
- * committees: mbls_verify_multiple_batches_committee_msgtable*, below), the mbls_multi handle and the shard form, a device-pointer append, splitting the chain of
- * up to 64 cached sums. */
+ * OUT OF SCOPE: the verification stream, the shared-list and per-set message forms, the mbls_multi handle and the shard form, a device-pointer append,
+ * splitting the chain of up to 64 cached sums. (Many such batches per call, one verdict per batch: mbls_verify_multiple_batches_committee_span_msgtable*, below.) */
 int mbls_verify_multiple_committee_span_msgtable_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96, const uint32_t* d_cmt_ids,
                                                         uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride,
                                                         const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n, uint8_t* d_result,
@@ -1135,8 +1134,8 @@ int mbls_plan_verify_multiple_span(const mbls_limits* limits, uint64_t n, uint64
  * PLANNING. mbls_plan_verify_multiple_batches_committee(limits, n_sets, n_batches, sets_per_batch (0: a ragged device-side table), table_size, max_groups, mode,
  *   locate, &plan), without a GPU: what a call reserves and acts on. MBLS_ERR_ARGUMENT for n_sets = 0, n_batches = 0, a mode outside 0..2, a uniform layout with
  *   n_batches x sets_per_batch != n_sets.
- * OUT OF SCOPE: committee spans per set, the mbls_multi handle, wire keys. (One batch per caller, coalesced into such calls: the verify_multiple stream,
- *   mbls_stream_create_vm_committee, above.) */
+ * OUT OF SCOPE: the mbls_multi handle, wire keys. (Committee spans per set: mbls_verify_multiple_batches_committee_span_msgtable*, below. One batch per caller,
+ *   coalesced into such calls: the verify_multiple stream, mbls_stream_create_vm_committee, above.) */
 #define MBLS_VBG_MAX_SETS 1024u
 typedef struct mbls_vm_batches_committee_plan {
     int32_t route;                 /* MBLS_VM_ROUTE_* */
@@ -1166,6 +1165,55 @@ int mbls_verify_multiple_batches_committee_msgtable_locate_rng(mbls_ctx* ctx, co
                                                                const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx,
                                                                uint64_t n_sets, const uint32_t* batch_offsets, uint32_t sets_per_batch, uint64_t n_batches,
                                                                uint8_t* results, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user);
+
+/* MANY verify_multiple BATCHES PER CALL OVER COMMITTEE SPANS AND THE RESIDENT MESSAGE TABLE. Range sync and block import verify many blocks at once, each block
+ * one verify_multiple batch of about a dozen sets, of which an attestation names up to 64 committees. These entries answer PER BATCH (per block), with per-set
+ * location: the SETS are exactly those of mbls_verify_multiple_committee_span_msgtable[_locate]_device (`committees, d_sigs96, d_cmt_ids, n_cmt_ids, d_cmt_off,
+ * d_bits, bits_stride, mt, d_msg_idx, d_rands, n_sets`), the BATCH TABLE AND OUTPUTS exactly those of mbls_verify_multiple_batches_committee_msgtable[_locate]_device
+ * (`d_batch_offsets, sets_per_batch, n_batches, max_groups, d_results, d_status[, d_set_results, d_set_status], stream`). Every rule of "verify_multiple OVER
+ * COMMITTEE SPANS" (the span rules, the single-key set, the per-segment route, malformed sets rejected on the device like a set that lists 0xFFFFFFFF) and every
+ * rule of "MANY verify_multiple BATCHES PER CALL OVER COMMITTEE BITFIELDS" (a faulty device-side batch table, a max_groups that is too small, the
+ * MBLS_VBG_MAX_SETS cap, n_batches = 0 and n_sets = 0, routing, enqueue only) holds unchanged and is not restated here.
+ * A malformed set, or a message index at or above the table's size (MBLS_ST_BAD_MSG_RANGE), rejects ITS BATCH ONLY and is named by _locate.
+ * CONTRACT. d_results[b], d_status[b], and for _locate every set byte and every set word, equal mbls_verify_multiple_batches[_locate]_indexed_device on the same
+ *   signatures, scalars and batch table with every set's selected members spelled out in (segment, member) order and every message as the bytes of its entry, and
+ *   equal one call of mbls_verify_multiple_committee_span_msgtable_locate_device per non-empty batch -- under every mode of mbls_ctx_set_vm_grouping and
+ *   mbls_ctx_set_committee_route and every split factor. A set of one plain committee, and a single-key set, give what
+ *   mbls_verify_multiple_batches_committee_msgtable_locate_device gives.
+ * SPLIT. The factor P is the one-call entry's rule on the CALL's n_sets under mbls_ctx_set_vm_span_split; the 2 P n_sets partial sums stand in workspace items
+ *   behind everything the batches plan lays out (csrc/mbls_vbg.h vbg_partial_first). The device work is the span key phase (k_vcs_expand, then the one-lane sum or
+ *   k_vcs_partial_d / k_vcs_combine) followed by the batches entries' path: existing kernels launched from a new place, no kernel of its own.
+ * HOST ENTRIES (_rng) draw exactly as mbls_verify_multiple_batches_committee_msgtable[_locate]_rng do. They refuse with MBLS_ERR_ARGUMENT, nothing queued and the
+ *   outputs untouched, a batch table that is not sound, a malformed set, and a key or message index that names nothing; they count the groups themselves.
+ * PLANNING. mbls_plan_verify_multiple_batches_committee_span(limits, n_sets, n_batches, sets_per_batch, table_size, max_groups, mode, locate, stride_words,
+ *   split_mode, &plan, &split), without a GPU: plan holds the values of mbls_plan_verify_multiple_batches_committee for the same arguments with workspace_items
+ *   raised by 2 P n_sets when P > 1; split is P (stride_words as in mbls_plan_verify_multiple_span). Argument errors: that function's, and a split_mode outside
+ *   {0, 1, 2, 4, 8, 16}.
+ * OUT OF SCOPE: a stream of span batches, the shared-list and per-set message forms, the mbls_multi handle and the shard form, wire keys, set kinds beyond span
+ * and single key, splitting the chain of cached sums, a split factor per batch. */
+int mbls_plan_verify_multiple_batches_committee_span(const mbls_limits* limits, uint64_t n_sets, uint64_t n_batches, uint32_t sets_per_batch, uint64_t table_size,
+                                                     uint64_t max_groups, int mode, int locate, uint64_t stride_words, int split_mode,
+                                                     mbls_vm_batches_committee_plan* out, uint32_t* split);
+int mbls_verify_multiple_batches_committee_span_msgtable_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96, const uint32_t* d_cmt_ids,
+                                                                uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride,
+                                                                const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands, uint64_t n_sets,
+                                                                const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint64_t max_groups,
+                                                                uint8_t* d_results, uint32_t* d_status, void* stream);
+int mbls_verify_multiple_batches_committee_span_msgtable_locate_device(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* d_sigs96,
+                                                                       const uint32_t* d_cmt_ids, uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits,
+                                                                       uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx,
+                                                                       const uint64_t* d_rands, uint64_t n_sets, const uint32_t* d_batch_offsets,
+                                                                       uint32_t sets_per_batch, uint64_t n_batches, uint64_t max_groups, uint8_t* d_results,
+                                                                       uint32_t* d_status, uint8_t* d_set_results, uint32_t* d_set_status, void* stream);
+int mbls_verify_multiple_batches_committee_span_msgtable_rng(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs96, const uint32_t* cmt_ids,
+                                                             uint64_t n_cmt_ids, const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride,
+                                                             const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n_sets, const uint32_t* batch_offsets,
+                                                             uint32_t sets_per_batch, uint64_t n_batches, uint8_t* results, mbls_scalar_source draw, void* user);
+int mbls_verify_multiple_batches_committee_span_msgtable_locate_rng(mbls_ctx* ctx, const mbls_committees* committees, const uint8_t* sigs96, const uint32_t* cmt_ids,
+                                                                    uint64_t n_cmt_ids, const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride,
+                                                                    const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n_sets, const uint32_t* batch_offsets,
+                                                                    uint32_t sets_per_batch, uint64_t n_batches, uint8_t* results, uint8_t* set_results,
+                                                                    uint32_t* set_status, mbls_scalar_source draw, void* user);
 /* test probe: the grouping of the grouped route alone (set map, k_vbg_group, the scan of the group counts) on host buffers and ANY batch table, faulty ones
  * included. Arrays over the sets: n_sets words each (0xFFFFFFFF: none); group_count: n_batches; group_off: n_batches + 1. */
 int mbls_vbg_group_probe(mbls_ctx* ctx, const uint32_t* msg_idx, uint64_t n_sets, uint64_t table_size, const uint32_t* batch_offsets, uint32_t sets_per_batch,

@@ -752,7 +752,68 @@ public:
         const bool ok = vm_span(rng, sets, table, &per_set);
         return {ok, per_set};
     }
+    // verify_multiple_aggregate_signatures(rng, block, table) over SpanSets once per batch (per block) of `batches`, in order, as ONE call on the GPU
+    // (mbls_verify_multiple_batches_committee_span_msgtable_rng): one bool per batch, a bad batch rejects itself and nothing else. rng is left where
+    // AggregateSignature::verify_multiple_aggregate_signatures_batches leaves it on the spelled-out sets. A malformed set, a key index or an entry index that
+    // names nothing throws (DeviceError).
+    template <typename Rng, typename Set, typename = typename std::enable_if<std::is_same<Set, SpanSet>::value>::type>
+    std::vector<bool> verify_multiple_aggregate_signatures_batches(Rng&& rng, const std::vector<std::vector<Set>>& batches, const MessageTable& table) const {
+        return vm_span_batches(rng, batches, table, nullptr);
+    }
+    // The same, and in the same call (mbls_verify_multiple_batches_committee_span_msgtable_locate_rng) which sets of the rejected batches are the bad ones.
+    template <typename Rng, typename Set, typename = typename std::enable_if<std::is_same<Set, SpanSet>::value>::type>
+    std::pair<std::vector<bool>, std::vector<std::vector<bool>>> verify_multiple_aggregate_signatures_batches_locate(
+            Rng&& rng, const std::vector<std::vector<Set>>& batches, const MessageTable& table) const {
+        std::vector<std::vector<bool>> per_set;
+        std::vector<bool> ok = vm_span_batches(rng, batches, table, &per_set);
+        return {ok, per_set};
+    }
 private:
+    template <typename Rng>
+    std::vector<bool> vm_span_batches(Rng& rng, const std::vector<std::vector<SpanSet>>& batches, const MessageTable& table,
+                                      std::vector<std::vector<bool>>* per_set) const {
+        if (batches.empty()) return {};
+        const size_t nb = batches.size();
+        size_t widest = 1;
+        for (const auto& b : batches) for (const auto& s : b) widest = std::max(widest, s.aggregation_bits.size());
+        const uint32_t stride = uint32_t((widest + 3) / 4 * 4);                         // one stride for every field, a multiple of 4
+        Bytes sigs, flat; std::vector<uint32_t> ids, off{0}, idx, boff{0};
+        for (const auto& b : batches) {
+            for (const SpanSet& s : b) {
+                sigs.insert(sigs.end(), s.signature->point.begin(), s.signature->point.end());
+                flat.resize(flat.size() + stride, 0);
+                std::copy(s.aggregation_bits.begin(), s.aggregation_bits.end(), flat.end() - stride);
+                ids.insert(ids.end(), s.committee_ids.begin(), s.committee_ids.end());
+                if (ids.size() > 0xFFFFFFFFull) throw std::invalid_argument("verify_multiple_aggregate_signatures_batches: span offsets are 32-bit");
+                off.push_back(uint32_t(ids.size())); idx.push_back(s.msg_index);
+            }
+            if (idx.size() > 0xFFFFFFFEull) throw std::invalid_argument("verify_multiple_aggregate_signatures_batches: set indices are 32-bit");
+            boff.push_back(uint32_t(idx.size()));
+        }
+        const size_t n = idx.size();
+        const uint64_t n_ids = ids.size();
+        if (ids.empty()) ids.push_back(0);
+        using R = typename std::remove_reference<Rng>::type;
+        struct src { R* rng; std::exception_ptr err; } u{&rng, nullptr};
+        mbls_scalar_source draw = [](void* user, uint64_t* out, uint64_t count) {
+            src* p = static_cast<src*>(user);
+            try { for (uint64_t i = 0; i < count; i++) out[i] = AggregateSignature::draw_scalar(*p->rng); }
+            catch (...) { p->err = std::current_exception(); for (uint64_t i = 0; i < count; i++) out[i] = 0; }        // never unwind through the C frames
+        };
+        std::vector<uint8_t> res(nb, 0), sres(per_set ? std::max<size_t>(n, 1) : 0, 0);
+        const int rc = per_set
+            ? mbls_verify_multiple_batches_committee_span_msgtable_locate_rng(detail::ctx(), h_, sigs.data(), ids.data(), n_ids, off.data(), flat.data(), stride,
+                                                                              table.handle(), idx.data(), n, boff.data(), 0, nb, res.data(), sres.data(), nullptr, draw, &u)
+            : mbls_verify_multiple_batches_committee_span_msgtable_rng(detail::ctx(), h_, sigs.data(), ids.data(), n_ids, off.data(), flat.data(), stride, table.handle(),
+                                                                       idx.data(), n, boff.data(), 0, nb, res.data(), draw, &u);
+        if (u.err) std::rethrow_exception(u.err);
+        detail::check(rc);
+        if (per_set) {
+            per_set->clear();
+            for (size_t b = 0; b < nb; b++) per_set->emplace_back(sres.begin() + boff[b], sres.begin() + boff[b + 1]);
+        }
+        return std::vector<bool>(res.begin(), res.end());
+    }
     template <typename Rng>
     bool vm_span(Rng& rng, const std::vector<SpanSet>& sets, const MessageTable& table, std::vector<bool>* per_set) const {
         if (sets.empty()) return true;

@@ -392,6 +392,16 @@ SIGNATURES = {
     "mbls_verify_multiple_batches_committee_msgtable_rng": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, SCALAR_SOURCE, vp]),
     "mbls_verify_multiple_batches_committee_msgtable_locate_rng": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp, vp,
                                                                              SCALAR_SOURCE, vp]),
+    "mbls_plan_verify_multiple_batches_committee_span": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_int, vp,
+                                                                   C.POINTER(C.c_uint32)]),
+    "mbls_verify_multiple_batches_committee_span_msgtable_device": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint32,
+                                                                              C.c_uint64, C.c_uint64, vp, vp, vp]),
+    "mbls_verify_multiple_batches_committee_span_msgtable_locate_device": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint32,
+                                                                                     C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]),
+    "mbls_verify_multiple_batches_committee_span_msgtable_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp,
+                                                                           SCALAR_SOURCE, vp]),
+    "mbls_verify_multiple_batches_committee_span_msgtable_locate_rng": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32,
+                                                                                  C.c_uint64, vp, vp, vp, SCALAR_SOURCE, vp]),
     "mbls_vbg_group_probe": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mbls_plan_locate_workspace_items": (C.c_uint64, [vp, C.c_uint64, C.c_uint64]),
     "mbls_verify_multiple_batches_locate_device": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, vp, vp,
@@ -742,6 +752,20 @@ def plan_verify_multiple_committee_span(n, table_size, stride_words, locate=Fals
     if rc != 0:
         raise MblsError(rc, "mbls_plan_verify_multiple_span")
     return int(split.value), int(items.value)
+
+
+def plan_verify_multiple_batches_committee_span(n_sets, n_batches, sets_per_batch=0, table_size=0, max_groups=0, mode=0, locate=False, stride_words=1, split_mode=0,
+                                                limits=None):
+    """the verify_multiple_batches_committee_span_msgtable entries (pure: no GPU): plan_verify_multiple_batches_committee's dict for the same arguments with
+    workspace_items raised by the partial sums of the split key phase, and the split factor P (stride_words as plan_verify_multiple_committee_span takes it)
+    -> (dict, P)"""
+    L = limits if limits is not None else default_limits()
+    vp_, split = VmBatchesCommitteePlan(), C.c_uint32(0)
+    rc = lib().mbls_plan_verify_multiple_batches_committee_span(C.byref(L), n_sets, n_batches, sets_per_batch, table_size, max_groups, mode, 1 if locate else 0,
+                                                                stride_words, split_mode, C.byref(vp_), C.byref(split))
+    if rc != OK:
+        raise MblsError(rc, "mbls_plan_verify_multiple_batches_committee_span")
+    return {f: getattr(vp_, f) for f, _ in VmBatchesCommitteePlan._fields_}, int(split.value)
 
 
 class CommitteeTable:

@@ -664,6 +664,71 @@ class AggregateSignature:
         per_set = [bool(x) for x in bytes(sres)[:n]]
         return out, [per_set[boffs[b]:boffs[b + 1]] for b in range(len(batches))]
 
+    @staticmethod
+    def verify_multiple_aggregate_signatures_committee_span_batches(rng, batches, committees, table):
+        """Not in the reference: verify_multiple_aggregate_signatures_committee_span once per batch (per block), in order, as ONE call on the GPU
+        (mbls_verify_multiple_batches_committee_span_msgtable_rng). `batches`: an iterable of iterables of the sets that method takes. Returns list[bool], one per
+        batch; a bad batch rejects itself and nothing else. `rng` is left exactly where verify_multiple_aggregate_signatures_batches leaves it on the spelled-out
+        sets. A malformed set, a key index or a message index that names nothing raises."""
+        return AggregateSignature._vm_committee_span_batches(rng, batches, committees, table, False)
+
+    @staticmethod
+    def verify_multiple_aggregate_signatures_committee_span_batches_locate(rng, batches, committees, table):
+        """verify_multiple_aggregate_signatures_committee_span_batches, and in the same call (mbls_verify_multiple_batches_committee_span_msgtable_locate_rng) which
+        sets of the rejected batches are the bad ones. Returns (list[bool], list[list[bool]]) with the semantics of
+        verify_multiple_aggregate_signatures_batches_locate."""
+        return AggregateSignature._vm_committee_span_batches(rng, batches, committees, table, True)
+
+    @staticmethod
+    def _vm_committee_span_batches(rng, batches, committees, table, locate):
+        batches = [list(b) for b in batches]
+        if not batches:
+            return ([], []) if locate else []
+        sets = [s for b in batches for s in b]
+        boffs = [0]
+        for b in batches:
+            boffs.append(boffs[-1] + len(b))
+        id_lists, fields = [], []
+        for s in sets:
+            if isinstance(s[1], SingleKey):
+                id_lists.append([N.VM_SET_SINGLE_KEY | s[1].index])
+                fields.append(b"")
+            else:
+                ids = [int(x) for x in s[1]]
+                if any(not 0 <= x < N.VM_SET_SINGLE_KEY for x in ids):
+                    raise ValueError("committee id out of range")
+                id_lists.append(ids)
+                fields.append(bytes(s[2]))
+        stride = max(4, (max([len(f) for f in fields] + [0]) + 3) // 4 * 4)
+        n = len(sets)
+        n_ids = sum(map(len, id_lists))
+        ids = (C.c_uint32 * max(1, n_ids))(*[x for l in id_lists for x in l])
+        off = (C.c_uint32 * (n + 1))(*([0] + [sum(map(len, id_lists[:i + 1])) for i in range(n)]))
+        failed = []
+        cb = N.SCALAR_SOURCE(_reference_draw(rng, failed))
+        midx = (C.c_uint32 * max(1, n))(*[int(s[3]) for s in sets])
+        boff = (C.c_uint32 * len(boffs))(*boffs)
+        res = N.outbuf(len(batches))
+        ctx = committees.ctx
+        S, B = N.cbuf(b"".join(s[0].point for s in sets)), N.cbuf(b"".join(f.ljust(stride, b"\0") for f in fields))
+        if locate:
+            sres = N.outbuf(max(1, n))
+            if not sets:
+                C.memset(sres, 1, 1)
+            rc = N.lib().mbls_verify_multiple_batches_committee_span_msgtable_locate_rng(ctx.handle, committees.handle, S, ids, n_ids, off, B, stride, table.handle, midx, n,
+                                                                                        boff, 0, len(batches), res, sres, None, cb, None)
+        else:
+            rc = N.lib().mbls_verify_multiple_batches_committee_span_msgtable_rng(ctx.handle, committees.handle, S, ids, n_ids, off, B, stride, table.handle, midx, n, boff, 0,
+                                                                                 len(batches), res, cb, None)
+        if failed:
+            raise failed[0]
+        ctx.check(rc)
+        out = [bool(x) for x in bytes(res)[:len(batches)]]
+        if not locate:
+            return out
+        per_set = [bool(x) for x in bytes(sres)[:n]]
+        return out, [per_set[boffs[b]:boffs[b + 1]] for b in range(len(batches))]
+
     @classmethod
     def from_bytes(cls, data):
         out = N.outbuf(96)

@@ -921,3 +921,59 @@ def verify_multiple_committee_span_msgtable_locate_rng(committees, msg_table, si
     ctx.check(N.lib().mbls_verify_multiple_committee_span_msgtable_locate_rng(ctx.handle, committees.handle, N.cbuf(sigs), ids, n_ids, off, bits, bits_stride,
                                                                               msg_table.handle, _midx(msg_idx, n), n, res, sres, sst, cb, None))
     return bool(bytes(res)[0]), [bool(x) for x in bytes(sres)[:n]], list(sst)[:n]
+
+
+# ---- many verify_multiple batches per call over committee spans and the resident message table (include/mbls.h,
+# mbls_verify_multiple_batches_committee_span_msgtable*): the sets of the span entries above, the batches and outputs of verify_multiple_batches_committee_msgtable*.
+plan_verify_multiple_batches_committee_span = N.plan_verify_multiple_batches_committee_span
+
+
+def verify_multiple_batches_committee_span_msgtable_device(committees, msg_table, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, d_msg_idx, d_rands, n_sets,
+                                                           n_batches, d_results, d_status=None, d_batch_offsets=None, sets_per_batch=0, max_groups=0, stream=None, ctx=None):
+    """verify_multiple_batches_committee_msgtable_device with the sets of verify_multiple_committee_span_msgtable_device: one verdict per batch. Enqueues only."""
+    ctx = ctx or committees.ctx
+    ctx.check(N.lib().mbls_verify_multiple_batches_committee_span_msgtable_device(ctx.handle, committees.handle, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits,
+                                                                                  bits_stride, msg_table.handle, d_msg_idx, d_rands, n_sets, d_batch_offsets,
+                                                                                  sets_per_batch, n_batches, max_groups, d_results, d_status, stream))
+
+
+def verify_multiple_batches_committee_span_msgtable_locate_device(committees, msg_table, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride, d_msg_idx, d_rands,
+                                                                  n_sets, n_batches, d_results, d_set_results, d_status=None, d_set_status=None, d_batch_offsets=None,
+                                                                  sets_per_batch=0, max_groups=0, stream=None, ctx=None):
+    """The same, and in the same call one answer per SET: n_sets result bytes at d_set_results (required), n_sets status words at d_set_status (optional)."""
+    ctx = ctx or committees.ctx
+    ctx.check(N.lib().mbls_verify_multiple_batches_committee_span_msgtable_locate_device(ctx.handle, committees.handle, d_sigs, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits,
+                                                                                         bits_stride, msg_table.handle, d_msg_idx, d_rands, n_sets, d_batch_offsets,
+                                                                                         sets_per_batch, n_batches, max_groups, d_results, d_status, d_set_results,
+                                                                                         d_set_status, stream))
+
+
+def verify_multiple_batches_committee_span_msgtable_rng(committees, msg_table, sigs, cmt_id_lists, fields, bits_stride, msg_idx, n_batches, draw, batch_offsets=None,
+                                                        sets_per_batch=0, ctx=None):
+    """Host buffers and the draw order of verify_multiple_batches_committee_msgtable_rng; the sets as verify_multiple_committee_span_msgtable_rng takes them. A
+    malformed set, a key or message index that names nothing, or a batch table that is not sound raises (MBLS_ERR_ARGUMENT). Returns list[bool], one per batch."""
+    ctx = ctx or committees.ctx
+    n = len(cmt_id_lists)
+    ids, n_ids, off, bits = _span(cmt_id_lists, fields, bits_stride)
+    res = N.outbuf(max(1, n_batches))
+    cb = _scalar_source(draw)
+    ctx.check(N.lib().mbls_verify_multiple_batches_committee_span_msgtable_rng(ctx.handle, committees.handle, N.cbuf(sigs), ids, n_ids, off, bits, bits_stride,
+                                                                               msg_table.handle, _midx(msg_idx, n), n, _boff(batch_offsets), sets_per_batch, n_batches,
+                                                                               res, cb, None))
+    return [bool(x) for x in bytes(res)[:n_batches]]
+
+
+def verify_multiple_batches_committee_span_msgtable_locate_rng(committees, msg_table, sigs, cmt_id_lists, fields, bits_stride, msg_idx, n_batches, draw, batch_offsets=None,
+                                                               sets_per_batch=0, ctx=None):
+    """verify_multiple_batches_committee_span_msgtable_rng with one answer per set. Returns (results, set_results, set_status)."""
+    ctx = ctx or committees.ctx
+    n = len(cmt_id_lists)
+    ids, n_ids, off, bits = _span(cmt_id_lists, fields, bits_stride)
+    res = N.outbuf(max(1, n_batches))
+    sres = N.outbuf(max(1, n))
+    sst = (C.c_uint32 * max(1, n))()
+    cb = _scalar_source(draw)
+    ctx.check(N.lib().mbls_verify_multiple_batches_committee_span_msgtable_locate_rng(ctx.handle, committees.handle, N.cbuf(sigs), ids, n_ids, off, bits, bits_stride,
+                                                                                      msg_table.handle, _midx(msg_idx, n), n, _boff(batch_offsets), sets_per_batch,
+                                                                                      n_batches, res, sres, sst, cb, None))
+    return [bool(x) for x in bytes(res)[:n_batches]], [bool(x) for x in bytes(sres)[:n]], list(sst)[:n]

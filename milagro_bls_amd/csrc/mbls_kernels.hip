@@ -3987,6 +3987,20 @@ static uint32_t vm_committee_split(const mbls_ctx* c, const keysrc& ks, uint64_t
     const mbls_limits L = ctx_limits(c);
     return ks.span ? vcs_split(n, keys_span_stride(ks), &L, c->vm_span_split) : 1u;
 }
+// The span key phase of verify_multiple_impl and vbg_impl on stream s: every set's two lists and record into the span scratch (reserve_committee_span), then the
+// span key sum into the sets' APK slots -- one lane per set, or under a split (P > 1) one lane per chunk of a list, whose partial sums take the workspace items
+// [partial_first, partial_first + 2 P n) and whose status words the same range of the context's words, and one combining lane per set. The sets' words: st_set.
+static void vm_span_key_phase(mbls_ctx* c, mbls_ws ws, const keysrc& ks, uint64_t n, uint32_t P, uint64_t partial_first, uint32_t* st_set, hipStream_t s) {
+    const uint64_t ls = keys_span_stride(ks);
+    mbls_vcs_launch_expand(ks.d_crecs, ks.ccount, ks.d_members, ks.d_cmt_ids, ks.n_cmt_ids, ks.d_cmt_span_off, ks.d_bits, ks.bits_stride, c->cmt_route_mode,
+                           c->d_cms_list, ls, c->d_cms_rec, n, s);
+    if (P > 1u)
+        mbls_vcs_launch_split(ws, partial_first, P, ks.d_recs, ks.tsize, c->d_cms_list, ls, c->d_cms_rec, ks.d_crecs, ks.d_cmt_ids, ks.d_cmt_span_off,
+                              c->d_status + partial_first, st_set, n, s);
+    else
+        mbls_vcs_launch_aggregate(ws, ks.d_recs, ks.tsize, c->d_cms_list, ls, c->d_cms_rec, ks.d_crecs, ks.d_cmt_ids, ks.d_cmt_span_off, c->d_cms_park, c->cms_items,
+                                  st_set, n, s);
+}
 // The key source of an entry that named its handle alone (keys_in_table, keys_in_committees, keys_in_committee_span), read at the sizes the handle has now (the
 // caller holds the context's lock) with the checks of keys_of_table / keys_of_committees (one context, key table alive, bits_stride, alignment of device
 // bitfields) / keys_of_committee_span (no bound between bits_stride and the largest committee -- every set's M is checked on its own)
@@ -4097,15 +4111,7 @@ static int verify_multiple_impl(mbls_ctx* c, const vm_call& d, void* stream) {
     if (hash_first) { rc = message_phase(); if (rc) return rc; }
     if (keys == VM_KEYS_SPAN) {   // sets given by committee span, or by one key index (mbls_vcs.h): every set's two lists and record, then the span key sum -- one lane per
         // set, or under a split one lane per chunk of a list (workspace items and status words behind the call's own and its extra lane) and one combining lane per set
-        const uint64_t ls = keys_span_stride(ks);
-        mbls_vcs_launch_expand(ks.d_crecs, ks.ccount, ks.d_members, ks.d_cmt_ids, ks.n_cmt_ids, ks.d_cmt_span_off, ks.d_bits, ks.bits_stride, c->cmt_route_mode,
-                               c->d_cms_list, ls, c->d_cms_rec, n, s);
-        if (span_split > 1u)
-            mbls_vcs_launch_split(ws, sh.base_items + 1, span_split, ks.d_recs, ks.tsize, c->d_cms_list, ls, c->d_cms_rec, ks.d_crecs, ks.d_cmt_ids, ks.d_cmt_span_off,
-                                  c->d_status + sh.base_items + 1, c->d_status, n, s);
-        else
-            mbls_vcs_launch_aggregate(ws, ks.d_recs, ks.tsize, c->d_cms_list, ls, c->d_cms_rec, ks.d_crecs, ks.d_cmt_ids, ks.d_cmt_span_off, c->d_cms_park, c->cms_items,
-                                      c->d_status, n, s);
+        vm_span_key_phase(c, ws, ks, n, span_split, sh.base_items + 1, c->d_status, s);
     } else if (keys == VM_KEYS_COMMITTEE) {       // sets given by committee and bitfield, or by one key index (mbls_vmc.h): every set's list, then the indexed key sum over it with the complement's fix-up
         const uint64_t ls = keys_list_stride(ks);
         uint32_t* const cnt = c->d_cmt_cnt; uint32_t* const route = c->d_cmt_cnt + c->cmt_items;
@@ -5006,6 +5012,17 @@ extern "C" int mbls_plan_verify_multiple_batches_committee(const mbls_limits* li
     if (sets_per_batch && (uint64_t)sets_per_batch * n_batches != n_sets) return MBLS_ERR_ARGUMENT;
     plan_vm_batches_committee(*limits, n_sets, n_batches, sets_per_batch, table_size, max_groups, mode, locate != 0, 0, out); return MBLS_OK;
 }
+// the span form (mbls_verify_multiple_batches_committee_span_msgtable*): the same plan; P = the split factor of the key phase on the call's n_sets (mbls_vcs.h
+// vcs_split), whose partial sums stand behind the plan's items (mbls_vbg.h vbg_partial_first): workspace_items is raised by vcs_extra_items
+extern "C" int mbls_plan_verify_multiple_batches_committee_span(const mbls_limits* limits, uint64_t n_sets, uint64_t n_batches, uint32_t sets_per_batch, uint64_t table_size,
+        uint64_t max_groups, int mode, int locate, uint64_t stride_words, int split_mode, mbls_vm_batches_committee_plan* out, uint32_t* split) {
+    if (!split || !vcs_split_mode_ok(split_mode)) return MBLS_ERR_ARGUMENT;
+    const int rc = mbls_plan_verify_multiple_batches_committee(limits, n_sets, n_batches, sets_per_batch, table_size, max_groups, mode, locate, out); if (rc) return rc;
+    const uint32_t P = vcs_split(n_sets, stride_words ? stride_words : 1, limits, split_mode);
+    const bool grouped = out->route == MBLS_VM_ROUTE_GROUPED;
+    out->workspace_items = vbg_partial_first(n_sets, n_batches, out->bound, grouped, locate != 0) + vcs_extra_items(n_sets, P);
+    *split = P; return MBLS_OK;
+}
 static int vbg_impl(mbls_ctx* c, const vm_call& d, void* stream) {
     if (!c || !d.mt) return MBLS_ERR_ARGUMENT;
     mbls_lock lk(c->mu);
@@ -5019,7 +5036,9 @@ static int vbg_impl(mbls_ctx* c, const vm_call& d, void* stream) {
     if (n > 0xFFFFFFFEull || B > 0xFFFFFFFEull) ARGFAIL(c, "set and batch indices are 32-bit");
     if (!d_boff && (uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch");
     if (n && !d_rands) ARGFAIL(c, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
-    if (n && ((!d.d_sigs && !d.sigs_resident) || !d_midx || !ks.d_cmt_idx || !ks.d_bits)) ARGFAIL(c, "null buffer");
+    const bool span = vm_key_kind(d) == VM_KEYS_SPAN;
+    if (n && ((!d.d_sigs && !d.sigs_resident) || !d_midx)) ARGFAIL(c, "null buffer");
+    if (n && (span ? !ks.d_cmt_span_off || (ks.n_cmt_ids && !ks.d_cmt_ids) || (ks.bits_stride && !ks.d_bits) : !ks.d_cmt_idx || !ks.d_bits)) ARGFAIL(c, "null buffer");
     if (mt->c != c) ARGFAIL(c, "message table belongs to another context");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
@@ -5028,8 +5047,10 @@ static int vbg_impl(mbls_ctx* c, const vm_call& d, void* stream) {
     plan_vm_batches_committee(ctx_limits(c), n, B, d_boff ? 0u : spb, T, max_groups, c->vm_grouping, loc, longest, &vp);
     const bool grouped = vp.route == MBLS_VM_ROUTE_GROUPED;
     const uint64_t bound = vp.bound, n_miller = vp.miller_items;
-    int rc = mbls_ctx_reserve(c, vp.workspace_items); if (rc) return rc;
-    if (n) { rc = reserve_committee(c, n, ks.cmax); if (rc) return rc; }
+    // the span form under a split: the partial sums' items behind everything the plan lays out (mbls_vbg.h vbg_partial_first); P = 1 for the committee form
+    const uint32_t span_split = vm_committee_split(c, ks, n);
+    int rc = mbls_ctx_reserve(c, vp.workspace_items + vcs_extra_items(n, span_split)); if (rc) return rc;
+    if (n) { rc = span ? reserve_committee_span(c, n, keys_span_stride(ks)) : reserve_committee(c, n, ks.cmax); if (rc) return rc; }
     if (grouped) { rc = reserve_groups(c, vbg_group_words(n, B)); if (rc) return rc; }
     uint32_t* map = nullptr;
     sbuf dmap(c, 9);
@@ -5077,13 +5098,16 @@ static int vbg_impl(mbls_ctx* c, const vm_call& d, void* stream) {
     if (n) {
         // the message phase of the per-set route: every set takes its entry's point (the grouped route reads the table from its Miller items)
         if (!grouped) hipLaunchKernelGGL(k_h_gather, dim3((unsigned)((n + MBLS_HB - 1) / MBLS_HB)), dim3(MBLS_HB), 0, s_msg, ws, tab, tstride, flags, d_midx, T, st_set, n);
-        // the key phase: the committee source of verify_multiple_impl
-        const uint64_t ls = keys_list_stride(ks);
-        uint32_t* const cnt = c->d_cmt_cnt; uint32_t* const route = c->d_cmt_cnt + c->cmt_items;
-        hipLaunchKernelGGL(k_vmc_expand, dim3((unsigned)n), dim3(WG), 0, s, ks.d_crecs, ks.ccount, ks.d_members, ks.d_cmt_idx, ks.d_bits, ks.bits_stride, c->cmt_route_mode,
-                           c->d_cmt_list, ls, cnt, route, n);
-        hipLaunchKernelGGL(k_aggregate_vmc_d, dim3(nblk(n)), dim3(WG), 0, s, ws, ks.d_recs, ks.tsize, (const uint32_t*)c->d_cmt_list, ls, (const uint32_t*)cnt, (const uint32_t*)route,
-                           ks.d_crecs, ks.d_cmt_idx, st_set, n);
+        // the key phase: the committee source of verify_multiple_impl, or its span form
+        if (span) vm_span_key_phase(c, ws, ks, n, span_split, vbg_partial_first(n, B, bound, grouped, loc), st_set, s);
+        else {
+            const uint64_t ls = keys_list_stride(ks);
+            uint32_t* const cnt = c->d_cmt_cnt; uint32_t* const route = c->d_cmt_cnt + c->cmt_items;
+            hipLaunchKernelGGL(k_vmc_expand, dim3((unsigned)n), dim3(WG), 0, s, ks.d_crecs, ks.ccount, ks.d_members, ks.d_cmt_idx, ks.d_bits, ks.bits_stride, c->cmt_route_mode,
+                               c->d_cmt_list, ls, cnt, route, n);
+            hipLaunchKernelGGL(k_aggregate_vmc_d, dim3(nblk(n)), dim3(WG), 0, s, ws, ks.d_recs, ks.tsize, (const uint32_t*)c->d_cmt_list, ls, (const uint32_t*)cnt, (const uint32_t*)route,
+                               ks.d_crecs, ks.d_cmt_idx, st_set, n);
+        }
         hipLaunchKernelGGL(k_blind_g1_d, dim3(nblk(n)), dim3(WG), 0, s, ws, (const uint8_t*)nullptr, d_rands, st_set, n);
         if (grouped) {      // groups, their offsets, the keys to their positions, the per-group sums: behind the keys on their stream
             mbls_vbg_launch_group(d_midx, T, d_boff, spb, B, n, (const uint32_t*)map, ga, st_set, s);
@@ -5200,14 +5224,15 @@ static int vbg_rng_impl(mbls_ctx* c, const vm_host& h) {
     uint64_t longest = spb;
     if (boff) { if (!vmb_offsets_ok(boff, B, n, &longest)) ARGFAIL(c, "batch_offsets must start at 0, be non-decreasing and end at n_sets"); }
     else if ((uint64_t)spb * B != n) ARGFAIL(c, "n_sets != n_batches * sets_per_batch");
-    keysrc ks = keys_in_committees(hc->t, nullptr, nullptr, hc->bits_stride);
+    keysrc ks = hc->span ? keys_in_committee_span(hc->t, nullptr, hc->n_cmt_ids, nullptr, nullptr, hc->bits_stride) : keys_in_committees(hc->t, nullptr, nullptr, hc->bits_stride);
     const int rk = vm_keys_resolve(c, &ks, false); if (rk) return rk;
     if (n == 0) { memset(h.result, 1, B); return MBLS_OK; }                 // empty iterators: true, the generator untouched
-    if (!h.sigs96 || !hc->cmt_idx || !hc->bits || !msg_idx) ARGFAIL(c, "null buffer");
+    if (!h.sigs96 || (!hc->span && (!hc->cmt_idx || !hc->bits)) || !msg_idx) ARGFAIL(c, "null buffer");
     if (!h.draw) ARGFAIL(c, "null scalar source");
     const uint64_t T = mt->size;
+    if (hc->span) { const int ri = vm_committee_span_sets_ok(c, *hc, ks, n); if (ri) return ri; }
     for (uint64_t i = 0; i < n; i++) {
-        if (vmc_names_nothing(hc->cmt_idx[i], ks.ccount, ks.tsize))
+        if (!hc->span && vmc_names_nothing(hc->cmt_idx[i], ks.ccount, ks.tsize))
             ARGFAIL(c, vmc_is_single(hc->cmt_idx[i]) ? "cmt_idx names no key of the key table" : "cmt_idx names no committee of the table");
         if ((uint64_t)msg_idx[i] >= T) ARGFAIL(c, "msg_idx names no entry of the message table");
     }
@@ -5226,14 +5251,18 @@ static int vbg_rng_impl(mbls_ctx* c, const vm_host& h) {
     // everything that may allocate comes before the first kernel: the workspace of the WHOLE call, the committee scratch, the group arrays, the staging
     mbls_vm_batches_committee_plan vp;
     plan_vm_batches_committee(ctx_limits(c), n, B, boff ? 0u : spb, T, groups, c->vm_grouping, h.locate, longest, &vp);
-    int rc = mbls_ctx_reserve(c, vp.workspace_items); if (rc) return rc;
-    rc = reserve_committee(c, n, ks.cmax); if (rc) return rc;
+    int rc = mbls_ctx_reserve(c, vp.workspace_items + vcs_extra_items(n, vm_committee_split(c, ks, n))); if (rc) return rc;      // (as vbg_impl will ask for it)
+    rc = hc->span ? reserve_committee_span(c, n, keys_span_stride(ks)) : reserve_committee(c, n, ks.cmax); if (rc) return rc;
     if (vp.route == MBLS_VM_ROUTE_GROUPED) { rc = reserve_groups(c, vbg_group_words(n, B)); if (rc) return rc; }
-    sbuf ds(c, 0), da(c, 1), dr(c, 3), dbo(c, 5), dres(c, 4), dmi(c, 7), dset(c, 8), dmap(c, 9), dci(c, 10);
-    HIPCHK(c, ds.up(h.sigs96, 96 * n)); HIPCHK(c, da.up(hc->bits, (size_t)hc->bits_stride * n)); HIPCHK(c, dci.up(hc->cmt_idx, 4 * n)); HIPCHK(c, dmi.up(msg_idx, 4 * n));
+    sbuf ds(c, 0), da(c, 1), dso(c, 2), dr(c, 3), dbo(c, 5), dres(c, 4), dmi(c, 7), dset(c, 8), dmap(c, 9), dci(c, 10);
+    HIPCHK(c, ds.up(h.sigs96, 96 * n)); HIPCHK(c, da.up(hc->bits, (size_t)hc->bits_stride * n)); HIPCHK(c, dmi.up(msg_idx, 4 * n));
     HIPCHK(c, dr.alloc(8 * n)); HIPCHK(c, dres.alloc(B));
     if (boff) { HIPCHK(c, dbo.up(boff, 4 * (B + 1))); HIPCHK(c, dmap.alloc(4 * n)); }
-    ks.d_cmt_idx = dci.as<uint32_t>(); ks.d_bits = da.as<uint8_t>();
+    ks.d_bits = da.as<uint8_t>();
+    if (hc->span) {     // the ids take the descriptor words' slot, the span offsets one of their own
+        HIPCHK(c, dci.up(hc->cmt_ids, 4 * hc->n_cmt_ids)); HIPCHK(c, dso.up(hc->cmt_off, 4 * (n + 1)));
+        ks.d_cmt_ids = dci.as<uint32_t>(); ks.d_cmt_span_off = dso.as<uint32_t>();
+    } else { HIPCHK(c, dci.up(hc->cmt_idx, 4 * n)); ks.d_cmt_idx = dci.as<uint32_t>(); }
     vm_call d = vm_sets(nullptr, dr.as<uint64_t>(), n).keys(ks, 0).msgs_in(mt, dmi.as<uint32_t>(), 0).second_half(dr.as<uint64_t>(), false)
                     .batches(boff ? dbo.as<uint32_t>() : nullptr, spb, B, groups).counted(longest ? longest : 1).out(dres.as<uint8_t>(), nullptr);
     if (h.locate) { HIPCHK(c, dset.alloc(5 * n)); d = d.out_sets(dset.as<uint8_t>() + 4 * n, dset.as<uint32_t>()); }
@@ -5261,6 +5290,37 @@ extern "C" int mbls_verify_multiple_batches_committee_msgtable_locate_rng(mbls_c
         const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, const uint32_t* boff, uint32_t spb, uint64_t B,
         uint8_t* results, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user) {
     const host_committees hc = {t, cmt_idx, bits, bits_stride};
+    return vbg_rng_impl(c, vm_host_sets(sigs96, n).keys(&hc).msgs_in(mt, msg_idx).source(draw, user).batches(boff, spb, B).out(results, nullptr)
+                               .out_sets(set_results, set_status));
+}
+
+// ---- B verify_multiple batches in one call over committee SPANS and the resident message table (include/mbls.h, mbls_verify_multiple_batches_committee_span_msgtable*):
+// the entries above with the sets of mbls_verify_multiple_committee_span_msgtable* -- vbg_impl and vbg_rng_impl with the span form of the key source, whose key
+// phase is verify_multiple_impl's (vm_span_key_phase). No kernel of its own.
+extern "C" int mbls_verify_multiple_batches_committee_span_msgtable_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_ids,
+        uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands,
+        uint64_t n, const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint64_t max_groups, uint8_t* d_results, uint32_t* d_status, void* stream) {
+    return vbg_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_committee_span(t, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride), 0).msgs_in(mt, d_msg_idx, 0)
+                             .batches(d_batch_offsets, sets_per_batch, n_batches, max_groups).out(d_results, d_status), stream);
+}
+extern "C" int mbls_verify_multiple_batches_committee_span_msgtable_locate_device(mbls_ctx* c, const mbls_committees* t, const uint8_t* d_sigs, const uint32_t* d_cmt_ids,
+        uint64_t n_cmt_ids, const uint32_t* d_cmt_off, const uint8_t* d_bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* d_msg_idx, const uint64_t* d_rands,
+        uint64_t n, const uint32_t* d_batch_offsets, uint32_t sets_per_batch, uint64_t n_batches, uint64_t max_groups, uint8_t* d_results, uint32_t* d_status,
+        uint8_t* d_set_results, uint32_t* d_set_status, void* stream) {
+    if (!d_set_results) return MBLS_ERR_ARGUMENT;
+    return vbg_device(c, vm_sets(d_sigs, d_rands, n).keys(keys_in_committee_span(t, d_cmt_ids, n_cmt_ids, d_cmt_off, d_bits, bits_stride), 0).msgs_in(mt, d_msg_idx, 0)
+                             .batches(d_batch_offsets, sets_per_batch, n_batches, max_groups).out(d_results, d_status).out_sets(d_set_results, d_set_status), stream);
+}
+extern "C" int mbls_verify_multiple_batches_committee_span_msgtable_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_ids, uint64_t n_cmt_ids,
+        const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, const uint32_t* boff, uint32_t spb,
+        uint64_t B, uint8_t* results, mbls_scalar_source draw, void* user) {
+    const host_committees hc = {t, nullptr, bits, bits_stride, true, cmt_ids, n_cmt_ids, cmt_off};
+    return vbg_rng_impl(c, vm_host_sets(sigs96, n).keys(&hc).msgs_in(mt, msg_idx).source(draw, user).batches(boff, spb, B).out(results, nullptr));
+}
+extern "C" int mbls_verify_multiple_batches_committee_span_msgtable_locate_rng(mbls_ctx* c, const mbls_committees* t, const uint8_t* sigs96, const uint32_t* cmt_ids,
+        uint64_t n_cmt_ids, const uint32_t* cmt_off, const uint8_t* bits, uint32_t bits_stride, const mbls_msgtable* mt, const uint32_t* msg_idx, uint64_t n, const uint32_t* boff,
+        uint32_t spb, uint64_t B, uint8_t* results, uint8_t* set_results, uint32_t* set_status, mbls_scalar_source draw, void* user) {
+    const host_committees hc = {t, nullptr, bits, bits_stride, true, cmt_ids, n_cmt_ids, cmt_off};
     return vbg_rng_impl(c, vm_host_sets(sigs96, n).keys(&hc).msgs_in(mt, msg_idx).source(draw, user).batches(boff, spb, B).out(results, nullptr)
                                .out_sets(set_results, set_status));
 }

@@ -133,6 +133,11 @@ MBLS_VFN uint64_t vbg_workspace_items(uint64_t n, uint64_t B, uint64_t bound, bo
     if (!grouped) return vmb_workspace_items(n, B, false) + (locate ? n : 0);      // (mbls_vml.h vml_workspace_items: the message phase is a gather, no lane pairs)
     return vbg_shadow_first(n, B, bound) + (locate ? 2 * n : 0);
 }
+// The span form (mbls_verify_multiple_batches_committee_span_msgtable*) under a split key sum (mbls_vcs.h, THE SPLIT): the 2 P n partial sums stand behind
+// everything the call lays out above -- per-set route: sets, signature pairs, the batches' view, the locate shadows; grouped route: group items, positions, tail,
+// two shadows per set --, lane g of k_vcs_partial_d at item vbg_partial_first + g, and its status word at the same index of the context's status words (behind
+// the sets' and batches' words and the candidate flags, which end at 2 n + 2 B <= this item). The call then takes vbg_partial_first + vcs_extra_items(n, P) items.
+MBLS_VFN uint64_t vbg_partial_first(uint64_t n, uint64_t B, uint64_t bound, bool grouped, bool locate) { return vbg_workspace_items(n, B, bound, grouped, locate); }
 // the words of the group arrays a call needs per array (pos, rlo, rhi, head, entry over the sets; gcount and goff over the batches share the sixth)
 MBLS_VFN uint64_t vbg_group_words(uint64_t n, uint64_t B) { const uint64_t a = n, b = 2 * B + 2; return a > b ? a : b; }
 #endif

@@ -276,6 +276,16 @@ extern "C" {
                                                                   bits: *const u8, bits_stride: u32, mt: *const mbls_msgtable, msg_idx: *const u32, n_sets: u64,
                                                                   batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64, results: *mut u8, set_results: *mut u8,
                                                                   set_status: *mut u32, draw: MblsScalarSource, user: *mut c_void) -> c_int;
+    // many verify_multiple batches per call over committee spans and the resident message table: the span sets, the batches of the entries above
+    fn mbls_verify_multiple_batches_committee_span_msgtable_rng(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs96: *const u8, cmt_ids: *const u32,
+                                                                n_cmt_ids: u64, cmt_off: *const u32, bits: *const u8, bits_stride: u32, mt: *const mbls_msgtable,
+                                                                msg_idx: *const u32, n_sets: u64, batch_offsets: *const u32, sets_per_batch: u32, n_batches: u64,
+                                                                results: *mut u8, draw: MblsScalarSource, user: *mut c_void) -> c_int;
+    fn mbls_verify_multiple_batches_committee_span_msgtable_locate_rng(ctx: *mut MblsCtx, committees: *const mbls_committees, sigs96: *const u8, cmt_ids: *const u32,
+                                                                       n_cmt_ids: u64, cmt_off: *const u32, bits: *const u8, bits_stride: u32, mt: *const mbls_msgtable,
+                                                                       msg_idx: *const u32, n_sets: u64, batch_offsets: *const u32, sets_per_batch: u32,
+                                                                       n_batches: u64, results: *mut u8, set_results: *mut u8, set_status: *mut u32,
+                                                                       draw: MblsScalarSource, user: *mut c_void) -> c_int;
     fn mbls_ctx_set_vm_span_split(ctx: *mut MblsCtx, mode: c_int) -> c_int;
     fn mbls_plan_verify_multiple_span(limits: *const mbls_limits, n: u64, table_size: u64, stride_words: u64, locate: c_int, split_mode: c_int, split: *mut u32,
                                                 workspace_items: *mut u64) -> c_int;
@@ -1924,6 +1934,94 @@ impl CommitteeTable {
             std::panic::resume_unwind(payload);
         }
         (rc == 0 && ok == 1, sres.iter().map(|&b| rc == 0 && b == 1).collect())
+    }
+    /// `verify_multiple_aggregate_signatures_spans` once per batch (per block), in order, as ONE call on the GPU
+    /// (`mbls_verify_multiple_batches_committee_span_msgtable_rng`): one bool per batch, a bad batch rejects itself and nothing else. `rng` is left where the
+    /// per-batch calls would leave it. A malformed set, a key index or an entry index that names nothing gives false for every batch.
+    pub fn verify_multiple_aggregate_signatures_spans_batches<'a, R>(&self, rng: &mut R, batches: &[Vec<(&'a AggregateSignature, SpanKeys<'a>, u32)>],
+                                                                     table: &MessageTable) -> Vec<bool>
+    where
+        R: Rng + ?Sized,
+    {
+        self.vm_committee_span_batches(rng, batches, table, false).0
+    }
+    /// The same, and in the same call (`mbls_verify_multiple_batches_committee_span_msgtable_locate_rng`) which sets of the rejected batches are the bad ones.
+    pub fn verify_multiple_aggregate_signatures_spans_batches_locate<'a, R>(&self, rng: &mut R, batches: &[Vec<(&'a AggregateSignature, SpanKeys<'a>, u32)>],
+                                                                            table: &MessageTable) -> (Vec<bool>, Vec<Vec<bool>>)
+    where
+        R: Rng + ?Sized,
+    {
+        self.vm_committee_span_batches(rng, batches, table, true)
+    }
+    fn vm_committee_span_batches<'a, R>(&self, rng: &mut R, batches: &[Vec<(&'a AggregateSignature, SpanKeys<'a>, u32)>], table: &MessageTable,
+                                        locate: bool) -> (Vec<bool>, Vec<Vec<bool>>)
+    where
+        R: Rng + ?Sized,
+    {
+        let nb = batches.len();
+        if nb == 0 {
+            return (Vec::new(), Vec::new());
+        }
+        let n: usize = batches.iter().map(|b| b.len()).sum();
+        let mut boff: Vec<u32> = Vec::with_capacity(nb + 1);
+        boff.push(0);
+        let mut sigs = Vec::new();
+        let (mut ids, mut off, mut idx): (Vec<u32>, Vec<u32>, Vec<u32>) = (Vec::new(), vec![0], Vec::with_capacity(n));
+        let mut fields: Vec<&[u8]> = Vec::with_capacity(n);
+        for b in batches {
+            for (s, k, j) in b {
+                sigs.extend_from_slice(&s.point);
+                match *k {
+                    SpanKeys::Committees { ids: c, bits } => {
+                        assert!(c.iter().all(|id| id & VM_SET_SINGLE_KEY == 0), "committee ids have 31 bits");
+                        ids.extend_from_slice(c);
+                        fields.push(bits);
+                    }
+                    SpanKeys::SingleKey(index) => {
+                        assert!(index & VM_SET_SINGLE_KEY == 0, "key indices have 31 bits");
+                        ids.push(VM_SET_SINGLE_KEY | index);
+                        fields.push(&[]);
+                    }
+                }
+                off.push(ids.len() as u32);
+                idx.push(*j);
+            }
+            boff.push(idx.len() as u32);
+        }
+        let stride = ((fields.iter().map(|f| f.len()).max().unwrap_or(0).max(1) + 3) / 4 * 4) as u32;        // one stride for every field, a multiple of 4
+        let mut flat = vec![0u8; stride as usize * n];
+        for (i, f) in fields.iter().enumerate() {
+            flat[stride as usize * i..stride as usize * i + f.len()].copy_from_slice(f);
+        }
+        let n_ids = ids.len() as u64;
+        if ids.is_empty() {
+            ids.push(0);
+        }
+        let mut st = DrawState { rng, panic: None };
+        let mut res: Vec<u8> = vec![0; nb];
+        let mut sres: Vec<u8> = vec![if n == 0 { 1 } else { 0 }; if locate { n.max(1) } else { 0 }];
+        let rc = unsafe {
+            if locate {
+                mbls_verify_multiple_batches_committee_span_msgtable_locate_rng(ctx(), self.h, sigs.as_ptr(), ids.as_ptr(), n_ids, off.as_ptr(), flat.as_ptr(), stride,
+                                                                                table.h, idx.as_ptr(), n as u64, boff.as_ptr(), 0, nb as u64, res.as_mut_ptr(),
+                                                                                sres.as_mut_ptr(), std::ptr::null_mut(), draw_scalars::<R>,
+                                                                                &mut st as *mut DrawState<R> as *mut c_void)
+            } else {
+                mbls_verify_multiple_batches_committee_span_msgtable_rng(ctx(), self.h, sigs.as_ptr(), ids.as_ptr(), n_ids, off.as_ptr(), flat.as_ptr(), stride, table.h,
+                                                                         idx.as_ptr(), n as u64, boff.as_ptr(), 0, nb as u64, res.as_mut_ptr(), draw_scalars::<R>,
+                                                                         &mut st as *mut DrawState<R> as *mut c_void)
+            }
+        };
+        if let Some(payload) = st.panic.take() {
+            std::panic::resume_unwind(payload);
+        }
+        let out: Vec<bool> = res.iter().map(|&b| rc == 0 && b == 1).collect();
+        let per_set: Vec<Vec<bool>> = if locate {
+            (0..nb).map(|b| sres[boff[b] as usize..boff[b + 1] as usize].iter().map(|&x| rc == 0 && x == 1).collect()).collect()
+        } else {
+            Vec::new()
+        };
+        (out, per_set)
     }
     /// The split factor of the key phase of the span form above: 0 auto, else 1, 2, 4, 8 or 16 lanes per key list (`mbls_ctx_set_vm_span_split`).
     pub fn set_vm_span_split(mode: u32) -> bool {
