@@ -8,7 +8,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmbls_hip.so")
 SOURCES = ["mbls_kernels.hip", "mbls_stream.hip", "mbls_cms.hip", "mbls_vcs.hip", "mbls_vbg.hip"]
 DEPS = ["mbls_fp.h", "mbls_fp_asm.inc", "mbls_fpd_asm.inc", "mbls_towerd_asm.inc", "mbls_tower.h", "mbls_curve.h", "mbls_hash.h", "mbls_pairing.h", "mbls_lanes.h", "mbls_ops.h", "mbls_coop.h", "mbls_coop_prog.inc",
-        "mbls_constants.inc", "mbls_stream.h", "mbls_vmb.h", "mbls_vml.h", "mbls_vms.h", "mbls_vsl.h", "mbls_vmt.h", "mbls_mtb.h", "mbls_batch.h", "mbls_vmd.h", "mbls_vmr.h", "mbls_cmt.h", "mbls_cmt_lanes.h", "mbls_vmc.h", "mbls_cms.h", "mbls_cms_lanes.h", "mbls_cms_launch.h", "mbls_vcs.h", "mbls_vcs_launch.h", "mbls_vbg.h", "mbls_vbg_launch.h", os.path.join("..", "..", "include", "mbls.h")]
+        "mbls_constants.inc", "mbls_stream.h", "mbls_stream_plan.h","mbls_vmb.h", "mbls_vml.h", "mbls_vms.h", "mbls_vsl.h", "mbls_vmt.h", "mbls_mtb.h", "mbls_batch.h", "mbls_vmd.h", "mbls_vmr.h", "mbls_cmt.h", "mbls_cmt_lanes.h", "mbls_vmc.h", "mbls_cms.h", "mbls_cms_lanes.h", "mbls_cms_launch.h", "mbls_vcs.h", "mbls_vcs_launch.h", "mbls_vbg.h", "mbls_vbg_launch.h", os.path.join("..", "..", "include", "mbls.h")]
 
 
 STAMP = LIB + ".srchash"

@@ -2,7 +2,8 @@
 // host compiler can build them for the CPU tests (tests/host_emul/mbls_stream_harness.cpp): the cutting rule that packs calls into rounds,
 // the layout decision of a round, the bit arithmetic of the scatter into a caller's bitmap, and one destination dword of a committee call's re-strided bitfield
 // (tests/stream_cmt_emul/mbls_stream_cmt_harness.cpp), and the whole-call rule and the batch table of a verify_multiple stream
-// (tests/stream_vm_emul/mbls_stream_vm_harness.cpp). mbls_stream.hip runs exactly these.
+// (tests/stream_vm_emul/mbls_stream_vm_harness.cpp), and the one step and walk over a queue of calls that both rules are reached through. mbls_stream.hip runs
+// exactly these; what a round looks like once it is cut is mbls_stream_plan.h.
 #ifndef MBLS_STREAM_H
 #define MBLS_STREAM_H
 #include <stdint.h>
@@ -14,8 +15,11 @@
 #define MBLS_SFN static inline
 #endif
 
-// ---- cutting: the fill of the open round and the largest run of a call's items that still fits it
-struct mbls_stream_fill { uint64_t items, keys, msg_bytes; };
+// ---- cutting: the fill of the open round (its items, their keys and message bytes; on a stream of whole calls its sets and the calls they came in) and the
+// largest run of a call's items that still fits it. cost: what of round_items is used -- the items, plus one per whole call; cost == items + calls at all
+// times. The whole-call rule once kept a fill of its own: its type name and its name for the sets remain as aliases, so code written against it still builds.
+struct mbls_stream_fill { union { uint64_t items, sets; }; uint64_t keys, msg_bytes, calls, cost; };
+typedef mbls_stream_fill mbls_stream_vm_fill;
 
 MBLS_SFN uint64_t stream_item_keys(const mbls_stream_call_shape& c, uint64_t i) { return c.pk_offsets ? (uint64_t)(c.pk_offsets[i + 1] - c.pk_offsets[i]) : c.k; }
 MBLS_SFN uint64_t stream_item_msg(const mbls_stream_call_shape& c, uint64_t i) { return c.msg_offsets ? c.msg_offsets[i + 1] - c.msg_offsets[i] : c.msg_len; }
@@ -41,7 +45,7 @@ MBLS_SFN uint64_t stream_take(const mbls_stream_opts& o, mbls_stream_fill& f, co
         }
         t = i - first; f.keys = keys; f.msg_bytes = msg;
     }
-    f.items += t;
+    f.items += t; f.cost += t;
     return t;
 }
 
@@ -49,23 +53,57 @@ MBLS_SFN uint64_t stream_take(const mbls_stream_opts& o, mbls_stream_fill& f, co
 // never split. A call of n_sets sets costs n_sets + 1 of round_items -- its sets plus its signature pair, the Miller items of the per-set route, so that launch
 // stays within a round. A call joins the open round when its cost fits what is left; otherwise it closes the round and opens the next one. A call that costs more
 // than an empty round holds is refused at submit (stream_vm_fits). mbls_stream_cut_vm states this rule as data.
-struct mbls_stream_vm_fill { uint64_t cost, sets, calls; };
 MBLS_SFN uint64_t stream_vm_cost(uint64_t n_sets) { return n_sets + 1; }
+// what the round's calls cost together: its sets plus one per call
+MBLS_SFN uint64_t stream_vm_used(const mbls_stream_fill& f) { return f.cost; }
 MBLS_SFN int stream_vm_fits(const mbls_stream_opts& o, uint64_t n_sets) { return n_sets >= 1 && n_sets < o.round_items; }
-// 1: the call joined the open round (f advanced: it is batch f.calls - 1 and its sets start at the old f.sets); 0: it does not fit, the round is closed
-MBLS_SFN int stream_take_whole(const mbls_stream_opts& o, mbls_stream_vm_fill& f, uint64_t n_sets) {
-    const uint64_t cost = stream_vm_cost(n_sets);
-    if (cost > o.round_items - f.cost) return 0;
-    f.cost += cost; f.sets += n_sets; f.calls++;
+// 1: the call joined the open round (f advanced: it is batch f.calls - 1 and its sets start at the old f.items); 0: it does not fit, the round is closed
+MBLS_SFN int stream_take_whole(const mbls_stream_opts& o, mbls_stream_fill& f, uint64_t n_sets) {
+    if (stream_vm_cost(n_sets) > o.round_items - stream_vm_used(f)) return 0;
+    f.items += n_sets; f.calls++; f.cost += stream_vm_cost(n_sets);
     return 1;
 }
 // no further call fits: the smallest one costs 2
-MBLS_SFN int stream_vm_full(const mbls_stream_opts& o, const mbls_stream_vm_fill& f) { return o.round_items - f.cost < 2; }
+MBLS_SFN int stream_vm_full(const mbls_stream_opts& o, const mbls_stream_fill& f) { return o.round_items - stream_vm_used(f) < 2; }
 // the ragged batch table of a round whose calls hold call_sets[0 .. n_calls) sets: off[0 .. n_calls], off[b] the first set of batch b, off[n_calls] the round's sets
 MBLS_SFN void stream_vm_offsets(const uint64_t* call_sets, uint64_t n_calls, uint32_t* off) {
     uint64_t at = 0;
     for (uint64_t b = 0; b < n_calls; b++) { off[b] = (uint32_t)at; at += call_sets[b]; }
     off[n_calls] = (uint32_t)at;
+}
+
+// ---- the step every walk over a queue of calls takes, under either rule (`whole`: a stream of whole calls): call c is offered to the open round from its item
+// `first` on. items: how many joined (a whole call: all or none), at round_first of the round, as batch `batch` of it (whole calls; 0 otherwise); full: the round
+// is closed -- the rest of the call did not fit, or nothing more can join. The launcher (absorb), mbls_stream_cut and mbls_stream_cut_vm run this and nothing else.
+struct mbls_stream_step { uint64_t items, round_first, batch; int full; };
+MBLS_SFN mbls_stream_step stream_step(const mbls_stream_opts& o, int whole, mbls_stream_fill& f, const mbls_stream_call_shape& c, uint64_t first) {
+    const uint64_t before = f.items;
+    if (whole) {
+        if (!stream_take_whole(o, f, c.n)) return mbls_stream_step{0, before, 0, 1};
+        return mbls_stream_step{c.n, before, f.calls - 1, stream_vm_full(o, f)};
+    }
+    const uint64_t t = stream_take(o, f, c, first);
+    return mbls_stream_step{t, before, 0, first + t < c.n || f.items == o.round_items};
+}
+
+// the walk over a whole queue: every call offered until all of it has joined, a full round followed by an empty one, a round closed behind a call whose
+// flush_after is set. shape(j): call j; piece(j, first, step, round, fill): a piece and the fill it leaves. Returns the rounds, or -1 when a call joins no
+// empty round (which the checks at submit exclude).
+template <typename Shape, typename Piece>
+static inline int64_t stream_walk(const mbls_stream_opts& o, int whole, uint64_t n_calls, Shape shape, Piece piece) {
+    mbls_stream_fill f{}; uint64_t round = 0;
+    for (uint64_t j = 0; j < n_calls; j++) {
+        const mbls_stream_call_shape c = shape(j);
+        for (uint64_t first = 0; first < c.n;) {
+            const bool was_empty = !f.items;
+            const mbls_stream_step st = stream_step(o, whole, f, c, first);
+            if (!st.items && was_empty) return -1;
+            if (st.items) { piece(j, first, st, round, (const mbls_stream_fill&)f); first += st.items; }
+            if (st.full) { round++; f = mbls_stream_fill{}; }
+        }
+        if (c.flush_after && f.items) { round++; f = mbls_stream_fill{}; }
+    }
+    return (int64_t)(round + (f.items ? 1 : 0));
 }
 
 // the call as a whole: offsets non-decreasing (messages below 2^32 bytes, as the host entries require), and no item larger than an empty round.

@@ -2,18 +2,27 @@
 // public device entries out. Built on the public ABI only: mbls_ctx_get_limits, mbls_ctx_reserve[_keys], mbls_plan_workspace_items and the
 // three *_device verification entries (a message-table stream: their `_msgtable_device` forms), so every result comes out of the same verify_pipeline the parity
 // tests pin. One hook below the ABI, not exported from the library: a message table counts the calls its streams hold (mblsi_msgtable_stream_calls), which mbls_msgtable_clear consults.
-// A committee stream (mbls_stream_create_committee) launches mbls_fast_aggregate_verify_batch_committee_msgtable_device over the slot; its device pieces are staged
-// by k_stream_gather_cmt, which re-strides every call's bitfields to the stream's stride, and its table is held by two more such hooks (mblsi_committees_stream_*).
-// A verify_multiple stream (mbls_stream_create_vm_committee) takes whole batches: a call is never split (stream_take_whole, the rule mbls_stream_cut_vm states as
-// data), a round is ONE call of mbls_verify_multiple_batches_committee_msgtable_locate_device over the slot with a ragged batch table the launcher builds, staged
-// by k_stream_gather_vm and answered per call and per set by k_stream_scatter_vm; one more hook reserves that entry's own staging (mblsi_vbg_reserve_staging).
 //
-// Per stream: depth + 1 staging SLOTS (one round each: the open one and up to depth launched), one LAUNCHER thread that cuts the queue of
-// submitted calls into the open slot (stream_take, the rule mbls_stream_cut states as data), gathers the round's inputs into the slot on the
-// stream's gather stream (k_stream_gather; host pieces by hipMemcpyAsync), runs the device entry on the stream's main HIP stream, scatters
-// the results back to the callers (k_stream_scatter; host pieces through a pinned area) and records a blocking-sync event, and one COMPLETER
-// thread that waits on those events in order, copies host results, advances completed_through and frees the slot. Neither thread calls into
-// the context with the stream's lock held; no HIP call is made from a host callback.
+// A stream has ONE KIND, fixed at creation (stream_kind, mbls_stream_plan.h), and what differs between kinds stands in one place per question, as one switch:
+//   what a call's arrays are, and who may submit it      submit / submit_cmt / submit_vm, refused for another kind by wrong_kind
+//   whether a call may be split                          stream_kind_whole -> stream_step (mbls_stream.h), the one step absorb and both mbls_stream_cut* take
+//   which slot buffers exist, how large                  slot_buffers
+//   what the kind reserves in the context and its table  reserve_for_kind
+//   what a round looks like (tiles, host copies, tables) stream_plan_keys / _committee / _vm (mbls_stream_plan.h), bounded by meta_capacity
+//   which entry a round calls                            run_entry
+//   how answers reach a host caller                      answer_host_piece
+// KEYS (mbls_stream_create[_msgtable]): byte keys or key-table indices, message bytes or message-table indices; gathered by k_stream_gather, byte segment by byte
+// segment. COMMITTEE (mbls_stream_create_committee): mbls_fast_aggregate_verify_batch_committee_msgtable_device over the slot; device pieces are staged by
+// k_stream_gather_cmt, which re-strides every call's bitfields to the stream's stride, and the table is held by two more hooks (mblsi_committees_stream_*).
+// VM (mbls_stream_create_vm_committee): whole verify_multiple batches, never split; a round is ONE call of
+// mbls_verify_multiple_batches_committee_msgtable_locate_device over the slot with the ragged batch table of the plan, staged by k_stream_gather_vm and answered
+// per call and per set by k_stream_scatter_vm; one more hook reserves that entry's own staging (mblsi_vbg_reserve_staging).
+//
+// Per stream: depth + 1 staging SLOTS (one round each: the open one and up to depth launched), one LAUNCHER thread that cuts the queue of submitted calls into the
+// open slot (absorb), makes the round's plan and issues it (launch_round, the only launch function: gather on the stream's gather stream, the device entry and the
+// scatter on its main HIP stream, a blocking-sync event behind them), and one COMPLETER thread that waits on those events in order, copies host results out of the
+// pinned result areas, advances completed_through and frees the slot. Neither thread calls into the context with the stream's lock held; no HIP call is made from
+// a host callback.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -26,7 +35,7 @@
 #include <new>
 #include <thread>
 #include <vector>
-#include "mbls_stream.h"
+#include "mbls_stream_plan.h"
 
 // the table's count of calls that streams bound to it have taken and not completed (mbls_kernels.hip; mbls_msgtable_clear refuses while there are any)
 extern "C" __attribute__((visibility("hidden"))) void mblsi_msgtable_stream_calls(mbls_msgtable* t, long long delta);
@@ -42,14 +51,6 @@ extern "C" __attribute__((visibility("hidden"))) int mblsi_vbg_reserve_staging(m
 namespace {
 
 constexpr unsigned SWG = 64;                        // one wave per workgroup, like the rest of the library
-constexpr uint64_t GATHER_TILE = 128 * 1024;         // bytes per gather tile (a multiple of 16: tiles of one segment keep its alignment)
-constexpr uint64_t SCATTER_TILE = 4096;              // items per scatter tile, cut at multiples of this in the CALL's item space (so at bitmap words)
-constexpr uint64_t CMT_TILE = 256;                   // items per gather tile of a committee piece
-
-struct gtile { const uint8_t* src; uint8_t* dst; uint64_t bytes; };
-struct stile { uint8_t* res; uint32_t* st; uint64_t* bm; uint64_t call_first, items, round_first; };
-// a tile of a committee piece: the caller's four arrays at the tile's first item, and where its items lie in the round
-struct ctile { const uint8_t* sigs; const uint32_t* midx; const uint32_t* cid; const uint8_t* bits; uint32_t bits_len, items; uint64_t round_first; };
 
 // the wave's copy of one segment: 16-byte loads and stores where source and destination are both 16-byte aligned, dwords where both are 4-byte aligned, bytes
 // otherwise (ragged messages start anywhere)
@@ -127,14 +128,6 @@ __global__ __launch_bounds__(SWG) void k_stream_scatter(const stile* __restrict_
     }
 }
 
-namespace {
-// a tile of at most CMT_TILE sets of a verify_multiple call: the caller's five arrays at the tile's first set, and where its sets lie in the round
-struct vtile { const uint8_t* sigs; const uint32_t* cid; const uint8_t* bits; const uint32_t* midx; const uint64_t* rands; uint32_t bits_len, items; uint64_t round_first; };
-// a device call's outputs: sets [call_first, call_first + items) of the call are sets [round_first, ...) of the round; the tile at call_first = 0 also carries the
-// call's batch byte and word, which the round keeps at n_round + batch
-struct vstile { uint8_t* res; uint32_t* st; uint8_t* set_res; uint32_t* set_st; uint64_t call_first, items, round_first, batch_at; };
-}  // namespace
-
 // One workgroup per tile of a device call of a verify_multiple stream: signatures, set words, message indices and scalars copied to the round's arrays at
 // round_first (wave_copy), the bitfields re-strided from bits_len bytes at any address to the slot's bits_stride (stream_bits_dword: every dword of every set's
 // stride is written -- for bits_len = 0 zeros, and nothing is read --, so a slot never shows a round the bits or scalars of the round before).
@@ -172,27 +165,22 @@ __global__ __launch_bounds__(SWG) void k_stream_scatter_vm(const vstile* __restr
 
 namespace {
 
-struct call_rec {
-    uint64_t ticket = 0; bool host = false; bool split = false;
-    mbls_stream_call_shape shape{};
-    const uint8_t* sigs = nullptr; const uint8_t* msgs = nullptr; const uint8_t* keys = nullptr;   // keys: bytes or indices (a committee call: its committee ids)
-    const uint8_t* bits = nullptr; uint32_t bits_len = 0;                     // a committee call: its bitfields, bits_len bytes per item
-    uint8_t* res = nullptr; uint64_t* bm = nullptr; uint32_t* st = nullptr;
+struct call_rec : stream_call {
+    uint64_t ticket = 0; bool split = false;
     hipEvent_t ev = nullptr;                                                 // device submits: recorded on the caller's stream
-    // a verify_multiple call (shape.n sets; keys: its set words; res / st: ONE byte and word): its scalars, its per-set outputs, the groups it may form
-    const uint64_t* rands = nullptr; uint8_t* set_res = nullptr; uint32_t* set_st = nullptr; uint64_t groups = 0;
 };
 struct piece_rec { std::shared_ptr<call_rec> c; uint64_t first, items, round_first; uint64_t batch = 0; };   // batch: a verify_multiple call's batch of the round
 
+// a slot's buffers: the round's arrays on the device (dev[RA_*]; RA_KEYS holds a committee or verify_multiple round's fields), its results and the meta area, and
+// in pinned memory the meta area, the results of host pieces and the mirrors the kind stages host pieces through (pin[RA_*]; slot_buffers says which exist)
 struct slot {
-    uint8_t *d_sigs = nullptr, *d_msgs = nullptr, *d_keys = nullptr, *d_res = nullptr, *d_meta = nullptr; uint32_t* d_st = nullptr;
-    uint8_t *h_meta = nullptr, *h_res = nullptr; uint32_t* h_st = nullptr;      // pinned
-    uint32_t* d_cid = nullptr; uint8_t* h_bits = nullptr;                       // a committee stream: the round's committee ids (its fields lie in d_keys); pinned: host pieces' fields, zero-extended
-    uint64_t* d_rands = nullptr; mbls_stream_vm_fill vfill{};                   // a verify_multiple stream: the round's scalars; its fill (fill.items mirrors vfill.cost)
-    uint8_t* h_sigs = nullptr; uint64_t* h_rands = nullptr; uint32_t *h_cid = nullptr, *h_midx = nullptr;   // and the pinned mirrors of its host calls' arrays (one block: h_sigs)
+    uint8_t* dev[RA_COUNT] = {}; uint8_t* pin[RA_COUNT] = {};
+    uint8_t *d_res = nullptr, *d_meta = nullptr; uint32_t* d_st = nullptr;
+    uint8_t *h_meta = nullptr, *h_res = nullptr; uint32_t* h_st = nullptr;
     hipEvent_t gev = nullptr, done = nullptr;
     std::vector<piece_rec> pieces;
     mbls_stream_fill fill{};
+    stream_round_plan plan;
     bool full = false;
     uint64_t first_ticket = 0, done_through = 0;
     int rc = MBLS_OK;
@@ -202,11 +190,10 @@ struct slot {
 
 struct mbls_stream {
     mbls_ctx* ctx = nullptr; const mbls_keytable* tab = nullptr;
-    mbls_msgtable* mt = nullptr;                     // non-null: a message-table stream -- a call's "message bytes" are its uint32 table indices (msg_len = 4)
-    mbls_committees* cm = nullptr; uint32_t bits_stride = 0; bool cm_bound = false;   // cm non-null: a committee stream (mt is set too) -- a call's keys are committee ids and bitfields
-    bool vm = false;                                 // a verify_multiple stream (cm and mt are set): a call is a batch, a round one call of the batches entry
-    int mode = 0, fmt = MBLS_PK_UNCOMPRESSED, dev = 0; size_t unit = 96;
-    mbls_stream_opts o{};
+    stream_consts k{};                               // the kind, fixed at creation, and the constants a round's plan reads (k.o: the options with their defaults filled in)
+    mbls_msgtable* mt = nullptr;                     // the message table of a committee or verify_multiple stream; on a keys stream non-null means a call's "message bytes" are its uint32 table indices (msg_len = 4)
+    mbls_committees* cm = nullptr;                   // the committee table of a committee or verify_multiple stream, set once it is bound to k.bits_stride (until free_stream)
+    int mode = 0, fmt = MBLS_PK_UNCOMPRESSED, dev = 0;
     uint64_t meta_bytes = 0;
     hipStream_t hs = nullptr, gs = nullptr;
     std::vector<slot> slots;
@@ -234,244 +221,112 @@ int fail(mbls_stream* s, int rc, const char* fmt, ...) {
     return rc;
 }
 
-uint64_t meta_capacity(const mbls_stream_opts& o, size_t unit, bool committee, bool vm) {
-    const uint64_t R = o.round_items;
-    // a verify_multiple round: at most R / 2 calls; a call takes at most sets / tile + 1 gather tiles and as many scatter tiles; the batch table
-    if (vm) return (R + R / CMT_TILE + 1) * sizeof(vtile) + (R + R / SCATTER_TILE + 1) * sizeof(vstile) + 4 * (R + 2) + 64;
-    const uint64_t bytes = 96 * R + o.round_msg_bytes + unit * o.round_keys;
-    const uint64_t ng = bytes / GATHER_TILE + 3 * R + 3, ns = 2 * R + R / SCATTER_TILE + 1;      // (a piece takes at most items / tile + 2 scatter tiles)
-    const uint64_t nc = committee ? R + R / CMT_TILE + 1 : 0;                                    // (and at most items / tile + 1 committee tiles)
-    return ng * sizeof(gtile) + ns * sizeof(stile) + nc * sizeof(ctile) + 4 * (R + 1) + 8 * (R + 1) + 64;
-}
-
-// The round in the open slot: gather, the device entry, scatter, completion event. Runs on the launcher thread without the stream's lock.
-int launch_round(mbls_stream* s, slot& sl) {
-    const uint64_t n = sl.fill.items;
-    mbls_stream_layout lay{};
-    for (size_t p = 0; p < sl.pieces.size(); p++) stream_layout_add(lay, p == 0, sl.pieces[p].c->shape);
-    if (s->mode == MBLS_STREAM_VERIFY) { lay.keys_uniform = 1; lay.k = 1; }
-    // the meta area, packed: gather tiles | scatter tiles | key offsets | message offsets -- one upload from pinned memory
-    std::vector<gtile> gt; std::vector<stile> stv;
-    std::vector<uint32_t> pkoff; std::vector<uint64_t> moff;
-    if (!lay.keys_uniform) pkoff.resize(n + 1);
-    if (!lay.msgs_uniform) moff.resize(n + 1);
-    uint64_t key_cur = 0, msg_cur = 0, gathered = 0;
-    bool any_host = false;
-    hipError_t e = hipSuccess;
-    auto seg = [&](bool host, const uint8_t* src, uint8_t* dst, uint64_t bytes) {
-        if (!bytes) return;
-        gathered += bytes;
-        if (host) { if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s->gs); return; }
-        for (uint64_t o = 0; o < bytes; o += GATHER_TILE) gt.push_back(gtile{src + o, dst + o, std::min(GATHER_TILE, bytes - o)});
-    };
-    hipEvent_t last_ev = nullptr;
-    std::vector<ctile> ct;
-    const uint64_t bs = s->bits_stride;
-    for (const piece_rec& p : sl.pieces) {
-        const call_rec& c = *p.c; const mbls_stream_call_shape& sh = c.shape;
-        if (!c.host && c.ev != last_ev) { if (e == hipSuccess) e = hipStreamWaitEvent(s->gs, c.ev, 0); last_ev = c.ev; }
-        any_host |= c.host;
-        if (s->cm && !c.host) {       // a device piece of a committee call: one record per CMT_TILE items, the four arrays in one kernel (k_stream_gather_cmt)
-            const uint32_t* midx = (const uint32_t*)c.msgs; const uint32_t* cid = (const uint32_t*)c.keys;
-            for (uint64_t a = p.first; a < p.first + p.items; a += CMT_TILE)
-                ct.push_back(ctile{c.sigs + 96 * a, midx + a, cid + a, c.bits + (uint64_t)c.bits_len * a, c.bits_len,
-                                   (uint32_t)std::min(CMT_TILE, p.first + p.items - a), p.round_first + (a - p.first)});
-            gathered += (96 + 4 + 4 + (uint64_t)c.bits_len) * p.items;
-        } else if (s->cm) {           // a host piece: three plain copies, and the fields zero-extended to the stride on their way through pinned memory
-            seg(true, c.sigs + 96 * p.first, sl.d_sigs + 96 * p.round_first, 96 * p.items);
-            seg(true, c.msgs + 4 * p.first, sl.d_msgs + 4 * p.round_first, 4 * p.items);
-            seg(true, c.keys + 4 * p.first, (uint8_t*)(sl.d_cid + p.round_first), 4 * p.items);
-            uint8_t* hb = sl.h_bits + bs * p.round_first; const uint8_t* src = c.bits + (uint64_t)c.bits_len * p.first;
-            if (c.bits_len == bs) memcpy(hb, src, bs * p.items);
-            else for (uint64_t i = 0; i < p.items; i++) { memcpy(hb + bs * i, src + (uint64_t)c.bits_len * i, c.bits_len); memset(hb + bs * i + c.bits_len, 0, bs - c.bits_len); }
-            seg(true, hb, sl.d_keys + bs * p.round_first, bs * p.items);
-            gathered -= (bs - c.bits_len) * p.items;                // (the statistic counts the bytes the call carries)
-        }
-        if (!s->cm) {
-        seg(c.host, c.sigs + 96 * p.first, sl.d_sigs + 96 * p.round_first, 96 * p.items);
-        const uint64_t m0 = sh.msg_offsets ? sh.msg_offsets[p.first] : (uint64_t)sh.msg_len * p.first;
-        const uint64_t mb = sh.msg_offsets ? sh.msg_offsets[p.first + p.items] - m0 : (uint64_t)sh.msg_len * p.items;
-        seg(c.host, c.msgs + m0, sl.d_msgs + msg_cur, mb);
-        const uint64_t k0 = sh.pk_offsets ? sh.pk_offsets[p.first] : (uint64_t)sh.k * p.first;
-        const uint64_t kc = sh.pk_offsets ? sh.pk_offsets[p.first + p.items] - k0 : (uint64_t)sh.k * p.items;
-        seg(c.host, c.keys + s->unit * k0, sl.d_keys + s->unit * key_cur, s->unit * kc);
-        if (!lay.keys_uniform || !lay.msgs_uniform)
-        for (uint64_t i = 0; i < p.items; i++) {
-            if (!lay.keys_uniform) pkoff[p.round_first + i] = (uint32_t)(key_cur + (sh.pk_offsets ? sh.pk_offsets[p.first + i] - k0 : (uint64_t)sh.k * i));
-            if (!lay.msgs_uniform) moff[p.round_first + i] = msg_cur + (sh.msg_offsets ? sh.msg_offsets[p.first + i] - m0 : (uint64_t)sh.msg_len * i);
-        }
-        key_cur += kc; msg_cur += mb;
-        }
-        if (!c.host)
-            for (uint64_t a = p.first; a < p.first + p.items;) {
-                const uint64_t b = std::min(p.first + p.items, (a / SCATTER_TILE + 1) * SCATTER_TILE);
-                stv.push_back(stile{c.res, c.st, c.bm, a, b - a, p.round_first + (a - p.first)});
-                a = b;
-            }
-    }
-    if (!lay.keys_uniform) pkoff[n] = (uint32_t)key_cur;
-    if (!lay.msgs_uniform) moff[n] = msg_cur;
-    auto up = [](uint64_t x, uint64_t a) { return (x + a - 1) / a * a; };
-    const uint64_t at_g = 0, at_s = up(at_g + gt.size() * sizeof(gtile), 16), at_k = up(at_s + stv.size() * sizeof(stile), 8), at_m = up(at_k + pkoff.size() * 4, 8);
-    const uint64_t at_c = up(at_m + moff.size() * 8, 16), off = at_c + ct.size() * sizeof(ctile);
-    if (off > s->meta_bytes) return fail(s, MBLS_ERR_DEVICE, "internal: round meta of %llu bytes exceeds the slot's %llu", (unsigned long long)off, (unsigned long long)s->meta_bytes);
-    if (!gt.empty()) memcpy(sl.h_meta + at_g, gt.data(), gt.size() * sizeof(gtile));
-    if (!stv.empty()) memcpy(sl.h_meta + at_s, stv.data(), stv.size() * sizeof(stile));
-    if (!pkoff.empty()) memcpy(sl.h_meta + at_k, pkoff.data(), pkoff.size() * 4);
-    if (!moff.empty()) memcpy(sl.h_meta + at_m, moff.data(), moff.size() * 8);
-    if (!ct.empty()) memcpy(sl.h_meta + at_c, ct.data(), ct.size() * sizeof(ctile));
-    if (e == hipSuccess && off) e = hipMemcpyAsync(sl.d_meta, sl.h_meta, off, hipMemcpyHostToDevice, s->gs);
-    if (e == hipSuccess && !gt.empty()) { hipLaunchKernelGGL(k_stream_gather, dim3((unsigned)gt.size()), dim3(SWG), 0, s->gs, (const gtile*)(sl.d_meta + at_g)); e = hipGetLastError(); }
-    if (e == hipSuccess && !ct.empty()) {
-        hipLaunchKernelGGL(k_stream_gather_cmt, dim3((unsigned)ct.size()), dim3(SWG), 0, s->gs, (const ctile*)(sl.d_meta + at_c), sl.d_sigs, (uint32_t*)sl.d_msgs, sl.d_cid, sl.d_keys,
-                           s->bits_stride);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(sl.gev, s->gs);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s->hs, sl.gev, 0);
-    if (e != hipSuccess) return fail(s, MBLS_ERR_DEVICE, "gather: %s", hipGetErrorString(e));
-    const uint64_t* d_moff = lay.msgs_uniform ? nullptr : (const uint64_t*)(sl.d_meta + at_m);
-    const uint32_t* d_pkoff = lay.keys_uniform ? nullptr : (const uint32_t*)(sl.d_meta + at_k);
-    const uint32_t msg_len = lay.msgs_uniform ? lay.msg_len : 0, k = lay.keys_uniform ? lay.k : 0;
+// the public entry a round of this kind is: one call over the slot's arrays, dense in round order (lock not held)
+int run_entry(mbls_stream* s, slot& sl, const stream_round_plan& r) {
+    const uint64_t n = r.n;
+    uint8_t* const d_sigs = sl.dev[RA_SIGS]; uint8_t* const d_msgs = sl.dev[RA_MSGS]; uint8_t* const d_keys = sl.dev[RA_KEYS];
+    const uint32_t* d_midx = (const uint32_t*)d_msgs; const uint32_t* d_cid = (const uint32_t*)sl.dev[RA_CID];
     int rc;
-    if (s->cm)           // the round's four arrays, dense in round order, every field at the stream's stride
-        rc = mbls_fast_aggregate_verify_batch_committee_msgtable_device(s->ctx, s->cm, sl.d_sigs, s->mt, (const uint32_t*)sl.d_msgs, sl.d_cid, sl.d_keys, s->bits_stride, n,
-                                                                        sl.d_res, nullptr, sl.d_st, s->hs);
-    else if (s->mt) {    // the staged "message bytes" are the items' table indices, dense in round order (every call has msg_len = 4 and no offsets)
-        const uint32_t* d_midx = (const uint32_t*)sl.d_msgs;
-        if (s->mode == MBLS_STREAM_VERIFY)
-            rc = mbls_verify_batch_msgtable_device(s->ctx, sl.d_sigs, s->mt, d_midx, sl.d_keys, s->fmt, n, sl.d_res, nullptr, sl.d_st, s->hs);
-        else if (s->tab)
-            rc = mbls_fast_aggregate_verify_batch_indexed_msgtable_device(s->ctx, s->tab, sl.d_sigs, s->mt, d_midx, (const uint32_t*)sl.d_keys, d_pkoff, n, k,
-                                                                          sl.d_res, nullptr, sl.d_st, s->hs);
-        else
-            rc = mbls_fast_aggregate_verify_batch_msgtable_device(s->ctx, sl.d_sigs, s->mt, d_midx, sl.d_keys, s->fmt, d_pkoff, n, k, sl.d_res, nullptr, sl.d_st, s->hs);
-    } else if (s->mode == MBLS_STREAM_VERIFY)
-        rc = mbls_verify_batch_device(s->ctx, sl.d_sigs, sl.d_msgs, msg_len, d_moff, sl.d_keys, s->fmt, n, sl.d_res, nullptr, sl.d_st, s->hs);
-    else if (s->tab)
-        rc = mbls_fast_aggregate_verify_batch_indexed_device(s->ctx, s->tab, sl.d_sigs, sl.d_msgs, msg_len, d_moff, (const uint32_t*)sl.d_keys, d_pkoff, n, k,
-                                                             sl.d_res, nullptr, sl.d_st, s->hs);
-    else
-        rc = mbls_fast_aggregate_verify_batch_device(s->ctx, sl.d_sigs, sl.d_msgs, msg_len, d_moff, sl.d_keys, s->fmt, d_pkoff, n, k, sl.d_res, nullptr, sl.d_st, s->hs);
+    switch (s->k.kind) {
+        case STREAM_KEYS: {
+            const uint64_t* d_moff = r.lay.msgs_uniform ? nullptr : (const uint64_t*)(sl.d_meta + r.at_m);
+            const uint32_t* d_pkoff = r.lay.keys_uniform ? nullptr : (const uint32_t*)(sl.d_meta + r.at_k);
+            const uint32_t msg_len = r.lay.msgs_uniform ? r.lay.msg_len : 0, k = r.lay.keys_uniform ? r.lay.k : 0;
+            const bool verify = s->mode == MBLS_STREAM_VERIFY;
+            // a message table: the staged "message bytes" are the items' table indices, dense in round order (every call has msg_len = 4 and no offsets)
+            if (s->mt && verify) rc = mbls_verify_batch_msgtable_device(s->ctx, d_sigs, s->mt, d_midx, d_keys, s->fmt, n, sl.d_res, nullptr, sl.d_st, s->hs);
+            else if (s->mt && s->tab)
+                rc = mbls_fast_aggregate_verify_batch_indexed_msgtable_device(s->ctx, s->tab, d_sigs, s->mt, d_midx, (const uint32_t*)d_keys, d_pkoff, n, k, sl.d_res, nullptr, sl.d_st, s->hs);
+            else if (s->mt) rc = mbls_fast_aggregate_verify_batch_msgtable_device(s->ctx, d_sigs, s->mt, d_midx, d_keys, s->fmt, d_pkoff, n, k, sl.d_res, nullptr, sl.d_st, s->hs);
+            else if (verify) rc = mbls_verify_batch_device(s->ctx, d_sigs, d_msgs, msg_len, d_moff, d_keys, s->fmt, n, sl.d_res, nullptr, sl.d_st, s->hs);
+            else if (s->tab)
+                rc = mbls_fast_aggregate_verify_batch_indexed_device(s->ctx, s->tab, d_sigs, d_msgs, msg_len, d_moff, (const uint32_t*)d_keys, d_pkoff, n, k, sl.d_res, nullptr, sl.d_st, s->hs);
+            else rc = mbls_fast_aggregate_verify_batch_device(s->ctx, d_sigs, d_msgs, msg_len, d_moff, d_keys, s->fmt, d_pkoff, n, k, sl.d_res, nullptr, sl.d_st, s->hs);
+            break;
+        }
+        case STREAM_COMMITTEE:
+            rc = mbls_fast_aggregate_verify_batch_committee_msgtable_device(s->ctx, s->cm, d_sigs, s->mt, d_midx, d_cid, d_keys, s->k.bits_stride, n, sl.d_res, nullptr, sl.d_st, s->hs);
+            break;
+        default:    // STREAM_VM: the batches entry with the ragged table of the meta area; the batches' bytes and words behind the sets'
+            rc = mbls_verify_multiple_batches_committee_msgtable_locate_device(s->ctx, s->cm, d_sigs, d_cid, d_keys, s->k.bits_stride, s->mt, d_midx, (const uint64_t*)sl.dev[RA_RANDS], n,
+                                                                               (const uint32_t*)(sl.d_meta + r.at_k), 0, r.batches, r.max_groups, sl.d_res + n, sl.d_st + n,
+                                                                               sl.d_res, sl.d_st, s->hs);
+            if (rc) return fail(s, rc, "round of %llu sets in %llu batches: %s", (unsigned long long)n, (unsigned long long)r.batches, mbls_last_error(s->ctx));
+    }
     if (rc) return fail(s, rc, "round of %llu items: %s", (unsigned long long)n, mbls_last_error(s->ctx));
-    if (!stv.empty()) { hipLaunchKernelGGL(k_stream_scatter, dim3((unsigned)stv.size()), dim3(SWG), 0, s->hs, (const stile*)(sl.d_meta + at_s), (const uint8_t*)sl.d_res, (const uint32_t*)sl.d_st); e = hipGetLastError(); }
-    if (e == hipSuccess && any_host) e = hipMemcpyAsync(sl.h_res, sl.d_res, n, hipMemcpyDeviceToHost, s->hs);
-    if (e == hipSuccess && any_host) e = hipMemcpyAsync(sl.h_st, sl.d_st, 4 * n, hipMemcpyDeviceToHost, s->hs);
-    if (e == hipSuccess) e = hipEventRecord(sl.done, s->hs);
-    if (e != hipSuccess) return fail(s, MBLS_ERR_DEVICE, "scatter: %s", hipGetErrorString(e));
-    std::lock_guard<std::mutex> g(s->mu);
-    s->stats.gathered_bytes += gathered;
     return MBLS_OK;
 }
 
-// The round of a verify_multiple stream: every piece is a whole call and a batch of the round. Gather (k_stream_gather_vm; host calls by copies, their fields
-// zero-extended in pinned memory), the ragged batch table with the meta area, ONE call of the public batches entry over the slot, scatter (k_stream_scatter_vm;
-// host calls through the pinned result areas). The slot keeps the sets' bytes and words at [0, n) of d_res / d_st and the batches' behind them at [n, n + B).
-int launch_round_vm(mbls_stream* s, slot& sl) {
-    const uint64_t n = sl.vfill.sets, B = sl.vfill.calls, bs = s->bits_stride;
-    std::vector<vtile> vt; std::vector<vstile> stv;
-    std::vector<uint64_t> sets(B); std::vector<uint32_t> boff(B + 1);
-    uint64_t gathered = 0, max_groups = 0;
-    bool any_host = false;
+// The round in the open slot: its plan (mbls_stream_plan.h), then the plan issued. On the gather stream the waits on the callers' events and the host copies in
+// piece order, the one meta upload, the gather kernel of every tile list the plan filled, gev; on the main stream the wait on gev, the entry, the scatter kernel,
+// the two result copies if a piece was a host piece, the completion event. Runs on the launcher thread without the stream's lock.
+int launch_round(mbls_stream* s, slot& sl) {
+    stream_round_plan& r = sl.plan;
+    stream_plan(s->k, sl.pieces.data(), sl.pieces.size(), sl.dev, r);
+    if (r.bytes > s->meta_bytes)
+        return fail(s, MBLS_ERR_DEVICE, "internal: round meta of %llu bytes exceeds the slot's %llu", (unsigned long long)r.bytes, (unsigned long long)s->meta_bytes);
+    stream_plan_pack(r, sl.h_meta);
     hipError_t e = hipSuccess;
     hipEvent_t last_ev = nullptr;
-    auto up_h = [&](const void* src, void* dst, uint64_t bytes) { if (bytes && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s->gs); };
-    // host calls: their five arrays are laid into the slot's pinned mirrors at their sets' places in the round (the fields zero-extended on the way), and every
-    // RUN of neighbouring host calls goes up in five copies -- a round of small host calls would otherwise pay five pageable copies per call
-    uint64_t run_lo = 0, run_hi = 0;
-    auto flush_run = [&]() {
-        const uint64_t a = run_lo, m = run_hi - run_lo;
-        if (!m) return;
-        up_h(sl.h_sigs + 96 * a, sl.d_sigs + 96 * a, 96 * m); up_h(sl.h_cid + a, sl.d_cid + a, 4 * m); up_h(sl.h_midx + a, sl.d_msgs + 4 * a, 4 * m);
-        up_h(sl.h_rands + a, sl.d_rands + a, 8 * m); up_h(sl.h_bits + bs * a, sl.d_keys + bs * a, bs * m);
-        run_lo = run_hi = 0;
-    };
-    for (const piece_rec& p : sl.pieces) {
-        const call_rec& c = *p.c; const uint64_t m = p.items, r0 = p.round_first;
-        sets[p.batch] = m; max_groups += c.groups;
-        gathered += (96 + 4 + 4 + 8 + (uint64_t)c.bits_len) * m;
-        if (c.host) {
-            any_host = true;
-            if (run_hi != r0) { flush_run(); run_lo = r0; }
-            run_hi = r0 + m;
-            memcpy(sl.h_sigs + 96 * r0, c.sigs, 96 * m); memcpy(sl.h_cid + r0, c.keys, 4 * m); memcpy(sl.h_midx + r0, c.msgs, 4 * m); memcpy(sl.h_rands + r0, c.rands, 8 * m);
-            uint8_t* hb = sl.h_bits + bs * r0;
-            if (c.bits_len == bs) { if (bs) memcpy(hb, c.bits, bs * m); }
-            else for (uint64_t i = 0; i < m; i++) { if (c.bits_len) memcpy(hb + bs * i, c.bits + (uint64_t)c.bits_len * i, c.bits_len); memset(hb + bs * i + c.bits_len, 0, bs - c.bits_len); }
-            continue;
+    size_t h = 0;
+    for (size_t i = 0; i <= sl.pieces.size(); i++) {
+        for (; h < r.hc.size() && r.hc[h].piece == i; h++) {
+            const stream_hcopy& c = r.hc[h];
+            uint8_t* const pinned = sl.pin[c.arr] + c.at;
+            switch (c.how) {
+                case HC_STAGE: memcpy(pinned, c.src, c.bytes); break;
+                case HC_WIDEN: stream_widen(pinned, c.src, c.items, c.len, c.bytes / c.items); break;
+                default:
+                    if (e == hipSuccess) e = hipMemcpyAsync(sl.dev[c.arr] + c.at, c.how == HC_UPLOAD ? pinned : c.src, c.bytes, hipMemcpyHostToDevice, s->gs);
+            }
         }
-        flush_run();
-        if (c.ev != last_ev) { if (e == hipSuccess) e = hipStreamWaitEvent(s->gs, c.ev, 0); last_ev = c.ev; }
-        const uint32_t* cid = (const uint32_t*)c.keys; const uint32_t* midx = (const uint32_t*)c.msgs;
-        for (uint64_t a = 0; a < m; a += CMT_TILE)
-            vt.push_back(vtile{c.sigs + 96 * a, cid + a, c.bits_len ? c.bits + (uint64_t)c.bits_len * a : nullptr, midx + a, c.rands + a, c.bits_len,
-                               (uint32_t)std::min(CMT_TILE, m - a), r0 + a});
-        for (uint64_t a = 0; a < m; a += SCATTER_TILE)
-            stv.push_back(vstile{c.res, c.st, c.set_res, c.set_st, a, std::min(SCATTER_TILE, m - a), r0 + a, n + p.batch});
+        if (i == sl.pieces.size()) break;
+        const call_rec& c = *sl.pieces[i].c;
+        if (!c.host && c.ev != last_ev) { if (e == hipSuccess) e = hipStreamWaitEvent(s->gs, c.ev, 0); last_ev = c.ev; }
     }
-    flush_run();
-    stream_vm_offsets(sets.data(), B, boff.data());
-    auto up = [](uint64_t x, uint64_t a) { return (x + a - 1) / a * a; };
-    const uint64_t at_v = 0, at_s = up(at_v + vt.size() * sizeof(vtile), 16), at_o = up(at_s + stv.size() * sizeof(vstile), 16), off = at_o + 4 * (B + 1);
-    if (off > s->meta_bytes) return fail(s, MBLS_ERR_DEVICE, "internal: round meta of %llu bytes exceeds the slot's %llu", (unsigned long long)off, (unsigned long long)s->meta_bytes);
-    if (!vt.empty()) memcpy(sl.h_meta + at_v, vt.data(), vt.size() * sizeof(vtile));
-    if (!stv.empty()) memcpy(sl.h_meta + at_s, stv.data(), stv.size() * sizeof(vstile));
-    memcpy(sl.h_meta + at_o, boff.data(), 4 * (B + 1));
-    if (e == hipSuccess) e = hipMemcpyAsync(sl.d_meta, sl.h_meta, off, hipMemcpyHostToDevice, s->gs);
-    if (e == hipSuccess && !vt.empty()) {
-        hipLaunchKernelGGL(k_stream_gather_vm, dim3((unsigned)vt.size()), dim3(SWG), 0, s->gs, (const vtile*)(sl.d_meta + at_v), sl.d_sigs, sl.d_cid, sl.d_keys, (uint32_t*)sl.d_msgs,
-                           sl.d_rands, s->bits_stride);
+    if (e == hipSuccess && r.bytes) e = hipMemcpyAsync(sl.d_meta, sl.h_meta, r.bytes, hipMemcpyHostToDevice, s->gs);
+    if (e == hipSuccess && !r.gt.empty()) { hipLaunchKernelGGL(k_stream_gather, dim3((unsigned)r.gt.size()), dim3(SWG), 0, s->gs, (const gtile*)(sl.d_meta + r.at_g)); e = hipGetLastError(); }
+    if (e == hipSuccess && !r.ct.empty()) {
+        hipLaunchKernelGGL(k_stream_gather_cmt, dim3((unsigned)r.ct.size()), dim3(SWG), 0, s->gs, (const ctile*)(sl.d_meta + r.at_c), sl.dev[RA_SIGS], (uint32_t*)sl.dev[RA_MSGS],
+                           (uint32_t*)sl.dev[RA_CID], sl.dev[RA_KEYS], s->k.bits_stride);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && !r.vt.empty()) {
+        hipLaunchKernelGGL(k_stream_gather_vm, dim3((unsigned)r.vt.size()), dim3(SWG), 0, s->gs, (const vtile*)(sl.d_meta + r.at_g), sl.dev[RA_SIGS], (uint32_t*)sl.dev[RA_CID], sl.dev[RA_KEYS],
+                           (uint32_t*)sl.dev[RA_MSGS], (uint64_t*)sl.dev[RA_RANDS], s->k.bits_stride);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(sl.gev, s->gs);
     if (e == hipSuccess) e = hipStreamWaitEvent(s->hs, sl.gev, 0);
     if (e != hipSuccess) return fail(s, MBLS_ERR_DEVICE, "gather: %s", hipGetErrorString(e));
-    const int rc = mbls_verify_multiple_batches_committee_msgtable_locate_device(s->ctx, s->cm, sl.d_sigs, sl.d_cid, sl.d_keys, s->bits_stride, s->mt, (const uint32_t*)sl.d_msgs,
-                                                                                 sl.d_rands, n, (const uint32_t*)(sl.d_meta + at_o), 0, B, max_groups, sl.d_res + n, sl.d_st + n,
-                                                                                 sl.d_res, sl.d_st, s->hs);
-    if (rc) return fail(s, rc, "round of %llu sets in %llu batches: %s", (unsigned long long)n, (unsigned long long)B, mbls_last_error(s->ctx));
-    if (!stv.empty()) { hipLaunchKernelGGL(k_stream_scatter_vm, dim3((unsigned)stv.size()), dim3(SWG), 0, s->hs, (const vstile*)(sl.d_meta + at_s), (const uint8_t*)sl.d_res, (const uint32_t*)sl.d_st); e = hipGetLastError(); }
-    if (e == hipSuccess && any_host) e = hipMemcpyAsync(sl.h_res, sl.d_res, n + B, hipMemcpyDeviceToHost, s->hs);
-    if (e == hipSuccess && any_host) e = hipMemcpyAsync(sl.h_st, sl.d_st, 4 * (n + B), hipMemcpyDeviceToHost, s->hs);
+    const int rc = run_entry(s, sl, r);
+    if (rc) return rc;
+    const uint64_t answers = r.n + r.batches;
+    if (!r.st.empty()) { hipLaunchKernelGGL(k_stream_scatter, dim3((unsigned)r.st.size()), dim3(SWG), 0, s->hs, (const stile*)(sl.d_meta + r.at_s), (const uint8_t*)sl.d_res, (const uint32_t*)sl.d_st); e = hipGetLastError(); }
+    if (!r.vst.empty()) { hipLaunchKernelGGL(k_stream_scatter_vm, dim3((unsigned)r.vst.size()), dim3(SWG), 0, s->hs, (const vstile*)(sl.d_meta + r.at_s), (const uint8_t*)sl.d_res, (const uint32_t*)sl.d_st); e = hipGetLastError(); }
+    if (e == hipSuccess && r.any_host) e = hipMemcpyAsync(sl.h_res, sl.d_res, answers, hipMemcpyDeviceToHost, s->hs);
+    if (e == hipSuccess && r.any_host) e = hipMemcpyAsync(sl.h_st, sl.d_st, 4 * answers, hipMemcpyDeviceToHost, s->hs);
     if (e == hipSuccess) e = hipEventRecord(sl.done, s->hs);
     if (e != hipSuccess) return fail(s, MBLS_ERR_DEVICE, "scatter: %s", hipGetErrorString(e));
     std::lock_guard<std::mutex> g(s->mu);
-    s->stats.gathered_bytes += gathered;
+    s->stats.gathered_bytes += r.gathered;
     return MBLS_OK;
 }
 
-// the same for a verify_multiple stream: whole calls only (stream_take_whole, the rule mbls_stream_cut_vm states as data); a call that does not fit closes the round
-void absorb_vm(mbls_stream* s, slot& sl) {
-    while (s->cursor <= s->last_ticket && !sl.full) {
-        const std::shared_ptr<call_rec>& c = s->calls[s->cursor - s->base];
-        if (sl.vfill.calls && sl.first_ticket <= s->flush_upto && c->ticket > s->flush_upto) break;
-        const uint64_t before = sl.vfill.sets;
-        if (!stream_take_whole(s->o, sl.vfill, c->shape.n)) { sl.full = true; break; }
-        if (sl.pieces.empty()) sl.first_ticket = c->ticket;
-        sl.pieces.push_back(piece_rec{c, 0, c->shape.n, before, sl.vfill.calls - 1});
-        sl.fill.items = sl.vfill.cost;
-        sl.done_through = c->ticket; s->cursor++;
-        if (stream_vm_full(s->o, sl.vfill)) sl.full = true;
-    }
-}
-
-// cut queued calls into the open slot (lock held): the same stream_take mbls_stream_cut runs, a flush boundary after call flush_upto
+// cut queued calls into the open slot (lock held): the step mbls_stream_cut and mbls_stream_cut_vm run (stream_step), a flush boundary after call flush_upto
 void absorb(mbls_stream* s, slot& sl) {
-    if (s->vm) { absorb_vm(s, sl); return; }
     while (s->cursor <= s->last_ticket && !sl.full) {
         const std::shared_ptr<call_rec>& c = s->calls[s->cursor - s->base];
         if (sl.fill.items && sl.first_ticket <= s->flush_upto && c->ticket > s->flush_upto) break;
-        const uint64_t before = sl.fill.items;
-        const uint64_t t = stream_take(s->o, sl.fill, c->shape, s->item_off);
-        if (t) {
+        const mbls_stream_step st = stream_step(s->k.o, stream_kind_whole(s->k.kind), sl.fill, c->shape, s->item_off);
+        if (st.items) {
             if (sl.pieces.empty()) sl.first_ticket = c->ticket;
             if (s->item_off) c->split = true;
-            sl.pieces.push_back(piece_rec{c, s->item_off, t, before});
-            s->item_off += t;
+            sl.pieces.push_back(piece_rec{c, s->item_off, st.items, st.round_first, st.batch});
+            s->item_off += st.items;
         }
         if (s->item_off == c->shape.n) { sl.done_through = c->ticket; s->cursor++; s->item_off = 0; }
-        else sl.full = true;
-        if (sl.fill.items == s->o.round_items) sl.full = true;
+        sl.full = st.full;
     }
 }
 
@@ -484,12 +339,12 @@ void launcher_main(mbls_stream* s) {
             if (s->stop) return;
             s->open = s->free_slots.front(); s->free_slots.pop_front();
             slot& o = s->slots[s->open];
-            o.pieces.clear(); o.fill = mbls_stream_fill{}; o.vfill = mbls_stream_vm_fill{}; o.full = false; o.first_ticket = 0; o.done_through = s->cut_done_through; o.rc = MBLS_OK;
+            o.pieces.clear(); o.fill = mbls_stream_fill{}; o.full = false; o.first_ticket = 0; o.done_through = s->cut_done_through; o.rc = MBLS_OK;
         }
         slot& o = s->slots[s->open];
         absorb(s, o);
         const bool flush = o.fill.items && o.first_ticket <= s->flush_upto;
-        const bool wc = s->o.policy == MBLS_STREAM_WORK_CONSERVING && s->inflight.size() < s->o.depth;
+        const bool wc = s->k.o.policy == MBLS_STREAM_WORK_CONSERVING && s->inflight.size() < s->k.o.depth;
         if (o.fill.items && (o.full || flush || wc)) {
             const int si = s->open; s->open = -1;
             s->cut_done_through = o.done_through;
@@ -497,7 +352,7 @@ void launcher_main(mbls_stream* s) {
             for (const piece_rec& p : o.pieces) if (p.first && p.c->split && p.first + p.items == p.c->shape.n) s->stats.split_calls++;
             const bool dead = s->dead;
             lk.unlock();
-            int rc = dead ? MBLS_ERR_DEVICE : s->vm ? launch_round_vm(s, o) : launch_round(s, o);
+            int rc = dead ? MBLS_ERR_DEVICE : launch_round(s, o);
             lk.lock();
             o.rc = rc;
             s->inflight.push_back(si);
@@ -507,6 +362,30 @@ void launcher_main(mbls_stream* s) {
         if (s->stop) return;
         s->cv_launch.wait(lk);
     }
+}
+
+// a completed round's answers to a host piece, from the slot's pinned result areas (lock not held)
+void answer_host_piece(const mbls_stream* s, const slot& sl, const piece_rec& p) {
+    const call_rec& c = *p.c;
+    switch (s->k.kind) {
+        case STREAM_VM: {     // the call's batch byte and word (kept behind the round's sets), then its sets'
+            const uint64_t at = sl.plan.n + p.batch;
+            c.res[0] = sl.h_res[at];
+            if (c.st) c.st[0] = sl.h_st[at];
+            if (c.set_res) memcpy(c.set_res, sl.h_res + p.round_first, p.items);
+            if (c.set_st) memcpy(c.set_st, sl.h_st + p.round_first, 4 * p.items);
+            break;
+        }
+        default:              // one byte and word per item, at the piece's place in the call
+            memcpy(c.res + p.first, sl.h_res + p.round_first, p.items);
+            if (c.st) memcpy(c.st + p.first, sl.h_st + p.round_first, 4 * p.items);
+    }
+}
+
+// the tables' counts of the calls this stream holds (the handles a kind does not have are null)
+void count_calls(mbls_stream* s, long long delta) {
+    if (s->mt) mblsi_msgtable_stream_calls(s->mt, delta);
+    if (s->cm) mblsi_committees_stream_calls(s->cm, delta);
 }
 
 void completer_main(mbls_stream* s) {
@@ -521,19 +400,7 @@ void completer_main(mbls_stream* s) {
         int rc = sl.rc;
         if (!rc) { const hipError_t e = hipEventSynchronize(sl.done); if (e != hipSuccess) rc = fail(s, MBLS_ERR_DEVICE, "round: %s", hipGetErrorString(e)); }
         if (!rc)
-            for (const piece_rec& p : sl.pieces) {
-                if (!p.c->host) continue;
-                if (s->vm) {          // the call's batch byte and word (kept behind the round's sets), then its sets'
-                    const uint64_t at = sl.vfill.sets + p.batch;
-                    p.c->res[0] = sl.h_res[at];
-                    if (p.c->st) p.c->st[0] = sl.h_st[at];
-                    if (p.c->set_res) memcpy(p.c->set_res, sl.h_res + p.round_first, p.items);
-                    if (p.c->set_st) memcpy(p.c->set_st, sl.h_st + p.round_first, 4 * p.items);
-                    continue;
-                }
-                memcpy(p.c->res + p.first, sl.h_res + p.round_first, p.items);
-                if (p.c->st) memcpy(p.c->st + p.first, sl.h_st + p.round_first, 4 * p.items);
-            }
+            for (const piece_rec& p : sl.pieces) if (p.c->host) answer_host_piece(s, sl, p);
         lk.lock();
         if (rc) {
             s->dead = true;
@@ -543,8 +410,7 @@ void completer_main(mbls_stream* s) {
         sl.pieces.clear();
         while (!s->calls.empty() && s->calls.front()->ticket <= s->completed_through && s->calls.front()->ticket < s->cursor) {
             if (s->calls.front()->ev) s->ev_pool.push_back(s->calls.front()->ev);
-            if (s->mt) mblsi_msgtable_stream_calls(s->mt, -1);
-            if (s->cm) mblsi_committees_stream_calls(s->cm, -1);
+            count_calls(s, -1);
             s->calls.pop_front(); s->base++;
         }
         s->inflight.pop_front(); s->free_slots.push_back(si);
@@ -552,13 +418,54 @@ void completer_main(mbls_stream* s) {
     }
 }
 
+// Every buffer of a slot of this stream, in the order they are allocated: where its pointer is kept, device or pinned memory, bytes. Everything is allocated at
+// creation (alloc_slot) and freed from the same list (free_stream). R items of 96 signature bytes; a keys round holds round_msg_bytes of messages and
+// round_keys keys of `unit` bytes; a committee or verify_multiple round holds R indices, ids and fields of bits_stride bytes, and the fields of host pieces pass
+// through pinned memory; a verify_multiple round also holds R scalars, and ONE pinned block mirrors its host calls' other four arrays (alloc_slot carves it).
+struct slot_buf { const char* name; void** p; bool pinned; uint64_t bytes; };
+constexpr size_t SLOT_BUFS = 16;
+size_t slot_buffers(const stream_consts& k, uint64_t meta_bytes, slot& sl, slot_buf* b) {
+    const uint64_t R = k.o.round_items, fields = std::max<uint64_t>((uint64_t)k.bits_stride * R, 16);
+    size_t n = 0;
+    auto dev = [&](const char* name, void* p, uint64_t bytes) { b[n++] = slot_buf{name, (void**)p, false, bytes}; };
+    auto pin = [&](const char* name, void* p, uint64_t bytes) { b[n++] = slot_buf{name, (void**)p, true, bytes}; };
+    dev("signatures", &sl.dev[RA_SIGS], 96 * R);
+    switch (k.kind) {
+        case STREAM_KEYS:
+            dev("messages", &sl.dev[RA_MSGS], std::max<uint64_t>(k.o.round_msg_bytes, 16));
+            dev("keys", &sl.dev[RA_KEYS], std::max<uint64_t>(k.unit * k.o.round_keys, 16));
+            break;
+        case STREAM_COMMITTEE:
+            dev("message indices", &sl.dev[RA_MSGS], std::max<uint64_t>(k.o.round_msg_bytes, 16));
+            dev("fields", &sl.dev[RA_KEYS], fields); dev("committee ids", &sl.dev[RA_CID], 4 * R); pin("host fields", &sl.pin[RA_KEYS], fields);
+            break;
+        default:    // STREAM_VM; the mirror: signatures | scalars | set words | message indices, each at its alignment
+            dev("message indices", &sl.dev[RA_MSGS], std::max<uint64_t>(4 * R, 16));
+            dev("scalars", &sl.dev[RA_RANDS], 8 * R); pin("host mirror", &sl.pin[RA_SIGS], (96 + 8 + 4 + 4) * R);
+            dev("fields", &sl.dev[RA_KEYS], fields); dev("set words", &sl.dev[RA_CID], 4 * R); pin("host fields", &sl.pin[RA_KEYS], fields);
+    }
+    dev("results", &sl.d_res, R); dev("status", &sl.d_st, 4 * R); dev("meta", &sl.d_meta, meta_bytes);
+    pin("host meta", &sl.h_meta, meta_bytes); pin("host results", &sl.h_res, R); pin("host status", &sl.h_st, 4 * R);
+    return n;
+}
+
+hipError_t alloc_slot(const mbls_stream* s, slot& sl) {
+    slot_buf b[SLOT_BUFS]; const size_t nb = slot_buffers(s->k, s->meta_bytes, sl, b);
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; i < nb && e == hipSuccess; i++) e = b[i].pinned ? hipHostMalloc(b[i].p, b[i].bytes, hipHostMallocDefault) : hipMalloc(b[i].p, b[i].bytes);
+    if (e == hipSuccess && s->k.kind == STREAM_VM) {
+        const uint64_t R = s->k.o.round_items;
+        sl.pin[RA_RANDS] = sl.pin[RA_SIGS] + 96 * R; sl.pin[RA_CID] = sl.pin[RA_RANDS] + 8 * R; sl.pin[RA_MSGS] = sl.pin[RA_CID] + 4 * R;
+    }
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.gev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync);
+    return e;
+}
+
 void free_stream(mbls_stream* s) {
     for (slot& sl : s->slots) {
-        for (uint8_t* p : {sl.d_sigs, sl.d_msgs, sl.d_keys, sl.d_res, sl.d_meta}) if (p) (void)hipFree(p);
-        if (sl.d_st) (void)hipFree(sl.d_st);
-        if (sl.d_cid) (void)hipFree(sl.d_cid);
-        if (sl.d_rands) (void)hipFree(sl.d_rands);
-        for (void* p : {(void*)sl.h_meta, (void*)sl.h_res, (void*)sl.h_st, (void*)sl.h_bits, (void*)sl.h_sigs}) if (p) (void)hipHostFree(p);
+        slot_buf b[SLOT_BUFS]; const size_t nb = slot_buffers(s->k, s->meta_bytes, sl, b);
+        for (size_t i = 0; i < nb; i++) if (*b[i].p) (void)(b[i].pinned ? hipHostFree(*b[i].p) : hipFree(*b[i].p));
         if (sl.gev) (void)hipEventDestroy(sl.gev);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
@@ -566,7 +473,7 @@ void free_stream(mbls_stream* s) {
     for (auto& c : s->calls) if (c->ev) (void)hipEventDestroy(c->ev);
     if (s->hs) (void)hipStreamDestroy(s->hs);
     if (s->gs) (void)hipStreamDestroy(s->gs);
-    if (s->cm_bound) mblsi_committees_stream_unbind(s->cm, s->bits_stride);
+    if (s->cm) mblsi_committees_stream_unbind(s->cm, s->k.bits_stride);      // (set once the table was bound to the stride)
     delete s;
 }
 
@@ -594,37 +501,63 @@ int enqueue(mbls_stream* s, const std::shared_ptr<call_rec>& c, void* stream, ui
     }
     c->ticket = ++s->last_ticket;
     s->calls.push_back(c);
-    if (s->mt) mblsi_msgtable_stream_calls(s->mt, 1);
-    if (s->cm) mblsi_committees_stream_calls(s->cm, 1);
+    count_calls(s, 1);
     s->stats.calls++; s->stats.items += n;
     *ticket = c->ticket;
     s->cv_launch.notify_one();
     return MBLS_OK;
 }
 
-int submit(mbls_stream* s, bool msgidx, bool host, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, const uint8_t* pks,
-           const uint32_t* idx, const uint32_t* poff, uint64_t n, uint32_t k, uint8_t* res, uint64_t* bm, uint32_t* st, void* stream, uint64_t* ticket) {
+// the four families of submit entries, and what each is told on a stream that does not take its calls (nullptr: this stream does)
+enum submit_via { VIA_BYTES, VIA_MSGIDX, VIA_COMMITTEE, VIA_VM };
+const char* wrong_kind(const mbls_stream* s, submit_via via) {
+    const int kind = s->k.kind;
+    switch (via) {
+        case VIA_BYTES:
+        case VIA_MSGIDX:
+            if (kind == STREAM_VM) return "a verify_multiple stream takes whole batches of sets (mbls_stream_submit_vm[_device])";
+            if (kind == STREAM_COMMITTEE) return "a committee stream takes committee ids and bitfields (mbls_stream_submit_committee[_device])";
+            if ((via == VIA_MSGIDX) == (s->mt != nullptr)) return nullptr;
+            return s->mt ? "a message-table stream takes message indices (mbls_stream_submit_msgidx[_device])"
+                         : "this stream takes messages, not message-table indices (mbls_stream_submit[_device])";
+        case VIA_COMMITTEE:
+            if (kind == STREAM_COMMITTEE) return nullptr;
+            if (kind == STREAM_VM) return "a verify_multiple stream takes whole batches of sets (mbls_stream_submit_vm[_device])";
+            return s->mt ? "this is not a committee stream: a message-table stream takes mbls_stream_submit_msgidx[_device]"
+                         : "this is not a committee stream: it takes messages and keys (mbls_stream_submit[_device])";
+        default:
+            if (kind == STREAM_VM) return nullptr;
+            if (kind == STREAM_COMMITTEE) return "this is not a verify_multiple stream: a committee stream takes mbls_stream_submit_committee[_device]";
+            return s->mt ? "this is not a verify_multiple stream: a message-table stream takes mbls_stream_submit_msgidx[_device]"
+                         : "this is not a verify_multiple stream: it takes messages and keys (mbls_stream_submit[_device])";
+    }
+}
+// what every submit checks first; 0: go on
+int refuse_early(mbls_stream* s, submit_via via, const uint64_t* ticket) {
     if (!s) return MBLS_ERR_ARGUMENT;
     if (!ticket) return fail(s, MBLS_ERR_ARGUMENT, "null ticket pointer");
-    if (s->vm) return fail(s, MBLS_ERR_ARGUMENT, "a verify_multiple stream takes whole batches of sets (mbls_stream_submit_vm[_device])");
-    if (s->cm) return fail(s, MBLS_ERR_ARGUMENT, "a committee stream takes committee ids and bitfields (mbls_stream_submit_committee[_device])");
-    if (msgidx != (s->mt != nullptr))
-        return fail(s, MBLS_ERR_ARGUMENT, s->mt ? "a message-table stream takes message indices (mbls_stream_submit_msgidx[_device])"
-                                                : "this stream takes messages, not message-table indices (mbls_stream_submit[_device])");
+    const char* why = wrong_kind(s, via);
+    return why ? fail(s, MBLS_ERR_ARGUMENT, "%s", why) : 0;
+}
+
+int submit(mbls_stream* s, bool msgidx, bool host, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len, const uint64_t* moff, const uint8_t* pks,
+           const uint32_t* idx, const uint32_t* poff, uint64_t n, uint32_t k, uint8_t* res, uint64_t* bm, uint32_t* st, void* stream, uint64_t* ticket) {
+    if (const int rc = refuse_early(s, msgidx ? VIA_MSGIDX : VIA_BYTES, ticket)) return rc;
     if (n == 0) return fail(s, MBLS_ERR_ARGUMENT, "a call holds at least one item");
     if (!sigs || !res) return fail(s, MBLS_ERR_ARGUMENT, "null buffer");
     if (s->mode == MBLS_STREAM_VERIFY && (poff || k != 1)) return fail(s, MBLS_ERR_ARGUMENT, "verify mode: one key per item (k = 1, no key offsets)");
     if (s->tab ? pks != nullptr : idx != nullptr)
         return fail(s, MBLS_ERR_ARGUMENT, s->tab ? "an index stream takes key indices, not key bytes" : "a byte-key stream takes key bytes, not key indices");
+    const mbls_stream_opts& o = s->k.o;
     mbls_stream_call_shape sh{n, k, msg_len, poff, moff, 0};
-    int what = 0; const uint64_t bad = stream_check_call(s->o, sh, &what);
+    int what = 0; const uint64_t bad = stream_check_call(o, sh, &what);
     if (bad) {
         const uint64_t i = bad - 1;
         if (what == 1) return fail(s, MBLS_ERR_ARGUMENT, "offset table runs backwards (or holds a message of 2^32 bytes or more) at item %llu", (unsigned long long)i);
         if (what == 2) return fail(s, MBLS_ERR_ARGUMENT, "item %llu has %llu keys; a round holds %llu (mbls_stream_opts.round_keys)", (unsigned long long)i,
-                                   (unsigned long long)stream_item_keys(sh, i), (unsigned long long)s->o.round_keys);
+                                   (unsigned long long)stream_item_keys(sh, i), (unsigned long long)o.round_keys);
         return fail(s, MBLS_ERR_ARGUMENT, "item %llu has a %llu-byte message; a round holds %llu message bytes (mbls_stream_opts.round_msg_bytes)", (unsigned long long)i,
-                    (unsigned long long)stream_item_msg(sh, i), (unsigned long long)s->o.round_msg_bytes);
+                    (unsigned long long)stream_item_msg(sh, i), (unsigned long long)o.round_msg_bytes);
     }
     const uint64_t msg_total = moff ? moff[n] - moff[0] : (uint64_t)msg_len * n;
     const uint64_t key_total = poff ? (uint64_t)(poff[n] - poff[0]) : (uint64_t)k * n;
@@ -638,20 +571,15 @@ int submit(mbls_stream* s, bool msgidx, bool host, const uint8_t* sigs, const ui
 // a committee call: the shape {n, k = 0, msg_len = 4} -- the message indices are its "message bytes", as on a message-table stream; ids and fields ride along
 int submit_cmt(mbls_stream* s, bool host, const uint8_t* sigs, const uint32_t* msg_idx, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_len, uint64_t n,
                uint8_t* res, uint64_t* bm, uint32_t* st, void* stream, uint64_t* ticket) {
-    if (!s) return MBLS_ERR_ARGUMENT;
-    if (!ticket) return fail(s, MBLS_ERR_ARGUMENT, "null ticket pointer");
-    if (s->vm) return fail(s, MBLS_ERR_ARGUMENT, "a verify_multiple stream takes whole batches of sets (mbls_stream_submit_vm[_device])");
-    if (!s->cm)
-        return fail(s, MBLS_ERR_ARGUMENT, s->mt ? "this is not a committee stream: a message-table stream takes mbls_stream_submit_msgidx[_device]"
-                                                : "this is not a committee stream: it takes messages and keys (mbls_stream_submit[_device])");
+    if (const int rc = refuse_early(s, VIA_COMMITTEE, ticket)) return rc;
     if (n == 0) return fail(s, MBLS_ERR_ARGUMENT, "a call holds at least one item");
     if (!sigs || !res || !msg_idx || !cmt_idx || !bits) return fail(s, MBLS_ERR_ARGUMENT, "null buffer");
-    if (bits_len == 0 || bits_len > s->bits_stride)
-        return fail(s, MBLS_ERR_ARGUMENT, "bits_len is %u; a field holds 1 to %u bytes (the stream's bits_stride)", bits_len, s->bits_stride);
+    if (bits_len == 0 || bits_len > s->k.bits_stride)
+        return fail(s, MBLS_ERR_ARGUMENT, "bits_len is %u; a field holds 1 to %u bytes (the stream's bits_stride)", bits_len, s->k.bits_stride);
     mbls_stream_call_shape sh{n, 0, 4, nullptr, nullptr, 0};
     int what = 0;
-    if (stream_check_call(s->o, sh, &what))
-        return fail(s, MBLS_ERR_ARGUMENT, "an item takes 4 message bytes; a round holds %llu (mbls_stream_opts.round_msg_bytes)", (unsigned long long)s->o.round_msg_bytes);
+    if (stream_check_call(s->k.o, sh, &what))
+        return fail(s, MBLS_ERR_ARGUMENT, "an item takes 4 message bytes; a round holds %llu (mbls_stream_opts.round_msg_bytes)", (unsigned long long)s->k.o.round_msg_bytes);
     auto c = std::make_shared<call_rec>();
     c->host = host; c->shape = sh; c->sigs = sigs; c->msgs = (const uint8_t*)msg_idx; c->keys = (const uint8_t*)cmt_idx; c->bits = bits; c->bits_len = bits_len;
     c->res = res; c->bm = bm; c->st = st;
@@ -661,20 +589,15 @@ int submit_cmt(mbls_stream* s, bool host, const uint8_t* sigs, const uint32_t* m
 // a verify_multiple call: one batch of n sets, never split (shape.n = its sets; the cutting reads nothing else of the shape)
 int submit_vm(mbls_stream* s, bool host, const uint8_t* sigs, const uint32_t* cmt_idx, const uint8_t* bits, uint32_t bits_len, const uint32_t* msg_idx, const uint64_t* rands,
               uint64_t n, uint8_t* res, uint32_t* st, uint8_t* set_res, uint32_t* set_st, void* stream, uint64_t* ticket) {
-    if (!s) return MBLS_ERR_ARGUMENT;
-    if (!ticket) return fail(s, MBLS_ERR_ARGUMENT, "null ticket pointer");
-    if (!s->vm)
-        return fail(s, MBLS_ERR_ARGUMENT, s->cm   ? "this is not a verify_multiple stream: a committee stream takes mbls_stream_submit_committee[_device]"
-                                          : s->mt ? "this is not a verify_multiple stream: a message-table stream takes mbls_stream_submit_msgidx[_device]"
-                                                  : "this is not a verify_multiple stream: it takes messages and keys (mbls_stream_submit[_device])");
+    if (const int rc = refuse_early(s, VIA_VM, ticket)) return rc;
     if (n == 0) return fail(s, MBLS_ERR_ARGUMENT, "a call holds at least one set");
     if (!rands) return fail(s, MBLS_ERR_ARGUMENT, "verify_multiple without blinding scalars is forgeable: rands must not be NULL");
     if (!sigs || !res || !msg_idx || !cmt_idx) return fail(s, MBLS_ERR_ARGUMENT, "null buffer");
-    if (bits_len > s->bits_stride) return fail(s, MBLS_ERR_ARGUMENT, "bits_len is %u; a field holds 0 to %u bytes (the stream's bits_stride)", bits_len, s->bits_stride);
+    if (bits_len > s->k.bits_stride) return fail(s, MBLS_ERR_ARGUMENT, "bits_len is %u; a field holds 0 to %u bytes (the stream's bits_stride)", bits_len, s->k.bits_stride);
     if (bits_len && !bits) return fail(s, MBLS_ERR_ARGUMENT, "null bitfields with bits_len = %u (only bits_len = 0 allows it)", bits_len);
-    if (!stream_vm_fits(s->o, n))
+    if (!stream_vm_fits(s->k.o, n))
         return fail(s, MBLS_ERR_ARGUMENT, "a call of %llu sets costs %llu of a round; a round holds %llu (mbls_stream_opts.round_items): at most %llu sets per call",
-                    (unsigned long long)n, (unsigned long long)stream_vm_cost(n), (unsigned long long)s->o.round_items, (unsigned long long)(s->o.round_items - 1));
+                    (unsigned long long)n, (unsigned long long)stream_vm_cost(n), (unsigned long long)s->k.o.round_items, (unsigned long long)(s->k.o.round_items - 1));
     auto c = std::make_shared<call_rec>();
     c->host = host; c->shape = mbls_stream_call_shape{n, 0, 4, nullptr, nullptr, 0};
     c->sigs = sigs; c->msgs = (const uint8_t*)msg_idx; c->keys = (const uint8_t*)cmt_idx; c->bits = bits; c->bits_len = bits_len; c->rands = rands;
@@ -691,24 +614,26 @@ int submit_vm(mbls_stream* s, bool host, const uint8_t* sigs, const uint32_t* cm
     return enqueue(s, c, stream, ticket);
 }
 
+// the cut of a queue as data: every piece the walk (stream_walk) makes of calls shape(0 .. n_calls), under either rule
+template <typename Shape>
+int cut_queue(const mbls_stream_opts& o, int whole, uint64_t n_calls, Shape shape, mbls_stream_piece* out, uint64_t max_pieces, uint64_t* n_pieces) {
+    uint64_t np = 0;
+    stream_walk(o, whole, n_calls, shape, [&](uint64_t j, uint64_t first, const mbls_stream_step& st, uint64_t round, const mbls_stream_fill&) {
+        if (np < max_pieces) out[np] = mbls_stream_piece{j, first, st.items, round, st.round_first};
+        np++;
+    });
+    *n_pieces = np;
+    return np <= max_pieces || !out ? MBLS_OK : MBLS_ERR_ARGUMENT;
+}
+
 }  // namespace
 
 extern "C" int mbls_stream_cut_vm(const mbls_stream_opts* o, const uint64_t* call_sets, const uint32_t* flush_after, uint64_t n_calls, mbls_stream_piece* out,
                                   uint64_t max_pieces, uint64_t* n_pieces) {
     if (!o || !call_sets || !n_calls || !n_pieces || !o->round_items || (!out && max_pieces)) return MBLS_ERR_ARGUMENT;
     for (uint64_t j = 0; j < n_calls; j++) if (!stream_vm_fits(*o, call_sets[j])) return MBLS_ERR_ARGUMENT;
-    mbls_stream_vm_fill f{}; uint64_t round = 0;
-    for (uint64_t j = 0; j < n_calls; j++) {
-        uint64_t before = f.sets;
-        if (!stream_take_whole(*o, f, call_sets[j])) {            // the call closes the open round and is the first of the next
-            round++; f = mbls_stream_vm_fill{}; before = 0;
-            (void)stream_take_whole(*o, f, call_sets[j]);
-        }
-        if (j < max_pieces) out[j] = mbls_stream_piece{j, 0, call_sets[j], round, before};
-        if ((flush_after && flush_after[j]) || stream_vm_full(*o, f)) { round++; f = mbls_stream_vm_fill{}; }
-    }
-    *n_pieces = n_calls;
-    return n_calls <= max_pieces || !out ? MBLS_OK : MBLS_ERR_ARGUMENT;
+    auto shape = [&](uint64_t j) { return mbls_stream_call_shape{call_sets[j], 0, 4, nullptr, nullptr, flush_after ? flush_after[j] : 0u}; };
+    return cut_queue(*o, 1, n_calls, shape, out, max_pieces, n_pieces);
 }
 
 extern "C" int mbls_stream_cut(const mbls_stream_opts* o, const mbls_stream_call_shape* calls, uint64_t n_calls, mbls_stream_piece* out, uint64_t max_pieces,
@@ -717,22 +642,58 @@ extern "C" int mbls_stream_cut(const mbls_stream_opts* o, const mbls_stream_call
     for (uint64_t j = 0; j < n_calls; j++) {
         int what; if (!calls[j].n || stream_check_call(*o, calls[j], &what)) return MBLS_ERR_ARGUMENT;
     }
-    mbls_stream_fill f{}; uint64_t round = 0, np = 0;
-    for (uint64_t j = 0; j < n_calls; j++) {
-        uint64_t first = 0;
-        while (first < calls[j].n) {
-            const uint64_t before = f.items, t = stream_take(*o, f, calls[j], first);
-            if (t) { if (np < max_pieces) out[np] = mbls_stream_piece{j, first, t, round, before}; np++; first += t; }
-            if (first < calls[j].n || f.items == o->round_items) { round++; f = mbls_stream_fill{}; }
-        }
-        if (calls[j].flush_after && f.items) { round++; f = mbls_stream_fill{}; }
-    }
-    *n_pieces = np;
-    return np <= max_pieces || !out ? MBLS_OK : MBLS_ERR_ARGUMENT;
+    return cut_queue(*o, 0, n_calls, [&](uint64_t j) { return calls[j]; }, out, max_pieces, n_pieces);
 }
 
-static int stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, mbls_msgtable* mt, mbls_committees* cm, uint32_t bits_stride,
-                         bool vm, const mbls_stream_opts* opts, mbls_stream** out) {
+// What a stream of this kind takes hold of at creation: its committee table, bound to the stride (checked against this context, and from here on its appends
+// against the stride; s->cm is set once bound, free_stream releases it), and in the context every round size's workspace up front, so that no round grows it.
+static int reserve_for_kind(mbls_stream* s, const mbls_limits& L, mbls_committees* cm, bool compressed_keys) {
+    const mbls_stream_opts& o = s->k.o;
+    uint64_t ws = 0;
+    // rounds of 1 .. round_items items (a partial round on the wave engine may take the eight-lane key sum, n + 8 n items)
+    auto rounds_of_items = [&](bool committee) {
+        const uint32_t kmax = (uint32_t)std::min<uint64_t>(o.round_keys, 0xFFFFFFFFull);
+        for (uint64_t n = 1; n <= o.round_items; n++) {
+            ws = std::max(ws, mbls_plan_workspace_items(&L, n, kmax, 1));
+            if (kmax >= 32) ws = std::max(ws, mbls_plan_workspace_items(&L, n, 32, 1));
+            if (committee) ws = std::max(ws, mbls_plan_workspace_items(&L, n, 0, 0));
+        }
+    };
+    auto bind = [&]() { const int rc = mblsi_committees_stream_bind(s->ctx, cm, s->k.bits_stride); if (!rc) s->cm = cm; return rc; };
+    // the index lists k_cmt_expand writes for a full round of the largest committees the stride admits
+    auto committee_items = [&]() { return mbls_ctx_reserve_committee_items(s->ctx, o.round_items, (uint32_t)std::min<uint64_t>(8ull * s->k.bits_stride, MBLS_COMMITTEE_MAX_MEMBERS)); };
+    int rc;
+    switch (s->k.kind) {
+        case STREAM_KEYS:
+            rounds_of_items(false);
+            rc = mbls_ctx_reserve(s->ctx, ws);                    // (leaves the context's device current on this thread)
+            if (!rc && compressed_keys) rc = mbls_ctx_reserve_keys(s->ctx, o.round_keys);
+            return rc;
+        case STREAM_COMMITTEE:
+            if ((rc = bind())) return rc;
+            rounds_of_items(true);
+            rc = mbls_ctx_reserve(s->ctx, ws);
+            return rc ? rc : committee_items();
+        default:    // STREAM_VM
+            if ((rc = bind())) return rc;
+            // a verify_multiple round holds B batches of n sets in all with n + B <= round_items and B <= n. What the batches entry reserves
+            // (mbls_plan_verify_multiple_batches_committee) does not decrease in n, in B or in the bound on the groups, and the bound is at most n: so the largest of
+            // every (n, B) a round can hold lies on n = round_items - B, with no promise on the groups and a table that caps nothing, on either route, with locate
+            for (uint64_t B = 1; 2 * B <= o.round_items; B++)
+                for (int route = 1; route <= 2; route++) {
+                    mbls_vm_batches_committee_plan vp;
+                    if (!mbls_plan_verify_multiple_batches_committee(&L, o.round_items - B, B, 0, 0xFFFFFFFFull, 0, route, 1, &vp)) ws = std::max(ws, vp.workspace_items);
+                }
+            rc = mbls_ctx_reserve(s->ctx, ws);
+            if (!rc) rc = committee_items();
+            // the batches entry's own grow-only staging: the set map of a ragged batch table and the group arrays, for the most sets and batches a round holds
+            if (!rc) rc = mblsi_vbg_reserve_staging(s->ctx, o.round_items - 1, o.round_items / 2);
+            return rc;
+    }
+}
+
+static int stream_create(mbls_ctx* ctx, int kind, int mode, int pk_format, const mbls_keytable* t, mbls_msgtable* mt, mbls_committees* cm, uint32_t bits_stride,
+                         const mbls_stream_opts* opts, mbls_stream** out) {
     if (!ctx || !out) return MBLS_ERR_ARGUMENT;
     *out = nullptr;
     if (mode != MBLS_STREAM_FAST_AGGREGATE_VERIFY && mode != MBLS_STREAM_VERIFY) return MBLS_ERR_ARGUMENT;
@@ -751,65 +712,19 @@ static int stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keyt
     if (!o.round_msg_bytes) o.round_msg_bytes = (mt ? 4 : 64) * o.round_items;
     if (!o.depth) o.depth = 2;
     if (o.round_items > (1ull << 31) || o.round_keys > 0xFFFFFFFFull || o.depth > 64) return MBLS_ERR_ARGUMENT;    // key offsets of a round are 32-bit
-    if (vm && o.round_items < 2) return MBLS_ERR_ARGUMENT;                  // the smallest call, one set and its signature pair, costs 2
+    if (stream_kind_whole(kind) && o.round_items < 2) return MBLS_ERR_ARGUMENT;   // the smallest whole call, one set and its signature pair, costs 2
     mbls_stream* s = new (std::nothrow) mbls_stream();
     if (!s) return MBLS_ERR_DEVICE;
-    s->ctx = ctx; s->tab = t; s->mt = mt; s->mode = mode; s->fmt = t ? MBLS_PK_UNCOMPRESSED : pk_format; s->o = o;
-    s->vm = vm;
-    s->unit = cm ? 0 : t ? 4 : (pk_format == MBLS_PK_COMPRESSED ? 48 : 96);
-    if (cm) {            // the table against this context and stride, and from here on its appends against the stride (released by free_stream)
-        rc = mblsi_committees_stream_bind(ctx, cm, bits_stride);
-        if (rc) { delete s; return rc; }
-        s->cm = cm; s->bits_stride = bits_stride; s->cm_bound = true;
-    }
-    // every round size's workspace up front (a partial round on the wave engine may take the eight-lane key sum, n + 8 n items): no round grows it
-    uint64_t ws = 0;
-    const uint32_t kmax = (uint32_t)std::min<uint64_t>(o.round_keys, 0xFFFFFFFFull);
-    for (uint64_t n = 1; n <= o.round_items && !vm; n++) {
-        ws = std::max(ws, mbls_plan_workspace_items(&L, n, kmax, 1));
-        if (kmax >= 32) ws = std::max(ws, mbls_plan_workspace_items(&L, n, 32, 1));
-        if (cm) ws = std::max(ws, mbls_plan_workspace_items(&L, n, 0, 0));
-    }
-    // a verify_multiple round holds B batches of n sets in all with n + B <= round_items and B <= n. What the batches entry reserves
-    // (mbls_plan_verify_multiple_batches_committee) does not decrease in n, in B or in the bound on the groups, and the bound is at most n: so the largest of every
-    // (n, B) a round can hold lies on n = round_items - B, with no promise on the groups and a table that caps nothing, on either route, with locate
-    for (uint64_t B = 1; vm && 2 * B <= o.round_items; B++)
-        for (int route = 1; route <= 2; route++) {
-            mbls_vm_batches_committee_plan vp;
-            if (!mbls_plan_verify_multiple_batches_committee(&L, o.round_items - B, B, 0, 0xFFFFFFFFull, 0, route, 1, &vp)) ws = std::max(ws, vp.workspace_items);
-        }
-    rc = mbls_ctx_reserve(ctx, ws);                       // (leaves the context's device current on this thread)
-    if (!rc && !t && !cm && pk_format == MBLS_PK_COMPRESSED) rc = mbls_ctx_reserve_keys(ctx, o.round_keys);
-    // the index lists k_cmt_expand writes for a full round of the largest committees the stride admits
-    if (!rc && cm) rc = mbls_ctx_reserve_committee_items(ctx, o.round_items, (uint32_t)std::min<uint64_t>(8ull * bits_stride, MBLS_COMMITTEE_MAX_MEMBERS));
-    // the batches entry's own grow-only staging: the set map of a ragged batch table and the group arrays, for the most sets and batches a round holds
-    if (!rc && vm) rc = mblsi_vbg_reserve_staging(ctx, o.round_items - 1, o.round_items / 2);
+    s->ctx = ctx; s->tab = t; s->mt = mt; s->mode = mode; s->fmt = t ? MBLS_PK_UNCOMPRESSED : pk_format;
+    s->k = stream_consts{kind, mode == MBLS_STREAM_VERIFY, kind != STREAM_KEYS ? 0u : t ? 4u : (pk_format == MBLS_PK_COMPRESSED ? 48u : 96u), bits_stride, o};
+    rc = reserve_for_kind(s, L, cm, !t && pk_format == MBLS_PK_COMPRESSED);
     if (rc) { free_stream(s); return rc; }
     hipError_t e = hipGetDevice(&s->dev);
-    s->meta_bytes = meta_capacity(o, s->unit, cm != nullptr, vm);
+    s->meta_bytes = meta_capacity(s->k);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->hs, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->gs, hipStreamNonBlocking);
     s->slots.resize(o.depth + 1);
-    for (slot& sl : s->slots) {
-        if (e == hipSuccess) e = hipMalloc(&sl.d_sigs, 96 * o.round_items);
-        if (e == hipSuccess) e = hipMalloc(&sl.d_msgs, std::max<uint64_t>(vm ? 4 * o.round_items : o.round_msg_bytes, 16));
-        if (e == hipSuccess && vm) e = hipMalloc(&sl.d_rands, 8 * o.round_items);
-        if (e == hipSuccess && vm) {      // signatures | scalars | set words | message indices, each at its alignment
-            e = hipHostMalloc((void**)&sl.h_sigs, (96 + 8 + 4 + 4) * o.round_items, hipHostMallocDefault);
-            if (e == hipSuccess) { sl.h_rands = (uint64_t*)(sl.h_sigs + 96 * o.round_items); sl.h_cid = (uint32_t*)(sl.h_rands + o.round_items); sl.h_midx = sl.h_cid + o.round_items; }
-        }
-        if (e == hipSuccess) e = hipMalloc(&sl.d_keys, std::max<uint64_t>(cm ? (uint64_t)bits_stride * o.round_items : s->unit * o.round_keys, 16));
-        if (e == hipSuccess && cm) e = hipMalloc(&sl.d_cid, 4 * o.round_items);
-        if (e == hipSuccess && cm) e = hipHostMalloc((void**)&sl.h_bits, std::max<uint64_t>((uint64_t)bits_stride * o.round_items, 16), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc(&sl.d_res, o.round_items);
-        if (e == hipSuccess) e = hipMalloc(&sl.d_st, 4 * o.round_items);
-        if (e == hipSuccess) e = hipMalloc(&sl.d_meta, s->meta_bytes);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&sl.h_meta, s->meta_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&sl.h_res, o.round_items, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&sl.h_st, 4 * o.round_items, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.gev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync);
-    }
+    for (slot& sl : s->slots) if (e == hipSuccess) e = alloc_slot(s, sl);
     if (e != hipSuccess) { free_stream(s); return MBLS_ERR_DEVICE; }
     for (int i = 0; i < (int)s->slots.size(); i++) s->free_slots.push_back(i);
     try {
@@ -826,23 +741,23 @@ static int stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keyt
 }
 
 extern "C" int mbls_stream_create(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, const mbls_stream_opts* opts, mbls_stream** out) {
-    return stream_create(ctx, mode, pk_format, t, nullptr, nullptr, 0, false, opts, out);
+    return stream_create(ctx, STREAM_KEYS, mode, pk_format, t, nullptr, nullptr, 0, opts, out);
 }
 extern "C" int mbls_stream_create_msgtable(mbls_ctx* ctx, int mode, int pk_format, const mbls_keytable* t, mbls_msgtable* mt, const mbls_stream_opts* opts, mbls_stream** out) {
     if (!mt) return MBLS_ERR_ARGUMENT;
-    return stream_create(ctx, mode, pk_format, t, mt, nullptr, 0, false, opts, out);
+    return stream_create(ctx, STREAM_KEYS, mode, pk_format, t, mt, nullptr, 0, opts, out);
 }
 // a committee stream: fast_aggregate_verify over the committee table (and through it its key table) and the message table
 extern "C" int mbls_stream_create_committee(mbls_ctx* ctx, mbls_committees* committees, mbls_msgtable* mt, uint32_t bits_stride, const mbls_stream_opts* opts,
                                             mbls_stream** out) {
     if (!committees || !mt) return MBLS_ERR_ARGUMENT;
-    return stream_create(ctx, MBLS_STREAM_FAST_AGGREGATE_VERIFY, MBLS_PK_UNCOMPRESSED, nullptr, mt, committees, bits_stride, false, opts, out);
+    return stream_create(ctx, STREAM_COMMITTEE, MBLS_STREAM_FAST_AGGREGATE_VERIFY, MBLS_PK_UNCOMPRESSED, nullptr, mt, committees, bits_stride, opts, out);
 }
 // a verify_multiple stream over the same two tables: a call is a batch, a round one call of mbls_verify_multiple_batches_committee_msgtable_locate_device
 extern "C" int mbls_stream_create_vm_committee(mbls_ctx* ctx, mbls_committees* committees, mbls_msgtable* mt, uint32_t bits_stride, const mbls_stream_opts* opts,
                                                mbls_stream** out) {
     if (!committees || !mt) return MBLS_ERR_ARGUMENT;
-    return stream_create(ctx, MBLS_STREAM_FAST_AGGREGATE_VERIFY, MBLS_PK_UNCOMPRESSED, nullptr, mt, committees, bits_stride, true, opts, out);
+    return stream_create(ctx, STREAM_VM, MBLS_STREAM_FAST_AGGREGATE_VERIFY, MBLS_PK_UNCOMPRESSED, nullptr, mt, committees, bits_stride, opts, out);
 }
 
 extern "C" void mbls_stream_destroy(mbls_stream* s) {

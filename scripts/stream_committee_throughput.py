@@ -91,7 +91,11 @@ out = {"form": "device-resident inputs; %d committees of %d members over a key t
        "round_items": int(ctx.limits().round_items), "shapes": {}}
 ctx.reserve(N.plan_workspace_items(NI, 0, False, ctx.limits())); ctx.reserve_committee_items(NI, M)
 opts = dict(round_items=NI, policy=N.STREAM_FULL_ROUNDS)
+ONLY = os.environ.get("SCT_ONLY", "")      # comma-separated substrings of "^<percent>_percent/calls_of_<n>$": the rows to run (default all)
+wanted = lambda percent, n: not ONLY or any(p in "^%d_percent/calls_of_%d$" % (percent, n) for p in ONLY.split(","))
 for percent in (99, 45):
+    if not any(wanted(percent, n) for n in SIZES):
+        continue
     cid, sk, bits, lists, off, expect_h, s = items_of(percent, 100 * M + percent)
     d_sk = torch.from_numpy(sk).to(dev)
     d_sigs = torch.empty((NI, 96), dtype=torch.uint8, device=dev)
@@ -144,7 +148,9 @@ for percent in (99, 45):
     rows = {}
     with VerifyStream(ctx, committees=ct, msg_table=mt, bits_stride=STRIDE, **opts) as vc, VerifyStream(ctx, table=table, msg_table=mt, **opts) as vi:
         for n in SIZES:
-            loop_calls = min(LOOP_CALLS, NI // n)
+            if not wanted(percent, n):
+                continue
+            loop_calls =min(LOOP_CALLS, NI // n)
             variants = [("stream_committee", lambda: stream_cmt(vc, n), NI), ("stream_indexed", lambda: stream_idx(vi, n), NI),
                         ("direct_loop", lambda: direct_calls(n, loop_calls) * (NI / (n * loop_calls)), n * loop_calls), ("direct_full_round", lambda: direct_calls(NI, 1), NI)]
             times = {name: [] for name, _, _ in variants}

@@ -79,21 +79,23 @@ def row(fn, n, *a):
             r, st = r
         ts.append(r)
     dt = float(np.median(ts))
-    d = {"calls": calls, "seconds": round(dt, 3), "items_per_s": round(calls * n / dt)}
+    d = {"calls": calls, "seconds": round(dt, 3), "seconds_all": [round(t, 5) for t in ts],"items_per_s": round(calls * n / dt)}
     if st:
         d["stats"] = st
     return d
 
 
+ONLY = os.environ.get("STREAM_ONLY", "")   # comma-separated substrings of "^<items per call>/<row name>$": the rows to run (default all)
+ROWS = [("a_direct_1ctx", run_direct, (1,)), ("b_direct_2ctx", run_direct, (2,)), ("c_stream_u96_work_conserving", run_stream, (N.STREAM_WORK_CONSERVING, False)),
+        ("c_stream_u96_full_rounds", run_stream, (N.STREAM_FULL_ROUNDS, False)), ("d_stream_indexed", run_stream, (N.STREAM_WORK_CONSERVING, True)),
+        ("e_stream_host_indexed", run_stream, (N.STREAM_WORK_CONSERVING, True, True))]
 for n in sizes:
     r = {}
-    r["a_direct_1ctx"] = row(run_direct, n, 1)
-    r["b_direct_2ctx"] = row(run_direct, n, 2)
-    r["c_stream_u96_work_conserving"] = row(run_stream, n, N.STREAM_WORK_CONSERVING, False)
-    r["c_stream_u96_full_rounds"] = row(run_stream, n, N.STREAM_FULL_ROUNDS, False)
-    r["d_stream_indexed"] = row(run_stream, n, N.STREAM_WORK_CONSERVING, True)
-    if n >= 4096:
-        r["e_stream_host_indexed"] = row(run_stream, n, N.STREAM_WORK_CONSERVING, True, True)
+    for name, fn, a in ROWS:
+        if (name != "e_stream_host_indexed" or n >= 4096) and (not ONLY or any(p in "^%d/%s$" % (n, name) for p in ONLY.split(","))):
+            r[name] = row(fn, n, *a)
+    if not r:
+        continue
     out["rows"][str(n)] = r
     print(n, json.dumps({kk: v["items_per_s"] for kk, v in r.items()}), flush=True)
 

@@ -107,7 +107,7 @@ ctx.reserve_committee_items(65536, M)
 for spb in (3, 10, 63, 192):
     for entries in (1, 10):
         name = "%d_sets/%d_entries_per_batch" % (spb, min(entries, spb))
-        if ONLY and ONLY not in name:
+        if ONLY and not any(p in "^" + name + "$" for p in ONLY.split(",")):     # (comma-separated alternatives; ^ and $ anchor a part at the ends of the name)
             continue
         B = int(math.ceil(FILL * ROUND_ITEMS / (spb + 1.0)))
         W = world(B, spb, min(entries, spb), 1000 * spb + entries)

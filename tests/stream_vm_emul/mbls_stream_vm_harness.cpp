@@ -13,24 +13,20 @@ extern "C" {
 
 int svh_fits(uint64_t round_items, uint64_t n_sets) { mbls_stream_opts o{}; o.round_items = round_items; return stream_vm_fits(o, n_sets); }
 
-// the launcher's walk over a queue of calls (absorb_vm): call j joins the open round or closes it; a launch is forced after call j where flush_after[j] != 0.
-// out_round[j], out_first[j]: the round of call j and its first set there; out_batch[j]: its batch of the round. Returns the rounds, or -1 for a call that is
-// refused at submit.
+// the launcher's walk over a queue of calls (stream_walk under the whole-call rule, the step absorb runs): call j joins the open round or closes it; a launch is
+// forced after call j where flush_after[j] != 0. out_round[j], out_first[j]: the round of call j and its first set there; out_batch[j]: its batch of the round.
+// Returns the rounds, or -1 for a call that is refused at submit.
 int64_t svh_walk(uint64_t round_items, const uint64_t* call_sets, const uint32_t* flush_after, uint64_t n_calls, uint64_t* out_round, uint64_t* out_first, uint64_t* out_batch) {
     mbls_stream_opts o{}; o.round_items = round_items;
-    mbls_stream_vm_fill f{}; uint64_t round = 0;
-    for (uint64_t j = 0; j < n_calls; j++) {
-        if (!stream_vm_fits(o, call_sets[j])) return -1;
-        uint64_t before = f.sets;
-        if (!stream_take_whole(o, f, call_sets[j])) {
-            round++; f = mbls_stream_vm_fill{}; before = 0;
-            if (!stream_take_whole(o, f, call_sets[j])) return -2;
-        }
-        out_round[j] = round; out_first[j] = before; out_batch[j] = f.calls - 1;
-        if (f.cost > round_items || f.cost != f.sets + f.calls) return -3;
-        if ((flush_after && flush_after[j]) || stream_vm_full(o, f)) { round++; f = mbls_stream_vm_fill{}; }
-    }
-    return (int64_t)(round + (f.calls ? 1 : 0));
+    for (uint64_t j = 0; j < n_calls; j++) if (!stream_vm_fits(o, call_sets[j])) return -1;
+    bool bad = false;
+    const int64_t rounds = stream_walk(o, 1, n_calls,
+        [&](uint64_t j) { return mbls_stream_call_shape{call_sets[j], 0, 4, nullptr, nullptr, flush_after ? flush_after[j] : 0u}; },
+        [&](uint64_t j, uint64_t first, const mbls_stream_step& st, uint64_t round, const mbls_stream_fill& f) {
+            out_round[j] = round; out_first[j] = st.round_first; out_batch[j] = st.batch;
+            if (first || st.items != call_sets[j] || f.cost > round_items || f.cost != f.sets + f.calls) bad = true;
+        });
+    return rounds < 0 ? -2 : bad ? -3 : rounds;
 }
 
 void svh_offsets(const uint64_t* call_sets, uint64_t n_calls, uint32_t* off) { stream_vm_offsets(call_sets, n_calls, off); }
